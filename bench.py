@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of the MI355X-native SD v1.4 sampling hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,7 +18,14 @@ ONE packed buffer [cond(77x768) | uncond(77x768)] over RCCL (backend "nccl");
 the image batch is sharded by global image index with no other collective
 (SURVEY.md 8e).  Weak scaling: images per GPU fixed.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0: `metric`, `value` (images/sec), `ms_per_step` and the
+configuration.  A plain run does only that: set up, warm up, time the K steps, print.
+`--dump-outputs DIR` writes, after the timed steps, the u8 RGB images the last timed step
+delivered to the host as DIR/images.npy (float32, [B, 512, 512, 3]; at most 64 MB, else a
+fixed seeded subset of the images) and their global image indices as DIR/image_index.npy
+(float64); at N > 1 every rank writes its own shard as images_rank<r>.npy / image_index_rank<r>.npy.
+
+`--full` adds the measurements that take runs of their own:
 `roofline` for the dominant kernel (implicit-GEMM conv on fp32 MFMA) measured
 live with HIP events on the engine's stream (its `traffic` from the committed
 rocprofv3 PMC passes, its `algorithmic_bytes_per_launch` from this run's shapes),
@@ -50,6 +57,7 @@ SPLIT_PRODUCTS = 6              # k_gemm3x.hip: bf16 MFMAs issued per fp32 16x16
 F_UNET = 0.8033e12              # FLOP per UNet forward per sample, T = 77
 F_VAE = 2.5145e12               # FLOP per decoded image
 T_CTX = 77
+DUMP_MAX_BYTES = 64 * 10 ** 6   # --dump-outputs: at most this many bytes in all (every rank's files together)
 
 
 def parse():
@@ -63,10 +71,14 @@ def parse():
     ap.add_argument("--precision", choices=["fp32", "bf16", "fp8"], default="fp32",
                     help="fp32 = BASELINE.json configs[1] (the metric's configuration, default); bf16 = configs[2..3] storage/compute")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE", help="engine option (sdmi_set_option), repeatable")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the bf16 configs[2] / configs[3]-shard measurements after the headline")
-    ap.add_argument("--no-parity", action="store_true", help="skip parity_in_run (one more un-timed sample_latent call; the PMC passes count launches per image)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the u8 images of the last timed step as DIR/images.npy (float32) and their global indices as DIR/image_index.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the un-timed extra measurements: roofline + per-class kernel times, parity_in_run, cpu_baseline and (N = 1) the secondary configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip roofline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the bf16 configs[2] / configs[3]-shard measurements after the headline")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip parity_in_run (one more un-timed sample_latent call; the PMC passes count launches per image)")
     ap.add_argument("--pmc-ddim-steps", type=int, default=0, help="PMC passes only: run this many DDIM steps instead of the configuration's (bytes PER LAUNCH do not depend "
                     "on the step count; rocprofv3's counter collection segfaults on the 100 k dispatches of configs[2]'s 50 steps)")
     ap.add_argument("--tune-file", default=str(ROOT / "stable_diffusion_burn_amd" / "tuning" / "gfx950_fp32.txt"))
@@ -74,6 +86,8 @@ def parse():
                     help="preset = BASELINE.json configs[i]: 1 fp32 B=1 S=20 (the default headline); 2 bf16 B=16 S=50; 3 bf16 B=8 per GPU S=20 "
                          "(64 images over 8 GPUs); 4 fp8 B=16 per GPU S=20 (128 images over 8 GPUs).  Sets --precision / --batch-per-gpu / --ddim-steps.")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.config is not None:
         a.precision, a.batch_per_gpu, a.ddim_steps = {1: ("fp32", 1, 20), 2: ("bf16", 16, 50), 3: ("bf16", 8, 20), 4: ("fp8", 16, 20)}[a.config]
     if a.pmc_ddim_steps > 0:
@@ -159,6 +173,19 @@ class Runner:
             self.step()
         barrier()
         return time.perf_counter() - t0
+
+    def dump_outputs(self, out_dir, max_bytes, suffix=""):
+        """The u8 images the last timed step left on the host (call after timed(): its barrier synchronised the copy) as float32, with their global
+        image indices; more than `max_bytes` of images: a fixed seeded subset of them, in index order."""
+        np = self.np
+        imgs = self.rgb_host.numpy()
+        keep = np.arange(self.B)
+        per_image = imgs[0].size * 4
+        if self.B * per_image > max_bytes:
+            keep = np.sort(np.random.default_rng(0).choice(self.B, max(1, max_bytes // per_image), replace=False))
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, f"images{suffix}.npy"), imgs[keep].astype(np.float32))
+        np.save(os.path.join(out_dir, f"image_index{suffix}.npy"), np.asarray(self.indices, dtype=np.float64)[keep])
 
     def parity_in_run(self):
         """What THIS run produced against the committed golden vectors (tests/golden/*.npz: the oracle's results for exactly these inputs) -- un-timed, after the
@@ -377,7 +404,7 @@ def main():
 
     B = args.batch_per_gpu
     ctx_dim = ModelConfig().ctx_dim
-    weights = syn.SyntheticWeights(cache=(rank == 0 and world == 1 and not args.no_cpu_baseline))
+    weights = syn.SyntheticWeights(cache=(args.full and rank == 0 and world == 1 and not args.no_cpu_baseline))
     # the flat fp32 image of the hot-path weights (untimed: numpy RNG, ~3.6 GB); every precision loads the same image.  N > 1: rank 0 generates it
     # once into /dev/shm and the other ranks map it (sharding.share_flat_array) instead of N ranks running the RNG on the same host cores
     t0 = time.perf_counter()
@@ -415,10 +442,12 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     stats = run.sd.last_call_stats()
+    if args.dump_outputs:
+        run.dump_outputs(args.dump_outputs, DUMP_MAX_BYTES // world - (1 << 20), f"_rank{rank}" if world > 1 else "")
 
     roofline, prof = (None, None)
-    parity = run.parity_in_run() if rank == 0 and not args.no_parity else None      # (after the timed region; reads the u8 image the last timed step left on the host)
-    if rank == 0 and not args.no_roofline:
+    parity = run.parity_in_run() if args.full and rank == 0 and not args.no_parity else None      # (after the timed region; reads the u8 image the last timed step left on the host)
+    if args.full and rank == 0 and not args.no_roofline:
         roofline, prof = run.roofline()
     bf16 = args.precision in ("bf16", "fp8")
     t_load = run.t_load
@@ -430,7 +459,7 @@ def main():
 
     # ---- secondary: the reduced-precision configurations BASELINE.json names, witnessed by the same run ----------
     secondary = []
-    if rank == 0 and world == 1 and not args.no_secondary and not bf16 and B == 1 and args.ddim_steps == 20:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and not bf16 and B == 1 and args.ddim_steps == 20:
         for (prec2, b2, s2, k2, extra) in (("fp32", 1, 20, 5, []), ("fp8", 16, 20, 5, []), ("bf16", 8, 20, 5, []), ("bf16", 16, 50, 5, [])):
             idx = list(range(b2))
             # the headline configuration once more with every GEMM on the fp32 matrix instruction (the split kernel off)
@@ -464,7 +493,7 @@ def main():
             r2.close()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(weights, args.ddim_steps)
 
     if rank == 0:
@@ -499,14 +528,14 @@ def main():
             "applicable_mfma_peak_note": ("dense bf16 MFMA peak" if bf16 else f"dense bf16 MFMA peak / {SPLIT_PRODUCTS} (fp32 operands as three bf16 terms, six partial products)" if split_on
                                           else "fp32 matrix instruction peak"),
             "kernels_per_image": stats["kernels"] / B, "weights_load_s": t_load, "weights_generate_s": t_gen,
-            "roofline": roofline, "cpu_baseline": cpu,
             # every engine option this run set beyond the defaults (--opt, the tile table's "tune" lines are counted, SDMI_OPTS from the environment listed by name)
             "applied_options": applied_options,
         }
-        out["parity_in_run"] = parity
-        out.update(classes)
-        if secondary:
-            out["secondary"] = secondary
+        if args.full:
+            out["roofline"], out["cpu_baseline"], out["parity_in_run"] = roofline, cpu, parity
+            out.update(classes)
+            if secondary:
+                out["secondary"] = secondary
         print(json.dumps(out), flush=True)
 
     if world > 1:

@@ -24,6 +24,16 @@ def gpu_available() -> bool:
 
 
 @pytest.fixture(scope="session")
+def bpe_vocab(tmp_path_factory):
+    """The reference's BPE merges file as far as the tokenizer reads it -- the "#version" line and the 48 894 merges that
+    SimpleTokenizer::new keeps (tokenizer.rs:93) -- unpacked once from tests/golden/bpe_simple_vocab_16e6_head.txt.bz2."""
+    import bz2
+    path = tmp_path_factory.mktemp("bpe") / "bpe_simple_vocab_16e6_head.txt"
+    path.write_bytes(bz2.decompress((ROOT / "tests" / "golden" / "bpe_simple_vocab_16e6_head.txt.bz2").read_bytes()))
+    return str(path)
+
+
+@pytest.fixture(scope="session")
 def tiny_dims():
     """Half-width model: same topology and head dims (40/80/160) as SD v1.4, 16x smaller maps."""
     from oracle.sd_oracle import Dims

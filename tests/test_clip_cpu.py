@@ -1,15 +1,13 @@
 """CLIP text encoder + tokenizer oracles vs the reference's own Python side and its Rust test vector.
 
 Fixtures come from tests/golden/gen_clip_from_reference_python.py (reference python/dump.py CLIP model and
-python/tokenizer.py, run once in the build container).  The tokenizer tests need the reference's merges
-file (not copied into this repository): $SDMI_BPE_VOCAB or /root/reference/bpe_simple_vocab_16e6.txt.
+python/tokenizer.py, run once in the build container).  The tokenizer tests read the reference's merges
+file as far as the tokenizer reads it: tests/golden/bpe_simple_vocab_16e6_head.txt.bz2 (fixture bpe_vocab, conftest.py).
 """
 import json
-import os
 from pathlib import Path
 
 import numpy as np
-import pytest
 import torch
 
 from oracle import clip_oracle as CO
@@ -17,16 +15,6 @@ from oracle.tokenizer_oracle import TokenizerOracle
 from stable_diffusion_burn_amd import synthetic as syn
 
 GOLD = Path(__file__).parent / "golden"
-
-
-def vocab_path():
-    for p in (os.environ.get("SDMI_BPE_VOCAB"), "/root/reference/bpe_simple_vocab_16e6.txt"):
-        if p and Path(p).exists():
-            return p
-    return None
-
-
-needs_vocab = pytest.mark.skipif(vocab_path() is None, reason="reference merges file not available")
 
 
 def test_attn_decoder_mask():
@@ -73,29 +61,26 @@ def test_causality():
     assert np.abs(a[:3] - b[:3]).max() < 1e-12 and np.abs(a[3:] - b[3:]).max() > 1e-3
 
 
-@needs_vocab
-def test_tokenizer_rust_kat():
+def test_tokenizer_rust_kat(bpe_vocab):
     """src/tokenizer.rs:209-221 test_encode_decode."""
     doc = json.loads((GOLD / "refpy_tokens.json").read_text())["rust_kat"]
-    t = TokenizerOracle(vocab_path())
+    t = TokenizerOracle(bpe_vocab)
     ids = t.encode(doc["text"])
     assert ids == doc["ids"]
     assert t.decode(ids) == doc["decoded"]
     assert len(t.encoder) == 49408 and t.encoder["<|startoftext|>"] == 49406 and t.encoder["<|endoftext|>"] == 49407
 
 
-@needs_vocab
-def test_tokenizer_matches_reference_python():
+def test_tokenizer_matches_reference_python(bpe_vocab):
     doc = json.loads((GOLD / "refpy_tokens.json").read_text())
-    t = TokenizerOracle(vocab_path())
+    t = TokenizerOracle(bpe_vocab)
     for row in doc["prompts"]:
         assert t.encode(row["text"]) == row["ids"], row["text"]
 
 
-@needs_vocab
-def test_context_tokens_unpadded():
+def test_context_tokens_unpadded(bpe_vocab):
     """StableDiffusion::context (stablediffusion/mod.rs:198-205): start + text + end, no padding (quirk Q2)."""
-    t = TokenizerOracle(vocab_path())
+    t = TokenizerOracle(bpe_vocab)
     assert t.context_tokens("") == [49406, 49407]
     ids = t.context_tokens("a photo of a cat")
     assert ids[0] == 49406 and ids[-1] == 49407 and len(ids) == 7

@@ -47,9 +47,10 @@ def test_padded_conv_is_the_reference_emulation():
     """PaddedConv2d (autoencoder/mod.rs:343-411): symmetric pad 2 + stride 2 + slice == asymmetric (0,1,0,1) padding."""
     import torch.nn.functional as F
     gen = torch.Generator().manual_seed(0)
-    x = torch.randn(2, 5, 12, 10, generator=gen, dtype=torch.float64)
-    w = torch.randn(7, 5, 3, 3, generator=gen, dtype=torch.float64)
-    b = torch.randn(7, generator=gen, dtype=torch.float64)
+    # small integers: every sum is exact in fp64, so the two convolutions agree bit for bit whichever CPU kernel and summation order each gets
+    x = torch.randint(-8, 9, (2, 5, 12, 10), generator=gen).to(torch.float64)
+    w = torch.randint(-8, 9, (7, 5, 3, 3), generator=gen).to(torch.float64)
+    b = torch.randint(-8, 9, (7,), generator=gen).to(torch.float64)
     full = F.conv2d(x, w, b, stride=2, padding=2)          # padding_actual = [2, 2]
     want = full[:, :, 1:1 + 6, 1:1 + 5]                     # skip = 1, desired = (0 + 1 + H - 3) / 2 + 1
     got = O.padded_conv2d(x, (w, b), 2, 0, 1, 0, 1)

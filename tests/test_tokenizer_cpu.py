@@ -1,7 +1,6 @@
 """The product tokenizer (C++, inside libsdmi.so; src/tokenizer.rs twin) against the oracle tokenizer, the
 reference's Rust test vector and the ids of the reference's python/tokenizer.py.  Host code: no GPU needed."""
 import json
-import os
 import random
 from pathlib import Path
 
@@ -11,16 +10,6 @@ from oracle.tokenizer_oracle import TokenizerOracle
 
 GOLD = Path(__file__).parent / "golden"
 MINI = GOLD / "mini_merges.txt"
-
-
-def vocab_path():
-    for p in (os.environ.get("SDMI_BPE_VOCAB"), "/root/reference/bpe_simple_vocab_16e6.txt"):
-        if p and Path(p).exists():
-            return p
-    return None
-
-
-needs_vocab = pytest.mark.skipif(vocab_path() is None, reason="reference merges file not available")
 
 ALPHABET = "abc XYZ'’ \t\n.,!?-_/0123456789éßΣσςİıǅ中文\U0001F680½²ªº  ́ſʰ·:<|>"
 
@@ -53,29 +42,26 @@ def test_missing_merges_file_is_an_error():
         SimpleTokenizer("/nonexistent/merges.txt")
 
 
-@needs_vocab
-def test_rust_kat():
+def test_rust_kat(bpe_vocab):
     """src/tokenizer.rs:209-221 test_encode_decode, run on the product tokenizer."""
     from stable_diffusion_burn_amd import SimpleTokenizer
     doc = json.loads((GOLD / "refpy_tokens.json").read_text())["rust_kat"]
-    tok = SimpleTokenizer(vocab_path())
+    tok = SimpleTokenizer(bpe_vocab)
     assert tok.vocab_size == 49408
     ids = tok.encode(doc["text"])
     assert ids == doc["ids"]
     assert tok.decode(ids) == doc["decoded"]
 
 
-@needs_vocab
-def test_reference_python_ids():
+def test_reference_python_ids(bpe_vocab):
     from stable_diffusion_burn_amd import SimpleTokenizer
     doc = json.loads((GOLD / "refpy_tokens.json").read_text())
-    tok = SimpleTokenizer(vocab_path())
+    tok = SimpleTokenizer(bpe_vocab)
     for row in doc["prompts"]:
         assert tok.encode(row["text"]) == row["ids"], row["text"]
 
 
-@needs_vocab
-def test_full_vocab_fuzz_matches_oracle():
+def test_full_vocab_fuzz_matches_oracle(bpe_vocab):
     from stable_diffusion_burn_amd import SimpleTokenizer
-    tok, ora = SimpleTokenizer(vocab_path()), TokenizerOracle(vocab_path())
+    tok, ora = SimpleTokenizer(bpe_vocab), TokenizerOracle(bpe_vocab)
     _fuzz(tok, ora, 1500, 1)
