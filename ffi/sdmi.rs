@@ -54,6 +54,19 @@ extern "C" {
     fn sdmi_latent_to_image(ctx: *mut c_void, latent: *const c_float, n: i32, rgb_out: *mut u8) -> c_int;
     fn sdmi_sample_image(ctx: *mut c_void, context: *const c_float, n: i32, t_len: i32, uncond: *const c_float, tu: i32,
                          scale: c_double, n_steps: usize, init_latent: *const c_float, seed: u64, rgb_out: *mut u8) -> c_int;
+    fn sdmi_img2img_timesteps(total: i32, n_steps: usize, strength: c_double, timesteps: *mut i32, capacity: i32, count: *mut i32) -> c_int;
+    fn sdmi_img2img_latent(ctx: *mut c_void, context: *const c_float, n: i32, t_len: i32, uncond: *const c_float, tu: i32, scale: c_double,
+                           n_steps: usize, strength: c_double, z0: *const c_float, mask: *const c_float, noise: *const c_float, seed: u64,
+                           latent_out: *mut c_float) -> c_int;
+    fn sdmi_img2img_image(ctx: *mut c_void, context: *const c_float, n: i32, t_len: i32, uncond: *const c_float, tu: i32, scale: c_double,
+                          n_steps: usize, strength: c_double, init_rgb: *const u8, mask: *const c_float, noise: *const c_float, seed: u64,
+                          rgb_out: *mut u8) -> c_int;
+    fn sdmi_img2img_latent_dev(ctx: *mut c_void, context: *const c_float, n: i32, t_len: i32, uncond: *const c_float, tu: i32, scale: c_double,
+                               n_steps: usize, strength: c_double, z0: *const c_float, mask: *const c_float, noise: *const c_float, seed: u64,
+                               latent_out: *mut c_float) -> c_int;
+    fn sdmi_img2img_image_dev(ctx: *mut c_void, context: *const c_float, n: i32, t_len: i32, uncond: *const c_float, tu: i32, scale: c_double,
+                              n_steps: usize, strength: c_double, init_rgb: *const u8, mask: *const c_float, noise: *const c_float, seed: u64,
+                              rgb_out: *mut u8) -> c_int;
     fn sdmi_tokenizer_create(out: *mut *mut c_void, merges_path: *const c_char) -> c_int;
     fn sdmi_tokenizer_destroy(tok: *mut c_void);
     fn sdmi_tokenizer_encode(tok: *const c_void, text: *const c_char, ids: *mut i32, capacity: i32, n_ids: *mut i32) -> c_int;
@@ -210,6 +223,27 @@ impl StableDiffusionMi355 {
         check(unsafe {
             sdmi_sample_image(self.ctx, context.as_ptr(), n_batch as i32, t as i32, unconditional_context.as_ptr(), tu as i32,
                               unconditional_guidance_scale, n_steps, std::ptr::null(), seed, flat.as_mut_ptr())
+        });
+        flat.chunks(per).map(|c| c.to_vec()).collect()
+    }
+
+    /// img2img (include/sdmi.h "img2img"; no reference counterpart): `sample_image` started from `init_images`
+    /// (n x [512,512,3] u8, sample_image's output layout) re-noised to the last `strength` of the schedule.
+    /// `mask` [n,1,64,64] (1 = regenerate, 0 = keep) or None; the noise is image i's stream `seed + i`.
+    pub fn sample_image_from(&self, context: &[f32], n_batch: usize, unconditional_context: &[f32],
+                             unconditional_guidance_scale: f64, n_steps: usize, strength: f64, init_images: &[Vec<u8>],
+                             mask: Option<&[f32]>, seed: u64) -> Vec<Vec<u8>> {
+        let t = context.len() / (n_batch * self.ctx_dim);
+        let tu = unconditional_context.len() / self.ctx_dim;
+        assert_eq!(context.len(), n_batch * t * self.ctx_dim);
+        let per = self.latent / 4 * 64 * 3; // 512*512*3
+        assert_eq!(init_images.len(), n_batch);
+        let init: Vec<u8> = init_images.iter().flat_map(|im| { assert_eq!(im.len(), per); im.iter().copied() }).collect();
+        let m = mask.map_or(std::ptr::null(), |s| { assert_eq!(s.len(), n_batch * self.latent / 4); s.as_ptr() });
+        let mut flat = vec![0u8; n_batch * per];
+        check(unsafe {
+            sdmi_img2img_image(self.ctx, context.as_ptr(), n_batch as i32, t as i32, unconditional_context.as_ptr(), tu as i32,
+                               unconditional_guidance_scale, n_steps, strength, init.as_ptr(), m, std::ptr::null(), seed, flat.as_mut_ptr())
         });
         flat.chunks(per).map(|c| c.to_vec()).collect()
     }

@@ -171,6 +171,32 @@ int sdmi_sample_image(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T,
                       const float* uncond, int32_t Tu, double scale, size_t n_steps,
                       const float* init_latent, uint64_t seed, uint8_t* rgb_out);
 
+/* ---- img2img: sampling from an init image, optionally masked (no reference counterpart) ----
+ * The DDIM + CFG loop of sdmi_sample_latent run over the LAST k of its timesteps ts (L entries, quirk Q5 included),
+ * k = min(L, (size_t)(strength * L)), t0 = ts[L - k], started from
+ *     x_t0 = sqrt(a_t0) z0 + sqrt(1 - a_t0) eps        (a = alphas_cumprod; coefficients in f64, applied as f32)
+ * eps = noise [n,4,h,w], or when noise is NULL image i's N(0,1) stream seed + i (the draws of sdmi_sample_latent's
+ * seed path, same elements).  Each step is sample_latent's update, unchanged.  mask [n,1,h,w] fp32 (1 = regenerate,
+ * 0 = keep, values between blend) or NULL: after each step's update to t_prev,
+ *     x <- m x + (1 - m)(sqrt(a_prev) z0 + sqrt(1 - a_prev) eps)   (same eps; not applied at t0)
+ * so m = 0 ends exactly at z0.  context [n,T,ctx_dim], uncond [Tu,ctx_dim] broadcast, as in sample_latent.
+ * SDMI_ERR_INVALID unless 0 < strength <= 1 and k >= 1. */
+
+/* Host only, needs no device: the timesteps ts[L - k ..] the call runs for `total` = len(alphas_cumprod) (1000).
+ * *count is always set to k when the arguments are valid; SDMI_ERR_INVALID if capacity < k (nothing written). */
+int sdmi_img2img_timesteps(int32_t total, size_t n_steps, double strength, int32_t* timesteps, int32_t capacity, int32_t* count);
+/* z0 [n,4,h,w]: the start latent in the sampler's space (= 0.18215 x the VAE posterior mean); latent_out [n,4,h,w].
+ * Does not need the encoder weights. */
+int sdmi_img2img_latent(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu,
+                        double scale, size_t n_steps, double strength, const float* z0, const float* mask,
+                        const float* noise, uint64_t seed, float* latent_out);
+/* init_rgb n x [8h,8w,3] uint8 HWC (sdmi_sample_image's output layout): z0 = 0.18215 * encode_image(v / 127.5 - 1).
+ * rgb_out = latent_to_image of the final latent, as sdmi_sample_image.  Pixels of the kept (m = 0) region go through
+ * one VAE round trip: they are NOT pasted back from init_rgb.  Needs the encoder weight group (SDMI_ERR_STATE otherwise). */
+int sdmi_img2img_image(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu,
+                       double scale, size_t n_steps, double strength, const uint8_t* init_rgb, const float* mask,
+                       const float* noise, uint64_t seed, uint8_t* rgb_out);
+
 /* qkv_attention (src/model/attention.rs:5-45 == src/backend.rs:88-128; the
  * operator seam of the commented-out `trait Backend`, backend.rs:4-84).
  * q [n,nq,n_state], k,v [n,nk,n_state], mask [>=nq, mask_ld>=nk] additive or
@@ -223,6 +249,13 @@ int sdmi_latent_to_image_dev(sdmi_ctx* ctx, const float* latent, int32_t n, uint
 int sdmi_sample_image_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T,
                           const float* uncond, int32_t Tu, double scale, size_t n_steps,
                           const float* init_latent, uint8_t* rgb_out);
+/* img2img with device pointers (mask / noise may be NULL) */
+int sdmi_img2img_latent_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu,
+                            double scale, size_t n_steps, double strength, const float* z0, const float* mask,
+                            const float* noise, uint64_t seed, float* latent_out);
+int sdmi_img2img_image_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu,
+                           double scale, size_t n_steps, double strength, const uint8_t* init_rgb, const float* mask,
+                           const float* noise, uint64_t seed, uint8_t* rgb_out);
 
 /* ---- multi-GPU: the image batch sharded over the devices of one node ----------------------
  * The reference's caller asks one StableDiffusion for n images of one prompt (src/bin/sample/main.rs:104-109).
@@ -309,7 +342,7 @@ int sdmi_last_call_stats(sdmi_ctx* ctx, double* gpu_ms, int64_t* n_kernels, doub
  * 6 conv_gemm_split (precision = 0: the conv/linear launches that run on the bf16 matrix pipe with three-way split fp32
  * operands, k_gemm3x.hip / k_gemm3p.hip; class 0 then holds the launches left on the fp32 matrix instruction), 7 split_rows (fp32 tensors
  * converted to bf16 planes for a plane GEMM outside their producer), 8 other (every launch of the path that is in no other class: layout converters, the
- * CFG + DDIM update, timestep embedding, SiLU of the embedding, row softmax / transposes of the unfused VAE attention, u8 conversion), 9 geglu (the GEGLU gate kernels
+ * CFG + DDIM update, img2img's u8 -> fp32 input conversion, start latent and masked CFG + DDIM update, timestep embedding, SiLU of the embedding, row softmax / transposes of the unfused VAE attention, u8 conversion), 9 geglu (the GEGLU gate kernels
  * where the gate is not fused into its GEMM; the quantising gate of precision = 2 included).  flops / bytes are the ALGORITHMIC work of
  * those launches (2*M*N*K; one read + one write of the tensor).  "profile_reset" clears. */
 int sdmi_profile_stats(sdmi_ctx* ctx, int32_t cls, double* ms, int64_t* launches, double* flops, double* bytes);

@@ -59,6 +59,9 @@ SIGNATURES = {
     "sdmi_decode_latent": (C.c_int, [_CTX, _F, C.c_int32, _F]),
     "sdmi_latent_to_image": (C.c_int, [_CTX, _F, C.c_int32, _U8]),
     "sdmi_sample_image": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F, C.c_int32, C.c_double, C.c_size_t, _F, C.c_uint64, _U8]),
+    "sdmi_img2img_timesteps": (C.c_int, [C.c_int32, C.c_size_t, C.c_double, _I32, C.c_int32, _I32]),
+    "sdmi_img2img_latent": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F, C.c_int32, C.c_double, C.c_size_t, C.c_double, _F, _F, _F, C.c_uint64, _F]),
+    "sdmi_img2img_image": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F, C.c_int32, C.c_double, C.c_size_t, C.c_double, _U8, _F, _F, C.c_uint64, _U8]),
     "sdmi_qkv_attention": (C.c_int, [_CTX, _F, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),
     "sdmi_tokenizer_create": (C.c_int, [C.POINTER(_TOK), C.c_char_p]),
     "sdmi_tokenizer_destroy": (None, [_TOK]),
@@ -72,6 +75,8 @@ SIGNATURES = {
     "sdmi_sample_latent_dev": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_size_t, C.c_void_p, C.c_void_p]),
     "sdmi_latent_to_image_dev": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_void_p]),
     "sdmi_sample_image_dev": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "sdmi_img2img_latent_dev": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_size_t, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "sdmi_img2img_image_dev": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_size_t, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "sdmi_create_multi": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SdmiConfig), _I32, C.c_int32]),
     "sdmi_destroy_multi": (None, [C.c_void_p]),
     "sdmi_multi_size": (C.c_int32, [C.c_void_p]),

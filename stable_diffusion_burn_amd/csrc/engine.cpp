@@ -547,7 +547,7 @@ void Engine::build_model() {
     }
 
     // ---- VAE encoder (autoencoder/mod.rs:30-32,76-144,220-265; names autoencoder/load.rs:120-190) -- SURVEY 8f rank 4
-    // Optional weight group: `sample` never encodes; sdmi_encode_image needs the whole group.
+    // Optional weight group: txt2img never encodes; sdmi_encode_image and sdmi_img2img_image need the whole group.
     {
         cur_group_ = 2;
         const int ech[4][2] = {{vc, vc}, {vc, 2 * vc}, {2 * vc, 4 * vc}, {4 * vc, 4 * vc}};
@@ -2228,11 +2228,22 @@ void Engine::sample_latent_dev(const float* context, int n, int T, const float* 
     check_batch(n);
     const size_t total = alphas_.size();
     if (n_steps == 0 || n_steps > total) throw Error(SDMI_ERR_INVALID, "sample_latent: n_steps out of range");
-    const int H = cfg_.latent_h, W = cfg_.latent_w, cd = cfg_.ctx_dim;
-    const int nb = 2 * n, t_max = std::max(T, Tu);
+    const int H = cfg_.latent_h, W = cfg_.latent_w;
     const size_t step_size = total / n_steps;                       // :111
     std::vector<int> ts;
     for (long long t = (long long)total - 1; t >= 0; t -= (long long)step_size) ts.push_back((int)t);  // :123
+    sample_loop(context, n, T, uncond, Tu, scale, ts, step_size, [&](float* latent, float* unet_in, long long per_half) {
+        SDMI_HIP(launch_nchw_to_nhwc(init_latent, latent, n, 4, H, W, 1.0f, stream_));
+        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_dup_latent(latent, unet_in, per_half, stream_)); }
+        count_kernel(); count_kernel();
+    }, nullptr, latent_out);
+}
+
+void Engine::sample_loop(const float* context, int n, int T, const float* uncond, int Tu, double scale, const std::vector<int>& ts,
+                         size_t step_size, const std::function<void(float* latent, float* unet_in, long long per_half)>& start,
+                         const Blend* blend, float* latent_out) {
+    const int H = cfg_.latent_h, W = cfg_.latent_w, cd = cfg_.ctx_dim;
+    const int nb = 2 * n, t_max = std::max(T, Tu);
 
     // packed context [2n][t_max][cd]: rows 0..n-1 = uncond (broadcast, :173-177), n..2n-1 = cond
     Buf ctx(this, (size_t)nb * t_max * cd * 4);
@@ -2248,9 +2259,7 @@ void Engine::sample_latent_dev(const float* context, int n, int T, const float* 
 
     const long long per_half = (long long)n * H * W * 4;
     Buf latent(this, per_half * 4), unet_in(this, 2 * per_half * 4), eps(this, 2 * per_half * 4);
-    SDMI_HIP(launch_nchw_to_nhwc(init_latent, latent.f(), n, 4, H, W, 1.0f, stream_));
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_dup_latent(latent.f(), unet_in.f(), per_half, stream_)); }
-    count_kernel(); count_kernel();
+    start(latent.f(), unet_in.f(), per_half);
     for (size_t s = 0; s < ts.size(); ++s) {
         const size_t t = (size_t)ts[s];
         const double cur = (double)alphas_[t];                                           // :124-129
@@ -2262,12 +2271,72 @@ void Engine::sample_latent_dev(const float* context, int n, int T, const float* 
         c.sqrt_prev = (float)std::sqrt(prev);
         c.dir_coef = (float)std::sqrt(1.0 - prev - 0.0);                                 // :153 (sigma = 0)
         unet_run(unet_in.f(), nb, (int)s, eps.f(), opt_cfg_share_ != 0);   // unet_in = [latent | latent]: a CFG pair
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_cfg_ddim(eps.f(), latent.f(), unet_in.f(), per_half, c, stream_)); }
+        if (blend) { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_cfg_ddim_masked(eps.f(), latent.f(), unet_in.f(), per_half, c, blend->mask, blend->z0, blend->eps, stream_)); }
+        else { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_cfg_ddim(eps.f(), latent.f(), unet_in.f(), per_half, c, stream_)); }
         count_kernel();
     }
     { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(latent.f(), latent_out, n, 4, H, W, stream_)); }
     count_kernel();
     unet_release();
+}
+
+// img2img rule 1 (sdmi_img2img_timesteps, DESIGN.md "img2img") plus the checks of sample_latent
+std::vector<int> Engine::img2img_schedule(int n, int T, int Tu, size_t n_steps, double strength, size_t* step_size) {
+    if (!finalized_) throw Error(SDMI_ERR_STATE, "weights not finalized");
+    if (n <= 0 || T <= 0 || Tu <= 0) throw Error(SDMI_ERR_INVALID, "img2img: n, T, Tu must be positive");
+    check_batch(n);
+    const size_t total = alphas_.size();
+    if (n_steps == 0 || n_steps > total) throw Error(SDMI_ERR_INVALID, "img2img: n_steps out of range");
+    std::vector<int> ts(total);
+    int32_t count = 0;
+    const int st = sdmi_img2img_timesteps((int32_t)total, n_steps, strength, ts.data(), (int32_t)total, &count);
+    if (st != SDMI_OK) throw Error(st, "img2img: strength must satisfy 0 < strength <= 1 and leave at least one step");
+    ts.resize(count);
+    *step_size = total / n_steps;
+    return ts;
+}
+
+void Engine::img2img_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps,
+                                double strength, const float* z0, const float* mask, const float* noise, uint64_t seed, float* latent_out) {
+    size_t step_size = 0;
+    const std::vector<int> ts = img2img_schedule(n, T, Tu, n_steps, strength, &step_size);
+    const long long hw = (long long)cfg_.latent_h * cfg_.latent_w, elems = (long long)n * hw * 4;
+    const double a0 = (double)alphas_[ts[0]];
+    const float sqrt_a = (float)std::sqrt(a0), sqrt_1ma = (float)std::sqrt(1.0 - a0);
+    Buf z0k(this, mask ? elems * 4 : 256), e0k(this, mask ? elems * 4 : 256);   // z0 and eps for the blend (NHWC)
+    const Blend blend{mask, z0k.f(), e0k.f()};
+    sample_loop(context, n, T, uncond, Tu, scale, ts, step_size, [&](float* latent, float* unet_in, long long per_half) {
+        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_img2img_start(z0, false, noise, seed, sqrt_a, sqrt_1ma, latent, unet_in, per_half,
+                                                                        mask ? z0k.f() : nullptr, mask ? e0k.f() : nullptr, n, hw, stream_)); }
+        count_kernel();
+    }, mask ? &blend : nullptr, latent_out);
+}
+
+void Engine::img2img_image_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps,
+                               double strength, const uint8_t* init_rgb, const float* mask, const float* noise, uint64_t seed, float* latent_out) {
+    if (finalized_ && !enc_ready_) throw Error(SDMI_ERR_STATE, "VAE encoder weights are not loaded (autoencoder/encoder/..., autoencoder/quant_conv)");
+    size_t step_size = 0;
+    const std::vector<int> ts = img2img_schedule(n, T, Tu, n_steps, strength, &step_size);
+    const int H = cfg_.latent_h, W = cfg_.latent_w;
+    const long long hw = (long long)H * W, elems = (long long)n * hw * 4;
+    const double a0 = (double)alphas_[ts[0]];
+    const float sqrt_a = (float)std::sqrt(a0), sqrt_1ma = (float)std::sqrt(1.0 - a0);
+    Buf z0k(this, mask ? elems * 4 : 256), e0k(this, mask ? elems * 4 : 256);
+    const Blend blend{mask, z0k.f(), e0k.f()};
+    sample_loop(context, n, T, uncond, Tu, scale, ts, step_size, [&](float* latent, float* unet_in, long long per_half) {
+        for (int i = 0; i < n; ++i) {   // one image at a time through the encoder, as encode_image_dev; its start latent right behind its quant_conv
+            Act rgb = new_act(1, 8 * H, 8 * W, 4, /*dt=*/0);
+            { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_rgb_u8_to_nhwc4(init_rgb + (size_t)i * 3 * 64 * hw, rgb.p, 64 * hw, stream_)); }
+            count_kernel();
+            Act q8 = encode_one(rgb);
+            const long long off = (long long)i * hw * 4;
+            { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_img2img_start(q8.p, true, noise ? noise + off : nullptr, seed + (uint64_t)i, sqrt_a, sqrt_1ma,
+                                                                            latent + off, unet_in + off, per_half, mask ? z0k.f() + off : nullptr,
+                                                                            mask ? e0k.f() + off : nullptr, 1, hw, stream_)); }
+            count_kernel();
+            release(q8);
+        }
+    }, mask ? &blend : nullptr, latent_out);
 }
 
 // Autoencoder::decode_latent (autoencoder/mod.rs:68-71) -> Decoder::forward (:205-217)
@@ -2324,44 +2393,49 @@ void Engine::encode_image_dev(const float* img_nchw, int n, float* latent_nchw) 
         Act rgb = new_act(1, H, W, 4, /*dt=*/0);
         { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nchw3_to_nhwc4(img_nchw + i * img_elems, rgb.p, 1, H, W, stream_)); }
         count_kernel();
-        Act x = new_act(1, H, W, enc_conv_in_.cout);
-        conv(enc_conv_in_, rgb, x, 1, 0, nullptr, 0, nullptr);
-        release(rgb);
-        for (int bi = 0; bi < 4; ++bi) {  // EncoderBlock::forward (:257-265)
-            const EncBlockW& b = enc_blocks_[bi];
-            for (int r = 0; r < 2; ++r) {
-                Act y = new_act(x.n, x.h, x.w, b.cout);
-                res_block(b.res[r], x, y, 0);
-                release(x);
-                x = y;
-            }
-            if (b.has_down) {
-                Act y = new_act(x.n, x.h / 2, x.w / 2, b.cout);
-                conv(b.down, x, y, 2, 0, nullptr, 0, nullptr, /*pad_br=*/true);
-                release(x);
-                x = y;
-            }
-        }
-        {   // Mid (:457-462)
-            Act a = new_act(x.n, x.h, x.w, x.c); res_block(enc_mid1_, x, a, 0); release(x);
-            Act b = new_act(a.n, a.h, a.w, a.c); vae_attn(enc_attn_, a, b); release(a);
-            Act c = new_act(b.n, b.h, b.w, b.c); res_block(enc_mid2_, b, c, 0); release(b);
-            x = c;
-        }
-        Act gn = new_act(x.n, x.h, x.w, x.c);
-        group_norm(enc_norm_out_, x, gn, true);
-        release(x);
-        Act m8 = new_act(gn.n, gn.h, gn.w, 8, /*dt=*/0);   // moments stay fp32 in both precisions
-        conv(enc_conv_out_, gn, m8, 1, 0, nullptr, 0, nullptr);
-        release(gn);
-        Act q8 = new_act(m8.n, m8.h, m8.w, 8, /*dt=*/0);
-        conv(quant_conv_, m8, q8, 1, 0, nullptr, 0, nullptr);
-        release(m8);
+        Act q8 = encode_one(rgb);
         // latent.slice([0..n, 0..4]): the first 4 of the 8 channels, NHWC8 -> NCHW4
         { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw_slice(q8.p, latent_nchw + i * lat_elems, 1, 8, 4, q8.h, q8.w, stream_)); }
         count_kernel();
         release(q8);
     }
+}
+
+Act Engine::encode_one(Act& rgb) {
+    Act x = new_act(1, rgb.h, rgb.w, enc_conv_in_.cout);
+    conv(enc_conv_in_, rgb, x, 1, 0, nullptr, 0, nullptr);
+    release(rgb);
+    for (int bi = 0; bi < 4; ++bi) {  // EncoderBlock::forward (:257-265)
+        const EncBlockW& b = enc_blocks_[bi];
+        for (int r = 0; r < 2; ++r) {
+            Act y = new_act(x.n, x.h, x.w, b.cout);
+            res_block(b.res[r], x, y, 0);
+            release(x);
+            x = y;
+        }
+        if (b.has_down) {
+            Act y = new_act(x.n, x.h / 2, x.w / 2, b.cout);
+            conv(b.down, x, y, 2, 0, nullptr, 0, nullptr, /*pad_br=*/true);
+            release(x);
+            x = y;
+        }
+    }
+    {   // Mid (:457-462)
+        Act a = new_act(x.n, x.h, x.w, x.c); res_block(enc_mid1_, x, a, 0); release(x);
+        Act b = new_act(a.n, a.h, a.w, a.c); vae_attn(enc_attn_, a, b); release(a);
+        Act c = new_act(b.n, b.h, b.w, b.c); res_block(enc_mid2_, b, c, 0); release(b);
+        x = c;
+    }
+    Act gn = new_act(x.n, x.h, x.w, x.c);
+    group_norm(enc_norm_out_, x, gn, true);
+    release(x);
+    Act m8 = new_act(gn.n, gn.h, gn.w, 8, /*dt=*/0);   // moments stay fp32 in both precisions
+    conv(enc_conv_out_, gn, m8, 1, 0, nullptr, 0, nullptr);
+    release(gn);
+    Act q8 = new_act(m8.n, m8.h, m8.w, 8, /*dt=*/0);
+    conv(quant_conv_, m8, q8, 1, 0, nullptr, 0, nullptr);
+    release(m8);
+    return q8;
 }
 
 // in_scale = 1/0.18215 for latent_to_image (stablediffusion/mod.rs:71), 1 for decode_latent.

@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -153,6 +154,14 @@ public:
     void encode_image_dev(const float* img_nchw, int n, float* latent_nchw);
     void sample_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale,
                            size_t n_steps, const float* init_latent, float* latent_out);
+    // img2img (DESIGN.md section "img2img"): the last k of sample_latent's timesteps (sdmi_img2img_timesteps), started from
+    // z0 re-noised to t0 with eps = noise [n,4,h,w] or, when null, image i's N(0,1) stream seed + i; mask [n,1,h,w] or null.
+    // _latent: z0 [n,4,h,w] NCHW; _image: z0 = 0.18215 * encode_image(rgb / 127.5 - 1), rgb = n x [8h,8w,3] u8 (needs the
+    // encoder weights).  latent_out [n,4,h,w].  Device pointers.
+    void img2img_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps,
+                            double strength, const float* z0, const float* mask, const float* noise, uint64_t seed, float* latent_out);
+    void img2img_image_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps,
+                           double strength, const uint8_t* init_rgb, const float* mask, const float* noise, uint64_t seed, float* latent_out);
     void decode_latent_dev(const float* latent_nchw, int n, float in_scale, float* img_nchw, uint8_t* rgb_u8);
     void qkv_attention_dev(const float* q, const float* k, const float* v, const float* mask, int mask_ld, int n,
                            int nq, int nk, int n_state, int n_head, float* out);
@@ -315,6 +324,17 @@ private:
     void unet_release();
     void unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bool cfg_pair = false);
     void decode_one(const float* z_nhwc, int n, Act& img);
+    // Encoder::forward + quant_conv of ONE image: rgb [1][8h][8w][4] fp32 (released here) -> the 8 moments [1][h][w][8] fp32 (caller releases)
+    Act encode_one(Act& rgb);
+    // The DDIM + CFG loop of sample_latent over `ts` (sample_latent's schedule or its tail): `start` writes x_ts[0] into the NHWC latent
+    // [n][hw][4] and both halves of unet_in [2n][hw][4] (per_half floats each).  blend (img2img with a mask): after each update
+    // x <- m x + (1 - m)(sqrt(a_prev) z0 + sqrt(1 - a_prev) eps), device pointers, z0 / eps NHWC.
+    struct Blend { const float* mask; const float* z0; const float* eps; };
+    void sample_loop(const float* context, int n, int T, const float* uncond, int Tu, double scale, const std::vector<int>& ts,
+                     size_t step_size, const std::function<void(float* latent, float* unet_in, long long per_half)>& start,
+                     const Blend* blend, float* latent_out);
+    // argument checks of both img2img entry points; returns the timesteps (rule 1) and the schedule's step size
+    std::vector<int> img2img_schedule(int n, int T, int Tu, size_t n_steps, double strength, size_t* step_size);
 
     void count_kernel(double flops = 0) { ++n_kernels_; flops_ += flops; }
     // roctx ranges (option "roctx=1"; rocprofv3 --marker-trace shows them): one per DDIM step, UNet block, ResBlock,

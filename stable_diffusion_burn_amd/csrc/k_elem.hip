@@ -12,6 +12,7 @@
 // All are HBM/latency bound and tiny next to the convolutions; they use 16-byte
 // accesses and grid-stride loops.
 #include "kernels.hpp"
+#include "k_sample.hpp"
 #include "k_split3.hpp"
 
 namespace sdmi {
@@ -172,13 +173,7 @@ __global__ void timestep_embedding_kernel(const int* __restrict__ t, int n_t, in
 __global__ void cfg_ddim_kernel(const float* __restrict__ eps, float* __restrict__ latent, float* __restrict__ unet_in,
                                 long long per_half, DdimCoef c) {
     GRID_STRIDE(i, per_half) {
-        const float eu = eps[i];
-        const float ec = eps[per_half + i];
-        const float e = eu + (ec - eu) * c.scale;                  // :190-191
-        const float x = latent[i];
-        const float predx0 = (x - e * c.sqrt_noise) / c.sqrt_cur;  // :152
-        const float dir = e * c.dir_coef;                          // :153
-        const float nx = predx0 * c.sqrt_prev + dir;               // :155 (sigma = 0)
+        const float nx = cfg_ddim_update(eps[i], eps[per_half + i], latent[i], c);   // k_sample.hpp
         latent[i] = nx;
         unet_in[i] = nx;
         unet_in[per_half + i] = nx;
@@ -203,21 +198,9 @@ __global__ void image_to_u8_kernel(const float* __restrict__ img, uint8_t* __res
     }
 }
 
-// splitmix64 -> Box-Muller; used only when the caller passes no initial latent
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
+// N(0,1) from splitmix64 -> Box-Muller (k_sample.hpp); used only when the caller passes no initial latent
 __global__ void fill_normal_kernel(float* __restrict__ dst, long long n, uint64_t seed) {
-    GRID_STRIDE(i, n) {
-        const uint64_t r = splitmix64(seed * 0xD1342543DE82EF95ull + (uint64_t)i);
-        const float u1 = ((float)(uint32_t)(r >> 40) + 1.0f) * (1.0f / 16777217.0f);
-        const float u2 = (float)(uint32_t)((r >> 8) & 0xFFFFFF) * (1.0f / 16777216.0f);
-        dst[i] = sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
-    }
+    GRID_STRIDE(i, n) dst[i] = normal_draw(seed, (uint64_t)i);
 }
 
 // ---- launchers ---------------------------------------------------------------------------

@@ -223,6 +223,20 @@ hipError_t launch_dup_latent(const float* latent, float* unet_in, long long per_
 hipError_t launch_image_to_u8(const float* img_nhwc, uint8_t* out, long long n_elem, hipStream_t s);
 hipError_t launch_fill_normal(float* dst, long long n, uint64_t seed, hipStream_t s);
 
+// ---- img2img (k_img2img.hip) -----------------------------------------------------------------------------
+// rgb [pixels][3] u8 (HWC, sample_image's output layout) -> dst [pixels][4] fp32 = v / 127.5 - 1, channel 3 = 0
+hipError_t launch_rgb_u8_to_nhwc4(const uint8_t* rgb, float* dst, long long pixels, hipStream_t s);
+// x_t0 = sqrt_a z0 + sqrt_1ma eps for n images of hw pixels -> latent [n][hw][4] and both halves of unet_in
+// (the conditional half starts half_elems floats in).  z_src: from_q8 ? the encoder's NHWC8 quant_conv output
+// (z0 = 0.18215 * channels 0..3) : z0 [n,4,h,w] NCHW.  noise [n,4,h,w] NCHW, or null: image b draws N(0,1) from
+// stream seed + b (launch_fill_normal's element order).  z0_out / eps_out [n][hw][4] (both or neither): kept for
+// launch_cfg_ddim_masked.
+hipError_t launch_img2img_start(const float* z_src, bool from_q8, const float* noise, uint64_t seed, float sqrt_a, float sqrt_1ma, float* latent,
+                                float* unet_in, long long half_elems, float* z0_out, float* eps_out, int n, long long hw, hipStream_t s);
+// launch_cfg_ddim, then latent <- m latent + (1 - m)(c.sqrt_prev z0 + c.dir_coef eps) with m = mask[n][hw] (1 = regenerate)
+hipError_t launch_cfg_ddim_masked(const float* eps, float* latent, float* unet_in, long long per_half, DdimCoef c, const float* mask,
+                                  const float* z0, const float* e0, hipStream_t s);
+
 // ---- bf16-storage variants (k_bf16.hip) ---------------------------------------------------------------
 // Launch geometry of the bf16 GroupNorm passes (statistics, apply, the MXFP8 apply of k_fp8.hip): a sample's hw rows are cut into `chunks` ranges, one workgroup
 // of cq x R threads each (cq = c / 8 columns of 8 channels, R pixel rows per pass).  Round 4 cut by size alone (32 KB per chunk): at the batches of

@@ -1,8 +1,11 @@
 // sdmi_capi.cpp -- extern "C" boundary of libsdmi.so (see include/sdmi.h).
 // Translates C arguments to Engine calls, C++ exceptions to sdmi_status codes,
 // and stages host buffers through the device pool for the host-pointer API.
+#include <algorithm>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <vector>
 
 #include "engine.hpp"
 #include "mpk_reader.hpp"
@@ -208,6 +211,33 @@ int sdmi_sample_image_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_
     });
 }
 
+int sdmi_img2img_latent_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale,
+                            size_t n_steps, double strength, const float* z0, const float* mask, const float* noise, uint64_t seed,
+                            float* latent_out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (!context || !uncond || !z0 || !latent_out) throw Error(SDMI_ERR_INVALID, "img2img_latent_dev: null pointer");
+        Engine::Call call(e, /*dev_inputs=*/true);
+        e.img2img_latent_dev(context, n, T, uncond, Tu, scale, n_steps, strength, z0, mask, noise, seed, latent_out);
+        call.finish();
+    });
+}
+
+int sdmi_img2img_image_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale,
+                           size_t n_steps, double strength, const uint8_t* init_rgb, const float* mask, const float* noise, uint64_t seed,
+                           uint8_t* rgb_out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (!context || !uncond || !init_rgb || !rgb_out) throw Error(SDMI_ERR_INVALID, "img2img_image_dev: null pointer");
+        if (n <= 0) throw Error(SDMI_ERR_INVALID, "img2img_image_dev: n must be positive");
+        Engine::Call call(e, /*dev_inputs=*/true);
+        Engine::Buf lat(&e, (size_t)n * 4 * e.latent_h() * e.latent_w() * sizeof(float));
+        e.img2img_image_dev(context, n, T, uncond, Tu, scale, n_steps, strength, init_rgb, mask, noise, seed, lat.f());
+        e.decode_latent_dev(lat.f(), n, (float)(1.0 / 0.18215), nullptr, rgb_out);
+        call.finish();
+    });
+}
+
 // ---- hot path, host pointers ---------------------------------------------------------
 int sdmi_unet_forward(sdmi_ctx* ctx, const float* x, int32_t t, const float* context, int32_t n, int32_t T, float* out) {
     return guarded([&] {
@@ -328,6 +358,70 @@ int sdmi_sample_latent(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T
         make_init_latent(e, init_latent, seed, n, x0);
         DevOut dout(e, latent_out, lat);
         e.sample_latent_dev(dc.f(), n, T, du.f(), Tu, scale, n_steps, x0.f(), dout.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
+int sdmi_img2img_timesteps(int32_t total, size_t n_steps, double strength, int32_t* timesteps, int32_t capacity, int32_t* count) {
+    return guarded([&] {
+        if (!count) throw Error(SDMI_ERR_INVALID, "img2img_timesteps: null count");
+        if (total <= 0 || n_steps == 0 || n_steps > (size_t)total) throw Error(SDMI_ERR_INVALID, "img2img_timesteps: n_steps out of range");
+        if (!(strength > 0.0 && strength <= 1.0)) throw Error(SDMI_ERR_INVALID, "img2img_timesteps: strength must satisfy 0 < strength <= 1");
+        const size_t step = (size_t)total / n_steps;                         // sample_latent's schedule (stablediffusion/mod.rs:111,123)
+        std::vector<int32_t> ts;
+        for (long long t = (long long)total - 1; t >= 0; t -= (long long)step) ts.push_back((int32_t)t);
+        const size_t L = ts.size(), k = std::min(L, (size_t)(strength * (double)L));
+        if (k < 1) throw Error(SDMI_ERR_INVALID, "img2img_timesteps: strength * steps leaves no step");
+        *count = (int32_t)k;
+        if (capacity < (int32_t)k || !timesteps) throw Error(SDMI_ERR_INVALID, "img2img_timesteps: capacity too small");
+        std::memcpy(timesteps, ts.data() + (L - k), k * sizeof(int32_t));
+    });
+}
+
+// optional host input (mask, noise): staged when given
+static std::unique_ptr<DevIn> dev_in_opt(Engine& e, const void* host, size_t bytes) {
+    return host ? std::unique_ptr<DevIn>(new DevIn(e, host, bytes)) : nullptr;
+}
+
+int sdmi_img2img_latent(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale,
+                        size_t n_steps, double strength, const float* z0, const float* mask, const float* noise, uint64_t seed,
+                        float* latent_out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (n <= 0 || T <= 0 || Tu <= 0) throw Error(SDMI_ERR_INVALID, "img2img_latent: n, T, Tu must be positive");
+        const int cd = e.config().ctx_dim;
+        const size_t hw = (size_t)e.latent_h() * e.latent_w(), lat = (size_t)n * 4 * hw * sizeof(float);
+        Engine::Call call(e);
+        DevIn dc(e, context, (size_t)n * T * cd * sizeof(float)), du(e, uncond, (size_t)Tu * cd * sizeof(float)), dz(e, z0, lat);
+        auto dm = dev_in_opt(e, mask, (size_t)n * hw * sizeof(float));
+        auto dn = dev_in_opt(e, noise, lat);
+        DevOut dout(e, latent_out, lat);
+        e.img2img_latent_dev(dc.f(), n, T, du.f(), Tu, scale, n_steps, strength, dz.f(), dm ? dm->f() : nullptr, dn ? dn->f() : nullptr, seed,
+                             dout.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
+int sdmi_img2img_image(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale,
+                       size_t n_steps, double strength, const uint8_t* init_rgb, const float* mask, const float* noise, uint64_t seed,
+                       uint8_t* rgb_out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (n <= 0 || T <= 0 || Tu <= 0) throw Error(SDMI_ERR_INVALID, "img2img_image: n, T, Tu must be positive");
+        const int cd = e.config().ctx_dim;
+        const size_t hw = (size_t)e.latent_h() * e.latent_w(), lat = (size_t)n * 4 * hw * sizeof(float);
+        Engine::Call call(e);
+        DevIn dc(e, context, (size_t)n * T * cd * sizeof(float)), du(e, uncond, (size_t)Tu * cd * sizeof(float));
+        DevIn drgb(e, init_rgb, (size_t)n * 3 * 64 * hw);
+        auto dm = dev_in_opt(e, mask, (size_t)n * hw * sizeof(float));
+        auto dn = dev_in_opt(e, noise, lat);
+        Engine::Buf xl(&e, lat);
+        DevOut dout(e, rgb_out, (size_t)n * 3 * 64 * hw);
+        e.img2img_image_dev(dc.f(), n, T, du.f(), Tu, scale, n_steps, strength, reinterpret_cast<const uint8_t*>(drgb.buf.p),
+                            dm ? dm->f() : nullptr, dn ? dn->f() : nullptr, seed, xl.f());
+        e.decode_latent_dev(xl.f(), n, (float)(1.0 / 0.18215), nullptr, reinterpret_cast<uint8_t*>(dout.buf.p));
         call.finish();
         dout.fetch();
     });

@@ -41,7 +41,17 @@ def mpk_list(path) -> list:
     return out
 
 
-__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
+def img2img_timesteps(n_steps: int, strength: float, total: int = 1000) -> list:
+    """The timesteps an img2img call runs (sdmi_img2img_timesteps, host only, no GPU): the last
+    k = min(L, int(strength * L)) of sample_latent's L timesteps.  Raises SdmiError unless 0 < strength <= 1 and k >= 1."""
+    lib = load_library()
+    buf = (C.c_int32 * max(1, int(total)))()
+    count = C.c_int32()
+    check(lib.sdmi_img2img_timesteps(int(total), int(n_steps), float(strength), buf, len(buf), C.byref(count)))
+    return list(buf[:count.value])
+
+
+__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "img2img_timesteps", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
 
 
 @dataclass(frozen=True)
@@ -297,6 +307,76 @@ class StableDiffusion:
                                           None if x0 is None else _fp(x0), int(seed),
                                           out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
+
+    # ---- img2img (include/sdmi.h "img2img"; DESIGN.md section "img2img") ----------------------
+    def _check_img2img(self, n, strength, mask, noise):
+        h, w = self.config.latent_h, self.config.latent_w
+        s = float(strength)
+        if not 0.0 < s <= 1.0:   # NaN fails too
+            raise ValueError(f"strength must satisfy 0 < strength <= 1, got {strength}")
+        if mask is not None:
+            mask = _f32(mask, name="mask")
+            if mask.shape not in ((n, h, w), (n, 1, h, w)):
+                raise ValueError(f"mask must be [n,{h},{w}] or [n,1,{h},{w}] with n = {n}, got {mask.shape}")
+            if not (np.isfinite(mask).all() and (mask >= 0).all() and (mask <= 1).all()):
+                raise ValueError("mask values must lie in [0, 1]")
+            mask = mask.reshape(n, 1, h, w)
+        if noise is not None:
+            noise = _f32(noise, (n, 4, h, w), "noise")
+        return s, mask, noise
+
+    def sample_latent_from(self, context, unconditional_context, unconditional_guidance_scale: float, n_steps: int, strength: float,
+                           z0, mask=None, noise=None, seed: int = 0) -> np.ndarray:
+        """img2img in latent space -> latent [n,4,h,w].  z0 [n,4,h,w] is the start latent in the sampler's space
+        (0.18215 x the VAE posterior mean); the loop runs the last int(strength * L) of sample_latent's L timesteps.
+        mask [n,h,w] / [n,1,h,w] (1 = regenerate, 0 = keep); noise [n,4,h,w], or None: image i draws from stream seed + i."""
+        context, uncond = self._check_ctx(context, unconditional_context)
+        n, T, _ = context.shape
+        h, w = self.config.latent_h, self.config.latent_w
+        z0 = _f32(z0, (n, 4, h, w), "z0")
+        s, mask, noise = self._check_img2img(n, strength, mask, noise)
+        out = np.empty((n, 4, h, w), dtype=np.float32)
+        check(self._lib.sdmi_img2img_latent(self._ctx, _fp(context), n, T, _fp(uncond), uncond.shape[0], float(unconditional_guidance_scale),
+                                            int(n_steps), s, _fp(z0), None if mask is None else _fp(mask),
+                                            None if noise is None else _fp(noise), int(seed), _fp(out)))
+        return out
+
+    def sample_image_from(self, context, unconditional_context, unconditional_guidance_scale: float, n_steps: int, strength: float,
+                          init_image, mask=None, noise=None, seed: int = 0) -> np.ndarray:
+        """img2img from a picture -> uint8 [n, 8h, 8w, 3].  init_image uint8 [n, 8h, 8w, 3] (sample_image's layout).
+        mask at latent resolution ([n,h,w] / [n,1,h,w]) or at pixel resolution ([n,8h,8w], bool / u8 0..255 / float; reduced
+        by an 8x8 max, so a touched pixel regenerates its latent cell).  Kept pixels go through one VAE round trip;
+        they are not pasted back.  Needs the VAE encoder weights."""
+        context, uncond = self._check_ctx(context, unconditional_context)
+        n, T, _ = context.shape
+        h, w = self.config.latent_h, self.config.latent_w
+        img = np.asarray(init_image)
+        if img.dtype != np.uint8 or img.shape != (n, 8 * h, 8 * w, 3):
+            raise ValueError(f"init_image must be uint8 [{n},{8 * h},{8 * w},3], got {img.dtype} {img.shape}")
+        img = np.ascontiguousarray(img)
+        if mask is not None:
+            m = np.asarray(mask)
+            if m.dtype == np.uint8:   # 0 / 255 image masks
+                m = m.astype(np.float32) / np.float32(255.0)
+            if m.shape == (n, 8 * h, 8 * w):
+                m = m.astype(np.float32).reshape(n, h, 8, w, 8).max(axis=(2, 4))
+            mask = m
+        s, mask, noise = self._check_img2img(n, strength, mask, noise)
+        out = np.empty((n, 8 * h, 8 * w, 3), dtype=np.uint8)
+        check(self._lib.sdmi_img2img_image(self._ctx, _fp(context), n, T, _fp(uncond), uncond.shape[0], float(unconditional_guidance_scale),
+                                           int(n_steps), s, img.ctypes.data_as(C.POINTER(C.c_uint8)), None if mask is None else _fp(mask),
+                                           None if noise is None else _fp(noise), int(seed), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def sample_latent_from_dev(self, context_ptr: int, n: int, T: int, uncond_ptr: int, Tu: int, scale: float, n_steps: int,
+                               strength: float, z0_ptr: int, mask_ptr, noise_ptr, seed: int, latent_out_ptr: int) -> None:
+        check(self._lib.sdmi_img2img_latent_dev(self._ctx, context_ptr, n, T, uncond_ptr, Tu, float(scale), int(n_steps), float(strength),
+                                                z0_ptr, mask_ptr, noise_ptr, int(seed), latent_out_ptr))
+
+    def sample_image_from_dev(self, context_ptr: int, n: int, T: int, uncond_ptr: int, Tu: int, scale: float, n_steps: int,
+                              strength: float, init_rgb_ptr: int, mask_ptr, noise_ptr, seed: int, rgb_out_ptr: int) -> None:
+        check(self._lib.sdmi_img2img_image_dev(self._ctx, context_ptr, n, T, uncond_ptr, Tu, float(scale), int(n_steps), float(strength),
+                                               init_rgb_ptr, mask_ptr, noise_ptr, int(seed), rgb_out_ptr))
 
     # ---- device-pointer variants (zero copy; pointers are ints, e.g. torch .data_ptr()) ----
     def sample_image_dev(self, context_ptr: int, n: int, T: int, uncond_ptr: int, Tu: int, scale: float,
