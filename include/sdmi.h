@@ -316,6 +316,17 @@ int sdmi_op_conv2d(sdmi_ctx* ctx, const float* x, const float* weight, const flo
 /* Burn nn::Linear::forward: x [rows,cin] @ weight [cin,cout] + bias. */
 int sdmi_op_linear(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias,
                    int32_t rows, int32_t cin, int32_t cout, float* out);
+/* sdmi_op_conv2d with the other two terms a UNet convolution adds in its GEMM epilogue (no reference counterpart; for tests):
+ * out = conv(x) + bias + temb[sample] + resid, any of the three NULL.  temb is [n,cout], or [cout] with temb_stride = 0 (one row
+ * for the batch, as the UNet's ResBlocks); resid has the output's shape [n,cout,ho,wo].  The engine keeps them the way the model's
+ * launches read them: temb as fp32 rows temb_stride (>= cout) floats apart, resid as NHWC rows resid_ld (0: cout) elements apart in
+ * the output's storage type (bf16 at precision >= 1), the padding columns NaN. */
+int sdmi_op_conv2d_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, const float* temb,
+                            int32_t temb_stride, const float* resid, int32_t resid_ld, int32_t n, int32_t cin, int32_t h,
+                            int32_t w, int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t upsample2x, float* out);
+/* sdmi_op_linear + resid [rows,cout] (NULL: none), kept as rows resid_ld (0: cout) elements apart like sdmi_op_conv2d_epilogue's. */
+int sdmi_op_linear_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, const float* resid,
+                            int32_t resid_ld, int32_t rows, int32_t cin, int32_t cout, float* out);
 /* GEGLU gate (unet/mod.rs:579-591): proj [rows,2*hidden] -> out [rows,hidden] = a*gelu_erf(gate). */
 int sdmi_op_geglu(sdmi_ctx* ctx, const float* proj, int32_t rows, int32_t hidden, float* out);
 /* timestep_embedding (unet/mod.rs:19-30): out [dim] for timestep t. */

@@ -1060,6 +1060,7 @@ void Engine::set_option(const std::string& key, const std::string& value) {
     else if (key == "fp8_linear") opt_fp8_linear_ = std::stoi(value);
     else if (key == "fp8_ops") opt_fp8_ops_ = std::stoi(value);
     else if (key == "op_resid") opt_op_resid_ = std::stoi(value);
+    else if (key == "op_misalign") opt_op_misalign_ = std::stoi(value);
     else if (key == "cfg_share") opt_cfg_share_ = std::stoi(value);
     else if (key == "attn_kv_splits") opt_attn_kv_splits_ = std::stoi(value);
     else if (key == "attn_kv_prefer8") opt_attn_kv_prefer8_ = std::stoi(value);
@@ -1245,6 +1246,16 @@ TileChoice Engine::choose_tile_p(int M, int N, int kt_total, bool even_ni_only) 
     return bc;
 }
 
+// ConvGemm::resid_acc for a launch of a kernel that can take it (`eligible`: large-tile bf16 / MXFP8, no split-K): every 16-byte bias / time-embedding load and
+// 8-byte residual load of gemm_acc_init_bf16 -- edge tiles included -- must be aligned, so besides the strides the base addresses are checked; a launch
+// that fails a condition leaves its bit unset and adds that term in the epilogue
+void Engine::set_resid_acc(ConvGemm& p, bool eligible, bool resid_ok) const {
+    p.resid_acc = 0;
+    if (!eligible || (p.N % 8) || (p.ldc % 8)) return;
+    if ((opt_resid_acc_ & 1) && p.resid && resid_ok && (p.ldr % 4) == 0 && ((uintptr_t)p.resid & 7) == 0) p.resid_acc |= 1;
+    if ((opt_resid_acc_ & 2) && (p.bias || p.rowvec) && (p.rowvec_stride % 4) == 0 && (((uintptr_t)p.bias | (uintptr_t)p.rowvec) & 15) == 0) p.resid_acc |= 2;
+}
+
 void Engine::launch_gemm(ConvGemm& p, int in_dt, int force_cfg, int force_splits) {
     const int kt_elems = in_dt ? 64 : 32;  // a k tile is 128 bytes of K per row in both storage types
     p.kt_total = (p.K + kt_elems - 1) / kt_elems;
@@ -1318,11 +1329,6 @@ void Engine::launch_gemm(ConvGemm& p, int in_dt, int force_cfg, int force_splits
     p.zero_page = zero_page_;
     // bf16 3x3 / stride-1 convolutions on the 256 x 320 / 256 x 256 tiles: the form that stages a kernel row's activations once for its three taps (k_gemm_bf16t.hip)
     if (in_dt && opt_conv3_reuse_ && !tile_forced && (tc.cfg == 100 || tc.cfg == 101) && conv_gemm_bf16t_supported(p)) tc.cfg += kNumGemmTilesX;
-    if (record_shapes_) {   // which kernel / tile / split-K each (M, N, K) got: option dump_choices
-        char ck[128];
-        std::snprintf(ck, sizeof ck, "%d,%d,%d k%d s%d u%d W%d cfg=%d splits=%d%s", p.M, p.N, p.K, p.KH, p.stride, p.ups, p.Ws, tc.cfg, splits, p.Bt3 || in_dt ? "" : " (no planes)");
-        ++choice_counts_[ck];
-    }
     if (tc.cfg >= 300 ? (in_dt || tc.cfg - 300 >= kNumGemmTilesP || !p_ok)
         : tc.cfg >= 200 ? (in_dt || tc.cfg - 200 >= kNumGemmTilesS || !s_ok) : (tc.cfg >= 100 && (tc.cfg - 100 >= (in_dt ? kNumGemmTilesXB : kNumGemmTilesX) || (!in_dt && !x32_ok))))
         throw Error(SDMI_ERR_INVALID, "gemm: large-tile kernel index out of range or not applicable to this layer");
@@ -1366,10 +1372,11 @@ void Engine::launch_gemm(ConvGemm& p, int in_dt, int force_cfg, int force_splits
     p.slabs = nullptr;
     // round 6: the large-tile bf16 kernels take the residual as the accumulators' initial value (k_gemm_bf16_epi.hpp gemm_acc_init_bf16) where their 8-byte loads apply
     // (option resid_acc: bit 0 = the residual, bit 1 = bias + time-embedding row; launches without split-K only -- the split-K combine adds them otherwise)
-    p.resid_acc = 0;
-    if (in_dt && tc.cfg >= 100 && splits == 1 && (p.N % 8) == 0 && (p.ldc % 8) == 0) {
-        if ((opt_resid_acc_ & 1) && p.resid && !p.geglu && (p.ldr % 4) == 0) p.resid_acc |= 1;
-        if ((opt_resid_acc_ & 2) && (p.bias || p.rowvec) && (p.rowvec_stride % 4) == 0) p.resid_acc |= 2;
+    set_resid_acc(p, in_dt && tc.cfg >= 100 && splits == 1, !p.geglu);
+    if (record_shapes_) {   // which kernel / tile / split-K each (M, N, K) got: option dump_choices
+        char ck[128];
+        std::snprintf(ck, sizeof ck, "%d,%d,%d k%d s%d u%d W%d cfg=%d splits=%d%s acc=%d", p.M, p.N, p.K, p.KH, p.stride, p.ups, p.Ws, tc.cfg, splits, p.Bt3 || in_dt ? "" : " (no planes)", p.resid_acc);
+        ++choice_counts_[ck];
     }
     const int pc = (!in_dt && tc.cfg >= 200) ? PC_CONV_SPLIT : PC_CONV_GEMM;   // k_gemm3x.hip launches are timed as their own class
     // ALGORITHMIC bytes of the launch in the formats the tensors are stored in: the source activations once, the weights once, the result once (bf16 2 B, fp32 4 B,
@@ -1738,7 +1745,7 @@ void Engine::group_norm_fp8(const NormW& w, const Act& x, ActQ& y, bool silu) {
     count_kernel(); count_kernel();
 }
 
-void Engine::conv_fp8(const ConvW& w, const ActQ& x, Act& y, const float* rowvec, const Act* resid, int stride, int ups) {
+void Engine::conv_fp8(const ConvW& w, const ActQ& x, Act& y, const float* rowvec, const Act* resid, int stride, int ups, int rowvec_stride) {
     if (x.c != w.cin || (w.k != 3 && w.k != 1) || !w.bt8) throw Error(SDMI_ERR_STATE, "conv_fp8: not an MXFP8-packed convolution");
     const int pad = w.k == 3 ? 1 : 0;
     const int hin = x.h << ups, win = x.w << ups;
@@ -1751,7 +1758,7 @@ void Engine::conv_fp8(const ConvW& w, const ActQ& x, Act& y, const float* rowvec
     p.M = x.n * ho * wo; p.N = w.cout; p.K = x.cp * w.k * w.k;
     p.NB = x.n; p.Hs = x.h; p.Ws = x.w; p.Cin = x.cp; p.Ho = ho; p.Wo = wo;
     p.KH = w.k; p.KW = w.k; p.stride = stride; p.pad = pad; p.ups = ups;
-    p.ldc = y.stride(); p.ldr = resid ? resid->stride() : y.stride(); p.a_ld = x.cp; p.b_ld = p.K; p.rowvec_stride = 0; p.CS = 128;
+    p.ldc = y.stride(); p.ldr = resid ? resid->stride() : y.stride(); p.a_ld = x.cp; p.b_ld = p.K; p.rowvec_stride = rowvec_stride; p.CS = 128;
     launch_fp8(p, 2.0 * p.M * (double)p.N * w.cin * w.k * w.k);   // algorithmic (unpadded) work
 }
 
@@ -1805,14 +1812,10 @@ void Engine::launch_fp8(ConvGemm& p, double flops) {
     p.kt_per_split = (p.kt_total + splits - 1) / splits;
     splits = (p.kt_total + p.kt_per_split - 1) / p.kt_per_split;
     p.splits = splits;
-    p.resid_acc = 0;   // (as Engine::launch_gemm)
-    if (splits == 1 && (p.N % 8) == 0 && (p.ldc % 8) == 0) {
-        if ((opt_resid_acc_ & 1) && p.resid && (p.ldr % 4) == 0) p.resid_acc |= 1;
-        if ((opt_resid_acc_ & 2) && (p.bias || p.rowvec) && (p.rowvec_stride % 4) == 0) p.resid_acc |= 2;
-    }
+    set_resid_acc(p, splits == 1, true);   // (as Engine::launch_gemm)
     if (record_shapes_) {   // option dump_choices: the MXFP8 launches are listed with their own tag, so a test can pin WHICH layers run on fp8 operands
         char ck[128];
-        std::snprintf(ck, sizeof ck, "%d,%d,%d k%d s%d u%d W%d fp8 cfg=%d splits=%d", p.M, p.N, p.K, p.KH, p.stride, p.ups, p.Ws, cfg, splits);
+        std::snprintf(ck, sizeof ck, "%d,%d,%d k%d s%d u%d W%d fp8 cfg=%d splits=%d acc=%d", p.M, p.N, p.K, p.KH, p.stride, p.ups, p.Ws, cfg, splits, p.resid_acc);
         ++choice_counts_[ck];
     }
     // algorithmic bytes: e4m3 operands + one E8M0 scale byte per 32 elements, bf16 result
@@ -2561,11 +2564,44 @@ void Engine::op_layer_norm(const float* x, const float* gamma, const float* beta
     SDMI_HIP(launch_layer_norm(x, out, gamma, beta, rows, c, eps, stream_));
 }
 
+const float* Engine::stage_epi(std::unique_ptr<Buf>& b, const float* host, long long rows, int c, int ld, int dt, long long nchw_hw) {
+    if (ld < c) throw Error(SDMI_ERR_INVALID, "epilogue operand: row stride below the channel count");
+    const size_t es = dt ? 2 : 4, bytes = (size_t)rows * ld * es;
+    std::vector<unsigned char> img(bytes);
+    for (long long r = 0; r < rows; ++r)
+        for (int j = 0; j < ld; ++j) {
+            const float v = j >= c ? std::nanf("") : nchw_hw ? host[((r / nchw_hw) * c + j) * nchw_hw + r % nchw_hw] : host[r * c + j];
+            unsigned char* d = img.data() + ((size_t)r * ld + j) * es;
+            if (dt) {
+                uint32_t u;
+                std::memcpy(&u, &v, 4);
+                const uint16_t hb = std::isnan(v) ? (uint16_t)0x7FC0 : (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+                std::memcpy(d, &hb, 2);
+            } else std::memcpy(d, &v, 4);
+        }
+    b.reset(new Buf(this, bytes + 16));
+    unsigned char* dst = static_cast<unsigned char*>(b->p) + (opt_op_misalign_ ? es : 0);
+    SDMI_HIP(hipMemcpyAsync(dst, img.data(), bytes, hipMemcpyHostToDevice, stream_));
+    SDMI_HIP(hipStreamSynchronize(stream_));     // (img is a local)
+    return reinterpret_cast<const float*>(dst);
+}
+
 void Engine::op_conv2d(const float* x, const float* wt, const float* bias, int n, int cin, int h, int wd, int cout,
-                       int k, int stride, int pad, int ups, float* out) {
+                       int k, int stride, int pad, int ups, float* out, const EpiOps* epi) {
     if (!(k == 1 || k == 3) || pad != (k == 3 ? 1 : 0) || !(stride == 1 || stride == 2))
         throw Error(SDMI_ERR_UNSUPPORTED, "conv2d: only 3x3 pad 1 / 1x1 pad 0, stride 1|2 are on the hot path");
     if (!(cin % 32 == 0 || (cin < 32 && cin % 4 == 0))) throw Error(SDMI_ERR_UNSUPPORTED, "conv2d: Cin must be a multiple of 32, or < 32 and a multiple of 4");
+    if (epi && epi->temb_stride && epi->temb_stride < cout) throw Error(SDMI_ERR_INVALID, "conv2d: temb_stride below cout");
+    // the caller's time-embedding row (fp32, as the model's) and residual (in the output's storage type y.dt, rows ho x wo pixels): epi != null
+    std::unique_ptr<Buf> tb, rb;
+    const float* temb = (epi && epi->temb) ? stage_epi(tb, epi->temb, epi->temb_stride ? n : 1, cout, epi->temb_stride ? epi->temb_stride : cout, 0) : nullptr;
+    auto epi_resid = [&](const Act& y) {
+        Act r = y;
+        r.view = true; r.p3 = nullptr;
+        r.ld = epi->resid_ld ? epi->resid_ld : y.c;
+        r.p = const_cast<float*>(stage_epi(rb, epi->resid, y.rows(), y.c, r.ld, y.dt, (long long)y.h * y.w));
+        return r;
+    };
     if (fp8_ && opt_fp8_convs_ && k == 3 && stride == 1 && !ups && cin % 32 == 0 && cout % 8 == 0) {
         // precision = 2 mirrors the model's ResBlock convs: MXFP8 input (quantised here from the fp32 argument; the model
         // gets it from the fused GroupNorm), MXFP8 weight, bf16 output
@@ -2580,7 +2616,9 @@ void Engine::op_conv2d(const float* x, const float* wt, const float* bias, int n
         SDMI_HIP(launch_quantize_fp8(a32.p, q.q, q.s, a32.rows(), cin, stream_));
         release(a32);
         Act y = new_act(n, h, wd, cout, 1);
-        conv_fp8(w, q, y, nullptr, nullptr);
+        Act r;
+        if (epi && epi->resid) r = epi_resid(y);
+        conv_fp8(w, q, y, temb, r.p ? &r : nullptr, 1, 0, epi ? epi->temb_stride : 0);
         SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(y.p, out, n, cout, h, wd, stream_));
         release(q); release(y);
         return;
@@ -2603,13 +2641,19 @@ void Engine::op_conv2d(const float* x, const float* wt, const float* bias, int n
     Act y = new_act(n, ho, wo, cout, (bf16_ && cout > 4) ? 1 : 0);
     // option op_resid (tests): out = conv(x) + x through the GEMM's residual epilogue, where the shapes allow it
     const bool with_resid = opt_op_resid_ && cin == cout && stride == 1 && !ups && a.dt == y.dt;
-    conv(w, a, y, stride, ups, nullptr, 0, with_resid ? &a : nullptr);
+    Act r;
+    if (epi && epi->resid) r = epi_resid(y);
+    conv(w, a, y, stride, ups, temb, epi ? epi->temb_stride : 0, r.p ? &r : with_resid ? &a : nullptr);
     if (y.dt) SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(y.p, out, n, cout, ho, wo, stream_));
     else SDMI_HIP(launch_nhwc_to_nchw(y.p, out, n, cout, ho, wo, stream_));
     release(a); release(y);
 }
 
-void Engine::op_linear(const float* x, const float* wt, const float* bias, int rows, int cin, int cout, float* out) {
+void Engine::op_linear(const float* x, const float* wt, const float* bias, int rows, int cin, int cout, float* out, const EpiOps* epi) {
+    // the caller's residual (epi != null) in the storage type of the route below: bf16 for the bf16 / MXFP8 kernels, fp32 otherwise
+    const int rld = (epi && epi->resid) ? (epi->resid_ld ? epi->resid_ld : cout) : 0;
+    std::unique_ptr<Buf> rb;
+    auto epi_resid = [&](int dt) { return rld ? stage_epi(rb, epi->resid, rows, cout, rld, dt) : nullptr; };
     if (fp8_ && opt_fp8_ops_ && cin % 32 == 0 && cout % 8 == 0) {   // option fp8_ops (tests): the Linear layer as the fp8_linear path runs it
         const size_t kp = (size_t)(cin + 127) / 128 * 128;
         Buf xh(this, (size_t)rows * cin * 2), yh(this, (size_t)rows * cout * 2), w8(this, (size_t)cout * kp), s8(this, (size_t)cout * kp / 32);
@@ -2619,7 +2663,7 @@ void Engine::op_linear(const float* x, const float* wt, const float* bias, int r
         ActQ q = new_rowsq(rows, cin);
         quantize(xa, q);
         LinW lw; lw.cin = cin; lw.cout = cout; lw.dt = 1; lw.bias = const_cast<float*>(bias); lw.bt8 = w8.f(); lw.bs8 = s8.f();
-        gemm_fp8(q, lw, cout, yh.p, cout, nullptr, 0);
+        gemm_fp8(q, lw, cout, yh.p, cout, epi_resid(1), rld);
         SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(yh.p, out, rows, cout, 1, 1, stream_));
         release(q);
         return;
@@ -2630,14 +2674,16 @@ void Engine::op_linear(const float* x, const float* wt, const float* bias, int r
         SDMI_HIP(launch_pack_linear_weight_bf16(wt, bt.p, cin, cout, stream_));
         SDMI_HIP(launch_f32_to_bf16(x, xh.p, (long long)rows * cin, stream_));
         const bool with_resid = opt_op_resid_ && cin == cout;   // option op_resid (tests): out = x W + b + x through the residual epilogue
-        gemm(xh.f(), rows, bt.f(), bias, cin, cout, yh.f(), cout, with_resid ? xh.f() : nullptr, with_resid ? cin : 0, 1);
+        if (rld) gemm(xh.f(), rows, bt.f(), bias, cin, cout, yh.f(), cout, epi_resid(1), rld, 1);
+        else gemm(xh.f(), rows, bt.f(), bias, cin, cout, yh.f(), cout, with_resid ? xh.f() : nullptr, with_resid ? cin : 0, 1);
         SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(yh.p, out, rows, cout, 1, 1, stream_));
         return;
     }
     SDMI_HIP(launch_pack_linear_weight(wt, bt.f(), cin, cout, stream_));
     TempSplit planes(this, bt.f(), cout, cin);
     const bool with_resid = opt_op_resid_ && cin == cout;
-    gemm(x, rows, bt.f(), bias, cin, cout, out, cout, with_resid ? x : nullptr, with_resid ? cin : 0, 0);
+    if (rld) gemm(x, rows, bt.f(), bias, cin, cout, out, cout, epi_resid(0), rld, 0);
+    else gemm(x, rows, bt.f(), bias, cin, cout, out, cout, with_resid ? x : nullptr, with_resid ? cin : 0, 0);
 }
 
 void Engine::op_geglu_forward(const float* x, const float* wt, const float* bias, int rows, int cin, int hidden, float* out) {

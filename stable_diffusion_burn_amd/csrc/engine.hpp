@@ -172,9 +172,14 @@ public:
     void op_group_norm_fp8(const float* x, const float* gamma, const float* beta, int n, int c, int h, int w, int groups, float eps,
                            bool silu, float* out);
     void op_layer_norm(const float* x, const float* gamma, const float* beta, int rows, int c, float eps, float* out);
+    // the time-embedding row and residual of an operator-level conv2d / Linear given by the caller (tests: sdmi_op_conv2d_epilogue / sdmi_op_linear_epilogue), as
+    // HOST arrays: temb [n][cout] ([cout] with temb_stride 0: one row for the batch), resid of the output's shape (NCHW; [rows][cout] for Linear).  Staged by
+    // stage_epi in the layout the model's launches read: temb rows temb_stride floats apart, the residual as NHWC rows resid_ld (0: cout) elements apart
+    // in the output's storage type
+    struct EpiOps { const float* temb = nullptr; int temb_stride = 0; const float* resid = nullptr; int resid_ld = 0; };
     void op_conv2d(const float* x, const float* w, const float* bias, int n, int cin, int h, int wd, int cout, int k,
-                   int stride, int pad, int ups, float* out);
-    void op_linear(const float* x, const float* w, const float* bias, int rows, int cin, int cout, float* out);
+                   int stride, int pad, int ups, float* out, const EpiOps* epi = nullptr);
+    void op_linear(const float* x, const float* w, const float* bias, int rows, int cin, int cout, float* out, const EpiOps* epi = nullptr);
     void op_geglu(const float* proj, int rows, int hidden, float* out);
     void op_geglu_forward(const float* x, const float* wt, const float* bias, int rows, int cin, int hidden, float* out);
     void op_timestep_embedding(int t, int dim, float* out);
@@ -220,6 +225,10 @@ public:
         Buf& operator=(const Buf&) = delete;
         float* f() const { return reinterpret_cast<float*>(p); }
     };
+    // host [rows][c] (nchw_hw > 0: NCHW with that many pixels per sample, row r = pixel r of the flattened batch) -> a new device buffer of rows x ld
+    // elements, fp32 (dt 0) or bf16 rounded to nearest even (dt 1), the ld - c padding columns NaN; option op_misalign starts it one element past an
+    // aligned address.  Returns the first element.
+    const float* stage_epi(std::unique_ptr<Buf>& b, const float* host, long long rows, int c, int ld, int dt, long long nchw_hw = 0);
 
 private:
     void destroy() noexcept;
@@ -291,10 +300,11 @@ private:
     void release(ActQ& a);
     void group_norm_fp8(const NormW& w, const Act& x, ActQ& y, bool silu);
     // stride / ups as conv(); 3x3 (pad 1) or 1x1 (pad 0) -- whatever was packed as MXFP8 (ConvW::bt8)
-    void conv_fp8(const ConvW& w, const ActQ& x, Act& y, const float* rowvec, const Act* resid, int stride = 1, int ups = 0);
+    void conv_fp8(const ConvW& w, const ActQ& x, Act& y, const float* rowvec, const Act* resid, int stride = 1, int ups = 0, int rowvec_stride = 0);
     bool use_fp8(const ConvW& w, const Act& x) const;
     // option fp8_linear: the layers beyond the ResBlock 3x3 convolutions -- Linear layers, 1x1 / up / down convolutions
     bool use_fp8_wide(const float* bt8, long long rows) const { return fp8_ && opt_fp8_convs_ && opt_fp8_linear_ && bt8 && rows >= opt_fp8_min_rows_; }
+    void set_resid_acc(ConvGemm& p, bool eligible, bool resid_ok) const;          // ConvGemm::resid_acc of a launch (option resid_acc, strides, base alignment)
     void launch_fp8(ConvGemm& p, double flops);                                   // tile / split-K choice + launch (+ reduce) of conv_gemm_fp8x_kernel
     void gemm_fp8(const ActQ& x, const LinW& w, int n_rows_w, void* C, int ldc, const float* resid, int ldr);   // C[rows][n_rows_w] = x W^T + b (+ resid), bf16 out
     void conv_raw(const ConvW& w, const Act& x, Act& y, int stride, int ups);     // conv() or, at precision = 2, quantize() + conv_fp8()
@@ -404,6 +414,7 @@ private:
     int opt_attn_kv_splits_ = 0;     // fp32 attention: key slices + merge launch where the query-tile grid leaves CUs idle (Engine::attention): 0 = automatic, 1 = never, S = forced
     int opt_cfg_share_ = 1;          // sample_latent: the part of the UNet in front of the first cross attention is computed once for the two identical halves of a CFG step (unet_run)
     int opt_op_resid_ = 0;           // tests: op_conv2d / op_linear add their input as the residual (cin == cout) through the GEMM epilogue
+    int opt_op_misalign_ = 0;        // tests: stage_epi starts the device copies of bias, time-embedding row and residual one element past an aligned address
     int opt_fp8_ops_ = 0;            // tests: op_linear / op_layer_norm / op_geglu run the fp8_linear path's kernels (outputs dequantised)
     int opt_fp8_linear_ = 0;         // precision = 2: 0 (default: the accuracy budget of 6e-2 final-latent relative RMS) = MXFP8 on the ResBlock / ResnetBlock 3x3
                                      // convolutions only; 1 = also the transformer blocks' Linear layers and the 1x1 / up / down convolutions (8.1e-2)

@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvGemm p) {
     const float* slabs = p.slabs;
     float* C = p.C;
     const int HoWo = p.Ho * p.Wo;
-    const bool vec_ok = ((p.N & 3) == 0) && ((p.ldc & 3) == 0) && (!p.resid || (p.ldr & 3) == 0);
+    const bool vec_ok = splitk_reduce_vec(p, false);
     if (vec_ok) {
         const int n4 = p.N >> 2;
         const long long total = (long long)p.M * n4;              // 16-byte outputs
@@ -179,7 +179,7 @@ static const GemmTileInfo kTiles[kNumGemmTiles] = {
 const GemmTileInfo& gemm_tile_info(int cfg) { return kTiles[cfg]; }
 
 hipError_t launch_splitk_reduce(const ConvGemm& p, hipStream_t stream) {
-    const bool vec = ((p.N & 3) == 0) && ((p.ldc & 3) == 0) && (!p.resid || (p.ldr & 3) == 0);
+    const bool vec = splitk_reduce_vec(p, false);
     if (!vec && (p.C3 || !p.C)) return hipErrorInvalidValue;   // the plane output is part of the 16-byte path only
     const long long work = ((long long)p.M * p.N + 3) / 4;
     // lanes per output: enough threads to cover the chip (>= 256 K) while every lane still has two slabs to sum

@@ -306,8 +306,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_bf16_kernel(const ConvGemm 
     const unsigned short* Rh = reinterpret_cast<const unsigned short*>(p.resid);
     const long long total = (long long)p.M * p.N;
     // round 6: four outputs per thread (16-byte slab loads, two slices in flight), the bias / time-embedding row / residual requested in front of the slab loads;
-    // the same sums in the same order as the scalar form below (which stays for odd strides): bit-identical
-    if (((p.N | p.ldc | p.rowvec_stride) & 3) == 0 && (!p.resid || (p.ldr & 3) == 0)) {
+    // the same sums in the same order as the scalar form below (which stays for odd strides and unaligned operands: splitk_reduce_vec): bit-identical
+    if (splitk_reduce_vec(p, true)) {
         typedef float rf32x4 __attribute__((ext_vector_type(4)));
         typedef unsigned int ru32x2 __attribute__((ext_vector_type(2)));
         const int n4 = p.N >> 2;
@@ -420,7 +420,7 @@ hipError_t launch_conv_gemm_bf16(const ConvGemm& p, int cfg, hipStream_t stream)
 }
 
 hipError_t launch_splitk_reduce_bf16(const ConvGemm& p, hipStream_t stream) {
-    const bool vec = ((p.N | p.ldc | p.rowvec_stride) & 3) == 0 && (!p.resid || (p.ldr & 3) == 0);    // the kernel's 16-byte path: four outputs per thread
+    const bool vec = splitk_reduce_vec(p, true);    // the kernel's 16-byte path: four outputs per thread
     const long long work = (long long)p.M * p.N / (vec ? 4 : 1);
     int blocks = (int)((work + 255) / 256);
     if (blocks > 4096) blocks = 4096;

@@ -372,8 +372,9 @@ static int persistent_workgroups() {
     return n_cu[dev];
 }
 
-// the persistent kernel's epilogue mode for this launch, or -1: ConvGemm::variant bit 0, no split-K, more tiles than workgroups, no residual (that path of the
-// epilogue spills inside the tile loop) and the conditions under which gemm_epilogue_bf16 takes its 16-byte bf16 paths (checked here, compiled in there)
+// the persistent kernel's epilogue mode for this launch, or -1: ConvGemm::variant bit 0, no split-K, more tiles than workgroups, no residual for the epilogue to add
+// (that path spills inside the tile loop; a residual in the accumulators -- ConvGemm::resid_acc bit 0 -- takes the loop) and the conditions under which
+// gemm_epilogue_bf16 takes its 16-byte bf16 paths (checked here, compiled in there)
 int conv_gemm_bf16x_persistent_mode(const ConvGemm& p, int cfg) {
     if (!(p.variant & 1) || p.splits != 1 || cfg < 0 || cfg >= kNumGemmTilesX || p.out_mode == 1) return -1;
     // (round 6, measured and not kept -- profiles/r06z_*: sending launches of >= 8 k tiles to the staggered one-tile form instead of the tile loop: GEMM class 30.94 -> 31.10 ms)

@@ -131,7 +131,8 @@ __device__ __forceinline__ void gemm_epilogue_f32(const ConvGemm& p, epi_f32x4 (
     // time-embedding row is then a per-column term like the bias) needs no bounds check, no sample-index division per fragment group and no 64-bit address product per
     // store.  Every lane-derived address is computed once per tile -- one LDS write address, NI LDS read addresses, NI 32-bit offsets each for the output, the residual and
     // the planes -- against wave-uniform row pointers that advance by 16 rows per group; the residual of group mi + 1 is requested before group mi is stored.  The general
-    // form below executed ~3x the instructions per group and waited out every time-embedding load where it was issued.  Same values in the same order.
+    // form below executed ~3x the instructions per group and waited out every time-embedding load where it was issued.  Same values in the same order: acc + (bias + row)
+// (+ residual) in both forms.
     if (!(p.variant & 64) && vec_ok && m0 + BM <= p.M && n0 + BN <= p.N) {
         int smp0 = 0;
         bool one_smp = true;
@@ -263,9 +264,11 @@ __device__ __forceinline__ void gemm_epilogue_f32(const ConvGemm& p, epi_f32x4 (
                     const int n = nw0 + ni * 16 + g4 * 4;
                     f32x4 v = acc[mi][ni];
                     if (!split && n < p.N) {
-                        if (early) v += bias_v[ni];
-                        else if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + n);
-                        if (p.rowvec) v += *reinterpret_cast<const f32x4*>(p.rowvec + (long long)smp * p.rowvec_stride + n);
+                        // (bias + row first, as the lean form above sums them -- (acc + bias) + row differed from it in the last bit, test_epilogue_gpu.py)
+                        f32x4 cv = bias_v[ni];
+                        if (!early && p.bias) cv = *reinterpret_cast<const f32x4*>(p.bias + n);
+                        if (p.rowvec) cv += *reinterpret_cast<const f32x4*>(p.rowvec + (long long)smp * p.rowvec_stride + n);
+                        v += cv;
                     }
                     *reinterpret_cast<f32x4*>(scr + c15 * LDSW + ni * 16 + g4 * 4) = v;
                 }

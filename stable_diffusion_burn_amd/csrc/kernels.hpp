@@ -130,6 +130,13 @@ hipError_t launch_pack_conv_weight_bf16(const float* w_oihw, void* bt, int cout,
 hipError_t launch_pack_linear_weight_bf16(const float* w_in_out, void* bt, int cin, int cout, hipStream_t s);
 // sums split-K slabs in fixed order and applies the epilogue
 hipError_t launch_splitk_reduce(const ConvGemm& p, hipStream_t stream);
+// the 16-byte form of the split-K reduce kernels (four outputs per thread; bf16: launch_splitk_reduce_bf16): strides AND base addresses aligned for its vector
+// loads and stores -- the fp32 bias / time-embedding rows 16 bytes, the residual and the output 8 (bf16) or 16 bytes (fp32); otherwise the scalar form
+__host__ __device__ inline bool splitk_reduce_vec(const ConvGemm& p, bool bf16) {
+    const uintptr_t ra = bf16 ? 7 : 15, ca = (bf16 && p.out_mode != 1) ? 7 : 15;
+    return ((p.N | p.ldc | p.rowvec_stride) & 3) == 0 && (!p.resid || (p.ldr & 3) == 0) && (((uintptr_t)p.bias | (uintptr_t)p.rowvec) & 15) == 0 &&
+           ((uintptr_t)p.resid & ra) == 0 && ((uintptr_t)p.C & ca) == 0;
+}
 // weight packing (done once at load)
 hipError_t launch_pack_conv_weight(const float* w_oihw, float* bt, int cout, int cin, int kh, int kw, hipStream_t s);
 hipError_t launch_pack_linear_weight(const float* w_in_out, float* bt, int cin, int cout, hipStream_t s);

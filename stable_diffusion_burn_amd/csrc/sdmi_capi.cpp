@@ -558,6 +558,46 @@ int sdmi_op_conv2d(sdmi_ctx* ctx, const float* x, const float* weight, const flo
     });
 }
 
+int sdmi_op_conv2d_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, const float* temb, int32_t temb_stride,
+                            const float* resid, int32_t resid_ld, int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cout, int32_t k, int32_t stride,
+                            int32_t pad, int32_t upsample2x, float* out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (n <= 0 || cin <= 0 || h <= 0 || w <= 0 || cout <= 0 || stride <= 0 || temb_stride < 0 || resid_ld < 0) throw Error(SDMI_ERR_INVALID, "conv2d_epilogue: bad shape");
+        const int ups = upsample2x ? 1 : 0;
+        const int hin = h << ups, win = w << ups;
+        const int ho = (hin + 2 * pad - k) / stride + 1, wo = (win + 2 * pad - k) / stride + 1;
+        Engine::Call call(e);
+        DevIn dx(e, x, (size_t)n * cin * h * w * sizeof(float)), dw(e, weight, (size_t)cout * cin * k * k * sizeof(float));
+        std::unique_ptr<Engine::Buf> db;
+        const float* bias_d = bias ? e.stage_epi(db, bias, 1, cout, cout, 0) : nullptr;
+        Engine::EpiOps epi;
+        epi.temb = temb; epi.temb_stride = temb_stride; epi.resid = resid; epi.resid_ld = resid_ld;
+        DevOut dout(e, out, (size_t)n * cout * ho * wo * sizeof(float));
+        e.op_conv2d(dx.f(), dw.f(), bias_d, n, cin, h, w, cout, k, stride, pad, ups, dout.f(), &epi);
+        call.finish();
+        dout.fetch();
+    });
+}
+
+int sdmi_op_linear_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, const float* resid, int32_t resid_ld, int32_t rows,
+                            int32_t cin, int32_t cout, float* out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (rows <= 0 || cin <= 0 || cout <= 0 || resid_ld < 0) throw Error(SDMI_ERR_INVALID, "linear_epilogue: bad shape");
+        Engine::Call call(e);
+        DevIn dx(e, x, (size_t)rows * cin * sizeof(float)), dw(e, weight, (size_t)cin * cout * sizeof(float));
+        std::unique_ptr<Engine::Buf> db;
+        const float* bias_d = bias ? e.stage_epi(db, bias, 1, cout, cout, 0) : nullptr;
+        Engine::EpiOps epi;
+        epi.resid = resid; epi.resid_ld = resid_ld;
+        DevOut dout(e, out, (size_t)rows * cout * sizeof(float));
+        e.op_linear(dx.f(), dw.f(), bias_d, rows, cin, cout, dout.f(), &epi);
+        call.finish();
+        dout.fetch();
+    });
+}
+
 int sdmi_op_geglu_forward(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, int32_t rows, int32_t cin,
                           int32_t hidden, float* out) {
     return guarded([&] {

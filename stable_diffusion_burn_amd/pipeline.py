@@ -493,6 +493,48 @@ class StableDiffusion:
                                        _fp(out)))
         return out
 
+    def op_conv2d_epilogue(self, x, weight, bias=None, temb=None, resid=None, stride=1, upsample2x=False, temb_stride=None, resid_ld=0):
+        """op_conv2d + temb[sample] + resid through the GEMM epilogue (tests).  temb: [cout] (one row for the batch) or [n, cout]; resid: the
+        output's shape.  temb_stride (default: 0 for one row, cout per sample) and resid_ld (0: cout) are the strides the engine keeps them at."""
+        x = _f32(x)
+        weight = _f32(weight)
+        n, cin, h, w = x.shape
+        cout, cin2, k, k2 = weight.shape
+        if cin2 != cin or k != k2:
+            raise ValueError("conv2d: weight shape does not match input")
+        pad = 1 if k == 3 else 0
+        ups = 1 if upsample2x else 0
+        ho = ((h << ups) + 2 * pad - k) // stride + 1
+        wo = ((w << ups) + 2 * pad - k) // stride + 1
+        out = np.empty((n, cout, ho, wo), dtype=np.float32)
+        b = None if bias is None else _f32(bias, (cout,))
+        t = None if temb is None else _f32(temb)
+        if t is not None:
+            if t.shape not in ((cout,), (n, cout)):
+                raise ValueError("conv2d_epilogue: temb must be [cout] or [n, cout]")
+            if temb_stride is None:
+                temb_stride = 0 if t.ndim == 1 else cout
+            if (temb_stride == 0) != (t.ndim == 1):
+                raise ValueError("conv2d_epilogue: temb_stride 0 means one row for the batch")
+        r = None if resid is None else _f32(resid, (n, cout, ho, wo))
+        check(self._lib.sdmi_op_conv2d_epilogue(self._ctx, _fp(x), _fp(weight), None if b is None else _fp(b), None if t is None else _fp(t),
+                                                temb_stride or 0, None if r is None else _fp(r), resid_ld, n, cin, h, w, cout, k, stride, pad, ups,
+                                                _fp(out)))
+        return out
+
+    def op_linear_epilogue(self, x, weight, bias=None, resid=None, resid_ld=0):
+        """op_linear + resid [rows, cout] through the GEMM epilogue (tests); resid_ld (0: cout) is the row stride the engine keeps it at."""
+        x = _f32(x)
+        weight = _f32(weight)
+        cin, cout = weight.shape
+        rows = x.size // cin
+        out = np.empty(x.shape[:-1] + (cout,), dtype=np.float32)
+        b = None if bias is None else _f32(bias, (cout,))
+        r = None if resid is None else _f32(resid, out.shape)
+        check(self._lib.sdmi_op_linear_epilogue(self._ctx, _fp(x), _fp(weight), None if b is None else _fp(b), None if r is None else _fp(r),
+                                                resid_ld, rows, cin, cout, _fp(out)))
+        return out
+
     def op_geglu_forward(self, x, weight_in_out, bias, hidden):
         """GEGLU::forward (unet/mod.rs:579-591): x [rows, cin] -> [rows, hidden]."""
         x = _f32(x)

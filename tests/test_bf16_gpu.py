@@ -337,7 +337,7 @@ def test_geglu_forward_bf16(ops16, rows, cin, hidden, fuse):
 # ---- round 5: the persistent tile loop (gemm_bf16x_variant bit 0, the default) ------------------------------------------------------------------------------------
 # It keeps every product, its order and the single rounding: results must be BIT-IDENTICAL to variant 0 (one tile per workgroup), which the tests above hold against
 # the oracle.  The shapes have more tiles than the chip has CUs (the persistent form's condition), ragged M, N tails, one to twenty k tiles, padding taps in a tile's
-# FIRST k tile (issue_first); with a residual the launch stays on the one-tile form (checked to be a no-op here).  (Round 5 also measured an epilogue without the LDS
+# FIRST k tile (issue_first); a residual launch takes the loop too when its residual is in the accumulators (resid_acc bit 0, the default; round 6), else the one-tile form.  (Round 5 also measured an epilogue without the LDS
 # transpose -- v_permlane16_swap pairs, 64-byte row pieces -- bit-identical and 4 ... 7 % slower per launch: removed, profiles/r05a_*.)
 def _variants(ops16, fn, what, variants=(1, 4, 5, 8, 13)):     # bit 0: persistent tile loop (round 5); bit 2: staggered DMA issue of the two wave groups (round 6); 5 = the default; bit 3: the GENERAL epilogue on interior tiles too (round 6: variant 0 and the default take the lean one)
     try:
