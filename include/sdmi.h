@@ -329,6 +329,11 @@ int sdmi_op_linear_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, 
                             int32_t resid_ld, int32_t rows, int32_t cin, int32_t cout, float* out);
 /* GEGLU gate (unet/mod.rs:579-591): proj [rows,2*hidden] -> out [rows,hidden] = a*gelu_erf(gate). */
 int sdmi_op_geglu(sdmi_ctx* ctx, const float* proj, int32_t rows, int32_t hidden, float* out);
+/* qkv_attention with a per-sample key count (the CFG batch's cross attention; for tests): q [n,nq,n_state],
+ * k,v [n,nk,n_state], kv_len [n] with 1 <= kv_len[b] <= nk; row b attends to keys 0 .. kv_len[b]-1 only and never reads
+ * the others. No mask. out [n,nq,n_state]. */
+int sdmi_op_qkv_attention_ragged(sdmi_ctx* ctx, const float* q, const float* k, const float* v, const int32_t* kv_len,
+                                 int32_t n, int32_t nq, int32_t nk, int32_t n_state, int32_t n_head, float* out);
 /* timestep_embedding (unet/mod.rs:19-30): out [dim] for timestep t. */
 /* GEGLU::forward (src/model/unet/mod.rs:579-591): x [rows, cin], weight [cin, 2*hidden] (Burn Linear layout), bias
  * [2*hidden] or NULL -> out [rows, hidden] = a * gelu(b), a | b = the halves of x W + bias.  One fused kernel when the

@@ -96,6 +96,7 @@ SIGNATURES = {
     "sdmi_op_linear_epilogue": (C.c_int, [_CTX, _F, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),
     "sdmi_op_geglu_forward": (C.c_int, [_CTX, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, _F]),
     "sdmi_op_geglu": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F]),
+    "sdmi_op_qkv_attention_ragged": (C.c_int, [_CTX, _F, _F, _F, _I32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),
     "sdmi_op_timestep_embedding": (C.c_int, [_CTX, C.c_int32, C.c_int32, _F]),
     "sdmi_set_option": (C.c_int, [_CTX, C.c_char_p, C.c_char_p]),
     "sdmi_last_call_stats": (C.c_int, [_CTX, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

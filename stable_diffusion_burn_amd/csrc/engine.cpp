@@ -1635,9 +1635,10 @@ void Engine::attention(const float* q, int ldq, long long q_bs, const float* k, 
     if (mask) throw Error(SDMI_ERR_UNSUPPORTED, "attention: additive mask is only supported for head dims 40/80/160");
     if (d_head % 32) throw Error(SDMI_ERR_UNSUPPORTED, "attention: head dim must be 40/80/160 or a multiple of 32");
     if (dt && (d_head % 64)) throw Error(SDMI_ERR_UNSUPPORTED, "bf16 attention (unfused path): head dim must be a multiple of 64");
+    for (int b = 0; b < n; ++b)   // every sample's key count before the first launch
+        if ((kv_len_host ? kv_len_host[b] : nk) % (dt ? 64 : 32)) throw Error(SDMI_ERR_UNSUPPORTED, "attention (unfused path): key count must be a multiple of 32 (64 for bf16)");
     for (int b = 0; b < n; ++b) {
         const int nkb = kv_len_host ? kv_len_host[b] : nk;
-        if (nkb % (dt ? 64 : 32)) throw Error(SDMI_ERR_UNSUPPORTED, "attention (unfused path): key count must be a multiple of 32 (64 for bf16)");
         Buf s(this, (size_t)nq * nkb * sizeof(float));            // scores stay fp32 in both precisions
         Buf pb(this, dt ? (size_t)nq * nkb * 2 : 256);             // bf16 probabilities (precision = 1)
         Buf vt(this, (size_t)d_head * nkb * (dt ? 2 : 4));
@@ -2463,9 +2464,20 @@ void Engine::decode_latent_dev(const float* latent_nchw, int n, float in_scale, 
 }
 
 void Engine::qkv_attention_dev(const float* q, const float* k, const float* v, const float* mask, int mask_ld, int n,
-                               int nq, int nk, int n_state, int n_head, float* out) {
+                               int nq, int nk, int n_state, int n_head, float* out, const int* kv_len_host) {
     if (n <= 0 || nq <= 0 || nk <= 0 || n_head <= 0 || n_state % n_head) throw Error(SDMI_ERR_INVALID, "qkv_attention: bad shape");
     if (mask && mask_ld < nk) throw Error(SDMI_ERR_INVALID, "qkv_attention: mask_ld < nk");
+    if (kv_len_host)
+        for (int b = 0; b < n; ++b)
+            if (kv_len_host[b] < 1 || kv_len_host[b] > nk) throw Error(SDMI_ERR_INVALID, "qkv_attention: kv_len entries must lie in 1 .. nk");
+    // per-sample key counts: a device copy for the kernels, the host array for the unfused path's per-sample loop (as unet_prepare keeps them)
+    std::unique_ptr<Buf> kl;
+    const int* kv_len_dev = nullptr;
+    if (kv_len_host) {
+        kl.reset(new Buf(this, (size_t)n * sizeof(int)));
+        SDMI_HIP(hipMemcpyAsync(kl->p, kv_len_host, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream_));
+        kv_len_dev = reinterpret_cast<const int*>(kl->p);
+    }
     const long long qe = (long long)n * nq * n_state, ke = (long long)n * nk * n_state;
     if (bf16_ && !mask) {  // precision = 1: the boundary is fp32, the kernel sees bf16 tensors
         Buf qh(this, qe * 2), kh(this, ke * 2), vh(this, ke * 2), oh(this, qe * 2);
@@ -2476,7 +2488,7 @@ void Engine::qkv_attention_dev(const float* q, const float* k, const float* v, c
         SDMI_HIP(launch_f32_to_bf16(v, vh.p, ke, stream_));
         attention(qh.f(), n_state, (long long)nq * n_state, kh.f(), n_state, (long long)nk * n_state, vh.f(), n_state,
                   (long long)nk * n_state, oh.f(), n_state, (long long)nq * n_state, n, nq, nk, n_head, n_state / n_head,
-                  nullptr, nullptr, nullptr, 0, 1, nullptr, q_prescaled(1, dh));
+                  kv_len_dev, kv_len_host, nullptr, 0, 1, nullptr, q_prescaled(1, dh));
         SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(oh.p, out, (int)((long long)n * nq), n_state, 1, 1, stream_));
         return;
     }
@@ -2484,13 +2496,13 @@ void Engine::qkv_attention_dev(const float* q, const float* k, const float* v, c
         Buf o3(this, (size_t)n * nq * (n_state / 32) * 192);
         attention(q, n_state, (long long)nq * n_state, k, n_state, (long long)nk * n_state, v, n_state,
                   (long long)nk * n_state, nullptr, n_state, (long long)nq * n_state, n, nq, nk, n_head, n_state / n_head,
-                  nullptr, nullptr, mask, mask_ld, 0, o3.p);
+                  kv_len_dev, kv_len_host, mask, mask_ld, 0, o3.p);
         SDMI_HIP(launch_join3_rows(o3.p, out, (long long)n * nq, n_state, (long long)(n_state / 32) * 192, n_state, stream_));
         return;
     }
     attention(q, n_state, (long long)nq * n_state, k, n_state, (long long)nk * n_state, v, n_state,
               (long long)nk * n_state, out, n_state, (long long)nq * n_state, n, nq, nk, n_head, n_state / n_head,
-              nullptr, nullptr, mask, mask_ld, 0);
+              kv_len_dev, kv_len_host, mask, mask_ld, 0);
 }
 
 // =============================================================================

@@ -163,8 +163,9 @@ public:
     void img2img_image_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps,
                            double strength, const uint8_t* init_rgb, const float* mask, const float* noise, uint64_t seed, float* latent_out);
     void decode_latent_dev(const float* latent_nchw, int n, float in_scale, float* img_nchw, uint8_t* rgb_u8);
+    // kv_len_host: null, or a HOST array [n] of per-sample key counts (1 .. nk; the CFG batch's cross attention, Engine::attention's kv_len)
     void qkv_attention_dev(const float* q, const float* k, const float* v, const float* mask, int mask_ld, int n,
-                           int nq, int nk, int n_state, int n_head, float* out);
+                           int nq, int nk, int n_state, int n_head, float* out, const int* kv_len_host = nullptr);
 
     // operator-level (device pointers, reference layouts)
     void op_group_norm(const float* x, const float* gamma, const float* beta, int n, int c, int h, int w, int groups,

@@ -492,6 +492,24 @@ int sdmi_qkv_attention(sdmi_ctx* ctx, const float* q, const float* k, const floa
     });
 }
 
+int sdmi_op_qkv_attention_ragged(sdmi_ctx* ctx, const float* q, const float* k, const float* v, const int32_t* kv_len,
+                                 int32_t n, int32_t nq, int32_t nk, int32_t n_state, int32_t n_head, float* out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (n <= 0 || nq <= 0 || nk <= 0 || n_state <= 0) throw Error(SDMI_ERR_INVALID, "qkv_attention_ragged: bad shape");
+        if (!kv_len) throw Error(SDMI_ERR_INVALID, "qkv_attention_ragged: kv_len is NULL");
+        for (int32_t b = 0; b < n; ++b)
+            if (kv_len[b] < 1 || kv_len[b] > nk) throw Error(SDMI_ERR_INVALID, "qkv_attention_ragged: kv_len[" + std::to_string(b) + "] = " + std::to_string(kv_len[b]) + " outside 1 .. nk");
+        const size_t qb = (size_t)n * nq * n_state * sizeof(float), kb = (size_t)n * nk * n_state * sizeof(float);
+        Engine::Call call(e);
+        DevIn dq(e, q, qb), dk(e, k, kb), dv(e, v, kb);
+        DevOut dout(e, out, qb);
+        e.qkv_attention_dev(dq.f(), dk.f(), dv.f(), nullptr, 0, n, nq, nk, n_state, n_head, dout.f(), kv_len);
+        call.finish();
+        dout.fetch();
+    });
+}
+
 // ---- operator-level entry points -----------------------------------------------------------
 int sdmi_op_group_norm(sdmi_ctx* ctx, const float* x, const float* gamma, const float* beta, int32_t n, int32_t c,
                        int32_t h, int32_t w, int32_t n_group, float eps, int32_t fuse_silu, float* out) {

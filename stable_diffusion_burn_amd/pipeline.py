@@ -571,6 +571,24 @@ class StableDiffusion:
                                            0 if m is None else m.shape[1], n, nq, nk, c, n_head, _fp(out)))
         return out
 
+    def qkv_attention_ragged(self, q, k, v, kv_len, n_head: int):
+        """qkv_attention without a mask where row b of the batch attends to its first kv_len[b] keys only (the CFG batch's cross
+        attention; tests): q [n,nq,c], k,v [n,nk,c], kv_len [n] or None (refused by the library, as are entries outside 1 .. nk)."""
+        q, k, v = _f32(q), _f32(k), _f32(v)
+        n, nq, c = q.shape
+        nk = k.shape[1]
+        if k.shape != (n, nk, c) or v.shape != (n, nk, c):
+            raise ValueError("qkv_attention_ragged: q/k/v shapes disagree")
+        kl = None
+        if kv_len is not None:
+            kl = np.ascontiguousarray(kv_len, dtype=np.int32)
+            if kl.shape != (n,):
+                raise ValueError(f"qkv_attention_ragged: kv_len must have shape ({n},), got {kl.shape}")
+        out = np.empty_like(q)
+        check(self._lib.sdmi_op_qkv_attention_ragged(self._ctx, _fp(q), _fp(k), _fp(v), None if kl is None else kl.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     n, nq, nk, c, n_head, _fp(out)))
+        return out
+
 
 def _make_cfg(lib, config: ModelConfig, device: int = 0) -> SdmiConfig:
     cfg = SdmiConfig()

@@ -107,7 +107,8 @@ def test_unet_forward_batch_independent(sd_tiny, tiny_dims):
 
 
 # (3, ..): 1000 / 3 = 333 -> t = 999, 666, 333, 0: FOUR iterations (quirk Q5, step_by)
-@pytest.mark.parametrize("n_steps,scale,T,Tu", [(1, 1.0, 7, 7), (4, 7.5, 7, 2), (5, 7.5, 3, 6), (3, 7.5, 7, 2)])
+# T / Tu of 65, 77 and 129: per-row key counts that cross the attention kernels' 32- / 64-key tiles (K / V padded to max(T, Tu))
+@pytest.mark.parametrize("n_steps,scale,T,Tu", [(1, 1.0, 7, 7), (4, 7.5, 7, 2), (5, 7.5, 3, 6), (3, 7.5, 7, 2), (3, 7.5, 77, 2), (3, 7.5, 65, 129)])
 def test_sample_latent(sd_tiny, synth, tiny_dims, n_steps, scale, T, Tu):
     """sample_latent (stablediffusion/mod.rs:102-160): DDIM + CFG, Tc != Tu, config-1 style 1 step."""
     d = tiny_dims
