@@ -327,6 +327,40 @@ int sdmi_op_conv2d_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, 
 /* sdmi_op_linear + resid [rows,cout] (NULL: none), kept as rows resid_ld (0: cout) elements apart like sdmi_op_conv2d_epilogue's. */
 int sdmi_op_linear_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, const float* resid,
                             int32_t resid_ld, int32_t rows, int32_t cin, int32_t cout, float* out);
+/* ---- the same operators on channel-slice VIEWS (no reference counterpart; for tests) ----
+ * The UNet realises Tensor::cat (unet/mod.rs:134) without a copy: the input of an output block is ONE buffer [x channels | skip channels], its
+ * producers write channel slices of it and the consumers of a skip read one.  These entries run the operator the same way: the engine allocates
+ * the parent buffers, cuts them with its own slice (row stride = the parent's width, base advanced by the offset) and calls the routines the model
+ * calls.  Input: x occupies columns [in_off, in_off + cin) of a parent in_ld (>= cin) channels wide whose other columns hold in_fill (NaN in the
+ * tests).  Output: the result goes to columns [out_off, out_off + cout) of a parent out_ld wide; the caller passes that parent PREFILLED as
+ * NHWC rows [pixels][out_ld] and gets the whole of it back (through the parent's storage type: bf16 at precision >= 1, when cout > 4), so the
+ * columns next to the slice are the caller's to judge.  in_planes / out_planes (precision 0): how the parent exists -- 0 or 1 fp32, 2 the three
+ * bf16 planes only, 3 both (cuts on multiples of 32 channels); a plane parent is returned joined (exact).  A view with ld < c, off < 0 or
+ * off + c > ld is SDMI_ERR_INVALID before anything is launched; a cut the engine's slice refuses (planes off a multiple of 32 channels, a base
+ * off a 16-byte boundary) is its SDMI_ERR_STATE.  On an error the parent still comes back as the device left it. */
+typedef struct sdmi_op_view {
+    int32_t in_ld, in_off;
+    int32_t out_ld, out_off;
+    float in_fill;
+    int32_t in_planes, out_planes;
+} sdmi_op_view;
+/* sdmi_op_conv2d_epilogue on views: x [n,cin,h,w]; parent [n*ho*wo, out_ld] in and out; parent_planes (NULL unless out_planes = 3): the joined
+ * plane copy of the parent, parent then being the fp32 copy. */
+int sdmi_op_conv2d_view(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, const float* temb, int32_t temb_stride,
+                        const float* resid, int32_t resid_ld, int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cout, int32_t k,
+                        int32_t stride, int32_t pad, int32_t upsample2x, const sdmi_op_view* view, float* parent, float* parent_planes);
+/* sdmi_op_linear_epilogue writing a slice (the engine's Linear reads dense rows: in_ld = cin, in_off = 0): parent [rows, out_ld] in and out. */
+int sdmi_op_linear_view(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, const float* resid, int32_t resid_ld,
+                        int32_t rows, int32_t cin, int32_t cout, const sdmi_op_view* view, float* parent);
+/* GroupNorm (32 groups) reading a slice (in_ld, in_off, in_fill, in_planes of view): x, out [n,c,h,w].  form 0: the context's GroupNorm (fp32 /
+ * bf16), 1: the plane-writing form (precision 0), 2: MXFP8 output, dequantised (precision 2). */
+int sdmi_op_group_norm_view(sdmi_ctx* ctx, const float* x, const float* gamma, const float* beta, int32_t n, int32_t c, int32_t h, int32_t w,
+                            int32_t n_group, float eps, int32_t fuse_silu, const sdmi_op_view* view, int32_t form, float* out);
+/* A block boundary: conv3x3(x, w_skip) -> channels [cx, cx + cskip), conv3x3(x, w_x) -> channels [0, cx) of one buffer, GroupNorm(+SiLU) over
+ * all cx + cskip.  dense = 0: the convolutions write slices (the model's way); 1: dense results joined by a copy.  out [n,cx+cskip,h,w]. */
+int sdmi_op_cat_chain(sdmi_ctx* ctx, const float* x, const float* w_x, const float* b_x, const float* w_skip, const float* b_skip,
+                      const float* gamma, const float* beta, int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cx, int32_t cskip,
+                      float eps, int32_t fuse_silu, int32_t dense, float* out);
 /* GEGLU gate (unet/mod.rs:579-591): proj [rows,2*hidden] -> out [rows,hidden] = a*gelu_erf(gate). */
 int sdmi_op_geglu(sdmi_ctx* ctx, const float* proj, int32_t rows, int32_t hidden, float* out);
 /* qkv_attention with a per-sample key count (the CFG batch's cross attention; for tests): q [n,nq,n_state],

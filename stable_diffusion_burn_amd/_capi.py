@@ -30,7 +30,14 @@ class SdmiConfig(C.Structure):
     ]
 
 
+class SdmiOpView(C.Structure):
+    """sdmi_op_view: where an operator's input and output sit inside wider parent buffers (sdmi_op_*_view; tests)"""
+    _fields_ = [("in_ld", C.c_int32), ("in_off", C.c_int32), ("out_ld", C.c_int32), ("out_off", C.c_int32), ("in_fill", C.c_float),
+                ("in_planes", C.c_int32), ("out_planes", C.c_int32)]
+
+
 _F = C.POINTER(C.c_float)
+_VIEW = C.POINTER(SdmiOpView)
 _U8 = C.POINTER(C.c_uint8)
 _CTX = C.c_void_p
 _TOK = C.c_void_p
@@ -94,6 +101,12 @@ SIGNATURES = {
     "sdmi_op_conv2d_epilogue": (C.c_int, [_CTX, _F, _F, _F, _F, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_int32, _F]),
     "sdmi_op_linear_epilogue": (C.c_int, [_CTX, _F, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),
+    "sdmi_op_conv2d_view": (C.c_int, [_CTX, _F, _F, _F, _F, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, _VIEW, _F, _F]),
+    "sdmi_op_linear_view": (C.c_int, [_CTX, _F, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VIEW, _F]),
+    "sdmi_op_group_norm_view": (C.c_int, [_CTX, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _VIEW, C.c_int32, _F]),
+    "sdmi_op_cat_chain": (C.c_int, [_CTX, _F, _F, _F, _F, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                    C.c_int32, _F]),
     "sdmi_op_geglu_forward": (C.c_int, [_CTX, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, _F]),
     "sdmi_op_geglu": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F]),
     "sdmi_op_qkv_attention_ragged": (C.c_int, [_CTX, _F, _F, _F, _I32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),

@@ -1004,6 +1004,8 @@ void Engine::release(Act& a) {
 
 Act Engine::slice(const Act& parent, int c_off, int c) {
     if (c_off < 0 || c <= 0 || c_off + c > parent.c || parent.view) throw Error(SDMI_ERR_STATE, "slice: bad channel range");
+    // every kernel that reads or writes a view takes its 16-byte forms from the strides alone (vec_ok, the GroupNorm / quantiser loads, the DMA gather): the cut keeps the base on 16 bytes
+    if (((size_t)c_off * (parent.dt ? 2 : 4)) % 16) throw Error(SDMI_ERR_STATE, "slice: the cut must start on a 16-byte boundary");
     Act a = parent;
     a.p = parent.p ? adv(parent.p, c_off, parent.dt) : nullptr;
     if (parent.p3) {
@@ -2696,6 +2698,212 @@ void Engine::op_linear(const float* x, const float* wt, const float* bias, int r
     const bool with_resid = opt_op_resid_ && cin == cout;
     if (rld) gemm(x, rows, bt.f(), bias, cin, cout, out, cout, epi_resid(0), rld, 0);
     else gemm(x, rows, bt.f(), bias, cin, cout, out, cout, with_resid ? x : nullptr, with_resid ? cin : 0, 0);
+}
+
+// ---- the same operators on channel-slice views (tests: sdmi_op_*_view) -------------------------------------------------------------------------------
+void Engine::check_view(const sdmi_op_view& v, int cin, int cout) {
+    if (v.in_ld < cin || v.in_off < 0 || v.in_off + cin > v.in_ld || v.out_ld < cout || v.out_off < 0 || v.out_off + cout > v.out_ld ||
+        v.in_planes < 0 || v.in_planes > 3 || v.out_planes < 0 || v.out_planes > 3)
+        throw Error(SDMI_ERR_INVALID, "view: need 0 <= off, off + c <= ld and planes in 0 .. 3");
+}
+
+void Engine::op_conv2d_view(const float* xp, const float* wt, const float* bias, int n, int cin, int h, int wd, int cout, int k, int stride, int pad, int ups,
+                            const sdmi_op_view& v, const EpiOps* epi, float* yp, float* yp3) {
+    check_view(v, cin, cout);
+    if (!(k == 1 || k == 3) || pad != (k == 3 ? 1 : 0) || !(stride == 1 || stride == 2))
+        throw Error(SDMI_ERR_UNSUPPORTED, "conv2d: only 3x3 pad 1 / 1x1 pad 0, stride 1|2 are on the hot path");
+    if (!(cin % 32 == 0 || (cin < 32 && cin % 4 == 0))) throw Error(SDMI_ERR_UNSUPPORTED, "conv2d: Cin must be a multiple of 32, or < 32 and a multiple of 4");
+    if (epi && epi->temb_stride && epi->temb_stride < cout) throw Error(SDMI_ERR_INVALID, "conv2d: temb_stride below cout");
+    const bool q8 = fp8_ && opt_fp8_convs_ && k == 3 && stride == 1 && !ups && cin % 32 == 0 && cout % 8 == 0;   // op_conv2d's MXFP8 route
+    const int wdt = (bf16_ && cin % 64 == 0) ? 1 : 0;
+    if (!q8 && bf16_ && !wdt && cin >= 32) throw Error(SDMI_ERR_UNSUPPORTED, "bf16 conv2d: Cin must be a multiple of 64 (or < 32)");
+    const int xdt = q8 ? 1 : wdt, ydt = q8 ? 1 : ((bf16_ && cout > 4) ? 1 : 0);
+    const int hin = h << ups, win = wd << ups;
+    const int ho = (hin + 2 * pad - k) / stride + 1, wo = (win + 2 * pad - k) / stride + 1;
+    if ((xdt && v.in_planes > 1) || (ydt && v.out_planes > 1)) throw Error(SDMI_ERR_INVALID, "view: planes are an fp32 format");
+    // the two parents, as unet_run allocates the input of an output block
+    Act a = (!xdt && v.in_planes > 1) ? new_act3(n, h, wd, v.in_ld, v.in_planes) : new_act(n, h, wd, v.in_ld, xdt);
+    if (xdt) SDMI_HIP(launch_f32_to_bf16(xp, a.p, a.rows() * v.in_ld, stream_));
+    else {
+        if (a.p) SDMI_HIP(hipMemcpyAsync(a.p, xp, a.bytes(), hipMemcpyDeviceToDevice, stream_));
+        if (a.p3) SDMI_HIP(launch_split3_rows(xp, a.p3, a.rows(), v.in_ld, v.in_ld, a.ld3, stream_));
+    }
+    Act y = (!ydt && v.out_planes > 1) ? new_act3(n, ho, wo, v.out_ld, v.out_planes) : new_act(n, ho, wo, v.out_ld, ydt);
+    if (ydt) SDMI_HIP(launch_f32_to_bf16(yp, y.p, y.rows() * v.out_ld, stream_));
+    else {
+        if (y.p) SDMI_HIP(hipMemcpyAsync(y.p, yp, y.bytes(), hipMemcpyDeviceToDevice, stream_));
+        if (y.p3) SDMI_HIP(launch_split3_rows(yp, y.p3, y.rows(), v.out_ld, v.out_ld, y.ld3, stream_));
+    }
+    // the WHOLE parent goes back: the caller judges the columns next to the slice (after a refused launch too: what it left behind)
+    auto give_back = [&] {
+        if (ydt) SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(y.p, yp, (int)y.rows(), v.out_ld, 1, 1, stream_));
+        else {
+            if (y.p) SDMI_HIP(hipMemcpyAsync(yp, y.p, y.bytes(), hipMemcpyDeviceToDevice, stream_));
+            if (y.p3) SDMI_HIP(launch_join3_rows(y.p3, y.p ? yp3 : yp, y.rows(), v.out_ld, y.ld3, v.out_ld, stream_));
+        }
+    };
+    try {
+        Act xs = slice(a, v.in_off, cin), ys = slice(y, v.out_off, cout);
+        std::unique_ptr<Buf> tb, rb;
+        const float* temb = (epi && epi->temb) ? stage_epi(tb, epi->temb, epi->temb_stride ? n : 1, cout, epi->temb_stride ? epi->temb_stride : cout, 0) : nullptr;
+        Act r;
+        if (epi && epi->resid) {
+            if (!ys.p) throw Error(SDMI_ERR_INVALID, "view: a residual needs the output as fp32");
+            r = ys;
+            r.view = true; r.p3 = nullptr;
+            r.ld = epi->resid_ld ? epi->resid_ld : cout;
+            r.p = const_cast<float*>(stage_epi(rb, epi->resid, ys.rows(), cout, r.ld, ydt, (long long)ho * wo));
+        }
+        if (q8) {
+            const int cp = (cin + 127) / 128 * 128;
+            ConvW w; w.cin = cin; w.cout = cout; w.k = 3; w.dt = 1; w.bias = const_cast<float*>(bias);
+            Buf bt8(this, (size_t)cout * cp * 9), bs8(this, (size_t)cout * cp * 9 / 32);
+            SDMI_HIP(launch_pack_conv_weight_fp8(wt, bt8.p, bs8.p, cout, cin, 3, 3, stream_));
+            w.bt8 = bt8.f(); w.bs8 = bs8.f();
+            ActQ q = new_actq(n, h, wd, cin);
+            quantize(xs, q);                      // the bf16 slice -> MXFP8, as res_block's shortcut and conv_raw do
+            conv_fp8(w, q, ys, temb, r.p ? &r : nullptr, 1, 0, epi ? epi->temb_stride : 0);
+            release(q);
+        } else {
+            ConvW w; w.cin = cin; w.cout = cout; w.k = k; w.dt = wdt;
+            Buf bt(this, (size_t)cout * cin * k * k * 4);
+            if (w.dt) SDMI_HIP(launch_pack_conv_weight_bf16(wt, bt.p, cout, cin, k, k, stream_));
+            else SDMI_HIP(launch_pack_conv_weight(wt, bt.f(), cout, cin, k, k, stream_));
+            TempSplit planes(this, bt.f(), w.dt ? 0 : cout, (long long)cin * k * k);
+            w.bt = bt.f(); w.bias = const_cast<float*>(bias);
+            conv(w, xs, ys, stride, ups, temb, epi ? epi->temb_stride : 0, r.p ? &r : nullptr);
+        }
+    } catch (...) {
+        try { give_back(); } catch (...) {}
+        throw;
+    }
+    give_back();
+    release(a); release(y);
+}
+
+void Engine::op_linear_view(const float* x, const float* wt, const float* bias, int rows, int cin, int cout, const sdmi_op_view& v, const EpiOps* epi, float* yp) {
+    check_view(v, cin, cout);
+    if (v.in_ld != cin || v.in_off || v.in_planes > 1 || v.out_planes > 1)
+        throw Error(SDMI_ERR_UNSUPPORTED, "linear view: Engine::gemm reads dense rows and writes fp32 / bf16 slices only");
+    const int rld = (epi && epi->resid) ? (epi->resid_ld ? epi->resid_ld : cout) : 0;
+    const bool q8 = fp8_ && opt_fp8_ops_ && cin % 32 == 0 && cout % 8 == 0;
+    const int dt = (q8 || (bf16_ && cin % 64 == 0)) ? 1 : 0;
+    Act y = new_act(1, 1, rows, v.out_ld, dt);
+    if (dt) SDMI_HIP(launch_f32_to_bf16(yp, y.p, (long long)rows * v.out_ld, stream_));
+    else SDMI_HIP(hipMemcpyAsync(y.p, yp, y.bytes(), hipMemcpyDeviceToDevice, stream_));
+    auto give_back = [&] {
+        if (dt) SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(y.p, yp, rows, v.out_ld, 1, 1, stream_));
+        else SDMI_HIP(hipMemcpyAsync(yp, y.p, y.bytes(), hipMemcpyDeviceToDevice, stream_));
+    };
+    try {
+            Act ys = slice(y, v.out_off, cout);
+            std::unique_ptr<Buf> rb;
+            const float* resid = rld ? stage_epi(rb, epi->resid, rows, cout, rld, dt) : nullptr;
+            if (q8) {
+                const size_t kp = (size_t)(cin + 127) / 128 * 128;
+                Buf xh(this, (size_t)rows * cin * 2), w8(this, (size_t)cout * kp), s8(this, (size_t)cout * kp / 32);
+                SDMI_HIP(launch_f32_to_bf16(x, xh.p, (long long)rows * cin, stream_));
+                SDMI_HIP(launch_pack_linear_weight_fp8(wt, w8.p, s8.p, cin, cout, stream_));
+                Act xa; xa.p = xh.f(); xa.n = 1; xa.h = 1; xa.w = rows; xa.c = cin; xa.dt = 1;
+                ActQ q = new_rowsq(rows, cin);
+                quantize(xa, q);
+                LinW lw; lw.cin = cin; lw.cout = cout; lw.dt = 1; lw.bias = const_cast<float*>(bias); lw.bt8 = w8.f(); lw.bs8 = s8.f();
+                gemm_fp8(q, lw, cout, ys.p, ys.stride(), resid, rld);
+                release(q);
+            } else if (dt) {
+                Buf bt(this, (size_t)cin * cout * 4), xh(this, (size_t)rows * cin * 2);
+                SDMI_HIP(launch_pack_linear_weight_bf16(wt, bt.p, cin, cout, stream_));
+                SDMI_HIP(launch_f32_to_bf16(x, xh.p, (long long)rows * cin, stream_));
+                gemm(xh.f(), rows, bt.f(), bias, cin, cout, ys.p, ys.stride(), resid, rld, 1);
+            } else {
+                Buf bt(this, (size_t)cin * cout * 4);
+                SDMI_HIP(launch_pack_linear_weight(wt, bt.f(), cin, cout, stream_));
+                TempSplit planes(this, bt.f(), cout, cin);
+                gemm(x, rows, bt.f(), bias, cin, cout, ys.p, ys.stride(), resid, rld, 0);
+            }
+    } catch (...) {
+        try { give_back(); } catch (...) {}
+        throw;
+    }
+    give_back();
+    release(y);
+}
+
+void Engine::op_group_norm_view(const float* xp, const float* gamma, const float* beta, int n, int c, int h, int w, int groups, float eps, bool silu,
+                                const sdmi_op_view& v, int form, float* out) {
+    check_view(v, c, c);
+    if (n <= 0 || c <= 0 || h <= 0 || w <= 0 || c % 32 || form < 0 || form > 2) throw Error(SDMI_ERR_INVALID, "group_norm view: bad shape");
+    if (groups != 32) throw Error(SDMI_ERR_UNSUPPORTED, "group_norm view: Engine::group_norm normalises 32 groups");
+    if ((form == 1 && bf16_) || (form == 2 && !fp8_)) throw Error(SDMI_ERR_STATE, "group_norm view: planes need precision 0, MXFP8 output precision 2");
+    const int dt = bf16_ ? 1 : 0;
+    if (dt && v.in_planes > 1) throw Error(SDMI_ERR_INVALID, "view: planes are an fp32 format");
+    Act a = (!dt && v.in_planes > 1) ? new_act3(n, h, w, v.in_ld, 3) : new_act(n, h, w, v.in_ld, dt);
+    if (dt) SDMI_HIP(launch_f32_to_bf16(xp, a.p, a.rows() * v.in_ld, stream_));
+    else {
+        SDMI_HIP(hipMemcpyAsync(a.p, xp, a.bytes(), hipMemcpyDeviceToDevice, stream_));
+        if (a.p3) SDMI_HIP(launch_split3_rows(xp, a.p3, a.rows(), v.in_ld, v.in_ld, a.ld3, stream_));
+    }
+    Act xs = slice(a, v.in_off, c);
+    NormW nw; nw.gamma = const_cast<float*>(gamma); nw.beta = const_cast<float*>(beta); nw.c = c; nw.eps = eps;
+    if (form == 2) {
+        ActQ q = new_actq(n, h, w, c);
+        group_norm_fp8(nw, xs, q, silu);
+        Act d = new_act(n, h, w, c, 0);
+        SDMI_HIP(launch_dequant_fp8(q.q, q.s, d.p, d.rows(), c, stream_));
+        SDMI_HIP(launch_nhwc_to_nchw(d.p, out, n, c, h, w, stream_));
+        release(q); release(d);
+    } else if (form == 1) {
+        Act b3 = new_act3(n, h, w, c, 2), b = new_act(n, h, w, c, 0);
+        group_norm(nw, xs, b3, silu);
+        SDMI_HIP(launch_join3_rows(b3.p3, b.p, b.rows(), c, b3.ld3, c, stream_));
+        SDMI_HIP(launch_nhwc_to_nchw(b.p, out, n, c, h, w, stream_));
+        release(b3); release(b);
+    } else {
+        Act b = new_act(n, h, w, c, dt);
+        group_norm(nw, xs, b, silu);
+        if (dt) SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(b.p, out, n, c, h, w, stream_));
+        else SDMI_HIP(launch_nhwc_to_nchw(b.p, out, n, c, h, w, stream_));
+        release(b);
+    }
+    release(a);
+}
+
+void Engine::op_cat_chain(const float* x, const float* w_x, const float* b_x, const float* w_skip, const float* b_skip, const float* gamma, const float* beta,
+                          int n, int cin, int h, int wd, int cx, int cskip, float eps, bool silu, bool dense, float* out) {
+    if (n <= 0 || h <= 0 || wd <= 0 || cin <= 0 || cx <= 0 || cskip <= 0 || (cx + cskip) % 32) throw Error(SDMI_ERR_INVALID, "cat_chain: bad shape");
+    const int dt = bf16_ ? 1 : 0, ctot = cx + cskip;
+    if (cin % (dt ? 64 : 32) || cx % 8 || cskip % 8) throw Error(SDMI_ERR_UNSUPPORTED, "cat_chain: Cin must be a multiple of 32 (bf16: 64), the halves of 8");
+    Act a = new_act(n, h, wd, cin, dt);
+    if (dt) SDMI_HIP(launch_nchw_f32_to_nhwc_bf16(x, a.p, n, cin, h, wd, 1.0f, stream_));
+    else SDMI_HIP(launch_nchw_to_nhwc(x, a.p, n, cin, h, wd, 1.0f, stream_));
+    auto run = [&](const float* wt, const float* bias, int cout, Act& y) {
+        ConvW w; w.cin = cin; w.cout = cout; w.k = 3; w.dt = dt;
+        Buf bt(this, (size_t)cout * cin * 9 * 4);
+        if (dt) SDMI_HIP(launch_pack_conv_weight_bf16(wt, bt.p, cout, cin, 3, 3, stream_));
+        else SDMI_HIP(launch_pack_conv_weight(wt, bt.f(), cout, cin, 3, 3, stream_));
+        TempSplit planes(this, bt.f(), dt ? 0 : cout, (long long)cin * 9);
+        w.bt = bt.f(); w.bias = const_cast<float*>(bias);
+        conv(w, a, y, 1, 0, nullptr, 0, nullptr);
+    };
+    Act cat = new_act(n, h, wd, ctot, dt);
+    if (dense) {
+        Act yx = new_act(n, h, wd, cx, dt), ys = new_act(n, h, wd, cskip, dt);
+        run(w_skip, b_skip, cskip, ys);
+        run(w_x, b_x, cx, yx);
+        // (the kernel moves 16-byte pieces: a bf16 row of c channels is c / 2 floats)
+        SDMI_HIP(launch_concat_channels(yx.p, ys.p, cat.p, cat.rows(), dt ? cx / 2 : cx, dt ? cskip / 2 : cskip, stream_));
+        release(yx); release(ys);
+    } else {
+        Act ys = slice(cat, cx, cskip), yx = slice(cat, 0, cx);   // the input block's half first, then the block below's: unet_run's order
+        run(w_skip, b_skip, cskip, ys);
+        run(w_x, b_x, cx, yx);
+    }
+    NormW nw; nw.gamma = const_cast<float*>(gamma); nw.beta = const_cast<float*>(beta); nw.c = ctot; nw.eps = eps;
+    Act g = new_act(n, h, wd, ctot, dt);
+    group_norm(nw, cat, g, silu);
+    if (dt) SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(g.p, out, n, ctot, h, wd, stream_));
+    else SDMI_HIP(launch_nhwc_to_nchw(g.p, out, n, ctot, h, wd, stream_));
+    release(a); release(cat); release(g);
 }
 
 void Engine::op_geglu_forward(const float* x, const float* wt, const float* bias, int rows, int cin, int hidden, float* out) {

@@ -182,6 +182,21 @@ public:
                    int stride, int pad, int ups, float* out, const EpiOps* epi = nullptr);
     void op_linear(const float* x, const float* w, const float* bias, int rows, int cin, int cout, float* out, const EpiOps* epi = nullptr);
     void op_geglu(const float* proj, int rows, int hidden, float* out);
+    // the same operators on channel-slice VIEWS, built with slice() on real Acts as unet_run builds the halves of a Tensor::cat (tests: sdmi_op_*_view).
+    // xp: the input's parent [rows][in_ld] fp32 NHWC on the device (the slice's columns hold x, the others the caller's filler); yp: the output's
+    // parent [rows][out_ld] fp32 NHWC, prefilled by the caller and returned whole; yp3 (may be null): the joined plane copy when the parent exists both
+    // as fp32 and as planes.  Parents take the storage type of the route (bf16 at precision >= 1; v.in_planes / v.out_planes at precision 0).
+    static void check_view(const sdmi_op_view& v, int cin, int cout);
+    void op_conv2d_view(const float* xp, const float* w, const float* bias, int n, int cin, int h, int wd, int cout, int k, int stride, int pad, int ups,
+                        const sdmi_op_view& v, const EpiOps* epi, float* yp, float* yp3);
+    void op_linear_view(const float* x, const float* w, const float* bias, int rows, int cin, int cout, const sdmi_op_view& v, const EpiOps* epi, float* yp);
+    // form 0: the precision's GroupNorm (fp32 / bf16), 1: planes out (precision 0), 2: MXFP8 out, dequantised (precision 2); out [n,c,h,w]
+    void op_group_norm_view(const float* xp, const float* gamma, const float* beta, int n, int c, int h, int w, int groups, float eps, bool silu,
+                            const sdmi_op_view& v, int form, float* out);
+    // a block boundary: conv3x3(x, w_skip) -> channels [cx, cx + cskip), conv3x3(x, w_x) -> channels [0, cx), GroupNorm(+SiLU) over all of them.
+    // dense = false: both convolutions write slices of one buffer (as unet_run); true: dense results joined by launch_concat_channels.  out [n,cx+cskip,h,w]
+    void op_cat_chain(const float* x, const float* w_x, const float* b_x, const float* w_skip, const float* b_skip, const float* gamma, const float* beta,
+                      int n, int cin, int h, int wd, int cx, int cskip, float eps, bool silu, bool dense, float* out);
     void op_geglu_forward(const float* x, const float* wt, const float* bias, int rows, int cin, int hidden, float* out);
     void op_timestep_embedding(int t, int dim, float* out);
     double bench_conv(int n, int cin, int h, int w, int cout, int k, int stride, int ups, int tile_cfg, int splitk,

@@ -311,8 +311,10 @@ __device__ __forceinline__ void gemm_epilogue_f32(const ConvGemm& p, epi_f32x4 (
                 if (n + r < p.N) {
                     float sv = v[r];
                     if (!split) {
-                        if (p.bias) sv += p.bias[n + r];
-                        if (p.rowvec) sv += p.rowvec[(long long)smp * p.rowvec_stride + n + r];
+                        // (bias + row first, then the residual: the order of the 16-byte forms above, so a launch gives the same bits whichever form its strides select -- test_views_gpu.py)
+                        float cv = p.bias ? p.bias[n + r] : 0.f;
+                        if (p.rowvec) cv += p.rowvec[(long long)smp * p.rowvec_stride + n + r];
+                        sv += cv;
                         if (p.resid) sv += p.resid[(long long)m * p.ldr + n + r];
                     }
                     Cf[(long long)m * ldc + n + r] = sv;

@@ -616,6 +616,125 @@ int sdmi_op_linear_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, 
     });
 }
 
+// ---- the operators on channel-slice views ---------------------------------------------------------------------------------
+namespace {
+// x [n,c,h,w] -> the host image of its parent: NHWC rows ld wide, x at columns [off, off + c), `fill` elsewhere
+std::vector<float> view_parent(const float* x, int n, int c, int h, int w, int ld, int off, float fill) {
+    if (!x) throw Error(SDMI_ERR_INVALID, "null input pointer");
+    const size_t hw = (size_t)h * w;
+    std::vector<float> img((size_t)n * hw * ld, fill);
+    for (int b = 0; b < n; ++b)
+        for (int j = 0; j < c; ++j) {
+            const float* src = x + ((size_t)b * c + j) * hw;
+            float* dst = img.data() + (size_t)b * hw * ld + off + j;
+            for (size_t i = 0; i < hw; ++i) dst[i * ld] = src[i];
+        }
+    return img;
+}
+void need_view(const sdmi_op_view* v, int cin, int cout) {
+    if (!v) throw Error(SDMI_ERR_INVALID, "null view");
+    Engine::check_view(*v, cin, cout);
+}
+}  // namespace
+
+int sdmi_op_conv2d_view(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, const float* temb, int32_t temb_stride,
+                        const float* resid, int32_t resid_ld, int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cout, int32_t k, int32_t stride,
+                        int32_t pad, int32_t upsample2x, const sdmi_op_view* view, float* parent, float* parent_planes) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (n <= 0 || cin <= 0 || h <= 0 || w <= 0 || cout <= 0 || stride <= 0 || k <= 0 || pad < 0 || temb_stride < 0 || resid_ld < 0) throw Error(SDMI_ERR_INVALID, "conv2d_view: bad shape");
+        need_view(view, cin, cout);
+        const int ups = upsample2x ? 1 : 0;
+        const int hin = h << ups, win = w << ups;
+        const int ho = (hin + 2 * pad - k) / stride + 1, wo = (win + 2 * pad - k) / stride + 1;
+        if (ho <= 0 || wo <= 0) throw Error(SDMI_ERR_INVALID, "conv2d_view: empty output");
+        const bool both = view->out_planes == 3 && e.config().precision == 0;
+        if (both && !parent_planes) throw Error(SDMI_ERR_INVALID, "conv2d_view: out_planes = 3 returns two copies of the parent");
+        const std::vector<float> xp = view_parent(x, n, cin, h, w, view->in_ld, view->in_off, view->in_fill);
+        const size_t pbytes = (size_t)n * ho * wo * view->out_ld * sizeof(float);
+        Engine::Call call(e);
+        DevIn dx(e, xp.data(), xp.size() * sizeof(float)), dw(e, weight, (size_t)cout * cin * k * k * sizeof(float));
+        std::unique_ptr<Engine::Buf> db;
+        const float* bias_d = bias ? e.stage_epi(db, bias, 1, cout, cout, 0) : nullptr;
+        Engine::EpiOps epi;
+        epi.temb = temb; epi.temb_stride = temb_stride; epi.resid = resid; epi.resid_ld = resid_ld;
+        DevIn dpre(e, parent, pbytes);
+        DevOut dout(e, parent, pbytes);
+        SDMI_HIP(hipMemcpyAsync(dout.buf.p, dpre.buf.p, pbytes, hipMemcpyDeviceToDevice, e.stream()));
+        std::unique_ptr<DevOut> dout3;
+        if (both) dout3.reset(new DevOut(e, parent_planes, pbytes));
+        try {
+            e.op_conv2d_view(dx.f(), dw.f(), bias_d, n, cin, h, w, cout, k, stride, pad, ups, *view, &epi, dout.f(), both ? dout3->f() : nullptr);
+        } catch (...) {
+            try { dout.fetch(); } catch (...) {}     // what a refused launch left of the parent
+            throw;
+        }
+        call.finish();
+        dout.fetch();
+        if (both) dout3->fetch();
+    });
+}
+
+int sdmi_op_linear_view(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, const float* resid, int32_t resid_ld, int32_t rows,
+                        int32_t cin, int32_t cout, const sdmi_op_view* view, float* parent) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (rows <= 0 || cin <= 0 || cout <= 0 || resid_ld < 0) throw Error(SDMI_ERR_INVALID, "linear_view: bad shape");
+        need_view(view, cin, cout);
+        const size_t pbytes = (size_t)rows * view->out_ld * sizeof(float);
+        Engine::Call call(e);
+        DevIn dx(e, x, (size_t)rows * cin * sizeof(float)), dw(e, weight, (size_t)cin * cout * sizeof(float));
+        std::unique_ptr<Engine::Buf> db;
+        const float* bias_d = bias ? e.stage_epi(db, bias, 1, cout, cout, 0) : nullptr;
+        Engine::EpiOps epi;
+        epi.resid = resid; epi.resid_ld = resid_ld;
+        DevIn dpre(e, parent, pbytes);
+        DevOut dout(e, parent, pbytes);
+        SDMI_HIP(hipMemcpyAsync(dout.buf.p, dpre.buf.p, pbytes, hipMemcpyDeviceToDevice, e.stream()));
+        try {
+            e.op_linear_view(dx.f(), dw.f(), bias_d, rows, cin, cout, *view, &epi, dout.f());
+        } catch (...) {
+            try { dout.fetch(); } catch (...) {}
+            throw;
+        }
+        call.finish();
+        dout.fetch();
+    });
+}
+
+int sdmi_op_group_norm_view(sdmi_ctx* ctx, const float* x, const float* gamma, const float* beta, int32_t n, int32_t c, int32_t h, int32_t w,
+                            int32_t n_group, float eps, int32_t fuse_silu, const sdmi_op_view* view, int32_t form, float* out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (n <= 0 || c <= 0 || h <= 0 || w <= 0) throw Error(SDMI_ERR_INVALID, "group_norm_view: bad shape");
+        need_view(view, c, c);
+        const std::vector<float> xp = view_parent(x, n, c, h, w, view->in_ld, view->in_off, view->in_fill);
+        Engine::Call call(e);
+        DevIn dx(e, xp.data(), xp.size() * sizeof(float)), dg(e, gamma, c * sizeof(float)), db(e, beta, c * sizeof(float));
+        DevOut dout(e, out, (size_t)n * c * h * w * sizeof(float));
+        e.op_group_norm_view(dx.f(), dg.f(), db.f(), n, c, h, w, n_group, eps, fuse_silu != 0, *view, form, dout.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
+int sdmi_op_cat_chain(sdmi_ctx* ctx, const float* x, const float* w_x, const float* b_x, const float* w_skip, const float* b_skip, const float* gamma,
+                      const float* beta, int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cx, int32_t cskip, float eps, int32_t fuse_silu,
+                      int32_t dense, float* out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (n <= 0 || cin <= 0 || h <= 0 || w <= 0 || cx <= 0 || cskip <= 0) throw Error(SDMI_ERR_INVALID, "cat_chain: bad shape");
+        const int ctot = cx + cskip;
+        Engine::Call call(e);
+        DevIn dx(e, x, (size_t)n * cin * h * w * sizeof(float)), dwx(e, w_x, (size_t)cx * cin * 9 * sizeof(float)), dws(e, w_skip, (size_t)cskip * cin * 9 * sizeof(float));
+        DevIn dbx(e, b_x, cx * sizeof(float)), dbs(e, b_skip, cskip * sizeof(float)), dg(e, gamma, ctot * sizeof(float)), db(e, beta, ctot * sizeof(float));
+        DevOut dout(e, out, (size_t)n * ctot * h * w * sizeof(float));
+        e.op_cat_chain(dx.f(), dwx.f(), dbx.f(), dws.f(), dbs.f(), dg.f(), db.f(), n, cin, h, w, cx, cskip, eps, fuse_silu != 0, dense != 0, dout.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
 int sdmi_op_geglu_forward(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, int32_t rows, int32_t cin,
                           int32_t hidden, float* out) {
     return guarded([&] {

@@ -23,7 +23,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _capi
-from ._capi import SdmiConfig, SdmiError, check, load_library
+from ._capi import SdmiConfig, SdmiError, SdmiOpView, check, load_library
 
 def mpk_list(path) -> list:
     """[(dump name, shape, file offset)] of a Burn .mpk record, parsed by the C++ reader (host only, no GPU)."""
@@ -533,6 +533,90 @@ class StableDiffusion:
         r = None if resid is None else _f32(resid, out.shape)
         check(self._lib.sdmi_op_linear_epilogue(self._ctx, _fp(x), _fp(weight), None if b is None else _fp(b), None if r is None else _fp(r),
                                                 resid_ld, rows, cin, cout, _fp(out)))
+        return out
+
+    # ---- the same operators on channel-slice views of wider buffers, as the UNet realises Tensor::cat (tests) ----
+    def _view_call(self, parent, fn):
+        """fn(); a refused call raises SdmiError carrying what the device left of the parent (.parent)"""
+        try:
+            fn()
+        except SdmiError as e:
+            e.parent = parent
+            raise
+
+    def op_conv2d_view(self, x, weight, bias=None, temb=None, resid=None, stride=1, upsample2x=False, temb_stride=None, resid_ld=0, *, parent, out_off,
+                       in_ld=None, in_off=0, in_fill=float("nan"), in_planes=0, out_planes=0):
+        """op_conv2d_epilogue with x read from columns [in_off, in_off + cin) of a buffer in_ld wide (the rest in_fill) and the result written to columns
+        [out_off, out_off + cout) of `parent` [n*ho*wo, out_ld] (NHWC rows, prefilled by the caller; not modified).  Returns the whole parent as the
+        engine left it; with out_planes = 3 (precision 0: fp32 and bf16-plane copies) the pair (fp32 copy, joined planes)."""
+        x = _f32(x)
+        weight = _f32(weight)
+        n, cin, h, w = x.shape
+        cout, cin2, k, k2 = weight.shape
+        if cin2 != cin or k != k2:
+            raise ValueError("conv2d: weight shape does not match input")
+        pad = 1 if k == 3 else 0
+        ups = 1 if upsample2x else 0
+        ho = ((h << ups) + 2 * pad - k) // stride + 1
+        wo = ((w << ups) + 2 * pad - k) // stride + 1
+        out = np.array(parent, dtype=np.float32, order="C", copy=True)
+        if out.ndim != 2 or out.shape[0] != n * ho * wo:
+            raise ValueError(f"conv2d_view: parent must be [{n * ho * wo}, out_ld], got {out.shape}")
+        b = None if bias is None else _f32(bias, (cout,))
+        t = None if temb is None else _f32(temb)
+        if t is not None:
+            if t.shape not in ((cout,), (n, cout)):
+                raise ValueError("conv2d_view: temb must be [cout] or [n, cout]")
+            if temb_stride is None:
+                temb_stride = 0 if t.ndim == 1 else cout
+        r = None if resid is None else _f32(resid, (n, cout, ho, wo))
+        v = SdmiOpView(cin if in_ld is None else in_ld, in_off, out.shape[1], out_off, in_fill, in_planes, out_planes)
+        out3 = np.empty_like(out) if out_planes == 3 else None
+        self._view_call(out, lambda: check(self._lib.sdmi_op_conv2d_view(
+            self._ctx, _fp(x), _fp(weight), None if b is None else _fp(b), None if t is None else _fp(t), temb_stride or 0,
+            None if r is None else _fp(r), resid_ld, n, cin, h, w, cout, k, stride, pad, ups, C.byref(v), _fp(out), None if out3 is None else _fp(out3))))
+        return out if out3 is None else (out, out3)
+
+    def op_linear_view(self, x, weight, bias=None, resid=None, resid_ld=0, *, parent, out_off):
+        """op_linear_epilogue writing columns [out_off, out_off + cout) of `parent` [rows, out_ld]; returns the whole parent."""
+        x = _f32(x)
+        weight = _f32(weight)
+        cin, cout = weight.shape
+        rows = x.size // cin
+        out = np.array(parent, dtype=np.float32, order="C", copy=True)
+        if out.ndim != 2 or out.shape[0] != rows:
+            raise ValueError(f"linear_view: parent must be [{rows}, out_ld], got {out.shape}")
+        b = None if bias is None else _f32(bias, (cout,))
+        r = None if resid is None else _f32(resid, (rows, cout))
+        v = SdmiOpView(cin, 0, out.shape[1], out_off, float("nan"), 0, 0)
+        self._view_call(out, lambda: check(self._lib.sdmi_op_linear_view(self._ctx, _fp(x), _fp(weight), None if b is None else _fp(b), None if r is None else _fp(r),
+                                                                         resid_ld, rows, cin, cout, C.byref(v), _fp(out))))
+        return out
+
+    def op_group_norm_view(self, x, gamma, beta, eps=1e-5, silu=False, *, in_ld, in_off, in_fill=float("nan"), in_planes=0, form=0):
+        """op_group_norm (32 groups) with x read from columns [in_off, in_off + c) of a buffer in_ld wide whose other columns hold in_fill.
+        form 0: the context's GroupNorm, 1: the plane-writing form (precision 0), 2: MXFP8 output, dequantised (precision 2)."""
+        x = _f32(x)
+        n, c, h, w = x.shape
+        out = np.empty_like(x)
+        v = SdmiOpView(in_ld, in_off, c, 0, in_fill, in_planes, 0)
+        check(self._lib.sdmi_op_group_norm_view(self._ctx, _fp(x), _fp(_f32(gamma, (c,))), _fp(_f32(beta, (c,))), n, c, h, w, 32, eps, int(silu), C.byref(v),
+                                                form, _fp(out)))
+        return out
+
+    def op_cat_chain(self, x, w_x, b_x, w_skip, b_skip, gamma, beta, eps=1e-5, silu=True, dense=False):
+        """GroupNorm(cat(conv3x3(x, w_x), conv3x3(x, w_skip))): the convolutions write the two channel slices of one buffer (dense=False, the UNet's
+        way) or dense tensors joined by a copy (dense=True)."""
+        x = _f32(x)
+        n, cin, h, w = x.shape
+        w_x, w_skip = _f32(w_x), _f32(w_skip)
+        cx, cskip = w_x.shape[0], w_skip.shape[0]
+        if w_x.shape != (cx, cin, 3, 3) or w_skip.shape != (cskip, cin, 3, 3):
+            raise ValueError("cat_chain: weights must be [cout, cin, 3, 3]")
+        out = np.empty((n, cx + cskip, h, w), dtype=np.float32)
+        check(self._lib.sdmi_op_cat_chain(self._ctx, _fp(x), _fp(w_x), _fp(_f32(b_x, (cx,))), _fp(w_skip), _fp(_f32(b_skip, (cskip,))),
+                                          _fp(_f32(gamma, (cx + cskip,))), _fp(_f32(beta, (cx + cskip,))), n, cin, h, w, cx, cskip, eps, int(silu), int(dense),
+                                          _fp(out)))
         return out
 
     def op_geglu_forward(self, x, weight_in_out, bias, hidden):
