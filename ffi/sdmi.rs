@@ -31,6 +31,18 @@ pub struct SdmiConfig {
     pub reserved: [i32; 3],
 }
 
+/// `sdmi_sampler` (include/sdmi.h "sampler choice"): kind 0 DDIM(eta) -- eta 0 = the reference's sampler = plain Euler, eta 1 =
+/// Euler-ancestral --, 1 DPM-Solver++(2M), 2 PLMS.
+#[repr(C)]
+pub struct SdmiSampler {
+    pub kind: i32,
+    pub reserved0: i32,
+    pub eta: f64,
+    pub noise_seed: u64,
+    pub image_base: i64,
+    pub reserved: [i64; 4],
+}
+
 #[link(name = "sdmi")]
 extern "C" {
     fn sdmi_default_config(cfg: *mut SdmiConfig) -> c_int;
@@ -67,6 +79,11 @@ extern "C" {
     fn sdmi_img2img_image_dev(ctx: *mut c_void, context: *const c_float, n: i32, t_len: i32, uncond: *const c_float, tu: i32, scale: c_double,
                               n_steps: usize, strength: c_double, init_rgb: *const u8, mask: *const c_float, noise: *const c_float, seed: u64,
                               rgb_out: *mut u8) -> c_int;
+    fn sdmi_set_sampler(ctx: *mut c_void, sampler: *const SdmiSampler) -> c_int;
+    fn sdmi_get_sampler(ctx: *mut c_void, out: *mut SdmiSampler) -> c_int;
+    fn sdmi_multi_set_sampler(m: *mut c_void, sampler: *const SdmiSampler) -> c_int;
+    fn sdmi_sampler_coefs(sampler: *const SdmiSampler, alphas_cumprod: *const c_float, total: i32, ts: *const i32, count: i32, step_size: i64,
+                          coefs: *mut c_double) -> c_int;
     fn sdmi_tokenizer_create(out: *mut *mut c_void, merges_path: *const c_char) -> c_int;
     fn sdmi_tokenizer_destroy(tok: *mut c_void);
     fn sdmi_tokenizer_encode(tok: *const c_void, text: *const c_char, ids: *mut i32, capacity: i32, n_ids: *mut i32) -> c_int;
@@ -155,6 +172,36 @@ impl StableDiffusionMi355 {
             return Err(last_error().into());
         }
         Ok(())
+    }
+
+    /// The sampler of every later sampling call (`sdmi_set_sampler`, sticky; no reference counterpart: the reference is DDIM at eta = 0).
+    /// kind 0 DDIM with 0 <= eta <= 1, 1 DPM-Solver++(2M), 2 PLMS; `noise_seed` keys the step noise of eta > 0.  `None` restores the default.
+    pub fn set_sampler(&mut self, sampler: Option<(i32, f64, u64)>) -> Result<(), Box<dyn Error>> {
+        let st = match sampler {
+            None => unsafe { sdmi_set_sampler(self.ctx, std::ptr::null()) },
+            Some((kind, eta, noise_seed)) => {
+                let s = SdmiSampler { kind, reserved0: 0, eta, noise_seed, image_base: 0, reserved: [0; 4] };
+                unsafe { sdmi_set_sampler(self.ctx, &s) }
+            }
+        };
+        if st != 0 { Err(last_error().into()) } else { Ok(()) }
+    }
+
+    /// The sampler in force (`sdmi_get_sampler`).
+    pub fn sampler(&self) -> SdmiSampler {
+        let mut s = SdmiSampler { kind: 0, reserved0: 0, eta: 0.0, noise_seed: 0, image_base: 0, reserved: [0; 4] };
+        check(unsafe { sdmi_get_sampler(self.ctx, &mut s) });
+        s
+    }
+
+    /// The per-step coefficients `[ts.len()][8]` = cx, ce, h1, h2, h3, cz, qx, qe of a sampler (`sdmi_sampler_coefs`, host only).
+    pub fn sampler_coefs(sampler: &SdmiSampler, alphas_cumprod: &[f32], ts: &[i32], step_size: i64) -> Result<Vec<[f64; 8]>, Box<dyn Error>> {
+        let mut out = vec![[0f64; 8]; ts.len()];
+        let st = unsafe {
+            sdmi_sampler_coefs(sampler, alphas_cumprod.as_ptr(), alphas_cumprod.len() as i32, ts.as_ptr(), ts.len() as i32, step_size,
+                               out.as_mut_ptr() as *mut c_double)
+        };
+        if st != 0 { Err(last_error().into()) } else { Ok(out) }
     }
 
     /// `load_stable_diffusion_model_file(filename, device)` (src/bin/sample/main.rs:27-34): the Burn
@@ -339,6 +386,18 @@ impl StableDiffusionMi355Node {
             }
             Ok(Self { m, ctx_dim: cfg.ctx_dim as usize, image_bytes: 3 * 64 * (cfg.latent_h * cfg.latent_w) as usize })
         }
+    }
+
+    /// `StableDiffusionMi355::set_sampler` on every device; each shard's image_base is the global index of its first image.
+    pub fn set_sampler(&mut self, sampler: Option<(i32, f64, u64)>) -> Result<(), Box<dyn Error>> {
+        let st = match sampler {
+            None => unsafe { sdmi_multi_set_sampler(self.m, std::ptr::null()) },
+            Some((kind, eta, noise_seed)) => {
+                let s = SdmiSampler { kind, reserved0: 0, eta, noise_seed, image_base: 0, reserved: [0; 4] };
+                unsafe { sdmi_multi_set_sampler(self.m, &s) }
+            }
+        };
+        if st != 0 { Err(last_error().into()) } else { Ok(()) }
     }
 
     pub fn sample_image(&self, context: &[f32], unconditional_context: &[f32], unconditional_guidance_scale: f64, n_steps: usize,

@@ -197,6 +197,46 @@ int sdmi_img2img_image(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T
                        double scale, size_t n_steps, double strength, const uint8_t* init_rgb, const float* mask,
                        const float* noise, uint64_t seed, uint8_t* rgb_out);
 
+/* ---- sampler choice: stochastic DDIM (eta), DPM-Solver++(2M), PLMS (no reference counterpart) ----
+ * The reference integrates with DDIM at sigma = 0 only (stablediffusion/mod.rs:142-156); that stays the default, on the same launches.
+ * A sampler set on a context applies to every sampling entry point above and below (sample_latent / sample_image / img2img, host and
+ * device pointers, sharded) until it is changed: sticky, like sdmi_set_stream.  Schedule (ts, step_size, prev, quirk Q5) and, for
+ * img2img, the tail sdmi_img2img_timesteps selects are unchanged; with cur = a[ts_j], prev = a[ts_j - step_size] (1 past the end),
+ * e = eu + (ec - eu) scale and x0 = (x - sqrt(1 - cur) e) / sqrt(cur):
+ *   kind 0, DDIM(eta), 0 <= eta <= 1: sigma = eta sqrt((1 - prev) / (1 - cur)) sqrt(1 - cur / prev),
+ *       x' = sqrt(prev) x0 + sqrt(1 - prev - sigma^2) e + sigma z.  eta = 0 is the default path, bit for bit.  Plain Euler on
+ *       sigma_k = sqrt((1 - a) / a) IS eta = 0 and Euler-ancestral IS eta = 1 (sqrt(prev) sigma_up = sigma): no kinds of their own.
+ *   kind 1, DPM-Solver++(2M) (data prediction, k-diffusion's sample_dpmpp_2m): lambda(a) = log(a / (1 - a)) / 2, h = lambda(prev) - lambda(cur),
+ *       D = x0 on the first step of a call and where prev = 1, else (1 + 1/(2r)) x0 - x0_last / (2r) with r = (lambda(cur) - lambda(cur_last)) / h;
+ *       x' = sqrt((1 - prev) / (1 - cur)) x - sqrt(prev) expm1(-h) D; where prev = 1 the step is its limit x' = x0.
+ *   kind 2, PLMS: Adams-Bashforth on e with warm-up orders 1, 2, 3, then 4 -- e' = e, (3e - e1)/2, (23e - 16e1 + 5e2)/12,
+ *       (55e - 59e1 + 37e2 - 9e3)/24 -- and the eta = 0 update with e' for e.  One UNet evaluation per step (CompVis plms.py spends a
+ *       second one on its first step; this variant does not).
+ * Step noise z (only where its weight is not 0): element i (NCHW order) of image b at index s of the FULL schedule ts is element i of the
+ * N(0,1) stream  noise_seed + image_base + b + ((uint64_t)(s + 1) << 32)  (the stream of sdmi_sample_latent's seed path; uint64 wraparound).
+ * image_base = the global index of the call's first image: a batch split into smaller calls draws the same noise per image.
+ * The img2img mask blend follows the update of any kind, unchanged. */
+typedef struct sdmi_sampler {
+    int32_t kind;          /* 0 DDIM(eta), 1 DPM-Solver++(2M), 2 PLMS                              */
+    int32_t reserved0;
+    double eta;            /* kind 0 only: 0 (deterministic, the default) .. 1; must be 0 otherwise */
+    uint64_t noise_seed;
+    int64_t image_base;
+    int64_t reserved[4];
+} sdmi_sampler;
+/* NULL restores the default (kind 0, eta 0).  SDMI_ERR_INVALID -- and nothing changes -- for an unknown kind, eta outside [0, 1] or NaN,
+ * eta != 0 with kind != 0. */
+int sdmi_set_sampler(sdmi_ctx* ctx, const sdmi_sampler* sampler);
+int sdmi_get_sampler(sdmi_ctx* ctx, sdmi_sampler* out);
+/* Host only, needs no device: THE implementation of the rules above (the engine calls it).  For the `count` timesteps ts a call runs
+ * (sample_latent's schedule or its img2img tail; ts[0] is the call's first step) it writes 8 doubles per step,
+ *     cx, ce, h1, h2, h3, cz, qx, qe:    q = qx x + qe e  (pushed to history: x0 for kind 1, e for kind 2, unused for kind 0)
+ *                                        x' = cx x + ce e + h1 q_-1 + h2 q_-2 + h3 q_-3 + cz z
+ * computed in f64 (the engine applies them as f32).  alphas_cumprod has `total` entries; SDMI_ERR_INVALID for a sampler sdmi_set_sampler
+ * refuses, a timestep outside [0, total), step_size < 1 or a null pointer. */
+int sdmi_sampler_coefs(const sdmi_sampler* sampler, const float* alphas_cumprod, int32_t total, const int32_t* ts, int32_t count,
+                       int64_t step_size, double* coefs);
+
 /* qkv_attention (src/model/attention.rs:5-45 == src/backend.rs:88-128; the
  * operator seam of the commented-out `trait Backend`, backend.rs:4-84).
  * q [n,nq,n_state], k,v [n,nk,n_state], mask [>=nq, mask_ld>=nk] additive or
@@ -277,6 +317,9 @@ int sdmi_multi_load_weights(sdmi_multi* m, const char* kind, const char* path);
 int sdmi_sample_image_sharded(sdmi_multi* m, const float* context, int32_t T, const float* uncond, int32_t Tu,
                               double scale, size_t n_steps, int32_t n_images, const float* init_latents, uint64_t seed,
                               uint8_t* rgb_out);
+/* sdmi_set_sampler on every device context; each shard's image_base is overridden with the global index of its first image, so the
+ * step noise, like the start noise, does not depend on the device count.  NULL restores the default. */
+int sdmi_multi_set_sampler(sdmi_multi* m, const sdmi_sampler* sampler);
 /* the contiguous global image range [begin, end) device `rank` of `n_ranks` samples (host only): the partition rule of
  * sdmi_sample_image_sharded, and of the one-process-per-GPU launcher (bench.py / sharding.py use the same rule) */
 int sdmi_shard_range(int32_t n_images, int32_t rank, int32_t n_ranks, int32_t* begin, int32_t* end);
@@ -392,7 +435,7 @@ int sdmi_last_call_stats(sdmi_ctx* ctx, double* gpu_ms, int64_t* n_kernels, doub
  * 6 conv_gemm_split (precision = 0: the conv/linear launches that run on the bf16 matrix pipe with three-way split fp32
  * operands, k_gemm3x.hip / k_gemm3p.hip; class 0 then holds the launches left on the fp32 matrix instruction), 7 split_rows (fp32 tensors
  * converted to bf16 planes for a plane GEMM outside their producer), 8 other (every launch of the path that is in no other class: layout converters, the
- * CFG + DDIM update, img2img's u8 -> fp32 input conversion, start latent and masked CFG + DDIM update, timestep embedding, SiLU of the embedding, row softmax / transposes of the unfused VAE attention, u8 conversion), 9 geglu (the GEGLU gate kernels
+ * CFG + DDIM update, the sampler-choice step (k_sampler.hip), img2img's u8 -> fp32 input conversion, start latent and masked CFG + DDIM update, timestep embedding, SiLU of the embedding, row softmax / transposes of the unfused VAE attention, u8 conversion), 9 geglu (the GEGLU gate kernels
  * where the gate is not fused into its GEMM; the quantising gate of precision = 2 included).  flops / bytes are the ALGORITHMIC work of
  * those launches (2*M*N*K; one read + one write of the tensor).  "profile_reset" clears. */
 int sdmi_profile_stats(sdmi_ctx* ctx, int32_t cls, double* ms, int64_t* launches, double* flops, double* bytes);

@@ -36,7 +36,14 @@ class SdmiOpView(C.Structure):
                 ("in_planes", C.c_int32), ("out_planes", C.c_int32)]
 
 
+class SdmiSampler(C.Structure):
+    """sdmi_sampler: the sampler choice of a context (sdmi_set_sampler)"""
+    _fields_ = [("kind", C.c_int32), ("reserved0", C.c_int32), ("eta", C.c_double), ("noise_seed", C.c_uint64), ("image_base", C.c_int64),
+                ("reserved", C.c_int64 * 4)]
+
+
 _F = C.POINTER(C.c_float)
+_SAMPLER = C.POINTER(SdmiSampler)
 _VIEW = C.POINTER(SdmiOpView)
 _U8 = C.POINTER(C.c_uint8)
 _CTX = C.c_void_p
@@ -69,6 +76,10 @@ SIGNATURES = {
     "sdmi_img2img_timesteps": (C.c_int, [C.c_int32, C.c_size_t, C.c_double, _I32, C.c_int32, _I32]),
     "sdmi_img2img_latent": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F, C.c_int32, C.c_double, C.c_size_t, C.c_double, _F, _F, _F, C.c_uint64, _F]),
     "sdmi_img2img_image": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F, C.c_int32, C.c_double, C.c_size_t, C.c_double, _U8, _F, _F, C.c_uint64, _U8]),
+    "sdmi_set_sampler": (C.c_int, [_CTX, _SAMPLER]),
+    "sdmi_get_sampler": (C.c_int, [_CTX, _SAMPLER]),
+    "sdmi_sampler_coefs": (C.c_int, [_SAMPLER, _F, C.c_int32, _I32, C.c_int32, C.c_int64, C.POINTER(C.c_double)]),
+    "sdmi_multi_set_sampler": (C.c_int, [C.c_void_p, _SAMPLER]),
     "sdmi_qkv_attention": (C.c_int, [_CTX, _F, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),
     "sdmi_tokenizer_create": (C.c_int, [C.POINTER(_TOK), C.c_char_p]),
     "sdmi_tokenizer_destroy": (None, [_TOK]),

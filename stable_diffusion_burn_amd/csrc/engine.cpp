@@ -2245,6 +2245,18 @@ void Engine::sample_latent_dev(const float* context, int n, int T, const float* 
     }, nullptr, latent_out);
 }
 
+void Engine::check_sampler(const sdmi_sampler& s) {
+    if (s.kind < 0 || s.kind > 2) throw Error(SDMI_ERR_INVALID, "sampler: kind must be 0 (DDIM), 1 (DPM-Solver++ 2M) or 2 (PLMS)");
+    if (!(s.eta >= 0.0 && s.eta <= 1.0)) throw Error(SDMI_ERR_INVALID, "sampler: eta must satisfy 0 <= eta <= 1");
+    if (s.kind != 0 && s.eta != 0.0) throw Error(SDMI_ERR_INVALID, "sampler: eta belongs to kind 0 (DDIM) only");
+}
+
+void Engine::set_sampler(const sdmi_sampler* s) {
+    if (!s) { sampler_ = sdmi_sampler{}; return; }
+    check_sampler(*s);
+    sampler_ = *s;
+}
+
 void Engine::sample_loop(const float* context, int n, int T, const float* uncond, int Tu, double scale, const std::vector<int>& ts,
                          size_t step_size, const std::function<void(float* latent, float* unet_in, long long per_half)>& start,
                          const Blend* blend, float* latent_out) {
@@ -2265,6 +2277,17 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
 
     const long long per_half = (long long)n * H * W * 4;
     Buf latent(this, per_half * 4), unet_in(this, 2 * per_half * 4), eps(this, 2 * per_half * 4);
+    // sampler choice: the coefficient table of the call and its history slots (x0 for DPM-Solver++(2M), three e for PLMS)
+    const bool custom = sampler_.kind != 0 || sampler_.eta != 0.0;
+    const int depth = !custom ? 0 : sampler_.kind == 1 ? 1 : sampler_.kind == 2 ? 3 : 0;
+    std::vector<double> coefs;
+    std::unique_ptr<Buf> hist[3];
+    if (custom) {
+        coefs.resize(ts.size() * 8);
+        const int st = sdmi_sampler_coefs(&sampler_, alphas_.data(), (int32_t)alphas_.size(), ts.data(), (int32_t)ts.size(), (int64_t)step_size, coefs.data());
+        if (st != SDMI_OK) throw Error(st, "sample_loop: sdmi_sampler_coefs refused the schedule");
+        for (int k = 0; k < depth; ++k) hist[k].reset(new Buf(this, per_half * 4));
+    }
     start(latent.f(), unet_in.f(), per_half);
     for (size_t s = 0; s < ts.size(); ++s) {
         const size_t t = (size_t)ts[s];
@@ -2277,6 +2300,25 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
         c.sqrt_prev = (float)std::sqrt(prev);
         c.dir_coef = (float)std::sqrt(1.0 - prev - 0.0);                                 // :153 (sigma = 0)
         unet_run(unet_in.f(), nb, (int)s, eps.f(), opt_cfg_share_ != 0);   // unet_in = [latent | latent]: a CFG pair
+        if (custom) {
+            const double* k = &coefs[s * 8];
+            SamplerStep p{};
+            p.scale = (float)scale;
+            p.cx = (float)k[0]; p.ce = (float)k[1]; p.h[0] = (float)k[2]; p.h[1] = (float)k[3]; p.h[2] = (float)k[4]; p.cz = (float)k[5];
+            p.qx = (float)k[6]; p.qe = (float)k[7];
+            p.blend_prev = c.sqrt_prev; p.blend_dir = c.dir_coef;
+            p.n_hist = (int)std::min<size_t>(s, (size_t)depth);
+            // slot (s mod depth) receives this step's q: the slot of the oldest one.  q of k + 1 steps ago sits in slot (s - 1 - k) mod depth.
+            const float* q_prev[3] = {nullptr, nullptr, nullptr};
+            for (int j = 0; j < p.n_hist; ++j) q_prev[j] = hist[(s - 1 - (size_t)j) % (size_t)depth]->f();
+            float* q_out = depth ? hist[s % (size_t)depth]->f() : nullptr;
+            // index of this step in the FULL schedule (ts may be its img2img tail): the noise key does not depend on strength
+            const uint64_t s_full = (uint64_t)((alphas_.size() - 1 - t) / step_size);
+            const uint64_t key = sampler_.noise_seed + (uint64_t)sampler_.image_base + ((s_full + 1) << 32);
+            ProfScope ps_o(this, PC_OTHER);
+            SDMI_HIP(launch_sampler_step(eps.f(), latent.f(), unet_in.f(), per_half, (long long)H * W, p, depth, q_prev, q_out, key,
+                                         blend ? blend->mask : nullptr, blend ? blend->z0 : nullptr, blend ? blend->eps : nullptr, stream_));
+        } else
         if (blend) { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_cfg_ddim_masked(eps.f(), latent.f(), unet_in.f(), per_half, c, blend->mask, blend->z0, blend->eps, stream_)); }
         else { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_cfg_ddim(eps.f(), latent.f(), unet_in.f(), per_half, c, stream_)); }
         count_kernel();

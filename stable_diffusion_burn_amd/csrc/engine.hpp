@@ -162,6 +162,11 @@ public:
                             double strength, const float* z0, const float* mask, const float* noise, uint64_t seed, float* latent_out);
     void img2img_image_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps,
                            double strength, const uint8_t* init_rgb, const float* mask, const float* noise, uint64_t seed, float* latent_out);
+    // sampler choice (sdmi_set_sampler): sticky, read by sample_loop -- every sampling entry point.  The default (kind 0,
+    // eta 0) is the reference's DDIM on its own launches.  check_sampler throws SDMI_ERR_INVALID for what the header lists; null = the default.
+    static void check_sampler(const sdmi_sampler& s);
+    void set_sampler(const sdmi_sampler* s);
+    const sdmi_sampler& sampler() const { return sampler_; }
     void decode_latent_dev(const float* latent_nchw, int n, float in_scale, float* img_nchw, uint8_t* rgb_u8);
     // kv_len_host: null, or a HOST array [n] of per-sample key counts (1 .. nk; the CFG batch's cross attention, Engine::attention's kv_len)
     void qkv_attention_dev(const float* q, const float* k, const float* v, const float* mask, int mask_ld, int n,
@@ -354,7 +359,8 @@ private:
     Act encode_one(Act& rgb);
     // The DDIM + CFG loop of sample_latent over `ts` (sample_latent's schedule or its tail): `start` writes x_ts[0] into the NHWC latent
     // [n][hw][4] and both halves of unet_in [2n][hw][4] (per_half floats each).  blend (img2img with a mask): after each update
-    // x <- m x + (1 - m)(sqrt(a_prev) z0 + sqrt(1 - a_prev) eps), device pointers, z0 / eps NHWC.
+    // x <- m x + (1 - m)(sqrt(a_prev) z0 + sqrt(1 - a_prev) eps), device pointers, z0 / eps NHWC.  With a non-default sampler_ the update of every step is
+    // launch_sampler_step on the coefficient table of sdmi_sampler_coefs instead (one launch per step either way), its history in pool buffers of the call.
     struct Blend { const float* mask; const float* z0; const float* eps; };
     void sample_loop(const float* context, int n, int T, const float* uncond, int Tu, double scale, const std::vector<int>& ts,
                      size_t step_size, const std::function<void(float* latent, float* unet_in, long long per_half)>& start,
@@ -434,6 +440,7 @@ private:
     int opt_fp8_ops_ = 0;            // tests: op_linear / op_layer_norm / op_geglu run the fp8_linear path's kernels (outputs dequantised)
     int opt_fp8_linear_ = 0;         // precision = 2: 0 (default: the accuracy budget of 6e-2 final-latent relative RMS) = MXFP8 on the ResBlock / ResnetBlock 3x3
                                      // convolutions only; 1 = also the transformer blocks' Linear layers and the 1x1 / up / down convolutions (8.1e-2)
+    sdmi_sampler sampler_{};          // all zero: kind 0, eta 0
     hipStream_t stream_ = nullptr;
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr, ev_user_ = nullptr;
     hipStream_t user_stream_ = nullptr;

@@ -1,6 +1,6 @@
-// k_sample.hpp -- device arithmetic of the sampler shared by k_elem.hip (txt2img) and k_img2img.hip (img2img):
-// one definition each of the N(0,1) stream and of the CFG + DDIM update, so that the two paths cannot draw or
-// round differently.
+// k_sample.hpp -- device arithmetic of the sampler shared by k_elem.hip (txt2img), k_img2img.hip (img2img) and
+// k_sampler.hip (sampler choice): one definition each of the N(0,1) stream, of the CFG + DDIM update and of the
+// linear sampler step, so that the paths cannot draw or round differently.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,6 +32,16 @@ __device__ __forceinline__ float cfg_ddim_update(float eu, float ec, float x, co
     const float predx0 = (x - e * c.sqrt_noise) / c.sqrt_cur;  // :152
     const float dir = e * c.dir_coef;                          // :153
     return predx0 * c.sqrt_prev + dir;                         // :155 (sigma = 0)
+}
+
+// Sampler choice: one element of a DDIM(eta) / DPM-Solver++(2M) / PLMS step in the linear form of
+// sdmi_sampler_coefs.  q1..q3 = the q of one / two / three steps ago (pass 0 where there is none: its weight is 0 then), z = the
+// step's N(0,1) draw (0 where cz = 0).  *q = what the step pushes to history (x0 for DPM-Solver++, e for PLMS).
+// Plain Euler on sigma = sqrt((1 - a) / a) is this step with DDIM's eta = 0 coefficients, Euler-ancestral with eta = 1.
+__device__ __forceinline__ float sampler_update(float eu, float ec, float x, float q1, float q2, float q3, float z, const SamplerStep& c, float* q) {
+    const float e = eu + (ec - eu) * c.scale;
+    *q = c.qx * x + c.qe * e;
+    return c.cx * x + c.ce * e + c.h[0] * q1 + c.h[1] * q2 + c.h[2] * q3 + c.cz * z;
 }
 
 }  // namespace sdmi

@@ -244,6 +244,19 @@ hipError_t launch_img2img_start(const float* z_src, bool from_q8, const float* n
 hipError_t launch_cfg_ddim_masked(const float* eps, float* latent, float* unet_in, long long per_half, DdimCoef c, const float* mask,
                                   const float* z0, const float* e0, hipStream_t s);
 
+// ---- sampler choice (k_sampler.hip) ---------------------------------------------------
+// One step of DDIM(eta) / DPM-Solver++(2M) / PLMS in the linear form sdmi_sampler_coefs returns (f64 on the host, applied as f32):
+//   e = eu + (ec - eu) scale;  q = qx x + qe e;  x' = cx x + ce e + h[0] q_-1 + h[1] q_-2 + h[2] q_-3 + cz z
+// then the optional mask blend of launch_cfg_ddim_masked (blend_prev = sqrt(a_prev), blend_dir = sqrt(1 - a_prev)).  n_hist = how many of the
+// history slots hold a q of this call (the others are not read).  Plain Euler / Euler-ancestral are DDIM at eta = 0 / 1: no kinds of their own.
+struct SamplerStep { float scale, cx, ce, h[3], cz, qx, qe, blend_prev, blend_dir; int n_hist; };
+// eps [2n][hw][4], latent [n][hw][4] in place, unet_in [2n][hw][4].  depth = 0 / 1 / 3 history slots: q_prev[k] = q of k + 1 steps ago
+// ([n][hw][4], read where k < n_hist), q_out receives this step's q (it may be the oldest slot: every thread reads its pixel before it writes it).
+// Noise (cz != 0 only): element i (NCHW order within the image) of image b is normal_draw(noise_key + b, i).  mask / z0 / e0: all or none.
+hipError_t launch_sampler_step(const float* eps, float* latent, float* unet_in, long long per_half, long long hw, SamplerStep c, int depth,
+                               const float* const q_prev[3], float* q_out, uint64_t noise_key, const float* mask, const float* z0, const float* e0,
+                               hipStream_t s);
+
 // ---- bf16-storage variants (k_bf16.hip) ---------------------------------------------------------------
 // Launch geometry of the bf16 GroupNorm passes (statistics, apply, the MXFP8 apply of k_fp8.hip): a sample's hw rows are cut into `chunks` ranges, one workgroup
 // of cq x R threads each (cq = c / 8 columns of 8 channels, R pixel rows per pass).  Round 4 cut by size alone (32 KB per chunk): at the batches of

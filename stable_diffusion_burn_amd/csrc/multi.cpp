@@ -166,12 +166,23 @@ public:
                     for (int i = 0; i < n; ++i)   // noise keyed by the global image index: independent of the device count
                         SDMI_HIP(launch_fill_normal(x0 + (size_t)i * lat_elems, (long long)lat_elems, seed + (uint64_t)(g0 + i), e.stream()));
                 }
+                {   // step noise of a stochastic sampler is keyed by the global image index too
+                    sdmi_sampler sp = e.sampler();
+                    sp.image_base = g0;
+                    e.set_sampler(&sp);
+                }
                 e.sample_latent_dev(ctx, n, T, prompt + n_cond, Tu, scale, n_steps, x0, lat);
                 e.decode_latent_dev(lat, n, (float)(1.0 / 0.18215), nullptr, reinterpret_cast<uint8_t*>(sh.rgb.p));
                 SDMI_HIP(hipMemcpyAsync(rgb_out + (size_t)g0 * img_bytes, sh.rgb.p, (size_t)n * img_bytes, hipMemcpyDeviceToHost, e.stream()));
             }
             call.finish();   // waits for this device's stream (incl. its share of the broadcast and the D2H copy)
         });
+    }
+
+    // sdmi_multi_set_sampler: checked once, then set on every device (sample_image overrides image_base per shard)
+    void set_sampler(const sdmi_sampler* s) {
+        if (s) Engine::check_sampler(*s);
+        for (int r = 0; r < size(); ++r) engine(r).set_sampler(s);
     }
 
     long long broadcasts() const { return broadcasts_; }
@@ -276,6 +287,13 @@ int sdmi_sample_image_sharded(sdmi_multi* m, const float* context, int32_t T, co
     return multi_guard([&] {
         if (!m) throw sdmi::Error(SDMI_ERR_INVALID, "null sdmi_multi");
         m->m->sample_image(context, T, uncond, Tu, scale, n_steps, n_images, init_latents, seed, rgb_out);
+    });
+}
+
+int sdmi_multi_set_sampler(sdmi_multi* m, const sdmi_sampler* sampler) {
+    return multi_guard([&] {
+        if (!m) throw sdmi::Error(SDMI_ERR_INVALID, "null sdmi_multi");
+        m->m->set_sampler(sampler);
     });
 }
 

@@ -2,6 +2,7 @@
 // Translates C arguments to Engine calls, C++ exceptions to sdmi_status codes,
 // and stages host buffers through the device pool for the host-pointer API.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -376,6 +377,73 @@ int sdmi_img2img_timesteps(int32_t total, size_t n_steps, double strength, int32
         *count = (int32_t)k;
         if (capacity < (int32_t)k || !timesteps) throw Error(SDMI_ERR_INVALID, "img2img_timesteps: capacity too small");
         std::memcpy(timesteps, ts.data() + (L - k), k * sizeof(int32_t));
+    });
+}
+
+// ---- sampler choice ----------------------------------------------------------------------------------
+int sdmi_set_sampler(sdmi_ctx* ctx, const sdmi_sampler* sampler) {
+    return guarded([&] { eng(ctx).set_sampler(sampler); });
+}
+
+int sdmi_get_sampler(sdmi_ctx* ctx, sdmi_sampler* out) {
+    return guarded([&] {
+        if (!out) throw Error(SDMI_ERR_INVALID, "get_sampler: null output");
+        *out = eng(ctx).sampler();
+    });
+}
+
+// The one implementation of the three samplers' rules (include/sdmi.h "sampler choice"): everything in f64.  With sc = sqrt(cur),
+// sn = sqrt(1 - cur), sp = sqrt(prev):  x0 = x / sc - (sn / sc) e.
+int sdmi_sampler_coefs(const sdmi_sampler* sampler, const float* alphas_cumprod, int32_t total, const int32_t* ts, int32_t count,
+                       int64_t step_size, double* coefs) {
+    return guarded([&] {
+        if (!sampler || !alphas_cumprod || !ts || !coefs) throw Error(SDMI_ERR_INVALID, "sampler_coefs: null pointer");
+        Engine::check_sampler(*sampler);
+        if (total <= 0 || count <= 0 || step_size < 1) throw Error(SDMI_ERR_INVALID, "sampler_coefs: total, count and step_size must be positive");
+        for (int32_t j = 0; j < count; ++j)
+            if (ts[j] < 0 || ts[j] >= total) throw Error(SDMI_ERR_INVALID, "sampler_coefs: timestep outside [0, total)");
+        auto lambda = [](double a) { return 0.5 * std::log(a / (1.0 - a)); };
+        static const double AB[4][4] = {{1.0, 0.0, 0.0, 0.0}, {3.0 / 2, -1.0 / 2, 0.0, 0.0}, {23.0 / 12, -16.0 / 12, 5.0 / 12, 0.0},
+                                        {55.0 / 24, -59.0 / 24, 37.0 / 24, -9.0 / 24}};
+        for (int32_t j = 0; j < count; ++j) {
+            const int64_t t = ts[j];
+            const double cur = (double)alphas_cumprod[t];
+            const double prev = t >= step_size ? (double)alphas_cumprod[t - step_size] : 1.0;
+            const double sc = std::sqrt(cur), sn = std::sqrt(1.0 - cur), sp = std::sqrt(prev);
+            double* k = coefs + (size_t)j * 8;
+            for (int i = 0; i < 8; ++i) k[i] = 0.0;
+            if (sampler->kind == 0) {
+                const double sigma = sampler->eta * std::sqrt((1.0 - prev) / (1.0 - cur)) * std::sqrt(1.0 - cur / prev);
+                const double dir = std::sqrt(1.0 - prev - sigma * sigma);
+                k[0] = sp / sc;
+                k[1] = dir - sp * sn / sc;
+                k[5] = sigma;                                   // exactly 0 where eta = 0 or prev = 1
+            } else if (sampler->kind == 1) {
+                const double qx = 1.0 / sc, qe = -sn / sc;      // q = x0
+                k[6] = qx; k[7] = qe;
+                if (prev >= 1.0) {                              // the limit h -> inf: x' = x0, the weight on x itself exactly 0
+                    k[0] = qx; k[1] = qe;
+                } else {
+                    const double h = lambda(prev) - lambda(cur);
+                    const double A = std::sqrt((1.0 - prev) / (1.0 - cur)), B = -sp * std::expm1(-h);
+                    double w0 = 1.0, w1 = 0.0;
+                    if (j > 0) {
+                        const double r = (lambda(cur) - lambda((double)alphas_cumprod[ts[j - 1]])) / h;
+                        w0 = 1.0 + 1.0 / (2.0 * r);
+                        w1 = -1.0 / (2.0 * r);
+                    }
+                    k[0] = A + B * w0 * qx;
+                    k[1] = B * w0 * qe;
+                    k[2] = B * w1;
+                }
+            } else {
+                const double ce = std::sqrt(1.0 - prev) - sp * sn / sc;   // the eta = 0 update's weight on e, spread over e' = sum w e_-i
+                const double* w = AB[j < 3 ? j : 3];
+                k[0] = sp / sc;
+                k[1] = ce * w[0]; k[2] = ce * w[1]; k[3] = ce * w[2]; k[4] = ce * w[3];
+                k[7] = 1.0;                                     // q = e
+            }
+        }
     });
 }
 

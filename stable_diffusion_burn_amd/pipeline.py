@@ -23,7 +23,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _capi
-from ._capi import SdmiConfig, SdmiError, SdmiOpView, check, load_library
+from ._capi import SdmiConfig, SdmiError, SdmiOpView, SdmiSampler, check, load_library
 
 def mpk_list(path) -> list:
     """[(dump name, shape, file offset)] of a Burn .mpk record, parsed by the C++ reader (host only, no GPU)."""
@@ -51,7 +51,36 @@ def img2img_timesteps(n_steps: int, strength: float, total: int = 1000) -> list:
     return list(buf[:count.value])
 
 
-__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "img2img_timesteps", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
+SAMPLER_KINDS = ("ddim", "dpmpp_2m", "plms")   # sdmi_sampler.kind 0, 1, 2 (plain Euler = "ddim" at eta 0, Euler-ancestral = "ddim" at eta 1)
+
+
+def _sampler_struct(kind, eta=0.0, noise_seed=0, image_base=0) -> SdmiSampler:
+    if kind not in SAMPLER_KINDS:
+        raise ValueError(f"sampler kind must be one of {SAMPLER_KINDS}, got {kind!r}")
+    eta = float(eta)
+    if not 0.0 <= eta <= 1.0:   # NaN fails too
+        raise ValueError(f"eta must satisfy 0 <= eta <= 1, got {eta}")
+    if eta != 0.0 and kind != "ddim":
+        raise ValueError("eta belongs to the ddim sampler only")
+    s = SdmiSampler()
+    s.kind, s.eta, s.noise_seed, s.image_base = SAMPLER_KINDS.index(kind), eta, int(noise_seed) & 0xFFFFFFFFFFFFFFFF, int(image_base)
+    return s
+
+
+def sampler_coefs(kind: str, eta: float, alphas_cumprod, ts, step_size: int) -> np.ndarray:
+    """The per-step coefficients [len(ts), 8] = (cx, ce, h1, h2, h3, cz, qx, qe) of a sampler over the timesteps `ts` a call runs
+    (sdmi_sampler_coefs, host only, no GPU; float64):  q = qx x + qe e,  x' = cx x + ce e + h1 q_-1 + h2 q_-2 + h3 q_-3 + cz z."""
+    lib = load_library()
+    s = _sampler_struct(kind, eta)
+    a = np.ascontiguousarray(alphas_cumprod, dtype=np.float32)
+    t = np.ascontiguousarray(ts, dtype=np.int32)
+    out = np.empty((t.size, 8), dtype=np.float64)
+    check(lib.sdmi_sampler_coefs(C.byref(s), _fp(a), a.size, t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, int(step_size),
+                                 out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "img2img_timesteps", "sampler_coefs", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
 
 
 @dataclass(frozen=True)
@@ -217,6 +246,22 @@ class StableDiffusion:
         """Name the HIP stream (integer handle, e.g. torch.cuda.current_stream().cuda_stream) the caller's device
         buffers of the *_dev calls are produced / consumed on (sdmi_set_stream)."""
         check(self._lib.sdmi_set_stream(self._ctx, C.c_void_p(int(hip_stream) if hip_stream else 0), 1 if enable else 0))
+
+    def set_sampler(self, kind="ddim", eta: float = 0.0, noise_seed: int = 0, image_base: int = 0) -> None:
+        """Choose the sampler of every later sampling call of this context (sdmi_set_sampler; sticky): "ddim" with 0 <= eta <= 1
+        (eta = 0, the default: the reference's deterministic DDIM = plain Euler; eta = 1 = Euler-ancestral), "dpmpp_2m"
+        (DPM-Solver++(2M)) or "plms".  None restores the default.  noise_seed keys the step noise of eta > 0; image_base is the global
+        index of the call's first image, so that a batch split into smaller calls draws the same noise per image."""
+        if kind is None:
+            check(self._lib.sdmi_set_sampler(self._ctx, None))
+            return
+        s = _sampler_struct(kind, eta, noise_seed, image_base)
+        check(self._lib.sdmi_set_sampler(self._ctx, C.byref(s)))
+
+    def get_sampler(self) -> dict:
+        s = SdmiSampler()
+        check(self._lib.sdmi_get_sampler(self._ctx, C.byref(s)))
+        return {"kind": SAMPLER_KINDS[s.kind], "eta": s.eta, "noise_seed": s.noise_seed, "image_base": s.image_base}
 
     def load_weights(self, provider, clip: bool = True, vae_encoder: bool = True) -> None:
         """Pull every tensor from `provider.get(name, shape, kind, fan_in)`
@@ -743,6 +788,15 @@ class MultiStableDiffusion:
                                                   None if x0 is None else _fp(x0), int(seed),
                                                   out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
+
+    def set_sampler(self, kind="ddim", eta: float = 0.0, noise_seed: int = 0) -> None:
+        """StableDiffusion.set_sampler on every device (sdmi_multi_set_sampler); each shard's image_base is the global index of its
+        first image, so the step noise does not depend on the device count.  None restores the default."""
+        if kind is None:
+            check(self._lib.sdmi_multi_set_sampler(self._m, None))
+            return
+        s = _sampler_struct(kind, eta, noise_seed, 0)
+        check(self._lib.sdmi_multi_set_sampler(self._m, C.byref(s)))
 
     def broadcast_count(self) -> int:
         return int(self._lib.sdmi_multi_broadcast_count(self._m))

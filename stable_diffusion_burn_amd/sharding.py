@@ -26,6 +26,14 @@ def shard_range(global_batch: int, rank: int, world: int) -> range:
     return range(start, start + base + (1 if rank < rem else 0))
 
 
+def set_shard_sampler(sd, global_batch: int, rank: int, world: int, kind="ddim", eta: float = 0.0, noise_seed: int = 0) -> range:
+    """The per-rank launcher's sampler choice: StableDiffusion.set_sampler with image_base = the first global image index of rank's
+    shard, so that the step noise of a stochastic sampler is keyed by the global image index like the start noise.  Returns the shard."""
+    shard = shard_range(global_batch, rank, world)
+    sd.set_sampler(kind, eta=eta, noise_seed=noise_seed, image_base=shard.start)
+    return shard
+
+
 def pack_prompt(cond, uncond):
     """[cond | uncond] as one flat float32 buffer + the two row counts (torch tensors)."""
     import torch
