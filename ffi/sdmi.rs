@@ -84,6 +84,12 @@ extern "C" {
     fn sdmi_multi_set_sampler(m: *mut c_void, sampler: *const SdmiSampler) -> c_int;
     fn sdmi_sampler_coefs(sampler: *const SdmiSampler, alphas_cumprod: *const c_float, total: i32, ts: *const i32, count: i32, step_size: i64,
                           coefs: *mut c_double) -> c_int;
+    fn sdmi_lora_create(ctx: *mut c_void, out: *mut *mut c_void) -> c_int;
+    fn sdmi_lora_add(a: *mut c_void, target: *const c_char, down: *const c_float, up: *const c_float, rank: i32, alpha: c_float) -> c_int;
+    fn sdmi_lora_set_scale(a: *mut c_void, scale: c_double) -> c_int;
+    fn sdmi_lora_get_scale(a: *mut c_void, scale: *mut c_double, n_targets: *mut i32) -> c_int;
+    fn sdmi_lora_destroy(a: *mut c_void) -> c_int;
+    fn sdmi_lora_effective_weight(ctx: *mut c_void, name: *const c_char, out: *mut c_float, n: usize) -> c_int;
     fn sdmi_tokenizer_create(out: *mut *mut c_void, merges_path: *const c_char) -> c_int;
     fn sdmi_tokenizer_destroy(tok: *mut c_void);
     fn sdmi_tokenizer_encode(tok: *const c_void, text: *const c_char, ids: *mut i32, capacity: i32, n_ids: *mut i32) -> c_int;
@@ -132,6 +138,31 @@ impl TokenizerMi355 {
 impl Drop for TokenizerMi355 {
     fn drop(&mut self) {
         unsafe { sdmi_tokenizer_destroy(self.tok) }
+    }
+}
+
+/// One attached LoRA adapter (`sdmi_lora`).  It borrows its context, so it cannot outlive it; dropping it detaches it (`sdmi_lora_destroy` = scale 0 + free).
+pub struct LoraMi355<'a> {
+    a: *mut c_void,
+    _ctx: std::marker::PhantomData<&'a StableDiffusionMi355>,
+}
+
+impl<'a> LoraMi355<'a> {
+    /// Re-merges and re-packs every target of the adapter (`sdmi_lora_set_scale`); blocks until done.
+    pub fn set_scale(&self, scale: f64) -> Result<(), Box<dyn Error>> {
+        if unsafe { sdmi_lora_set_scale(self.a, scale) } != 0 { Err(last_error().into()) } else { Ok(()) }
+    }
+
+    /// (scale, number of targets) (`sdmi_lora_get_scale`).
+    pub fn scale(&self) -> Result<(f64, i32), Box<dyn Error>> {
+        let (mut s, mut n) = (0f64, 0i32);
+        if unsafe { sdmi_lora_get_scale(self.a, &mut s, &mut n) } != 0 { Err(last_error().into()) } else { Ok((s, n)) }
+    }
+}
+
+impl<'a> Drop for LoraMi355<'a> {
+    fn drop(&mut self) {
+        unsafe { sdmi_lora_destroy(self.a); }
     }
 }
 
@@ -192,6 +223,36 @@ impl StableDiffusionMi355 {
         let mut s = SdmiSampler { kind: 0, reserved0: 0, eta: 0.0, noise_seed: 0, image_base: 0, reserved: [0; 4] };
         check(unsafe { sdmi_get_sampler(self.ctx, &mut s) });
         s
+    }
+
+    /// A LoRA adapter merged into the packed weights on the device (`sdmi_lora_*`; no reference counterpart).  The context must
+    /// have been given the option `("keep_masters", "1")` before its weights were loaded.  `targets`: (dump-tree name of a conv / Linear weight,
+    /// down `[rank, in]` / `[rank, cin, k, k]`, up `[out, rank]`, rank, alpha).  The adapter is returned at `scale`; it borrows this context (the
+    /// sampling methods take `&self`, so they stay usable while it lives).
+    pub fn lora_attach(&self, targets: &[(&str, &[f32], &[f32], i32, f32)], scale: f64) -> Result<LoraMi355<'_>, Box<dyn Error>> {
+        let mut a: *mut c_void = std::ptr::null_mut();
+        if unsafe { sdmi_lora_create(self.ctx, &mut a) } != 0 {
+            return Err(last_error().into());
+        }
+        let lora = LoraMi355 { a, _ctx: std::marker::PhantomData };
+        for (name, down, up, rank, alpha) in targets {
+            let n = CString::new(*name)?;
+            if unsafe { sdmi_lora_add(lora.a, n.as_ptr(), down.as_ptr(), up.as_ptr(), *rank, *alpha) } != 0 {
+                return Err(last_error().into());   // dropping `lora` frees what was added
+            }
+        }
+        lora.set_scale(scale)?;
+        Ok(lora)
+    }
+
+    /// The fp32 tensor (reference layout, `n` elements) currently packed for a conv / Linear weight (`sdmi_lora_effective_weight`).
+    pub fn effective_weight(&self, name: &str, n: usize) -> Result<Vec<f32>, Box<dyn Error>> {
+        let c = CString::new(name)?;
+        let mut out = vec![0f32; n];
+        if unsafe { sdmi_lora_effective_weight(self.ctx, c.as_ptr(), out.as_mut_ptr(), n) } != 0 {
+            return Err(last_error().into());
+        }
+        Ok(out)
     }
 
     /// The per-step coefficients `[ts.len()][8]` = cx, ce, h1, h2, h3, cz, qx, qe of a sampler (`sdmi_sampler_coefs`, host only).

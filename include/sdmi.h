@@ -237,6 +237,34 @@ int sdmi_get_sampler(sdmi_ctx* ctx, sdmi_sampler* out);
 int sdmi_sampler_coefs(const sdmi_sampler* sampler, const float* alphas_cumprod, int32_t total, const int32_t* ts, int32_t count,
                        int64_t step_size, double* coefs);
 
+/* ---- LoRA adapters: low-rank deltas merged into the packed weights on the device (no reference counterpart) ----
+ * The reference runs the base checkpoint only.  An adapter is a set of targets -- conv or Linear weights named by their dump-tree path -- each
+ * with two factors; at scale s the context computes with
+ *     W = W0 + sum_a c_a (up_a . down_a),   c_a = (float)(s_a alpha_a / rank_a) formed in f64,   a = the adapters on that tensor with c_a != 0,
+ * in creation order, all arithmetic fp32 (csrc/k_lora.hip), and re-packs W through the routine the loader uses: at every precision the result is,
+ * bit for bit, what sdmi_set_weight of that fp32 W packs.  W0 is the fp32 tensor as loaded, which the context keeps only under the engine option
+ * "keep_masters=1" (set before the first weight is loaded; about 3.4 GB for the UNet, 0.5 GB for CLIP at full size): at precision 1 / 2 the device
+ * otherwise holds W0 already rounded to bf16 / MXFP8, to which no delta can be added exactly.  A merge is not part of sampling: no launch of a
+ * sampling call changes, and a tensor without an active adapter is re-packed from W0 itself (scale 0 restores the loaded model bit for bit).
+ * Factor shapes: Linear [in,out]: down [rank,in], up [out,rank].  Conv [cout,cin,k,k]: down [rank,cin,k,k], up [cout,rank].
+ * Adapters belong to one context (with sdmi_multi: attach to every sdmi_multi_ctx); several may share a target, their deltas add. */
+typedef struct sdmi_lora sdmi_lora;      /* owned by its context; freed by sdmi_lora_destroy or sdmi_destroy */
+/* A new adapter with no targets at scale 0.  SDMI_ERR_STATE unless the weights are finalized and "keep_masters=1" was set before they were loaded. */
+int sdmi_lora_create(sdmi_ctx* ctx, sdmi_lora** out);
+/* Adds one target and copies its factors to the device.  Only while the adapter's scale is 0 (SDMI_ERR_STATE otherwise).  SDMI_ERR_INVALID: an unknown
+ * target, a norm / bias / embedding, rank outside 1..256, a non-finite alpha, a target this adapter already has (the factor shapes are the caller's
+ * to get right: the pointers carry none).  SDMI_ERR_UNSUPPORTED: the 3-channel RGB conv_in of the VAE encoder (packed in a padded form). */
+int sdmi_lora_add(sdmi_lora* a, const char* target, const float* down, const float* up, int32_t rank, float alpha);
+/* Re-merges and re-packs every target of `a` with ALL adapters active on it; blocks until done.  A non-finite scale is SDMI_ERR_INVALID and changes nothing. */
+int sdmi_lora_set_scale(sdmi_lora* a, double scale);
+int sdmi_lora_get_scale(sdmi_lora* a, double* scale, int32_t* n_targets);
+/* = sdmi_lora_set_scale(a, 0) + free; `a` is invalid afterwards */
+int sdmi_lora_destroy(sdmi_lora* a);
+/* The fp32 tensor (reference layout) that is currently packed for the conv / Linear weight `name`: W0, or the merge above.  n = its element count
+ * (SDMI_ERR_INVALID otherwise, and for names that are no conv / Linear weight); SDMI_ERR_STATE without "keep_masters=1".  While an adapter with a
+ * non-zero scale holds a tensor, sdmi_set_weight on it is SDMI_ERR_STATE; otherwise sdmi_set_weight replaces W0 as well. */
+int sdmi_lora_effective_weight(sdmi_ctx* ctx, const char* name, float* out, size_t n);
+
 /* qkv_attention (src/model/attention.rs:5-45 == src/backend.rs:88-128; the
  * operator seam of the commented-out `trait Backend`, backend.rs:4-84).
  * q [n,nq,n_state], k,v [n,nk,n_state], mask [>=nq, mask_ld>=nk] additive or

@@ -80,6 +80,12 @@ SIGNATURES = {
     "sdmi_get_sampler": (C.c_int, [_CTX, _SAMPLER]),
     "sdmi_sampler_coefs": (C.c_int, [_SAMPLER, _F, C.c_int32, _I32, C.c_int32, C.c_int64, C.POINTER(C.c_double)]),
     "sdmi_multi_set_sampler": (C.c_int, [C.c_void_p, _SAMPLER]),
+    "sdmi_lora_create": (C.c_int, [_CTX, C.POINTER(C.c_void_p)]),
+    "sdmi_lora_add": (C.c_int, [C.c_void_p, C.c_char_p, _F, _F, C.c_int32, C.c_float]),
+    "sdmi_lora_set_scale": (C.c_int, [C.c_void_p, C.c_double]),
+    "sdmi_lora_get_scale": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), _I32]),
+    "sdmi_lora_destroy": (C.c_int, [C.c_void_p]),
+    "sdmi_lora_effective_weight": (C.c_int, [_CTX, C.c_char_p, _F, C.c_size_t]),
     "sdmi_qkv_attention": (C.c_int, [_CTX, _F, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),
     "sdmi_tokenizer_create": (C.c_int, [C.POINTER(_TOK), C.c_char_p]),
     "sdmi_tokenizer_destroy": (None, [_TOK]),

@@ -269,6 +269,11 @@ Engine::~Engine() { destroy(); }
 void Engine::destroy() noexcept {
     (void)hipSetDevice(cfg_.device);
     if (stream_) (void)hipStreamSynchronize(stream_);
+    for (sdmi_lora* a : loras_) {
+        for (void* p : a->allocs) (void)hipFree(p);
+        delete a;
+    }
+    loras_.clear();
     for (void* p : weight_allocs_) (void)hipFree(p);
     for (auto& p : prof_pending_) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (hipEvent_t e : prof_free_) (void)hipEventDestroy(e);
@@ -660,6 +665,22 @@ void Engine::ensure_arena(int group) {
             off += (count * (e.wdt ? 2 : 4) + 255) / 256 * 256;
         }
     }
+    if (opt_keep_masters_) {   // the fp32 masters of every conv / Linear tensor of the group (the packed q | k | v members included), same slot rule
+        size_t mtotal = 0;
+        for (auto& e : entries_)
+            if (e.group == group && e.kind <= 1) mtotal += (stage_elems(e) * sizeof(float) + 255) / 256 * 256;
+        if (mtotal) {
+            char* mbase = nullptr;
+            SDMI_HIP(hipMalloc((void**)&mbase, mtotal));
+            weight_allocs_.push_back(mbase);
+            size_t off = 0;
+            for (auto& e : entries_) {
+                if (e.group != group || e.kind > 1) continue;
+                e.master = reinterpret_cast<float*>(mbase + off);
+                off += (stage_elems(e) * sizeof(float) + 255) / 256 * 256;
+            }
+        }
+    }
     arena_done_[group] = true;
 }
 
@@ -694,6 +715,60 @@ static size_t entry_count(const WeightEntry& e) {
     return count;
 }
 
+size_t Engine::stage_elems(const WeightEntry& e) {
+    const size_t count = entry_count(e);
+    return (e.kind == 0 && e.dims[1] == 3) ? count / 3 * 4 : count;   // RGB conv_in: a zero 4th input channel
+}
+
+void Engine::pack_entry(WeightEntry& e, float* stage) {
+    const size_t n_stage = stage_elems(e);
+    if (e.pre_scale != 1.f) SDMI_HIP(launch_scale_f32(stage, (long long)n_stage, e.pre_scale, stream_));
+    hipError_t err;
+    if (e.kind == 0) {
+        const int cout = (int)e.dims[0], cin = e.dims[1] == 3 ? 4 : (int)e.dims[1], k = (int)e.dims[2];
+        if (!(cin % 32 == 0 || (cin < 32 && cin % 4 == 0))) throw Error(SDMI_ERR_UNSUPPORTED, "conv Cin must be a multiple of 32, or < 32 and a multiple of 4");
+        err = e.wdt ? launch_pack_conv_weight_bf16(stage, *e.dst, cout, cin, k, k, stream_)
+                    : launch_pack_conv_weight(stage, *e.dst, cout, cin, k, k, stream_);
+        if (err == hipSuccess && e.dst8) {
+            const size_t kp = (size_t)((cin + 127) / 128 * 128) * k * k;
+            if (!*e.dst8) {
+                void *q = nullptr, *sc = nullptr;
+                SDMI_HIP(hipMalloc(&q, (size_t)cout * kp));
+                weight_allocs_.push_back(q);
+                SDMI_HIP(hipMalloc(&sc, (size_t)cout * kp / 32));
+                weight_allocs_.push_back(sc);
+                *e.dst8 = reinterpret_cast<float*>(q);
+                *e.dsts = reinterpret_cast<float*>(sc);
+            }
+            err = launch_pack_conv_weight_fp8(stage, *e.dst8, *e.dsts, cout, cin, k, k, stream_);
+        }
+    } else {
+        err = e.wdt ? launch_pack_linear_weight_bf16(stage, *e.dst, (int)e.dims[0], (int)e.dims[1], stream_)
+                    : launch_pack_linear_weight(stage, *e.dst, (int)e.dims[0], (int)e.dims[1], stream_);
+        if (err == hipSuccess && e.dst8) {
+            const int cin = (int)e.dims[0], cout = (int)e.dims[1];
+            const size_t kp = (size_t)(cin + 127) / 128 * 128;
+            if (!*e.dst8) {
+                void *q = nullptr, *sc = nullptr;
+                SDMI_HIP(hipMalloc(&q, (size_t)cout * kp));
+                weight_allocs_.push_back(q);
+                SDMI_HIP(hipMalloc(&sc, (size_t)cout * kp / 32));
+                weight_allocs_.push_back(sc);
+                *e.dst8 = reinterpret_cast<float*>(q);
+                *e.dsts = reinterpret_cast<float*>(sc);
+            }
+            err = launch_pack_linear_weight_fp8(stage, *e.dst8, *e.dsts, cin, cout, stream_);
+        }
+    }
+    SDMI_HIP(err);
+    if (!e.wdt) {   // the bf16 planes of the packed fp32 rows (k_gemm3x.hip)
+        const long long rows = e.kind == 0 ? e.dims[0] : e.dims[1];
+        const long long K = e.kind == 0 ? (e.dims[1] == 3 ? 4 : e.dims[1]) * e.dims[2] * e.dims[3] : e.dims[0];
+        void* planes = const_cast<void*>(split_planes(*e.dst));
+        if (planes && K % 32 == 0) SDMI_HIP(launch_pack_split3(*e.dst, planes, rows, (int)K, stream_, b3_grouped(rows)));
+    }
+}
+
 // Enqueues the upload + packing of one tensor whose fp32 values (reference layout) the caller has written to the
 // pinned block (half, offset) returned by stage_reserve.
 void Engine::stage_commit(WeightEntry& e, size_t offset, int half) {
@@ -710,54 +785,10 @@ void Engine::stage_commit(WeightEntry& e, size_t offset, int half) {
         SDMI_HIP(hipMemcpyAsync(*e.dst, host, count * sizeof(float), hipMemcpyHostToDevice, stream_));
     } else {
         float* stage = reinterpret_cast<float*>(st.dev[half] + offset);
-        size_t n_stage = count;
-        if (e.kind == 0 && e.dims[1] == 3) n_stage = count / 3 * 4;   // padded on the host by the caller of stage_commit
+        const size_t n_stage = stage_elems(e);   // (the RGB conv_in: padded on the host by the caller of stage_commit)
         SDMI_HIP(hipMemcpyAsync(stage, host, n_stage * sizeof(float), hipMemcpyHostToDevice, stream_));
-        if (e.pre_scale != 1.f) SDMI_HIP(launch_scale_f32(stage, (long long)n_stage, e.pre_scale, stream_));
-        hipError_t err;
-        if (e.kind == 0) {
-            const int cout = (int)e.dims[0], cin = e.dims[1] == 3 ? 4 : (int)e.dims[1], k = (int)e.dims[2];
-            if (!(cin % 32 == 0 || (cin < 32 && cin % 4 == 0))) throw Error(SDMI_ERR_UNSUPPORTED, "conv Cin must be a multiple of 32, or < 32 and a multiple of 4");
-            err = e.wdt ? launch_pack_conv_weight_bf16(stage, *e.dst, cout, cin, k, k, stream_)
-                        : launch_pack_conv_weight(stage, *e.dst, cout, cin, k, k, stream_);
-            if (err == hipSuccess && e.dst8) {
-                const size_t kp = (size_t)((cin + 127) / 128 * 128) * k * k;
-                if (!*e.dst8) {
-                    void *q = nullptr, *sc = nullptr;
-                    SDMI_HIP(hipMalloc(&q, (size_t)cout * kp));
-                    weight_allocs_.push_back(q);
-                    SDMI_HIP(hipMalloc(&sc, (size_t)cout * kp / 32));
-                    weight_allocs_.push_back(sc);
-                    *e.dst8 = reinterpret_cast<float*>(q);
-                    *e.dsts = reinterpret_cast<float*>(sc);
-                }
-                err = launch_pack_conv_weight_fp8(stage, *e.dst8, *e.dsts, cout, cin, k, k, stream_);
-            }
-        } else {
-            err = e.wdt ? launch_pack_linear_weight_bf16(stage, *e.dst, (int)e.dims[0], (int)e.dims[1], stream_)
-                        : launch_pack_linear_weight(stage, *e.dst, (int)e.dims[0], (int)e.dims[1], stream_);
-            if (err == hipSuccess && e.dst8) {
-                const int cin = (int)e.dims[0], cout = (int)e.dims[1];
-                const size_t kp = (size_t)(cin + 127) / 128 * 128;
-                if (!*e.dst8) {
-                    void *q = nullptr, *sc = nullptr;
-                    SDMI_HIP(hipMalloc(&q, (size_t)cout * kp));
-                    weight_allocs_.push_back(q);
-                    SDMI_HIP(hipMalloc(&sc, (size_t)cout * kp / 32));
-                    weight_allocs_.push_back(sc);
-                    *e.dst8 = reinterpret_cast<float*>(q);
-                    *e.dsts = reinterpret_cast<float*>(sc);
-                }
-                err = launch_pack_linear_weight_fp8(stage, *e.dst8, *e.dsts, cin, cout, stream_);
-            }
-        }
-        SDMI_HIP(err);
-        if (!e.wdt) {   // the bf16 planes of the packed fp32 rows (k_gemm3x.hip)
-            const long long rows = e.kind == 0 ? e.dims[0] : e.dims[1];
-            const long long K = e.kind == 0 ? (e.dims[1] == 3 ? 4 : e.dims[1]) * e.dims[2] * e.dims[3] : e.dims[0];
-            void* planes = const_cast<void*>(split_planes(*e.dst));
-            if (planes && K % 32 == 0) SDMI_HIP(launch_pack_split3(*e.dst, planes, rows, (int)K, stream_, b3_grouped(rows)));
-        }
+        if (e.master) SDMI_HIP(hipMemcpyAsync(e.master, stage, n_stage * sizeof(float), hipMemcpyDeviceToDevice, stream_));
+        pack_entry(e, stage);
     }
     e.set = true;
     finalized_ = false;
@@ -824,6 +855,9 @@ void Engine::set_weight(const char* name, const float* data, int ndim, const int
         os << "]";
         throw Error(SDMI_ERR_WEIGHTS, os.str());
     }
+    // a tensor under an active adapter is refused here, before anything is staged (the bulk loaders refuse at their start: lora_refuse_bulk_load)
+    if (e.master && lora_active_on(it->second))
+        throw Error(SDMI_ERR_STATE, std::string("set_weight: '") + name + "' carries a LoRA adapter with a non-zero scale: set its scale to 0 first");
     SDMI_HIP(hipSetDevice(cfg_.device));
     upload_weight(e, data);   // data is copied into the pinned ring before this returns: the caller may free it
 }
@@ -838,6 +872,7 @@ size_t Engine::packed_size(int groups) const {
 void Engine::load_weights_packed(const float* data, size_t n_floats, int groups) {
     if (!data) throw Error(SDMI_ERR_INVALID, "load_weights_packed: null pointer");
     if (groups <= 0 || groups > 7) throw Error(SDMI_ERR_INVALID, "load_weights_packed: groups is a bit mask of 1 (hot path), 2 (CLIP), 4 (VAE encoder)");
+    lora_refuse_bulk_load("load_weights_packed");
     if (n_floats != packed_size(groups)) throw Error(SDMI_ERR_WEIGHTS, "load_weights_packed: expected " + std::to_string(packed_size(groups)) + " floats, got " + std::to_string(n_floats));
     SDMI_HIP(hipSetDevice(cfg_.device));
     size_t off = 0;
@@ -855,6 +890,7 @@ void Engine::load_weights_packed(const float* data, size_t n_floats, int groups)
 void Engine::load_weights_mpk(const char* path) {
     if (!path) throw Error(SDMI_ERR_INVALID, "load_weights_mpk: null path");
     SDMI_HIP(hipSetDevice(cfg_.device));
+    lora_refuse_bulk_load("load_weights_mpk");
     MpkFile f(path);
     size_t used = 0;
     for (const MpkTensor& t : f.tensors()) {
@@ -900,6 +936,168 @@ void Engine::finalize_weights() {
     finalized_ = true;
 }
 
+// =============================================================================
+// LoRA adapters (include/sdmi.h "LoRA adapters")
+// =============================================================================
+// A merge rewrites packed weights outside any sampling call: W0 (the fp32 master, option keep_masters) + the deltas of the adapters active on a tensor go
+// through launch_lora_merge into a pool buffer, and pack_entry -- the loader's own routine -- packs that buffer.  finalized_ / clip_ready_ / enc_ready_ are
+// not touched, the pinned ring (released by finalize_weights) is not used.  No device tensor is derived from more than one entry at load time (the packed
+// q | k | v regions are three entries' slots side by side, each with its own planes / MXFP8 rows; finalize_weights derives nothing), so re-packing the
+// entry is all there is to re-derive.
+bool Engine::lora_owned(const sdmi_lora* a) const { return a && std::find(loras_.begin(), loras_.end(), a) != loras_.end(); }
+
+bool Engine::lora_active_on(int entry) const {
+    for (const sdmi_lora* a : loras_) {
+        if (a->scale == 0) continue;
+        for (const LoraTarget& t : a->targets)
+            if (t.entry == entry) return true;
+    }
+    return false;
+}
+
+// a bulk load replaces every master: refused as a whole, before the first tensor is staged, while any adapter is merged in
+void Engine::lora_refuse_bulk_load(const char* what) const {
+    for (const sdmi_lora* a : loras_)
+        if (a->scale != 0 && !a->targets.empty())
+            throw Error(SDMI_ERR_STATE, std::string(what) + ": a LoRA adapter with a non-zero scale is attached: set its scale to 0 first");
+}
+
+sdmi_lora* Engine::lora_create() {
+    if (!finalized_) throw Error(SDMI_ERR_STATE, "lora_create: weights not finalized");
+    if (!opt_keep_masters_) throw Error(SDMI_ERR_STATE, "lora_create: the context keeps no fp32 master weights (option keep_masters=1, set before the weights are loaded)");
+    sdmi_lora* a = new sdmi_lora{};
+    a->engine = this;
+    loras_.push_back(a);
+    return a;
+}
+
+void Engine::lora_add(sdmi_lora* a, const char* target, const float* down, const float* up, int rank, float alpha) {
+    if (!lora_owned(a)) throw Error(SDMI_ERR_INVALID, "lora_add: not an adapter of this context");
+    if (!target || !down || !up) throw Error(SDMI_ERR_INVALID, "lora_add: null argument");
+    if (a->scale != 0) throw Error(SDMI_ERR_STATE, "lora_add: targets are added while the adapter's scale is 0");
+    auto it = entry_index_.find(target);
+    if (it == entry_index_.end()) throw Error(SDMI_ERR_INVALID, std::string("lora_add: unknown tensor '") + target + "'");
+    const WeightEntry& e = entries_[it->second];
+    if (e.kind > 1) throw Error(SDMI_ERR_INVALID, std::string("lora_add: '") + target + "' is not a conv or Linear weight");
+    if (e.kind == 0 && e.dims[1] == 3) throw Error(SDMI_ERR_UNSUPPORTED, std::string("lora_add: '") + target + "' is the 3-channel conv_in, packed in a padded form");
+    if (rank < 1 || rank > 256) throw Error(SDMI_ERR_INVALID, "lora_add: rank must be 1 .. 256");
+    if (!std::isfinite(alpha)) throw Error(SDMI_ERR_INVALID, "lora_add: alpha is not finite");
+    for (const LoraTarget& t : a->targets)
+        if (t.entry == it->second) throw Error(SDMI_ERR_INVALID, std::string("lora_add: the adapter already has '") + target + "'");
+    if (!e.master || !e.set) throw Error(SDMI_ERR_STATE, std::string("lora_add: '") + target + "' is not loaded");
+    // Linear [in, out]: down [rank][in], up [out][rank]; conv [cout][cin][k][k]: down [rank][cin k k], up [cout][rank]
+    const size_t n_in = e.kind == 0 ? (size_t)(e.dims[1] * e.dims[2] * e.dims[3]) : (size_t)e.dims[0];
+    const size_t n_out = e.kind == 0 ? (size_t)e.dims[0] : (size_t)e.dims[1];
+    SDMI_HIP(hipSetDevice(cfg_.device));
+    float* dev = nullptr;
+    SDMI_HIP(hipMalloc((void**)&dev, (size_t)rank * (n_in + n_out) * sizeof(float)));
+    hipError_t err = hipMemcpy(dev, down, (size_t)rank * n_in * sizeof(float), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(dev + (size_t)rank * n_in, up, (size_t)rank * n_out * sizeof(float), hipMemcpyHostToDevice);
+    if (err != hipSuccess) { (void)hipFree(dev); SDMI_HIP(err); }
+    a->allocs.push_back(dev);
+    a->targets.push_back(LoraTarget{it->second, rank, (double)alpha, dev, dev + (size_t)rank * n_in});
+}
+
+void Engine::lora_compose(int entry, float* dst) {
+    const WeightEntry& e = entries_[entry];
+    const size_t n = stage_elems(e);
+    LoraMerge m{};
+    m.R = (int)e.dims[0];   // conv: cout rows of cin k k; Linear: in rows of out
+    m.Cc = (int)(n / (size_t)m.R);
+    m.W0 = e.master; m.W = dst;
+    bool any = false;
+    auto flush = [&] {
+        SDMI_HIP(launch_lora_merge(m, stream_));
+        m.W0 = dst;   // more than kLoraMaxTerms active adapters on one tensor: the next launch continues the sum in place
+        m.n_terms = 0;
+        any = true;
+    };
+    for (const sdmi_lora* a : loras_)
+        for (const LoraTarget& t : a->targets) {
+            if (t.entry != entry) continue;
+            const float coef = (float)(a->scale * t.alpha / (double)t.rank);
+            if (coef == 0.f) continue;
+            LoraTerm& lt = m.t[m.n_terms++];
+            lt.rank = t.rank; lt.coef = coef;
+            if (e.kind == 0) {   // rows = cout: P = up [cout][rank], Q = down [rank][Cc]
+                lt.P = t.up; lt.p_rs = t.rank; lt.p_js = 1;
+                lt.Q = t.down; lt.q_js = m.Cc; lt.q_cs = 1;
+            } else {             // rows = in: P(i, j) = down[j][i], Q(j, o) = up[o][j]
+                lt.P = t.down; lt.p_rs = 1; lt.p_js = m.R;
+                lt.Q = t.up; lt.q_js = 1; lt.q_cs = t.rank;
+            }
+            if (m.n_terms == kLoraMaxTerms) flush();
+        }
+    if (m.n_terms) flush();
+    // no active adapter: W0 itself -- not a merge with zero coefficients, which would turn -0.0 into +0.0
+    if (!any) SDMI_HIP(hipMemcpyAsync(dst, e.master, n * sizeof(float), hipMemcpyDeviceToDevice, stream_));
+}
+
+void Engine::lora_repack(int entry) {
+    WeightEntry& e = entries_[entry];
+    Buf stage(this, stage_elems(e) * sizeof(float));
+    lora_compose(entry, stage.f());
+    pack_entry(e, stage.f());
+}
+
+void Engine::lora_set_scale(sdmi_lora* a, double scale) {
+    if (!lora_owned(a)) throw Error(SDMI_ERR_INVALID, "lora_set_scale: not an adapter of this context");
+    if (!std::isfinite(scale)) throw Error(SDMI_ERR_INVALID, "lora_set_scale: scale is not finite");
+    if (scale == a->scale) return;
+    SDMI_HIP(hipSetDevice(cfg_.device));
+    const double old = a->scale;
+    a->scale = scale;
+    size_t done = 0;
+    try {
+        for (; done < a->targets.size(); ++done) lora_repack(a->targets[done].entry);
+        SDMI_HIP(hipStreamSynchronize(stream_));
+    } catch (...) {
+        // back to the old scale: the targets already re-packed (and the one that failed) are re-packed at it, so that the packed weights, get_scale and
+        // effective_weight agree again.  Best effort: after a HIP error the context is usually lost anyway, and the first error is the one reported.
+        a->scale = old;
+        for (size_t i = 0; i <= done && i < a->targets.size(); ++i) {
+            try { lora_repack(a->targets[i].entry); } catch (...) {}
+        }
+        (void)hipStreamSynchronize(stream_);
+        throw;
+    }
+}
+
+void Engine::lora_destroy(sdmi_lora* a) {
+    if (!lora_owned(a)) throw Error(SDMI_ERR_INVALID, "lora_destroy: not an adapter of this context");
+    lora_set_scale(a, 0.0);
+    SDMI_HIP(hipSetDevice(cfg_.device));
+    for (void* p : a->allocs) (void)hipFree(p);
+    loras_.erase(std::find(loras_.begin(), loras_.end(), a));
+    delete a;
+}
+
+void Engine::effective_weight(const char* name, float* out, size_t n) {
+    if (!name || !out) throw Error(SDMI_ERR_INVALID, "effective_weight: null argument");
+    auto it = entry_index_.find(name);
+    if (it == entry_index_.end()) throw Error(SDMI_ERR_INVALID, std::string("effective_weight: unknown tensor '") + name + "'");
+    const WeightEntry& e = entries_[it->second];
+    if (e.kind > 1) throw Error(SDMI_ERR_INVALID, std::string("effective_weight: '") + name + "' is not a conv or Linear weight");
+    if (n != entry_count(e)) throw Error(SDMI_ERR_INVALID, std::string("effective_weight: '") + name + "' has " + std::to_string(entry_count(e)) + " elements");
+    if (!opt_keep_masters_) throw Error(SDMI_ERR_STATE, "effective_weight: the context keeps no fp32 master weights (option keep_masters=1)");
+    if (!e.master || !e.set) throw Error(SDMI_ERR_STATE, std::string("effective_weight: '") + name + "' is not loaded");
+    SDMI_HIP(hipSetDevice(cfg_.device));
+    const size_t ns = stage_elems(e);
+    Buf stage(this, ns * sizeof(float));
+    lora_compose(it->second, stage.f());
+    if (ns == n) {
+        SDMI_HIP(hipMemcpyAsync(out, stage.p, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+        SDMI_HIP(hipStreamSynchronize(stream_));
+    } else {   // the RGB conv_in: drop the zero 4th input channel
+        std::vector<float> padded(ns);
+        SDMI_HIP(hipMemcpyAsync(padded.data(), stage.p, ns * sizeof(float), hipMemcpyDeviceToHost, stream_));
+        SDMI_HIP(hipStreamSynchronize(stream_));
+        const size_t T = (size_t)(e.dims[2] * e.dims[3]);
+        for (size_t o = 0; o < (size_t)e.dims[0]; ++o)
+            for (size_t c = 0; c < 3; ++c) std::memcpy(out + (o * 3 + c) * T, padded.data() + (o * 4 + c) * T, T * sizeof(float));
+    }
+}
+
 // npy-dump reader: src/model/load.rs:17-28 -- a 1-D float32 .npy whose first D
 // values are the shape and whose remaining values are the row-major data.
 // Returns the number of floats in the file; `sink(n)` supplies the destination for them.
@@ -931,6 +1129,7 @@ static size_t read_npy_f32(const std::string& path, Sink&& sink) {
 void Engine::load_weights_dir(const char* dir) {
     if (!dir) throw Error(SDMI_ERR_INVALID, "load_weights_dir: null path");
     SDMI_HIP(hipSetDevice(cfg_.device));
+    lora_refuse_bulk_load("load_weights_dir");
     // the CLIP subtree is read when it exists (load_stable_diffusion always has it, stablediffusion/load.rs:24)
     const bool have_clip = std::ifstream(std::string(dir) + "/clip/token_embedding/weight.npy").good();
     const bool have_enc = std::ifstream(std::string(dir) + "/autoencoder/encoder/conv_in/weight.npy").good();
@@ -1070,6 +1269,11 @@ void Engine::set_option(const std::string& key, const std::string& value) {
         if (!entries_.empty() && std::any_of(entries_.begin(), entries_.end(), [](const WeightEntry& w) { return w.set; }))
             throw Error(SDMI_ERR_STATE, "b3_grouped selects the layout the weight planes are packed in: set it before the first weight is loaded");
         opt_b3_grouped_ = std::stoi(value);
+    }
+    else if (key == "keep_masters") {
+        if (std::any_of(entries_.begin(), entries_.end(), [](const WeightEntry& w) { return w.set; }) || arena_done_[0] || arena_done_[1] || arena_done_[2])
+            throw Error(SDMI_ERR_STATE, "keep_masters decides what the weight arenas hold: set it before the first weight is loaded");
+        opt_keep_masters_ = std::stoi(value) != 0;
     }
     else if (key == "attn_pack_tail") opt_attn_pack_tail_ = (value == "default") ? 3 : std::stoi(value);
     else if (key == "gn32_min_wgs") opt_gn32_min_wgs_ = (opt_gn32_min_wgs_ & ~0xFFFF) | (std::stoi(value) & 0xFFFF);

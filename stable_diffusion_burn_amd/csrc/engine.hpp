@@ -121,7 +121,12 @@ struct WeightEntry {
     float** dsts = nullptr;
     float pre_scale = 1.f;    // the tensor is multiplied by this in fp32 before it is packed (bf16 / MXFP8 query projections: attn_bf16_q_scale)
     bool set = false;
+    float* master = nullptr;  // option keep_masters, kind 0 / 1: the fp32 tensor as the packing kernels read it (reference layout, RGB conv_in padded to 4 channels, before pre_scale)
 };
+
+// One target of a LoRA adapter (sdmi_lora_add): the factors on the device as the caller stored them -- down [rank][in] / [rank][cin k k],
+// up [out][rank] / [cout][rank] -- in one allocation.
+struct LoraTarget { int entry; int rank; double alpha; float* down; float* up; };
 
 // Per-module scalar / 2-vector files of the dump tree that are not tensors (python/save.py:23-68): `store` != null: the value
 // is honoured (a norm's eps); otherwise it must equal `expect` (the hyper-parameters this engine hard-wires).
@@ -144,6 +149,12 @@ public:
     size_t packed_size(int groups) const;
     void finalize_weights();
     const std::vector<WeightEntry>& entries() const { return entries_; }
+    // LoRA adapters merged into the packed weights on the device (include/sdmi.h "LoRA adapters").  Needs option keep_masters.
+    sdmi_lora* lora_create();
+    void lora_add(sdmi_lora* a, const char* target, const float* down, const float* up, int rank, float alpha);
+    void lora_set_scale(sdmi_lora* a, double scale);
+    void lora_destroy(sdmi_lora* a);
+    void effective_weight(const char* name, float* out, size_t n);
 
     // hot path (device pointers, reference layouts)
     void unet_forward_dev(const float* x_nchw, int t, const float* context, int n, int T, float* out_nchw);
@@ -282,6 +293,18 @@ private:
     const void* temp_split_planes_ = nullptr;
     char* stage_reserve(size_t bytes, size_t* offset, int* half);
     void stage_commit(WeightEntry& e, size_t offset, int half);
+    // THE packing routine, shared by the loader (stage_commit) and a LoRA re-merge (lora_repack): the device fp32 tensor `stage` (reference layout, the padded
+    // element count of stage_elems; clobbered by pre_scale) -> the entry's packed slot, its MXFP8 copy and its bf16 planes.  Enqueues on stream_.
+    void pack_entry(WeightEntry& e, float* stage);
+    static size_t stage_elems(const WeightEntry& e);
+    // option keep_masters: fp32 master copies of every conv / Linear tensor, one arena per weight group laid out like the packed one (ensure_arena)
+    int opt_keep_masters_ = 0;
+    std::vector<sdmi_lora*> loras_;      // in creation order: the order the deltas of a shared target are added in
+    bool lora_owned(const sdmi_lora* a) const;
+    void lora_refuse_bulk_load(const char* what) const;          // SDMI_ERR_STATE while any adapter has a non-zero scale
+    bool lora_active_on(int entry) const;                       // an adapter with a non-zero scale holds this entry
+    void lora_compose(int entry, float* dst);                   // dst (stage_elems floats, device) = W0, or W0 + the active adapters' deltas (launch_lora_merge)
+    void lora_repack(int entry);                                // lora_compose into a pool buffer + pack_entry
     void upload_weight(WeightEntry& e, const float* data);
     void stager_release();
     void ensure_arena(int group);
@@ -539,7 +562,13 @@ void set_last_error(const std::string& msg);   // the thread-local message behin
 
 }  // namespace sdmi
 
-// the opaque handle of include/sdmi.h
+// the opaque handles of include/sdmi.h
 struct sdmi_ctx {
     sdmi::Engine* engine;
+};
+struct sdmi_lora {
+    sdmi::Engine* engine;
+    double scale = 0;
+    std::vector<sdmi::LoraTarget> targets;
+    std::vector<void*> allocs;   // device memory of the factors
 };

@@ -282,4 +282,13 @@ hipError_t launch_nchw_f32_to_nhwc_bf16(const float* src, void* dst, int n, int 
 hipError_t launch_transpose2d_bf16(const void* src, void* dst, int rows, int cols, int src_ld, hipStream_t s);
 hipError_t launch_softmax_rows_f32_to_bf16(const float* x, void* y, int rows, int cols, float scale, hipStream_t s);
 
+// ---- LoRA merge (k_lora.hip) ---------------------------------------------------------------------------------
+// W[r][c] = W0[r][c] + sum_t coef_t * sum_j P_t(r, j) Q_t(j, c) over a row-major [R][Cc] fp32 tensor, terms in order, fp32 throughout.
+// P_t(r, j) = P[r * p_rs + j * p_js], Q_t(j, c) = Q[j * q_js + c * q_cs] (element strides: the factors are read as the caller stored them,
+// whichever way the target's layout turns them).  W may be W0 (every element is read and written by one thread).
+struct LoraTerm { const float* P; const float* Q; long long p_rs, p_js, q_js, q_cs; int rank; float coef; };
+constexpr int kLoraMaxTerms = 8;
+struct LoraMerge { const float* W0; float* W; int R, Cc, n_terms; LoraTerm t[kLoraMaxTerms]; };
+hipError_t launch_lora_merge(const LoraMerge& m, hipStream_t s);
+
 }  // namespace sdmi

@@ -392,6 +392,41 @@ int sdmi_get_sampler(sdmi_ctx* ctx, sdmi_sampler* out) {
     });
 }
 
+// ---- LoRA adapters -------------------------------------------------------------------------------------
+static sdmi_lora& lora(sdmi_lora* a) {
+    if (!a || !a->engine) throw Error(SDMI_ERR_INVALID, "null sdmi_lora");
+    return *a;
+}
+
+int sdmi_lora_create(sdmi_ctx* ctx, sdmi_lora** out) {
+    if (!out) { g_last_error = "sdmi_lora_create: null argument"; return SDMI_ERR_INVALID; }
+    *out = nullptr;
+    return guarded([&] { *out = eng(ctx).lora_create(); });
+}
+
+int sdmi_lora_add(sdmi_lora* a, const char* target, const float* down, const float* up, int32_t rank, float alpha) {
+    return guarded([&] { lora(a).engine->lora_add(a, target, down, up, rank, alpha); });
+}
+
+int sdmi_lora_set_scale(sdmi_lora* a, double scale) {
+    return guarded([&] { lora(a).engine->lora_set_scale(a, scale); });
+}
+
+int sdmi_lora_get_scale(sdmi_lora* a, double* scale, int32_t* n_targets) {
+    return guarded([&] {
+        if (scale) *scale = lora(a).scale;
+        if (n_targets) *n_targets = (int32_t)lora(a).targets.size();
+    });
+}
+
+int sdmi_lora_destroy(sdmi_lora* a) {
+    return guarded([&] { lora(a).engine->lora_destroy(a); });
+}
+
+int sdmi_lora_effective_weight(sdmi_ctx* ctx, const char* name, float* out, size_t n) {
+    return guarded([&] { eng(ctx).effective_weight(name, out, n); });
+}
+
 // The one implementation of the three samplers' rules (include/sdmi.h "sampler choice"): everything in f64.  With sc = sqrt(cur),
 // sn = sqrt(1 - cur), sp = sqrt(prev):  x0 = x / sc - (sn / sc) e.
 int sdmi_sampler_coefs(const sdmi_sampler* sampler, const float* alphas_cumprod, int32_t total, const int32_t* ts, int32_t count,

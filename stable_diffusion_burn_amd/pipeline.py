@@ -80,7 +80,143 @@ def sampler_coefs(kind: str, eta: float, alphas_cumprod, ts, step_size: int) -> 
     return out
 
 
-__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "img2img_timesteps", "sampler_coefs", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
+def load_lora_npz(path) -> dict:
+    """{target: (down, up, alpha)} from an .npz holding "<target>::down", "<target>::up" and "<target>::alpha" per target (dump-tree
+    names of conv / Linear weights; Linear [in,out]: down [rank,in], up [out,rank]; conv [cout,cin,k,k]: down [rank,cin,k,k], up [cout,rank]) --
+    what StableDiffusion.lora_attach takes.  save_lora_npz writes it."""
+    out = {}
+    with np.load(str(path)) as z:
+        keys = set(z.files)
+        for key in sorted(keys):
+            target, sep, part = key.rpartition("::")
+            if not sep or part not in ("down", "up", "alpha"):
+                raise ValueError(f"{path}: unexpected entry '{key}' (expected '<target>::down|up|alpha')")
+            if part != "down":
+                continue
+            missing = [q for q in ("up", "alpha") if f"{target}::{q}" not in keys]
+            if missing:
+                raise ValueError(f"{path}: '{target}' lacks {missing}")
+            alpha = np.asarray(z[f"{target}::alpha"], dtype=np.float64)
+            if alpha.size != 1:
+                raise ValueError(f"{path}: '{target}::alpha' must be one number")
+            out[target] = (np.asarray(z[key], dtype=np.float32), np.asarray(z[f"{target}::up"], dtype=np.float32), float(alpha.reshape(())))
+        for key in keys:
+            if key.rpartition("::")[0] not in out:
+                raise ValueError(f"{path}: '{key}' has no '::down' partner")
+    return out
+
+
+def save_lora_npz(path, tensors: dict) -> None:
+    """The inverse of load_lora_npz."""
+    flat = {}
+    for target, (down, up, alpha) in tensors.items():
+        flat[f"{target}::down"] = np.asarray(down, dtype=np.float32)
+        flat[f"{target}::up"] = np.asarray(up, dtype=np.float32)
+        flat[f"{target}::alpha"] = np.float32(alpha)
+    np.savez(str(path), **flat)
+
+
+LORA_MAX_RANK = 256
+
+
+def check_lora_tensors(tensors, shapes: dict) -> list:
+    """The argument checks of lora_attach (before anything reaches the library): [(target, down, up, rank, alpha)] as contiguous float32.
+    `shapes` = dict(weight_specs())."""
+    if not isinstance(tensors, dict) or not tensors:
+        raise ValueError("lora tensors must be a non-empty dict {target: (down, up, alpha)}")
+    out = []
+    for target, item in tensors.items():
+        if target not in shapes:
+            raise ValueError(f"lora target '{target}' is not a tensor of this model")
+        shape = tuple(shapes[target])
+        if not target.endswith("/weight") or len(shape) not in (2, 4) or "embedding" in target:
+            raise ValueError(f"lora target '{target}' is not a conv or Linear weight")
+        try:
+            down, up, alpha = item
+        except (TypeError, ValueError):
+            raise ValueError(f"lora target '{target}': expected (down, up, alpha)") from None
+        down, up, alpha = _f32(down, name=f"{target} down"), _f32(up, name=f"{target} up"), float(alpha)
+        if not np.isfinite(alpha):
+            raise ValueError(f"lora target '{target}': alpha must be finite, got {alpha}")
+        rank = down.shape[0] if down.ndim else 0
+        if not 1 <= rank <= LORA_MAX_RANK:
+            raise ValueError(f"lora target '{target}': rank must be 1..{LORA_MAX_RANK}, got {rank}")
+        if len(shape) == 4:
+            if shape[1] == 3:
+                raise ValueError(f"lora target '{target}': the 3-channel conv_in is not supported")
+            want_down, want_up = (rank,) + shape[1:], (shape[0], rank)
+        else:
+            want_down, want_up = (rank, shape[0]), (shape[1], rank)
+        if down.shape != want_down:
+            raise ValueError(f"lora target '{target}' {shape}: down must be {want_down}, got {down.shape}")
+        if up.shape != want_up:
+            raise ValueError(f"lora target '{target}' {shape}: up must be {want_up}, got {up.shape}")
+        out.append((target, down, up, rank, alpha))
+    return out
+
+
+class LoraAdapter:
+    """One adapter attached to a StableDiffusion (sdmi_lora): .set_scale(s) re-merges its targets on the device, .scale reads it back,
+    .detach() restores the targets and frees it.  Owned by the context: closing the StableDiffusion invalidates it."""
+
+    def __init__(self, sd: "StableDiffusion", handle):
+        self._sd, self._a = sd, handle
+
+    def _handle(self):
+        if self._a is None or not self._sd._ctx.value:
+            raise ValueError("this adapter is detached (or its context is closed)")
+        return self._a
+
+    def set_scale(self, scale: float) -> None:
+        s = float(scale)
+        if not np.isfinite(s):
+            raise ValueError(f"lora scale must be finite, got {scale}")
+        check(self._sd._lib.sdmi_lora_set_scale(self._handle(), s))
+
+    @property
+    def scale(self) -> float:
+        s, n = C.c_double(), C.c_int32()
+        check(self._sd._lib.sdmi_lora_get_scale(self._handle(), C.byref(s), C.byref(n)))
+        return s.value
+
+    @property
+    def n_targets(self) -> int:
+        s, n = C.c_double(), C.c_int32()
+        check(self._sd._lib.sdmi_lora_get_scale(self._handle(), C.byref(s), C.byref(n)))
+        return n.value
+
+    def detach(self) -> None:
+        if self._a is not None and self._sd._ctx.value:
+            a, self._a = self._a, None
+            check(self._sd._lib.sdmi_lora_destroy(a))
+        self._a = None
+
+
+class MultiLoraAdapter:
+    """The same adapter on every device of a MultiStableDiffusion."""
+
+    def __init__(self, parts, owner=None):
+        self._parts = list(parts)
+        self._owner = owner
+
+    def set_scale(self, scale: float) -> None:
+        for p in self._parts:
+            p.set_scale(scale)
+
+    @property
+    def scale(self) -> float:
+        return self._parts[0].scale
+
+    def detach(self) -> None:
+        for p in self._parts:
+            p.detach()
+        if self._owner is not None:      # the owner no longer has to invalidate these device views when it closes
+            views = {id(p._sd) for p in self._parts}
+            self._owner._lora_views = [v for v in self._owner._lora_views if id(v) not in views]
+            self._owner = None
+
+
+__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "img2img_timesteps", "sampler_coefs", "load_lora_npz", "save_lora_npz", "LoraAdapter", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
 
 
 @dataclass(frozen=True)
@@ -262,6 +398,37 @@ class StableDiffusion:
         s = SdmiSampler()
         check(self._lib.sdmi_get_sampler(self._ctx, C.byref(s)))
         return {"kind": SAMPLER_KINDS[s.kind], "eta": s.eta, "noise_seed": s.noise_seed, "image_base": s.image_base}
+
+    # ---- LoRA adapters (include/sdmi.h "LoRA adapters") ----------------
+    def lora_attach(self, tensors, scale: float = 1.0) -> LoraAdapter:
+        """Attach a LoRA adapter and merge it at `scale`: tensors = {target: (down, up, alpha)} (load_lora_npz), the effective weight of each
+        target becomes W0 + scale * alpha / rank * up @ down, merged and re-packed on the device.  The context must have been given
+        set_option("keep_masters", 1) before its weights were loaded.  Returns the adapter (.set_scale(s), .scale, .detach())."""
+        items = check_lora_tensors(tensors, dict(self.weight_specs()))
+        s = float(scale)
+        if not np.isfinite(s):
+            raise ValueError(f"lora scale must be finite, got {scale}")
+        h = C.c_void_p()
+        check(self._lib.sdmi_lora_create(self._ctx, C.byref(h)))
+        adapter = LoraAdapter(self, h)
+        try:
+            for target, down, up, rank, alpha in items:
+                check(self._lib.sdmi_lora_add(h, target.encode(), _fp(down), _fp(up), rank, alpha))
+            adapter.set_scale(s)
+        except Exception:
+            adapter.detach()
+            raise
+        return adapter
+
+    def effective_weight(self, name: str) -> np.ndarray:
+        """The fp32 tensor (reference layout) currently packed for the conv / Linear weight `name`: the loaded one, or the merge of the
+        adapters active on it (sdmi_lora_effective_weight; needs keep_masters)."""
+        shapes = dict(self.weight_specs())
+        if name not in shapes:
+            raise ValueError(f"'{name}' is not a tensor of this model")
+        out = np.empty(shapes[name], dtype=np.float32)
+        check(self._lib.sdmi_lora_effective_weight(self._ctx, name.encode(), _fp(out), out.size))
+        return out
 
     def load_weights(self, provider, clip: bool = True, vae_encoder: bool = True) -> None:
         """Pull every tensor from `provider.get(name, shape, kind, fan_in)`
@@ -743,9 +910,12 @@ class MultiStableDiffusion:
         self._m = C.c_void_p()
         check(self._lib.sdmi_create_multi(C.byref(self._m), C.byref(cfg), devs, len(devices)))
         self.devices = tuple(devices)
+        self._lora_views = []      # device views that carry a live adapter (lora_attach): invalidated by close()
 
     def close(self):
         if getattr(self, "_m", None) is not None and self._m.value:
+            for v in self._lora_views:   # their adapters die with the device contexts
+                v._ctx = C.c_void_p()
             self._lib.sdmi_destroy_multi(self._m)
             self._m = C.c_void_p()
 
@@ -797,6 +967,19 @@ class MultiStableDiffusion:
             return
         s = _sampler_struct(kind, eta, noise_seed, 0)
         check(self._lib.sdmi_multi_set_sampler(self._m, C.byref(s)))
+
+    def lora_attach(self, tensors, scale: float = 1.0) -> MultiLoraAdapter:
+        """StableDiffusion.lora_attach on every device (adapters are per device context; each needs keep_masters before its weights are loaded)."""
+        parts = []
+        try:
+            for i in range(len(self.devices)):
+                parts.append(self.device_view(i).lora_attach(tensors, scale))
+        except Exception:
+            for p in parts:
+                p.detach()
+            raise
+        self._lora_views.extend(p._sd for p in parts)
+        return MultiLoraAdapter(parts, self)
 
     def broadcast_count(self) -> int:
         return int(self._lib.sdmi_multi_broadcast_count(self._m))
