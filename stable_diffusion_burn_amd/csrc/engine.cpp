@@ -238,25 +238,7 @@ Engine::Engine(const sdmi_config& cfg) : cfg_(cfg) {
     weight_allocs_.push_back(zero_page_);
     SDMI_HIP(hipMemsetAsync(zero_page_, 0, 256, stream_));
     SDMI_HIP(hipStreamSynchronize(stream_));
-    {   // measured per-shape tile choices (tools/autotune.py -> tuning/gfx950_fp32.txt)
-        struct Row { const char* key; int cfg; int splits; };
-        static const Row rows[] = {
-#include "tuning_table.inc"
-            {nullptr, 0, 0}};
-        for (const Row* r = rows; r->key; ++r) tuned_[r->key] = TileChoice{r->cfg, r->splits};
-        static const Row rows_mfma[] = {
-#include "tuning_table_mfma.inc"
-            {nullptr, 0, 0}};
-        for (const Row* r = rows_mfma; r->key; ++r) tuned_mfma_[r->key] = TileChoice{r->cfg, r->splits};
-        static const Row rows_p[] = {
-#include "tuning_table_planes.inc"
-            {nullptr, 0, 0}};
-        for (const Row* r = rows_p; r->key; ++r) tuned_p_[r->key] = TileChoice{r->cfg, r->splits};
-        static const Row rows16[] = {
-#include "tuning_table_bf16.inc"
-            {nullptr, 0, 0}};
-        for (const Row* r = rows16; r->key; ++r) tuned_bf16_[r->key] = TileChoice{r->cfg, r->splits};
-    }
+    tuning_.load_builtin();   // measured per-shape tile choices (tools/autotune.py -> tuning/gfx950_*.txt)
     build_model();
     } catch (...) {   // the destructor does not run for a half-built object
         destroy();
@@ -1253,8 +1235,8 @@ void Engine::abort_call() noexcept {
 }
 
 void Engine::set_option(const std::string& key, const std::string& value) {
-    if (key == "gemm_tile") opt_force_tile_ = (value == "auto") ? -1 : std::stoi(value);
-    else if (key == "splitk") opt_force_splits_ = std::stoi(value);
+    if (key == "gemm_tile") gopt_.force_tile = (value == "auto") ? -1 : std::stoi(value);
+    else if (key == "splitk") gopt_.force_splits = std::stoi(value);
     else if (key == "roctx") roctx_enable(std::stoi(value) != 0);
     else if (key == "fp8_convs") opt_fp8_convs_ = std::stoi(value);
     else if (key == "fp8_min_rows") opt_fp8_min_rows_ = std::stoi(value);
@@ -1286,13 +1268,13 @@ void Engine::set_option(const std::string& key, const std::string& value) {
     else if (key == "attn_bf16") opt_attn_bf16_ = std::stoi(value);
     else if (key == "attn_bf16_variant") opt_attn_bf16_variant_ = (value == "default") ? kAttnBf16VariantDefault : std::stoi(value, nullptr, 0);
     else if (key == "attn_split") opt_attn_split_ = std::stoi(value);
-    else if (key == "gemm_bf16x") opt_gemm_bf16x_ = std::stoi(value);
-    else if (key == "gemm_x32") opt_gemm_x32_ = std::stoi(value);
-    else if (key == "gemm_f32s") opt_gemm_f32s_ = std::stoi(value);
+    else if (key == "gemm_bf16x") gopt_.gemm_bf16x = std::stoi(value);
+    else if (key == "gemm_x32") gopt_.gemm_x32 = std::stoi(value);
+    else if (key == "gemm_f32s") gopt_.gemm_f32s = std::stoi(value);
     else if (key == "bench_cold") opt_bench_cold_ = std::stoi(value);
     else if (key == "gemm_probe") opt_gemm_probe_ = std::stoi(value);
-    else if (key == "conv3_reuse") opt_conv3_reuse_ = std::stoi(value);
-    else if (key == "gemm_planes") opt_gemm_planes_ = (value == "default") ? kGemmPlanesDefault : std::stoi(value);
+    else if (key == "conv3_reuse") gopt_.conv3_reuse = std::stoi(value);
+    else if (key == "gemm_planes") gopt_.gemm_planes = (value == "default") ? GemmPlanOpts().gemm_planes : std::stoi(value);
     else if (key == "gemm3x_variant") opt_gemm3x_variant_ = (value == "default") ? kGemm3xVariantDefault : std::stoi(value);
     else if (key == "gemm_bf16x_variant") opt_gemm_bf16x_variant_ = (value == "default") ? kGemmBf16xVariantDefault : std::stoi(value);
     else if (key == "geglu_fuse") opt_geglu_fuse_ = std::stoi(value);
@@ -1315,141 +1297,9 @@ void Engine::set_option(const std::string& key, const std::string& value) {
         for (auto& kv : prof_tags_) f << kv.second.ms << " " << kv.second.launches << " " << kv.second.flops << " " << kv.second.bytes << "\t" << kv.first << "\n";
     }
     else if (key == "profile_reset") prof_reset();
-    else if (key == "tune" || key == "tune_bf16") {
-        // "M,N,K=cfg,splits" (tune_bf16: cfg 100 + x selects a k_gemm_bf16x.hip tile)
-        const size_t eq = value.find('=');
-        if (eq == std::string::npos) throw Error(SDMI_ERR_INVALID, "tune expects M,N,K=cfg,splits");
-        const bool b16 = key == "tune_bf16";
-        TileChoice tc{0, 1};
-        if (std::sscanf(value.c_str() + eq + 1, "%d,%d", &tc.cfg, &tc.splits) != 2 || tc.cfg < 0 || tc.splits < 1 ||
-            !(tc.cfg < kNumGemmTiles || (tc.cfg >= 100 && tc.cfg < 100 + (b16 ? kNumGemmTilesXB : kNumGemmTilesX)) || (!b16 && tc.cfg >= 200 && tc.cfg < 200 + kNumGemmTilesS) ||
-              (!b16 && tc.cfg >= 300 && tc.cfg < 300 + kNumGemmTilesP)))
-            throw Error(SDMI_ERR_INVALID, "tune: bad value");
-        (b16 ? tuned_bf16_ : (tc.cfg >= 300 ? tuned_p_ : tuned_))[value.substr(0, eq)] = tc;   // plane tiles (300 + x) have their own table: what a GEMM whose input arrives as planes chooses from
-    } else if (key == "tune_clear") { tuned_.clear(); tuned_bf16_.clear(); tuned_mfma_.clear(); tuned_p_.clear(); }
+    else if (key == "tune" || key == "tune_bf16") tuning_.set(value, key == "tune_bf16");   // "M,N,K=cfg,splits"
+    else if (key == "tune_clear") tuning_.clear();
     else throw Error(SDMI_ERR_INVALID, "unknown option '" + key + "'");
-}
-
-// Heuristic tile / split-K choice: minimise (work per CU after round-robin
-// placement) / (tile efficiency) + split-K slab traffic.  Overridden per shape by
-// measured entries ("tune" option, see tools/autotune.py).  The K-reduction order
-// depends only on (M,N,K), so a sample's result is independent of where it sits
-// in the batch only for equal M; see DESIGN.md "Determinism".
-TileChoice Engine::choose_tile(int M, int N, int kt_total, bool allow_x, bool allow_s) const {
-    static const double eff[kNumGemmTiles] = {0.85, 0.75, 0.60, 0.90, 0.75, 0.85, 0.75, 0.85, 0.65, 0.75};
-    static const int split_opts[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48};
-    const int n_cu = 256;
-    double best = 1e300;
-    TileChoice bc{0, 1};
-    for (int c = 0; c < kNumGemmTiles; ++c) {
-        const int bm = gemm_tile_info(c).bm, bn = gemm_tile_info(c).bn;
-        const long long tiles = (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-        for (int s : split_opts) {
-            if (s > 1 && kt_total / s < 4) break;
-            const int kt_per = (kt_total + s - 1) / s;
-            const long long wgs = tiles * ((kt_total + kt_per - 1) / kt_per);
-            const double per_cu = (double)((wgs + n_cu - 1) / n_cu);
-            // cycles: one k tile of a bm x bn block = bm*bn*32*2 flop at 256 flop/clk/CU
-            double t = per_cu * (double)bm * bn * kt_per * 64.0 / 256.0 / eff[c];
-            t += 3000.0 * per_cu;  // prologue / epilogue per workgroup
-            if (s > 1) t += 8000.0 + (double)M * N * 4.0 * (s + 1) / (5.0e12 / 2.4e9);  // reduce launch + slab traffic
-            if (t < best) { best = t; bc = {c, s}; }
-        }
-    }
-    if (allow_x && opt_gemm_x32_) {
-        // k_gemm2x.hip: 8 waves, one workgroup per CU; ~0.9 of the matrix rate in the k loop, but the DMA prologue and the
-        // output tile's store are not hidden by a neighbour
-        static const double eff_x[kNumGemmTilesX] = {0.90, 0.90, 0.88, 0.90};
-        for (int c = 0; c < kNumGemmTilesX; ++c) {
-            const int bm = gemm_tile_info_x(c).bm, bn = gemm_tile_info_x(c).bn;
-            const long long tiles = (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-            for (int s : split_opts) {
-                if (s > 1 && kt_total / s < 4) break;
-                const int kt_per = (kt_total + s - 1) / s;
-                const long long wgs = tiles * ((kt_total + kt_per - 1) / kt_per);
-                const double per_cu = (double)((wgs + n_cu - 1) / n_cu);
-                double t = per_cu * ((double)bm * bn * kt_per * 64.0 / 256.0 / eff_x[c] + 8000.0 + bm * bn * 4.0 / 10.0);
-                if (s > 1) t += 8000.0 + (double)M * N * 4.0 * (s + 1) / (5.0e12 / 2.4e9);
-                if (t < best) { best = t; bc = {100 + c, s}; }
-            }
-        }
-    }
-    if (allow_s && opt_gemm_f32s_) {
-        // k_gemm3x.hip: six bf16 MFMAs per 16x16x32 block = 96 cycles/SIMD against 256 on the fp32 pipe; the efficiencies
-        // are measured ones (tools/autotune.py), the per-workgroup constant covers the DMA prologue and the epilogue
-        static const double eff_s[kNumGemmTilesS] = {0.55, 0.55, 0.52, 0.52, 0.46, 0.44};
-        for (int c = 0; c < kNumGemmTilesS; ++c) {
-            const int bm = gemm_tile_info_s(c).bm, bn = gemm_tile_info_s(c).bn;
-            const long long tiles = (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-            for (int s : split_opts) {
-                if (s > 1 && kt_total / s < 4) break;
-                const int kt_per = (kt_total + s - 1) / s;
-                const long long wgs = tiles * ((kt_total + kt_per - 1) / kt_per);
-                const double per_cu = (double)((wgs + n_cu - 1) / n_cu);
-                double t = per_cu * ((double)bm * bn * kt_per * 384.0 / 4096.0 / eff_s[c] + 8000.0 + bm * bn * 4.0 / 10.0);
-                if (s > 1) t += 8000.0 + (double)M * N * 4.0 * (s + 1) / (5.0e12 / 2.4e9);
-                if (t < best) { best = t; bc = {200 + c, s}; }
-            }
-        }
-    }
-    return bc;
-}
-
-// precision = 1: the 4-wave tiles of k_gemm_bf16.hip (cfg 0..9) against the 8-wave LDS-DMA tiles of
-// k_gemm_bf16x.hip (cfg 100 + x).  Cycles per CU at 4096 bf16 flop/clk/CU; the efficiencies are measured
-// ones (tools/autotune.py --precision bf16), the per-workgroup constants cover prologue DMA latency + epilogue.
-TileChoice Engine::choose_tile_bf16(int M, int N, int kt_total) const {
-    static const double eff_old[kNumGemmTiles] = {0.31, 0.22, 0.16, 0.22, 0.20, 0.20, 0.22, 0.26, 0.15, 0.28};
-    static const double eff_x[kNumGemmTilesX] = {0.54, 0.46, 0.38, 0.48};
-    static const int split_opts[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48};
-    const int n_cu = 256;
-    double best = 1e300;
-    TileChoice bc{0, 1};
-    auto consider = [&](int cfg, int bm, int bn, double eff, double wg_overhead) {
-        const long long tiles = (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-        for (int s : split_opts) {
-            if (s > 1 && kt_total / s < 4) break;
-            const int kt_per = (kt_total + s - 1) / s;
-            const long long wgs = tiles * ((kt_total + kt_per - 1) / kt_per);
-            const double per_cu = (double)((wgs + n_cu - 1) / n_cu);
-            double t = per_cu * ((double)bm * bn * kt_per * 128.0 / 4096.0 / eff + wg_overhead);
-            if (s > 1) t += 8000.0 + (double)M * N * 4.0 * (s + 1) / (5.0e12 / 2.4e9);
-            if (t < best) { best = t; bc = {cfg, s}; }
-        }
-    };
-    for (int c = 0; c < kNumGemmTiles; ++c) consider(c, gemm_tile_info(c).bm, gemm_tile_info(c).bn, eff_old[c], 3000.0);
-    if (opt_gemm_bf16x_)
-        for (int c = 0; c < kNumGemmTilesX; ++c) {
-            // one workgroup per CU (144 KB of LDS): the DMA prologue and the output tile's store are not hidden by a neighbour
-            const int bm = gemm_tile_info_x(c).bm, bn = gemm_tile_info_x(c).bn;
-            consider(100 + c, bm, bn, eff_x[c], 6000.0 + bm * bn * 2.0 / 20.0);
-        }
-    return bc;
-}
-
-// k_gemm3p.hip tiles (300 + x): what a GEMM whose activations arrive as planes chooses from when its shape is not in the measured table
-// (tuning/gfx950_fp32_planes.txt).  Same cost form as choose_tile's split branch; efficiencies from tools/autotune.py --families p.
-TileChoice Engine::choose_tile_p(int M, int N, int kt_total, bool even_ni_only) const {
-    static const double eff_p[kNumGemmTilesP] = {0.62, 0.60, 0.60, 0.52, 0.50, 0.34, 0.40, 0.50, 0.40};
-    static const int split_opts[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48};
-    const int n_cu = 256;
-    double best = 1e300;
-    TileChoice bc{304, 1};
-    for (int c = 0; c < kNumGemmTilesP; ++c) {
-        if (even_ni_only && (c == 0 || c == 3 || c == 7)) continue;
-        const int bm = gemm_tile_info_p(c).bm, bn = gemm_tile_info_p(c).bn;
-        const long long tiles = (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-        for (int s : split_opts) {
-            if (s > 1 && kt_total / s < 4) break;
-            const int kt_per = (kt_total + s - 1) / s;
-            const long long wgs = tiles * ((kt_total + kt_per - 1) / kt_per);
-            const double per_cu = (double)((wgs + n_cu - 1) / n_cu);
-            double t = per_cu * ((double)bm * bn * kt_per * 384.0 / 4096.0 / eff_p[c] + 8000.0 + bm * bn * 4.0 / 10.0);
-            if (s > 1) t += 8000.0 + (double)M * N * 4.0 * (s + 1) / (5.0e12 / 2.4e9);
-            if (t < best) { best = t; bc = {300 + c, s}; }
-        }
-    }
-    return bc;
 }
 
 // ConvGemm::resid_acc for a launch of a kernel that can take it (`eligible`: large-tile bf16 / MXFP8, no split-K): every 16-byte bias / time-embedding load and
@@ -1462,6 +1312,41 @@ void Engine::set_resid_acc(ConvGemm& p, bool eligible, bool resid_ok) const {
     if ((opt_resid_acc_ & 2) && (p.bias || p.rowvec) && (p.rowvec_stride % 4) == 0 && (((uintptr_t)p.bias | (uintptr_t)p.rowvec) & 15) == 0) p.resid_acc |= 2;
 }
 
+// option dump_choices (with record_shapes): which kernel / tile / split-K each (M, N, K) got
+void Engine::record_choice(const ConvGemm& p, const char* kind, int cfg, const char* note) {
+    if (!record_shapes_) return;
+    char ck[128];
+    std::snprintf(ck, sizeof ck, "%d,%d,%d k%d s%d u%d W%d%s cfg=%d splits=%d%s acc=%d", p.M, p.N, p.K, p.KH, p.stride, p.ups, p.Ws, kind, cfg, p.splits, note, p.resid_acc);
+    ++choice_counts_[ck];
+}
+
+// The launch of a planned GEMM (p.splits set), profiled and counted: the kernel, and behind a split-K launch the reduce over its slabs.
+// `what` / cfg name the launch in the profile tags; reduce_tag: 0 = the reduce carries none.
+void Engine::run_gemm(ConvGemm& p, const GemmRun& r) {
+    if (p.splits == 1) {
+        p.slabs = nullptr; p.slab_stride = 0;
+        ProfScope ps(this, r.pc, r.flops, r.bytes);
+        ps.set_tag("%s %d,%d,%d k%d%s%s%s cfg=%d splits=1", r.what, p.M, p.N, p.K, p.KH, p.geglu ? " geglu" : "", p.resid ? " resid" : "", p.rowvec ? " rowvec" : "", r.cfg);
+        SDMI_HIP(r.launch(p, r.index, stream_));
+        count_kernel(r.flops);
+        return;
+    }
+    p.slab_stride = (long long)p.M * p.N;
+    Buf slab(this, (size_t)p.splits * p.slab_stride * sizeof(float));
+    p.slabs = slab.f();
+    {
+        ProfScope ps(this, r.pc, r.flops, r.bytes);
+        ps.set_tag("%s %d,%d,%d k%d%s cfg=%d splits=%d", r.what, p.M, p.N, p.K, p.KH, p.geglu ? " geglu" : "", r.cfg, p.splits);
+        SDMI_HIP(r.launch(p, r.index, stream_));
+    }
+    count_kernel(r.flops);
+    ProfScope ps(this, PC_SPLITK_REDUCE, 0, (double)(p.splits + 1) * p.slab_stride * 4.0);
+    if (r.reduce_tag) ps.set_tag("reduce %d,%d,%d k%d cfg=%d splits=%d", p.M, p.N, p.K, p.KH, r.cfg, p.splits);
+    SDMI_HIP(r.bf16_reduce ? launch_splitk_reduce_bf16(p, stream_) : launch_splitk_reduce(p, stream_));
+    count_kernel();
+}
+
+// Which tile and how many K slices: plan_gemm (gemm_plan.cpp).  Here: the facts it plans from, the temporary buffers, the launch.
 void Engine::launch_gemm(ConvGemm& p, int in_dt, int force_cfg, int force_splits) {
     const int kt_elems = in_dt ? 64 : 32;  // a k tile is 128 bytes of K per row in both storage types
     p.kt_total = (p.K + kt_elems - 1) / kt_elems;
@@ -1471,73 +1356,33 @@ void Engine::launch_gemm(ConvGemm& p, int in_dt, int force_cfg, int force_splits
         std::snprintf(sk, sizeof sk, "%d,%d,%d,%d,%d,%d,%d,%d", p.NB, p.Cin, p.Hs, p.Ws, p.N, p.KH, p.stride, p.ups);
         ++shape_counts_[sk];
     }
-    auto tile_info = [&](int cfg) -> const GemmTileInfo& {
-        if (in_dt) return cfg >= 100 ? gemm_tile_info_xb(cfg - 100) : gemm_tile_info(cfg);
-        return cfg >= 300 ? gemm_tile_info_p(cfg - 300) : cfg >= 200 ? gemm_tile_info_s(cfg - 200) : cfg >= 100 ? gemm_tile_info_x(cfg - 100) : gemm_tile_info(cfg);
-    };
-    TileChoice tc;
-    char key[64];
-    std::snprintf(key, sizeof key, "%d,%d,%d", p.M, p.N, p.K);
-    const auto& table = in_dt ? tuned_bf16_ : tuned_;  // measured per storage type (tuning/gfx950_{fp32,bf16}.txt)
-    auto it = table.find(key);
-    const bool x32_ok = !in_dt && p.CS == 32 && p.Cin % 32 == 0 && p.out_mode == 0;   // what k_gemm2x.hip handles
     p.Bt3 = in_dt ? nullptr : split_planes(p.Bt);
     p.b3_grouped = b3_grouped((long long)p.N * (p.geglu ? 2 : 1)) ? 1 : 0;   // the layout the planes of a weight with that many rows were packed in
     p.variant = in_dt ? opt_gemm_bf16x_variant_ : opt_gemm3x_variant_;
+    p.zero_page = zero_page_;
+    p.probe = probe_buf_;
+    GemmPlanIn in{};
+    in.M = p.M; in.N = p.N; in.K = p.K; in.kt_total = p.kt_total; in.bf16 = in_dt; in.geglu = p.geglu; in.out_mode = p.out_mode; in.force_cfg = force_cfg; in.force_splits = force_splits;
+    in.KH = p.KH; in.KW = p.KW; in.stride = p.stride; in.pad = p.pad; in.ups = p.ups; in.Cin = p.Cin; in.Hs = p.Hs; in.Ws = p.Ws; in.Ho = p.Ho; in.Wo = p.Wo;
+    in.zero_page = zero_page_ != nullptr;
+    in.x32_ok = !in_dt && p.CS == 32 && p.Cin % 32 == 0 && p.out_mode == 0;   // what k_gemm2x.hip handles
     // k_gemm3x.hip: the same layers, when the weight has its bf16 planes (weights in the arenas; not e.g. the K / V operands of
     // the unfused VAE attention) and the 32-bit piece offsets reach
-    const bool s_ok = x32_ok && p.Bt3 && (unsigned long long)p.N * (p.geglu ? 2 : 1) * (unsigned long long)p.kt_total * 192ull < 0xFFFFFF00ull;
-    // k_gemm3p.hip (300 + x): the same layers with the activations as planes too -- written by their producer (p.A3) or, for a tensor that
+    in.s_ok = in.x32_ok && p.Bt3 && (unsigned long long)p.N * (p.geglu ? 2 : 1) * (unsigned long long)p.kt_total * 192ull < 0xFFFFFF00ull;
+    // k_gemm3p.hip: the same layers with the activations as planes too -- written by their producer (p.A3) or, for a tensor that
     // arrives as fp32, by split3_rows_kernel right here
-    const bool p_ok = s_ok && (unsigned long long)p.NB * p.Hs * p.Ws * (unsigned long long)(p.A3 ? p.a3_ld : p.Cin * 6) < 0xFFFFFF00ull;
+    in.p_ok = in.s_ok && (unsigned long long)p.NB * p.Hs * p.Ws * (unsigned long long)(p.A3 ? p.a3_ld : p.Cin * 6) < 0xFFFFFF00ull;
     // the activations arrive as planes (their producer wrote them): the GEMM runs on a plane tile -- from the plane table or the cost model
-    const bool from_planes = !in_dt && p.A3 != nullptr;
-    if (from_planes && !p_ok)
-        throw Error(s_ok ? SDMI_ERR_UNSUPPORTED : SDMI_ERR_STATE,
-                    s_ok ? "fp32 GEMM: an activation tensor stored as bf16 planes (6 bytes per element) reaches 4 GiB (32-bit piece offsets): lower the batch (at 64x64x960 the CFG "
-                           "batch 2n must stay <= 182) or set option gemm_planes=0"
-                         : "gemm: activation planes given for a layer the plane kernel does not take");
-    if (!from_planes && !p.A) throw Error(SDMI_ERR_STATE, "gemm: no activations");
-    auto usable = [&](int cfg) { return cfg < 100 || (in_dt ? opt_gemm_bf16x_ != 0 : (cfg >= 300 ? p_ok : cfg >= 200 ? (opt_gemm_f32s_ != 0 && s_ok) : (opt_gemm_x32_ != 0 && x32_ok))); };
-    const auto it2 = in_dt ? tuned_mfma_.end() : tuned_mfma_.find(key);   // the table measured without the split kernels
-    if (from_planes) {
-        const auto itp = tuned_p_.find(key);
-        const bool even = p.geglu != 0;
-        if (itp != tuned_p_.end() && !(even && (itp->second.cfg == 300 || itp->second.cfg == 303 || itp->second.cfg == 307))) tc = itp->second;
-        else tc = choose_tile_p(p.M, p.N, p.kt_total, even);
-    }
-    else if (it != table.end() && usable(it->second.cfg)) tc = it->second;
-    else if (it2 != tuned_mfma_.end() && usable(it2->second.cfg)) tc = it2->second;
-    else tc = in_dt ? choose_tile_bf16(p.M, p.N, p.kt_total) : choose_tile(p.M, p.N, p.kt_total, x32_ok, s_ok);
-    bool tile_forced = false;   // by option gemm_tile or by the caller: the launch then runs exactly that tile (no upgrade to the kernel-row form below)
-    if (opt_force_tile_ >= 0 && (from_planes ? opt_force_tile_ >= 300 : (opt_force_tile_ < 100 || in_dt || (opt_force_tile_ >= 300 ? p_ok : opt_force_tile_ >= 200 ? s_ok : x32_ok)))) { tc.cfg = opt_force_tile_; tile_forced = true; }  // 100+ / 200+: large-tile kernels, where applicable
-    if (opt_force_splits_ > 0) tc.splits = opt_force_splits_;
-    if (force_cfg >= 0) { tc.cfg = force_cfg; tile_forced = true; }
-    // gemm_planes = 2 (A/B switch, tests): every launch that chose a k_gemm3x.hip tile runs on the k_gemm3p.hip tile nearest in shape, its
-    // fp32 activations converted by split3_rows_kernel in front of it
-    if (!in_dt && !from_planes && p_ok && opt_gemm_planes_ == 2 && tc.cfg >= 200 && tc.cfg < 200 + kNumGemmTilesS) {
-        static const int kSplitToP[kNumGemmTilesS] = {300, 303, 301, 302, 303, 304};
-        const int c = kSplitToP[tc.cfg - 200];
-        if (!p.geglu || c == 301 || c == 302 || c == 304) tc.cfg = c;   // (even fragment counts only for the GEGLU epilogue)
-    }
-    if (from_planes && tc.cfg < 300) throw Error(SDMI_ERR_STATE, "gemm: activation planes need a plane tile (300 + x)");
-    if (force_splits > 0) tc.splits = force_splits;
-    if (!in_dt && p.out_mode == 2) tc.splits = 1;  // fp32 kernel emitting bf16: no split-K path
-    int splits = std::max(1, std::min(tc.splits, p.kt_total));
-    p.kt_per_split = (p.kt_total + splits - 1) / splits;
-    splits = (p.kt_total + p.kt_per_split - 1) / p.kt_per_split;
-    p.splits = splits;
+    in.from_planes = !in_dt && p.A3 != nullptr;
+    if (!in.from_planes && !p.A) throw Error(SDMI_ERR_STATE, "gemm: no activations");
+    const GemmPlan g = plan_gemm(in, gopt_, tuning_);
+    p.kt_per_split = g.kt_per_split; p.splits = g.splits;
+    const bool w_planes = g.tile.family >= kFamS, a_planes = g.tile.family == kFamP;   // the operands the kernel reads as three bf16 planes
     const double flops = 2.0 * p.M * (double)p.N * p.K * (p.geglu ? 2.0 : 1.0);
     // raw buffer loads: the range check needs 32-bit extents
     const unsigned long long es = in_dt ? 2ull : 4ull;
     const unsigned long long a_ext = ((unsigned long long)p.NB * p.Hs * p.Ws - 1) * (unsigned long long)p.a_ld * es + (unsigned long long)p.Cin * es;
     const unsigned long long b_ext = ((unsigned long long)p.N * (p.geglu ? 2 : 1) - 1) * (unsigned long long)p.b_ld * es + (unsigned long long)p.K * es;
-    p.zero_page = zero_page_;
-    // bf16 3x3 / stride-1 convolutions on the 256 x 320 / 256 x 256 tiles: the form that stages a kernel row's activations once for its three taps (k_gemm_bf16t.hip)
-    if (in_dt && opt_conv3_reuse_ && !tile_forced && (tc.cfg == 100 || tc.cfg == 101) && conv_gemm_bf16t_supported(p)) tc.cfg += kNumGemmTilesX;
-    if (tc.cfg >= 300 ? (in_dt || tc.cfg - 300 >= kNumGemmTilesP || !p_ok)
-        : tc.cfg >= 200 ? (in_dt || tc.cfg - 200 >= kNumGemmTilesS || !s_ok) : (tc.cfg >= 100 && (tc.cfg - 100 >= (in_dt ? kNumGemmTilesXB : kNumGemmTilesX) || (!in_dt && !x32_ok))))
-        throw Error(SDMI_ERR_INVALID, "gemm: large-tile kernel index out of range or not applicable to this layer");
     if (a_ext >= 0xFFFFFFE0ull || b_ext >= 0xFFFFFFE0ull) throw Error(SDMI_ERR_UNSUPPORTED, "GEMM: operand larger than 4 GiB (the buffer-load range check needs 32-bit extents)");
     p.a_bytes = (unsigned)a_ext;
     p.b_bytes = (unsigned)b_ext;
@@ -1546,7 +1391,7 @@ void Engine::launch_gemm(ConvGemm& p, int in_dt, int force_cfg, int force_splits
     void* const c3_want = in_dt ? nullptr : p.C3;
     const int ldc3_want = p.ldc3;
     const bool vec_out = (p.N % 4 == 0) && (!p.C || p.ldc % 4 == 0) && (!p.resid || p.ldr % 4 == 0);
-    const bool c3_native = c3_want && tc.cfg >= 200 && vec_out && (!p.geglu || (p.geglu == 2 && tc.cfg >= 300));
+    const bool c3_native = c3_want && w_planes && vec_out && (!p.geglu || (p.geglu == 2 && a_planes));
     std::unique_ptr<Buf> c_tmp;
     if (!c3_native) {
         p.C3 = nullptr;
@@ -1557,7 +1402,7 @@ void Engine::launch_gemm(ConvGemm& p, int in_dt, int force_cfg, int force_splits
     }
     if (!p.C) p.ldc = p.N;
     std::unique_ptr<Buf> a3_tmp;
-    if (tc.cfg >= 300 && !p.A3) {   // the source is fp32: split it once for this launch (a producer that writes planes itself saves this pass)
+    if (a_planes && !p.A3) {   // the source is fp32: split it once for this launch (a producer that writes planes itself saves this pass)
         const long long rows = (long long)p.NB * p.Hs * p.Ws;
         p.a3_ld = (p.Cin / 32) * 192;
         a3_tmp.reset(new Buf(this, (size_t)rows * p.a3_ld));
@@ -1566,54 +1411,20 @@ void Engine::launch_gemm(ConvGemm& p, int in_dt, int force_cfg, int force_splits
         count_kernel();
         p.A3 = a3_tmp->p;
     }
-    p.probe = probe_buf_;
-    auto launch = [&](const ConvGemm& q) {
-        if (tc.cfg >= 300) return launch_conv_gemm3p(q, tc.cfg - 300, stream_);
-        if (in_dt && tc.cfg >= 100) return launch_conv_gemm_bf16_large(q, tc.cfg - 100, stream_);
-        if (tc.cfg >= 200) return launch_conv_gemm3x(q, tc.cfg - 200, stream_);
-        if (tc.cfg >= 100) return launch_conv_gemm2x(q, tc.cfg - 100, stream_);
-        if (in_dt) return launch_conv_gemm_bf16(q, tc.cfg, stream_);
-        return launch_conv_gemm2(q, tc.cfg, stream_);
-    };
-    p.slabs = nullptr;
-    // round 6: the large-tile bf16 kernels take the residual as the accumulators' initial value (k_gemm_bf16_epi.hpp gemm_acc_init_bf16) where their 8-byte loads apply
+    // the large-tile bf16 kernels take the residual as the accumulators' initial value (k_gemm_bf16_epi.hpp gemm_acc_init_bf16) where their 8-byte loads apply
     // (option resid_acc: bit 0 = the residual, bit 1 = bias + time-embedding row; launches without split-K only -- the split-K combine adds them otherwise)
-    set_resid_acc(p, in_dt && tc.cfg >= 100 && splits == 1, !p.geglu);
-    if (record_shapes_) {   // which kernel / tile / split-K each (M, N, K) got: option dump_choices
-        char ck[128];
-        std::snprintf(ck, sizeof ck, "%d,%d,%d k%d s%d u%d W%d cfg=%d splits=%d%s acc=%d", p.M, p.N, p.K, p.KH, p.stride, p.ups, p.Ws, tc.cfg, splits, p.Bt3 || in_dt ? "" : " (no planes)", p.resid_acc);
-        ++choice_counts_[ck];
-    }
-    const int pc = (!in_dt && tc.cfg >= 200) ? PC_CONV_SPLIT : PC_CONV_GEMM;   // k_gemm3x.hip launches are timed as their own class
+    set_resid_acc(p, in_dt && g.tile.family == kFamX && g.splits == 1, !p.geglu);
+    record_choice(p, "", g.cfg, p.Bt3 || in_dt ? "" : " (no planes)");
     // ALGORITHMIC bytes of the launch in the formats the tensors are stored in: the source activations once, the weights once, the result once (bf16 2 B, fp32 4 B,
     // planes 6 B per element; split-K slabs and im2col / tile re-reads are not algorithmic) -- what the PMC byte counters of profiles/pmc_summary.json are held against
-    const double a_es = in_dt ? 2.0 : (tc.cfg >= 300 ? 6.0 : 4.0), w_es = in_dt ? 2.0 : (tc.cfg >= 200 ? 6.0 : 4.0);
+    const double a_es = in_dt ? 2.0 : (a_planes ? 6.0 : 4.0), w_es = in_dt ? 2.0 : (w_planes ? 6.0 : 4.0);
     const double c_es = in_dt ? (p.out_mode == 1 ? 4.0 : 2.0) : (p.out_mode == 2 ? 2.0 : ((p.C ? 4.0 : 0.0) + (c3_native ? 6.0 : 0.0)));
     const double gemm_bytes = (double)p.NB * p.Hs * p.Ws * p.Cin * a_es + (double)p.N * (p.geglu ? 2.0 : 1.0) * p.K * w_es + (double)p.M * p.N * c_es;
-    if (splits == 1) {
-        p.slab_stride = 0;
-        ProfScope ps(this, pc, flops, gemm_bytes);
-        ps.set_tag("gemm %d,%d,%d k%d%s%s%s cfg=%d splits=1", p.M, p.N, p.K, p.KH, p.geglu ? " geglu" : "", p.resid ? " resid" : "", p.rowvec ? " rowvec" : "", tc.cfg);
-        SDMI_HIP(launch(p));
-        count_kernel(flops);
-    } else {
-        p.slab_stride = (long long)p.M * p.N;
-        Buf slab(this, (size_t)splits * p.slab_stride * sizeof(float));
-        p.slabs = slab.f();
-        {
-            ProfScope ps(this, pc, flops, gemm_bytes);
-            ps.set_tag("gemm %d,%d,%d k%d%s cfg=%d splits=%d", p.M, p.N, p.K, p.KH, p.geglu ? " geglu" : "", tc.cfg, splits);
-            SDMI_HIP(launch(p));
-        }
-        count_kernel(flops);
-        {
-            ProfScope ps(this, PC_SPLITK_REDUCE, 0, (double)(splits + 1) * p.slab_stride * 4.0);
-            ps.set_tag("reduce %d,%d,%d k%d cfg=%d splits=%d", p.M, p.N, p.K, p.KH, tc.cfg, splits);
-            if (in_dt) SDMI_HIP(launch_splitk_reduce_bf16(p, stream_));
-            else SDMI_HIP(launch_splitk_reduce(p, stream_));
-            count_kernel();
-        }
-    }
+    // kernel by storage type and family (bf16: plan_gemm lets only the first two through)
+    static const GemmLauncher kLaunchers[2][kNumGemmFamilies] = {{launch_conv_gemm2, launch_conv_gemm2x, launch_conv_gemm3x, launch_conv_gemm3p},
+                                                                 {launch_conv_gemm_bf16, launch_conv_gemm_bf16_large, nullptr, nullptr}};
+    // (k_gemm3x.hip / k_gemm3p.hip launches are timed as their own class)
+    run_gemm(p, GemmRun{kLaunchers[in_dt ? 1 : 0][g.tile.family], g.tile.index, "gemm", g.cfg, w_planes ? PC_CONV_SPLIT : PC_CONV_GEMM, in_dt != 0, true, flops, gemm_bytes});
     if (c3_want && !c3_native) {
         ProfScope ps(this, PC_SPLIT_ROWS, 0, (double)p.M * p.N * 10.0);
         SDMI_HIP(launch_split3_rows(p.C, c3_want, p.M, p.N, p.ldc, ldc3_want, stream_));
@@ -1650,19 +1461,25 @@ void Engine::conv(const ConvW& w, const Act& x, Act& y, int stride, int ups, con
     launch_gemm(p, x.dt);
 }
 
+// the ConvGemm of a Linear layer: [rows, cin] x [cout, cin]^T as a 1x1 convolution over one image of 1 x rows pixels
+static ConvGemm linear_gemm(const float* A, int rows, const float* bt, const float* bias, int cin, int cout, float* C, int ldc, const float* resid, int ldr) {
+    ConvGemm p{};
+    p.A = A; p.Bt = bt; p.C = C; p.bias = bias; p.resid = resid;
+    p.M = rows; p.N = cout; p.K = cin;
+    p.NB = 1; p.Hs = 1; p.Ws = rows; p.Cin = cin; p.Ho = 1; p.Wo = rows;
+    p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.ups = 0;
+    p.ldc = ldc; p.ldr = ldr; p.a_ld = cin; p.b_ld = cin; p.rowvec_stride = 0; p.CS = 32;
+    return p;
+}
+
 void Engine::gemm(const float* A, int a_rows, const float* bt, const float* bias, int cin, int cout, float* C, int ldc,
                   const float* resid, int ldr, int dt, int out_mode, const void* A3, void* C3) {
     if (dt < 0) dt = edt();
     if (cin % 32) throw Error(SDMI_ERR_UNSUPPORTED, "linear: in_features must be a multiple of 32");
-    ConvGemm p{};
-    p.A = A; p.Bt = bt; p.C = C; p.bias = bias; p.resid = resid;
+    ConvGemm p = linear_gemm(A, a_rows, bt, bias, cin, cout, C, ldc, resid, ldr);
     p.A3 = A3; p.a3_ld = (cin / 32) * 192;          // dense planes in ...
     p.C3 = C3; p.ldc3 = (cout / 32) * 192;          // ... and out
     if (C3 && (cout % 32)) throw Error(SDMI_ERR_STATE, "linear: plane output needs out_features % 32 == 0");
-    p.M = a_rows; p.N = cout; p.K = cin;
-    p.NB = 1; p.Hs = 1; p.Ws = a_rows; p.Cin = cin; p.Ho = 1; p.Wo = a_rows;
-    p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.ups = 0;
-    p.ldc = ldc; p.ldr = ldr; p.a_ld = cin; p.b_ld = cin; p.rowvec_stride = 0; p.CS = 32;
     p.out_mode = out_mode;
     launch_gemm(p, dt);
 }
@@ -1671,27 +1488,14 @@ void Engine::gemm_geglu(const float* x, long long rows, const float* bt, const f
                         const void* x3, void* out3) {
     if (dt < 0) dt = edt();
     if (x3 && (out3 || out) && !dt && opt_geglu_fuse_ && hidden % 32 == 0 && cin % 32 == 0 && split_planes(bt)) {
-        // round 5: the gate in the plane GEMM's epilogue -- value / gate rows split by WAVE column, so the tiles with an odd fragment count per wave (256 x 160:
-        // the batch-1 model's) qualify.  The tile is the one the unfused projection [rows, 2 hidden] would take (same tile count: 80 outputs = 160 weight rows per
-        // tile); it must run without split-K and have an even number of wave columns (not 128 x 64).
-        const int kt_total = (cin + 31) / 32;
-        char key[64];
-        std::snprintf(key, sizeof key, "%lld,%d,%d", rows, 2 * hidden, cin);
-        const auto itp = tuned_p_.find(key);
-        const TileChoice tc = itp != tuned_p_.end() ? itp->second : choose_tile_p((int)rows, 2 * hidden, kt_total, false);
-        const int force = opt_force_tile_ >= 300 ? opt_force_tile_ : tc.cfg;
-        if (force >= 300 && force != 308 && (tc.splits == 1 || opt_force_tile_ >= 300) && opt_force_splits_ <= 1) {
-            ConvGemm p{};
-            p.A = x; p.Bt = bt; p.C = out; p.bias = bias;
+        // the gate in the plane GEMM's epilogue -- value / gate rows split by WAVE column, so the tiles with an odd fragment count per wave (256 x 160: the batch-1 model's) qualify
+        const int cfg = plan_geglu_plane_tile(rows, hidden, cin, gopt_, tuning_);
+        if (cfg >= 0) {
+            ConvGemm p = linear_gemm(x, (int)rows, bt, bias, cin, hidden, out, hidden, nullptr, hidden);
             p.A3 = x3; p.a3_ld = (cin / 32) * 192;
             p.C3 = out3; p.ldc3 = (hidden / 32) * 192;
-            p.M = (int)rows; p.N = hidden; p.K = cin;
-            p.NB = 1; p.Hs = 1; p.Ws = (int)rows; p.Cin = cin; p.Ho = 1; p.Wo = (int)rows;
-            p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.ups = 0;
-            p.ldc = hidden; p.ldr = hidden; p.a_ld = cin; p.b_ld = cin; p.rowvec_stride = 0; p.CS = 32;
-            p.out_mode = 0;
             p.geglu = 2;
-            launch_gemm(p, 0, force, 1);
+            launch_gemm(p, 0, cfg, 1);
             return;
         }
     }
@@ -1706,38 +1510,16 @@ void Engine::gemm_geglu(const float* x, long long rows, const float* bt, const f
         count_kernel();
         return;
     }
-    const size_t es = dt ? 2 : 4;
     // the fused form needs a large-tile kernel with an even fragment count per wave (256x256 or 256x128 tiles, no split-K)
-    int cfg = -1;
-    const bool eligible = opt_geglu_fuse_ && hidden % 8 == 0 && cin % (dt ? 64 : 32) == 0 && (dt ? opt_gemm_bf16x_ : opt_gemm_x32_);
-    if (eligible) {
-        const long long mt = (rows + 255) / 256;
-        const long long t256 = mt * ((hidden + 127) / 128), t128 = mt * ((hidden + 63) / 64);   // tiles with 256x256 / 256x128
-        // measured (same box, --opt geglu_fuse=0/1): at batch 1 the 256-wide tiles quantise badly against 256 CUs (320 tiles =
-        // two rounds) and the fused form LOSES 2.6 % end to end in fp32; with >= 4 rounds it wins ~1 % (bf16, batch 8)
-        if (t256 >= 1024 || opt_geglu_fuse_ == 3) cfg = 101;
-        else if (t128 >= 1024 || opt_geglu_fuse_ == 2) cfg = 102;
-        // precision = 0 with the split kernels: their even-fragment tiles (128x256s / 256x128s / 128x128s = 128 / 64 / 64 output
-        // columns per tile); geglu_fuse = 4 / 5 / 6 force them
-        if (!dt && opt_gemm_f32s_ && split_planes(bt)) {
-            if (opt_geglu_fuse_ == 4) cfg = 203;
-            else if (opt_geglu_fuse_ == 5) cfg = 202;
-            else if (opt_geglu_fuse_ == 6) cfg = 205;      // (measured at batch 1: 3.56 / 3.58 / 3.54 img/s against 3.66 unfused)
-        }
-    }
+    const bool eligible = opt_geglu_fuse_ && hidden % 8 == 0 && cin % (dt ? 64 : 32) == 0 && (dt ? gopt_.gemm_bf16x : gopt_.gemm_x32);
+    const int cfg = eligible ? plan_geglu_paired_tile(rows, hidden, opt_geglu_fuse_, !dt && gopt_.gemm_f32s && split_planes(bt)) : -1;
     if (cfg >= 0) {
-        ConvGemm p{};
-        p.A = x; p.Bt = bt; p.C = out; p.bias = bias;
-        p.M = (int)rows; p.N = hidden; p.K = cin;
-        p.NB = 1; p.Hs = 1; p.Ws = (int)rows; p.Cin = cin; p.Ho = 1; p.Wo = (int)rows;
-        p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.ups = 0;
-        p.ldc = hidden; p.ldr = hidden; p.a_ld = cin; p.b_ld = cin; p.rowvec_stride = 0; p.CS = 32;
-        p.out_mode = 0;
+        ConvGemm p = linear_gemm(x, (int)rows, bt, bias, cin, hidden, out, hidden, nullptr, hidden);
         p.geglu = 1;
         launch_gemm(p, dt, cfg, 1);
         return;
     }
-    Buf proj(this, (size_t)rows * 2 * hidden * es);
+    Buf proj(this, (size_t)rows * 2 * hidden * (dt ? 2 : 4));
     gemm(x, (int)rows, bt, bias, cin, 2 * hidden, proj.f(), 2 * hidden, nullptr, 0, dt);
     {
         ProfScope ps(this, PC_GEGLU, 0, (double)rows * hidden * (dt ? 6.0 : 12.0));
@@ -1972,13 +1754,8 @@ void Engine::conv_fp8(const ConvW& w, const ActQ& x, Act& y, const float* rowvec
 // C[rows][n_rows_w] (bf16) = x W^T + bias (+ resid): a Linear layer on MXFP8 operands (n_rows_w = w.cout, or 3 cout for the packed q | k | v)
 void Engine::gemm_fp8(const ActQ& x, const LinW& w, int n_rows_w, void* C, int ldc, const float* resid, int ldr) {
     if (x.c != w.cin || !w.bt8) throw Error(SDMI_ERR_STATE, "gemm_fp8: not an MXFP8-packed Linear layer");
-    ConvGemm p{};
-    p.A = reinterpret_cast<const float*>(x.q); p.Bt = w.bt8; p.C = reinterpret_cast<float*>(C); p.bias = w.bias; p.resid = resid;
-    p.a_scale = x.s; p.b_scale = w.bs8;
-    p.M = (int)x.rows(); p.N = n_rows_w; p.K = x.cp;
-    p.NB = 1; p.Hs = 1; p.Ws = p.M; p.Cin = x.cp; p.Ho = 1; p.Wo = p.M;
-    p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.ups = 0;
-    p.ldc = ldc; p.ldr = ldr; p.a_ld = x.cp; p.b_ld = p.K; p.rowvec_stride = 0; p.CS = 128;
+    ConvGemm p = linear_gemm(reinterpret_cast<const float*>(x.q), (int)x.rows(), w.bt8, w.bias, x.cp, n_rows_w, reinterpret_cast<float*>(C), ldc, resid, ldr);
+    p.a_scale = x.s; p.b_scale = w.bs8; p.CS = 128;
     launch_fp8(p, 2.0 * p.M * (double)p.N * w.cin);
 }
 
@@ -1988,64 +1765,13 @@ void Engine::launch_fp8(ConvGemm& p, double flops) {
     p.zero_page = zero_page_;
     p.kt_total = p.K / 128;
     if ((unsigned long long)p.NB * p.Hs * p.Ws * (unsigned long long)p.a_ld >= 0xFFFFFFE0ull || (unsigned long long)p.N * p.K >= 0xFFFFFFE0ull) throw Error(SDMI_ERR_UNSUPPORTED, "fp8 GEMM: operand larger than 4 GiB");
-    // tile + split-K: rounds of workgroups on 256 CUs x the time of one tile at the rate each tile shape sustains when the
-    // chip is full (tools/bench_gemm_fp8.py on MI355X: 256x320 2.4, 256x256 2.1, 256x128 1.7 PFLOP/s); K is split only when
-    // the tiles would leave half of the chip or more idle
-    static const double kRate[kNumGemmTilesQ] = {2400.0, 2100.0, 1700.0};
-    int cfg = opt_fp8_tile_, splits = 1;
-    auto plan = [&](int c, int* sp) {
-        const int bm = gemm_tile_info_q(c).bm, bn = gemm_tile_info_q(c).bn;
-        const long long tiles = (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn);
-        int s_ = 1;
-        // (round 6: <= 128 -- half a round of tiles is split too: M = 8192, N = 1280 on 256 x 320 tiles is 128 workgroups; K = 11520: 167.5 -> 143.0 us, K = 23040: 314 -> 240, profiles/r06q_fp8_shapes.txt)
-        if (tiles <= 128) s_ = (int)std::max<long long>(1, std::min<long long>(p.kt_total / 4, (256 + tiles - 1) / tiles));
-        *sp = s_;
-        const double rounds = (double)((tiles * s_ + 255) / 256);
-        return rounds * (double)bm * bn / kRate[c] / s_ + (s_ > 1 ? 0.15 * (double)bm * bn / kRate[c] : 0.0);
-    };
-    if (cfg < 0) {
-        double best = 1e300;
-        for (int c = 0; c < kNumGemmTilesQ; ++c) {
-            int sp;
-            const double t = plan(c, &sp);
-            if (t < best) { best = t; cfg = c; splits = sp; }
-        }
-    } else {
-        if (cfg >= kNumGemmTilesQ) throw Error(SDMI_ERR_INVALID, "fp8_tile out of range");
-        (void)plan(cfg, &splits);
-    }
-    if (opt_force_splits_ > 0) splits = opt_force_splits_;
-    splits = std::max(1, std::min(splits, p.kt_total));
-    p.kt_per_split = (p.kt_total + splits - 1) / splits;
-    splits = (p.kt_total + p.kt_per_split - 1) / p.kt_per_split;
-    p.splits = splits;
-    set_resid_acc(p, splits == 1, true);   // (as Engine::launch_gemm)
-    if (record_shapes_) {   // option dump_choices: the MXFP8 launches are listed with their own tag, so a test can pin WHICH layers run on fp8 operands
-        char ck[128];
-        std::snprintf(ck, sizeof ck, "%d,%d,%d k%d s%d u%d W%d fp8 cfg=%d splits=%d acc=%d", p.M, p.N, p.K, p.KH, p.stride, p.ups, p.Ws, cfg, splits, p.resid_acc);
-        ++choice_counts_[ck];
-    }
+    const TileChoice tc = plan_gemm_fp8(p.M, p.N, p.kt_total, opt_fp8_tile_, gopt_.force_splits, &p.kt_per_split);
+    p.splits = tc.splits;
+    set_resid_acc(p, tc.splits == 1, true);   // (as Engine::launch_gemm)
+    record_choice(p, " fp8", tc.cfg, "");   // the MXFP8 launches are listed with their own tag, so a test can pin WHICH layers run on fp8 operands
     // algorithmic bytes: e4m3 operands + one E8M0 scale byte per 32 elements, bf16 result
     const double fp8_bytes = ((double)p.NB * p.Hs * p.Ws * p.a_ld + (double)p.N * p.K) * (1.0 + 1.0 / 32.0) + (double)p.M * p.N * 2.0;
-    if (splits == 1) {
-        ProfScope ps(this, PC_CONV_FP8, flops, fp8_bytes);
-        ps.set_tag("gemm_fp8 %d,%d,%d k%d%s%s cfg=%d splits=1", p.M, p.N, p.K, p.KH, p.resid ? " resid" : "", p.rowvec ? " rowvec" : "", cfg);
-        SDMI_HIP(launch_conv_gemm_fp8x(p, cfg, stream_));
-        count_kernel(flops);
-    } else {
-        p.slab_stride = (long long)p.M * p.N;
-        Buf slab(this, (size_t)splits * p.slab_stride * sizeof(float));
-        p.slabs = slab.f();
-        {
-            ProfScope ps(this, PC_CONV_FP8, flops, fp8_bytes);
-            ps.set_tag("gemm_fp8 %d,%d,%d k%d cfg=%d splits=%d", p.M, p.N, p.K, p.KH, cfg, splits);
-            SDMI_HIP(launch_conv_gemm_fp8x(p, cfg, stream_));
-        }
-        count_kernel(flops);
-        ProfScope ps(this, PC_SPLITK_REDUCE, 0, (double)(splits + 1) * p.slab_stride * 4.0);
-        SDMI_HIP(launch_splitk_reduce_bf16(p, stream_));
-        count_kernel();
-    }
+    run_gemm(p, GemmRun{launch_conv_gemm_fp8x, tc.cfg, "gemm_fp8", tc.cfg, PC_CONV_FP8, true, false, flops, fp8_bytes});
 }
 
 // a convolution whose input is a raw (not normalised) activation -- the down / up convolutions (unet/mod.rs:397,425; autoencoder/mod.rs:319):
@@ -3243,6 +2969,9 @@ void Engine::probe_report(void* pb_dev, size_t kMaxBlocks, int n, int cin, int h
                  q(wait_frac, 0), q(wait_frac, 0.5), q(wait_frac, 1), q(mhz, 0), q(mhz, 0.5), q(mhz, 1));
 }
 
+// puts an option back when the scope ends, however it ends
+struct OptRestore { int& opt; const int saved = opt; ~OptRestore() { opt = saved; } };
+
 double Engine::bench_conv(int n, int cin, int h, int w, int cout, int k, int stride, int ups, int tile_cfg, int splitk,
                           int iters) {
     SDMI_HIP(hipSetDevice(cfg_.device));
@@ -3261,8 +2990,8 @@ double Engine::bench_conv(int n, int cin, int h, int w, int cout, int k, int str
         SDMI_HIP(launch_quantize_fp8(x32.p, q.q, q.s, x32.rows(), cin, stream_));
         SDMI_HIP(launch_pack_conv_weight_fp8(w32.f(), bt8.p, bs8.p, cout, cin, 3, 3, stream_));
         ConvW cw; cw.cin = cin; cw.cout = cout; cw.k = 3; cw.dt = 1; cw.bias = bias.f(); cw.bt8 = bt8.f(); cw.bs8 = bs8.f();
-        const int save_t = opt_fp8_tile_, save_s = opt_force_splits_;
-        opt_fp8_tile_ = tile_cfg; opt_force_splits_ = splitk;
+        const OptRestore r1{opt_fp8_tile_}, r2{gopt_.force_splits};
+        opt_fp8_tile_ = tile_cfg; gopt_.force_splits = splitk;
         float ms = 0;
         try {
             conv_fp8(cw, q, y, nullptr, nullptr);
@@ -3272,11 +3001,9 @@ double Engine::bench_conv(int n, int cin, int h, int w, int cout, int k, int str
             SDMI_HIP(hipEventSynchronize(ev1_));
             SDMI_HIP(hipEventElapsedTime(&ms, ev0_, ev1_));
         } catch (...) {
-            opt_fp8_tile_ = save_t; opt_force_splits_ = save_s;
             release(x32); release(y); release(q);
             throw;
         }
-        opt_fp8_tile_ = save_t; opt_force_splits_ = save_s;
         release(x32); release(y); release(q);
         return (double)ms / std::max(1, iters);
     }
@@ -3293,14 +3020,15 @@ double Engine::bench_conv(int n, int cin, int h, int w, int cout, int k, int str
     }
     SDMI_HIP(launch_fill_normal(bias.f(), cout, 13, stream_));
     TempSplit planes(this, bt.f(), wdt ? 0 : cout, (long long)cin * k * k);
-    if (!wdt && tile_cfg >= 300 && cin % 32 == 0) {   // plane tiles are timed on planes their producer would have written
+    const bool plane_tile = tile_cfg >= 0 && gemm_tile_id(tile_cfg).family == kFamP;
+    if (!wdt && plane_tile && cin % 32 == 0) {   // plane tiles are timed on planes their producer would have written
         a.p3 = pool_.alloc(a.bytes3()); a.ld3 = (cin / 32) * 192;
         SDMI_HIP(launch_split3_rows(a.p, a.p3, a.rows(), cin, cin, a.ld3, stream_));
     }
     ConvW cw; cw.cin = cin; cw.cout = cout; cw.k = k; cw.bt = bt.f(); cw.bias = bias.f(); cw.dt = wdt;
-    const int save_t = opt_force_tile_, save_s = opt_force_splits_, save_p = opt_gemm_planes_;
-    opt_force_tile_ = tile_cfg; opt_force_splits_ = splitk;
-    if (tile_cfg >= 300 && !opt_gemm_planes_) opt_gemm_planes_ = 2;
+    const OptRestore r1{gopt_.force_tile}, r2{gopt_.force_splits}, r3{gopt_.gemm_planes};
+    gopt_.force_tile = tile_cfg; gopt_.force_splits = splitk;
+    if (plane_tile && !gopt_.gemm_planes) gopt_.gemm_planes = 2;
     float ms = 0;
     try {
         conv(cw, a, y, stride, ups, nullptr, 0, nullptr);  // warm-up
@@ -3347,11 +3075,9 @@ double Engine::bench_conv(int n, int cin, int h, int w, int cout, int k, int str
             probe_report(pb.p, kMaxBlocks, n, cin, h, w, cout, k, tile_cfg, splitk);
         }
     } catch (...) {
-        opt_force_tile_ = save_t; opt_force_splits_ = save_s; opt_gemm_planes_ = save_p;
         release(a); release(y);
         throw;
     }
-    opt_force_tile_ = save_t; opt_force_splits_ = save_s; opt_gemm_planes_ = save_p;
     release(a); release(y);
     return (double)ms / std::max(1, iters);
 }

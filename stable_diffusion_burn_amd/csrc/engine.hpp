@@ -21,6 +21,7 @@
 
 #include "../../include/sdmi.h"
 #include "error.hpp"
+#include "gemm_plan.hpp"
 #include "kernels.hpp"
 
 namespace sdmi {
@@ -131,8 +132,6 @@ struct LoraTarget { int entry; int rank; double alpha; float* down; float* up; }
 // Per-module scalar / 2-vector files of the dump tree that are not tensors (python/save.py:23-68): `store` != null: the value
 // is honoured (a norm's eps); otherwise it must equal `expect` (the hyper-parameters this engine hard-wires).
 struct MetaEntry { std::string name; int n; float expect[2]; float* store; };
-
-struct TileChoice { int cfg; int splits; };
 
 class Engine {
 public:
@@ -331,13 +330,16 @@ private:
     void gemm(const float* A, int a_rows, const float* bt, const float* bias, int cin, int cout, float* C, int ldc,
               const float* resid, int ldr, int dt = -1, int out_mode = 0, const void* A3 = nullptr, void* C3 = nullptr);
     // fp32 engine, option gemm_planes: does the GEMM cin -> cout take its activations as planes (k_gemm3p.hip)?
-    bool plane_gemm(int cin, int cout) const { return !bf16_ && opt_gemm_planes_ != 0 && opt_gemm_f32s_ != 0 && cin % 32 == 0 && cout >= 32; }
-    void launch_gemm(ConvGemm& p, int in_dt, int force_cfg = -1, int force_splits = 0);
+    bool plane_gemm(int cin, int cout) const { return !bf16_ && gopt_.gemm_planes != 0 && gopt_.gemm_f32s != 0 && cin % 32 == 0 && cout >= 32; }
+    void launch_gemm(ConvGemm& p, int in_dt, int force_cfg = -1, int force_splits = 0);   // plan (gemm_plan.hpp), temporary plane / fp32 buffers, run_gemm
+    using GemmLauncher = hipError_t (*)(const ConvGemm&, int, hipStream_t);
+    struct GemmRun { GemmLauncher launch; int index; const char* what; int cfg; int pc; bool bf16_reduce, reduce_tag; double flops, bytes; };
+    void record_choice(const ConvGemm& p, const char* kind, int cfg, const char* note);
+    void run_gemm(ConvGemm& p, const GemmRun& r);   // kernel (+ slabs and split-K reduce), profiled and counted; shared with launch_fp8
     int edt() const { return bf16_ ? 1 : 0; }
     size_t esz() const { return bf16_ ? 2 : 4; }
     // element-wise pointer advance on an activation of type dt
     static float* adv(const float* p, long long elems, int dt) { return (float*)((char*)const_cast<float*>(p) + elems * (dt ? 2 : 4)); }
-    TileChoice choose_tile(int M, int N, int kt_total, bool allow_x = false, bool allow_s = false) const;   // cfg >= 100: k_gemm2x.hip tile cfg - 100, >= 200: k_gemm3x.hip tile cfg - 200
     void group_norm(const NormW& w, const Act& x, Act& y, bool silu);
     // precision = 2: GroupNorm(+SiLU) writing MXFP8, and the 3x3 convolution that consumes it (k_fp8.hip)
     ActQ new_actq(int n, int h, int w, int c);
@@ -518,38 +520,25 @@ private:
     } us_;
 
     // options
-    int opt_force_tile_ = -1;
-    int opt_force_splits_ = 0;
     int opt_resid_acc_ = 3;     // precision >= 1, large-tile kernels without split-K (ConvGemm::resid_acc): bit 0 = the residual, bit 1 = bias + time-embedding row are the accumulators'
                                 // initial value, loaded in front of the k loop; 0 = added by the epilogue (round 5)
-    int opt_attn_bf16_ = 1;
+    int opt_attn_bf16_ = 1;     // precision = 1: 1 = bf16 matrix-core attention, 0 = bf16 storage widened onto the fp32 kernel
     static constexpr int kAttnBf16VariantDefault = 7;
     int opt_attn_bf16_variant_ = kAttnBf16VariantDefault;   // k_attn_bf16.hip (AttnParams::variant): bit 0 = 4-wave workgroups, two per CU; bit 1 / 2 = 64 query rows per wave (d = 40) on 8- / 4-wave workgroups; 0x100 = whatever the grid (tests)
     int opt_geglu_fuse_ = 1;    // GEGLU gate in the projection GEMM's epilogue: 0 never, 1 where there are >= 4 rounds of tiles, 2 / 3 always (256x128 / 256x256 tiles; tests)
     int opt_attn_split_ = 1;    // precision = 0: 1 = d_head 40 / 80 attention on the bf16 matrix pipe with three-way split operands (k_attn_split.hip)
-    int opt_gemm_f32s_ = 1;     // precision = 0: 1 = fp32 GEMMs on the bf16 matrix pipe (three-way operand split, k_gemm3x.hip) where faster
     static constexpr int kGemm3xVariantDefault = 2;
     int opt_gemm3x_variant_ = kGemm3xVariantDefault;     // k_gemm3x.hip: bit 0: DMA in one block per k tile; bit 1: scalar residual subtractions (+0.7 %); bit 2: two LDS stages on the 128-row tiles
                                      // (default three: +5..10 % on long K); bit 4: s_setprio 1 for waves 4-7 (measured: no gain)
-    static constexpr int kGemmPlanesDefault = 1;
-    int opt_gemm_planes_ = kGemmPlanesDefault;   // precision = 0: k_gemm3p.hip (activations as bf16 planes too, no split in the k loop): 0 never, 1 every launch that would take a k_gemm3x.hip tile,
-                                // 2 = A/B switch (tests): every launch that chose a k_gemm3x.hip tile runs on the nearest k_gemm3p.hip tile, its fp32 input converted by split3_rows_kernel in front of it
-    int opt_conv3_reuse_ = 1;   // precision >= 1: 1 = 3x3 / stride-1 convolutions that chose the 256 x 320 / 256 x 256 tile run on k_gemm_bf16t.hip (one staged activation tile per kernel row)
     int opt_gemm_probe_ = 0;    // bench_conv: 1 = one extra launch with per-workgroup phase stamps (ConvGemm::probe), summary on stderr
     unsigned long long* probe_buf_ = nullptr;
     int opt_bench_cold_ = 0;    // bench_conv: 1 = evict the weights from the Infinity Cache between timed launches (what a layer sees inside the model)
-    int opt_gemm_x32_ = 1;      // precision = 0: 1 = large-tile LDS-DMA fp32 GEMM (k_gemm2x.hip) where measured / modelled faster
     static constexpr int kGemmBf16xVariantDefault = 5;
     int opt_gemm_bf16x_variant_ = kGemmBf16xVariantDefault; // precision >= 1, k_gemm_bf16x.hip / k_gemm_bf16t.hip: bit 2 (round 6) = waves 4 - 7 issue their DMA pieces between a tile's two k steps (one-tile forms and the kernel-row convolution); bit 0 = persistent tile loop (launches without split-K or residual and with more tiles than CUs;
                                      // bit-identical results, +0.4 ... 0.7 % per image: profiles/r05a_*)
-    int opt_gemm_bf16x_ = 1;    // precision = 1: 1 = large-tile LDS-DMA GEMM where the cost model prefers it; 0 = never
     void* zero_page_ = nullptr;
-    TileChoice choose_tile_p(int M, int N, int kt_total, bool even_ni_only) const;   // k_gemm3p.hip tiles (300 + x)
-    TileChoice choose_tile_bf16(int M, int N, int kt_total) const;   // cfg >= 100: k_gemm_bf16x.hip tile cfg - 100     // precision = 1: 1 = bf16 matrix-core attention, 0 = bf16 storage widened onto the fp32 kernel  // 1: attn2_kernel, 0: attn_f32_kernel
-    std::map<std::string, TileChoice> tuned_;        // fp32 kernels: "M,N,K" -> (tile cfg, split-K)
-    std::map<std::string, TileChoice> tuned_bf16_;   // bf16 kernels; cfg >= 100 = k_gemm_bf16x.hip tile
-    std::map<std::string, TileChoice> tuned_p_;      // fp32 shapes whose activations arrive as planes: k_gemm3p.hip tiles (300 + x) only
-    std::map<std::string, TileChoice> tuned_mfma_;   // fp32 shapes measured with the fp32-MFMA kernels only (gemm_f32s=0)
+    GemmPlanOpts gopt_;   // options gemm_tile, splitk, gemm_x32, gemm_f32s, gemm_bf16x, gemm_planes, conv3_reuse
+    GemmTuning tuning_;   // measured per-shape tile choices: tuning/gfx950_*.txt, options tune / tune_bf16 / tune_clear
     bool record_shapes_ = false;
     std::map<std::string, long long> shape_counts_;  // "n,cin,h,w,cout,k,stride,ups" -> launches
     std::map<std::string, long long> choice_counts_;   // "M,N,K cfg=.. splits=.." -> launches (record_shapes)

@@ -281,9 +281,6 @@ __global__ __launch_bounds__(512) void conv_gemm_fp8x_kernel(const ConvGemm p) {
     gemm_epilogue_bf16<MI, NI, WM, WN>(p, acc, smem_q, m0, n0, z, wave, lane, HoWo);
 }
 
-static const GemmTileInfo kTilesQ[kNumGemmTilesQ] = {{256, 320, "256x320q"}, {256, 256, "256x256q"}, {256, 128, "256x128q"}};
-const GemmTileInfo& gemm_tile_info_q(int cfg) { return kTilesQ[cfg]; }
-
 template <int MI, int NI, int WM, int WN>
 static hipError_t launch_cfg_fp8x(const ConvGemm& p, dim3 grid, hipStream_t stream) {
     auto k = conv_gemm_fp8x_kernel<MI, NI, WM, WN>;

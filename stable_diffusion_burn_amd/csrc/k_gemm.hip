@@ -163,21 +163,6 @@ __global__ void pack_linear_weight_kernel(const float* __restrict__ w, float* __
 }
 
 // ---- host side ----------------------------------------------------------------------
-static const GemmTileInfo kTiles[kNumGemmTiles] = {
-    {128, 128, "128x128"},  // 0: wave 64x64
-    {128, 64, "128x64"},    // 1: wave 64x32
-    {64, 64, "64x64"},      // 2: wave 32x32
-    {256, 128, "256x128"},  // 3: wave 128x64
-    {128, 80, "128x80"},    // 4: wave 32x80  (N = 320 -> 4 column tiles)
-    {256, 80, "256x80"},    // 5: wave 64x80
-    {64, 128, "64x128"},    // 6: wave 32x64
-    {128, 160, "128x160"},  // 7: wave 64x80 (2x2 waves)
-    {64, 80, "64x80"},      // 8: wave 16x80  (M = 8192, N = 320 -> 512 tiles, no split-K)
-    {64, 160, "64x160"},    // 9: wave 32x80 (2x2 waves)
-};
-
-const GemmTileInfo& gemm_tile_info(int cfg) { return kTiles[cfg]; }
-
 hipError_t launch_splitk_reduce(const ConvGemm& p, hipStream_t stream) {
     const bool vec = splitk_reduce_vec(p, false);
     if (!vec && (p.C3 || !p.C)) return hipErrorInvalidValue;   // the plane output is part of the 16-byte path only

@@ -21,7 +21,7 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void global_cvoid;
 
-// tile list shared with the bf16 kernel: gemm_tile_info_x() (k_gemm_bf16x.hip)
+// tile list shared with the bf16 kernel: gemm_tile_info_x() (gemm_tiles.hpp)
 
 template <int MI, int NI, int WM, int WN>
 __global__ __launch_bounds__(512) void conv_gemm2x_kernel(const ConvGemm p) {

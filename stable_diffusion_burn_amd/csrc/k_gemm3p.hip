@@ -32,11 +32,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void global_cvoid;
 
-static const GemmTileInfo kTilesP[kNumGemmTilesP] = {
-    {256, 160, "256x160p"}, {256, 128, "256x128p"}, {128, 256, "128x256p"}, {128, 160, "128x160p"}, {128, 128, "128x128p"},
-    {64, 64, "64x64p"}, {64, 128, "64x128p"}, {64, 320, "64x320p"}, {128, 64, "128x64p"}};
-const GemmTileInfo& gemm_tile_info_p(int cfg) { return kTilesP[cfg]; }
-
 // Per-wave state of the k loop; every array is indexed with compile-time constants (member templates) and lives in registers.  The
 // issue order of a k tile is spelled out and fenced with sched_barrier(0) as in k_gemm3x.hip: with LDS-DMA in flight every wait hipcc
 // inserts is lgkmcnt(0), so a plane read is issued NI matrix instructions or more ahead of its first use and never right in front of it.

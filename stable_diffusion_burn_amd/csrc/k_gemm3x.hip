@@ -39,10 +39,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void global_cvoid;
 
-static const GemmTileInfo kTilesS[kNumGemmTilesS] = {
-    {256, 160, "256x160s"}, {128, 320, "128x320s"}, {256, 128, "256x128s"}, {128, 256, "128x256s"}, {128, 160, "128x160s"}, {128, 128, "128x128s"}};
-const GemmTileInfo& gemm_tile_info_s(int cfg) { return kTilesS[cfg]; }
-
 // Per-wave state of the k loop.  Everything is indexed with compile-time constants (member templates), so the arrays live in
 // registers; the issue order of one k tile is spelled out instruction group by instruction group and fenced with
 // sched_barrier(0), because (a) hipcc otherwise hoists all the splits in front of the MFMAs and (b) with LDS-DMA in flight its

@@ -32,9 +32,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void global_cvoid;
 
-static const GemmTileInfo kTilesT[kNumGemmTilesT] = {{256, 320, "256x320t"}, {256, 256, "256x256t"}};
-const GemmTileInfo& gemm_tile_info_t(int cfg) { return kTilesT[cfg]; }
-
 // WF = W / 16: fragments per image row (1, 2, 4, 8)
 template <int NI, int WF>
 __global__ __launch_bounds__(512) void conv3_gemm_bf16t_kernel(const ConvGemm p) {
@@ -221,20 +218,9 @@ static hipError_t launch_cfg_bf16t(const ConvGemm& p, dim3 grid, hipStream_t str
     return hipGetLastError();
 }
 
-// what the kernel takes: a 3x3 / stride-1 / pad-1 convolution without upsampling over images whose width is 16, 32, 64 or 128 and whose pixel count is a
-// multiple of the 256-row tile (so a tile lies inside one image), bf16 storage, k slices of whole kernel rows, no GEGLU pairing
-bool conv_gemm_bf16t_supported(const ConvGemm& p) {
-    if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.ups != 0 || p.geglu) return false;
-    if ((p.Cin % 64) || !p.zero_page) return false;
-    if (p.Ws != 16 && p.Ws != 32 && p.Ws != 64 && p.Ws != 128) return false;
-    if (p.Ho != p.Hs || p.Wo != p.Ws || (p.Hs * p.Ws) % 256 || p.M % 256) return false;
-    if (p.kt_per_split % 3) return false;
-    return true;
-}
-
 hipError_t launch_conv_gemm_bf16t(const ConvGemm& p, int cfg, hipStream_t stream) {
-    if (cfg < 0 || cfg >= kNumGemmTilesT || !conv_gemm_bf16t_supported(p)) return hipErrorInvalidValue;
-    const int bm = kTilesT[cfg].bm, bn = kTilesT[cfg].bn;
+    if (cfg < 0 || cfg >= kNumGemmTilesT || !conv_gemm_bf16t_supported(p, p.kt_per_split)) return hipErrorInvalidValue;
+    const int bm = gemm_tile_info_t(cfg).bm, bn = gemm_tile_info_t(cfg).bn;
     const int MT = p.M / bm, NT = (p.N + bn - 1) / bn;
     const dim3 grid = gemm_grid(p, MT * NT);
     const int wf = p.Ws / 16;

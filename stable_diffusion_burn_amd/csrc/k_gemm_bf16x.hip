@@ -35,10 +35,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void global_cvoid;
 
-static const GemmTileInfo kTilesX[kNumGemmTilesX] = {
-    {256, 320, "256x320x"}, {256, 256, "256x256x"}, {256, 128, "256x128x"}, {128, 320, "128x320x"}};
-const GemmTileInfo& gemm_tile_info_x(int cfg) { return kTilesX[cfg]; }
-
 // PERSIST (round 5; ConvGemm::variant bit 0, launches without split-K and with more tiles than workgroups): the grid is one workgroup per CU and every workgroup
 // walks the tiles vb = blockIdx.x, blockIdx.x + gridDim.x, ... of the same XCD-aware order.  Behind the last k tile of a tile: workgroup barrier (every wave is done
 // with stage L) -> the FIRST k tile of the next tile is DMA'd into stage L -> epilogue with its LDS scratch in stage L ^ 1 (free since the top of the last k

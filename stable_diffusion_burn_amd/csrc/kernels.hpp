@@ -10,6 +10,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "gemm_tiles.hpp"
 
 namespace sdmi {
 
@@ -67,28 +68,17 @@ inline dim3 gemm_grid(const ConvGemm& p, int tiles) {
     return dim3((unsigned)(((tiles + 7) / 8) * 8), 1, (unsigned)p.splits);
 }
 
-// tile configurations (index = tile_cfg); BM x BN per 256-thread workgroup
-struct GemmTileInfo { int bm, bn; const char* name; };
-constexpr int kNumGemmTiles = 10;
-const GemmTileInfo& gemm_tile_info(int cfg);
-hipError_t launch_conv_gemm2(const ConvGemm& p, int tile_cfg, hipStream_t stream);  // k_gemm2.hip
+hipError_t launch_conv_gemm2(const ConvGemm& p, int tile_cfg, hipStream_t stream);  // k_gemm2.hip; the tile lists of every family (index = tile_cfg): gemm_tiles.hpp
 size_t gemm2_tile_lds_bytes(int cfg);
 // bf16 storage / fp32 accumulate (k_gemm_bf16.hip); A, Bt, resid and (unless out_mode == 1) C are bf16
 hipError_t launch_conv_gemm_bf16(const ConvGemm& p, int tile_cfg, hipStream_t stream);
 hipError_t launch_splitk_reduce_bf16(const ConvGemm& p, hipStream_t stream);
 // large-tile (256-row, 8-wave, LDS-DMA staged) bf16 kernel (k_gemm_bf16x.hip); its own tile list
-constexpr int kNumGemmTilesX = 4;
-const GemmTileInfo& gemm_tile_info_x(int cfg);
 hipError_t launch_conv_gemm_bf16x(const ConvGemm& p, int tile_cfg, hipStream_t stream);
 // the 256 x 320 / 256 x 256 tiles for 3x3 / stride-1 / pad-1 convolutions with the three taps of a kernel row read from one staged activation tile
-// (k_gemm_bf16t.hip); bf16 tile_cfg 100 + kNumGemmTilesX + x.  launch_conv_gemm_bf16t fails (hipErrorInvalidValue) unless conv_gemm_bf16t_supported(p).
-constexpr int kNumGemmTilesT = 2;
-const GemmTileInfo& gemm_tile_info_t(int cfg);
-bool conv_gemm_bf16t_supported(const ConvGemm& p);          // needs p.kt_per_split
+// (k_gemm_bf16t.hip); bf16 tile_cfg 100 + kNumGemmTilesX + x.  launch_conv_gemm_bf16t fails (hipErrorInvalidValue) unless conv_gemm_bf16t_supported(p, p.kt_per_split).
 hipError_t launch_conv_gemm_bf16t(const ConvGemm& p, int tile_cfg, hipStream_t stream);
 // bf16 large tiles as one list: 100 + [0, kNumGemmTilesX) = k_gemm_bf16x.hip, then k_gemm_bf16t.hip
-constexpr int kNumGemmTilesXB = kNumGemmTilesX + kNumGemmTilesT;
-inline const GemmTileInfo& gemm_tile_info_xb(int c) { return c < kNumGemmTilesX ? gemm_tile_info_x(c) : gemm_tile_info_t(c - kNumGemmTilesX); }
 inline hipError_t launch_conv_gemm_bf16_large(const ConvGemm& p, int c, hipStream_t stream) {
     return c < kNumGemmTilesX ? launch_conv_gemm_bf16x(p, c, stream) : launch_conv_gemm_bf16t(p, c - kNumGemmTilesX, stream);
 }
@@ -96,13 +86,9 @@ inline hipError_t launch_conv_gemm_bf16_large(const ConvGemm& p, int c, hipStrea
 hipError_t launch_conv_gemm2x(const ConvGemm& p, int tile_cfg, hipStream_t stream);
 // fp32 on the bf16 matrix pipe: operands as exact sums of three bf16 terms, six partial products (k_gemm3x.hip); its own tile
 // list; needs p.Bt3 (launch_pack_split3 of the packed fp32 rows, once at load)
-constexpr int kNumGemmTilesS = 6;
-const GemmTileInfo& gemm_tile_info_s(int cfg);
 hipError_t launch_conv_gemm3x(const ConvGemm& p, int tile_cfg, hipStream_t stream);
 hipError_t launch_pack_split3(const float* bt, void* w3, long long rows, int K, hipStream_t s, bool grouped = false);   // grouped needs rows % 16 == 0
 // the same arithmetic with the ACTIVATIONS as planes too, written once by their producer (k_gemm3p.hip; tile_cfg 300 + x; needs p.A3)
-constexpr int kNumGemmTilesP = 9;
-const GemmTileInfo& gemm_tile_info_p(int cfg);
 hipError_t launch_conv_gemm3p(const ConvGemm& p, int tile_cfg, hipStream_t stream);
 // fp32 rows [rows][ld] (c channels, c % 32 == 0) -> planes [rows][ld3_bytes / 192 slices][3][32] bf16 (slices [0, c / 32) written)
 hipError_t launch_split3_rows(const float* x, void* y3, long long rows, int c, long long ld, long long ld3_bytes, hipStream_t s);
@@ -110,8 +96,6 @@ hipError_t launch_join3_rows(const void* x3, float* y, long long rows, int c, lo
 // hipFuncAttributeMaxDynamicSharedMemorySize, once per (kernel, device); safe to call from several host threads (multi.cpp)
 hipError_t set_max_dynamic_lds(const void* kernel, int bytes);
 // MXFP8 (e4m3 + E8M0 block scales) 256-row LDS-DMA kernel on v_mfma_scale_f32_16x16x128_f8f6f4 (k_fp8.hip); its own tile list
-constexpr int kNumGemmTilesQ = 3;
-const GemmTileInfo& gemm_tile_info_q(int cfg);
 hipError_t launch_conv_gemm_fp8x(const ConvGemm& p, int tile_cfg, hipStream_t stream);
 // fp32 OIHW -> e4m3 [Cout][Kp] + scales [Cout][Kp / 32], Kp = roundup(Cin, 128) * kh * kw, k = (slice * T + tap) * 128 + ci
 hipError_t launch_pack_conv_weight_fp8(const float* w_oihw, void* bt8, void* bs, int cout, int cin, int kh, int kw, hipStream_t s);
