@@ -43,6 +43,20 @@ pub struct SdmiSampler {
     pub reserved: [i64; 4],
 }
 
+/// `sdmi_hires` (include/sdmi.h "hires fix"): the first pass's latent size, the resampling mode (0 nearest-exact, 1 bilinear, 2 bicubic;
+/// antialias for modes 1 and 2) and the img2img tail of the second pass (`hires_steps` 0 = n_steps, 0 < strength <= 1, noise stream `hires_seed + i`).
+#[repr(C)]
+pub struct SdmiHires {
+    pub base_h: i32,
+    pub base_w: i32,
+    pub mode: i32,
+    pub antialias: i32,
+    pub hires_steps: i64,
+    pub strength: f64,
+    pub hires_seed: u64,
+    pub reserved: [i64; 4],
+}
+
 #[link(name = "sdmi")]
 extern "C" {
     fn sdmi_default_config(cfg: *mut SdmiConfig) -> c_int;
@@ -79,6 +93,11 @@ extern "C" {
     fn sdmi_img2img_image_dev(ctx: *mut c_void, context: *const c_float, n: i32, t_len: i32, uncond: *const c_float, tu: i32, scale: c_double,
                               n_steps: usize, strength: c_double, init_rgb: *const u8, mask: *const c_float, noise: *const c_float, seed: u64,
                               rgb_out: *mut u8) -> c_int;
+    fn sdmi_set_latent_size(ctx: *mut c_void, h: i32, w: i32) -> c_int;
+    fn sdmi_get_latent_size(ctx: *mut c_void, h: *mut i32, w: *mut i32) -> c_int;
+    fn sdmi_hires_image(ctx: *mut c_void, context: *const c_float, n: i32, t_len: i32, uncond: *const c_float, tu: i32, scale: c_double,
+                        n_steps: usize, init_latent: *const c_float, seed: u64, hires: *const SdmiHires, hires_noise: *const c_float,
+                        rgb_out: *mut u8) -> c_int;
     fn sdmi_set_sampler(ctx: *mut c_void, sampler: *const SdmiSampler) -> c_int;
     fn sdmi_get_sampler(ctx: *mut c_void, out: *mut SdmiSampler) -> c_int;
     fn sdmi_multi_set_sampler(m: *mut c_void, sampler: *const SdmiSampler) -> c_int;
@@ -203,6 +222,39 @@ impl StableDiffusionMi355 {
             return Err(last_error().into());
         }
         Ok(())
+    }
+
+    /// The latent size [h, w] of every later call (`sdmi_set_latent_size`, sticky; no reference counterpart: the reference's latent is 4x64x64):
+    /// positive multiples of 8, pictures are 8x.  The weights do not depend on it.
+    pub fn set_latent_size(&mut self, h: i32, w: i32) -> Result<(), Box<dyn Error>> {
+        if unsafe { sdmi_set_latent_size(self.ctx, h, w) } != 0 {
+            return Err(last_error().into());
+        }
+        self.latent = 4 * (h * w) as usize;
+        Ok(())
+    }
+
+    /// The latent size in force (`sdmi_get_latent_size`).
+    pub fn latent_size(&self) -> (i32, i32) {
+        let (mut h, mut w) = (0i32, 0i32);
+        check(unsafe { sdmi_get_latent_size(self.ctx, &mut h, &mut w) });
+        (h, w)
+    }
+
+    /// Hires fix (include/sdmi.h "hires fix"; no reference counterpart): `sample_image` at `hires.base_h x base_w`, the latent resampled on the
+    /// device to the current size, re-noised to the last `strength` of the `hires_steps` schedule and finished there.  Seeds replace the noise tensors.
+    pub fn sample_image_hires(&self, context: &[f32], n_batch: usize, unconditional_context: &[f32], unconditional_guidance_scale: f64,
+                              n_steps: usize, seed: u64, hires: &SdmiHires) -> Vec<Vec<u8>> {
+        let t = context.len() / (n_batch * self.ctx_dim);
+        let tu = unconditional_context.len() / self.ctx_dim;
+        assert_eq!(context.len(), n_batch * t * self.ctx_dim);
+        let per = self.latent / 4 * 64 * 3;
+        let mut flat = vec![0u8; n_batch * per];
+        check(unsafe {
+            sdmi_hires_image(self.ctx, context.as_ptr(), n_batch as i32, t as i32, unconditional_context.as_ptr(), tu as i32,
+                             unconditional_guidance_scale, n_steps, std::ptr::null(), seed, hires, std::ptr::null(), flat.as_mut_ptr())
+        });
+        flat.chunks(per).map(|c| c.to_vec()).collect()
     }
 
     /// The sampler of every later sampling call (`sdmi_set_sampler`, sticky; no reference counterpart: the reference is DDIM at eta = 0).

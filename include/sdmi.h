@@ -237,6 +237,58 @@ int sdmi_get_sampler(sdmi_ctx* ctx, sdmi_sampler* out);
 int sdmi_sampler_coefs(const sdmi_sampler* sampler, const float* alphas_cumprod, int32_t total, const int32_t* ts, int32_t count,
                        int64_t step_size, double* coefs);
 
+/* ---- latent size per call, and the two-pass "hires fix" (no reference counterpart: its latent is hard-coded 4x64x64, stablediffusion/mod.rs:116;
+ * DESIGN.md section 9d) ----
+ * The weights do not depend on the picture size and the context caches nothing per size, so one context serves any size.  sdmi_config.latent_h / latent_w are
+ * the INITIAL size; sdmi_set_latent_size changes it for every later call of the context -- unet_forward, sample_*, img2img_*, decode / encode / latent_to_image,
+ * host and device pointers: each reads the current size for its shapes and buffers -- until it is changed again: sticky, like sdmi_set_sampler and
+ * sdmi_set_stream.  The rule is sdmi_create's: positive multiples of 8; anything else is SDMI_ERR_INVALID and changes nothing.  The contexts of an sdmi_multi
+ * are set one by one (sdmi_multi_ctx); sdmi_sample_image_sharded returns SDMI_ERR_STATE when they disagree. */
+int sdmi_set_latent_size(sdmi_ctx* ctx, int32_t h, int32_t w);
+int sdmi_get_latent_size(sdmi_ctx* ctx, int32_t* h, int32_t* w);
+
+/* Host only, needs no device: THE resampling rule of one axis (the engine calls it once per axis and applies the table as f32).  Output index o is
+ *     y[o] = sum_{j < count[o]} taps[o * *max_taps + j] * x[first[o] + j]          (ascending j; 0 <= first[o], first[o] + count[o] <= in_size)
+ * mode 0 nearest-exact (one tap 1.0), 1 bilinear, 2 bicubic; antialias != 0 (modes 1 and 2 only) selects the antialiased filters.  The definition is
+ * torch.nn.functional.interpolate(x, size = out_size, mode = ..., align_corners = False, antialias = ...) on the CPU in float64, its border rule and its
+ * bicubic constants (A = -0.75; -0.5 antialiased) included; a tap torch clamps to the border is folded onto the border index, so every index is in range.
+ * Mode 0: torch keeps two nearest-exact rules, floorf((o + 0.5) * scale) with scale = in / out held in float or in double, which differ where scale (o + 0.5) is
+ * an integer in exact arithmetic, and picks by the output size of the whole call (float where out_h + out_w <= 128).  One axis cannot see the other: the table
+ * is torch's on a one-axis tensor [1,1,1,in_size] -> (1, out_size), i.e. the float rule where out_size + 1 <= 128, the double rule above.
+ * in_size == out_size gives the single tap 1.0 at first[o] = o in every mode.  *max_taps (may be NULL) = the largest count; *needed (may be NULL) = the number
+ * of doubles `taps` must hold = out_size * *max_taps; both are always set when the arguments are valid.  first / count hold out_size entries.  With first,
+ * count and taps all NULL the call is the capacity query.  SDMI_ERR_INVALID: a size < 1, a mode outside 0..2, antialias with mode 0, some but not all
+ * outputs NULL, capacity < *needed (nothing is written). */
+int sdmi_resize_weights(int32_t in_size, int32_t out_size, int32_t mode, int32_t antialias, int32_t* first, int32_t* count, double* taps,
+                        int32_t capacity, int32_t* max_taps, int32_t* needed);
+
+/* Hires fix: sample at the size the model was trained for, enlarge the latent on the device, re-noise it part-way and finish the schedule at the context's
+ * size H x W (the output size, as for every other call):
+ *   1. sdmi_sample_latent at base_h x base_w: init_latent [n,4,base_h,base_w] = x_T, or NULL: image i draws from stream seed + i at that size.
+ *   2. its final latent resampled to H x W by the rule of sdmi_resize_weights(mode, antialias), rows then columns (csrc/k_resize.hip).
+ *   3. sdmi_img2img_latent at H x W, unchanged, without a mask: timesteps sdmi_img2img_timesteps(total, hires_steps ? hires_steps : n_steps, strength),
+ *      x_t0 = sqrt(a_t0) z0 + sqrt(1 - a_t0) eps with z0 = the result of 2 and eps = hires_noise [n,4,H,W], or NULL: image i's stream hires_seed + i.
+ * The sticky sampler applies to both passes; its history starts empty in the second pass, as in any img2img tail, and both passes key their step noise by the
+ * same noise_seed (rule of sdmi_set_sampler: the index in each pass's own full schedule).  Nothing leaves the device between the passes.  The result equals,
+ * bit for bit, the composition of the public calls set_latent_size(base), sample_latent, set_latent_size(H, W), sdmi_op_resize, img2img_latent.
+ * SDMI_ERR_INVALID: hires NULL, a base size that breaks the size rule, mode outside 0..2, antialias with mode 0, strength outside (0, 1], a schedule that
+ * leaves no step (k < 1).  After any error the context's size is what it was.  The GEMM tile tables hold no entries tuned for other sizes than 64 x 64:
+ * the planner's fallbacks serve them. */
+typedef struct sdmi_hires {
+    int32_t base_h, base_w;   /* latent size of the first pass                          */
+    int32_t mode;             /* 0 nearest-exact, 1 bilinear, 2 bicubic                 */
+    int32_t antialias;        /* modes 1 and 2                                          */
+    int64_t hires_steps;      /* schedule length of the second pass; 0 = n_steps        */
+    double strength;          /* 0 < strength <= 1                                      */
+    uint64_t hires_seed;
+    int64_t reserved[4];
+} sdmi_hires;
+int sdmi_hires_latent(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps,
+                      const float* init_latent, uint64_t seed, const sdmi_hires* hires, const float* hires_noise, float* latent_out);
+/* rgb_out = sdmi_latent_to_image of sdmi_hires_latent's result: n x [8H,8W,3] uint8 */
+int sdmi_hires_image(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps,
+                     const float* init_latent, uint64_t seed, const sdmi_hires* hires, const float* hires_noise, uint8_t* rgb_out);
+
 /* ---- LoRA adapters: low-rank deltas merged into the packed weights on the device (no reference counterpart) ----
  * The reference runs the base checkpoint only.  An adapter is a set of targets -- conv or Linear weights named by their dump-tree path -- each
  * with two factors; at scale s the context computes with
@@ -324,6 +376,11 @@ int sdmi_img2img_latent_dev(sdmi_ctx* ctx, const float* context, int32_t n, int3
 int sdmi_img2img_image_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu,
                            double scale, size_t n_steps, double strength, const uint8_t* init_rgb, const float* mask,
                            const float* noise, uint64_t seed, uint8_t* rgb_out);
+/* hires fix with device pointers: init_latent [n,4,base_h,base_w] is required (as in sdmi_sample_latent_dev); hires_noise may be NULL */
+int sdmi_hires_latent_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps,
+                          const float* init_latent, const sdmi_hires* hires, const float* hires_noise, float* latent_out);
+int sdmi_hires_image_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps,
+                         const float* init_latent, const sdmi_hires* hires, const float* hires_noise, uint8_t* rgb_out);
 
 /* ---- multi-GPU: the image batch sharded over the devices of one node ----------------------
  * The reference's caller asks one StableDiffusion for n images of one prompt (src/bin/sample/main.rs:104-109).
@@ -439,6 +496,11 @@ int sdmi_op_geglu(sdmi_ctx* ctx, const float* proj, int32_t rows, int32_t hidden
  * the others. No mask. out [n,nq,n_state]. */
 int sdmi_op_qkv_attention_ragged(sdmi_ctx* ctx, const float* q, const float* k, const float* v, const int32_t* kv_len,
                                  int32_t n, int32_t nq, int32_t nk, int32_t n_state, int32_t n_head, float* out);
+/* The resampler of the hires fix on its own (csrc/k_resize.hip; no reference counterpart): x [n,4,h,w] -> out [n,4,out_h,out_w] by the tables of
+ * sdmi_resize_weights(mode, antialias), applied as f32: the horizontal pass, then the vertical one, taps summed in ascending order (bit-identical run to
+ * run); an axis whose size does not change is skipped.  Any positive sizes. */
+int sdmi_op_resize(sdmi_ctx* ctx, const float* x, int32_t n, int32_t h, int32_t w, int32_t out_h, int32_t out_w, int32_t mode, int32_t antialias,
+                   float* out);
 /* timestep_embedding (unet/mod.rs:19-30): out [dim] for timestep t. */
 /* GEGLU::forward (src/model/unet/mod.rs:579-591): x [rows, cin], weight [cin, 2*hidden] (Burn Linear layout), bias
  * [2*hidden] or NULL -> out [rows, hidden] = a * gelu(b), a | b = the halves of x W + bias.  One fused kernel when the
@@ -463,7 +525,7 @@ int sdmi_last_call_stats(sdmi_ctx* ctx, double* gpu_ms, int64_t* n_kernels, doub
  * 6 conv_gemm_split (precision = 0: the conv/linear launches that run on the bf16 matrix pipe with three-way split fp32
  * operands, k_gemm3x.hip / k_gemm3p.hip; class 0 then holds the launches left on the fp32 matrix instruction), 7 split_rows (fp32 tensors
  * converted to bf16 planes for a plane GEMM outside their producer), 8 other (every launch of the path that is in no other class: layout converters, the
- * CFG + DDIM update, the sampler-choice step (k_sampler.hip), img2img's u8 -> fp32 input conversion, start latent and masked CFG + DDIM update, timestep embedding, SiLU of the embedding, row softmax / transposes of the unfused VAE attention, u8 conversion), 9 geglu (the GEGLU gate kernels
+ * CFG + DDIM update, the sampler-choice step (k_sampler.hip), img2img's u8 -> fp32 input conversion, start latent and masked CFG + DDIM update, the resampler of the hires fix (k_resize.hip), timestep embedding, SiLU of the embedding, row softmax / transposes of the unfused VAE attention, u8 conversion), 9 geglu (the GEGLU gate kernels
  * where the gate is not fused into its GEMM; the quantising gate of precision = 2 included).  flops / bytes are the ALGORITHMIC work of
  * those launches (2*M*N*K; one read + one write of the tensor).  "profile_reset" clears. */
 int sdmi_profile_stats(sdmi_ctx* ctx, int32_t cls, double* ms, int64_t* launches, double* flops, double* bytes);

@@ -42,7 +42,14 @@ class SdmiSampler(C.Structure):
                 ("reserved", C.c_int64 * 4)]
 
 
+class SdmiHires(C.Structure):
+    """sdmi_hires: the second pass of the hires fix (sdmi_hires_latent / sdmi_hires_image)"""
+    _fields_ = [("base_h", C.c_int32), ("base_w", C.c_int32), ("mode", C.c_int32), ("antialias", C.c_int32), ("hires_steps", C.c_int64),
+                ("strength", C.c_double), ("hires_seed", C.c_uint64), ("reserved", C.c_int64 * 4)]
+
+
 _F = C.POINTER(C.c_float)
+_HIRES = C.POINTER(SdmiHires)
 _SAMPLER = C.POINTER(SdmiSampler)
 _VIEW = C.POINTER(SdmiOpView)
 _U8 = C.POINTER(C.c_uint8)
@@ -79,6 +86,14 @@ SIGNATURES = {
     "sdmi_set_sampler": (C.c_int, [_CTX, _SAMPLER]),
     "sdmi_get_sampler": (C.c_int, [_CTX, _SAMPLER]),
     "sdmi_sampler_coefs": (C.c_int, [_SAMPLER, _F, C.c_int32, _I32, C.c_int32, C.c_int64, C.POINTER(C.c_double)]),
+    "sdmi_set_latent_size": (C.c_int, [_CTX, C.c_int32, C.c_int32]),
+    "sdmi_get_latent_size": (C.c_int, [_CTX, _I32, _I32]),
+    "sdmi_resize_weights": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I32, _I32, C.POINTER(C.c_double), C.c_int32, _I32, _I32]),
+    "sdmi_hires_latent": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F, C.c_int32, C.c_double, C.c_size_t, _F, C.c_uint64, _HIRES, _F, _F]),
+    "sdmi_hires_image": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F, C.c_int32, C.c_double, C.c_size_t, _F, C.c_uint64, _HIRES, _F, _U8]),
+    "sdmi_hires_latent_dev": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_size_t, C.c_void_p, _HIRES, C.c_void_p, C.c_void_p]),
+    "sdmi_hires_image_dev": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_size_t, C.c_void_p, _HIRES, C.c_void_p, C.c_void_p]),
+    "sdmi_op_resize": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),
     "sdmi_multi_set_sampler": (C.c_int, [C.c_void_p, _SAMPLER]),
     "sdmi_lora_create": (C.c_int, [_CTX, C.POINTER(C.c_void_p)]),
     "sdmi_lora_add": (C.c_int, [C.c_void_p, C.c_char_p, _F, _F, C.c_int32, C.c_float]),

@@ -218,8 +218,9 @@ Engine::Engine(const sdmi_config& cfg) : cfg_(cfg) {
     if (cfg.vae_ch % 32 || cfg.vae_ch <= 0) throw Error(SDMI_ERR_INVALID, "vae_ch must be a positive multiple of 32");
     if (cfg.n_head <= 0 || cfg.model_channels % cfg.n_head) throw Error(SDMI_ERR_INVALID, "n_head must divide model_channels");
     if (cfg.ctx_dim % 32 || cfg.ctx_dim <= 0) throw Error(SDMI_ERR_INVALID, "ctx_dim must be a positive multiple of 32");
-    if (cfg.latent_h % 8 || cfg.latent_w % 8 || cfg.latent_h <= 0 || cfg.latent_w <= 0)
-        throw Error(SDMI_ERR_INVALID, "latent_h/latent_w must be positive multiples of 8");
+    check_latent_size(cfg.latent_h, cfg.latent_w);
+    lat_h_ = cfg.latent_h;
+    lat_w_ = cfg.latent_w;
     int ndev = 0;
     SDMI_HIP(hipGetDeviceCount(&ndev));
     if (ndev <= 0) throw Error(SDMI_ERR_HIP, "no HIP device visible: libsdmi has no CPU fallback");
@@ -247,6 +248,10 @@ Engine::Engine(const sdmi_config& cfg) : cfg_(cfg) {
 }
 
 Engine::~Engine() { destroy(); }
+
+void Engine::check_latent_size(int h, int w) {
+    if (h % 8 || w % 8 || h <= 0 || w <= 0) throw Error(SDMI_ERR_INVALID, "latent_h/latent_w must be positive multiples of 8");
+}
 
 void Engine::destroy() noexcept {
     (void)hipSetDevice(cfg_.device);
@@ -2022,7 +2027,7 @@ void Engine::unet_prepare(const float* ctx_packed, int nb, int t_max, const int*
 // the middle block) writes the x slice, and output block i reads the whole buffer.
 void Engine::unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bool cfg_pair) {
     Range rng(this, "UNet::forward step " + std::to_string(step));
-    const int H = cfg_.latent_h, W = cfg_.latent_w;
+    const int H = lat_h_, W = lat_w_;
     Act x; x.p = const_cast<float*>(x_nhwc); x.n = nb; x.h = H; x.w = W; x.c = 4; x.dt = 0;  // latents stay fp32
 
     // every block's last kernel writes `y` (dense or a channel slice)
@@ -2144,7 +2149,7 @@ void Engine::unet_forward_dev(const float* x_nchw, int t, const float* context, 
     if (!finalized_) throw Error(SDMI_ERR_STATE, "weights not finalized");
     if (n <= 0 || T <= 0) throw Error(SDMI_ERR_INVALID, "unet_forward: n and T must be positive");
     check_batch(n);
-    const int H = cfg_.latent_h, W = cfg_.latent_w;
+    const int H = lat_h_, W = lat_w_;
     std::vector<int> kv(n, T), ts(1, t);
     unet_prepare(context, n, T, kv.data(), ts);
     Buf xin(this, (size_t)n * H * W * 4 * 4), xout(this, (size_t)n * H * W * 4 * 4);
@@ -2158,13 +2163,13 @@ void Engine::unet_forward_dev(const float* x_nchw, int t, const float* context, 
 
 // StableDiffusion::sample_latent + forward_diffuser (stablediffusion/mod.rs:102-192)
 void Engine::sample_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale,
-                               size_t n_steps, const float* init_latent, float* latent_out) {
+                               size_t n_steps, const float* init_latent, float* latent_out, bool out_nhwc) {
     if (!finalized_) throw Error(SDMI_ERR_STATE, "weights not finalized");
     if (n <= 0 || T <= 0 || Tu <= 0) throw Error(SDMI_ERR_INVALID, "sample_latent: n, T, Tu must be positive");
     check_batch(n);
     const size_t total = alphas_.size();
     if (n_steps == 0 || n_steps > total) throw Error(SDMI_ERR_INVALID, "sample_latent: n_steps out of range");
-    const int H = cfg_.latent_h, W = cfg_.latent_w;
+    const int H = lat_h_, W = lat_w_;
     const size_t step_size = total / n_steps;                       // :111
     std::vector<int> ts;
     for (long long t = (long long)total - 1; t >= 0; t -= (long long)step_size) ts.push_back((int)t);  // :123
@@ -2172,7 +2177,7 @@ void Engine::sample_latent_dev(const float* context, int n, int T, const float* 
         SDMI_HIP(launch_nchw_to_nhwc(init_latent, latent, n, 4, H, W, 1.0f, stream_));
         { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_dup_latent(latent, unet_in, per_half, stream_)); }
         count_kernel(); count_kernel();
-    }, nullptr, latent_out);
+    }, nullptr, latent_out, out_nhwc);
 }
 
 void Engine::check_sampler(const sdmi_sampler& s) {
@@ -2189,8 +2194,8 @@ void Engine::set_sampler(const sdmi_sampler* s) {
 
 void Engine::sample_loop(const float* context, int n, int T, const float* uncond, int Tu, double scale, const std::vector<int>& ts,
                          size_t step_size, const std::function<void(float* latent, float* unet_in, long long per_half)>& start,
-                         const Blend* blend, float* latent_out) {
-    const int H = cfg_.latent_h, W = cfg_.latent_w, cd = cfg_.ctx_dim;
+                         const Blend* blend, float* latent_out, bool out_nhwc) {
+    const int H = lat_h_, W = lat_w_, cd = cfg_.ctx_dim;
     const int nb = 2 * n, t_max = std::max(T, Tu);
 
     // packed context [2n][t_max][cd]: rows 0..n-1 = uncond (broadcast, :173-177), n..2n-1 = cond
@@ -2253,8 +2258,12 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
         else { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_cfg_ddim(eps.f(), latent.f(), unet_in.f(), per_half, c, stream_)); }
         count_kernel();
     }
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(latent.f(), latent_out, n, 4, H, W, stream_)); }
-    count_kernel();
+    if (out_nhwc) {
+        SDMI_HIP(hipMemcpyAsync(latent_out, latent.p, (size_t)per_half * 4, hipMemcpyDeviceToDevice, stream_));
+    } else {
+        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(latent.f(), latent_out, n, 4, H, W, stream_)); }
+        count_kernel();
+    }
     unet_release();
 }
 
@@ -2278,7 +2287,7 @@ void Engine::img2img_latent_dev(const float* context, int n, int T, const float*
                                 double strength, const float* z0, const float* mask, const float* noise, uint64_t seed, float* latent_out) {
     size_t step_size = 0;
     const std::vector<int> ts = img2img_schedule(n, T, Tu, n_steps, strength, &step_size);
-    const long long hw = (long long)cfg_.latent_h * cfg_.latent_w, elems = (long long)n * hw * 4;
+    const long long hw = (long long)lat_h_ * lat_w_, elems = (long long)n * hw * 4;
     const double a0 = (double)alphas_[ts[0]];
     const float sqrt_a = (float)std::sqrt(a0), sqrt_1ma = (float)std::sqrt(1.0 - a0);
     Buf z0k(this, mask ? elems * 4 : 256), e0k(this, mask ? elems * 4 : 256);   // z0 and eps for the blend (NHWC)
@@ -2295,7 +2304,7 @@ void Engine::img2img_image_dev(const float* context, int n, int T, const float* 
     if (finalized_ && !enc_ready_) throw Error(SDMI_ERR_STATE, "VAE encoder weights are not loaded (autoencoder/encoder/..., autoencoder/quant_conv)");
     size_t step_size = 0;
     const std::vector<int> ts = img2img_schedule(n, T, Tu, n_steps, strength, &step_size);
-    const int H = cfg_.latent_h, W = cfg_.latent_w;
+    const int H = lat_h_, W = lat_w_;
     const long long hw = (long long)H * W, elems = (long long)n * hw * 4;
     const double a0 = (double)alphas_[ts[0]];
     const float sqrt_a = (float)std::sqrt(a0), sqrt_1ma = (float)std::sqrt(1.0 - a0);
@@ -2317,10 +2326,110 @@ void Engine::img2img_image_dev(const float* context, int n, int T, const float* 
     }, mask ? &blend : nullptr, latent_out);
 }
 
+// ---- latent resampler + hires fix (include/sdmi.h "hires fix") ----------------------------------------------------
+namespace {
+// the table of one axis on the device: [first: out ints][count: out ints][taps: out * max_taps floats] in one pool buffer
+struct AxisTable {
+    std::unique_ptr<Engine::Buf> buf;
+    int max_taps = 0, out = 0;
+    const int* first() const { return reinterpret_cast<const int*>(buf->p); }
+    const int* count() const { return first() + out; }
+    const float* taps() const { return reinterpret_cast<const float*>(count() + out); }
+};
+AxisTable upload_axis(Engine& e, int in_size, int out_size, int mode, int antialias) {
+    const std::vector<ResizeRow> rows = resize_rows(in_size, out_size, mode, antialias != 0);
+    size_t T = 0;
+    for (const ResizeRow& r : rows) {   // the kernel reads x[first .. first + count) unchecked
+        if (r.first < 0 || r.w.empty() || r.first + (long long)r.w.size() > in_size) throw Error(SDMI_ERR_STATE, "resize: tap table out of range");
+        T = std::max(T, r.w.size());
+    }
+    std::vector<int32_t> img(2 * (size_t)out_size + (size_t)out_size * T, 0);
+    float* tf = reinterpret_cast<float*>(img.data() + 2 * (size_t)out_size);
+    for (int o = 0; o < out_size; ++o) {
+        const ResizeRow& r = rows[(size_t)o];
+        img[(size_t)o] = r.first;
+        img[(size_t)out_size + o] = (int32_t)r.w.size();
+        for (size_t j = 0; j < r.w.size(); ++j) tf[(size_t)o * T + j] = (float)r.w[j];
+    }
+    AxisTable t;
+    t.max_taps = (int)T; t.out = out_size;
+    t.buf.reset(new Engine::Buf(&e, img.size() * 4));
+    // `img` is pageable and dies with this frame: HIP stages a pageable host-to-device copy before hipMemcpyAsync returns (stage_epi and unet_prepare rely on the same)
+    SDMI_HIP(hipMemcpyAsync(t.buf->p, img.data(), img.size() * 4, hipMemcpyHostToDevice, e.stream()));
+    return t;
+}
+}  // namespace
+
+void Engine::resize_nhwc4(const float* x, int n, int h, int w, int oh, int ow, int mode, int antialias, float* y) {
+    if (n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0) throw Error(SDMI_ERR_INVALID, "resize: sizes must be positive");
+    if (mode < 0 || mode > 2) throw Error(SDMI_ERR_INVALID, "resize: mode must be 0 (nearest-exact), 1 (bilinear) or 2 (bicubic)");
+    if (mode == 0 && antialias) throw Error(SDMI_ERR_INVALID, "resize: antialias belongs to modes 1 and 2");
+    if (h == oh && w == ow) {   // both axes are the identity
+        SDMI_HIP(hipMemcpyAsync(y, x, (size_t)n * h * w * 16, hipMemcpyDeviceToDevice, stream_));
+        return;
+    }
+    const float* src = x;
+    std::unique_ptr<Buf> mid;
+    if (w != ow) {   // horizontal: [n * h][w] -> [n * h][ow]
+        float* dst = y;
+        if (h != oh) { mid.reset(new Buf(this, (size_t)n * h * ow * 16)); dst = mid->f(); }
+        AxisTable t = upload_axis(*this, w, ow, mode, antialias);
+        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_resize_axis(src, dst, t.first(), t.count(), t.taps(), t.max_taps, (long long)n * h, w, ow, 1, mode == 0, stream_)); }
+        count_kernel();
+        src = dst;
+    }
+    if (h != oh) {   // vertical: [n][h][ow] -> [n][oh][ow]
+        AxisTable t = upload_axis(*this, h, oh, mode, antialias);
+        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_resize_axis(src, y, t.first(), t.count(), t.taps(), t.max_taps, n, h, oh, ow, mode == 0, stream_)); }
+        count_kernel();
+    }
+}
+
+void Engine::op_resize(const float* x_nchw, int n, int h, int w, int oh, int ow, int mode, int antialias, float* out_nchw) {
+    if (n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0) throw Error(SDMI_ERR_INVALID, "resize: sizes must be positive");
+    Buf xin(this, (size_t)n * h * w * 16), xout(this, (size_t)n * oh * ow * 16);
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nchw_to_nhwc(x_nchw, xin.f(), n, 4, h, w, 1.0f, stream_)); }
+    count_kernel();
+    resize_nhwc4(xin.f(), n, h, w, oh, ow, mode, antialias, xout.f());
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(xout.f(), out_nchw, n, 4, oh, ow, stream_)); }
+    count_kernel();
+}
+
+void Engine::check_hires(const sdmi_hires* hr) {
+    if (!hr) throw Error(SDMI_ERR_INVALID, "hires: null sdmi_hires");
+    check_latent_size(hr->base_h, hr->base_w);
+    if (hr->mode < 0 || hr->mode > 2) throw Error(SDMI_ERR_INVALID, "hires: mode must be 0 (nearest-exact), 1 (bilinear) or 2 (bicubic)");
+    if (hr->mode == 0 && hr->antialias) throw Error(SDMI_ERR_INVALID, "hires: antialias belongs to modes 1 and 2");
+    if (!(hr->strength > 0.0 && hr->strength <= 1.0)) throw Error(SDMI_ERR_INVALID, "hires: strength must satisfy 0 < strength <= 1");
+    if (hr->hires_steps < 0) throw Error(SDMI_ERR_INVALID, "hires: hires_steps must not be negative");
+}
+
+void Engine::hires_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps, const float* init_latent,
+                              const sdmi_hires& hr, const float* hires_noise, float* latent_out) {
+    check_hires(&hr);
+    const size_t steps2 = hr.hires_steps ? (size_t)hr.hires_steps : n_steps;
+    {   // the second pass's argument errors before the first pass runs
+        size_t step_size = 0;
+        (void)img2img_schedule(n, T, Tu, steps2, hr.strength, &step_size);
+    }
+    const int H = lat_h_, W = lat_w_;
+    Buf zb(this, (size_t)n * hr.base_h * hr.base_w * 16), zr(this, (size_t)n * H * W * 16), z0(this, (size_t)n * H * W * 16);
+    {
+        struct Restore { Engine* e; int h, w; ~Restore() { e->lat_h_ = h; e->lat_w_ = w; } } restore{this, H, W};
+        lat_h_ = hr.base_h; lat_w_ = hr.base_w;
+        sample_latent_dev(context, n, T, uncond, Tu, scale, n_steps, init_latent, zb.f(), /*out_nhwc=*/true);
+    }
+    resize_nhwc4(zb.f(), n, hr.base_h, hr.base_w, H, W, hr.mode, hr.antialias, zr.f());
+    // launch_img2img_start reads its caller's z0 as NCHW: one transposing launch in front of it, and the second pass is img2img_latent_dev itself
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(zr.f(), z0.f(), n, 4, H, W, stream_)); }
+    count_kernel();
+    img2img_latent_dev(context, n, T, uncond, Tu, scale, steps2, hr.strength, z0.f(), nullptr, hires_noise, hr.hires_seed, latent_out);
+}
+
 // Autoencoder::decode_latent (autoencoder/mod.rs:68-71) -> Decoder::forward (:205-217)
 void Engine::decode_one(const float* z_nhwc, int n, Act& img) {
     Range rng(this, "Decoder::forward");
-    const int H = cfg_.latent_h, W = cfg_.latent_w, vc = cfg_.vae_ch;
+    const int H = lat_h_, W = lat_w_, vc = cfg_.vae_ch;
     Act z; z.p = const_cast<float*>(z_nhwc); z.n = n; z.h = H; z.w = W; z.c = 4; z.dt = 0;
     Act pq = new_act(n, H, W, 4, /*dt=*/0);  // the two Cin = 4 layers run on the fp32 kernel in both precisions
     conv(post_quant_, z, pq, 1, 0, nullptr, 0, nullptr);
@@ -2365,8 +2474,8 @@ void Engine::encode_image_dev(const float* img_nchw, int n, float* latent_nchw) 
     if (!enc_ready_) throw Error(SDMI_ERR_STATE, "VAE encoder weights are not loaded (autoencoder/encoder/..., autoencoder/quant_conv)");
     if (n <= 0) throw Error(SDMI_ERR_INVALID, "encode_image: n must be positive");
     check_batch(n);
-    const int H = 8 * cfg_.latent_h, W = 8 * cfg_.latent_w;
-    const size_t img_elems = (size_t)3 * H * W, lat_elems = (size_t)4 * cfg_.latent_h * cfg_.latent_w;
+    const int H = 8 * lat_h_, W = 8 * lat_w_;
+    const size_t img_elems = (size_t)3 * H * W, lat_elems = (size_t)4 * lat_h_ * lat_w_;
     for (int i = 0; i < n; ++i) {
         Act rgb = new_act(1, H, W, 4, /*dt=*/0);
         { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nchw3_to_nhwc4(img_nchw + i * img_elems, rgb.p, 1, H, W, stream_)); }
@@ -2422,7 +2531,7 @@ void Engine::decode_latent_dev(const float* latent_nchw, int n, float in_scale, 
     if (!finalized_) throw Error(SDMI_ERR_STATE, "weights not finalized");
     if (n <= 0) throw Error(SDMI_ERR_INVALID, "decode: n must be positive");
     check_batch(n);
-    const int H = cfg_.latent_h, W = cfg_.latent_w;
+    const int H = lat_h_, W = lat_w_;
     const size_t lat_elems = (size_t)4 * H * W, img_elems = (size_t)3 * 64 * H * W;
     for (int i = 0; i < n; ++i) {  // one image at a time: peak activations are ~1 GB per image at 512x512
         Buf z(this, lat_elems * 4);

@@ -163,7 +163,7 @@ public:
     // Autoencoder::encode_image (autoencoder/mod.rs:60-66): img [n,3,8h,8w] NCHW -> latent mean [n,4,h,w] NCHW (device pointers)
     void encode_image_dev(const float* img_nchw, int n, float* latent_nchw);
     void sample_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale,
-                           size_t n_steps, const float* init_latent, float* latent_out);
+                           size_t n_steps, const float* init_latent, float* latent_out, bool out_nhwc = false);   // out_nhwc: see sample_loop
     // img2img (DESIGN.md section "img2img"): the last k of sample_latent's timesteps (sdmi_img2img_timesteps), started from
     // z0 re-noised to t0 with eps = noise [n,4,h,w] or, when null, image i's N(0,1) stream seed + i; mask [n,1,h,w] or null.
     // _latent: z0 [n,4,h,w] NCHW; _image: z0 = 0.18215 * encode_image(rgb / 127.5 - 1), rgb = n x [8h,8w,3] u8 (needs the
@@ -172,6 +172,15 @@ public:
                             double strength, const float* z0, const float* mask, const float* noise, uint64_t seed, float* latent_out);
     void img2img_image_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps,
                            double strength, const uint8_t* init_rgb, const float* mask, const float* noise, uint64_t seed, float* latent_out);
+    // Hires fix (include/sdmi.h "hires fix"): sample_latent at hr.base_h x base_w, the NHWC latent resampled on the device to the
+    // current size, img2img_latent_dev from it (no mask).  init_latent [n,4,base_h,base_w], hires_noise [n,4,H,W] or null, latent_out [n,4,H,W]: device pointers.
+    // The size is switched for the first pass and restored on every way out.
+    void hires_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps, const float* init_latent,
+                          const sdmi_hires& hr, const float* hires_noise, float* latent_out);
+    static void check_hires(const sdmi_hires* hr);   // the argument errors of sdmi_hires_* that need no context
+    // x [n][h*w][4] -> y [n][oh*ow][4] (NHWC4, device) by the tables of sdmi_resize_weights: horizontal pass, then vertical; an unchanged axis is skipped
+    void resize_nhwc4(const float* x, int n, int h, int w, int oh, int ow, int mode, int antialias, float* y);
+    void op_resize(const float* x_nchw, int n, int h, int w, int oh, int ow, int mode, int antialias, float* out_nchw);
     // sampler choice (sdmi_set_sampler): sticky, read by sample_loop -- every sampling entry point.  The default (kind 0,
     // eta 0) is the reference's DDIM on its own launches.  check_sampler throws SDMI_ERR_INVALID for what the header lists; null = the default.
     static void check_sampler(const sdmi_sampler& s);
@@ -244,8 +253,12 @@ public:
     hipStream_t stream() const { return stream_; }
     DevPool& pool() { return pool_; }
     const sdmi_config& config() const { return cfg_; }
-    int latent_h() const { return cfg_.latent_h; }
-    int latent_w() const { return cfg_.latent_w; }
+    // The CURRENT latent size (sdmi_set_latent_size): cfg_.latent_h / latent_w are its initial value.  Every entry point reads it
+    // at call time and nothing is cached per size.  check_latent_size: sdmi_create's rule (positive multiples of 8), SDMI_ERR_INVALID otherwise.
+    int latent_h() const { return lat_h_; }
+    int latent_w() const { return lat_w_; }
+    static void check_latent_size(int h, int w);
+    void set_latent_size(int h, int w) { check_latent_size(h, w); lat_h_ = h; lat_w_ = w; }
 
     // RAII helper for pool scratch
     struct Buf {
@@ -386,10 +399,11 @@ private:
     // [n][hw][4] and both halves of unet_in [2n][hw][4] (per_half floats each).  blend (img2img with a mask): after each update
     // x <- m x + (1 - m)(sqrt(a_prev) z0 + sqrt(1 - a_prev) eps), device pointers, z0 / eps NHWC.  With a non-default sampler_ the update of every step is
     // launch_sampler_step on the coefficient table of sdmi_sampler_coefs instead (one launch per step either way), its history in pool buffers of the call.
+    // out_nhwc (the first pass of the hires fix): latent_out receives the NHWC latent itself (a device copy) instead of the NCHW conversion launch.
     struct Blend { const float* mask; const float* z0; const float* eps; };
     void sample_loop(const float* context, int n, int T, const float* uncond, int Tu, double scale, const std::vector<int>& ts,
                      size_t step_size, const std::function<void(float* latent, float* unet_in, long long per_half)>& start,
-                     const Blend* blend, float* latent_out);
+                     const Blend* blend, float* latent_out, bool out_nhwc = false);
     // argument checks of both img2img entry points; returns the timesteps (rule 1) and the schedule's step size
     std::vector<int> img2img_schedule(int n, int T, int Tu, size_t n_steps, double strength, size_t* step_size);
 
@@ -444,6 +458,7 @@ private:
     std::vector<ProfPending> prof_pending_;
 
     sdmi_config cfg_;
+    int lat_h_ = 0, lat_w_ = 0;   // current latent size
     bool bf16_ = false;  // precision >= 1: bf16 activations / weights, fp32 accumulate
     bool fp8_ = false;   // precision = 2: additionally the ResBlock / ResnetBlock 3x3 convs in MXFP8 (k_fp8.hip)
     int opt_fp8_convs_ = 1;          // 0: run the fp8-capable convs on the bf16 kernels (A/B, accuracy comparison)
@@ -546,6 +561,11 @@ private:
     long long n_kernels_ = 0;
     double flops_ = 0;
 };
+
+// One output index of a resampling axis (include/sdmi.h, sdmi_resize_weights): y[o] = sum_j w[j] x[first + j].  resize_rows is THE implementation of the rule
+// (sdmi_capi.cpp); throws SDMI_ERR_INVALID for what sdmi_resize_weights refuses.
+struct ResizeRow { int first = 0; std::vector<double> w; };
+std::vector<ResizeRow> resize_rows(int in_size, int out_size, int mode, bool antialias);
 
 void set_last_error(const std::string& msg);   // the thread-local message behind sdmi_last_error() (sdmi_capi.cpp)
 

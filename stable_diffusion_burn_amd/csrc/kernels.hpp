@@ -228,6 +228,15 @@ hipError_t launch_img2img_start(const float* z_src, bool from_q8, const float* n
 hipError_t launch_cfg_ddim_masked(const float* eps, float* latent, float* unet_in, long long per_half, DdimCoef c, const float* mask,
                                   const float* z0, const float* e0, hipStream_t s);
 
+// ---- latent resampler of the hires fix (k_resize.hip) -----------------------------------
+// One axis of a separable resample over NHWC4 latents (one f32x4 per pixel): x [outer][in_size][inner] -> y [outer][out_size][inner] pixels,
+//     y[a][o][i] = sum_{j < count[o]} taps[o * max_taps + j] * x[a][first[o] + j][i]      (ascending j, fp32)
+// inner = 1, outer = n * h: the horizontal pass; inner = the row length, outer = n: the vertical one.  first / count / taps: DEVICE arrays holding the table
+// of sdmi_resize_weights (taps as f32); the caller guarantees 0 <= first[o] and first[o] + count[o] <= in_size.  gather: every row is the single tap 1.0
+// (nearest): the pixel is copied, not multiplied.
+hipError_t launch_resize_axis(const float* x, float* y, const int* first, const int* count, const float* taps, int max_taps, long long outer,
+                              int in_size, int out_size, long long inner, bool gather, hipStream_t s);
+
 // ---- sampler choice (k_sampler.hip) ---------------------------------------------------
 // One step of DDIM(eta) / DPM-Solver++(2M) / PLMS in the linear form sdmi_sampler_coefs returns (f64 on the host, applied as f32):
 //   e = eu + (ec - eu) scale;  q = qx x + qe e;  x' = cx x + ce e + h[0] q_-1 + h[1] q_-2 + h[2] q_-3 + cz z

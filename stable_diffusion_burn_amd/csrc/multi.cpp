@@ -112,6 +112,8 @@ public:
         if (T <= 0 || Tu <= 0 || n_images <= 0) throw Error(SDMI_ERR_INVALID, "sample_image_sharded: T, Tu and n_images must be positive");
         const int R = size();
         const int cd = engine(0).config().ctx_dim, H = engine(0).latent_h(), W = engine(0).latent_w();
+        for (int r = 1; r < R; ++r)   // sdmi_set_latent_size is per device context
+            if (engine(r).latent_h() != H || engine(r).latent_w() != W) throw Error(SDMI_ERR_STATE, "sample_image_sharded: the device contexts disagree on the latent size");
         const size_t n_cond = (size_t)T * cd, n_unc = (size_t)Tu * cd, n_prompt = n_cond + n_unc;
         const size_t lat_elems = (size_t)4 * H * W, img_bytes = (size_t)3 * 64 * H * W;
 

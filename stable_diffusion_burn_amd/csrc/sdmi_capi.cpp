@@ -2,7 +2,9 @@
 // Translates C arguments to Engine calls, C++ exceptions to sdmi_status codes,
 // and stages host buffers through the device pool for the host-pointer API.
 #include <algorithm>
+#include <climits>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -337,8 +339,8 @@ int sdmi_write_png(const char* path, const uint8_t* rgb, int32_t width, int32_t 
     });
 }
 
-static void make_init_latent(Engine& e, const float* init_latent, uint64_t seed, int n, Engine::Buf& dst) {
-    const size_t per = (size_t)4 * e.latent_h() * e.latent_w();
+static void make_init_latent(Engine& e, const float* init_latent, uint64_t seed, int n, int h, int w, Engine::Buf& dst) {
+    const size_t per = (size_t)4 * h * w;
     if (init_latent) {
         SDMI_HIP(hipMemcpyAsync(dst.p, init_latent, n * per * sizeof(float), hipMemcpyHostToDevice, e.stream()));
     } else {
@@ -356,7 +358,7 @@ int sdmi_sample_latent(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T
         Engine::Call call(e);
         DevIn dc(e, context, (size_t)n * T * cd * sizeof(float)), du(e, uncond, (size_t)Tu * cd * sizeof(float));
         Engine::Buf x0(&e, lat);
-        make_init_latent(e, init_latent, seed, n, x0);
+        make_init_latent(e, init_latent, seed, n, e.latent_h(), e.latent_w(), x0);
         DevOut dout(e, latent_out, lat);
         e.sample_latent_dev(dc.f(), n, T, du.f(), Tu, scale, n_steps, x0.f(), dout.f());
         call.finish();
@@ -389,6 +391,225 @@ int sdmi_get_sampler(sdmi_ctx* ctx, sdmi_sampler* out) {
     return guarded([&] {
         if (!out) throw Error(SDMI_ERR_INVALID, "get_sampler: null output");
         *out = eng(ctx).sampler();
+    });
+}
+
+// optional host input (mask, noise): staged when given
+static std::unique_ptr<DevIn> dev_in_opt(Engine& e, const void* host, size_t bytes) {
+    return host ? std::unique_ptr<DevIn>(new DevIn(e, host, bytes)) : nullptr;
+}
+
+// ---- latent size, resampling rule, hires fix ---------------------------------------------------------------
+int sdmi_set_latent_size(sdmi_ctx* ctx, int32_t h, int32_t w) {
+    return guarded([&] { eng(ctx).set_latent_size(h, w); });
+}
+
+int sdmi_get_latent_size(sdmi_ctx* ctx, int32_t* h, int32_t* w) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (!h || !w) throw Error(SDMI_ERR_INVALID, "get_latent_size: null output");
+        *h = e.latent_h();
+        *w = e.latent_w();
+    });
+}
+
+extern "C++" {
+namespace {
+// torch's cubic convolution pieces (ATen/native/UpSample.h): |x| <= 1 and 1 < |x| < 2
+double cubic_near(double x, double A) { return ((A + 2.0) * x - (A + 3.0)) * x * x + 1.0; }
+double cubic_far(double x, double A) { return ((A * x - 5.0 * A) * x + 8.0 * A) * x - 4.0 * A; }
+using TapRow = sdmi::ResizeRow;
+// adds weight `wt` at input index `idx` clamped to [0, in): a clamped tap lands on the border index
+void fold_tap(TapRow& r, int idx, int in, double wt) {
+    idx = std::min(std::max(idx, 0), in - 1);
+    if (r.w.empty()) r.first = idx;
+    const int j = idx - r.first;       // indices arrive in ascending order
+    if (j >= (int)r.w.size()) r.w.resize((size_t)j + 1, 0.0);
+    r.w[(size_t)j] += wt;
+}
+// One output row of torch.nn.functional.interpolate's CPU kernels in float64 (align_corners = False); every rounding step that decides an index is theirs:
+// the source index passes through float before floorf (UpSampleKernel.cpp, guard_index_and_lambda), the weights stay in double.
+TapRow resize_row(int in, int out, int mode, bool aa, int o) {
+    TapRow r;
+    if (in == out) { r.first = o; r.w.assign(1, 1.0); return r; }
+    const double scale = (double)in / (double)out;
+    if (mode == 0) {
+        // nearest-exact.  torch has TWO rules that differ where scale (o + 0.5) is an integer in exact arithmetic, and picks by the OUTPUT size of the whole call
+        // (UpSampleKernel.cpp, _use_vectorized_kernel_cond_2d: out_h + out_w <= 128).  A table of one axis cannot see the other one: it follows the call on a
+        // one-axis tensor [1,1,1,in] -> (1, out), i.e. the switch at out + 1 <= 128.
+        int idx;
+        if (out + 1 <= 128) {      // nearest_exact_idx: scale = in / out held in float, floorf((o + 0.5) * scale)
+            const float fscale = (float)in / (float)out;
+            idx = (int)std::floor((float)(((double)o + 0.5) * (double)fscale));
+        } else {                   // the generic kernel: scale in double, floorf(scale (o + 0.5) - 0.5 + 0.5)
+            idx = (int)std::floor((float)(scale * ((double)o + 0.5) - 0.5 + 0.5));
+        }
+        r.first = std::min(std::max(idx, 0), in - 1);
+        r.w.assign(1, 1.0);
+        return r;
+    }
+    if (!aa) {
+        double real = scale * ((double)o + 0.5) - 0.5;
+        if (mode == 1 && real < 0.0) real = 0.0;         // the linear kernel clamps the source index at 0; the cubic one does not
+        const int i0 = std::min((int)std::floor((float)real), in - 1);
+        const double t = std::min(std::max(real - (double)i0, 0.0), 1.0);
+        if (mode == 1) {
+            fold_tap(r, i0, in, 1.0 - t);
+            fold_tap(r, i0 + 1, in, t);
+        } else {
+            const double A = -0.75;
+            fold_tap(r, i0 - 1, in, cubic_far(t + 1.0, A));
+            fold_tap(r, i0, in, cubic_near(t, A));
+            fold_tap(r, i0 + 1, in, cubic_near(1.0 - t, A));
+            fold_tap(r, i0 + 2, in, cubic_far(2.0 - t, A));
+        }
+        return r;
+    }
+    // antialiased (_compute_indices_min_size_weights_aa): the filter is stretched by the scale when shrinking and the row is normalised
+    const double half = mode == 1 ? 1.0 : 2.0;
+    const double support = scale >= 1.0 ? half * scale : half;
+    const int max_size = (int)std::ceil(support) * 2 + 1;
+    const double center = scale * ((double)o + 0.5), inv = scale >= 1.0 ? 1.0 / scale : 1.0;
+    const long long xmin = std::max((long long)(center - support + 0.5), 0LL);
+    long long xsize = std::min((long long)(center + support + 0.5), (long long)in) - xmin;
+    xsize = std::min(std::max(xsize, 0LL), (long long)max_size);
+    if (xsize < 1) throw Error(SDMI_ERR_STATE, "resize_weights: empty filter window");
+    r.first = (int)xmin;
+    r.w.resize((size_t)xsize);
+    double total = 0.0;
+    for (long long j = 0; j < xsize; ++j) {
+        const double x = std::fabs(((double)(j + xmin) - center + 0.5) * inv);
+        double wt;
+        if (mode == 1) wt = x < 1.0 ? 1.0 - x : 0.0;
+        else wt = x < 1.0 ? cubic_near(x, -0.5) : x < 2.0 ? cubic_far(x, -0.5) : 0.0;
+        r.w[(size_t)j] = wt;
+        total += wt;
+    }
+    if (total != 0.0) for (double& wt : r.w) wt /= total;
+    return r;
+}
+}  // namespace
+
+// the rows of one axis, each computed once: shared by sdmi_resize_weights and the engine (Engine::resize_nhwc4)
+std::vector<sdmi::ResizeRow> sdmi::resize_rows(int in_size, int out_size, int mode, bool antialias) {
+    if (in_size < 1 || out_size < 1) throw Error(SDMI_ERR_INVALID, "resize_weights: sizes must be positive");
+    if (mode < 0 || mode > 2) throw Error(SDMI_ERR_INVALID, "resize_weights: mode must be 0 (nearest-exact), 1 (bilinear) or 2 (bicubic)");
+    if (mode == 0 && antialias) throw Error(SDMI_ERR_INVALID, "resize_weights: antialias belongs to modes 1 and 2");
+    std::vector<ResizeRow> rows((size_t)out_size);
+    for (int o = 0; o < out_size; ++o) rows[(size_t)o] = resize_row(in_size, out_size, mode, antialias, o);
+    return rows;
+}
+}  // extern "C++"
+
+int sdmi_resize_weights(int32_t in_size, int32_t out_size, int32_t mode, int32_t antialias, int32_t* first, int32_t* count, double* taps,
+                        int32_t capacity, int32_t* max_taps, int32_t* needed) {
+    return guarded([&] {
+        const bool query = !first && !count && !taps;
+        if (!query && (!first || !count || !taps)) throw Error(SDMI_ERR_INVALID, "resize_weights: first, count and taps are given together or not at all");
+        const std::vector<TapRow> rows = sdmi::resize_rows(in_size, out_size, mode, antialias != 0);
+        size_t T = 0;
+        for (const TapRow& r : rows) T = std::max(T, r.w.size());
+        const long long need = (long long)out_size * (long long)T;
+        if (need > INT32_MAX) throw Error(SDMI_ERR_INVALID, "resize_weights: table too large");
+        if (max_taps) *max_taps = (int32_t)T;
+        if (needed) *needed = (int32_t)need;
+        if (query) return;
+        if ((long long)capacity < need) throw Error(SDMI_ERR_INVALID, "resize_weights: capacity too small");
+        for (int o = 0; o < out_size; ++o) {
+            const TapRow& r = rows[(size_t)o];
+            first[o] = r.first;
+            count[o] = (int32_t)r.w.size();
+            for (size_t j = 0; j < T; ++j) taps[(size_t)o * T + j] = j < r.w.size() ? r.w[j] : 0.0;
+        }
+    });
+}
+
+// the argument checks the hires entry points share; returns the byte sizes of the base (optional) and the final latent batch
+static void hires_sizes(Engine& e, int n, int T, int Tu, const sdmi_hires* hr, size_t* base_bytes, size_t* final_bytes) {
+    if (n <= 0 || T <= 0 || Tu <= 0) throw Error(SDMI_ERR_INVALID, "hires: n, T, Tu must be positive");
+    Engine::check_hires(hr);
+    if (base_bytes) *base_bytes = (size_t)n * 4 * hr->base_h * hr->base_w * sizeof(float);
+    *final_bytes = (size_t)n * 4 * e.latent_h() * e.latent_w() * sizeof(float);
+}
+
+int sdmi_hires_latent_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps,
+                          const float* init_latent, const sdmi_hires* hires, const float* hires_noise, float* latent_out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (!context || !uncond || !init_latent || !latent_out) throw Error(SDMI_ERR_INVALID, "hires_latent_dev: null pointer");
+        Engine::check_hires(hires);
+        Engine::Call call(e, /*dev_inputs=*/true);
+        e.hires_latent_dev(context, n, T, uncond, Tu, scale, n_steps, init_latent, *hires, hires_noise, latent_out);
+        call.finish();
+    });
+}
+
+int sdmi_hires_image_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps,
+                         const float* init_latent, const sdmi_hires* hires, const float* hires_noise, uint8_t* rgb_out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (!context || !uncond || !init_latent || !rgb_out) throw Error(SDMI_ERR_INVALID, "hires_image_dev: null pointer");
+        size_t lat = 0;
+        hires_sizes(e, n, T, Tu, hires, nullptr, &lat);
+        Engine::Call call(e, /*dev_inputs=*/true);
+        Engine::Buf xl(&e, lat);
+        e.hires_latent_dev(context, n, T, uncond, Tu, scale, n_steps, init_latent, *hires, hires_noise, xl.f());
+        e.decode_latent_dev(xl.f(), n, (float)(1.0 / 0.18215), nullptr, rgb_out);
+        call.finish();
+    });
+}
+
+int sdmi_hires_latent(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps,
+                      const float* init_latent, uint64_t seed, const sdmi_hires* hires, const float* hires_noise, float* latent_out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        size_t base = 0, lat = 0;
+        hires_sizes(e, n, T, Tu, hires, &base, &lat);
+        const int cd = e.config().ctx_dim;
+        Engine::Call call(e);
+        DevIn dc(e, context, (size_t)n * T * cd * sizeof(float)), du(e, uncond, (size_t)Tu * cd * sizeof(float));
+        Engine::Buf x0(&e, base);
+        make_init_latent(e, init_latent, seed, n, hires->base_h, hires->base_w, x0);
+        auto dn = dev_in_opt(e, hires_noise, lat);
+        DevOut dout(e, latent_out, lat);
+        e.hires_latent_dev(dc.f(), n, T, du.f(), Tu, scale, n_steps, x0.f(), *hires, dn ? dn->f() : nullptr, dout.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
+int sdmi_hires_image(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps,
+                     const float* init_latent, uint64_t seed, const sdmi_hires* hires, const float* hires_noise, uint8_t* rgb_out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        size_t base = 0, lat = 0;
+        hires_sizes(e, n, T, Tu, hires, &base, &lat);
+        const int cd = e.config().ctx_dim;
+        const size_t hw = (size_t)e.latent_h() * e.latent_w();
+        Engine::Call call(e);
+        DevIn dc(e, context, (size_t)n * T * cd * sizeof(float)), du(e, uncond, (size_t)Tu * cd * sizeof(float));
+        Engine::Buf x0(&e, base), xl(&e, lat);
+        make_init_latent(e, init_latent, seed, n, hires->base_h, hires->base_w, x0);
+        auto dn = dev_in_opt(e, hires_noise, lat);
+        DevOut dout(e, rgb_out, (size_t)n * 3 * 64 * hw);
+        e.hires_latent_dev(dc.f(), n, T, du.f(), Tu, scale, n_steps, x0.f(), *hires, dn ? dn->f() : nullptr, xl.f());
+        e.decode_latent_dev(xl.f(), n, (float)(1.0 / 0.18215), nullptr, reinterpret_cast<uint8_t*>(dout.buf.p));
+        call.finish();
+        dout.fetch();
+    });
+}
+
+int sdmi_op_resize(sdmi_ctx* ctx, const float* x, int32_t n, int32_t h, int32_t w, int32_t out_h, int32_t out_w, int32_t mode, int32_t antialias,
+                   float* out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (n <= 0 || h <= 0 || w <= 0 || out_h <= 0 || out_w <= 0) throw Error(SDMI_ERR_INVALID, "resize: sizes must be positive");
+        Engine::Call call(e);
+        DevIn dx(e, x, (size_t)n * 4 * h * w * sizeof(float));
+        DevOut dout(e, out, (size_t)n * 4 * out_h * out_w * sizeof(float));
+        e.op_resize(dx.f(), n, h, w, out_h, out_w, mode, antialias, dout.f());
+        call.finish();
+        dout.fetch();
     });
 }
 
@@ -482,11 +703,6 @@ int sdmi_sampler_coefs(const sdmi_sampler* sampler, const float* alphas_cumprod,
     });
 }
 
-// optional host input (mask, noise): staged when given
-static std::unique_ptr<DevIn> dev_in_opt(Engine& e, const void* host, size_t bytes) {
-    return host ? std::unique_ptr<DevIn>(new DevIn(e, host, bytes)) : nullptr;
-}
-
 int sdmi_img2img_latent(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale,
                         size_t n_steps, double strength, const float* z0, const float* mask, const float* noise, uint64_t seed,
                         float* latent_out) {
@@ -569,7 +785,7 @@ int sdmi_sample_image(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T,
         Engine::Call call(e);
         DevIn dc(e, context, (size_t)n * T * cd * sizeof(float)), du(e, uncond, (size_t)Tu * cd * sizeof(float));
         Engine::Buf x0(&e, lat), xl(&e, lat);
-        make_init_latent(e, init_latent, seed, n, x0);
+        make_init_latent(e, init_latent, seed, n, e.latent_h(), e.latent_w(), x0);
         DevOut dout(e, rgb_out, (size_t)n * 3 * 64 * hw);
         e.sample_latent_dev(dc.f(), n, T, du.f(), Tu, scale, n_steps, x0.f(), xl.f());
         e.decode_latent_dev(xl.f(), n, (float)(1.0 / 0.18215), nullptr, reinterpret_cast<uint8_t*>(dout.buf.p));

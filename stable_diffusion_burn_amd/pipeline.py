@@ -23,7 +23,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _capi
-from ._capi import SdmiConfig, SdmiError, SdmiOpView, SdmiSampler, check, load_library
+from ._capi import SdmiConfig, SdmiError, SdmiHires, SdmiOpView, SdmiSampler, check, load_library
 
 def mpk_list(path) -> list:
     """[(dump name, shape, file offset)] of a Burn .mpk record, parsed by the C++ reader (host only, no GPU)."""
@@ -78,6 +78,33 @@ def sampler_coefs(kind: str, eta: float, alphas_cumprod, ts, step_size: int) -> 
     check(lib.sdmi_sampler_coefs(C.byref(s), _fp(a), a.size, t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, int(step_size),
                                  out.ctypes.data_as(C.POINTER(C.c_double))))
     return out
+
+
+RESIZE_MODES = ("nearest", "bilinear", "bicubic")   # sdmi_resize_weights / sdmi_hires.mode 0, 1, 2 ("nearest" = torch's "nearest-exact")
+
+
+def _resize_mode(mode) -> int:
+    if isinstance(mode, str):
+        if mode not in RESIZE_MODES:
+            raise ValueError(f"resize mode must be one of {RESIZE_MODES}, got {mode!r}")
+        return RESIZE_MODES.index(mode)
+    return int(mode)
+
+
+def resize_weights(in_size: int, out_size: int, mode="bicubic", antialias: bool = False):
+    """The resampling table of one axis (sdmi_resize_weights, host only, no GPU): (first [out] int32, count [out] int32, taps [out, max_taps]
+    float64) with y[o] = sum_j taps[o, j] x[first[o] + j], j < count[o] -- torch.nn.functional.interpolate's rule (align_corners=False)."""
+    lib = load_library()
+    m, aa = _resize_mode(mode), 1 if antialias else 0
+    T, need = C.c_int32(), C.c_int32()
+    check(lib.sdmi_resize_weights(int(in_size), int(out_size), m, aa, None, None, None, 0, C.byref(T), C.byref(need)))
+    first = np.empty(int(out_size), dtype=np.int32)
+    count = np.empty(int(out_size), dtype=np.int32)
+    taps = np.empty((int(out_size), T.value), dtype=np.float64)
+    i32 = C.POINTER(C.c_int32)
+    check(lib.sdmi_resize_weights(int(in_size), int(out_size), m, aa, first.ctypes.data_as(i32), count.ctypes.data_as(i32),
+                                  taps.ctypes.data_as(C.POINTER(C.c_double)), need.value, None, None))
+    return first, count, taps
 
 
 def load_lora_npz(path) -> dict:
@@ -216,7 +243,7 @@ class MultiLoraAdapter:
             self._owner = None
 
 
-__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "img2img_timesteps", "sampler_coefs", "load_lora_npz", "save_lora_npz", "LoraAdapter", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
+__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "img2img_timesteps", "sampler_coefs", "resize_weights", "load_lora_npz", "save_lora_npz", "LoraAdapter", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
 
 
 @dataclass(frozen=True)
@@ -383,6 +410,20 @@ class StableDiffusion:
         buffers of the *_dev calls are produced / consumed on (sdmi_set_stream)."""
         check(self._lib.sdmi_set_stream(self._ctx, C.c_void_p(int(hip_stream) if hip_stream else 0), 1 if enable else 0))
 
+    def set_latent_size(self, h: int, w: int) -> None:
+        """The latent size [h, w] of every later call of this context (sdmi_set_latent_size; sticky): positive multiples of 8, pictures are 8x.
+        config.latent_h / latent_w are the initial value; the weights do not depend on the size."""
+        check(self._lib.sdmi_set_latent_size(self._ctx, int(h), int(w)))
+
+    @property
+    def latent_size(self) -> tuple:
+        """the current (h, w) of the context (sdmi_get_latent_size); without a live context, the configured size"""
+        if not self._ctx.value:
+            return self.config.latent_h, self.config.latent_w
+        h, w = C.c_int32(), C.c_int32()
+        check(self._lib.sdmi_get_latent_size(self._ctx, C.byref(h), C.byref(w)))
+        return h.value, w.value
+
     def set_sampler(self, kind="ddim", eta: float = 0.0, noise_seed: int = 0, image_base: int = 0) -> None:
         """Choose the sampler of every later sampling call of this context (sdmi_set_sampler; sticky): "ddim" with 0 <= eta <= 1
         (eta = 0, the default: the reference's deterministic DDIM = plain Euler; eta = 1 = Euler-ancestral), "dpmpp_2m"
@@ -487,7 +528,7 @@ class StableDiffusion:
         is x_T (the reference draws it from an unseeded RNG)."""
         context, uncond = self._check_ctx(context, unconditional_context)
         n, T, _ = context.shape
-        h, w = self.config.latent_h, self.config.latent_w
+        h, w = self.latent_size
         out = np.empty((n, 4, h, w), dtype=np.float32)
         x0 = None if init_latent is None else _f32(init_latent, (n, 4, h, w), "init_latent")
         check(self._lib.sdmi_sample_latent(self._ctx, _fp(context), n, T, _fp(uncond), uncond.shape[0],
@@ -497,7 +538,7 @@ class StableDiffusion:
 
     def latent_to_image(self, latent) -> np.ndarray:
         """stablediffusion/mod.rs:69-100 -> uint8 [n, 8h, 8w, 3] (the reference's Vec<Vec<u8>>)."""
-        h, w = self.config.latent_h, self.config.latent_w
+        h, w = self.latent_size
         latent = _f32(latent, name="latent")
         if latent.ndim != 4 or latent.shape[1:] != (4, h, w):
             raise ValueError(f"latent must be [n,4,{h},{w}], got {latent.shape}")
@@ -511,7 +552,7 @@ class StableDiffusion:
         """stablediffusion/mod.rs:51-67 -> uint8 [n, 8h, 8w, 3]."""
         context, uncond = self._check_ctx(context, unconditional_context)
         n, T, _ = context.shape
-        h, w = self.config.latent_h, self.config.latent_w
+        h, w = self.latent_size
         out = np.empty((n, 8 * h, 8 * w, 3), dtype=np.uint8)
         x0 = None if init_latent is None else _f32(init_latent, (n, 4, h, w), "init_latent")
         check(self._lib.sdmi_sample_image(self._ctx, _fp(context), n, T, _fp(uncond), uncond.shape[0],
@@ -522,7 +563,7 @@ class StableDiffusion:
 
     # ---- img2img (include/sdmi.h "img2img"; DESIGN.md section "img2img") ----------------------
     def _check_img2img(self, n, strength, mask, noise):
-        h, w = self.config.latent_h, self.config.latent_w
+        h, w = self.latent_size
         s = float(strength)
         if not 0.0 < s <= 1.0:   # NaN fails too
             raise ValueError(f"strength must satisfy 0 < strength <= 1, got {strength}")
@@ -544,7 +585,7 @@ class StableDiffusion:
         mask [n,h,w] / [n,1,h,w] (1 = regenerate, 0 = keep); noise [n,4,h,w], or None: image i draws from stream seed + i."""
         context, uncond = self._check_ctx(context, unconditional_context)
         n, T, _ = context.shape
-        h, w = self.config.latent_h, self.config.latent_w
+        h, w = self.latent_size
         z0 = _f32(z0, (n, 4, h, w), "z0")
         s, mask, noise = self._check_img2img(n, strength, mask, noise)
         out = np.empty((n, 4, h, w), dtype=np.float32)
@@ -561,7 +602,7 @@ class StableDiffusion:
         they are not pasted back.  Needs the VAE encoder weights."""
         context, uncond = self._check_ctx(context, unconditional_context)
         n, T, _ = context.shape
-        h, w = self.config.latent_h, self.config.latent_w
+        h, w = self.latent_size
         img = np.asarray(init_image)
         if img.dtype != np.uint8 or img.shape != (n, 8 * h, 8 * w, 3):
             raise ValueError(f"init_image must be uint8 [{n},{8 * h},{8 * w},3], got {img.dtype} {img.shape}")
@@ -579,6 +620,70 @@ class StableDiffusion:
                                            int(n_steps), s, img.ctypes.data_as(C.POINTER(C.c_uint8)), None if mask is None else _fp(mask),
                                            None if noise is None else _fp(noise), int(seed), out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
+
+    # ---- hires fix (include/sdmi.h "hires fix") ------------------------------
+    def _hires_args(self, n, base_size, mode, antialias, hires_steps, strength, hires_seed, init_latent, hires_noise):
+        h, w = self.latent_size
+        hr = self._hires_struct(base_size, mode, antialias, hires_steps, strength, hires_seed)
+        if hr.base_h <= 0 or hr.base_w <= 0 or hr.base_h % 8 or hr.base_w % 8:
+            raise ValueError(f"base_size must be positive multiples of 8, got {base_size}")
+        if not 0.0 < hr.strength <= 1.0:   # NaN fails too
+            raise ValueError(f"strength must satisfy 0 < strength <= 1, got {strength}")
+        x0 = None if init_latent is None else _f32(init_latent, (n, 4, hr.base_h, hr.base_w), "init_latent")
+        noise = None if hires_noise is None else _f32(hires_noise, (n, 4, h, w), "hires_noise")
+        return hr, x0, noise
+
+    def sample_latent_hires(self, context, unconditional_context, unconditional_guidance_scale: float, n_steps: int, base_size, strength: float,
+                            mode="bicubic", antialias: bool = False, hires_steps: int = 0, init_latent=None, seed: int = 0, hires_noise=None,
+                            hires_seed: int = 0) -> np.ndarray:
+        """Hires fix -> latent [n,4,h,w] at the context's current size: sample_latent at base_size = (base_h, base_w) (init_latent
+        [n,4,base_h,base_w], or image i's stream seed + i), the latent resampled on the device (mode "nearest" / "bilinear" / "bicubic", torch's
+        F.interpolate rule), then sample_latent_from over the last int(strength * L) of the hires_steps (0: n_steps) schedule with noise
+        hires_noise [n,4,h,w] or image i's stream hires_seed + i."""
+        context, uncond = self._check_ctx(context, unconditional_context)
+        n, T, _ = context.shape
+        h, w = self.latent_size
+        hr, x0, noise = self._hires_args(n, base_size, mode, antialias, hires_steps, strength, hires_seed, init_latent, hires_noise)
+        out = np.empty((n, 4, h, w), dtype=np.float32)
+        check(self._lib.sdmi_hires_latent(self._ctx, _fp(context), n, T, _fp(uncond), uncond.shape[0], float(unconditional_guidance_scale), int(n_steps),
+                                          None if x0 is None else _fp(x0), int(seed), C.byref(hr), None if noise is None else _fp(noise), _fp(out)))
+        return out
+
+    def sample_image_hires(self, context, unconditional_context, unconditional_guidance_scale: float, n_steps: int, base_size, strength: float,
+                           mode="bicubic", antialias: bool = False, hires_steps: int = 0, init_latent=None, seed: int = 0, hires_noise=None,
+                           hires_seed: int = 0) -> np.ndarray:
+        """latent_to_image of sample_latent_hires -> uint8 [n, 8h, 8w, 3]."""
+        context, uncond = self._check_ctx(context, unconditional_context)
+        n, T, _ = context.shape
+        h, w = self.latent_size
+        hr, x0, noise = self._hires_args(n, base_size, mode, antialias, hires_steps, strength, hires_seed, init_latent, hires_noise)
+        out = np.empty((n, 8 * h, 8 * w, 3), dtype=np.uint8)
+        check(self._lib.sdmi_hires_image(self._ctx, _fp(context), n, T, _fp(uncond), uncond.shape[0], float(unconditional_guidance_scale), int(n_steps),
+                                         None if x0 is None else _fp(x0), int(seed), C.byref(hr), None if noise is None else _fp(noise),
+                                         out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    @staticmethod
+    def _hires_struct(base_size, mode, antialias, hires_steps, strength, hires_seed) -> SdmiHires:
+        hr = SdmiHires()
+        hr.base_h, hr.base_w = int(base_size[0]), int(base_size[1])
+        hr.mode = _resize_mode(mode)
+        hr.antialias, hr.hires_steps, hr.strength, hr.hires_seed = (1 if antialias else 0), int(hires_steps or 0), float(strength), int(hires_seed)
+        return hr
+
+    def sample_latent_hires_dev(self, context_ptr: int, n: int, T: int, uncond_ptr: int, Tu: int, scale: float, n_steps: int, base_size,
+                                strength: float, init_latent_ptr: int, hires_noise_ptr, latent_out_ptr: int, mode="bicubic", antialias: bool = False,
+                                hires_steps: int = 0, hires_seed: int = 0) -> None:
+        hr = self._hires_struct(base_size, mode, antialias, hires_steps, strength, hires_seed)
+        check(self._lib.sdmi_hires_latent_dev(self._ctx, context_ptr, n, T, uncond_ptr, Tu, float(scale), int(n_steps), init_latent_ptr, C.byref(hr),
+                                              hires_noise_ptr, latent_out_ptr))
+
+    def sample_image_hires_dev(self, context_ptr: int, n: int, T: int, uncond_ptr: int, Tu: int, scale: float, n_steps: int, base_size,
+                               strength: float, init_latent_ptr: int, hires_noise_ptr, rgb_out_ptr: int, mode="bicubic", antialias: bool = False,
+                               hires_steps: int = 0, hires_seed: int = 0) -> None:
+        hr = self._hires_struct(base_size, mode, antialias, hires_steps, strength, hires_seed)
+        check(self._lib.sdmi_hires_image_dev(self._ctx, context_ptr, n, T, uncond_ptr, Tu, float(scale), int(n_steps), init_latent_ptr, C.byref(hr),
+                                             hires_noise_ptr, rgb_out_ptr))
 
     def sample_latent_from_dev(self, context_ptr: int, n: int, T: int, uncond_ptr: int, Tu: int, scale: float, n_steps: int,
                                strength: float, z0_ptr: int, mask_ptr, noise_ptr, seed: int, latent_out_ptr: int) -> None:
@@ -650,6 +755,20 @@ class StableDiffusion:
         return ms.value
 
     # ---- operator-level entry points (parity tests) ----------------------------------------
+    def op_resize(self, x, out_size, mode="bicubic", antialias: bool = False):
+        """The resampler of the hires fix on its own (sdmi_op_resize): x [n,4,h,w] -> [n,4,out_h,out_w]."""
+        x = _f32(x)
+        if x.ndim != 4 or x.shape[1] != 4:
+            raise ValueError(f"op_resize: x must be [n,4,h,w], got {x.shape}")
+        n, _, h, w = x.shape
+        oh, ow = (int(v) for v in out_size)
+        if oh <= 0 or ow <= 0:
+            raise ValueError(f"op_resize: out_size must be positive, got {out_size}")
+        m = _resize_mode(mode)
+        out = np.empty((n, 4, oh, ow), dtype=np.float32)
+        check(self._lib.sdmi_op_resize(self._ctx, _fp(x), n, h, w, oh, ow, m, 1 if antialias else 0, _fp(out)))
+        return out
+
     def op_group_norm(self, x, gamma, beta, n_group=32, eps=1e-5, silu=False):
         x = _f32(x)
         n, c, h, w = x.shape
@@ -942,7 +1061,8 @@ class MultiStableDiffusion:
 
     def sample_image(self, context, unconditional_context, unconditional_guidance_scale: float, n_steps: int, n_images: int,
                      init_latents=None, seed: int = 0) -> np.ndarray:
-        cd, h, w = self.config.ctx_dim, self.config.latent_h, self.config.latent_w
+        cd = self.config.ctx_dim
+        h, w = self.latent_size
         context = _f32(context, name="context")
         if context.ndim == 3 and context.shape[0] == 1:
             context = context[0]
@@ -967,6 +1087,23 @@ class MultiStableDiffusion:
             return
         s = _sampler_struct(kind, eta, noise_seed, 0)
         check(self._lib.sdmi_multi_set_sampler(self._m, C.byref(s)))
+
+    def set_latent_size(self, h: int, w: int) -> None:
+        """StableDiffusion.set_latent_size on every device context; if one refuses, every context keeps the size it had."""
+        views = [self.device_view(i) for i in range(len(self.devices))]
+        before = [v.latent_size for v in views]
+        try:
+            for v in views:
+                v.set_latent_size(h, w)
+        except Exception:
+            for v, size in zip(views, before):
+                v.set_latent_size(*size)
+            raise
+
+    @property
+    def latent_size(self) -> tuple:
+        """the current (h, w) of the first device context (sample_image refuses contexts that disagree)"""
+        return self.device_view(0).latent_size
 
     def lora_attach(self, tensors, scale: float = 1.0) -> MultiLoraAdapter:
         """StableDiffusion.lora_attach on every device (adapters are per device context; each needs keep_masters before its weights are loaded)."""
@@ -993,7 +1130,7 @@ class UNet:
 
     def forward(self, x, timesteps, context) -> np.ndarray:
         sd = self._sd
-        h, w = sd.config.latent_h, sd.config.latent_w
+        h, w = sd.latent_size
         x = _f32(x, name="x")
         if x.ndim != 4 or x.shape[1:] != (4, h, w):
             raise ValueError(f"x must be [n,4,{h},{w}], got {x.shape}")
@@ -1077,7 +1214,7 @@ class Autoencoder:
     def encode_image(self, x) -> np.ndarray:
         """autoencoder/mod.rs:60-66: image [n,3,8h,8w] -> latent [n,4,h,w] (first 4 quant_conv channels)."""
         sd = self._sd
-        h, w = sd.config.latent_h, sd.config.latent_w
+        h, w = sd.latent_size
         x = _f32(x, name="x")
         if x.ndim != 4 or x.shape[1:] != (3, 8 * h, 8 * w):
             raise ValueError(f"x must be [n,3,{8 * h},{8 * w}], got {x.shape}")
@@ -1091,7 +1228,7 @@ class Autoencoder:
 
     def decode_latent(self, latent) -> np.ndarray:
         sd = self._sd
-        h, w = sd.config.latent_h, sd.config.latent_w
+        h, w = sd.latent_size
         latent = _f32(latent, name="latent")
         if latent.ndim != 4 or latent.shape[1:] != (4, h, w):
             raise ValueError(f"latent must be [n,4,{h},{w}], got {latent.shape}")
