@@ -39,6 +39,11 @@ void* DevPool::alloc(size_t bytes) {
                     live_[p] = Live{(int)si, bytes, ++serial_};
                     in_use_ += bytes;
                     high_ = std::max(high_, in_use_);
+                    if (fill_ >= 0) {
+                        hipError_t e = hipMemsetAsync(p, fill_, bytes, stream_);
+                        if (e != hipSuccess) { free(p); throw Error(SDMI_ERR_HIP, std::string("DevPool: hipMemsetAsync failed: ") + hipGetErrorString(e)); }
+                        note_fill(bytes);
+                    }
                     return p;
                 }
             }
@@ -232,6 +237,7 @@ Engine::Engine(const sdmi_config& cfg) : cfg_(cfg) {
         throw Error(SDMI_ERR_UNSUPPORTED, std::string("libsdmi is built for gfx950 (MI355X) only; device is ") + prop.gcnArchName);
     try {
     SDMI_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    pool_.set_stream(stream_);
     SDMI_HIP(hipEventCreate(&ev0_));
     SDMI_HIP(hipEventCreate(&ev1_));
     SDMI_HIP(hipEventCreateWithFlags(&ev_user_, hipEventDisableTiming));
@@ -369,13 +375,11 @@ void Engine::build_model() {
         if (c == cctx) {
             // self-attention: query/key/value weights are packed into ONE [3c][c] buffer so the three
             // projections of unet/mod.rs:645-647 run as a single GEMM with N = 3c
-            void* p = nullptr;
-            SDMI_HIP(hipMalloc(&p, (size_t)3 * c * c * esz()));
+            void* p = persistent_alloc((size_t)3 * c * c * esz());
             weight_allocs_.push_back(p);
             m.q.bt = reinterpret_cast<float*>(p);
             if (!bf16_) {   // and its bf16 planes (k_gemm3x.hip), same 1.5x offset rule as the arenas
-                void* pl = nullptr;
-                SDMI_HIP(hipMalloc(&pl, (size_t)3 * c * c * 6));
+                void* pl = persistent_alloc((size_t)3 * c * c * 6);
                 weight_allocs_.push_back(pl);
                 split_regions_.push_back(SplitRegion{reinterpret_cast<char*>(p), (size_t)3 * c * c * 4, reinterpret_cast<char*>(pl)});
             }
@@ -383,10 +387,9 @@ void Engine::build_model() {
             m.v.bt = adv(m.q.bt, (long long)2 * c * c, edt());
             if (fp8_ && c % 32 == 0) {   // the packed [3c][Kp] MXFP8 copy + its scales: one N = 3c GEMM as well
                 const size_t kp = (size_t)(c + 127) / 128 * 128;
-                void *q8 = nullptr, *s8 = nullptr;
-                SDMI_HIP(hipMalloc(&q8, (size_t)3 * c * kp));
+                void* q8 = persistent_alloc((size_t)3 * c * kp);
                 weight_allocs_.push_back(q8);
-                SDMI_HIP(hipMalloc(&s8, (size_t)3 * c * kp / 32));
+                void* s8 = persistent_alloc((size_t)3 * c * kp / 32);
                 weight_allocs_.push_back(s8);
                 m.q.bt8 = reinterpret_cast<float*>(q8);
                 m.k.bt8 = reinterpret_cast<float*>((char*)q8 + (size_t)c * kp);
@@ -517,11 +520,9 @@ void Engine::build_model() {
         for (int i = 0; i < L; ++i) {
             ClipBlockW& b = clip_blocks_[i];
             const std::string bp = "clip/blocks/" + std::to_string(i);
-            void* w = nullptr;
-            void* bias = nullptr;
-            SDMI_HIP(hipMalloc(&w, (size_t)3 * cs * cs * sizeof(float)));
+            void* w = persistent_alloc((size_t)3 * cs * cs * sizeof(float));
             weight_allocs_.push_back(w);
-            SDMI_HIP(hipMalloc(&bias, (size_t)3 * cs * sizeof(float)));
+            void* bias = persistent_alloc((size_t)3 * cs * sizeof(float));
             weight_allocs_.push_back(bias);
             b.q.bt = reinterpret_cast<float*>(w); b.k.bt = b.q.bt + (size_t)cs * cs; b.v.bt = b.q.bt + (size_t)2 * cs * cs;
             b.q.bias = reinterpret_cast<float*>(bias); b.k.bias = b.q.bias + cs; b.v.bias = b.q.bias + 2 * cs;
@@ -622,6 +623,19 @@ char* Engine::stage_reserve(size_t bytes, size_t* offset, int* half) {
     return st.pinned[st.cur] + *offset;
 }
 
+void* Engine::persistent_alloc(size_t bytes, bool weight_buffer) {
+    void* p = nullptr;
+    SDMI_HIP(hipMalloc(&p, bytes));
+    if (pool_.fill() >= 0) {
+        hipError_t e = hipMemsetAsync(p, pool_.fill(), bytes, stream_);
+        if (e == hipSuccess && !weight_buffer) e = hipStreamSynchronize(stream_);
+        if (e != hipSuccess) { (void)hipFree(p); SDMI_HIP(e); }
+        pool_.note_fill(bytes);
+    }
+    if (weight_buffer) persistent_blocks_.push_back({p, bytes});
+    return p;
+}
+
 void Engine::ensure_arena(int group) {
     if (arena_done_[group]) return;
     size_t total = 0;
@@ -633,13 +647,12 @@ void Engine::ensure_arena(int group) {
         total += (count * (e.wdt ? 2 : 4) + 255) / 256 * 256;
     }
     if (total) {
-        char* base = nullptr;
-        SDMI_HIP(hipMalloc((void**)&base, total));
+        char* base = static_cast<char*>(persistent_alloc(total));
         weight_allocs_.push_back(base);
         arena_base_[group] = base;
         arena_bytes_[group] = total;
         if (!bf16_) {
-            SDMI_HIP(hipMalloc((void**)&split_base_[group], total / 2 * 3));
+            split_base_[group] = static_cast<char*>(persistent_alloc(total / 2 * 3));
             weight_allocs_.push_back(split_base_[group]);
         }
         size_t off = 0;
@@ -657,8 +670,7 @@ void Engine::ensure_arena(int group) {
         for (auto& e : entries_)
             if (e.group == group && e.kind <= 1) mtotal += (stage_elems(e) * sizeof(float) + 255) / 256 * 256;
         if (mtotal) {
-            char* mbase = nullptr;
-            SDMI_HIP(hipMalloc((void**)&mbase, mtotal));
+            char* mbase = static_cast<char*>(persistent_alloc(mtotal));
             weight_allocs_.push_back(mbase);
             size_t off = 0;
             for (auto& e : entries_) {
@@ -719,10 +731,9 @@ void Engine::pack_entry(WeightEntry& e, float* stage) {
         if (err == hipSuccess && e.dst8) {
             const size_t kp = (size_t)((cin + 127) / 128 * 128) * k * k;
             if (!*e.dst8) {
-                void *q = nullptr, *sc = nullptr;
-                SDMI_HIP(hipMalloc(&q, (size_t)cout * kp));
+                void* q = persistent_alloc((size_t)cout * kp);
                 weight_allocs_.push_back(q);
-                SDMI_HIP(hipMalloc(&sc, (size_t)cout * kp / 32));
+                void* sc = persistent_alloc((size_t)cout * kp / 32);
                 weight_allocs_.push_back(sc);
                 *e.dst8 = reinterpret_cast<float*>(q);
                 *e.dsts = reinterpret_cast<float*>(sc);
@@ -736,10 +747,9 @@ void Engine::pack_entry(WeightEntry& e, float* stage) {
             const int cin = (int)e.dims[0], cout = (int)e.dims[1];
             const size_t kp = (size_t)(cin + 127) / 128 * 128;
             if (!*e.dst8) {
-                void *q = nullptr, *sc = nullptr;
-                SDMI_HIP(hipMalloc(&q, (size_t)cout * kp));
+                void* q = persistent_alloc((size_t)cout * kp);
                 weight_allocs_.push_back(q);
-                SDMI_HIP(hipMalloc(&sc, (size_t)cout * kp / 32));
+                void* sc = persistent_alloc((size_t)cout * kp / 32);
                 weight_allocs_.push_back(sc);
                 *e.dst8 = reinterpret_cast<float*>(q);
                 *e.dsts = reinterpret_cast<float*>(sc);
@@ -976,8 +986,8 @@ void Engine::lora_add(sdmi_lora* a, const char* target, const float* down, const
     const size_t n_in = e.kind == 0 ? (size_t)(e.dims[1] * e.dims[2] * e.dims[3]) : (size_t)e.dims[0];
     const size_t n_out = e.kind == 0 ? (size_t)e.dims[0] : (size_t)e.dims[1];
     SDMI_HIP(hipSetDevice(cfg_.device));
-    float* dev = nullptr;
-    SDMI_HIP(hipMalloc((void**)&dev, (size_t)rank * (n_in + n_out) * sizeof(float)));
+    // the copies below run on the null stream, which nothing orders behind the engine's: a fill of this buffer is complete before they start
+    float* dev = static_cast<float*>(persistent_alloc((size_t)rank * (n_in + n_out) * sizeof(float), /*weight_buffer=*/false));
     hipError_t err = hipMemcpy(dev, down, (size_t)rank * n_in * sizeof(float), hipMemcpyHostToDevice);
     if (err == hipSuccess) err = hipMemcpy(dev + (size_t)rank * n_in, up, (size_t)rank * n_out * sizeof(float), hipMemcpyHostToDevice);
     if (err != hipSuccess) { (void)hipFree(dev); SDMI_HIP(err); }
@@ -1249,6 +1259,26 @@ void Engine::set_option(const std::string& key, const std::string& value) {
     else if (key == "fp8_ops") opt_fp8_ops_ = std::stoi(value);
     else if (key == "op_resid") opt_op_resid_ = std::stoi(value);
     else if (key == "op_misalign") opt_op_misalign_ = std::stoi(value);
+    else if (key == "pool_fill") {   // tests: -1 = off, 0 .. 255 = the byte every pool block and persistent allocation made from now on is filled with (DevPool::set_fill)
+        const int b = std::stoi(value);
+        if (b < -1 || b > 255) throw Error(SDMI_ERR_INVALID, "pool_fill: -1 (off) or a byte 0 .. 255");
+        pool_.set_fill(b);
+        // the constructor allocated the fused q | k | v weight buffers before any option could be set: while no weight is loaded they hold nothing, fill them as well
+        if (b >= 0 && std::none_of(entries_.begin(), entries_.end(), [](const WeightEntry& w) { return w.set; })) {
+            SDMI_HIP(hipSetDevice(cfg_.device));
+            for (const PersistentBlock& pb : persistent_blocks_) {
+                SDMI_HIP(hipMemsetAsync(pb.p, b, pb.bytes, stream_));
+                pool_.note_fill(pb.bytes);
+            }
+        }
+    }
+    else if (key == "dump_pool_fills") {   // "blocks bytes" filled since this option was last written (or the context was created)
+        std::ofstream f(value);
+        if (!f) throw Error(SDMI_ERR_IO, "dump_pool_fills: cannot write " + value);
+        unsigned long long blocks = 0, bytes = 0;
+        pool_.take_fill_counts(&blocks, &bytes);
+        f << blocks << " " << bytes << "\n";
+    }
     else if (key == "cfg_share") opt_cfg_share_ = std::stoi(value);
     else if (key == "attn_kv_splits") opt_attn_kv_splits_ = std::stoi(value);
     else if (key == "attn_kv_prefer8") opt_attn_kv_prefer8_ = std::stoi(value);

@@ -49,6 +49,15 @@ public:
     // (the clean-up of a call that threw half way through a forward pass)
     unsigned long long serial() const { return serial_; }
     size_t free_since(unsigned long long mark);
+    // tests (option pool_fill): byte >= 0 overwrites every block alloc hands out, over its whole rounded size, with that byte -- a hipMemsetAsync on `stream`
+    // (the stream all of the pool's users work on), enqueued before alloc returns and so in front of the block's first write; -1 = off, nothing is enqueued.
+    // note_fill / take_fill_counts: blocks and bytes filled since the counts were last taken (option dump_pool_fills; the engine's own persistent
+    // allocations are counted here too).
+    void set_stream(hipStream_t s) { stream_ = s; }
+    void set_fill(int byte) { fill_ = byte; }
+    int fill() const { return fill_; }
+    void note_fill(size_t bytes) { ++fill_blocks_; fill_bytes_ += bytes; }
+    void take_fill_counts(unsigned long long* blocks, unsigned long long* bytes) { *blocks = fill_blocks_; *bytes = fill_bytes_; fill_blocks_ = fill_bytes_ = 0; }
 
 private:
     struct Block { size_t off, size; };
@@ -58,6 +67,9 @@ private:
     std::map<void*, Live> live_;
     size_t reserved_ = 0, in_use_ = 0, high_ = 0;
     unsigned long long serial_ = 0;
+    hipStream_t stream_ = nullptr;
+    int fill_ = -1;
+    unsigned long long fill_blocks_ = 0, fill_bytes_ = 0;
 };
 
 // dt: storage type of a device tensor -- 0 = fp32, 1 = bf16 (precision = 1).  `p` is typed float* for
@@ -491,6 +503,13 @@ private:
     std::vector<WeightEntry> entries_;
     std::map<std::string, int> entry_index_;
     std::vector<void*> weight_allocs_;
+    // every hipMalloc of persistent device data (weight arenas, planes, masters, fused q | k | v weights, MXFP8 copies, LoRA factors) goes through here, so that option
+    // pool_fill reaches what the pool does not hold: the allocation is filled like a pool block when the option is on at that moment.  weight_buffer: written on
+    // stream_ only, and remembered, so that pool_fill set before the first weight is loaded also fills the buffers the constructor made; false (the LoRA factors, copied
+    // on the null stream): the fill is complete on return.  The caller records the pointer for the matching hipFree.
+    void* persistent_alloc(size_t bytes, bool weight_buffer = true);
+    struct PersistentBlock { void* p; size_t bytes; };
+    std::vector<PersistentBlock> persistent_blocks_;
     bool finalized_ = false;
     std::vector<float> alphas_;
 

@@ -714,7 +714,7 @@ class StableDiffusion:
         check(self._lib.sdmi_synchronize(self._ctx))
 
     # options that change no kernel choice (measurement / dump switches): not listed as non-default settings
-    _PASSIVE_OPTIONS = ("profile", "profile_reset", "record_shapes", "dump_shapes", "dump_choices", "dump_profile_tags", "roctx")
+    _PASSIVE_OPTIONS = ("profile", "profile_reset", "record_shapes", "dump_shapes", "dump_choices", "dump_profile_tags", "dump_pool_fills", "roctx")
 
     def set_option(self, key: str, value) -> None:
         check(self._lib.sdmi_set_option(self._ctx, key.encode(), str(value).encode()))
