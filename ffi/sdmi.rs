@@ -66,6 +66,11 @@ extern "C" {
     fn sdmi_set_weight(ctx: *mut c_void, name: *const c_char, data: *const c_float, ndim: i32, dims: *const i64) -> c_int;
     fn sdmi_load_weights_dir(ctx: *mut c_void, dump_dir: *const c_char) -> c_int;
     fn sdmi_load_weights_mpk(ctx: *mut c_void, mpk_path: *const c_char) -> c_int;
+    fn sdmi_load_weights_safetensors(ctx: *mut c_void, path: *const c_char) -> c_int;
+    fn sdmi_safetensors_list(path: *const c_char, out: *mut c_char, capacity: usize, needed: *mut usize) -> c_int;
+    fn sdmi_checkpoint_key(dump_name: *const c_char, out: *mut c_char, capacity: usize, needed: *mut usize, transposed: *mut i32) -> c_int;
+    fn sdmi_default_alphas_cumprod(out: *mut c_float, n: i32) -> c_int;
+    fn sdmi_op_unpack_tensor(ctx: *mut c_void, raw: *const c_void, dtype: i32, ndim: i32, dims: *const i64, transform: i32, out: *mut c_float) -> c_int;
     fn sdmi_finalize_weights(ctx: *mut c_void) -> c_int;
     fn sdmi_set_option(ctx: *mut c_void, key: *const c_char, value: *const c_char) -> c_int;
     fn sdmi_create_multi(out: *mut *mut c_void, cfg: *const SdmiConfig, devices: *const i32, n_devices: i32) -> c_int;
@@ -342,6 +347,68 @@ impl StableDiffusionMi355 {
         }
     }
 
+    /// An SD v1.x checkpoint in the CompVis layout, one `.safetensors` file (F32 / F16 / BF16), converted on the device
+    /// (`sdmi_load_weights_safetensors`; no reference counterpart: the reference converts checkpoints in Python).
+    pub fn load_safetensors(path: &str, device: i32, precision: i32) -> Result<Self, Box<dyn Error>> {
+        unsafe {
+            let mut cfg: SdmiConfig = std::mem::zeroed();
+            sdmi_default_config(&mut cfg);
+            cfg.device = device;
+            cfg.precision = precision;
+            let mut ctx: *mut c_void = std::ptr::null_mut();
+            if sdmi_create(&mut ctx, &cfg) != 0 {
+                return Err(last_error().into());
+            }
+            let p = CString::new(path)?;
+            if sdmi_load_weights_safetensors(ctx, p.as_ptr()) != 0 || sdmi_finalize_weights(ctx) != 0 {
+                let e = last_error();
+                sdmi_destroy(ctx);
+                return Err(e.into());
+            }
+            Ok(Self { ctx, ctx_dim: cfg.ctx_dim as usize, clip_ctx: cfg.clip_ctx as usize,
+                      latent: 4 * (cfg.latent_h * cfg.latent_w) as usize })
+        }
+    }
+
+    /// The CompVis checkpoint key of a dump-tree tensor name and whether the checkpoint holds its transpose (`sdmi_checkpoint_key`, host only).
+    pub fn checkpoint_key(dump_name: &str) -> Result<(String, bool), Box<dyn Error>> {
+        let name = CString::new(dump_name)?;
+        let mut buf = vec![0u8; 512];
+        let (mut needed, mut transposed) = (0usize, 0i32);
+        let st = unsafe { sdmi_checkpoint_key(name.as_ptr(), buf.as_mut_ptr() as *mut c_char, buf.len(), &mut needed, &mut transposed) };
+        if st != 0 { return Err(last_error().into()); }
+        buf.truncate(needed.saturating_sub(1));
+        Ok((String::from_utf8(buf)?, transposed != 0))
+    }
+
+    /// `key\tdtype\tshape\tfile offset\tdump name or -` lines of a `.safetensors` file (`sdmi_safetensors_list`, host only).
+    pub fn safetensors_list(path: &str) -> Result<String, Box<dyn Error>> {
+        let p = CString::new(path)?;
+        let mut needed = 0usize;
+        if unsafe { sdmi_safetensors_list(p.as_ptr(), std::ptr::null_mut(), 0, &mut needed) } != 0 { return Err(last_error().into()); }
+        let mut buf = vec![0u8; needed];
+        if unsafe { sdmi_safetensors_list(p.as_ptr(), buf.as_mut_ptr() as *mut c_char, buf.len(), &mut needed) } != 0 { return Err(last_error().into()); }
+        buf.truncate(needed.saturating_sub(1));
+        Ok(String::from_utf8(buf)?)
+    }
+
+    /// The LDM schedule a checkpoint without `alphas_cumprod` gets (`sdmi_default_alphas_cumprod`, host only).
+    pub fn default_alphas_cumprod(n: usize) -> Result<Vec<f32>, Box<dyn Error>> {
+        let mut out = vec![0f32; n];
+        if unsafe { sdmi_default_alphas_cumprod(out.as_mut_ptr(), n as i32) } != 0 { return Err(last_error().into()); }
+        Ok(out)
+    }
+
+    /// The checkpoint conversion kernel on its own (`sdmi_op_unpack_tensor`): `raw` = the tensor's bytes, dtype 0 F32 / 1 F16 / 2 BF16,
+    /// transform 0 copy / 1 2-D transpose / 2 `[cout,3,kh,kw]` padded to 4 input channels.
+    pub fn op_unpack_tensor(&self, raw: &[u8], dtype: i32, dims: &[i64], transform: i32) -> Result<Vec<f32>, Box<dyn Error>> {
+        let count: i64 = dims.iter().product();
+        if count <= 0 || raw.len() != count as usize * if dtype == 0 { 4 } else { 2 } { return Err("op_unpack_tensor: raw does not match dims".into()); }
+        let mut out = vec![0f32; if transform == 2 { count as usize / 3 * 4 } else { count as usize }];
+        let st = unsafe { sdmi_op_unpack_tensor(self.ctx, raw.as_ptr() as *const c_void, dtype, dims.len() as i32, dims.as_ptr(), transform, out.as_mut_ptr()) };
+        if st != 0 { Err(last_error().into()) } else { Ok(out) }
+    }
+
     /// `context(&tokenizer, text)` (stablediffusion/mod.rs:198-210): `[T, ctx_dim]` row-major, T = tokens + 2.
     /// Needs the clip/ subtree in the dump; `unconditional_context` (:194-196) is `context(tok, "")`.
     pub fn context(&self, tokenizer: &TokenizerMi355, text: &str) -> Vec<f32> {
@@ -481,7 +548,7 @@ pub struct StableDiffusionMi355Node {
 }
 
 impl StableDiffusionMi355Node {
-    /// kind = "dump" (npy tree, load_stable_diffusion) | "burn" (.mpk record, load_stable_diffusion_model_file)
+    /// kind = "dump" (npy tree, load_stable_diffusion) | "burn" (.mpk record, load_stable_diffusion_model_file) | "safetensors" (CompVis checkpoint)
     pub fn load(kind: &str, path: &str, devices: &[i32], precision: i32) -> Result<Self, Box<dyn Error>> {
         unsafe {
             let mut cfg: SdmiConfig = std::mem::zeroed();

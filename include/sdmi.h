@@ -120,6 +120,32 @@ int sdmi_load_weights_mpk(sdmi_ctx* ctx, const char* mpk_path);
 /* Host only (no context): the tensors of a record as text, one "name<TAB>d0,d1,..<TAB>file offset" line each (dump-tree
  * names), after a "# format=.. float=.." line.  *needed = bytes incl. the terminator; out may be NULL to query it. */
 int sdmi_mpk_list(const char* mpk_path, char* out, size_t capacity, size_t* needed);
+/* An SD v1.x checkpoint in the CompVis layout -- ONE .safetensors file with keys "model.diffusion_model.…", "first_stage_model.…",
+ * "cond_stage_model.transformer.text_model.…" and "alphas_cumprod", F32 / F16 / BF16, Linear weights as torch's [out, in] -- read natively (DESIGN.md
+ * section 9e): the file is memory-mapped, every tensor of the configured model is looked up under sdmi_checkpoint_key(its dump name), its RAW bytes are
+ * moved to the device and converted there (csrc/k_unpack.hip: exact widening to fp32, the Linear transpose, the zero 4th input channel of the VAE
+ * encoder's RGB conv_in), and packed like every other loader's tensors.  Keys the model has no tensor for (model_ema.*, position_ids, ...) are skipped
+ * whatever their dtype.  alphas_cumprod is taken from the file (F64 accepted) or, when absent, computed (sdmi_default_alphas_cumprod).
+ * SDMI_ERR_IO / SDMI_ERR_WEIGHTS: an unreadable / malformed file (csrc/safetensors_reader.hpp lists what is refused); SDMI_ERR_WEIGHTS: a hot-path
+ * tensor without a source (the message names the dump name and the key), a shape other than the model's (key, file's shape, expected shape), no
+ * matching key at all; SDMI_ERR_UNSUPPORTED: F64 or an integer dtype on a tensor of the model; SDMI_ERR_STATE: a LoRA adapter with a non-zero
+ * scale.  Everything is checked before the first tensor is staged: a refused file leaves the context as it was.  The CLIP and VAE-encoder groups are
+ * all-or-nothing by sdmi_finalize_weights' rule; call it after.  Out of scope: .ckpt pickles, diffusers-layout and sharded checkpoints, SD 2.x / SDXL. */
+int sdmi_load_weights_safetensors(sdmi_ctx* ctx, const char* path);
+/* Host only (no context): the tensors of a .safetensors file as text, one "key<TAB>dtype<TAB>d0,d1,..<TAB>file offset<TAB>dump name or -" line each, in
+ * header order.  A backslash, tab, newline or other control character inside a key is written as its JSON escape, so that a key stays one field.  The dump
+ * name is the one whose sdmi_checkpoint_key is the key (SD v1.4's tensor set), "-" for any other key.  *needed = bytes incl. the terminator; out may be
+ * NULL to query it. */
+int sdmi_safetensors_list(const char* path, char* out, size_t capacity, size_t* needed);
+/* Host only.  Writes the CompVis checkpoint key of `dump_name`, e.g. "unet/input_blocks/rt1/res/conv_in/weight" ->
+ * "model.diffusion_model.input_blocks.1.0.in_layers.2.weight" (derived by rule, csrc/ckpt_keys.cpp; pinned against the reference's Python model and
+ * exporters by tests/golden/sd14_ckpt_keys.txt).  *transposed = 1 where the checkpoint holds torch's [out,in] of a dump [in,out].  *needed = bytes
+ * incl. the terminator; out may be NULL to query it.
+ * SDMI_ERR_INVALID for a name that has no checkpoint source: module metadata such as eps / n_group, n_steps. */
+int sdmi_checkpoint_key(const char* dump_name, char* out, size_t capacity, size_t* needed, int32_t* transposed);
+/* Host only.  The schedule sdmi_load_weights_safetensors installs when the file has no alphas_cumprod: the LDM "scaled linear" one,
+ * float32(cumprod(1 - linspace(sqrt(0.00085), sqrt(0.012), n)^2)) computed in f64.  out [n], n >= 1. */
+int sdmi_default_alphas_cumprod(float* out, int32_t n);
 /* One flat image of every tensor: `data` holds, for each entry i of the configured model in
  * sdmi_weight_info() order and restricted to the weight groups selected by `groups` (bit 0: hot path = UNet,
  * VAE decoder, alphas_cumprod; bit 1: CLIP; bit 2: VAE encoder), the tensor's fp32 values in the reference's
@@ -395,7 +421,8 @@ void sdmi_destroy_multi(sdmi_multi* m);
 int32_t sdmi_multi_size(sdmi_multi* m);
 /* the per-device context (owned by m): for sdmi_set_weight / sdmi_load_weights_* / sdmi_set_option per device */
 sdmi_ctx* sdmi_multi_ctx(sdmi_multi* m, int32_t index);
-/* load_stable_diffusion / load_stable_diffusion_model_file on every device in parallel + finalize; kind = "dump" | "burn" */
+/* load_stable_diffusion / load_stable_diffusion_model_file / sdmi_load_weights_safetensors on every device in parallel + finalize;
+ * kind = "dump" | "burn" | "safetensors" */
 int sdmi_multi_load_weights(sdmi_multi* m, const char* kind, const char* path);
 /* StableDiffusion::sample_image for n_images of ONE prompt: context [T, ctx_dim], uncond [Tu, ctx_dim] (host);
  * init_latents [n_images,4,h,w] or NULL (image i draws N(0,1) from stream seed + i); rgb_out n_images x [8h,8w,3] (host). */
@@ -501,6 +528,11 @@ int sdmi_op_qkv_attention_ragged(sdmi_ctx* ctx, const float* q, const float* k, 
  * run); an axis whose size does not change is skipped.  Any positive sizes. */
 int sdmi_op_resize(sdmi_ctx* ctx, const float* x, int32_t n, int32_t h, int32_t w, int32_t out_h, int32_t out_w, int32_t mode, int32_t antialias,
                    float* out);
+/* The checkpoint conversion kernel on its own (csrc/k_unpack.hip; no reference counterpart).
+ * raw = ndim-D tensor of `dtype` (0 F32, 1 F16, 2 BF16) in host memory.
+ * transform: 0 copy, 1 2-D transpose ([d0,d1] -> [d1,d0]), 2 conv [cout,3,kh,kw] with cin 3 padded to 4 (-> [cout,4,kh,kw], the 4th channel zero).
+ * out = the fp32 stage tensor.  Exact, on the bit patterns: f16 subnormals, infinities and NaN payloads included. */
+int sdmi_op_unpack_tensor(sdmi_ctx* ctx, const void* raw, int32_t dtype, int32_t ndim, const int64_t* dims, int32_t transform, float* out);
 /* timestep_embedding (unet/mod.rs:19-30): out [dim] for timestep t. */
 /* GEGLU::forward (src/model/unet/mod.rs:579-591): x [rows, cin], weight [cin, 2*hidden] (Burn Linear layout), bias
  * [2*hidden] or NULL -> out [rows, hidden] = a * gelu(b), a | b = the halves of x W + bias.  One fused kernel when the

@@ -72,6 +72,10 @@ SIGNATURES = {
     "sdmi_load_weights_dir": (C.c_int, [_CTX, C.c_char_p]),
     "sdmi_load_weights_mpk": (C.c_int, [_CTX, C.c_char_p]),
     "sdmi_mpk_list": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sdmi_load_weights_safetensors": (C.c_int, [_CTX, C.c_char_p]),
+    "sdmi_safetensors_list": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sdmi_checkpoint_key": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
+    "sdmi_default_alphas_cumprod": (C.c_int, [_F, C.c_int32]),
     "sdmi_load_weights_packed": (C.c_int, [_CTX, _F, C.c_size_t, C.c_int32]),
     "sdmi_packed_size": (C.c_int64, [_CTX, C.c_int32]),
     "sdmi_finalize_weights": (C.c_int, [_CTX]),
@@ -94,6 +98,7 @@ SIGNATURES = {
     "sdmi_hires_latent_dev": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_size_t, C.c_void_p, _HIRES, C.c_void_p, C.c_void_p]),
     "sdmi_hires_image_dev": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_size_t, C.c_void_p, _HIRES, C.c_void_p, C.c_void_p]),
     "sdmi_op_resize": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),
+    "sdmi_op_unpack_tensor": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, _F]),
     "sdmi_multi_set_sampler": (C.c_int, [C.c_void_p, _SAMPLER]),
     "sdmi_lora_create": (C.c_int, [_CTX, C.POINTER(C.c_void_p)]),
     "sdmi_lora_add": (C.c_int, [C.c_void_p, C.c_char_p, _F, _F, C.c_int32, C.c_float]),

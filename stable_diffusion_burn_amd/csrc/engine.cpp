@@ -1,7 +1,9 @@
 // engine.cpp -- see engine.hpp.  Reference citations are relative to
 // Gadersd/stable-diffusion-burn (src/model/...).
 #include "engine.hpp"
+#include "ckpt_keys.hpp"
 #include "mpk_reader.hpp"
+#include "safetensors_reader.hpp"
 
 #include <dlfcn.h>
 
@@ -911,6 +913,152 @@ void Engine::load_weights_mpk(const char* path) {
     if (!used) throw Error(SDMI_ERR_WEIGHTS, std::string("load_weights_mpk: no tensor of ") + path + " matches the configured model");
     SDMI_HIP(hipStreamSynchronize(stream_));
     stager_release();
+}
+
+// An SD v1.x checkpoint in the CompVis layout, one .safetensors file.  Every weight entry is looked up under the key
+// checkpoint_key derives from its dump name; the tensor's RAW bytes go mapping -> pinned ring -> device as they are (half the bytes for F16 / BF16), and ONE
+// launch of k_unpack.hip writes the fp32 tensor in the reference's layout -- into a stage buffer for the consumers of stage_commit (conv / Linear: master copy,
+// pre_scale, pack_entry as for every other loader), or straight into the arena slot (norms, biases, embedding tables).  Everything about the file is checked
+// before the first tensor is staged, so a refused file leaves the context as it was.  Keys the model has no entry for (model_ema.*, position_ids, ...) are skipped.
+static int unpack_dtype(const std::string& d) { return d == "F32" ? 0 : d == "F16" ? 1 : d == "BF16" ? 2 : -1; }
+
+static float raw_to_f32(const unsigned char* p, const std::string& dtype, size_t i) {   // host twin of k_unpack.hip's conversions, + F64 (alphas_cumprod)
+    if (dtype == "F64") { double v; std::memcpy(&v, p + 8 * i, 8); return (float)v; }
+    uint32_t bits;
+    if (dtype == "F32") {
+        std::memcpy(&bits, p + 4 * i, 4);
+    } else {
+        uint16_t h;
+        std::memcpy(&h, p + 2 * i, 2);
+        if (dtype == "BF16") {
+            bits = (uint32_t)h << 16;
+        } else {
+            const uint32_t sign = ((uint32_t)h & 0x8000u) << 16, ex = (h >> 10) & 31u;
+            uint32_t man = h & 0x3ffu;
+            if (ex == 0) {
+                if (man == 0) bits = sign;
+                else { uint32_t s = 0; while (!(man & 0x400u)) { man <<= 1; ++s; } bits = sign | ((113u - s) << 23) | ((man & 0x3ffu) << 13); }
+            } else {
+                bits = sign | ((ex == 31 ? 255u : ex + 112u) << 23) | (man << 13);
+            }
+        }
+    }
+    float f;
+    std::memcpy(&f, &bits, 4);
+    return f;
+}
+
+static std::string shape_str(const int64_t* d, size_t n) {
+    std::string s = "[";
+    for (size_t i = 0; i < n; ++i) s += (i ? "," : "") + std::to_string(d[i]);
+    return s + "]";
+}
+
+void Engine::load_weights_safetensors(const char* path) {
+    if (!path) throw Error(SDMI_ERR_INVALID, "load_weights_safetensors: null path");
+    SDMI_HIP(hipSetDevice(cfg_.device));
+    lora_refuse_bulk_load("load_weights_safetensors");
+    SafetensorsFile f(path);
+    struct Job { WeightEntry* e; const StTensor* t; int dtype; int transform; };
+    std::vector<Job> jobs;
+    const StTensor* alphas = nullptr;
+    WeightEntry* alphas_entry = nullptr;
+    for (auto& e : entries_) {
+        std::string key;
+        bool transposed = false;
+        if (!checkpoint_key(e.name, &key, &transposed)) throw Error(SDMI_ERR_STATE, "load_weights_safetensors: no checkpoint key rule for '" + e.name + "'");
+        const StTensor* t = f.find(key);
+        if (e.kind == 3) { alphas = t; alphas_entry = &e; continue; }   // optional: the LDM schedule is computed when the file has none
+        if (!t) {
+            if (e.group == 0)
+                throw Error(SDMI_ERR_WEIGHTS, std::string("load_weights_safetensors: ") + path + " has no tensor '" + key + "' (the source of '" + e.name + "')");
+            continue;   // CLIP / VAE encoder: all or nothing, decided by finalize_weights
+        }
+        const int dt = unpack_dtype(t->dtype);
+        if (dt < 0) throw Error(SDMI_ERR_UNSUPPORTED, "load_weights_safetensors: '" + key + "' has dtype " + t->dtype + "; F32, F16 and BF16 are supported");
+        if (transposed && (e.kind != 1 || e.ndim != 2)) throw Error(SDMI_ERR_STATE, "load_weights_safetensors: '" + e.name + "' is not a Linear weight");
+        int64_t want[4];
+        for (int i = 0; i < e.ndim; ++i) want[i] = e.dims[i];
+        if (transposed) std::swap(want[0], want[1]);   // torch's [out, in]
+        bool ok = (int)t->shape.size() == e.ndim;
+        for (int i = 0; ok && i < e.ndim; ++i) ok = t->shape[i] == want[i];
+        if (!ok)
+            throw Error(SDMI_ERR_WEIGHTS, "load_weights_safetensors: '" + key + "' has shape " + shape_str(t->shape.data(), t->shape.size()) +
+                                              ", the configured model expects " + shape_str(want, (size_t)e.ndim) + " ('" + e.name + "')");
+        jobs.push_back(Job{&e, t, dt, transposed ? 1 : (e.kind == 0 && e.dims[1] == 3) ? 2 : 0});
+    }
+    if (jobs.empty()) throw Error(SDMI_ERR_WEIGHTS, std::string("load_weights_safetensors: no tensor of ") + path + " matches the configured model");
+    std::vector<float> schedule;
+    if (alphas_entry) {
+        const size_t n = entry_count(*alphas_entry);
+        schedule.resize(n);
+        if (alphas) {
+            if (alphas->dtype != "F64" && unpack_dtype(alphas->dtype) < 0)
+                throw Error(SDMI_ERR_UNSUPPORTED, "load_weights_safetensors: 'alphas_cumprod' has dtype " + alphas->dtype);
+            if (alphas->shape.size() != 1 || (size_t)alphas->shape[0] != n)
+                throw Error(SDMI_ERR_WEIGHTS, "load_weights_safetensors: 'alphas_cumprod' has shape " + shape_str(alphas->shape.data(), alphas->shape.size()) +
+                                                  ", expected [" + std::to_string(n) + "]");
+            for (size_t i = 0; i < n; ++i) schedule[i] = raw_to_f32(alphas->data, alphas->dtype, i);
+        } else {
+            default_alphas_cumprod(schedule.data(), (int)n);
+        }
+    }
+
+    // The raw bytes go through the ring, so its limit applies to the file's bytes alone, as for every other loader.  The fp32 result of a conv / Linear tensor
+    // goes to ONE device buffer of this call, sized for the largest of them (118 MB for SD v1.4's 2560 -> 1280 3x3 convolutions) and shared by all: the stream
+    // orders tensor k's packing in front of tensor k + 1's conversion.  It is freed with the stager, so a load leaves nothing resident behind.
+    size_t conv_bytes = 0;
+    for (const Job& j : jobs)
+        if (j.e->kind <= 1) conv_bytes = std::max(conv_bytes, stage_elems(*j.e) * sizeof(float));
+    struct DevTemp {
+        void* p = nullptr;
+        ~DevTemp() { if (p) (void)hipFree(p); }
+    } conv_stage;
+    if (conv_bytes) SDMI_HIP(hipMalloc(&conv_stage.p, conv_bytes));
+    struct Drain {   // the temporary outlives everything enqueued on it, also on the way out of an error
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{stream_};
+    for (const Job& j : jobs) {
+        WeightEntry& e = *j.e;
+        ensure_arena(e.group);
+        size_t off; int half;
+        char* pinned = stage_reserve(j.t->nbytes, &off, &half);
+        std::memcpy(pinned, j.t->data, j.t->nbytes);   // any file alignment
+        char* dev = stager_->dev[half] + off;
+        SDMI_HIP(hipMemcpyAsync(dev, pinned, j.t->nbytes, hipMemcpyHostToDevice, stream_));
+        float* out = e.kind <= 1 ? static_cast<float*>(conv_stage.p) : *e.dst;
+        long long d0, d1;
+        if (j.transform == 1) { d0 = e.dims[1]; d1 = e.dims[0]; }
+        else if (j.transform == 2) { d0 = e.dims[0]; d1 = e.dims[2] * e.dims[3]; }
+        else { d0 = (long long)entry_count(e); d1 = 1; }
+        {
+            ProfScope ps_o(this, PC_OTHER, 0, (double)j.t->nbytes + (double)(e.kind <= 1 ? stage_elems(e) : entry_count(e)) * 4);
+            ps_o.set_tag("unpack %s t%d %lldx%lld", j.t->dtype.c_str(), j.transform, d0, d1);
+            SDMI_HIP(launch_unpack_tensor(dev, j.dtype, j.transform, d0, d1, out, stream_));
+        }
+        count_kernel();
+        if (e.kind <= 1) {
+            if (e.master) SDMI_HIP(hipMemcpyAsync(e.master, out, stage_elems(e) * sizeof(float), hipMemcpyDeviceToDevice, stream_));
+            pack_entry(e, out);
+        }
+        e.set = true;
+        finalized_ = false;
+    }
+    if (alphas_entry) { alphas_ = schedule; alphas_entry->set = true; }
+    SDMI_HIP(hipStreamSynchronize(stream_));
+    if (profiling_) prof_flush();
+    stager_release();
+}
+
+// the conversion kernel on its own (tests: sdmi_op_unpack_tensor); raw / out: device pointers
+void Engine::op_unpack_tensor(const void* raw, int dtype, int ndim, const int64_t* dims, int transform, float* out) {
+    long long d0, d1;
+    if (transform == 1) { d0 = dims[0]; d1 = dims[1]; }
+    else if (transform == 2) { d0 = dims[0]; d1 = dims[2] * dims[3]; }
+    else { d0 = 1; for (int i = 0; i < ndim; ++i) d0 *= dims[i]; d1 = 1; }
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_unpack_tensor(raw, dtype, transform, d0, d1, out, stream_)); }
+    count_kernel();
 }
 
 void Engine::finalize_weights() {

@@ -156,6 +156,7 @@ public:
     void set_weight(const char* name, const float* data, int ndim, const int64_t* dims);
     void load_weights_dir(const char* dir);
     void load_weights_mpk(const char* path);
+    void load_weights_safetensors(const char* path);   // an SD v1.x CompVis checkpoint, converted on the device
     void load_weights_packed(const float* data, size_t n_floats, int groups);
     size_t packed_size(int groups) const;
     void finalize_weights();
@@ -193,6 +194,8 @@ public:
     // x [n][h*w][4] -> y [n][oh*ow][4] (NHWC4, device) by the tables of sdmi_resize_weights: horizontal pass, then vertical; an unchanged axis is skipped
     void resize_nhwc4(const float* x, int n, int h, int w, int oh, int ow, int mode, int antialias, float* y);
     void op_resize(const float* x_nchw, int n, int h, int w, int oh, int ow, int mode, int antialias, float* out_nchw);
+    // k_unpack.hip on its own: raw = a checkpoint tensor's bytes (dtype 0 F32 / 1 F16 / 2 BF16), transform 0 copy / 1 2-D transpose / 2 RGB conv padded to 4 input channels
+    void op_unpack_tensor(const void* raw, int dtype, int ndim, const int64_t* dims, int transform, float* out);
     // sampler choice (sdmi_set_sampler): sticky, read by sample_loop -- every sampling entry point.  The default (kind 0,
     // eta 0) is the reference's DDIM on its own launches.  check_sampler throws SDMI_ERR_INVALID for what the header lists; null = the default.
     static void check_sampler(const sdmi_sampler& s);

@@ -284,4 +284,10 @@ constexpr int kLoraMaxTerms = 8;
 struct LoraMerge { const float* W0; float* W; int R, Cc, n_terms; LoraTerm t[kLoraMaxTerms]; };
 hipError_t launch_lora_merge(const LoraMerge& m, hipStream_t s);
 
+// ---- checkpoint tensors (k_unpack.hip) ---------------------------------------------------
+// raw: the bytes of a checkpoint tensor on the device, dtype 0 F32 / 1 F16 / 2 BF16 (exact conversions, on the bit patterns); out: fp32.
+// transform 0: out[i] = raw[i], i < d0 d1.  1: raw [d0][d1] -> out [d1][d0] (a Linear weight, torch [out, in] -> the dump's [in, out]).
+// 2: raw [d0][3][d1] -> out [d0][4][d1], the 4th input channel zero (the VAE encoder's RGB conv_in; d1 = kh kw).  One launch.
+hipError_t launch_unpack_tensor(const void* raw, int dtype, int transform, long long d0, long long d1, float* out, hipStream_t s);
+
 }  // namespace sdmi

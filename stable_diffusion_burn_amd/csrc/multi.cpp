@@ -275,10 +275,12 @@ int sdmi_multi_load_weights(sdmi_multi* m, const char* kind, const char* path) {
     return multi_guard([&] {
         if (!m || !kind || !path) throw sdmi::Error(SDMI_ERR_INVALID, "multi_load_weights: null argument");
         const std::string k = kind;
-        if (k != "dump" && k != "burn") throw sdmi::Error(SDMI_ERR_INVALID, "multi_load_weights: kind must be \"dump\" or \"burn\"");
+        if (k != "dump" && k != "burn" && k != "safetensors") throw sdmi::Error(SDMI_ERR_INVALID, "multi_load_weights: kind must be \"dump\", \"burn\" or \"safetensors\"");
         m->m->for_each_device([&](int r) {
             sdmi::Engine& e = m->m->engine(r);
-            if (k == "dump") e.load_weights_dir(path); else e.load_weights_mpk(path);
+            if (k == "dump") e.load_weights_dir(path);
+            else if (k == "burn") e.load_weights_mpk(path);
+            else e.load_weights_safetensors(path);
             e.finalize_weights();
         });
     });

@@ -1,13 +1,14 @@
 // sdmi_sample -- the C++ twin of the reference's `sample` binary (src/bin/sample/main.rs:36-125), same argv:
 //
-//   sdmi_sample <model_type(burn or dump)> <model_name> <unconditional_guidance_scale> <n_diffusion_steps>
+//   sdmi_sample <model_type(burn, dump or safetensors)> <model_name> <unconditional_guidance_scale> <n_diffusion_steps>
 //               <prompt> <output_image_name> [device]
 //
 // It is a pure consumer of the C ABI (include/sdmi.h) -- the same calls the Rust shim (ffi/sdmi.rs) makes:
 // tokenizer -> CLIP context -> sample_image -> PNG.  Differences from the reference, all forced:
 //   * model_type "burn" reads the NamedMpkFileRecorder<FullPrecisionSettings> record "<model_name>.mpk" natively (the
 //     recorder sets the extension itself, main.rs:27-34; layout assumptions: csrc/mpk_reader.hpp); "dump" is the npy tree
-//     of python/dump.py (main.rs:94);
+//     of python/dump.py (main.rs:94); "safetensors" (no reference counterpart) is an SD v1.x checkpoint in the CompVis layout, <model_name> its file;
+//   * the usage line names the third model type, "safetensors"; every other message, and what "burn" and "dump" do, is unchanged;
 //   * device is "hip", "hip:N" or "cuda[N]" (alias, index N); "cpu" / "mps" are refused -- there is no CPU path;
 //   * the reference's noise is unseeded; here SDMI_SEED (default 0) seeds the device generator;
 //   * the merges file is $SDMI_BPE_VOCAB, default "bpe_simple_vocab_16e6.txt" in the working directory (tokenizer.rs:91);
@@ -54,7 +55,7 @@ static void apply_overrides(sdmi_config& cfg, const char* spec) {
 
 int main(int argc, char** argv) {
     if (argc != 7 && argc != 8) {
-        std::fprintf(stderr, "Usage: %s <model_type(burn or dump)> <model_name> <unconditional_guidance_scale> <n_diffusion_steps> <prompt> <output_image_name> [device(hip, hip:N)]\n", argv[0]);
+        std::fprintf(stderr, "Usage: %s <model_type(burn, dump or safetensors)> <model_name> <unconditional_guidance_scale> <n_diffusion_steps> <prompt> <output_image_name> [device(hip, hip:N)]\n", argv[0]);
         return 1;
     }
     const std::string model_type = argv[1], model_name = argv[2], prompt = argv[5], output = argv[6];
@@ -92,6 +93,8 @@ int main(int argc, char** argv) {
         std::string file = model_name;
         if (file.size() < 4 || file.compare(file.size() - 4, 4, ".mpk") != 0) file += ".mpk";   // FileRecorder::load sets the extension
         if (sdmi_load_weights_mpk(ctx, file.c_str()) != SDMI_OK || sdmi_finalize_weights(ctx) != SDMI_OK) die("Error loading model");
+    } else if (model_type == "safetensors") {
+        if (sdmi_load_weights_safetensors(ctx, model_name.c_str()) != SDMI_OK || sdmi_finalize_weights(ctx) != SDMI_OK) die("Error loading checkpoint");
     } else if (sdmi_load_weights_dir(ctx, model_name.c_str()) != SDMI_OK || sdmi_finalize_weights(ctx) != SDMI_OK) {
         die("Error loading model dump");
     }

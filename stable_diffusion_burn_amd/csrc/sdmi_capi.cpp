@@ -5,13 +5,17 @@
 #include <climits>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "engine.hpp"
+#include "ckpt_keys.hpp"
 #include "mpk_reader.hpp"
+#include "safetensors_reader.hpp"
 #include "tokenizer.hpp"
 
 using sdmi::Engine;
@@ -163,6 +167,63 @@ int sdmi_mpk_list(const char* mpk_path, char* out, size_t capacity, size_t* need
         *needed = s.size() + 1;
         if (out && capacity >= s.size() + 1) std::memcpy(out, s.c_str(), s.size() + 1);
         else if (out && capacity) throw Error(SDMI_ERR_INVALID, "mpk_list: capacity too small");
+    });
+}
+
+int sdmi_load_weights_safetensors(sdmi_ctx* ctx, const char* path) {
+    return guarded([&] { eng(ctx).load_weights_safetensors(path); });
+}
+
+// copies `s` + terminator to a caller's buffer by the query-then-fill convention of sdmi_mpk_list
+static void text_out(const std::string& s, char* out, size_t capacity, size_t* needed, const char* what) {
+    *needed = s.size() + 1;
+    if (out && capacity >= s.size() + 1) std::memcpy(out, s.c_str(), s.size() + 1);
+    else if (out && capacity) throw Error(SDMI_ERR_INVALID, std::string(what) + ": capacity too small");
+}
+
+// a key as one field of a tab-separated line: backslash and control characters as JSON escapes
+static std::string listing_escape(const std::string& key) {
+    std::string s;
+    for (unsigned char ch : key) {
+        if (ch == '\\') s += "\\\\";
+        else if (ch == '\t') s += "\\t";
+        else if (ch == '\n') s += "\\n";
+        else if (ch < 0x20 || ch == 0x7f) { char b[8]; std::snprintf(b, sizeof b, "\\u%04x", ch); s += b; }
+        else s += (char)ch;
+    }
+    return s;
+}
+
+int sdmi_safetensors_list(const char* path, char* out, size_t capacity, size_t* needed) {
+    return guarded([&] {
+        if (!path || !needed) throw Error(SDMI_ERR_INVALID, "safetensors_list: null argument");
+        sdmi::SafetensorsFile f(path);
+        std::string s;
+        for (const auto& t : f.tensors()) {
+            s += listing_escape(t.key) + "\t" + t.dtype + "\t";
+            for (size_t i = 0; i < t.shape.size(); ++i) s += (i ? "," : "") + std::to_string(t.shape[i]);
+            std::string dump;
+            s += "\t" + std::to_string(t.file_offset) + "\t" + (sdmi::dump_name_of_checkpoint_key(t.key, &dump) ? dump : std::string("-")) + "\n";
+        }
+        text_out(s, out, capacity, needed, "safetensors_list");
+    });
+}
+
+int sdmi_checkpoint_key(const char* dump_name, char* out, size_t capacity, size_t* needed, int32_t* transposed) {
+    return guarded([&] {
+        if (!dump_name || !needed) throw Error(SDMI_ERR_INVALID, "checkpoint_key: null argument");
+        std::string key;
+        bool tr = false;
+        if (!sdmi::checkpoint_key(dump_name, &key, &tr)) throw Error(SDMI_ERR_INVALID, std::string("checkpoint_key: '") + dump_name + "' has no checkpoint source");
+        if (transposed) *transposed = tr ? 1 : 0;
+        text_out(key, out, capacity, needed, "checkpoint_key");
+    });
+}
+
+int sdmi_default_alphas_cumprod(float* out, int32_t n) {
+    return guarded([&] {
+        if (!out || n < 1) throw Error(SDMI_ERR_INVALID, "default_alphas_cumprod: null output or n < 1");
+        sdmi::default_alphas_cumprod(out, n);
     });
 }
 
@@ -608,6 +669,28 @@ int sdmi_op_resize(sdmi_ctx* ctx, const float* x, int32_t n, int32_t h, int32_t 
         DevIn dx(e, x, (size_t)n * 4 * h * w * sizeof(float));
         DevOut dout(e, out, (size_t)n * 4 * out_h * out_w * sizeof(float));
         e.op_resize(dx.f(), n, h, w, out_h, out_w, mode, antialias, dout.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
+int sdmi_op_unpack_tensor(sdmi_ctx* ctx, const void* raw, int32_t dtype, int32_t ndim, const int64_t* dims, int32_t transform, float* out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (!dims || ndim < 1 || ndim > 4) throw Error(SDMI_ERR_INVALID, "unpack_tensor: ndim must be 1 .. 4");
+        if (dtype < 0 || dtype > 2) throw Error(SDMI_ERR_INVALID, "unpack_tensor: dtype must be 0 (F32), 1 (F16) or 2 (BF16)");
+        size_t count = 1;
+        for (int i = 0; i < ndim; ++i) {
+            if (dims[i] < 1 || dims[i] > (int64_t)1 << 30 || count > ((size_t)1 << 34) / (size_t)dims[i]) throw Error(SDMI_ERR_INVALID, "unpack_tensor: dimensions must be positive (at most 2^34 elements)");
+            count *= (size_t)dims[i];
+        }
+        if (transform < 0 || transform > 2 || (transform == 1 && ndim != 2) || (transform == 2 && (ndim != 4 || dims[1] != 3)))
+            throw Error(SDMI_ERR_INVALID, "unpack_tensor: transform 0 (copy), 1 (a 2-D tensor transposed) or 2 (a [cout,3,kh,kw] conv padded to 4 input channels)");
+        const size_t n_out = transform == 2 ? count / 3 * 4 : count;
+        Engine::Call call(e);
+        DevIn dx(e, raw, count * (dtype == 0 ? 4 : 2));
+        DevOut dout(e, out, n_out * sizeof(float));
+        e.op_unpack_tensor(dx.buf.p, dtype, ndim, dims, transform, dout.f());
         call.finish();
         dout.fetch();
     });

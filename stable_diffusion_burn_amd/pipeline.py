@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from dataclasses import dataclass
 
 import numpy as np
@@ -38,6 +39,44 @@ def mpk_list(path) -> list:
             continue
         name, shape, off = line.split("\t")
         out.append((name, tuple(int(v) for v in shape.split(",")) if shape else (), int(off)))
+    return out
+
+
+def _text_query(fn, *args) -> str:
+    """the query-then-fill convention of the listing entry points: fn(*args, out, capacity, &needed)"""
+    need = C.c_size_t()
+    check(fn(*args, None, 0, C.byref(need)))
+    buf = C.create_string_buffer(need.value)
+    check(fn(*args, buf, need.value, C.byref(need)))
+    return buf.value.decode()
+
+
+def safetensors_list(path) -> list:
+    """[(key, dtype, shape, file offset, dump name or None)] of a .safetensors file, parsed by the C++ reader (host only, no GPU)."""
+    out = []
+    for line in _text_query(load_library().sdmi_safetensors_list, str(path).encode()).split("\n"):
+        if not line:
+            continue
+        key, dtype, shape, off, name = line.rsplit("\t", 4)
+        key = re.sub(r"\\(u[0-9a-f]{4}|.)", lambda m: {"t": "\t", "n": "\n"}.get(m.group(1), chr(int(m.group(1)[1:], 16)) if len(m.group(1)) == 5 else m.group(1)), key)
+        out.append((key, dtype, tuple(int(v) for v in shape.split(",")) if shape else (), int(off), None if name == "-" else name))
+    return out
+
+
+def checkpoint_key(name: str) -> tuple:
+    """(CompVis checkpoint key, transposed?) of a dump-tree tensor name (sdmi_checkpoint_key, host only, no GPU); SdmiError for a name without one."""
+    lib = load_library()
+    need, tr = C.c_size_t(), C.c_int32()
+    check(lib.sdmi_checkpoint_key(name.encode(), None, 0, C.byref(need), C.byref(tr)))
+    buf = C.create_string_buffer(need.value)
+    check(lib.sdmi_checkpoint_key(name.encode(), buf, need.value, C.byref(need), C.byref(tr)))
+    return buf.value.decode(), bool(tr.value)
+
+
+def default_alphas_cumprod(n: int = 1000) -> np.ndarray:
+    """The LDM schedule a checkpoint without alphas_cumprod gets (sdmi_default_alphas_cumprod, host only, no GPU)."""
+    out = np.empty(int(n), np.float32)
+    check(load_library().sdmi_default_alphas_cumprod(_fp(out), int(n)))
     return out
 
 
@@ -243,7 +282,7 @@ class MultiLoraAdapter:
             self._owner = None
 
 
-__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "img2img_timesteps", "sampler_coefs", "resize_weights", "load_lora_npz", "save_lora_npz", "LoraAdapter", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
+__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "safetensors_list", "checkpoint_key", "default_alphas_cumprod", "img2img_timesteps", "sampler_coefs", "resize_weights", "load_lora_npz", "save_lora_npz", "LoraAdapter", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
 
 
 @dataclass(frozen=True)
@@ -403,6 +442,11 @@ class StableDiffusion:
     def load_weights_mpk(self, path) -> None:
         """The reference's `burn` model type: a NamedMpkFileRecorder<FullPrecisionSettings> record (sample/main.rs:27-34)."""
         check(self._lib.sdmi_load_weights_mpk(self._ctx, str(path).encode()))
+        check(self._lib.sdmi_finalize_weights(self._ctx))
+
+    def load_weights_safetensors(self, path) -> None:
+        """An SD v1.x checkpoint in the CompVis layout, one .safetensors file (F32 / F16 / BF16), converted on the device + finalize."""
+        check(self._lib.sdmi_load_weights_safetensors(self._ctx, str(path).encode()))
         check(self._lib.sdmi_finalize_weights(self._ctx))
 
     def set_stream(self, hip_stream, enable: bool = True) -> None:
@@ -755,6 +799,23 @@ class StableDiffusion:
         return ms.value
 
     # ---- operator-level entry points (parity tests) ----------------------------------------
+    def op_unpack_tensor(self, raw, dtype: str, transform: int = 0) -> np.ndarray:
+        """The checkpoint conversion kernel on its own (sdmi_op_unpack_tensor): raw = float32, float16, or uint16 holding bf16 bits;
+        dtype "F32" | "F16" | "BF16"; transform 0 copy, 1 2-D transpose, 2 [cout,3,kh,kw] padded to 4 input channels."""
+        code = {"F32": 0, "F16": 1, "BF16": 2}[dtype]
+        raw = np.ascontiguousarray(raw, dtype={0: np.float32, 1: np.float16, 2: np.uint16}[code])
+        shape = raw.shape
+        if transform == 1:
+            out_shape = shape[::-1]
+        elif transform == 2:
+            out_shape = (shape[0], 4) + tuple(shape[2:])
+        else:
+            out_shape = shape
+        out = np.empty(out_shape, np.float32)
+        dims = (C.c_int64 * raw.ndim)(*shape)
+        check(self._lib.sdmi_op_unpack_tensor(self._ctx, raw.ctypes.data_as(C.c_void_p), code, raw.ndim, dims, int(transform), _fp(out)))
+        return out
+
     def op_resize(self, x, out_size, mode="bicubic", antialias: bool = False):
         """The resampler of the hires fix on its own (sdmi_op_resize): x [n,4,h,w] -> [n,4,out_h,out_w]."""
         x = _f32(x)
@@ -1056,7 +1117,7 @@ class MultiStableDiffusion:
             self.device_view(i).load_weights(provider, clip=clip, vae_encoder=vae_encoder)
 
     def load_weights_path(self, kind: str, path) -> None:
-        """kind = "dump" (npy tree) | "burn" (.mpk record), on every device in parallel."""
+        """kind = "dump" (npy tree) | "burn" (.mpk record) | "safetensors" (CompVis checkpoint), on every device in parallel."""
         check(self._lib.sdmi_multi_load_weights(self._m, kind.encode(), str(path).encode()))
 
     def sample_image(self, context, unconditional_context, unconditional_guidance_scale: float, n_steps: int, n_images: int,

@@ -17,6 +17,7 @@ by the reference's own exporters (tests/golden/refdump/).
 """
 from __future__ import annotations
 
+import json
 from pathlib import Path
 
 import numpy as np
@@ -144,3 +145,83 @@ def write_dump_tree(dump_dir, specs, get_tensor, alphas_cumprod, n_head: int = 8
         _save(root / "autoencoder/decoder/n_block.npy", encode_scalar(4))           # autoencoder/load.rs:139
     if any(n.startswith("autoencoder/encoder/blocks/") for n in shapes):
         _save(root / "autoencoder/encoder/n_block.npy", encode_scalar(4))           # autoencoder/load.rs:163
+
+
+# ---- .safetensors: SD v1.x checkpoints in the CompVis layout ---------------------------------------------
+# The format: 8 bytes little-endian header length, a JSON header {key: {"dtype", "shape", "data_offsets": [begin, end]}} (+ an optional
+# "__metadata__" {str: str}), then the tensors' bytes back to back; offsets are relative to the end of the header.
+
+_ST_DTYPES = {np.dtype(np.float32): "F32", np.dtype(np.float16): "F16", np.dtype(np.float64): "F64", np.dtype(np.int64): "I64",
+              np.dtype(np.int32): "I32", np.dtype(np.uint8): "U8"}
+
+
+def bf16_bits(a) -> np.ndarray:
+    """float32 -> the uint16 bit patterns of its bfloat16 rounding (to nearest, ties to even; NaN stays NaN)."""
+    a = np.ascontiguousarray(a, np.float32)
+    bits = a.view(np.uint32)
+    rounded = ((bits + np.uint32(0x7FFF) + ((bits >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
+    return np.where(np.isnan(a), np.uint16(0x7FC0), rounded).astype(np.uint16)
+
+
+def bf16_to_f32(bits) -> np.ndarray:
+    """uint16 bfloat16 bit patterns -> float32 (exact)."""
+    return (np.ascontiguousarray(bits, np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+def write_safetensors(path, tensors: dict, metadata: dict | None = None) -> None:
+    """Write {key: ndarray} as one .safetensors file, without the safetensors package.
+
+    The dtype follows the array: float32 F32, float16 F16, float64 F64, int64 I64, int32 I32, uint8 U8.  bfloat16 has no numpy type: pass
+    (uint16 array of bit patterns, "BF16") -- any (array, tag) pair stores the array's bytes under that tag.
+    """
+    header, arrays, off = {}, [], 0
+    if metadata:
+        header["__metadata__"] = {str(k): str(v) for k, v in metadata.items()}
+    for key, value in tensors.items():
+        if isinstance(value, tuple):
+            arr, tag = np.asarray(value[0]), str(value[1])
+        else:
+            arr = np.asarray(value)
+            if arr.dtype not in _ST_DTYPES:
+                raise TypeError(f"write_safetensors: '{key}' has dtype {arr.dtype}; pass (array, tag) for anything but {sorted(_ST_DTYPES.values())}")
+            tag = _ST_DTYPES[arr.dtype]
+        shape = [int(d) for d in arr.shape]
+        arr = np.ascontiguousarray(arr.astype(arr.dtype.newbyteorder("<"), copy=False)).reshape(-1)   # little-endian bytes, row-major
+        header[str(key)] = {"dtype": tag, "shape": shape, "data_offsets": [off, off + arr.nbytes]}
+        arrays.append(arr)
+        off += arr.nbytes
+    text = json.dumps(header, separators=(",", ":")).encode("utf-8")
+    text += b" " * (-len(text) % 8)
+    with open(path, "wb") as f:
+        f.write(len(text).to_bytes(8, "little"))
+        f.write(text)
+        for arr in arrays:
+            if arr.nbytes:
+                f.write(arr.view(np.uint8).data)
+
+
+def write_checkpoint_safetensors(path, specs, get_tensor, alphas_cumprod, dtype: str = "F32", key_of=None, extra: dict | None = None) -> None:
+    """Write a model in the CHECKPOINT's naming and layouts: the inverse of the loader's key map and the twin of write_dump_tree.
+
+    specs: [(dump name, shape)] from StableDiffusion.weight_specs(); get_tensor(name, shape) -> ndarray in the dump's own layout (Linear
+    [in,out], Conv [Cout,Cin,kh,kw]): a Linear weight is stored transposed back to torch's [out,in].  dtype "F32" | "F16" | "BF16" for the
+    model's tensors; alphas_cumprod stays F32 (None: the file gets none).  key_of(dump name) -> (checkpoint key, transposed?), default
+    pipeline.checkpoint_key (the C++ rules).  extra: further {key: tensor} entries, written as write_safetensors takes them.
+    """
+    if dtype not in ("F32", "F16", "BF16"):
+        raise ValueError(f"write_checkpoint_safetensors: dtype must be F32, F16 or BF16, got {dtype!r}")
+    if key_of is None:
+        from .pipeline import checkpoint_key as key_of
+    tensors = {}
+    for name, shape in specs:
+        if name == "alphas_cumprod":
+            if alphas_cumprod is not None:
+                tensors["alphas_cumprod"] = np.asarray(alphas_cumprod, np.float32)
+            continue
+        key, transposed = key_of(name)
+        a = np.asarray(get_tensor(name, shape), np.float32)
+        if transposed:
+            a = np.ascontiguousarray(a.T)
+        tensors[key] = a if dtype == "F32" else a.astype(np.float16) if dtype == "F16" else (bf16_bits(a), "BF16")
+    tensors.update(extra or {})
+    write_safetensors(path, tensors)
