@@ -1428,8 +1428,8 @@ void Engine::set_option(const std::string& key, const std::string& value) {
         f << blocks << " " << bytes << "\n";
     }
     else if (key == "cfg_share") opt_cfg_share_ = std::stoi(value);
-    else if (key == "attn_kv_splits") opt_attn_kv_splits_ = std::stoi(value);
-    else if (key == "attn_kv_prefer8") opt_attn_kv_prefer8_ = std::stoi(value);
+    else if (key == "attn_kv_splits") aopt_.attn_kv_splits = std::stoi(value);
+    else if (key == "attn_kv_prefer8") aopt_.attn_kv_prefer8 = std::stoi(value);
     else if (key == "b3_grouped") {
         if (!entries_.empty() && std::any_of(entries_.begin(), entries_.end(), [](const WeightEntry& w) { return w.set; }))
             throw Error(SDMI_ERR_STATE, "b3_grouped selects the layout the weight planes are packed in: set it before the first weight is loaded");
@@ -1440,7 +1440,7 @@ void Engine::set_option(const std::string& key, const std::string& value) {
             throw Error(SDMI_ERR_STATE, "keep_masters decides what the weight arenas hold: set it before the first weight is loaded");
         opt_keep_masters_ = std::stoi(value) != 0;
     }
-    else if (key == "attn_pack_tail") opt_attn_pack_tail_ = (value == "default") ? 3 : std::stoi(value);
+    else if (key == "attn_pack_tail") aopt_.attn_pack_tail = (value == "default") ? AttnPlanOpts().attn_pack_tail : std::stoi(value);
     else if (key == "gn32_min_wgs") opt_gn32_min_wgs_ = (opt_gn32_min_wgs_ & ~0xFFFF) | (std::stoi(value) & 0xFFFF);
     else if (key == "gn32_stats_min_wgs") opt_gn32_min_wgs_ = (opt_gn32_min_wgs_ & 0xFFFF) | ((std::stoi(value) + 1) << 16);   // the statistics pass cut differently from the apply pass (-1: the same)
     else if (key == "gn_target_wgs") gn_tune_.target_wgs = std::stoi(value);
@@ -1448,9 +1448,9 @@ void Engine::set_option(const std::string& key, const std::string& value) {
     else if (key == "gn_unroll") gn_tune_.unroll = std::stoi(value);
     else if (key == "fp8_tile") opt_fp8_tile_ = (value == "auto") ? -1 : std::stoi(value);
     else if (key == "resid_acc") opt_resid_acc_ = std::stoi(value);
-    else if (key == "attn_bf16") opt_attn_bf16_ = std::stoi(value);
-    else if (key == "attn_bf16_variant") opt_attn_bf16_variant_ = (value == "default") ? kAttnBf16VariantDefault : std::stoi(value, nullptr, 0);
-    else if (key == "attn_split") opt_attn_split_ = std::stoi(value);
+    else if (key == "attn_bf16") aopt_.attn_bf16 = std::stoi(value);
+    else if (key == "attn_bf16_variant") aopt_.attn_bf16_variant = (value == "default") ? AttnPlanOpts().attn_bf16_variant : std::stoi(value, nullptr, 0);
+    else if (key == "attn_split") aopt_.attn_split = std::stoi(value);
     else if (key == "gemm_bf16x") gopt_.gemm_bf16x = std::stoi(value);
     else if (key == "gemm_x32") gopt_.gemm_x32 = std::stoi(value);
     else if (key == "gemm_f32s") gopt_.gemm_f32s = std::stoi(value);
@@ -1750,12 +1750,15 @@ void Engine::attention(const float* q, int ldq, long long q_bs, const float* k, 
                        const float* mask, int mask_ld, int dt, void* o3, bool q_log2) {
     if (dt < 0) dt = edt();
     if (nq <= 0 || nk <= 0) throw Error(SDMI_ERR_INVALID, "attention: empty sequence");
-    if (o3 && (dt || !attn_supported_head_dim(d_head) || (n_head * d_head) % 32)) throw Error(SDMI_ERR_STATE, "attention: plane output needs a fused fp32 kernel");
+    AttnPlanIn in{};
+    in.n = n; in.n_head = n_head; in.nq = nq; in.nk = nk; in.d_head = d_head; in.bf16 = dt; in.has_mask = mask != nullptr; in.planes_out = o3 != nullptr;
+    in.rows_aligned = !((ldq | ldk | ldv | ldo) & (dt ? 7 : 3));
+    const AttnPlan plan = plan_attention(in, aopt_);   // kernel, workgroup form, key slices (attn_plan.cpp); refuses what no kernel serves
     // q_log2 (stated by the caller, Engine::q_prescaled): q arrives in log2 units (attn_bf16_q_scale: folded into the query weights at load, applied by
     // qkv_attention_dev's conversion); the bf16 kernel needs no scale, the widened fp32 kernel (attn_bf16=0) gets scale^2 = ln 2
     if (q_log2 != q_prescaled(dt, d_head)) throw Error(SDMI_ERR_STATE, "attention: the caller's statement about the query's scale does not match the storage type / head dim");
     const float scale = q_log2 ? 0.83255461115769775635f : (float)std::pow((double)d_head, -0.25);
-    if (attn_supported_head_dim(d_head)) {
+    if (plan.kernel != AttnKernel::Unfused) {
         AttnParams p{};
         p.q = q; p.k = k; p.v = v; p.o = o; p.kv_len = kv_len_dev; p.mask = mask; p.mask_ld = mask_ld;
         p.n = n; p.n_head = n_head; p.nq = nq; p.nk = nk; p.d_head = d_head;
@@ -1764,27 +1767,8 @@ void Engine::attention(const float* q, int ldq, long long q_bs, const float* k, 
         p.bf16 = dt;
         p.q_log2 = q_log2 ? 1 : 0;
         p.o3 = o3; p.ldo3 = (n_head * d_head / 32) * 192;
-        p.pack_tail = opt_attn_pack_tail_;
-        p.variant = opt_attn_bf16_variant_;
-        if (dt && mask) throw Error(SDMI_ERR_UNSUPPORTED, "attention: additive mask is fp32-only");
         const double fl = 4.0 * n * n_head * (double)nq * nk * d_head;
-        const bool on_split = !dt && opt_attn_split_ && attn_split_supported(p);
-        // Key slices (round 5; fp32, no mask): at batch 1 the 32 x 32 level's self attention is 128 workgroups and the 16 x 16 level's 64 -- most CUs idle while each
-        // workgroup walks every key.  S slices of the keys run as S x the workgroups (blockIdx.z) and a merge launch combines them in slice order.  S = what fills
-        // 256 CUs, at least two K / V tiles per slice, at most 8; option attn_kv_splits: 0 = this rule, 1 = never, S = forced.
-        int kv_splits = 1;
-        if (!dt && !mask && opt_attn_kv_splits_ != 1) {
-            const long long wgs = (long long)((nq + (on_split ? 127 : 63)) / (on_split ? 128 : 64)) * n * n_head;   // the 4-wave workgroups these sizes get
-            const int tiles = (nk + attn_f32_kv_tile(p) - 1) / attn_f32_kv_tile(p);
-            long long s_auto = wgs > 0 && wgs <= 128 ? 256 / wgs : 1;
-            s_auto = std::min<long long>(std::min<long long>(s_auto, tiles / 2), 8);
-            if (on_split && opt_attn_kv_prefer8_) {   // k_attn_split.hip: enough slices that the 8-wave form fills the chip beat fewer slices of the 4-wave form
-                const long long wgs8 = (long long)((nq + 255) / 256) * n * n_head;
-                const long long s8 = std::min<long long>(std::min<long long>(wgs8 < 256 ? (256 + wgs8 - 1) / wgs8 : 1, tiles / 2), 8);
-                if (s8 >= 2 && wgs8 * s8 >= 256) s_auto = s8;
-            }
-            kv_splits = opt_attn_kv_splits_ > 1 ? std::min(opt_attn_kv_splits_, std::max(1, tiles)) : (int)std::max<long long>(1, s_auto);
-        }
+        const int kv_splits = plan.kv_splits;
         std::unique_ptr<Buf> part_o, part_ml;
         if (kv_splits > 1) {
             part_o.reset(new Buf(this, (size_t)kv_splits * n * nq * n_head * d_head * sizeof(float)));
@@ -1793,9 +1777,9 @@ void Engine::attention(const float* q, int ldq, long long q_bs, const float* k, 
         }
         ProfScope ps(this, PC_ATTENTION, fl, 0, kv_splits > 1 ? 2 : 1);
         ps.set_tag("attention n%d nq%d nk%d h%d d%d slices=%d", n, nq, nk, n_head, d_head, kv_splits);
-        if (dt && opt_attn_bf16_ && (d_head == 40 || d_head == 80 || d_head == 160)) SDMI_HIP(launch_attention_bf16(p, stream_));
-        else if (on_split) SDMI_HIP(launch_attention_split(p, stream_));
-        else SDMI_HIP(launch_attention(p, stream_));
+        if (plan.kernel == AttnKernel::Bf16) SDMI_HIP(launch_attention_bf16(p, plan, stream_));
+        else if (plan.kernel == AttnKernel::Split) SDMI_HIP(launch_attention_split(p, plan, stream_));
+        else SDMI_HIP(launch_attention(p, plan, stream_));
         count_kernel(fl);
         if (kv_splits > 1) {
             SDMI_HIP(launch_attention_combine(p, stream_));
@@ -1803,9 +1787,6 @@ void Engine::attention(const float* q, int ldq, long long q_bs, const float* k, 
         }
         return;
     }
-    if (mask) throw Error(SDMI_ERR_UNSUPPORTED, "attention: additive mask is only supported for head dims 40/80/160");
-    if (d_head % 32) throw Error(SDMI_ERR_UNSUPPORTED, "attention: head dim must be 40/80/160 or a multiple of 32");
-    if (dt && (d_head % 64)) throw Error(SDMI_ERR_UNSUPPORTED, "bf16 attention (unfused path): head dim must be a multiple of 64");
     for (int b = 0; b < n; ++b)   // every sample's key count before the first launch
         if ((kv_len_host ? kv_len_host[b] : nk) % (dt ? 64 : 32)) throw Error(SDMI_ERR_UNSUPPORTED, "attention (unfused path): key count must be a multiple of 32 (64 for bf16)");
     for (int b = 0; b < n; ++b) {

@@ -396,7 +396,7 @@ private:
     // ONE rule for "the query arrives multiplied by attn_bf16_q_scale(d_head)": bf16 storage at the head dims the fused bf16 kernel serves.  The weight loader
     // folds the factor into the query projection by it, the fp32 -> bf16 conversions of the operator entry points apply it by it, and every attention() call
     // passes it as q_log2 -- the kernel launcher refuses a bf16 call that does not state it.
-    static bool q_prescaled(int dt, int d_head) { return dt != 0 && attn_bf16_q_is_log2(d_head); }
+    static bool q_prescaled(int dt, int d_head) { return dt != 0 && attn_bf16_head_dim(d_head); }
 
     // composite blocks
     void res_block(const ResW& w, const Act& x, Act& y, int step);
@@ -485,10 +485,7 @@ private:
                                      // measured at batch 1: GroupNorm class 21.3 -> 17.3 ms per image (profiles/r05d, r05f, r05o, r05p)
     GnTune gn_tune_;                 // launch geometry of the bf16 / MXFP8 GroupNorm passes (kernels.hpp; options gn_target_wgs, gn_max_threads, gn_unroll)
     int opt_b3_grouped_ = 1;         // precision 0: weight planes in 16-row fragment groups (1 KiB DMA pieces, sequential per group); 0 = row-major planes.  Before the weights are loaded.
-    int opt_attn_pack_tail_ = 3;     // fp32 attention (k_attn_split.hip): bit 0: d = 40's columns 32..39 as a packed k step / packed output tile; bit 1: scores in log2 units with the
-                                     // reference maximum as accumulator input and the row sum from a ones column (A/B, tests)
-    int opt_attn_kv_prefer8_ = 1;    // ... and, for k_attn_split.hip, as many slices as let its 8-wave form fill the chip (A/B switch)
-    int opt_attn_kv_splits_ = 0;     // fp32 attention: key slices + merge launch where the query-tile grid leaves CUs idle (Engine::attention): 0 = automatic, 1 = never, S = forced
+    AttnPlanOpts aopt_;              // options attn_split, attn_bf16, attn_bf16_variant, attn_pack_tail, attn_kv_splits, attn_kv_prefer8 (attn_plan.hpp)
     int opt_cfg_share_ = 1;          // sample_latent: the part of the UNet in front of the first cross attention is computed once for the two identical halves of a CFG step (unet_run)
     int opt_op_resid_ = 0;           // tests: op_conv2d / op_linear add their input as the residual (cin == cout) through the GEMM epilogue
     int opt_op_misalign_ = 0;        // tests: stage_epi starts the device copies of bias, time-embedding row and residual one element past an aligned address
@@ -559,11 +556,7 @@ private:
     // options
     int opt_resid_acc_ = 3;     // precision >= 1, large-tile kernels without split-K (ConvGemm::resid_acc): bit 0 = the residual, bit 1 = bias + time-embedding row are the accumulators'
                                 // initial value, loaded in front of the k loop; 0 = added by the epilogue (round 5)
-    int opt_attn_bf16_ = 1;     // precision = 1: 1 = bf16 matrix-core attention, 0 = bf16 storage widened onto the fp32 kernel
-    static constexpr int kAttnBf16VariantDefault = 7;
-    int opt_attn_bf16_variant_ = kAttnBf16VariantDefault;   // k_attn_bf16.hip (AttnParams::variant): bit 0 = 4-wave workgroups, two per CU; bit 1 / 2 = 64 query rows per wave (d = 40) on 8- / 4-wave workgroups; 0x100 = whatever the grid (tests)
     int opt_geglu_fuse_ = 1;    // GEGLU gate in the projection GEMM's epilogue: 0 never, 1 where there are >= 4 rounds of tiles, 2 / 3 always (256x128 / 256x256 tiles; tests)
-    int opt_attn_split_ = 1;    // precision = 0: 1 = d_head 40 / 80 attention on the bf16 matrix pipe with three-way split operands (k_attn_split.hip)
     static constexpr int kGemm3xVariantDefault = 2;
     int opt_gemm3x_variant_ = kGemm3xVariantDefault;     // k_gemm3x.hip: bit 0: DMA in one block per k tile; bit 1: scalar residual subtractions (+0.7 %); bit 2: two LDS stages on the 128-row tiles
                                      // (default three: +5..10 % on long K); bit 4: s_setprio 1 for waves 4-7 (measured: no gain)

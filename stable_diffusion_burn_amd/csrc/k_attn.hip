@@ -358,29 +358,29 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float* x, int rows, i
 }
 
 // ---- host side ------------------------------------------------------------------------------
-bool attn_supported_head_dim(int d) { return d == 40 || d == 64 || d == 80 || d == 160; }  // 64: CLIP (768 / 12)
-
 template <int D, int NW, bool HAS_MASK, bool H16>
-static hipError_t launch_attn2_d(const AttnParams& p, hipStream_t stream) {
+static hipError_t launch_attn2_d(const AttnParams& p, const AttnPlan& plan, hipStream_t stream) {
+    static_assert(Attn2Cfg<D, NW, H16>::BKV == attn_geom(AttnKernel::Flash, D)->kv_tile, "attn_plan.hpp's table and Attn2Cfg disagree");
+    static_assert(attn_geom(AttnKernel::Flash, D)->rows_per_wave == 16, "attn_plan.hpp's table and attn2_kernel's row mapping (qrow) disagree");
+    if (plan.q_rows != 16 * NW) return hipErrorInvalidValue;   // a plan made for another form
     auto k = attn2_kernel<D, NW, HAS_MASK, H16>;
     const size_t lds = Attn2Cfg<D, NW, H16>::LDS_BYTES;
     if (hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(k), (int)lds); e != hipSuccess) return e;
-    dim3 grid((p.nq + 16 * NW - 1) / (16 * NW), p.n * p.n_head, (!H16 && !HAS_MASK && p.kv_splits > 1) ? p.kv_splits : 1);
+    dim3 grid((p.nq + plan.q_rows - 1) / plan.q_rows, p.n * p.n_head, plan.kv_splits);
     hipLaunchKernelGGL(k, grid, dim3(NW * 64), lds, stream, p);
     return hipGetLastError();
 }
 
 template <int D>
-static hipError_t launch_attn2_any(const AttnParams& p, hipStream_t stream) {
-    // 8-wave workgroups once they still fill the chip (>= 1.5 workgroups per CU), else 4-wave
-    const long long wg8 = (long long)((p.nq + 127) / 128) * p.n * p.n_head;
-    const bool big = wg8 >= 384;
+static hipError_t launch_attn2_any(const AttnParams& p, const AttnPlan& plan, hipStream_t stream) {
+    if (plan.waves != 4 && plan.waves != 8) return hipErrorInvalidValue;
+    const bool big = plan.waves == 8;
     if (p.bf16) {
         if (p.mask) return hipErrorInvalidValue;  // the masked (CLIP) path is fp32 only
-        return big ? launch_attn2_d<D, 8, false, true>(p, stream) : launch_attn2_d<D, 4, false, true>(p, stream);
+        return big ? launch_attn2_d<D, 8, false, true>(p, plan, stream) : launch_attn2_d<D, 4, false, true>(p, plan, stream);
     }
-    if (p.mask) return big ? launch_attn2_d<D, 8, true, false>(p, stream) : launch_attn2_d<D, 4, true, false>(p, stream);
-    return big ? launch_attn2_d<D, 8, false, false>(p, stream) : launch_attn2_d<D, 4, false, false>(p, stream);
+    if (p.mask) return big ? launch_attn2_d<D, 8, true, false>(p, plan, stream) : launch_attn2_d<D, 4, true, false>(p, plan, stream);
+    return big ? launch_attn2_d<D, 8, false, false>(p, plan, stream) : launch_attn2_d<D, 4, false, false>(p, plan, stream);
 }
 
 // ---- merge of the key slices of a kv_splits > 1 launch (this file's fp32 kernel or k_attn_split.hip's) -----------------------------------------
@@ -448,15 +448,14 @@ hipError_t launch_attention_combine(const AttnParams& p, hipStream_t stream) {
     return hipGetLastError();
 }
 
-int attn_f32_kv_tile(const AttnParams& p) { return attn_split_supported(p) ? 64 : (p.d_head > 96 ? 32 : 64); }
-
-hipError_t launch_attention(const AttnParams& p, hipStream_t stream) {
+hipError_t launch_attention(const AttnParams& p, const AttnPlan& plan, hipStream_t stream) {
+    if (plan.kernel != AttnKernel::Flash || plan.kv_splits != (p.kv_splits > 1 ? p.kv_splits : 1)) return hipErrorInvalidValue;
     if (p.kv_splits > 1 && (p.bf16 || p.mask || !p.part_o || !p.part_ml)) return hipErrorInvalidValue;
     switch (p.d_head) {
-        case 40: return launch_attn2_any<40>(p, stream);
-        case 64: return launch_attn2_any<64>(p, stream);
-        case 80: return launch_attn2_any<80>(p, stream);
-        case 160: return launch_attn2_any<160>(p, stream);
+        case 40: return launch_attn2_any<40>(p, plan, stream);
+        case 64: return launch_attn2_any<64>(p, plan, stream);
+        case 80: return launch_attn2_any<80>(p, plan, stream);
+        case 160: return launch_attn2_any<160>(p, plan, stream);
     }
     return hipErrorInvalidValue;
 }

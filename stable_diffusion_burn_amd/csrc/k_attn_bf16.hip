@@ -377,47 +377,57 @@ __global__ __launch_bounds__(NW * 64, WPE) void attn_bf16_kernel(const AttnParam
 }
 
 template <int D, int NW, int WPE = 1, int QR = 1>
-static hipError_t launch_attn_bf16_d(const AttnParams& p, hipStream_t stream) {
+static hipError_t launch_attn_bf16_d(const AttnParams& p, const AttnPlan& plan, hipStream_t stream) {
+    static_assert(AttnBfCfg<D, NW, QR>::BKV == attn_geom(AttnKernel::Bf16, D, QR)->kv_tile, "attn_plan.hpp's table and AttnBfCfg disagree");
+    static_assert(attn_geom(AttnKernel::Bf16, D, QR)->rows_per_wave == 32 * QR, "attn_plan.hpp's table and attn_bf16_kernel's row mapping (qrow) disagree");
+    if (plan.q_rows != 32 * NW * QR) return hipErrorInvalidValue;   // a plan made for another form
     auto k = attn_bf16_kernel<D, NW, WPE, QR>;
     const size_t lds = AttnBfCfg<D, NW, QR>::LDS_BYTES;
     if (hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(k), (int)lds); e != hipSuccess) return e;
-    dim3 grid((p.nq + 32 * NW * QR - 1) / (32 * NW * QR), p.n * p.n_head);
+    dim3 grid((p.nq + plan.q_rows - 1) / plan.q_rows, p.n * p.n_head);
     hipLaunchKernelGGL(k, grid, dim3(NW * 64), lds, stream, p);
     return hipGetLastError();
 }
 
+// Round 6 forms (measured at CFG batch 16, profiles/r06d_*, r06e_*):
+//   <8, 2, 2>  d = 40, self attention: 64 query rows per wave on 8-wave workgroups -- 64 x 64: 555 -> 476 us (619 -> 721 TFLOP/s);
+//   <4, 2, 2>  d = 40, a context of at most two 64-key tiles: the same on 4-wave workgroups, two per CU -- 4096 x 77: 50.5 -> 34.6 us;
+//   <4, 2>     d = 80 (and d = 40): 4-wave workgroups, two per CU -- 1024 x 77: 23.2 -> 19.7 us; no gain on the self attentions, so short contexts only.
 template <int D>
-static hipError_t launch_attn_bf16_any(const AttnParams& p, hipStream_t stream) {
-    // widest workgroup that still gives every CU a workgroup (256 CUs)
-    const long long bh = (long long)p.n * p.n_head;
-    // Round 6 forms (AttnParams::variant; 0x100 = tests: the form whatever the grid size).  Measured at CFG batch 16 (profiles/r06d_*, r06e_*):
-    //   bit 1  d = 40, self attention: 64 query rows per wave on 8-wave workgroups -- 64 x 64: 555 -> 476 us (619 -> 721 TFLOP/s);
-    //   bit 2  d = 40, a context of at most two 64-key tiles: the same on 4-wave workgroups, two per CU -- 4096 x 77: 50.5 -> 34.6 us;
-    //   bit 0  d = 80 (and d = 40 without bits 1 / 2): 4-wave workgroups, two per CU -- 1024 x 77: 23.2 -> 19.7 us; no gain on the self attentions, so short contexts only.
-    const bool force = (p.variant & 0x100) != 0;
-    const bool short_ctx = p.nk <= 128;
-    if constexpr (D == 40) {
-        if ((p.variant & 4) && (force ? !(p.variant & 2) : (short_ctx && (long long)((p.nq + 255) / 256) * bh >= 512))) return launch_attn_bf16_d<D, 4, 2, 2>(p, stream);
-        if ((p.variant & 2) && (force || (!short_ctx && (long long)((p.nq + 511) / 512) * bh >= 256))) return launch_attn_bf16_d<D, 8, 2, 2>(p, stream);
+static hipError_t launch_attn_bf16_any(const AttnParams& p, const AttnPlan& plan, hipStream_t stream) {
+    if (plan.wpe == 2 && plan.qr == 2) {
+        if constexpr (D == 40) {
+            if (plan.waves == 4) return launch_attn_bf16_d<D, 4, 2, 2>(p, plan, stream);
+            if (plan.waves == 8) return launch_attn_bf16_d<D, 8, 2, 2>(p, plan, stream);
+        }
+        return hipErrorInvalidValue;
     }
-    if constexpr (D == 40 || D == 80) {
-        if ((p.variant & 1) && (force || (short_ctx && (long long)((p.nq + 127) / 128) * bh >= 512))) return launch_attn_bf16_d<D, 4, 2>(p, stream);
+    if (plan.wpe == 2 && plan.qr == 1) {
+        if constexpr (D == 40 || D == 80) {
+            if (plan.waves == 4) return launch_attn_bf16_d<D, 4, 2>(p, plan, stream);
+        }
+        return hipErrorInvalidValue;
     }
-    if ((long long)((p.nq + 255) / 256) * bh >= 256) return launch_attn_bf16_d<D, 8>(p, stream);
-    if ((long long)((p.nq + 127) / 128) * bh >= 256) return launch_attn_bf16_d<D, 4>(p, stream);
-    return launch_attn_bf16_d<D, 2>(p, stream);
+    if (plan.wpe != 1 || plan.qr != 1) return hipErrorInvalidValue;
+    switch (plan.waves) {
+        case 8: return launch_attn_bf16_d<D, 8>(p, plan, stream);
+        case 4: return launch_attn_bf16_d<D, 4>(p, plan, stream);
+        case 2: return launch_attn_bf16_d<D, 2>(p, plan, stream);
+    }
+    return hipErrorInvalidValue;
 }
 
 // bf16 matrix-core attention; p.bf16 must be set, no additive mask (the masked CLIP path is fp32).  q must arrive multiplied by
 // d_head^-0.5 log2(e) (kernel header); p.scale is not used.
-hipError_t launch_attention_bf16(const AttnParams& p, hipStream_t stream) {
+hipError_t launch_attention_bf16(const AttnParams& p, const AttnPlan& plan, hipStream_t stream) {
+    if (plan.kernel != AttnKernel::Bf16 || plan.kv_splits != 1 || p.kv_splits > 1) return hipErrorInvalidValue;
     if (!p.bf16 || p.mask) return hipErrorInvalidValue;
     if (!p.q_log2) return hipErrorInvalidValue;   // the kernel applies no scale: a q without attn_bf16_q_scale folded in would give a silently wrong softmax
     if ((p.ldq | p.ldk | p.ldv | p.ldo) & 7) return hipErrorInvalidValue;  // 16-byte row alignment
     switch (p.d_head) {
-        case 40: return launch_attn_bf16_any<40>(p, stream);
-        case 80: return launch_attn_bf16_any<80>(p, stream);
-        case 160: return launch_attn_bf16_any<160>(p, stream);
+        case 40: return launch_attn_bf16_any<40>(p, plan, stream);
+        case 80: return launch_attn_bf16_any<80>(p, plan, stream);
+        case 160: return launch_attn_bf16_any<160>(p, plan, stream);
     }
     return hipErrorInvalidValue;
 }

@@ -445,44 +445,45 @@ __global__ __launch_bounds__(NW * 64) void attn_split_kernel(const AttnParams p)
 }
 
 template <int D, int NW, bool PK, bool LG>
-static hipError_t launch_attn_split_d(const AttnParams& p, hipStream_t stream) {
+static hipError_t launch_attn_split_d(const AttnParams& p, const AttnPlan& plan, hipStream_t stream) {
+    static_assert(AttnSpCfg<D, NW>::BKV == attn_geom(AttnKernel::Split, D)->kv_tile, "attn_plan.hpp's table and AttnSpCfg disagree");
+    static_assert(attn_geom(AttnKernel::Split, D)->rows_per_wave == 32, "attn_plan.hpp's table and attn_split_kernel's row mapping (qrow) disagree");
+    if (plan.q_rows != 32 * NW) return hipErrorInvalidValue;   // a plan made for another form
     auto k = attn_split_kernel<D, NW, PK, LG>;
     const size_t lds = AttnSpCfg<D, NW>::LDS_BYTES;
     if (hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(k), (int)lds); e != hipSuccess) return e;
-    dim3 grid((p.nq + 32 * NW - 1) / (32 * NW), p.n * p.n_head, p.kv_splits > 1 ? p.kv_splits : 1);
+    dim3 grid((p.nq + plan.q_rows - 1) / plan.q_rows, p.n * p.n_head, plan.kv_splits);
     hipLaunchKernelGGL(k, grid, dim3(NW * 64), lds, stream, p);
     return hipGetLastError();
 }
 
+// The 8-wave form runs two waves per SIMD (the softmax of one beside the matrix instructions of the other) and splits a K / V tile with half the work per thread -- per unit
+// of work it is 1.5 x the 4-wave form (profiles/r05l: 64 x 64, one sample: 185 us on 256 4-wave workgroups, two samples 142 us on 256 8-wave workgroups).
+// Round 4's softmax (the A/B form, LG = false) has no 8-wave d = 80 instantiation: it needs 260 registers (it spilled 4).
 template <int D>
-static hipError_t launch_attn_split_any(const AttnParams& p, hipStream_t stream) {
-    // widest workgroup that still gives every CU a workgroup (256 CUs), key slices included: the 8-wave form runs two waves per SIMD (the softmax of one beside
-    // the matrix instructions of the other) and splits a K / V tile with half the work per thread -- per unit of work it is 1.5 x the 4-wave form
-    // (profiles/r05l: 64 x 64, one sample: 185 us on 256 4-wave workgroups, two samples 142 us on 256 8-wave workgroups)
-    const long long bh = (long long)p.n * p.n_head * (p.kv_splits > 1 ? p.kv_splits : 1);
-    const bool w8 = (long long)((p.nq + 255) / 256) * bh >= 256;
-    if constexpr (D == 40) {
-        if (p.pack_tail & 1) {
-            if (p.pack_tail & 2) return w8 ? launch_attn_split_d<D, 8, true, true>(p, stream) : launch_attn_split_d<D, 4, true, true>(p, stream);
-            return w8 ? launch_attn_split_d<D, 8, true, false>(p, stream) : launch_attn_split_d<D, 4, true, false>(p, stream);
+static hipError_t launch_attn_split_any(const AttnParams& p, const AttnPlan& plan, hipStream_t stream) {
+    if (plan.waves != 4 && plan.waves != 8) return hipErrorInvalidValue;
+    const bool w8 = plan.waves == 8;
+    if (plan.pk) {
+        if constexpr (D == 40) {
+            if (plan.lg) return w8 ? launch_attn_split_d<D, 8, true, true>(p, plan, stream) : launch_attn_split_d<D, 4, true, true>(p, plan, stream);
+            return w8 ? launch_attn_split_d<D, 8, true, false>(p, plan, stream) : launch_attn_split_d<D, 4, true, false>(p, plan, stream);
         }
+        return hipErrorInvalidValue;
     }
-    if (p.pack_tail & 2) return w8 ? launch_attn_split_d<D, 8, false, true>(p, stream) : launch_attn_split_d<D, 4, false, true>(p, stream);
-    // round 4's softmax (the A/B form, attn_pack_tail bit 1 = 0): its 8-wave d = 80 instantiation needs 260 registers (it spilled 4); that form runs 4-wave workgroups at d = 80
-    if constexpr (D == 80) return launch_attn_split_d<D, 4, false, false>(p, stream);
-    else return w8 ? launch_attn_split_d<D, 8, false, false>(p, stream) : launch_attn_split_d<D, 4, false, false>(p, stream);
+    if (plan.lg) return w8 ? launch_attn_split_d<D, 8, false, true>(p, plan, stream) : launch_attn_split_d<D, 4, false, true>(p, plan, stream);
+    if constexpr (D == 80) return w8 ? hipErrorInvalidValue : launch_attn_split_d<D, 4, false, false>(p, plan, stream);
+    else return w8 ? launch_attn_split_d<D, 8, false, false>(p, plan, stream) : launch_attn_split_d<D, 4, false, false>(p, plan, stream);
 }
 
-bool attn_split_supported(const AttnParams& p) {
-    return !p.bf16 && !p.mask && (p.d_head == 40 || p.d_head == 80) && !((p.ldq | p.ldk | p.ldv | p.ldo) & 3);
-}
-
-// fp32 q/k/v/o, no additive mask, d_head 40 or 80, 16-byte aligned rows (attn_split_supported)
-hipError_t launch_attention_split(const AttnParams& p, hipStream_t stream) {
-    if (!attn_split_supported(p)) return hipErrorInvalidValue;
+// fp32 q/k/v/o, no additive mask, d_head 40 or 80, 16-byte aligned rows
+hipError_t launch_attention_split(const AttnParams& p, const AttnPlan& plan, hipStream_t stream) {
+    if (plan.kernel != AttnKernel::Split || plan.kv_splits != (p.kv_splits > 1 ? p.kv_splits : 1)) return hipErrorInvalidValue;
+    if (p.bf16 || p.mask || ((p.ldq | p.ldk | p.ldv | p.ldo) & 3)) return hipErrorInvalidValue;
     if (p.kv_splits > 1 && (!p.part_o || !p.part_ml)) return hipErrorInvalidValue;
-    if (p.d_head == 40) return launch_attn_split_any<40>(p, stream);
-    return launch_attn_split_any<80>(p, stream);
+    if (p.d_head == 40) return launch_attn_split_any<40>(p, plan, stream);
+    if (p.d_head == 80) return launch_attn_split_any<80>(p, plan, stream);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace sdmi

@@ -10,6 +10,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "attn_plan.hpp"
 #include "gemm_tiles.hpp"
 
 namespace sdmi {
@@ -143,27 +144,23 @@ struct AttnParams {
     // fp32 kernels, no mask (round 5): kv_splits = S > 1 -> blockIdx.z = key slice: workgroup z walks K / V tiles [z T / S, (z + 1) T / S) and writes its
     // UNNORMALISED output rows + (running maximum in log2 units, row sum) instead of o / o3; launch_attention_combine merges the S slices in slice order.  For the
     // batch-1 levels whose (query tile x head) grid leaves most CUs without a workgroup (32 x 32: 128 workgroups, 16 x 16: 64).
-    int kv_splits;
+    int kv_splits;                      // = AttnPlan::kv_splits
     float* part_o;                      // [S][n][nq][n_head * d_head]
     float* part_ml;                     // [S][n][n_head][nq][2]
-    int variant;                        // k_attn_bf16.hip (option attn_bf16_variant): bit 0 = 4-wave workgroups, TWO per CU (independent barriers: the two waves of a SIMD drift out of phase)
-    int pack_tail;                      // k_attn_split.hip, d = 40: the packed form of the head's last 8 columns (kernel header); 0 = the six-instruction form (A/B, tests)
 };
-bool attn_supported_head_dim(int d);
-hipError_t launch_attention(const AttnParams& p, hipStream_t stream);
-// fp32 q/k/v/o on the bf16 matrix pipe, three-way split operands (k_attn_split.hip): d_head 40 / 80, no additive mask
-bool attn_split_supported(const AttnParams& p);
-hipError_t launch_attention_split(const AttnParams& p, hipStream_t stream);
+// The three fused kernels.  Which one runs, its workgroup form and the slice count are decided by plan_attention (attn_plan.hpp): a launcher only maps
+// (d_head, plan.waves, form flags) to the template instantiation, takes the grid from plan.q_rows and plan.kv_splits, and keeps the argument checks the kernel's
+// safety rests on.  A plan for another kernel, or one that names no instantiated form, is hipErrorInvalidValue.
+// k_attn.hip: fp32 matrix instructions, fp32 or (widened) bf16 storage, additive mask in fp32
+hipError_t launch_attention(const AttnParams& p, const AttnPlan& plan, hipStream_t stream);
+// k_attn_split.hip: fp32 q/k/v/o on the bf16 matrix pipe, three-way split operands: d_head 40 / 80, no additive mask, 16-byte aligned rows
+hipError_t launch_attention_split(const AttnParams& p, const AttnPlan& plan, hipStream_t stream);
 // merges the key slices of a kv_splits > 1 launch (either fp32 kernel) into p.o / p.o3
 hipError_t launch_attention_combine(const AttnParams& p, hipStream_t stream);
-// K / V tile (keys per loop iteration) of the fp32 kernel that would run p: the unit kv_splits cuts
-int attn_f32_kv_tile(const AttnParams& p);
-// bf16 matrix-core kernel (k_attn_bf16.hip): p.bf16 set, no additive mask; q must arrive multiplied by attn_bf16_q_scale(d_head)
-// (the engine folds it into the query projection's weight at load) and the caller must say so (p.q_log2, else hipErrorInvalidValue); p.scale is not used
+// k_attn_bf16.hip: p.bf16 set, no additive mask; q must arrive multiplied by attn_bf16_q_scale(d_head) (the engine folds it into the query projection's
+// weight at load: Engine::q_prescaled) and the caller must say so (p.q_log2, else hipErrorInvalidValue); p.scale is not used
 inline float attn_bf16_q_scale(int d_head) { return (float)(1.4426950408889634 / __builtin_sqrt((double)d_head)); }
-// the head dims whose bf16 q tensors follow that convention (the fused bf16 kernel's; every other head dim keeps the reference's scale in the kernel)
-inline bool attn_bf16_q_is_log2(int d_head) { return d_head == 40 || d_head == 80 || d_head == 160; }
-hipError_t launch_attention_bf16(const AttnParams& p, hipStream_t stream);
+hipError_t launch_attention_bf16(const AttnParams& p, const AttnPlan& plan, hipStream_t stream);
 // row softmax (in place) for the unfused single-head VAE attention: x[rows][cols] *= scale first
 hipError_t launch_softmax_rows(float* x, int rows, int cols, float scale, hipStream_t stream);
 

@@ -1,0 +1,195 @@
+// attn_plan_main.cpp -- replays the attention planner (csrc/attn_plan.cpp, host-only) over a fixed list of cases and compares what it
+// decides with tests/golden/attn_plan_choices.txt, line by line.  Built by tests/test_attn_plan_cpu.py with plain g++ (no HIP).
+//
+//   attn_plan <fixture>      exit 0 when every line is reproduced, 1 with the first differing lines otherwise
+//   attn_plan                prints the lines (how the fixture was written -- by the code BEFORE the planner was restructured)
+//
+// One line per (storage, d, n, heads, nq, nk), one token per option variant in the order of variants() below; equal neighbours are
+// folded into "token*count".  A token is
+//   F<waves>                k_attn.hip
+//   S<waves>[p][l]          k_attn_split.hip, template flags PK / LG
+//   B<waves>[.<wpe>.<qr>]   k_attn_bf16.hip (.1.1 left out)
+//   U                       the unfused path
+// followed by /<slices> when there is more than one key slice, or E<status> for an sdmi::Error.  The "# geometry" section lists query
+// rows per workgroup and keys per tile of every (kernel, d, waves, qr) that occurred.  The fixture holds results only, so the
+// enumeration below must not change unless the fixture is regenerated from a trusted planner.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <map>
+#include <set>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "../../stable_diffusion_burn_amd/csrc/attn_plan.hpp"
+#include "../../stable_diffusion_burn_amd/csrc/error.hpp"
+
+using namespace sdmi;
+
+static std::set<std::string> g_forms;                // every instantiation / slice rule that occurred: condition (b)
+static std::map<std::string, std::string> g_geom;    // (kernel, d, waves, qr) -> "q_rows kv_tile"
+static int g_refused = 0;                            // condition (a)
+
+static std::vector<AttnPlanOpts> variants(bool bf16) {
+    std::vector<AttnPlanOpts> v;
+    if (!bf16) {
+        for (int split : {1, 0})
+            for (int kv : {0, 1, 2, 8, 1000})
+                for (int p8 : {1, 0})
+                    for (int pack : {3, 2, 1, 0}) {
+                        AttnPlanOpts o;
+                        o.attn_split = split; o.attn_kv_splits = kv; o.attn_kv_prefer8 = p8; o.attn_pack_tail = pack;
+                        v.push_back(o);
+                    }
+    } else {
+        for (int on : {1, 0})
+            for (int var : {7, 0, 1, 2, 4, 6, 0x101, 0x102, 0x104, 0x106}) {
+                AttnPlanOpts o;
+                o.attn_bf16 = on; o.attn_bf16_variant = var;
+                v.push_back(o);
+            }
+    }
+    return v;
+}
+
+static std::string run(const AttnPlanIn& in, const AttnPlanOpts& o) {
+    try {
+        const AttnPlan a = plan_attention(in, o);
+        const std::string where = in.bf16 ? "bf16" : in.has_mask ? "f32 mask" : "f32";
+        const std::string d = " d" + std::to_string(in.d_head), w = std::to_string(a.waves);
+        std::string t;
+        switch (a.kernel) {
+            case AttnKernel::Unfused: return "U";
+            case AttnKernel::Flash: t = "F" + w; break;
+            case AttnKernel::Split: t = "S" + w + (a.pk ? "p" : "") + (a.lg ? "l" : ""); break;
+            case AttnKernel::Bf16: t = "B" + w + (a.wpe == 1 && a.qr == 1 ? "" : "." + std::to_string(a.wpe) + "." + std::to_string(a.qr)); break;
+        }
+        g_forms.insert(t + d + " " + where);
+        const std::string key = t.substr(0, 1) + d + " w" + w + " qr" + std::to_string(a.qr);
+        const std::string geom = std::to_string(a.q_rows) + " " + std::to_string(a.kv_tile);
+        if (g_geom.count(key) && g_geom[key] != geom) return "BAD";
+        g_geom[key] = geom;
+        if (!in.bf16 && !in.has_mask && o.attn_kv_splits == 0 && (a.kv_splits == 1 || a.kv_splits == 4 || a.kv_splits == 8))   // the automatic slice counts the model reaches
+            g_forms.insert("auto" + std::to_string(a.kv_splits) + (a.kv_splits != 8 ? "" : o.attn_kv_prefer8 ? " prefer8=1" : " prefer8=0"));
+        if (a.kv_splits > 1) t += "/" + std::to_string(a.kv_splits);
+        return t;
+    } catch (const Error& e) {
+        ++g_refused;
+        return "E" + std::to_string(e.status);
+    }
+}
+
+static AttnPlanIn make_in(bool bf16, int d, int n, int heads, int nq, int nk, bool mask = false, bool planes = false, bool aligned = true) {
+    AttnPlanIn p{};
+    p.n = n; p.n_head = heads; p.nq = nq; p.nk = nk; p.d_head = d; p.bf16 = bf16; p.has_mask = mask; p.planes_out = planes; p.rows_aligned = aligned;
+    return p;
+}
+
+static void line(std::ostream& os, const AttnPlanIn& in, const char* note = "") {
+    os << (in.bf16 ? "bf16" : "f32") << note << " d" << in.d_head << " n" << in.n << " h" << in.n_head << " q" << in.nq << " k" << in.nk << ":";
+    std::string prev;
+    int count = 0;
+    auto flush = [&] {
+        if (!count) return;
+        os << " " << prev;
+        if (count > 1) os << "*" << count;
+    };
+    for (const AttnPlanOpts& o : variants(in.bf16 != 0)) {
+        const std::string t = run(in, o);
+        if (t == prev) { ++count; continue; }
+        flush();
+        prev = t; count = 1;
+    }
+    flush();
+    os << "\n";
+}
+
+int main(int argc, char** argv) {
+    std::ostringstream os;
+    os << "# written by the planner's first form, Engine::attention's and the launchers' rules moved out verbatim; never regenerated since\n";
+    for (int bf16 = 0; bf16 < 2; ++bf16) {
+        os << (bf16 ? "# grid bf16\n" : "# grid fp32\n");
+        for (int d : {40, 64, 80, 160})
+            for (int n : {1, 2, 4, 16})
+                for (int heads : {1, 8})
+                    for (int nq : {64, 256, 1024, 2085, 4096})
+                        for (int nk : {77, 128, 129, nq}) line(os, make_in(bf16 != 0, d, n, heads, nq, nk));
+    }
+    os << "# masked fp32\n";
+    line(os, make_in(false, 64, 1, 12, 77, 77, true));   // CLIP
+    for (int d : {40, 64, 80, 160}) {
+        line(os, make_in(false, d, 2, 8, 64, 77, true));
+        line(os, make_in(false, d, 2, 8, 4096, 77, true));
+        line(os, make_in(false, d, 16, 8, 1024, 1024, true));
+    }
+    os << "# planes out\n";
+    for (int d : {40, 64, 80, 160})
+        for (int n : {1, 2})
+            for (int nq : {64, 1024, 4096})
+                for (int nk : {77, nq}) line(os, make_in(false, d, n, 8, nq, nk, false, true));
+    line(os, make_in(false, 40, 1, 4, 1024, 1024, false, true));
+    os << "# row strides not 16-byte aligned\n";
+    for (int bf16 = 0; bf16 < 2; ++bf16)
+        for (int d : {40, 80})
+            for (int nq : {64, 4096}) line(os, make_in(bf16 != 0, d, 2, 8, nq, nq, false, false, false), " unaligned");
+    os << "# unfused\n";
+    for (int bf16 = 0; bf16 < 2; ++bf16)
+        for (int n : {1, 2})
+            for (int nq : {1024, 4096}) line(os, make_in(bf16 != 0, 512, n, 1, nq, nq));
+    if (g_refused) { std::fprintf(stderr, "%d cases of the grid were refused\n", g_refused); return 2; }   // (a)
+
+    os << "# refusals\n";
+    line(os, make_in(true, 40, 2, 8, 1024, 77, true), " mask");
+    line(os, make_in(true, 64, 1, 12, 77, 77, true), " mask");
+    line(os, make_in(false, 48, 2, 8, 1024, 1024));
+    line(os, make_in(true, 48, 2, 8, 1024, 1024));
+    line(os, make_in(false, 512, 1, 1, 1024, 1024, true), " mask");
+    line(os, make_in(true, 96, 1, 1, 1024, 1024));
+    line(os, make_in(true, 40, 2, 8, 1024, 1024, false, true), " planes");
+    line(os, make_in(false, 40, 2, 1, 1024, 1024, false, true), " planes");
+    line(os, make_in(false, 80, 2, 1, 1024, 77, false, true), " planes");
+    line(os, make_in(false, 512, 1, 1, 1024, 1024, false, true), " planes");
+    line(os, make_in(true, 512, 1, 1, 1024, 1024, false, true), " planes");
+
+    os << "# geometry: kernel, d, waves, query blocks per wave: query rows per workgroup, keys per tile\n";
+    for (auto& kv : g_geom) os << kv.first << ": " << kv.second << "\n";
+
+    // (b) every instantiated kernel and every automatic slice count occurs
+    std::vector<std::string> need = {"auto1", "auto4", "auto8 prefer8=1", "auto8 prefer8=0"};
+    for (int d : {40, 64, 80, 160})
+        for (const char* w : {"F4", "F8"})
+            for (const char* where : {"f32", "f32 mask", "bf16"}) need.push_back(std::string(w) + " d" + std::to_string(d) + " " + where);
+    for (const char* f : {"S4", "S4p", "S4l", "S4pl", "S8", "S8p", "S8l", "S8pl"}) need.push_back(std::string(f) + " d40 f32");
+    for (const char* f : {"S4", "S4l", "S8l"}) need.push_back(std::string(f) + " d80 f32");
+    for (int d : {40, 80, 160})
+        for (const char* f : {"B2", "B4", "B8"}) need.push_back(std::string(f) + " d" + std::to_string(d) + " bf16");
+    for (const char* f : {"B4.2.2 d40", "B8.2.2 d40", "B4.2.1 d40", "B4.2.1 d80"}) need.push_back(std::string(f) + " bf16");
+    int missing = 0;
+    for (const std::string& f : need)
+        if (!g_forms.count(f)) { std::fprintf(stderr, "form never planned: %s\n", f.c_str()); ++missing; }
+    if (missing || need.size() != g_forms.size()) {
+        for (const std::string& f : g_forms)
+            if (std::find(need.begin(), need.end(), f) == need.end()) std::fprintf(stderr, "form without an instantiation: %s\n", f.c_str());
+        return 2;
+    }
+
+    const std::string got = os.str();
+    if (argc < 2) { std::fputs(got.c_str(), stdout); return 0; }
+    std::ifstream f(argv[1]);
+    if (!f) { std::fprintf(stderr, "cannot read %s\n", argv[1]); return 2; }
+    std::istringstream g(got);
+    std::string a, b;
+    int ln = 0, bad = 0;
+    for (;;) {
+        const bool ha = (bool)std::getline(f, a), hb = (bool)std::getline(g, b);
+        if (!ha && !hb) break;
+        ++ln;
+        if (ha != hb || a != b) {
+            if (++bad <= 5) std::fprintf(stderr, "line %d differs:\n  fixture: %s\n  planner: %s\n", ln, ha ? a.c_str() : "<end>", hb ? b.c_str() : "<end>");
+        }
+    }
+    std::printf("%d lines, %d differ\n", ln, bad);
+    return bad ? 1 : 0;
+}
