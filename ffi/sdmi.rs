@@ -71,6 +71,8 @@ extern "C" {
     fn sdmi_checkpoint_key(dump_name: *const c_char, out: *mut c_char, capacity: usize, needed: *mut usize, transposed: *mut i32) -> c_int;
     fn sdmi_default_alphas_cumprod(out: *mut c_float, n: i32) -> c_int;
     fn sdmi_op_unpack_tensor(ctx: *mut c_void, raw: *const c_void, dtype: i32, ndim: i32, dims: *const i64, transform: i32, out: *mut c_float) -> c_int;
+    fn sdmi_op_conv2d_pair(ctx: *mut c_void, x: *const c_float, h: *const c_float, w_skip: *const c_float, b_skip: *const c_float, w_out: *const c_float,
+                           b_out: *const c_float, n: i32, cin_x: i32, cout: i32, hh: i32, ww: i32, out: *mut c_float, out_planes: *mut c_float) -> c_int;
     fn sdmi_finalize_weights(ctx: *mut c_void) -> c_int;
     fn sdmi_set_option(ctx: *mut c_void, key: *const c_char, value: *const c_char) -> c_int;
     fn sdmi_create_multi(out: *mut *mut c_void, cfg: *const SdmiConfig, devices: *const i32, n_devices: i32) -> c_int;
@@ -406,6 +408,20 @@ impl StableDiffusionMi355 {
         if count <= 0 || raw.len() != count as usize * if dtype == 0 { 4 } else { 2 } { return Err("op_unpack_tensor: raw does not match dims".into()); }
         let mut out = vec![0f32; if transform == 2 { count as usize / 3 * 4 } else { count as usize }];
         let st = unsafe { sdmi_op_unpack_tensor(self.ctx, raw.as_ptr() as *const c_void, dtype, dims.len() as i32, dims.as_ptr(), transform, out.as_mut_ptr()) };
+        if st != 0 { Err(last_error().into()) } else { Ok(out) }
+    }
+
+    /// The tail of a ResBlock with a 1x1 shortcut (`sdmi_op_conv2d_pair`): `conv3x3(h, w_out) + b_out + conv1x1(x, w_skip) + b_skip`, NCHW, `[n, cout, hh, ww]`.
+    /// Option `skip_slices` = 1: one split-K launch carrying the shortcut on extra K slices; 0: two launches.
+    #[allow(clippy::too_many_arguments)]
+    pub fn op_conv2d_pair(&self, x: &[f32], h: &[f32], w_skip: &[f32], b_skip: &[f32], w_out: &[f32], b_out: &[f32], n: i32, cin_x: i32, cout: i32, hh: i32,
+                          ww: i32) -> Result<Vec<f32>, Box<dyn Error>> {
+        let px = (n * hh * ww) as usize;
+        if x.len() != px * cin_x as usize || h.len() != px * cout as usize || w_skip.len() != (cout * cin_x) as usize || w_out.len() != (cout * cout * 9) as usize
+            || b_skip.len() != cout as usize || b_out.len() != cout as usize { return Err("op_conv2d_pair: slices do not match the dims".into()); }
+        let mut out = vec![0f32; px * cout as usize];
+        let st = unsafe { sdmi_op_conv2d_pair(self.ctx, x.as_ptr(), h.as_ptr(), w_skip.as_ptr(), b_skip.as_ptr(), w_out.as_ptr(), b_out.as_ptr(), n, cin_x, cout, hh, ww,
+                                              out.as_mut_ptr(), std::ptr::null_mut()) };
         if st != 0 { Err(last_error().into()) } else { Ok(out) }
     }
 

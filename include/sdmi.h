@@ -479,6 +479,14 @@ int sdmi_op_linear(sdmi_ctx* ctx, const float* x, const float* weight, const flo
 int sdmi_op_conv2d_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, const float* temb,
                             int32_t temb_stride, const float* resid, int32_t resid_ld, int32_t n, int32_t cin, int32_t h,
                             int32_t w, int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t upsample2x, float* out);
+/* The tail of a ResBlock whose shortcut is a 1x1 convolution (no reference counterpart; for tests; precision 0 only, cin_x and cout multiples of 32):
+ * out = conv3x3(h, w_out, pad 1) + b_out + conv1x1(x, w_skip) + b_skip.  x [n,cin_x,hh,ww], h [n,cout,hh,ww], w_skip [cout,cin_x,1,1], w_out [cout,cout,3,3],
+ * biases [cout] or NULL, out [n,cout,hh,ww].  Both inputs reach the engine as bf16 planes, as in the model.  Option skip_slices = 1: ONE split-K launch whose extra
+ * K slices compute the shortcut, plus its reduce (an error where that form does not apply); 0: the shortcut's launch, then conv_out with it as the residual.
+ * Options gemm_tile / splitk / splitk_aux force the tile and request the (main, auxiliary) slice counts.  out_planes (NULL: none) receives the result the same
+ * launch wrote as bf16 planes, joined back to fp32. */
+int sdmi_op_conv2d_pair(sdmi_ctx* ctx, const float* x, const float* h, const float* w_skip, const float* b_skip, const float* w_out,
+                        const float* b_out, int32_t n, int32_t cin_x, int32_t cout, int32_t hh, int32_t ww, float* out, float* out_planes);
 /* sdmi_op_linear + resid [rows,cout] (NULL: none), kept as rows resid_ld (0: cout) elements apart like sdmi_op_conv2d_epilogue's. */
 int sdmi_op_linear_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, const float* resid,
                             int32_t resid_ld, int32_t rows, int32_t cin, int32_t cout, float* out);

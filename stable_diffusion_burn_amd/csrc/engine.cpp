@@ -690,18 +690,21 @@ Engine::TempSplit::TempSplit(Engine* e_, const float* bt_, long long rows, long 
     planes = e->pool_.alloc((size_t)rows * K * 6);
     hipError_t err = launch_pack_split3(bt, planes, rows, (int)K, e->stream_, e->b3_grouped(rows));
     if (err != hipSuccess) { e->pool_.free(planes); planes = nullptr; SDMI_HIP(err); }
-    e->temp_split_bt_ = bt;
-    e->temp_split_planes_ = planes;
+    const int slot = e->temp_split_bt_[0] ? 1 : 0;   // (two at a time: op_conv2d_pair's weights)
+    e->temp_split_bt_[slot] = bt;
+    e->temp_split_planes_[slot] = planes;
 }
 Engine::TempSplit::~TempSplit() {
     if (!planes) return;
-    e->temp_split_bt_ = nullptr;
-    e->temp_split_planes_ = nullptr;
+    const int slot = e->temp_split_planes_[0] == planes ? 0 : 1;
+    e->temp_split_bt_[slot] = nullptr;
+    e->temp_split_planes_[slot] = nullptr;
     e->pool_.free(planes);
 }
 
 const void* Engine::split_planes(const float* bt) const {
-    if (bt && bt == temp_split_bt_) return temp_split_planes_;
+    for (int slot = 0; slot < 2; ++slot)
+        if (bt && bt == temp_split_bt_[slot]) return temp_split_planes_[slot];
     const char* b = reinterpret_cast<const char*>(bt);
     for (int g = 0; g < 3; ++g)
         if (split_base_[g] && b >= arena_base_[g] && b < arena_base_[g] + arena_bytes_[g]) return split_base_[g] + (size_t)(b - arena_base_[g]) / 2 * 3;
@@ -1400,6 +1403,8 @@ void Engine::abort_call() noexcept {
 void Engine::set_option(const std::string& key, const std::string& value) {
     if (key == "gemm_tile") gopt_.force_tile = (value == "auto") ? -1 : std::stoi(value);
     else if (key == "splitk") gopt_.force_splits = std::stoi(value);
+    else if (key == "splitk_aux") opt_splitk_aux_ = std::stoi(value);
+    else if (key == "skip_slices") opt_skip_slices_ = std::stoi(value);
     else if (key == "roctx") roctx_enable(std::stoi(value) != 0);
     else if (key == "fp8_convs") opt_fp8_convs_ = std::stoi(value);
     else if (key == "fp8_min_rows") opt_fp8_min_rows_ = std::stoi(value);
@@ -1529,6 +1534,24 @@ void Engine::run_gemm(ConvGemm& p, const GemmRun& r) {
     count_kernel();
 }
 
+// what the planner (gemm_plan.hpp) is told about a launch; p.kt_total, p.Bt3 and the shape are set
+GemmPlanIn Engine::gemm_plan_in(const ConvGemm& p, int in_dt, int force_cfg, int force_splits) const {
+    GemmPlanIn in{};
+    in.M = p.M; in.N = p.N; in.K = p.K; in.kt_total = p.kt_total; in.bf16 = in_dt; in.geglu = p.geglu; in.out_mode = p.out_mode; in.force_cfg = force_cfg; in.force_splits = force_splits;
+    in.KH = p.KH; in.KW = p.KW; in.stride = p.stride; in.pad = p.pad; in.ups = p.ups; in.Cin = p.Cin; in.Hs = p.Hs; in.Ws = p.Ws; in.Ho = p.Ho; in.Wo = p.Wo;
+    in.zero_page = zero_page_ != nullptr;
+    in.x32_ok = !in_dt && p.CS == 32 && p.Cin % 32 == 0 && p.out_mode == 0;   // what k_gemm2x.hip handles
+    // k_gemm3x.hip: the same layers, when the weight has its bf16 planes (weights in the arenas; not e.g. the K / V operands of
+    // the unfused VAE attention) and the 32-bit piece offsets reach
+    in.s_ok = in.x32_ok && p.Bt3 && (unsigned long long)p.N * (p.geglu ? 2 : 1) * (unsigned long long)p.kt_total * 192ull < 0xFFFFFF00ull;
+    // k_gemm3p.hip: the same layers with the activations as planes too -- written by their producer (p.A3) or, for a tensor that
+    // arrives as fp32, by split3_rows_kernel right here
+    in.p_ok = in.s_ok && (unsigned long long)p.NB * p.Hs * p.Ws * (unsigned long long)(p.A3 ? p.a3_ld : p.Cin * 6) < 0xFFFFFF00ull;
+    // the activations arrive as planes (their producer wrote them): the GEMM runs on a plane tile -- from the plane table or the cost model
+    in.from_planes = !in_dt && p.A3 != nullptr;
+    return in;
+}
+
 // Which tile and how many K slices: plan_gemm (gemm_plan.cpp).  Here: the facts it plans from, the temporary buffers, the launch.
 void Engine::launch_gemm(ConvGemm& p, int in_dt, int force_cfg, int force_splits) {
     const int kt_elems = in_dt ? 64 : 32;  // a k tile is 128 bytes of K per row in both storage types
@@ -1544,19 +1567,7 @@ void Engine::launch_gemm(ConvGemm& p, int in_dt, int force_cfg, int force_splits
     p.variant = in_dt ? opt_gemm_bf16x_variant_ : opt_gemm3x_variant_;
     p.zero_page = zero_page_;
     p.probe = probe_buf_;
-    GemmPlanIn in{};
-    in.M = p.M; in.N = p.N; in.K = p.K; in.kt_total = p.kt_total; in.bf16 = in_dt; in.geglu = p.geglu; in.out_mode = p.out_mode; in.force_cfg = force_cfg; in.force_splits = force_splits;
-    in.KH = p.KH; in.KW = p.KW; in.stride = p.stride; in.pad = p.pad; in.ups = p.ups; in.Cin = p.Cin; in.Hs = p.Hs; in.Ws = p.Ws; in.Ho = p.Ho; in.Wo = p.Wo;
-    in.zero_page = zero_page_ != nullptr;
-    in.x32_ok = !in_dt && p.CS == 32 && p.Cin % 32 == 0 && p.out_mode == 0;   // what k_gemm2x.hip handles
-    // k_gemm3x.hip: the same layers, when the weight has its bf16 planes (weights in the arenas; not e.g. the K / V operands of
-    // the unfused VAE attention) and the 32-bit piece offsets reach
-    in.s_ok = in.x32_ok && p.Bt3 && (unsigned long long)p.N * (p.geglu ? 2 : 1) * (unsigned long long)p.kt_total * 192ull < 0xFFFFFF00ull;
-    // k_gemm3p.hip: the same layers with the activations as planes too -- written by their producer (p.A3) or, for a tensor that
-    // arrives as fp32, by split3_rows_kernel right here
-    in.p_ok = in.s_ok && (unsigned long long)p.NB * p.Hs * p.Ws * (unsigned long long)(p.A3 ? p.a3_ld : p.Cin * 6) < 0xFFFFFF00ull;
-    // the activations arrive as planes (their producer wrote them): the GEMM runs on a plane tile -- from the plane table or the cost model
-    in.from_planes = !in_dt && p.A3 != nullptr;
+    const GemmPlanIn in = gemm_plan_in(p, in_dt, force_cfg, force_splits);
     if (!in.from_planes && !p.A) throw Error(SDMI_ERR_STATE, "gemm: no activations");
     const GemmPlan g = plan_gemm(in, gopt_, tuning_);
     p.kt_per_split = g.kt_per_split; p.splits = g.splits;
@@ -1642,6 +1653,61 @@ void Engine::conv(const ConvW& w, const Act& x, Act& y, int stride, int ups, con
     p.out_mode = x.dt ? (y.dt ? 0 : 1) : (y.dt ? 2 : 0);
     if (resid && !x.dt && y.dt) throw Error(SDMI_ERR_STATE, "conv: residual not supported on the fp32->bf16 layers");
     launch_gemm(p, x.dt);
+}
+
+// y = conv3x3(h, w_out) + conv1x1(x, w_skip) as ONE split-K plane launch + its reduce: the 1x1 shortcut of a ResBlock runs on extra K slices of conv_out's grid
+// (ConvGemm::z_aux) and the reduce sums all slabs and adds both biases.  Against the two-launch path the shortcut's GEMM launch, its reduce where it is split and the
+// write + read of its result as conv_out's residual are gone, and its matrix work joins a k loop that already runs.  Returns false -- nothing launched, the caller
+// runs the two launches -- when the layers, the buffers or the planner (plan_gemm_pair: "do not pair") do not allow it.
+bool Engine::conv_pair(const ConvW& w_out, const Act& h, const ConvW& w_skip, const Act& x, Act& y) {
+    if (bf16_ || h.dt || x.dt || y.dt || w_out.dt || w_skip.dt || w_out.k != 3 || w_skip.k != 1 || probe_buf_) return false;
+    if (h.c != w_out.cin || x.c != w_skip.cin || w_out.cout != w_skip.cout || y.c != w_out.cout) return false;
+    if (h.n != x.n || h.h != x.h || h.w != x.w || y.n != h.n || y.h != h.h || y.w != h.w) return false;
+    if (!plane_gemm(w_out.cin, w_out.cout) || !plane_gemm(w_skip.cin, w_skip.cout) || !h.p3 || !x.p3 || (!y.p && !y.p3)) return false;
+    if (gopt_.force_splits > 0 && opt_splitk_aux_ <= 0) return false;   // option splitk alone forces the slices of ordinary launches: those run
+    ConvGemm p{};
+    p.Bt = w_out.bt; p.bias = w_out.bias; p.bias_aux = w_skip.bias;
+    p.Bt3 = split_planes(w_out.bt); p.Bt3_aux = split_planes(w_skip.bt);
+    if (!p.Bt3 || !p.Bt3_aux) return false;
+    p.A3 = h.p3; p.a3_ld = h.ld3; p.A3_aux = x.p3; p.a3_ld_aux = x.ld3;
+    p.C = y.p; p.C3 = y.p3; p.ldc3 = y.ld3;
+    p.M = (int)h.rows(); p.N = w_out.cout; p.K = w_out.cin * 9;
+    p.NB = h.n; p.Hs = h.h; p.Ws = h.w; p.Cin = w_out.cin; p.Ho = h.h; p.Wo = h.w;
+    p.KH = 3; p.KW = 3; p.stride = 1; p.pad = 1; p.ups = 0;
+    p.ldc = y.p ? y.stride() : p.N; p.ldr = p.ldc; p.a_ld = h.stride(); p.b_ld = p.K; p.CS = 32;
+    p.kt_total = p.K / 32; p.Cin_aux = w_skip.cin; p.kt_total_aux = w_skip.cin / 32;
+    p.b3_grouped = b3_grouped(p.N) ? 1 : 0;
+    p.variant = opt_gemm3x_variant_;
+    p.zero_page = zero_page_;
+    // the output conditions of launch_gemm's native plane output, on the reduce's 16-byte path (the only one that writes planes or adds two biases at once)
+    if (!splitk_reduce_vec(p, false) || ((uintptr_t)p.bias_aux & 15) || (p.C3 && (p.N % 32 || p.ldc3 % 192))) return false;
+    const GemmPlanIn in = gemm_plan_in(p, 0, -1, 0);
+    if (!in.p_ok) return false;
+    if ((unsigned long long)p.N * (unsigned long long)p.kt_total_aux * 192ull >= 0xFFFFFF00ull || (unsigned long long)p.NB * p.Hs * p.Ws * (unsigned long long)p.a3_ld_aux >= 0xFFFFFF00ull) return false;
+    const GemmPairPlan g = plan_gemm_pair(in, w_skip.cin, p.kt_total_aux, gopt_, tuning_, opt_splitk_aux_ > 0 ? std::max(gopt_.force_splits, 1) : 0, std::max(opt_splitk_aux_, 0));
+    if (!g.pair) return false;
+    p.kt_per_split = g.kt_per_split; p.splits = g.splits_main + g.splits_aux; p.z_aux = g.splits_main;
+    if (record_shapes_) {
+        char note[48];
+        std::snprintf(note, sizeof note, " +aux K%d z%d", w_skip.cin, p.z_aux);
+        record_choice(p, " pair", g.cfg, note);
+    }
+    p.slab_stride = (long long)p.M * p.N;
+    Buf slab(this, (size_t)p.splits * p.slab_stride * sizeof(float));
+    p.slabs = slab.f();
+    const double flops = 2.0 * p.M * (double)p.N * ((double)p.K + w_skip.cin);
+    const double bytes = (double)p.M * (w_out.cin + w_skip.cin) * 6.0 + (double)p.N * (p.K + w_skip.cin) * 6.0 + (double)p.M * p.N * ((p.C ? 4.0 : 0.0) + (p.C3 ? 6.0 : 0.0));
+    {
+        ProfScope ps(this, PC_CONV_SPLIT, flops, bytes);
+        ps.set_tag("gemm %d,%d,%d+%d k3+1 cfg=%d splits=%d+%d", p.M, p.N, p.K, w_skip.cin, g.cfg, g.splits_main, g.splits_aux);
+        SDMI_HIP(launch_conv_gemm3p(p, g.tile.index, stream_));
+    }
+    count_kernel(flops);
+    ProfScope ps(this, PC_SPLITK_REDUCE, 0, (double)(p.splits + 1) * p.slab_stride * 4.0);
+    ps.set_tag("reduce %d,%d,%d+%d k3+1 cfg=%d splits=%d+%d", p.M, p.N, p.K, w_skip.cin, g.cfg, g.splits_main, g.splits_aux);
+    SDMI_HIP(launch_splitk_reduce(p, stream_));
+    count_kernel();
+    return true;
 }
 
 // the ConvGemm of a Linear layer: [rows, cin] x [cout, cin]^T as a 1x1 convolution over one image of 1 x rows pixels
@@ -1841,6 +1907,18 @@ void Engine::res_block(const ResW& w, const Act& x, Act& y, int step) {
         conv(w.conv_in, h1, h2, 1, 0, rowvec, 0, nullptr);
         release(h1);
     }
+    // fp32 engine, option skip_slices: the 1x1 shortcut rides on extra K slices of conv_out's split-K launch (conv_pair) -- no launch, reduce or
+    // residual buffer of its own.  Where conv_pair declines (x without planes, conv_out not split, a "0" row of the pairs table ...) the two launches below run.
+    Act h3{};
+    if (w.has_skip && opt_skip_slices_ && !bf16_ && !fp8_ && plane_gemm(w.cout, w.cout) && plane_gemm(x.c, w.cout) && x.p3) {
+        h3 = new_act3(x.n, x.h, x.w, w.cout, 2);
+        group_norm(w.norm_out, h2, h3, true);   // (independent of the shortcut: where conv_pair declines, the launches below find it done)
+        release(h2);
+        if (conv_pair(w.conv_out, h3, w.skip, x, y)) {
+            release(h3);
+            return;
+        }
+    }
     // the shortcut's result is the residual of conv_out: it goes through y's fp32 buffer, or through a temporary when y exists as planes only
     Act sk{};
     if (w.has_skip) {
@@ -1863,9 +1941,11 @@ void Engine::res_block(const ResW& w, const Act& x, Act& y, int step) {
         conv_fp8(w.conv_out, q3, y, nullptr, resid);
         release(q3);
     } else {
-        Act h3 = plane_gemm(w.cout, w.cout) ? new_act3(x.n, x.h, x.w, w.cout, 2) : new_act(x.n, x.h, x.w, w.cout);
-        group_norm(w.norm_out, h2, h3, true);
-        release(h2);
+        if (!h3.p3) {
+            h3 = plane_gemm(w.cout, w.cout) ? new_act3(x.n, x.h, x.w, w.cout, 2) : new_act(x.n, x.h, x.w, w.cout);
+            group_norm(w.norm_out, h2, h3, true);
+            release(h2);
+        }
         conv(w.conv_out, h3, y, 1, 0, nullptr, 0, resid);
         release(h3);
     }
@@ -2901,6 +2981,42 @@ void Engine::op_conv2d(const float* x, const float* wt, const float* bias, int n
     if (y.dt) SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(y.p, out, n, cout, ho, wo, stream_));
     else SDMI_HIP(launch_nhwc_to_nchw(y.p, out, n, cout, ho, wo, stream_));
     release(a); release(y);
+}
+
+// conv3x3(h, w_out) + b_out + conv1x1(x, w_skip) + b_skip as Engine::res_block computes the tail of a ResBlock with a shortcut: both inputs as planes, option skip_slices
+// = 1 -> conv_pair (an error where it declines: no quiet other path), 0 -> the two launches.  out / out3 [n,cout,h,w]; out3 (may be null): the result also written
+// as planes by the same launch and joined back (exact).
+void Engine::op_conv2d_pair(const float* x, const float* hp, const float* w_skip, const float* b_skip, const float* w_out, const float* b_out, int n, int cin_x, int cout,
+                            int h, int wd, float* out, float* out3) {
+    if (n <= 0 || h <= 0 || wd <= 0 || cin_x <= 0 || cout <= 0) throw Error(SDMI_ERR_INVALID, "conv2d_pair: bad shape");
+    if (bf16_ || !plane_gemm(cin_x, cout) || !plane_gemm(cout, cout)) throw Error(SDMI_ERR_UNSUPPORTED, "conv2d_pair: the fp32 plane kernels only (channels in multiples of 32)");
+    Buf bt_o(this, (size_t)cout * cout * 9 * 4), bt_s(this, (size_t)cout * cin_x * 4);
+    SDMI_HIP(launch_pack_conv_weight(w_out, bt_o.f(), cout, cout, 3, 3, stream_));
+    SDMI_HIP(launch_pack_conv_weight(w_skip, bt_s.f(), cout, cin_x, 1, 1, stream_));
+    TempSplit po(this, bt_o.f(), cout, (long long)cout * 9), psk(this, bt_s.f(), cout, cin_x);
+    ConvW wo; wo.cin = cout; wo.cout = cout; wo.k = 3; wo.bt = bt_o.f(); wo.bias = const_cast<float*>(b_out);
+    ConvW ws; ws.cin = cin_x; ws.cout = cout; ws.k = 1; ws.bt = bt_s.f(); ws.bias = const_cast<float*>(b_skip);
+    Act ax = new_act3(n, h, wd, cin_x, 3), ah = new_act3(n, h, wd, cout, 3);
+    SDMI_HIP(launch_nchw_to_nhwc(x, ax.p, n, cin_x, h, wd, 1.0f, stream_));
+    SDMI_HIP(launch_nchw_to_nhwc(hp, ah.p, n, cout, h, wd, 1.0f, stream_));
+    SDMI_HIP(launch_split3_rows(ax.p, ax.p3, ax.rows(), cin_x, cin_x, ax.ld3, stream_));
+    SDMI_HIP(launch_split3_rows(ah.p, ah.p3, ah.rows(), cout, cout, ah.ld3, stream_));
+    Act y = new_act3(n, h, wd, cout, out3 ? 3 : 1);
+    if (opt_skip_slices_) {
+        if (!conv_pair(wo, ah, ws, ax, y)) throw Error(SDMI_ERR_UNSUPPORTED, "conv2d_pair: this shape / these options do not pair (skip_slices=0 runs the two launches)");
+    } else {
+        Act sk = y; sk.p3 = nullptr; sk.view = true;
+        conv(ws, ax, sk, 1, 0, nullptr, 0, nullptr);
+        conv(wo, ah, y, 1, 0, nullptr, 0, &sk);
+    }
+    SDMI_HIP(launch_nhwc_to_nchw(y.p, out, n, cout, h, wd, stream_));
+    if (out3) {
+        Act j = new_act(n, h, wd, cout);
+        SDMI_HIP(launch_join3_rows(y.p3, j.p, y.rows(), cout, y.ld3, cout, stream_));
+        SDMI_HIP(launch_nhwc_to_nchw(j.p, out3, n, cout, h, wd, stream_));
+        release(j);
+    }
+    release(ax); release(ah); release(y);
 }
 
 void Engine::op_linear(const float* x, const float* wt, const float* bias, int rows, int cin, int cout, float* out, const EpiOps* epi) {

@@ -220,6 +220,9 @@ public:
     void op_conv2d(const float* x, const float* w, const float* bias, int n, int cin, int h, int wd, int cout, int k,
                    int stride, int pad, int ups, float* out, const EpiOps* epi = nullptr);
     void op_linear(const float* x, const float* w, const float* bias, int rows, int cin, int cout, float* out, const EpiOps* epi = nullptr);
+    // the tail of a ResBlock with a shortcut (tests: sdmi_op_conv2d_pair): conv3x3(h, w_out) + b_out + conv1x1(x, w_skip) + b_skip; out3: the planes output, joined
+    void op_conv2d_pair(const float* x, const float* h, const float* w_skip, const float* b_skip, const float* w_out, const float* b_out, int n, int cin_x, int cout,
+                        int hh, int wd, float* out, float* out3);
     void op_geglu(const float* proj, int rows, int hidden, float* out);
     // the same operators on channel-slice VIEWS, built with slice() on real Acts as unet_run builds the halves of a Tensor::cat (tests: sdmi_op_*_view).
     // xp: the input's parent [rows][in_ld] fp32 NHWC on the device (the slice's columns hold x, the others the caller's filler); yp: the output's
@@ -316,8 +319,8 @@ private:
         TempSplit(const TempSplit&) = delete;
         TempSplit& operator=(const TempSplit&) = delete;
     };
-    const float* temp_split_bt_ = nullptr;
-    const void* temp_split_planes_ = nullptr;
+    const float* temp_split_bt_[2] = {nullptr, nullptr};
+    const void* temp_split_planes_[2] = {nullptr, nullptr};
     char* stage_reserve(size_t bytes, size_t* offset, int* half);
     void stage_commit(WeightEntry& e, size_t offset, int half);
     // THE packing routine, shared by the loader (stage_commit) and a LoRA re-merge (lora_repack): the device fp32 tensor `stage` (reference layout, the padded
@@ -353,6 +356,8 @@ private:
     void probe_report(void* pb_dev, size_t max_blocks, int n, int cin, int h, int w, int cout, int k, int tile_cfg, int splitk);
     void conv(const ConvW& w, const Act& x, Act& y, int stride, int ups, const float* rowvec, int rowvec_stride,
               const Act* resid, bool pad_br = false);
+    // conv3x3(h, w_out) + conv1x1(x, w_skip) + both biases as one split-K plane launch (ConvGemm::z_aux) + reduce; false: not launched (see engine.cpp)
+    bool conv_pair(const ConvW& w_out, const Act& h, const ConvW& w_skip, const Act& x, Act& y);
     static Act slice(const Act& parent, int c_off, int c);   // channel-slice view
     // A3 / C3: the input / output as three bf16 planes (dense rows: 192 bytes per 32 channels); A and / or C may then be null
     void gemm(const float* A, int a_rows, const float* bt, const float* bias, int cin, int cout, float* C, int ldc,
@@ -360,6 +365,7 @@ private:
     // fp32 engine, option gemm_planes: does the GEMM cin -> cout take its activations as planes (k_gemm3p.hip)?
     bool plane_gemm(int cin, int cout) const { return !bf16_ && gopt_.gemm_planes != 0 && gopt_.gemm_f32s != 0 && cin % 32 == 0 && cout >= 32; }
     void launch_gemm(ConvGemm& p, int in_dt, int force_cfg = -1, int force_splits = 0);   // plan (gemm_plan.hpp), temporary plane / fp32 buffers, run_gemm
+    GemmPlanIn gemm_plan_in(const ConvGemm& p, int in_dt, int force_cfg, int force_splits) const;
     using GemmLauncher = hipError_t (*)(const ConvGemm&, int, hipStream_t);
     struct GemmRun { GemmLauncher launch; int index; const char* what; int cfg; int pc; bool bf16_reduce, reduce_tag; double flops, bytes; };
     void record_choice(const ConvGemm& p, const char* kind, int cfg, const char* note);
@@ -487,6 +493,8 @@ private:
     int opt_b3_grouped_ = 1;         // precision 0: weight planes in 16-row fragment groups (1 KiB DMA pieces, sequential per group); 0 = row-major planes.  Before the weights are loaded.
     AttnPlanOpts aopt_;              // options attn_split, attn_bf16, attn_bf16_variant, attn_pack_tail, attn_kv_splits, attn_kv_prefer8 (attn_plan.hpp)
     int opt_cfg_share_ = 1;          // sample_latent: the part of the UNet in front of the first cross attention is computed once for the two identical halves of a CFG step (unet_run)
+    int opt_skip_slices_ = 1;        // fp32 ResBlocks with a 1x1 shortcut: 1 = the shortcut runs on extra K slices of conv_out's split-K launch (conv_pair); 0 = its own launches
+    int opt_splitk_aux_ = 0;         // tests (with splitk): requested slice count of the auxiliary problem of a paired launch; 0 = planned
     int opt_op_resid_ = 0;           // tests: op_conv2d / op_linear add their input as the residual (cin == cout) through the GEMM epilogue
     int opt_op_misalign_ = 0;        // tests: stage_epi starts the device copies of bias, time-embedding row and residual one element past an aligned address
     int opt_fp8_ops_ = 0;            // tests: op_linear / op_layer_norm / op_geglu run the fp8_linear path's kernels (outputs dequantised)

@@ -20,6 +20,11 @@ static const TuneRow kTuneRows[] = {
 #include "tuning_table_bf16.inc"
     {nullptr, 0, 0}};
 
+// tuning/gfx950_fp32_pairs.txt: "M,N,Kmain+Kaux" -> (cfg, k tiles per slice)
+static const TuneRow kPairRows[] = {
+#include "tuning_table_pairs.inc"
+    {nullptr, 0, 0}};
+
 // ---- cost model of the five MFMA families ------------------------------------------------------------------------------
 // Cycles per CU: (rounds of workgroups on 256 CUs) x (k loop of one workgroup / tile efficiency + per-workgroup overhead)
 // + split-K reduce launch and slab traffic.  A k tile of a bm x bn block is bm * bn * flop / rate cycles: fp32 MFMA 32 * 2 flop at
@@ -93,12 +98,20 @@ void GemmTuning::load_builtin() {
     for (const TuneRow& r : kTuneRows)
         if (r.key) (*tables[t])[r.key] = TileChoice{r.cfg, r.splits};
         else ++t;
+    for (const TuneRow& r : kPairRows)
+        if (r.key) pairs[r.key] = TileChoice{r.cfg, r.splits};
 }
 
 void GemmTuning::set(const std::string& value, bool b16) {
     const size_t eq = value.find('=');
     if (eq == std::string::npos) throw Error(SDMI_ERR_INVALID, "tune expects M,N,K=cfg,splits");
     TileChoice tc{0, 1};
+    if (!b16 && value.find('+') < eq) {   // a pair row: plane tiles, k tiles per slice (0: do not pair)
+        if (std::sscanf(value.c_str() + eq + 1, "%d,%d", &tc.cfg, &tc.splits) != 2 || tc.splits < 0 || gemm_tile_id(tc.cfg).family != kFamP || !gemm_tile_id(tc.cfg).in_range(false))
+            throw Error(SDMI_ERR_INVALID, "tune: a pair row is M,N,Kmain+Kaux=cfg,kt_per_split with a plane tile (300 + x)");
+        pairs[value.substr(0, eq)] = tc;
+        return;
+    }
     if (std::sscanf(value.c_str() + eq + 1, "%d,%d", &tc.cfg, &tc.splits) != 2 || tc.cfg < 0 || tc.splits < 1 || !gemm_tile_id(tc.cfg).in_range(b16))
         throw Error(SDMI_ERR_INVALID, "tune: bad value");
     // plane tiles have their own table: what a GEMM whose input arrives as planes chooses from
@@ -154,6 +167,46 @@ GemmPlan plan_gemm(const GemmPlanIn& in, const GemmPlanOpts& o, const GemmTuning
         throw Error(SDMI_ERR_INVALID, "gemm: large-tile kernel index out of range or not applicable to this layer");
     g.tile = tile; g.cfg = tile.cfg(); g.tile_forced = tile_forced;
     return g;
+}
+
+GemmPairPlan plan_gemm_pair(const GemmPlanIn& main, int k_aux, int kt_aux, const GemmPlanOpts& o, const GemmTuning& t, int force_main, int force_aux) {
+    GemmPairPlan pp{};
+    if (main.bf16 || !main.from_planes || main.geglu || main.out_mode != 0 || kt_aux <= 0 || main.kt_total <= 0) return pp;
+    const GemmPlan g = plan_gemm(main, o, t);
+    if (g.tile.family != kFamP) return pp;
+    pp.tile = g.tile; pp.cfg = g.cfg;
+    const int ktm = main.kt_total;
+    auto slices = [](int kt_total, int kt) { return (kt_total + kt - 1) / kt; };
+    int kt = 0;
+    if (force_main > 0 || force_aux > 0) {
+        const int sm = std::max(1, std::min(force_main, ktm)), sa = std::max(1, std::min(force_aux, kt_aux));
+        kt = std::max(slices(ktm, sm), slices(kt_aux, sa));
+    } else {
+        char key[80];
+        std::snprintf(key, sizeof key, "%d,%d,%d+%d", main.M, main.N, main.K, k_aux);
+        const TileChoice* const row = g.tile_forced ? nullptr : find(t.pairs, key);
+        if (row) {
+            if (row->splits <= 0) return pp;
+            const GemmTileId id = gemm_tile_id(row->cfg);
+            if (id.family != kFamP || !id.in_range(false)) throw Error(SDMI_ERR_INVALID, "pairs table: not a plane tile");
+            pp.tile = id; pp.cfg = id.cfg();
+            kt = std::min(row->splits, std::max(ktm, kt_aux));
+        } else {
+            if (g.splits <= 1) return pp;
+            const GemmTileInfo& ti = g.tile.info();
+            const long long tiles = (long long)((main.M + ti.bm - 1) / ti.bm) * ((main.N + ti.bn - 1) / ti.bn);
+            const long long rounds_today = (tiles * g.splits + 255) / 256;
+            // never finer than the main launch is cut today: that count is the measured (or modelled) balance of k-loop length against slab traffic
+            for (int c = std::max(std::min(4, ktm), g.kt_per_split); c <= ktm; ++c)
+                if ((tiles * (slices(ktm, c) + slices(kt_aux, c)) + 255) / 256 <= rounds_today) { kt = c; break; }
+            if (!kt) return pp;
+        }
+    }
+    pp.kt_per_split = kt;
+    pp.splits_main = slices(ktm, kt);
+    pp.splits_aux = slices(kt_aux, kt);
+    pp.pair = true;
+    return pp;
 }
 
 // Rounds of workgroups on 256 CUs x the time of one tile at the rate each tile shape sustains when the chip is full

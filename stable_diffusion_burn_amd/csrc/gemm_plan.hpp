@@ -41,14 +41,28 @@ struct GemmTuning {
     std::map<std::string, TileChoice> mfma;    // fp32 shapes measured with the fp32-MFMA kernels only (gemm_f32s=0)
     std::map<std::string, TileChoice> planes;  // fp32 shapes whose activations arrive as planes: k_gemm3p.hip tiles only
     std::map<std::string, TileChoice> bf16;    // bf16 kernels
+    // paired launches (plan_gemm_pair), "M,N,Kmain+Kaux" -> (cfg, k tiles per slice; 0 = do not pair): tuning/gfx950_fp32_pairs.txt.  TileChoice::splits holds the k tiles.
+    std::map<std::string, TileChoice> pairs;
     void load_builtin();
-    void set(const std::string& value, bool b16);   // "M,N,K=cfg,splits"
-    void clear() { f32.clear(); mfma.clear(); planes.clear(); bf16.clear(); }
+    void set(const std::string& value, bool b16);   // "M,N,K=cfg,splits"; "M,N,Kmain+Kaux=cfg,kt_per_split" goes to pairs
+    void clear() { f32.clear(); mfma.clear(); planes.clear(); bf16.clear(); pairs.clear(); }
 };
 
 struct GemmPlan { GemmTileId tile; int cfg, splits, kt_per_split; bool tile_forced; };   // cfg = tile.cfg(); tile_forced: by option gemm_tile or by the caller
 
 GemmPlan plan_gemm(const GemmPlanIn& in, const GemmPlanOpts& o, const GemmTuning& t);   // throws Error
+
+// A split-K plane launch that carries a second, 1x1 problem over the same rows and columns on extra slices (kernels.hpp, ConvGemm::z_aux): slices [0, splits_main) hold
+// the main problem's k tiles, [splits_main, splits_main + splits_aux) the auxiliary one's, kt_per_split tiles each (the last of either may be short; none is empty).
+struct GemmPairPlan { bool pair; GemmTileId tile; int cfg, kt_per_split, splits_main, splits_aux; };
+// main: the launch as plan_gemm would see it alone (from_planes).  The tile is plan_gemm's.  kt_per_split is the smallest one -- not below the k tiles a slice of the main
+// launch holds today (the measured or modelled balance of k-loop length against slab traffic), nor below four (the cost model's floor for a slice) -- with which
+// tiles x (main + auxiliary slices) needs no more rounds of 256 workgroups than the main launch alone needs today: the auxiliary k tiles join a k loop that already
+// runs and never add a round.  pair = false ("run the two launches"): the main launch is not on a plane tile or not split today (the reduce
+// would be a new dependent phase), no such kt exists, or the pairs table says 0 for the shape.  A table row's cfg / kt are taken as measured.
+// force_main / force_aux > 0 (tests, with option gemm_tile for the tile): requested slice counts.  Both problems share kt_per_split, so the request is met as
+// kt = max(ceil(kt_main / force_main), ceil(kt_aux / force_aux)) and the counts that follow from it; it pairs whatever today's split count is.
+GemmPairPlan plan_gemm_pair(const GemmPlanIn& main, int k_aux, int kt_aux, const GemmPlanOpts& o, const GemmTuning& t, int force_main = 0, int force_aux = 0);   // throws Error
 // MXFP8 (k_fp8.hip): tile index (fp8_tile >= 0 forces it) and split count
 TileChoice plan_gemm_fp8(int M, int N, int kt_total, int fp8_tile, int force_splits, int* kt_per_split);
 // the plane tile the GEGLU projection [rows, 2 hidden] takes with the gate split by wave column in its epilogue, or -1 (unfused)

@@ -84,6 +84,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvGemm p) {
             f32x4 eb = {0.f, 0.f, 0.f, 0.f}, ev = eb, er = eb;
             if (live && g == 0) {
                 if (p.bias) eb = *reinterpret_cast<const f32x4*>(p.bias + n);
+                if (p.bias_aux) eb += *reinterpret_cast<const f32x4*>(p.bias_aux + n);   // a paired launch (ConvGemm::z_aux): bias + bias_aux, one term of the sum
                 if (p.rowvec) ev = *reinterpret_cast<const f32x4*>(p.rowvec + (long long)(m / HoWo) * p.rowvec_stride + n);
                 if (p.resid) er = *reinterpret_cast<const f32x4*>(p.resid + (long long)m * p.ldr + n);
             }
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvGemm p) {
                 for (int e = 0; e < 4; ++e) v[e] += __shfl_xor(v[e], o, 64);
             }
             if (live && g == 0) {
-                if (p.bias) v += eb;
+                if (p.bias || p.bias_aux) v += eb;
                 if (p.rowvec) v += ev;
                 if (p.resid) v += er;
                 if (C) *reinterpret_cast<f32x4*>(C + (long long)m * p.ldc + n) = v;
@@ -118,7 +119,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvGemm p) {
             const int n = (int)(i - (long long)m * p.N);
             float v = slabs[i];
             for (int s = 1; s < p.splits; ++s) v += slabs[s * p.slab_stride + i];
-            if (p.bias) v += p.bias[n];
+            if (p.bias_aux) v += (p.bias ? p.bias[n] : 0.f) + p.bias_aux[n];
+            else if (p.bias) v += p.bias[n];
             if (p.rowvec) v += p.rowvec[(long long)(m / HoWo) * p.rowvec_stride + n];
             if (p.resid) v += p.resid[(long long)m * p.ldr + n];
             C[(long long)m * p.ldc + n] = v;
@@ -166,6 +168,8 @@ __global__ void pack_linear_weight_kernel(const float* __restrict__ w, float* __
 hipError_t launch_splitk_reduce(const ConvGemm& p, hipStream_t stream) {
     const bool vec = splitk_reduce_vec(p, false);
     if (!vec && (p.C3 || !p.C)) return hipErrorInvalidValue;   // the plane output is part of the 16-byte path only
+    if (p.z_aux && (p.resid || p.rowvec)) return hipErrorInvalidValue;   // a paired launch: the shortcut IS the residual
+    if (p.bias_aux && vec && ((uintptr_t)p.bias_aux & 15)) return hipErrorInvalidValue;
     const long long work = ((long long)p.M * p.N + 3) / 4;
     // lanes per output: enough threads to cover the chip (>= 256 K) while every lane still has two slabs to sum
     int g = 1;

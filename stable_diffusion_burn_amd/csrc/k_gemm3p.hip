@@ -197,10 +197,15 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm3p_kernel(const Conv
     const int m0 = gw.tm * BM;
     const int n0 = gw.tn * BNO;
     const int z = gw.z;
-    const int kt_begin = z * p.kt_per_split;
-    const int kt_end = min(kt_begin + p.kt_per_split, p.kt_total);
+    // Slices [z_aux, splits) of a paired launch (ConvGemm::z_aux != 0) work on the auxiliary 1x1 problem: other planes, other k range, one tap, no padding.  blockIdx.z
+    // decides, so every select below is wave-uniform, and all of them sit in front of the first DMA: the k loop does not know which problem it runs.
+    const bool aux = p.z_aux != 0 && z >= p.z_aux;
+    const int kt_total = aux ? p.kt_total_aux : p.kt_total;
+    const int kt_begin = (aux ? z - p.z_aux : z) * p.kt_per_split;
+    const int kt_end = min(kt_begin + p.kt_per_split, kt_total);
     const int n_t = kt_end - kt_begin;
-    const int T = p.KH * p.KW;
+    const int KH = aux ? 1 : p.KH, KW = aux ? 1 : p.KW, pad = aux ? 0 : p.pad;
+    const int T = KH * KW;
     const int HoWo = p.Ho * p.Wo;
 
     P3Wave<MI, NI, NAG, NBW, A_BYTES, NWV> w;
@@ -208,12 +213,12 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm3p_kernel(const Conv
     w.Win = p.Ws << p.ups;
     w.ups = p.ups;
     w.Ws = p.Ws;
-    w.KH = p.KH;
-    w.KW = p.KW;
+    w.KH = KH;
+    w.KW = KW;
     w.wave = wave;
-    w.pix_bytes = (unsigned)p.a3_ld;
-    w.Abase = reinterpret_cast<const char*>(p.A3);
-    w.Wbase = reinterpret_cast<const char*>(p.Bt3);
+    w.pix_bytes = (unsigned)(aux ? p.a3_ld_aux : p.a3_ld);
+    w.Abase = reinterpret_cast<const char*>(aux ? p.A3_aux : p.A3);
+    w.Wbase = reinterpret_cast<const char*>(aux ? p.Bt3_aux : p.Bt3);
     w.zero = reinterpret_cast<const char*>(p.zero_page);
     w.a_src = w.zero;
 
@@ -230,10 +235,10 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm3p_kernel(const Conv
         const int oy = rem / p.Wo;
         const int ox = rem - oy * p.Wo;
         w.a_off[j] = (unsigned)nb * (unsigned)(p.Hs * p.Ws) * w.pix_bytes + ch * 16;
-        w.a_iy0[j] = ok ? oy * p.stride - p.pad : -(1 << 28);   // rows past M: never in range -> zero page
-        w.a_ix0[j] = ox * p.stride - p.pad;
+        w.a_iy0[j] = ok ? oy * p.stride - pad : -(1 << 28);   // rows past M: never in range -> zero page
+        w.a_ix0[j] = ox * p.stride - pad;
     }
-    const unsigned w_row_bytes = (unsigned)p.kt_total * 192u;
+    const unsigned w_row_bytes = (unsigned)kt_total * 192u;
 #pragma unroll
     for (int j = 0; j < NBW; ++j) {
         const int q = wave + NWV * j;
@@ -259,8 +264,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm3p_kernel(const Conv
 
     w.cs = kt_begin / T;
     const int tap0 = kt_begin - w.cs * T;
-    w.ky = tap0 / p.KW;
-    w.kx = tap0 - w.ky * p.KW;
+    w.ky = tap0 / KW;
+    w.kx = tap0 - w.ky * KW;
     w.kt_next = kt_begin;
     w.kt_end = kt_end;
 
@@ -357,6 +362,16 @@ hipError_t launch_conv_gemm3p(const ConvGemm& p, int cfg, hipStream_t stream) {
     if (p.geglu != 0 && p.geglu != 1 && p.geglu != 2) return hipErrorInvalidValue;
     if ((unsigned long long)p.N * (p.geglu ? 2 : 1) * (unsigned long long)p.kt_total * 192ull >= 0xFFFFFF00ull) return hipErrorInvalidValue;   // 32-bit piece offsets
     if ((unsigned long long)p.NB * p.Hs * p.Ws * (unsigned long long)p.a3_ld >= 0xFFFFFF00ull) return hipErrorInvalidValue;
+    if (p.z_aux) {
+        // the auxiliary problem reads source pixel = output pixel: the main one must be stride 1 without upsampling; same checks on its operands; slices [0, z_aux)
+        // are exactly the main problem's and [z_aux, splits) exactly the auxiliary one's -- none empty, none straddling, no k tile left out
+        if (p.stride != 1 || p.ups != 0 || p.Hs != p.Ho || p.Ws != p.Wo || p.geglu || p.probe || p.rowvec || p.resid) return hipErrorInvalidValue;
+        if (!p.A3_aux || !p.Bt3_aux || p.Cin_aux <= 0 || (p.Cin_aux % 32) || p.kt_total_aux != p.Cin_aux / 32 || p.a3_ld_aux < p.kt_total_aux * 192 || (p.a3_ld_aux % 192)) return hipErrorInvalidValue;
+        if (p.kt_per_split <= 0 || p.z_aux != (p.kt_total + p.kt_per_split - 1) / p.kt_per_split ||
+            p.splits - p.z_aux != (p.kt_total_aux + p.kt_per_split - 1) / p.kt_per_split || !p.slabs) return hipErrorInvalidValue;
+        if ((unsigned long long)p.N * (unsigned long long)p.kt_total_aux * 192ull >= 0xFFFFFF00ull) return hipErrorInvalidValue;
+        if ((unsigned long long)p.NB * p.Hs * p.Ws * (unsigned long long)p.a3_ld_aux >= 0xFFFFFF00ull) return hipErrorInvalidValue;
+    }
     const int bm = kTilesP[cfg].bm, bn = kTilesP[cfg].bn;
     const int bno = p.geglu ? bn / 2 : bn;
     const int MT = (p.M + bm - 1) / bm, NT = (p.N + bno - 1) / bno;

@@ -59,6 +59,17 @@ struct ConvGemm {
                                 // epilogue writes value * gelu_erf(gate) -- GEGLU::forward (unet/mod.rs:579-591) without the [M, 2N] tensor
     unsigned long long* probe;  // diagnostic (option gemm_probe; k_gemm3p.hip tiles 300 / 303 / 304 only): when non-null the PROBE instantiation runs and
                                 // stores 24 words per workgroup (see conv_gemm3p_kernel)
+    // A second problem on the slices [z_aux, splits) of a split-K launch (k_gemm3p.hip only; every other launcher refuses z_aux != 0): a 1x1 / stride-1 / pad-0 GEMM over the
+    // same M output rows and the same N, its own activation planes and weight planes -- the ResBlock shortcut riding in conv_out's launch (Engine::conv_pair).  The main
+    // problem must be stride 1 without upsampling (source pixel = output pixel).  Slices [0, z_aux) cover the kt_total k tiles of the main problem, slice z >= z_aux the
+    // k tiles [(z - z_aux) kt_per_split, ...) of the kt_total_aux auxiliary ones: no slice holds tiles of both.  Slabs are indexed by z; launch_splitk_reduce sums all
+    // `splits` of them in slice order and adds bias + bias_aux.
+    const void* A3_aux;         // [NB][Hs][Ws][a3_ld_aux / 192 slices][3][32]
+    int a3_ld_aux;
+    const void* Bt3_aux;        // [N][Cin_aux / 32][3][32], in the layout b3_grouped names (it depends on N only)
+    int Cin_aux, kt_total_aux;
+    int z_aux;                  // first slice of the auxiliary problem; 0: none
+    const float* bias_aux;      // [N] or null
 };
 
 // capacity of ConvGemm::probe in workgroups (24 words each); launch_conv_gemm3p refuses a probe launch with a larger grid

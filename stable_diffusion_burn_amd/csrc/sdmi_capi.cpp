@@ -1000,6 +1000,28 @@ int sdmi_op_conv2d_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, 
     });
 }
 
+int sdmi_op_conv2d_pair(sdmi_ctx* ctx, const float* x, const float* h, const float* w_skip, const float* b_skip, const float* w_out, const float* b_out, int32_t n,
+                        int32_t cin_x, int32_t cout, int32_t hh, int32_t ww, float* out, float* out_planes) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (n <= 0 || cin_x <= 0 || cout <= 0 || hh <= 0 || ww <= 0) throw Error(SDMI_ERR_INVALID, "conv2d_pair: bad shape");
+        const size_t px = (size_t)n * hh * ww;
+        Engine::Call call(e);
+        DevIn dx(e, x, px * cin_x * sizeof(float)), dh(e, h, px * cout * sizeof(float));
+        DevIn dws(e, w_skip, (size_t)cout * cin_x * sizeof(float)), dwo(e, w_out, (size_t)cout * cout * 9 * sizeof(float));
+        std::unique_ptr<Engine::Buf> dbs, dbo;
+        const float* bs = b_skip ? e.stage_epi(dbs, b_skip, 1, cout, cout, 0) : nullptr;
+        const float* bo = b_out ? e.stage_epi(dbo, b_out, 1, cout, cout, 0) : nullptr;
+        DevOut dout(e, out, px * cout * sizeof(float));
+        std::unique_ptr<DevOut> dout3;
+        if (out_planes) dout3.reset(new DevOut(e, out_planes, px * cout * sizeof(float)));
+        e.op_conv2d_pair(dx.f(), dh.f(), dws.f(), bs, dwo.f(), bo, n, cin_x, cout, hh, ww, dout.f(), dout3 ? dout3->f() : nullptr);
+        call.finish();
+        dout.fetch();
+        if (dout3) dout3->fetch();
+    });
+}
+
 int sdmi_op_linear_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, const float* resid, int32_t resid_ld, int32_t rows,
                             int32_t cin, int32_t cout, float* out) {
     return guarded([&] {

@@ -914,6 +914,25 @@ class StableDiffusion:
                                                 _fp(out)))
         return out
 
+    def op_conv2d_pair(self, x, h, w_skip, b_skip, w_out, b_out, planes=False):
+        """conv3x3(h, w_out) + b_out + conv1x1(x, w_skip) + b_skip, the tail of a ResBlock with a shortcut (tests; precision 0).  Option skip_slices=1: one
+        split-K launch carrying the shortcut on extra K slices; 0: two launches.  planes=True also returns the result the launch wrote as bf16 planes, joined."""
+        x = _f32(x)
+        h = _f32(h)
+        n, cin_x, hh, ww = x.shape
+        cout = h.shape[1]
+        if h.shape != (n, cout, hh, ww):
+            raise ValueError("conv2d_pair: x and h must cover the same pixels")
+        ws = _f32(w_skip, (cout, cin_x, 1, 1))
+        wo = _f32(w_out, (cout, cout, 3, 3))
+        bs = None if b_skip is None else _f32(b_skip, (cout,))
+        bo = None if b_out is None else _f32(b_out, (cout,))
+        out = np.empty((n, cout, hh, ww), dtype=np.float32)
+        out3 = np.empty_like(out) if planes else None
+        check(self._lib.sdmi_op_conv2d_pair(self._ctx, _fp(x), _fp(h), _fp(ws), None if bs is None else _fp(bs), _fp(wo), None if bo is None else _fp(bo),
+                                            n, cin_x, cout, hh, ww, _fp(out), None if out3 is None else _fp(out3)))
+        return (out, out3) if planes else out
+
     def op_linear_epilogue(self, x, weight, bias=None, resid=None, resid_ld=0):
         """op_linear + resid [rows, cout] through the GEMM epilogue (tests); resid_ld (0: cout) is the row stride the engine keeps it at."""
         x = _f32(x)

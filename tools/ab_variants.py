@@ -84,6 +84,7 @@ def main():
         best, med = min(times[i]), sorted(times[i])[len(times[i]) // 2]
         rec = {"arm": args.arms[i], "precision": args.precision, "batch": args.batch, "ddim_steps": args.ddim_steps,
                "img_per_s_best": args.batch / best, "img_per_s_median": args.batch / med, "ms_per_image_median": med / args.batch * 1e3,
+               "ms_per_image_rounds": [round(t / args.batch * 1e3, 3) for t in times[i]],
                "classes_ms_per_image": {k: round(v["ms"] / args.batch, 3) for k, v in prof.items() if v["ms"] > 0}}
         g = prof.get("conv_gemm_split") if args.precision == "fp32" else prof.get("conv_gemm")
         if g and g["ms"] > 0:
