@@ -28,7 +28,8 @@ pub struct SdmiConfig {
     pub clip_heads: i32,
     pub clip_vocab: i32,
     pub clip_ctx: i32,
-    pub reserved: [i32; 3],
+    pub unet_in_ch: i32,
+    pub reserved: [i32; 2],
 }
 
 /// `sdmi_sampler` (include/sdmi.h "sampler choice"): kind 0 DDIM(eta) -- eta 0 = the reference's sampler = plain Euler, eta 1 =
@@ -54,6 +55,14 @@ pub struct SdmiHires {
     pub hires_steps: i64,
     pub strength: f64,
     pub hires_seed: u64,
+    pub reserved: [i64; 4],
+}
+
+/// `sdmi_inpaint` (include/sdmi.h "inpainting"): the options of `sdmi_inpaint_image`; all zero = neither.
+#[repr(C)]
+pub struct SdmiInpaint {
+    pub latent_blend: i32,
+    pub paste_back: i32,
     pub reserved: [i64; 4],
 }
 
@@ -94,6 +103,22 @@ extern "C" {
     fn sdmi_img2img_image(ctx: *mut c_void, context: *const c_float, n: i32, t_len: i32, uncond: *const c_float, tu: i32, scale: c_double,
                           n_steps: usize, strength: c_double, init_rgb: *const u8, mask: *const c_float, noise: *const c_float, seed: u64,
                           rgb_out: *mut u8) -> c_int;
+    fn sdmi_unet_forward_cond(ctx: *mut c_void, x: *const c_float, t: i32, context: *const c_float, cond: *const c_float, n: i32, t_len: i32,
+                              out: *mut c_float) -> c_int;
+    fn sdmi_img2img_latent_cond(ctx: *mut c_void, context: *const c_float, n: i32, t_len: i32, uncond: *const c_float, tu: i32, scale: c_double,
+                                n_steps: usize, strength: c_double, z0: *const c_float, mask: *const c_float, noise: *const c_float, seed: u64,
+                                cond: *const c_float, latent_out: *mut c_float) -> c_int;
+    fn sdmi_img2img_latent_cond_dev(ctx: *mut c_void, context: *const c_float, n: i32, t_len: i32, uncond: *const c_float, tu: i32, scale: c_double,
+                                    n_steps: usize, strength: c_double, z0: *const c_float, mask: *const c_float, noise: *const c_float, seed: u64,
+                                    cond: *const c_float, latent_out: *mut c_float) -> c_int;
+    fn sdmi_inpaint_latent_mask(mask_u8: *const u8, n: i32, h: i32, w: i32, out: *mut c_float) -> c_int;
+    fn sdmi_inpaint_cond(ctx: *mut c_void, init_rgb: *const u8, mask_u8: *const u8, n: i32, cond_out: *mut c_float) -> c_int;
+    fn sdmi_inpaint_image(ctx: *mut c_void, context: *const c_float, n: i32, t_len: i32, uncond: *const c_float, tu: i32, scale: c_double,
+                          n_steps: usize, strength: c_double, init_rgb: *const u8, mask_u8: *const u8, opt: *const SdmiInpaint, noise: *const c_float,
+                          seed: u64, rgb_out: *mut u8) -> c_int;
+    fn sdmi_inpaint_image_dev(ctx: *mut c_void, context: *const c_float, n: i32, t_len: i32, uncond: *const c_float, tu: i32, scale: c_double,
+                              n_steps: usize, strength: c_double, init_rgb: *const u8, mask_u8: *const u8, opt: *const SdmiInpaint, noise: *const c_float,
+                              seed: u64, rgb_out: *mut u8) -> c_int;
     fn sdmi_img2img_latent_dev(ctx: *mut c_void, context: *const c_float, n: i32, t_len: i32, uncond: *const c_float, tu: i32, scale: c_double,
                                n_steps: usize, strength: c_double, z0: *const c_float, mask: *const c_float, noise: *const c_float, seed: u64,
                                latent_out: *mut c_float) -> c_int;

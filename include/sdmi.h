@@ -78,7 +78,10 @@ typedef struct sdmi_config {
     int32_t clip_heads;      /* 12                                              */
     int32_t clip_vocab;      /* 49408                                           */
     int32_t clip_ctx;        /* 77                                              */
-    int32_t reserved[3];
+    int32_t unet_in_ch;      /* 4; input channels of the UNet's first convolution: 4 = the latent alone, 5..12 = the latent + (unet_in_ch - 4)
+                              * conditioning channels given per call (the *_cond entry points; 9 = the SD v1 inpainting checkpoints, 8 = instruct-pix2pix-shaped
+                              * UNets).  0 means 4, so that a zeroed struct keeps working; anything else is SDMI_ERR_INVALID from sdmi_create. */
+    int32_t reserved[2];
 } sdmi_config;
 
 int sdmi_default_config(sdmi_config* cfg);
@@ -127,7 +130,8 @@ int sdmi_mpk_list(const char* mpk_path, char* out, size_t capacity, size_t* need
  * encoder's RGB conv_in), and packed like every other loader's tensors.  Keys the model has no tensor for (model_ema.*, position_ids, ...) are skipped
  * whatever their dtype.  alphas_cumprod is taken from the file (F64 accepted) or, when absent, computed (sdmi_default_alphas_cumprod).
  * SDMI_ERR_IO / SDMI_ERR_WEIGHTS: an unreadable / malformed file (csrc/safetensors_reader.hpp lists what is refused); SDMI_ERR_WEIGHTS: a hot-path
- * tensor without a source (the message names the dump name and the key), a shape other than the model's (key, file's shape, expected shape), no
+ * tensor without a source (the message names the dump name and the key), a shape other than the model's (key, file's shape, expected shape: a 9-channel
+ * inpainting conv_in into a 4-channel context, or the reverse, is refused here), no
  * matching key at all; SDMI_ERR_UNSUPPORTED: F64 or an integer dtype on a tensor of the model; SDMI_ERR_STATE: a LoRA adapter with a non-zero
  * scale.  Everything is checked before the first tensor is staged: a refused file leaves the context as it was.  The CLIP and VAE-encoder groups are
  * all-or-nothing by sdmi_finalize_weights' rule; call it after.  Out of scope: .ckpt pickles, diffusers-layout and sharded checkpoints, SD 2.x / SDXL. */
@@ -315,6 +319,52 @@ int sdmi_hires_latent(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T,
 int sdmi_hires_image(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps,
                      const float* init_latent, uint64_t seed, const sdmi_hires* hires, const float* hires_noise, uint8_t* rgb_out);
 
+/* ---- a UNet with conditioning channels, and the SD v1 inpainting checkpoints (no reference counterpart: its UNet takes the 4 latent channels, unet/mod.rs:109-143;
+ * DESIGN.md section 9f) ----
+ * sdmi_config.unet_in_ch = 4 + cond_ch builds a UNet whose first convolution, unet/input_blocks/conv/weight [model_channels, unet_in_ch, 3, 3], reads the latent and
+ * cond_ch conditioning channels: 9 = sd-v1-5-inpainting and its derivatives (1 mask channel + the 4-channel latent of the masked picture), 8 = instruct-pix2pix-shaped
+ * UNets.  Every loader takes the weight in that shape; the context stores it with its input channels zero-padded to a multiple of 4.  The conditioning is an input of
+ * the call, constant over its steps: cond [n, cond_ch, h, w] fp32 NCHW; both halves of a CFG batch -- the unconditional and the conditional forward of sample b --
+ * read cond[b].  Only the UNet sees it: schedule, start latent, noise, sampler and mask blend are those of the unconditioned entry.
+ * A context with cond_ch > 0 answers the entries that take no cond -- sdmi_unet_forward, sdmi_sample_*, sdmi_img2img_*, sdmi_hires_* -- with SDMI_ERR_STATE (the
+ * message names the _cond entry) and sdmi_sample_image_sharded with SDMI_ERR_UNSUPPORTED; the _cond entries and sdmi_inpaint_cond / sdmi_inpaint_image on a
+ * 4-channel context, and sdmi_inpaint_* where unet_in_ch != 9, are SDMI_ERR_STATE.  A NULL cond is SDMI_ERR_INVALID. */
+
+/* sdmi_unet_forward with x [n,4,h,w] joined by cond [n,cond_ch,h,w] in front of the first convolution (torch.cat([x, cond], 1)). */
+int sdmi_unet_forward_cond(sdmi_ctx* ctx, const float* x, int32_t t, const float* context, const float* cond /* [n,cond_ch,h,w] */, int32_t n, int32_t T,
+                           float* out);
+/* sdmi_img2img_latent -- timesteps, x_t0, noise streams, the sticky sampler and the optional latent `mask` blend unchanged -- on a conditioned UNet: every forward
+ * of the loop reads [x | cond]. */
+int sdmi_img2img_latent_cond(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps,
+                             double strength, const float* z0, const float* mask, const float* noise, uint64_t seed, const float* cond, float* latent_out);
+int sdmi_img2img_latent_cond_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps,
+                                 double strength, const float* z0, const float* mask, const float* noise, uint64_t seed, const float* cond, float* latent_out);
+
+/* Host only, needs no device: THE rule that takes a pixel mask to the latent mask.  mask_u8 n x [8h, 8w] uint8, >= 128 = regenerate; out [n, h, w] fp32,
+ *     out[b][y][x] = mask_u8[b][8y][8x] >= 128 ? 1 : 0
+ * which is torch.nn.functional.interpolate((mask >= 128).float(), size = (h, w)) in its default (legacy) "nearest" mode at the exact scale 8.  The device kernel
+ * (csrc/k_inpaint.hip) agrees with it.  SDMI_ERR_INVALID: a NULL pointer, n, h or w < 1. */
+int sdmi_inpaint_latent_mask(const uint8_t* mask_u8, int32_t n, int32_t h, int32_t w, float* out);
+/* The conditioning of an inpainting checkpoint (unet_in_ch = 9), by the rule of the CompVis inpainting script with the posterior mean for its posterior sample:
+ *     masked picture = (v / 127.5 - 1) where mask_u8 < 128, exactly 0 elsewhere          (init_rgb n x [8h,8w,3] uint8 HWC, mask_u8 n x [8h,8w] uint8)
+ *     cond_out [n,5,h,w] = [ sdmi_inpaint_latent_mask(mask_u8) | 0.18215 * sdmi_encode_image(masked picture) ]
+ * Host pointers.  Needs the encoder weight group and unet_in_ch == 9 (SDMI_ERR_STATE otherwise). */
+int sdmi_inpaint_cond(sdmi_ctx* ctx, const uint8_t* init_rgb, const uint8_t* mask_u8, int32_t n, float* cond_out);
+/* Inpainting from a picture and a pixel mask in one call: cond = sdmi_inpaint_cond(init_rgb, mask_u8), z0 = 0.18215 * sdmi_encode_image(init_rgb / 127.5 - 1) (the
+ * WHOLE picture), sdmi_img2img_latent_cond from z0 with `strength`, `noise` [n,4,h,w] or NULL (stream seed + i) and -- latent_blend = 1 -- the latent mask as its
+ * blend mask (NULL mask otherwise), sdmi_latent_to_image, and -- paste_back = 1 -- one last kernel: rgb_out = mask_u8 >= 128 ? generated : init_rgb, byte for byte.
+ * Nothing leaves the device between the stages; the result is, bit for bit, the composition of those public calls plus the paste.  opt NULL: both 0. */
+typedef struct sdmi_inpaint {
+    int32_t latent_blend;   /* 1: blend the kept region toward the re-noised init latent after every step (sdmi_img2img_latent's mask)  */
+    int32_t paste_back;     /* 1: pixels with mask_u8 < 128 are copied from init_rgb into rgb_out                                        */
+    int64_t reserved[4];
+} sdmi_inpaint;
+int sdmi_inpaint_image(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps, double strength,
+                       const uint8_t* init_rgb, const uint8_t* mask_u8, const sdmi_inpaint* opt, const float* noise, uint64_t seed, uint8_t* rgb_out);
+/* device pointers (noise may be NULL) */
+int sdmi_inpaint_image_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps, double strength,
+                           const uint8_t* init_rgb, const uint8_t* mask_u8, const sdmi_inpaint* opt, const float* noise, uint64_t seed, uint8_t* rgb_out);
+
 /* ---- LoRA adapters: low-rank deltas merged into the packed weights on the device (no reference counterpart) ----
  * The reference runs the base checkpoint only.  An adapter is a set of targets -- conv or Linear weights named by their dump-tree path -- each
  * with two factors; at scale s the context computes with
@@ -331,7 +381,8 @@ typedef struct sdmi_lora sdmi_lora;      /* owned by its context; freed by sdmi_
 int sdmi_lora_create(sdmi_ctx* ctx, sdmi_lora** out);
 /* Adds one target and copies its factors to the device.  Only while the adapter's scale is 0 (SDMI_ERR_STATE otherwise).  SDMI_ERR_INVALID: an unknown
  * target, a norm / bias / embedding, rank outside 1..256, a non-finite alpha, a target this adapter already has (the factor shapes are the caller's
- * to get right: the pointers carry none).  SDMI_ERR_UNSUPPORTED: the 3-channel RGB conv_in of the VAE encoder (packed in a padded form). */
+ * to get right: the pointers carry none).  SDMI_ERR_UNSUPPORTED: a conv_in packed with padded input channels -- the 3-channel RGB one of the VAE encoder, the
+ * 9-channel one of an inpainting UNet (an 8-channel one is stored as it is: an ordinary target). */
 int sdmi_lora_add(sdmi_lora* a, const char* target, const float* down, const float* up, int32_t rank, float alpha);
 /* Re-merges and re-packs every target of `a` with ALL adapters active on it; blocks until done.  A non-finite scale is SDMI_ERR_INVALID and changes nothing. */
 int sdmi_lora_set_scale(sdmi_lora* a, double scale);
@@ -538,7 +589,8 @@ int sdmi_op_resize(sdmi_ctx* ctx, const float* x, int32_t n, int32_t h, int32_t 
                    float* out);
 /* The checkpoint conversion kernel on its own (csrc/k_unpack.hip; no reference counterpart).
  * raw = ndim-D tensor of `dtype` (0 F32, 1 F16, 2 BF16) in host memory.
- * transform: 0 copy, 1 2-D transpose ([d0,d1] -> [d1,d0]), 2 conv [cout,3,kh,kw] with cin 3 padded to 4 (-> [cout,4,kh,kw], the 4th channel zero).
+ * transform: 0 copy, 1 2-D transpose ([d0,d1] -> [d1,d0]), 2 conv [cout,cin,kh,kw], cin < 32 and no multiple of 4, with cin padded to the next multiple of 4
+ * (-> [cout,pc,kh,kw], the added input channels zero: 3 -> 4 the VAE encoder's RGB conv_in, 9 -> 12 an inpainting UNet's; a cin that needs no padding is transform 0's).
  * out = the fp32 stage tensor.  Exact, on the bit patterns: f16 subnormals, infinities and NaN payloads included. */
 int sdmi_op_unpack_tensor(sdmi_ctx* ctx, const void* raw, int32_t dtype, int32_t ndim, const int64_t* dims, int32_t transform, float* out);
 /* timestep_embedding (unet/mod.rs:19-30): out [dim] for timestep t. */
@@ -565,7 +617,7 @@ int sdmi_last_call_stats(sdmi_ctx* ctx, double* gpu_ms, int64_t* n_kernels, doub
  * 6 conv_gemm_split (precision = 0: the conv/linear launches that run on the bf16 matrix pipe with three-way split fp32
  * operands, k_gemm3x.hip / k_gemm3p.hip; class 0 then holds the launches left on the fp32 matrix instruction), 7 split_rows (fp32 tensors
  * converted to bf16 planes for a plane GEMM outside their producer), 8 other (every launch of the path that is in no other class: layout converters, the
- * CFG + DDIM update, the sampler-choice step (k_sampler.hip), img2img's u8 -> fp32 input conversion, start latent and masked CFG + DDIM update, the resampler of the hires fix (k_resize.hip), timestep embedding, SiLU of the embedding, row softmax / transposes of the unfused VAE attention, u8 conversion), 9 geglu (the GEGLU gate kernels
+ * CFG + DDIM update, the sampler-choice step (k_sampler.hip), img2img's u8 -> fp32 input conversion, start latent and masked CFG + DDIM update, the conditioned UNet's input assembly and the inpainting conditioning / paste kernels (k_inpaint.hip), the resampler of the hires fix (k_resize.hip), timestep embedding, SiLU of the embedding, row softmax / transposes of the unfused VAE attention, u8 conversion), 9 geglu (the GEGLU gate kernels
  * where the gate is not fused into its GEMM; the quantising gate of precision = 2 included).  flops / bytes are the ALGORITHMIC work of
  * those launches (2*M*N*K; one read + one write of the tensor).  "profile_reset" clears. */
 int sdmi_profile_stats(sdmi_ctx* ctx, int32_t cls, double* ms, int64_t* launches, double* flops, double* bytes);

@@ -26,7 +26,7 @@ class SdmiConfig(C.Structure):
         ("device", C.c_int32), ("model_channels", C.c_int32), ("n_head", C.c_int32), ("ctx_dim", C.c_int32),
         ("latent_h", C.c_int32), ("latent_w", C.c_int32), ("vae_ch", C.c_int32), ("max_batch", C.c_int32),
         ("precision", C.c_int32), ("clip_layers", C.c_int32), ("clip_heads", C.c_int32), ("clip_vocab", C.c_int32),
-        ("clip_ctx", C.c_int32), ("reserved", C.c_int32 * 3),
+        ("clip_ctx", C.c_int32), ("unet_in_ch", C.c_int32), ("reserved", C.c_int32 * 2),
     ]
 
 
@@ -40,6 +40,11 @@ class SdmiSampler(C.Structure):
     """sdmi_sampler: the sampler choice of a context (sdmi_set_sampler)"""
     _fields_ = [("kind", C.c_int32), ("reserved0", C.c_int32), ("eta", C.c_double), ("noise_seed", C.c_uint64), ("image_base", C.c_int64),
                 ("reserved", C.c_int64 * 4)]
+
+
+class SdmiInpaint(C.Structure):
+    """sdmi_inpaint: the options of sdmi_inpaint_image"""
+    _fields_ = [("latent_blend", C.c_int32), ("paste_back", C.c_int32), ("reserved", C.c_int64 * 4)]
 
 
 class SdmiHires(C.Structure):
@@ -87,6 +92,13 @@ SIGNATURES = {
     "sdmi_img2img_timesteps": (C.c_int, [C.c_int32, C.c_size_t, C.c_double, _I32, C.c_int32, _I32]),
     "sdmi_img2img_latent": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F, C.c_int32, C.c_double, C.c_size_t, C.c_double, _F, _F, _F, C.c_uint64, _F]),
     "sdmi_img2img_image": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F, C.c_int32, C.c_double, C.c_size_t, C.c_double, _U8, _F, _F, C.c_uint64, _U8]),
+    "sdmi_unet_forward_cond": (C.c_int, [_CTX, _F, C.c_int32, _F, _F, C.c_int32, C.c_int32, _F]),
+    "sdmi_img2img_latent_cond": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F, C.c_int32, C.c_double, C.c_size_t, C.c_double, _F, _F, _F, C.c_uint64, _F, _F]),
+    "sdmi_img2img_latent_cond_dev": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_size_t, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "sdmi_inpaint_latent_mask": (C.c_int, [_U8, C.c_int32, C.c_int32, C.c_int32, _F]),
+    "sdmi_inpaint_cond": (C.c_int, [_CTX, _U8, _U8, C.c_int32, _F]),
+    "sdmi_inpaint_image": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F, C.c_int32, C.c_double, C.c_size_t, C.c_double, _U8, _U8, C.POINTER(SdmiInpaint), _F, C.c_uint64, _U8]),
+    "sdmi_inpaint_image_dev": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_size_t, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(SdmiInpaint), C.c_void_p, C.c_uint64, C.c_void_p]),
     "sdmi_set_sampler": (C.c_int, [_CTX, _SAMPLER]),
     "sdmi_get_sampler": (C.c_int, [_CTX, _SAMPLER]),
     "sdmi_sampler_coefs": (C.c_int, [_SAMPLER, _F, C.c_int32, _I32, C.c_int32, C.c_int64, C.POINTER(C.c_double)]),

@@ -225,6 +225,8 @@ Engine::Engine(const sdmi_config& cfg) : cfg_(cfg) {
     if (cfg.vae_ch % 32 || cfg.vae_ch <= 0) throw Error(SDMI_ERR_INVALID, "vae_ch must be a positive multiple of 32");
     if (cfg.n_head <= 0 || cfg.model_channels % cfg.n_head) throw Error(SDMI_ERR_INVALID, "n_head must divide model_channels");
     if (cfg.ctx_dim % 32 || cfg.ctx_dim <= 0) throw Error(SDMI_ERR_INVALID, "ctx_dim must be a positive multiple of 32");
+    if (cfg_.unet_in_ch == 0) cfg_.unet_in_ch = 4;   // a zeroed field: the latent alone
+    if (cfg_.unet_in_ch < 4 || cfg_.unet_in_ch > 12) throw Error(SDMI_ERR_INVALID, "unet_in_ch must be 4 (the latent alone) or 5 .. 12 (the latent + conditioning channels)");
     check_latent_size(cfg.latent_h, cfg.latent_w);
     lat_h_ = cfg.latent_h;
     lat_w_ = cfg.latent_w;
@@ -306,7 +308,7 @@ void Engine::build_model() {
     // layers and the time-embedding MLPs (M = n_steps rows, once per call) stay fp32
     // stride / pad: what the engine applies to this layer; checked against the dump's metadata files (load_conv2d, load.rs:118-160)
     auto conv = [&](ConvW& w, const std::string& path, int cin, int cout, int k, int stride = 1, int pad = -1) {
-        w.cin = cin; w.cout = cout; w.k = k;
+        w.cin = cin < 32 ? (cin + 3) / 4 * 4 : cin; w.cout = cout; w.k = k;   // what the layer reads: padded_cin of its weight (9 -> 12: a conditioned UNet's conv_in)
         w.dt = (bf16_ && cin % 64 == 0) ? 1 : 0;
         if (bf16_ && !w.dt && cin >= 32) throw Error(SDMI_ERR_UNSUPPORTED, "bf16: conv Cin must be a multiple of 64 (or < 32)");
         add(this, path + "/weight", 0, {cout, cin, k, k}, &w.bt, w.dt);
@@ -440,7 +442,7 @@ void Engine::build_model() {
     lin(lin2_time_, "unet/lin2_time_embed", ed, ed, true, /*keep_f32=*/true);
     struct Spec { BlockKind kind; const char* name; int cin, cout; };
     const Spec in_spec[12] = {
-        {BK_CONV, "conv", 4, c1},   {BK_RES_ST, "rt1", c1, c1}, {BK_RES_ST, "rt2", c1, c1}, {BK_DOWN, "d1", c1, c1},
+        {BK_CONV, "conv", cfg_.unet_in_ch, c1},   {BK_RES_ST, "rt1", c1, c1}, {BK_RES_ST, "rt2", c1, c1}, {BK_DOWN, "d1", c1, c1},
         {BK_RES_ST, "rt3", c1, c2}, {BK_RES_ST, "rt4", c2, c2}, {BK_DOWN, "d2", c2, c2},    {BK_RES_ST, "rt5", c2, c4},
         {BK_RES_ST, "rt6", c4, c4}, {BK_DOWN, "d3", c4, c4},    {BK_RES, "r1", c4, c4},     {BK_RES, "r2", c4, c4}};
     const Spec out_spec[12] = {
@@ -643,9 +645,7 @@ void Engine::ensure_arena(int group) {
     size_t total = 0;
     for (auto& e : entries_) {
         if (e.group != group || e.kind == 3 || *e.dst) continue;
-        size_t count = 1;
-        for (int i = 0; i < e.ndim; ++i) count *= (size_t)e.dims[i];
-        if (e.kind == 0 && e.dims[1] == 3) count = count / 3 * 4;   // RGB conv_in: packed with a zero 4th input channel
+        const size_t count = stage_elems(e);   // (a conv_in with padded input channels: the padded count)
         total += (count * (e.wdt ? 2 : 4) + 255) / 256 * 256;
     }
     if (total) {
@@ -660,9 +660,7 @@ void Engine::ensure_arena(int group) {
         size_t off = 0;
         for (auto& e : entries_) {
             if (e.group != group || e.kind == 3 || *e.dst) continue;
-            size_t count = 1;
-            for (int i = 0; i < e.ndim; ++i) count *= (size_t)e.dims[i];
-            if (e.kind == 0 && e.dims[1] == 3) count = count / 3 * 4;
+            const size_t count = stage_elems(e);
             *e.dst = reinterpret_cast<float*>(base + off);
             off += (count * (e.wdt ? 2 : 4) + 255) / 256 * 256;
         }
@@ -719,9 +717,15 @@ static size_t entry_count(const WeightEntry& e) {
     return count;
 }
 
+// THE rule for a convolution's stored input channels: Cin < 32 is kept as one channel slice, which the GEMM kernels read in 16-byte pieces, so it is zero-padded
+// up to the next multiple of 4 (the RGB conv_in of the VAE encoder 3 -> 4, the 9-channel conv_in of an inpainting UNet 9 -> 12; 4 and 8 stay).
+int Engine::padded_cin(const WeightEntry& e) {
+    return (e.kind == 0 && e.dims[1] < 32) ? (int)((e.dims[1] + 3) / 4 * 4) : (int)e.dims[1];
+}
+
 size_t Engine::stage_elems(const WeightEntry& e) {
     const size_t count = entry_count(e);
-    return (e.kind == 0 && e.dims[1] == 3) ? count / 3 * 4 : count;   // RGB conv_in: a zero 4th input channel
+    return e.kind == 0 ? count / (size_t)e.dims[1] * (size_t)padded_cin(e) : count;
 }
 
 void Engine::pack_entry(WeightEntry& e, float* stage) {
@@ -729,7 +733,7 @@ void Engine::pack_entry(WeightEntry& e, float* stage) {
     if (e.pre_scale != 1.f) SDMI_HIP(launch_scale_f32(stage, (long long)n_stage, e.pre_scale, stream_));
     hipError_t err;
     if (e.kind == 0) {
-        const int cout = (int)e.dims[0], cin = e.dims[1] == 3 ? 4 : (int)e.dims[1], k = (int)e.dims[2];
+        const int cout = (int)e.dims[0], cin = padded_cin(e), k = (int)e.dims[2];
         if (!(cin % 32 == 0 || (cin < 32 && cin % 4 == 0))) throw Error(SDMI_ERR_UNSUPPORTED, "conv Cin must be a multiple of 32, or < 32 and a multiple of 4");
         err = e.wdt ? launch_pack_conv_weight_bf16(stage, *e.dst, cout, cin, k, k, stream_)
                     : launch_pack_conv_weight(stage, *e.dst, cout, cin, k, k, stream_);
@@ -765,7 +769,7 @@ void Engine::pack_entry(WeightEntry& e, float* stage) {
     SDMI_HIP(err);
     if (!e.wdt) {   // the bf16 planes of the packed fp32 rows (k_gemm3x.hip)
         const long long rows = e.kind == 0 ? e.dims[0] : e.dims[1];
-        const long long K = e.kind == 0 ? (e.dims[1] == 3 ? 4 : e.dims[1]) * e.dims[2] * e.dims[3] : e.dims[0];
+        const long long K = e.kind == 0 ? (long long)padded_cin(e) * e.dims[2] * e.dims[3] : e.dims[0];
         void* planes = const_cast<void*>(split_planes(*e.dst));
         if (planes && K % 32 == 0) SDMI_HIP(launch_pack_split3(*e.dst, planes, rows, (int)K, stream_, b3_grouped(rows)));
     }
@@ -787,7 +791,7 @@ void Engine::stage_commit(WeightEntry& e, size_t offset, int half) {
         SDMI_HIP(hipMemcpyAsync(*e.dst, host, count * sizeof(float), hipMemcpyHostToDevice, stream_));
     } else {
         float* stage = reinterpret_cast<float*>(st.dev[half] + offset);
-        const size_t n_stage = stage_elems(e);   // (the RGB conv_in: padded on the host by the caller of stage_commit)
+        const size_t n_stage = stage_elems(e);   // (a padded conv_in: padded on the host by the caller of stage_commit)
         SDMI_HIP(hipMemcpyAsync(stage, host, n_stage * sizeof(float), hipMemcpyHostToDevice, stream_));
         if (e.master) SDMI_HIP(hipMemcpyAsync(e.master, stage, n_stage * sizeof(float), hipMemcpyDeviceToDevice, stream_));
         pack_entry(e, stage);
@@ -796,16 +800,15 @@ void Engine::stage_commit(WeightEntry& e, size_t offset, int half) {
     finalized_ = false;
 }
 
-// copies one tensor into the pinned ring (padding the RGB conv_in to 4 input channels) and commits it
+// copies one tensor into the pinned ring (zero-padding the input channels of a conv_in that is stored padded: padded_cin) and commits it
 void Engine::upload_weight(WeightEntry& e, const float* data) {
     const size_t count = entry_count(e);
     size_t off; int half;
-    if (e.kind == 0 && e.dims[1] == 3) {
-        const int cout = (int)e.dims[0], T = (int)(e.dims[2] * e.dims[3]);
-        float* dst = reinterpret_cast<float*>(stage_reserve((size_t)cout * 4 * T * sizeof(float), &off, &half));
-        std::memset(dst, 0, (size_t)cout * 4 * T * sizeof(float));
-        for (int o = 0; o < cout; ++o)
-            for (int c = 0; c < 3; ++c) std::memcpy(dst + ((size_t)o * 4 + c) * T, data + ((size_t)o * 3 + c) * T, T * sizeof(float));
+    if (e.kind == 0 && padded_cin(e) != e.dims[1]) {
+        const int cout = (int)e.dims[0], T = (int)(e.dims[2] * e.dims[3]), cin = (int)e.dims[1], pc = padded_cin(e);
+        float* dst = reinterpret_cast<float*>(stage_reserve((size_t)cout * pc * T * sizeof(float), &off, &half));
+        std::memset(dst, 0, (size_t)cout * pc * T * sizeof(float));
+        for (int o = 0; o < cout; ++o) std::memcpy(dst + (size_t)o * pc * T, data + (size_t)o * cin * T, (size_t)cin * T * sizeof(float));
     } else {
         char* dst = stage_reserve(count * sizeof(float), &off, &half);
         std::memcpy(dst, data, count * sizeof(float));
@@ -988,7 +991,7 @@ void Engine::load_weights_safetensors(const char* path) {
         if (!ok)
             throw Error(SDMI_ERR_WEIGHTS, "load_weights_safetensors: '" + key + "' has shape " + shape_str(t->shape.data(), t->shape.size()) +
                                               ", the configured model expects " + shape_str(want, (size_t)e.ndim) + " ('" + e.name + "')");
-        jobs.push_back(Job{&e, t, dt, transposed ? 1 : (e.kind == 0 && e.dims[1] == 3) ? 2 : 0});
+        jobs.push_back(Job{&e, t, dt, transposed ? 1 : (e.kind == 0 && padded_cin(e) != e.dims[1]) ? 2 : 0});
     }
     if (jobs.empty()) throw Error(SDMI_ERR_WEIGHTS, std::string("load_weights_safetensors: no tensor of ") + path + " matches the configured model");
     std::vector<float> schedule;
@@ -1038,7 +1041,7 @@ void Engine::load_weights_safetensors(const char* path) {
         {
             ProfScope ps_o(this, PC_OTHER, 0, (double)j.t->nbytes + (double)(e.kind <= 1 ? stage_elems(e) : entry_count(e)) * 4);
             ps_o.set_tag("unpack %s t%d %lldx%lld", j.t->dtype.c_str(), j.transform, d0, d1);
-            SDMI_HIP(launch_unpack_tensor(dev, j.dtype, j.transform, d0, d1, out, stream_));
+            SDMI_HIP(launch_unpack_tensor(dev, j.dtype, j.transform, d0, d1, out, stream_, (int)e.dims[1]));
         }
         count_kernel();
         if (e.kind <= 1) {
@@ -1060,7 +1063,7 @@ void Engine::op_unpack_tensor(const void* raw, int dtype, int ndim, const int64_
     if (transform == 1) { d0 = dims[0]; d1 = dims[1]; }
     else if (transform == 2) { d0 = dims[0]; d1 = dims[2] * dims[3]; }
     else { d0 = 1; for (int i = 0; i < ndim; ++i) d0 *= dims[i]; d1 = 1; }
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_unpack_tensor(raw, dtype, transform, d0, d1, out, stream_)); }
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_unpack_tensor(raw, dtype, transform, d0, d1, out, stream_, transform == 2 ? (int)dims[1] : 3)); }
     count_kernel();
 }
 
@@ -1127,7 +1130,8 @@ void Engine::lora_add(sdmi_lora* a, const char* target, const float* down, const
     if (it == entry_index_.end()) throw Error(SDMI_ERR_INVALID, std::string("lora_add: unknown tensor '") + target + "'");
     const WeightEntry& e = entries_[it->second];
     if (e.kind > 1) throw Error(SDMI_ERR_INVALID, std::string("lora_add: '") + target + "' is not a conv or Linear weight");
-    if (e.kind == 0 && e.dims[1] == 3) throw Error(SDMI_ERR_UNSUPPORTED, std::string("lora_add: '") + target + "' is the 3-channel conv_in, packed in a padded form");
+    if (e.kind == 0 && padded_cin(e) != e.dims[1])
+        throw Error(SDMI_ERR_UNSUPPORTED, std::string("lora_add: '") + target + "' is the " + std::to_string(e.dims[1]) + "-channel conv_in, packed in a padded form");
     if (rank < 1 || rank > 256) throw Error(SDMI_ERR_INVALID, "lora_add: rank must be 1 .. 256");
     if (!std::isfinite(alpha)) throw Error(SDMI_ERR_INVALID, "lora_add: alpha is not finite");
     for (const LoraTarget& t : a->targets)
@@ -1236,13 +1240,12 @@ void Engine::effective_weight(const char* name, float* out, size_t n) {
     if (ns == n) {
         SDMI_HIP(hipMemcpyAsync(out, stage.p, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
         SDMI_HIP(hipStreamSynchronize(stream_));
-    } else {   // the RGB conv_in: drop the zero 4th input channel
+    } else {   // a padded conv_in: drop the zero input channels
         std::vector<float> padded(ns);
         SDMI_HIP(hipMemcpyAsync(padded.data(), stage.p, ns * sizeof(float), hipMemcpyDeviceToHost, stream_));
         SDMI_HIP(hipStreamSynchronize(stream_));
-        const size_t T = (size_t)(e.dims[2] * e.dims[3]);
-        for (size_t o = 0; o < (size_t)e.dims[0]; ++o)
-            for (size_t c = 0; c < 3; ++c) std::memcpy(out + (o * 3 + c) * T, padded.data() + (o * 4 + c) * T, T * sizeof(float));
+        const size_t T = (size_t)(e.dims[2] * e.dims[3]), cin = (size_t)e.dims[1], pc = (size_t)padded_cin(e);
+        for (size_t o = 0; o < (size_t)e.dims[0]; ++o) std::memcpy(out + o * cin * T, padded.data() + o * pc * T, cin * T * sizeof(float));
     }
 }
 
@@ -1294,7 +1297,7 @@ void Engine::load_weights_dir(const char* dir) {
         if ((e.group == 1 && !have_clip) || (e.group == 2 && !have_enc)) continue;
         const std::string path = std::string(dir) + "/" + e.name + ".npy";
         const size_t count = entry_count(e);
-        if (e.kind == 0 && e.dims[1] == 3) {   // rare (one tensor): through the padding path
+        if (e.kind == 0 && padded_cin(e) != e.dims[1]) {   // rare (a padded conv_in): through the padding path
             std::vector<float> raw;
             read_npy_f32(path, [&](size_t n) { raw.resize(n); return raw.data(); });
             if (raw.size() != count + (size_t)e.ndim) throw Error(SDMI_ERR_WEIGHTS, "shape prefix does not match payload in " + path);
@@ -2267,7 +2270,8 @@ void Engine::unet_prepare(const float* ctx_packed, int nb, int t_max, const int*
 void Engine::unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bool cfg_pair) {
     Range rng(this, "UNet::forward step " + std::to_string(step));
     const int H = lat_h_, W = lat_w_;
-    Act x; x.p = const_cast<float*>(x_nhwc); x.n = nb; x.h = H; x.w = W; x.c = 4; x.dt = 0;  // latents stay fp32
+    // latents stay fp32; a conditioned model (unet_in_ch > 4) reads the assembled [latent | cond | pad] rows of launch_assemble_unet_in
+    Act x; x.p = const_cast<float*>(x_nhwc); x.n = nb; x.h = H; x.w = W; x.c = in_blocks_[0].conv.cin; x.dt = 0;
 
     // every block's last kernel writes `y` (dense or a channel slice)
     auto run_block = [&](const UBlock& b, const Act& in, Act& y) {
@@ -2384,8 +2388,37 @@ void Engine::clip_forward_dev(const int32_t* tokens, int n, int T, float* out) {
     layer_norm(clip_ln_, x.f(), M, out, 0);
 }
 
-void Engine::unet_forward_dev(const float* x_nchw, int t, const float* context, int n, int T, float* out_nchw) {
+// ---- conditioned UNet input (unet_in_ch > 4; include/sdmi.h "conditioned UNet") ---------------------------------------
+// An entry point that takes no conditioning cannot serve a model that needs it, and the other way round: both are SDMI_ERR_STATE.
+void Engine::check_cond(const char* entry, bool given) const {
+    if (cond_ch() > 0 && !given)
+        throw Error(SDMI_ERR_STATE, std::string(entry) + ": this context's UNet takes " + std::to_string(cond_ch()) + " conditioning channels (unet_in_ch = " +
+                                        std::to_string(cfg_.unet_in_ch) + "): use the _cond entry (sdmi_unet_forward_cond, sdmi_img2img_latent_cond, sdmi_inpaint_image)");
+    if (cond_ch() == 0 && given) throw Error(SDMI_ERR_STATE, std::string(entry) + ": this context's UNet takes no conditioning channels (unet_in_ch = 4)");
+}
+
+// the caller's cond [n, cond_ch, h, w] (device, NCHW) -> a pool buffer [n][hw][padded_in_ch - 4] (the caller frees it)
+float* Engine::cond_to_nhwc(const float* cond_nchw, int n) {
+    const long long hw = (long long)lat_h_ * lat_w_;
+    const int pcc = unet_in_padded() - 4;
+    float* c = reinterpret_cast<float*>(pool_.alloc((size_t)n * hw * pcc * sizeof(float)));
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_cond_nchw_to_nhwc(cond_nchw, c, n, cond_ch(), hw, pcc, stream_)); }
+    count_kernel();
+    return c;
+}
+
+// unet_in [rows][hw][4] + cond [n][hw][pc - 4] -> dst [rows][hw][pc], in front of a unet_run
+void Engine::assemble_unet_in(const float* unet_in, const float* cond_nhwc, int rows, int n, float* dst) {
+    const long long hw = (long long)lat_h_ * lat_w_;
+    const int pc = unet_in_padded();
+    ProfScope ps_o(this, PC_OTHER, 0, (double)rows * hw * (4 + (pc - 4) + pc) * 4.0);
+    SDMI_HIP(launch_assemble_unet_in(unet_in, cond_nhwc, dst, (long long)rows * hw, (long long)n * hw, pc, cond_ch(), stream_));
+    count_kernel();
+}
+
+void Engine::unet_forward_dev(const float* x_nchw, int t, const float* context, int n, int T, float* out_nchw, const float* cond_nchw) {
     if (!finalized_) throw Error(SDMI_ERR_STATE, "weights not finalized");
+    check_cond("unet_forward", cond_nchw != nullptr);
     if (n <= 0 || T <= 0) throw Error(SDMI_ERR_INVALID, "unet_forward: n and T must be positive");
     check_batch(n);
     const int H = lat_h_, W = lat_w_;
@@ -2394,6 +2427,13 @@ void Engine::unet_forward_dev(const float* x_nchw, int t, const float* context, 
     Buf xin(this, (size_t)n * H * W * 4 * 4), xout(this, (size_t)n * H * W * 4 * 4);
     { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nchw_to_nhwc(x_nchw, xin.f(), n, 4, H, W, 1.0f, stream_)); }
     count_kernel();
+    if (cond_nchw) {
+        Buf xc(this, (size_t)n * H * W * unet_in_padded() * 4);
+        float* c = cond_to_nhwc(cond_nchw, n);
+        assemble_unet_in(xin.f(), c, n, n, xc.f());
+        pool_.free(c);
+        unet_run(xc.f(), n, 0, xout.f());
+    } else
     unet_run(xin.f(), n, 0, xout.f());
     { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(xout.f(), out_nchw, n, 4, H, W, stream_)); }
     count_kernel();
@@ -2404,6 +2444,7 @@ void Engine::unet_forward_dev(const float* x_nchw, int t, const float* context, 
 void Engine::sample_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale,
                                size_t n_steps, const float* init_latent, float* latent_out, bool out_nhwc) {
     if (!finalized_) throw Error(SDMI_ERR_STATE, "weights not finalized");
+    check_cond("sample_latent", false);
     if (n <= 0 || T <= 0 || Tu <= 0) throw Error(SDMI_ERR_INVALID, "sample_latent: n, T, Tu must be positive");
     check_batch(n);
     const size_t total = alphas_.size();
@@ -2433,7 +2474,7 @@ void Engine::set_sampler(const sdmi_sampler* s) {
 
 void Engine::sample_loop(const float* context, int n, int T, const float* uncond, int Tu, double scale, const std::vector<int>& ts,
                          size_t step_size, const std::function<void(float* latent, float* unet_in, long long per_half)>& start,
-                         const Blend* blend, float* latent_out, bool out_nhwc) {
+                         const Blend* blend, float* latent_out, bool out_nhwc, const float* cond_nhwc) {
     const int H = lat_h_, W = lat_w_, cd = cfg_.ctx_dim;
     const int nb = 2 * n, t_max = std::max(T, Tu);
 
@@ -2451,6 +2492,9 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
 
     const long long per_half = (long long)n * H * W * 4;
     Buf latent(this, per_half * 4), unet_in(this, 2 * per_half * 4), eps(this, 2 * per_half * 4);
+    // a conditioned model: the update kernels keep writing unet_in [2n][hw][4]; one launch per step assembles [latent | cond | pad] from it (k_inpaint.hip)
+    std::unique_ptr<Buf> unet_in_c;
+    if (cond_nhwc) unet_in_c.reset(new Buf(this, (size_t)(2 * per_half / 4) * unet_in_padded() * 4));
     // sampler choice: the coefficient table of the call and its history slots (x0 for DPM-Solver++(2M), three e for PLMS)
     const bool custom = sampler_.kind != 0 || sampler_.eta != 0.0;
     const int depth = !custom ? 0 : sampler_.kind == 1 ? 1 : sampler_.kind == 2 ? 3 : 0;
@@ -2473,7 +2517,8 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
         c.sqrt_cur = (float)std::sqrt(cur);
         c.sqrt_prev = (float)std::sqrt(prev);
         c.dir_coef = (float)std::sqrt(1.0 - prev - 0.0);                                 // :153 (sigma = 0)
-        unet_run(unet_in.f(), nb, (int)s, eps.f(), opt_cfg_share_ != 0);   // unet_in = [latent | latent]: a CFG pair
+        if (cond_nhwc) assemble_unet_in(unet_in.f(), cond_nhwc, nb, n, unet_in_c->f());
+        unet_run(cond_nhwc ? unet_in_c->f() : unet_in.f(), nb, (int)s, eps.f(), opt_cfg_share_ != 0);   // unet_in = [latent | latent]: a CFG pair (with the same cond rows)
         if (custom) {
             const double* k = &coefs[s * 8];
             SamplerStep p{};
@@ -2523,9 +2568,12 @@ std::vector<int> Engine::img2img_schedule(int n, int T, int Tu, size_t n_steps, 
 }
 
 void Engine::img2img_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps,
-                                double strength, const float* z0, const float* mask, const float* noise, uint64_t seed, float* latent_out) {
+                                double strength, const float* z0, const float* mask, const float* noise, uint64_t seed, float* latent_out, const float* cond_nchw) {
+    if (finalized_) check_cond("img2img_latent", cond_nchw != nullptr);
     size_t step_size = 0;
     const std::vector<int> ts = img2img_schedule(n, T, Tu, n_steps, strength, &step_size);
+    struct PoolPtr { DevPool& pool; float* p; ~PoolPtr() { if (p) pool.free(p); } } cond{pool_, nullptr};
+    if (cond_nchw) cond.p = cond_to_nhwc(cond_nchw, n);
     const long long hw = (long long)lat_h_ * lat_w_, elems = (long long)n * hw * 4;
     const double a0 = (double)alphas_[ts[0]];
     const float sqrt_a = (float)std::sqrt(a0), sqrt_1ma = (float)std::sqrt(1.0 - a0);
@@ -2535,11 +2583,12 @@ void Engine::img2img_latent_dev(const float* context, int n, int T, const float*
         { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_img2img_start(z0, false, noise, seed, sqrt_a, sqrt_1ma, latent, unet_in, per_half,
                                                                         mask ? z0k.f() : nullptr, mask ? e0k.f() : nullptr, n, hw, stream_)); }
         count_kernel();
-    }, mask ? &blend : nullptr, latent_out);
+    }, mask ? &blend : nullptr, latent_out, false, cond.p);
 }
 
 void Engine::img2img_image_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps,
-                               double strength, const uint8_t* init_rgb, const float* mask, const float* noise, uint64_t seed, float* latent_out) {
+                               double strength, const uint8_t* init_rgb, const float* mask, const float* noise, uint64_t seed, float* latent_out, const float* cond_nhwc) {
+    if (finalized_) check_cond("img2img_image", cond_nhwc != nullptr);
     if (finalized_ && !enc_ready_) throw Error(SDMI_ERR_STATE, "VAE encoder weights are not loaded (autoencoder/encoder/..., autoencoder/quant_conv)");
     size_t step_size = 0;
     const std::vector<int> ts = img2img_schedule(n, T, Tu, n_steps, strength, &step_size);
@@ -2562,7 +2611,61 @@ void Engine::img2img_image_dev(const float* context, int n, int T, const float* 
             count_kernel();
             release(q8);
         }
-    }, mask ? &blend : nullptr, latent_out);
+    }, mask ? &blend : nullptr, latent_out, false, cond_nhwc);
+}
+
+// ---- inpainting (unet_in_ch = 9; include/sdmi.h "inpainting") ---------------------------------------------------------
+void Engine::check_inpaint(const char* entry) const {
+    if (!finalized_) throw Error(SDMI_ERR_STATE, "weights not finalized");
+    if (cfg_.unet_in_ch != 9)
+        throw Error(SDMI_ERR_STATE, std::string(entry) + ": needs an inpainting UNet (unet_in_ch = 9: latent, mask, masked-picture latent); this context has unet_in_ch = " +
+                                        std::to_string(cfg_.unet_in_ch));
+    if (!enc_ready_) throw Error(SDMI_ERR_STATE, "VAE encoder weights are not loaded (autoencoder/encoder/..., autoencoder/quant_conv)");
+}
+
+// cond rows [n][hw][8] = latent mask | 0.18215 * posterior mean of the masked picture | 0 0 0; lat_mask (may be null) [n][hw].  One image at a time through
+// encode_one, as img2img_image_dev.
+void Engine::inpaint_cond_nhwc(const uint8_t* init_rgb, const uint8_t* mask_u8, int n, float* cond_nhwc, float* lat_mask) {
+    const int H = lat_h_, W = lat_w_;
+    const long long hw = (long long)H * W;
+    for (int i = 0; i < n; ++i) {
+        Act rgb = new_act(1, 8 * H, 8 * W, 4, /*dt=*/0);
+        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_rgb_u8_masked_to_nhwc4(init_rgb + (size_t)i * 3 * 64 * hw, mask_u8 + (size_t)i * 64 * hw, rgb.p, 64 * hw, stream_)); }
+        count_kernel();
+        Act q8 = encode_one(rgb);
+        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_inpaint_cond_pack(q8.p, mask_u8 + (size_t)i * 64 * hw, cond_nhwc + (size_t)i * hw * 8, lat_mask ? lat_mask + (size_t)i * hw : nullptr, H, W, stream_)); }
+        count_kernel();
+        release(q8);
+    }
+}
+
+void Engine::inpaint_cond_dev(const uint8_t* init_rgb, const uint8_t* mask_u8, int n, float* cond_nchw) {
+    check_inpaint("inpaint_cond");
+    if (n <= 0) throw Error(SDMI_ERR_INVALID, "inpaint_cond: n must be positive");
+    check_batch(n);
+    const int H = lat_h_, W = lat_w_;
+    Buf cond(this, (size_t)n * H * W * 8 * sizeof(float));
+    inpaint_cond_nhwc(init_rgb, mask_u8, n, cond.f(), nullptr);
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw_slice(cond.f(), cond_nchw, n, 8, 5, H, W, stream_)); }
+    count_kernel();
+}
+
+void Engine::inpaint_image_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps, double strength,
+                               const uint8_t* init_rgb, const uint8_t* mask_u8, const sdmi_inpaint* opt, const float* noise, uint64_t seed, uint8_t* rgb_out) {
+    check_inpaint("inpaint_image");
+    if (n <= 0) throw Error(SDMI_ERR_INVALID, "inpaint_image: n must be positive");
+    check_batch(n);
+    const bool latent_blend = opt && opt->latent_blend != 0, paste_back = opt && opt->paste_back != 0;
+    const int H = lat_h_, W = lat_w_;
+    const size_t hw = (size_t)H * W;
+    Buf cond(this, (size_t)n * hw * 8 * sizeof(float)), lmask(this, latent_blend ? (size_t)n * hw * sizeof(float) : 256), lat(this, (size_t)n * hw * 4 * sizeof(float));
+    inpaint_cond_nhwc(init_rgb, mask_u8, n, cond.f(), latent_blend ? lmask.f() : nullptr);
+    img2img_image_dev(context, n, T, uncond, Tu, scale, n_steps, strength, init_rgb, latent_blend ? lmask.f() : nullptr, noise, seed, lat.f(), cond.f());
+    decode_latent_dev(lat.f(), n, (float)(1.0 / 0.18215), nullptr, rgb_out);
+    if (paste_back) {
+        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_inpaint_paste(rgb_out, init_rgb, mask_u8, rgb_out, (long long)n * 64 * hw, stream_)); }
+        count_kernel();
+    }
 }
 
 // ---- latent resampler + hires fix (include/sdmi.h "hires fix") ----------------------------------------------------
@@ -2646,6 +2749,7 @@ void Engine::check_hires(const sdmi_hires* hr) {
 void Engine::hires_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps, const float* init_latent,
                               const sdmi_hires& hr, const float* hires_noise, float* latent_out) {
     check_hires(&hr);
+    if (finalized_) check_cond("hires", false);
     const size_t steps2 = hr.hires_steps ? (size_t)hr.hires_steps : n_steps;
     {   // the second pass's argument errors before the first pass runs
         size_t step_size = 0;

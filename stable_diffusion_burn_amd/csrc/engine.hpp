@@ -134,7 +134,7 @@ struct WeightEntry {
     float** dsts = nullptr;
     float pre_scale = 1.f;    // the tensor is multiplied by this in fp32 before it is packed (bf16 / MXFP8 query projections: attn_bf16_q_scale)
     bool set = false;
-    float* master = nullptr;  // option keep_masters, kind 0 / 1: the fp32 tensor as the packing kernels read it (reference layout, RGB conv_in padded to 4 channels, before pre_scale)
+    float* master = nullptr;  // option keep_masters, kind 0 / 1: the fp32 tensor as the packing kernels read it (reference layout, a conv_in's input channels padded by padded_cin, before pre_scale)
 };
 
 // One target of a LoRA adapter (sdmi_lora_add): the factors on the device as the caller stored them -- down [rank][in] / [rank][cin k k],
@@ -169,7 +169,12 @@ public:
     void effective_weight(const char* name, float* out, size_t n);
 
     // hot path (device pointers, reference layouts)
-    void unet_forward_dev(const float* x_nchw, int t, const float* context, int n, int T, float* out_nchw);
+    // cond_nchw: null for a 4-channel model; [n, cond_ch, h, w] for a conditioned one (unet_in_ch > 4) -- anything else is SDMI_ERR_STATE
+    void unet_forward_dev(const float* x_nchw, int t, const float* context, int n, int T, float* out_nchw, const float* cond_nchw = nullptr);
+    // Conditioning channels of the UNet input: cond_ch = unet_in_ch - 4 per-call channels next to the latent, stored padded to a multiple of 4 (padded_cin).
+    int cond_ch() const { return cfg_.unet_in_ch - 4; }
+    int unet_in_padded() const { return (cfg_.unet_in_ch + 3) / 4 * 4; }
+    void check_cond(const char* entry, bool given) const;
     // CLIP::forward (clip/mod.rs:56-75): int32 tokens [n, T] on the device -> [n, T, ctx_dim] fp32 (both precisions)
     void clip_forward_dev(const int32_t* tokens, int n, int T, float* out);
     bool clip_ready() const { return clip_ready_; }
@@ -182,9 +187,19 @@ public:
     // _latent: z0 [n,4,h,w] NCHW; _image: z0 = 0.18215 * encode_image(rgb / 127.5 - 1), rgb = n x [8h,8w,3] u8 (needs the
     // encoder weights).  latent_out [n,4,h,w].  Device pointers.
     void img2img_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps,
-                            double strength, const float* z0, const float* mask, const float* noise, uint64_t seed, float* latent_out);
+                            double strength, const float* z0, const float* mask, const float* noise, uint64_t seed, float* latent_out,
+                            const float* cond_nchw = nullptr);   // cond [n, cond_ch, h, w]: only the UNet sees it
     void img2img_image_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps,
-                           double strength, const uint8_t* init_rgb, const float* mask, const float* noise, uint64_t seed, float* latent_out);
+                           double strength, const uint8_t* init_rgb, const float* mask, const float* noise, uint64_t seed, float* latent_out,
+                           const float* cond_nhwc = nullptr);    // cond rows [n][hw][padded_in_ch - 4], as inpaint_cond_nhwc writes them
+    // Inpainting checkpoints (unet_in_ch = 9; include/sdmi.h "inpainting"): cond = [latent mask | 0.18215 * encode(masked picture)[:, :4]].  init_rgb n x [8h,8w,3] u8,
+    // mask_u8 n x [8h,8w] u8 (>= 128: regenerate), device pointers.  inpaint_cond_dev: cond_nchw [n,5,h,w].  inpaint_image_dev: cond, z0 = 0.18215 * encode(init),
+    // the img2img loop (opt->latent_blend: the latent mask as its blend mask), latent_to_image, opt->paste_back: kept pixels copied from init_rgb.
+    void check_inpaint(const char* entry) const;
+    void inpaint_cond_nhwc(const uint8_t* init_rgb, const uint8_t* mask_u8, int n, float* cond_nhwc, float* lat_mask);
+    void inpaint_cond_dev(const uint8_t* init_rgb, const uint8_t* mask_u8, int n, float* cond_nchw);
+    void inpaint_image_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps, double strength,
+                           const uint8_t* init_rgb, const uint8_t* mask_u8, const sdmi_inpaint* opt, const float* noise, uint64_t seed, uint8_t* rgb_out);
     // Hires fix (include/sdmi.h "hires fix"): sample_latent at hr.base_h x base_w, the NHWC latent resampled on the device to the
     // current size, img2img_latent_dev from it (no mask).  init_latent [n,4,base_h,base_w], hires_noise [n,4,H,W] or null, latent_out [n,4,H,W]: device pointers.
     // The size is switched for the first pass and restored on every way out.
@@ -194,7 +209,7 @@ public:
     // x [n][h*w][4] -> y [n][oh*ow][4] (NHWC4, device) by the tables of sdmi_resize_weights: horizontal pass, then vertical; an unchanged axis is skipped
     void resize_nhwc4(const float* x, int n, int h, int w, int oh, int ow, int mode, int antialias, float* y);
     void op_resize(const float* x_nchw, int n, int h, int w, int oh, int ow, int mode, int antialias, float* out_nchw);
-    // k_unpack.hip on its own: raw = a checkpoint tensor's bytes (dtype 0 F32 / 1 F16 / 2 BF16), transform 0 copy / 1 2-D transpose / 2 RGB conv padded to 4 input channels
+    // k_unpack.hip on its own: raw = a checkpoint tensor's bytes (dtype 0 F32 / 1 F16 / 2 BF16), transform 0 copy / 1 2-D transpose / 2 a conv_in's input channels (dims[1] < 32) padded to the next multiple of 4
     void op_unpack_tensor(const void* raw, int dtype, int ndim, const int64_t* dims, int transform, float* out);
     // sampler choice (sdmi_set_sampler): sticky, read by sample_loop -- every sampling entry point.  The default (kind 0,
     // eta 0) is the reference's DDIM on its own launches.  check_sampler throws SDMI_ERR_INVALID for what the header lists; null = the default.
@@ -327,6 +342,7 @@ private:
     // element count of stage_elems; clobbered by pre_scale) -> the entry's packed slot, its MXFP8 copy and its bf16 planes.  Enqueues on stream_.
     void pack_entry(WeightEntry& e, float* stage);
     static size_t stage_elems(const WeightEntry& e);
+    static int padded_cin(const WeightEntry& e);   // a conv weight's stored input channels (engine.cpp: the one rule)
     // option keep_masters: fp32 master copies of every conv / Linear tensor, one arena per weight group laid out like the packed one (ensure_arena)
     int opt_keep_masters_ = 0;
     std::vector<sdmi_lora*> loras_;      // in creation order: the order the deltas of a shared target are added in
@@ -424,7 +440,10 @@ private:
     struct Blend { const float* mask; const float* z0; const float* eps; };
     void sample_loop(const float* context, int n, int T, const float* uncond, int Tu, double scale, const std::vector<int>& ts,
                      size_t step_size, const std::function<void(float* latent, float* unet_in, long long per_half)>& start,
-                     const Blend* blend, float* latent_out, bool out_nhwc = false);
+                     const Blend* blend, float* latent_out, bool out_nhwc = false, const float* cond_nhwc = nullptr);
+    // cond_nhwc (a conditioned model): [n][hw][padded_in_ch - 4]; every unet_run is preceded by assemble_unet_in into a buffer of the call
+    float* cond_to_nhwc(const float* cond_nchw, int n);
+    void assemble_unet_in(const float* unet_in, const float* cond_nhwc, int rows, int n, float* dst);
     // argument checks of both img2img entry points; returns the timesteps (rule 1) and the schedule's step size
     std::vector<int> img2img_schedule(int n, int T, int Tu, size_t n_steps, double strength, size_t* step_size);
 

@@ -17,7 +17,8 @@
 //               time a device-to-device copy takes for the same output bytes, in a kernel class that is 5 % of a load.  16-byte accesses need every row of that side to start 16-byte aligned
 //               (C % 8 == 0 for 16-bit, C % 4 == 0 for F32 sources; R % 4 == 0 for the result): then a piece is inside or outside the tensor as a whole
 //               and edge tiles only mask pieces.  Otherwise (odd row lengths) that side goes element by element, still coalesced.
-//   pad         the VAE encoder's RGB conv_in [cout][3][T] -> [cout][4][T] with a zero 4th input channel (what upload_weight does on the host).
+//   pad         a conv_in whose input channels are stored padded, [cout][cin][T] -> [cout][pc][T] with pc = cin rounded up to a multiple of 4 and the channels
+//               cin .. pc - 1 zero (what upload_weight does on the host): the VAE encoder's RGB conv_in 3 -> 4, an inpainting UNet's conv_in 9 -> 12.
 #include <algorithm>
 #include <cstdint>
 
@@ -97,13 +98,13 @@ __global__ __launch_bounds__(256) void unpack_copy_kernel(const void* __restrict
 }
 
 template <int DT>
-__global__ __launch_bounds__(256) void unpack_pad3_kernel(const void* __restrict__ raw, float* __restrict__ out, long long cout, int T) {
-    const long long n = cout * 4 * T;
+__global__ __launch_bounds__(256) void unpack_pad_kernel(const void* __restrict__ raw, float* __restrict__ out, long long cout, int cin, int pc, int T) {
+    const long long n = cout * pc * T;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const int t = (int)(i % T);
-        const int c = (int)((i / T) & 3);
-        const long long o = i / ((long long)4 * T);
-        out[i] = c == 3 ? 0.f : load_one<DT>(raw, (o * 3 + c) * T + t);
+        const int c = (int)((i / T) % pc);
+        const long long o = i / ((long long)pc * T);
+        out[i] = c >= cin ? 0.f : load_one<DT>(raw, (o * cin + c) * T + t);
     }
 }
 
@@ -153,7 +154,7 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 
 }  // namespace
 
-hipError_t launch_unpack_tensor(const void* raw, int dtype, int transform, long long d0, long long d1, float* out, hipStream_t s) {
+hipError_t launch_unpack_tensor(const void* raw, int dtype, int transform, long long d0, long long d1, float* out, hipStream_t s, int cin) {
     if (!raw || !out || dtype < 0 || dtype > 2 || transform < 0 || transform > 2 || d0 <= 0 || d1 <= 0) return hipErrorInvalidValue;
     if (d0 > (1ll << 40) / d1) return hipErrorInvalidValue;
     if (!aligned16(raw) || !aligned16(out)) return hipErrorInvalidValue;   // every caller hands over ring / arena / pool addresses
@@ -174,12 +175,13 @@ hipError_t launch_unpack_tensor(const void* raw, int dtype, int transform, long 
         else if (dtype == 1) hipLaunchKernelGGL(unpack_transpose_kernel<1>, dim3(blocks), dim3(256), 0, s, raw, out, R, C, vec_in, vec_out);
         else hipLaunchKernelGGL(unpack_transpose_kernel<2>, dim3(blocks), dim3(256), 0, s, raw, out, R, C, vec_in, vec_out);
     } else {
-        if (d1 > 4096) return hipErrorInvalidValue;
-        const long long n = d0 * 4 * d1;
+        if (d1 > 4096 || cin < 1 || cin >= 32) return hipErrorInvalidValue;
+        const int pc = (cin + 3) / 4 * 4;
+        const long long n = d0 * pc * d1;
         const unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
-        if (dtype == 0) hipLaunchKernelGGL(unpack_pad3_kernel<0>, dim3(blocks), dim3(256), 0, s, raw, out, d0, (int)d1);
-        else if (dtype == 1) hipLaunchKernelGGL(unpack_pad3_kernel<1>, dim3(blocks), dim3(256), 0, s, raw, out, d0, (int)d1);
-        else hipLaunchKernelGGL(unpack_pad3_kernel<2>, dim3(blocks), dim3(256), 0, s, raw, out, d0, (int)d1);
+        if (dtype == 0) hipLaunchKernelGGL(unpack_pad_kernel<0>, dim3(blocks), dim3(256), 0, s, raw, out, d0, cin, pc, (int)d1);
+        else if (dtype == 1) hipLaunchKernelGGL(unpack_pad_kernel<1>, dim3(blocks), dim3(256), 0, s, raw, out, d0, cin, pc, (int)d1);
+        else hipLaunchKernelGGL(unpack_pad_kernel<2>, dim3(blocks), dim3(256), 0, s, raw, out, d0, cin, pc, (int)d1);
     }
     return hipGetLastError();
 }

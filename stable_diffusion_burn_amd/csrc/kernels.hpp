@@ -236,6 +236,21 @@ hipError_t launch_img2img_start(const float* z_src, bool from_q8, const float* n
 hipError_t launch_cfg_ddim_masked(const float* eps, float* latent, float* unet_in, long long per_half, DdimCoef c, const float* mask,
                                   const float* z0, const float* e0, hipStream_t s);
 
+// ---- conditioned UNet input and the inpainting conditioning (k_inpaint.hip) ------------------------------------
+// unet_in [rows_pixels][4] + cond [cond_pixels][pc - 4] -> out [rows_pixels][pc]: latent | cond channels 0 .. cond_ch - 1 | zeros (written on every launch).
+// Pixel i reads cond pixel i mod cond_pixels (cond_pixels = n hw: both halves of a CFG batch read their sample's row).  pc % 4 == 0, pc - 4 - cond_ch <= 3.
+hipError_t launch_assemble_unet_in(const float* unet_in, const float* cond, float* out, long long rows_pixels, long long cond_pixels, int pc, int cond_ch,
+                                   hipStream_t s);
+// cond [n][cond_ch][hw] NCHW -> [n][hw][pcc] (pcc % 4 == 0, >= cond_ch; the channels past cond_ch zero)
+hipError_t launch_cond_nchw_to_nhwc(const float* cond_nchw, float* cond_nhwc, int n, int cond_ch, long long hw, int pcc, hipStream_t s);
+// launch_rgb_u8_to_nhwc4 times (mask < 128): a regenerated pixel (mask >= 128) becomes exactly 0.  mask [pixels] u8
+hipError_t launch_rgb_u8_masked_to_nhwc4(const uint8_t* rgb, const uint8_t* mask, float* dst, long long pixels, hipStream_t s);
+// ONE image: q8 [h w][8] (the encoder's quant_conv output for the masked picture), mask [8h][8w] u8 -> cond [h w][8] = m | 0.18215 q8[0..3] | 0 0 0 with
+// m[y][x] = mask[8y][8x] >= 128 (sdmi_inpaint_latent_mask); lat_mask (may be null) [h w] receives m on its own
+hipError_t launch_inpaint_cond_pack(const float* q8, const uint8_t* mask, float* cond, float* lat_mask, int h, int w, hipStream_t s);
+// out = mask >= 128 ? gen : init, per pixel of 3 bytes; out may be gen
+hipError_t launch_inpaint_paste(const uint8_t* gen, const uint8_t* init, const uint8_t* mask, uint8_t* out, long long pixels, hipStream_t s);
+
 // ---- latent resampler of the hires fix (k_resize.hip) -----------------------------------
 // One axis of a separable resample over NHWC4 latents (one f32x4 per pixel): x [outer][in_size][inner] -> y [outer][out_size][inner] pixels,
 //     y[a][o][i] = sum_{j < count[o]} taps[o * max_taps + j] * x[a][first[o] + j][i]      (ascending j, fp32)
@@ -295,7 +310,8 @@ hipError_t launch_lora_merge(const LoraMerge& m, hipStream_t s);
 // ---- checkpoint tensors (k_unpack.hip) ---------------------------------------------------
 // raw: the bytes of a checkpoint tensor on the device, dtype 0 F32 / 1 F16 / 2 BF16 (exact conversions, on the bit patterns); out: fp32.
 // transform 0: out[i] = raw[i], i < d0 d1.  1: raw [d0][d1] -> out [d1][d0] (a Linear weight, torch [out, in] -> the dump's [in, out]).
-// 2: raw [d0][3][d1] -> out [d0][4][d1], the 4th input channel zero (the VAE encoder's RGB conv_in; d1 = kh kw).  One launch.
-hipError_t launch_unpack_tensor(const void* raw, int dtype, int transform, long long d0, long long d1, float* out, hipStream_t s);
+// 2: raw [d0][cin][d1] -> out [d0][pc][d1], pc = cin rounded up to a multiple of 4, the input channels cin .. pc - 1 zero (a conv_in stored with padded input
+// channels: the VAE encoder's RGB one, cin = 3; an inpainting UNet's, cin = 9; d1 = kh kw; cin < 32).  One launch.
+hipError_t launch_unpack_tensor(const void* raw, int dtype, int transform, long long d0, long long d1, float* out, hipStream_t s, int cin = 3);
 
 }  // namespace sdmi

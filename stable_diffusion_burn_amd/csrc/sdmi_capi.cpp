@@ -98,6 +98,7 @@ int sdmi_default_config(sdmi_config* cfg) {
     cfg->clip_heads = 12;
     cfg->clip_vocab = 49408;
     cfg->clip_ctx = 77;
+    cfg->unet_in_ch = 4;        // the latent alone (9: the SD v1 inpainting checkpoints)
     return SDMI_OK;
 }
 
@@ -684,9 +685,9 @@ int sdmi_op_unpack_tensor(sdmi_ctx* ctx, const void* raw, int32_t dtype, int32_t
             if (dims[i] < 1 || dims[i] > (int64_t)1 << 30 || count > ((size_t)1 << 34) / (size_t)dims[i]) throw Error(SDMI_ERR_INVALID, "unpack_tensor: dimensions must be positive (at most 2^34 elements)");
             count *= (size_t)dims[i];
         }
-        if (transform < 0 || transform > 2 || (transform == 1 && ndim != 2) || (transform == 2 && (ndim != 4 || dims[1] != 3)))
-            throw Error(SDMI_ERR_INVALID, "unpack_tensor: transform 0 (copy), 1 (a 2-D tensor transposed) or 2 (a [cout,3,kh,kw] conv padded to 4 input channels)");
-        const size_t n_out = transform == 2 ? count / 3 * 4 : count;
+        if (transform < 0 || transform > 2 || (transform == 1 && ndim != 2) || (transform == 2 && (ndim != 4 || dims[1] >= 32 || dims[1] % 4 == 0)))
+            throw Error(SDMI_ERR_INVALID, "unpack_tensor: transform 0 (copy), 1 (a 2-D tensor transposed) or 2 (a [cout,cin,kh,kw] conv, cin < 32 and no multiple of 4, padded to the next multiple of 4 input channels)");
+        const size_t n_out = transform == 2 ? count / (size_t)dims[1] * (size_t)((dims[1] + 3) / 4 * 4) : count;
         Engine::Call call(e);
         DevIn dx(e, raw, count * (dtype == 0 ? 4 : 2));
         DevOut dout(e, out, n_out * sizeof(float));
@@ -824,6 +825,116 @@ int sdmi_img2img_image(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T
         e.img2img_image_dev(dc.f(), n, T, du.f(), Tu, scale, n_steps, strength, reinterpret_cast<const uint8_t*>(drgb.buf.p),
                             dm ? dm->f() : nullptr, dn ? dn->f() : nullptr, seed, xl.f());
         e.decode_latent_dev(xl.f(), n, (float)(1.0 / 0.18215), nullptr, reinterpret_cast<uint8_t*>(dout.buf.p));
+        call.finish();
+        dout.fetch();
+    });
+}
+
+// ---- conditioned UNet input and inpainting -----------------------------------------------------------------------------
+int sdmi_inpaint_latent_mask(const uint8_t* mask_u8, int32_t n, int32_t h, int32_t w, float* out) {
+    return guarded([&] {
+        if (!mask_u8 || !out) throw Error(SDMI_ERR_INVALID, "inpaint_latent_mask: null pointer");
+        if (n < 1 || h < 1 || w < 1) throw Error(SDMI_ERR_INVALID, "inpaint_latent_mask: n, h and w must be positive (the mask is n x [8h, 8w])");
+        for (int64_t b = 0; b < n; ++b)
+            for (int64_t y = 0; y < h; ++y)
+                for (int64_t x = 0; x < w; ++x) out[(b * h + y) * w + x] = mask_u8[(b * 8 * h + 8 * y) * 8 * w + 8 * x] >= 128 ? 1.0f : 0.0f;
+    });
+}
+
+int sdmi_unet_forward_cond(sdmi_ctx* ctx, const float* x, int32_t t, const float* context, const float* cond, int32_t n, int32_t T, float* out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        e.check_cond("unet_forward_cond", true);
+        if (!cond) throw Error(SDMI_ERR_INVALID, "unet_forward_cond: null cond");
+        if (n <= 0 || T <= 0) throw Error(SDMI_ERR_INVALID, "unet_forward_cond: n and T must be positive");
+        const size_t hw = (size_t)e.latent_h() * e.latent_w(), lat = (size_t)n * 4 * hw * sizeof(float);
+        Engine::Call call(e);
+        DevIn dx(e, x, lat), dc(e, context, (size_t)n * T * e.config().ctx_dim * sizeof(float)), dk(e, cond, (size_t)n * e.cond_ch() * hw * sizeof(float));
+        DevOut dout(e, out, lat);
+        e.unet_forward_dev(dx.f(), t, dc.f(), n, T, dout.f(), dk.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
+int sdmi_img2img_latent_cond_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps,
+                                 double strength, const float* z0, const float* mask, const float* noise, uint64_t seed, const float* cond, float* latent_out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        e.check_cond("img2img_latent_cond_dev", true);
+        if (!cond) throw Error(SDMI_ERR_INVALID, "img2img_latent_cond_dev: null cond");
+        if (!context || !uncond || !z0 || !latent_out) throw Error(SDMI_ERR_INVALID, "img2img_latent_cond_dev: null pointer");
+        Engine::Call call(e, /*dev_inputs=*/true);
+        e.img2img_latent_dev(context, n, T, uncond, Tu, scale, n_steps, strength, z0, mask, noise, seed, latent_out, cond);
+        call.finish();
+    });
+}
+
+int sdmi_img2img_latent_cond(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps,
+                             double strength, const float* z0, const float* mask, const float* noise, uint64_t seed, const float* cond, float* latent_out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        e.check_cond("img2img_latent_cond", true);
+        if (!cond) throw Error(SDMI_ERR_INVALID, "img2img_latent_cond: null cond");
+        if (n <= 0 || T <= 0 || Tu <= 0) throw Error(SDMI_ERR_INVALID, "img2img_latent_cond: n, T, Tu must be positive");
+        const int cd = e.config().ctx_dim;
+        const size_t hw = (size_t)e.latent_h() * e.latent_w(), lat = (size_t)n * 4 * hw * sizeof(float);
+        Engine::Call call(e);
+        DevIn dc(e, context, (size_t)n * T * cd * sizeof(float)), du(e, uncond, (size_t)Tu * cd * sizeof(float)), dz(e, z0, lat);
+        DevIn dk(e, cond, (size_t)n * e.cond_ch() * hw * sizeof(float));
+        auto dm = dev_in_opt(e, mask, (size_t)n * hw * sizeof(float));
+        auto dn = dev_in_opt(e, noise, lat);
+        DevOut dout(e, latent_out, lat);
+        e.img2img_latent_dev(dc.f(), n, T, du.f(), Tu, scale, n_steps, strength, dz.f(), dm ? dm->f() : nullptr, dn ? dn->f() : nullptr, seed, dout.f(), dk.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
+int sdmi_inpaint_cond(sdmi_ctx* ctx, const uint8_t* init_rgb, const uint8_t* mask_u8, int32_t n, float* cond_out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        e.check_inpaint("inpaint_cond");
+        if (!init_rgb || !mask_u8 || !cond_out) throw Error(SDMI_ERR_INVALID, "inpaint_cond: null pointer");
+        if (n <= 0) throw Error(SDMI_ERR_INVALID, "inpaint_cond: n must be positive");
+        const size_t hw = (size_t)e.latent_h() * e.latent_w();
+        Engine::Call call(e);
+        DevIn drgb(e, init_rgb, (size_t)n * 3 * 64 * hw), dm(e, mask_u8, (size_t)n * 64 * hw);
+        DevOut dout(e, cond_out, (size_t)n * 5 * hw * sizeof(float));
+        e.inpaint_cond_dev(reinterpret_cast<const uint8_t*>(drgb.buf.p), reinterpret_cast<const uint8_t*>(dm.buf.p), n, dout.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
+int sdmi_inpaint_image_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps, double strength,
+                           const uint8_t* init_rgb, const uint8_t* mask_u8, const sdmi_inpaint* opt, const float* noise, uint64_t seed, uint8_t* rgb_out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        e.check_inpaint("inpaint_image_dev");
+        if (!context || !uncond || !init_rgb || !mask_u8 || !rgb_out) throw Error(SDMI_ERR_INVALID, "inpaint_image_dev: null pointer");
+        Engine::Call call(e, /*dev_inputs=*/true);
+        e.inpaint_image_dev(context, n, T, uncond, Tu, scale, n_steps, strength, init_rgb, mask_u8, opt, noise, seed, rgb_out);
+        call.finish();
+    });
+}
+
+int sdmi_inpaint_image(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale, size_t n_steps, double strength,
+                       const uint8_t* init_rgb, const uint8_t* mask_u8, const sdmi_inpaint* opt, const float* noise, uint64_t seed, uint8_t* rgb_out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        e.check_inpaint("inpaint_image");
+        if (!init_rgb || !mask_u8) throw Error(SDMI_ERR_INVALID, "inpaint_image: null pointer");
+        if (n <= 0 || T <= 0 || Tu <= 0) throw Error(SDMI_ERR_INVALID, "inpaint_image: n, T, Tu must be positive");
+        const int cd = e.config().ctx_dim;
+        const size_t hw = (size_t)e.latent_h() * e.latent_w(), lat = (size_t)n * 4 * hw * sizeof(float);
+        Engine::Call call(e);
+        DevIn dc(e, context, (size_t)n * T * cd * sizeof(float)), du(e, uncond, (size_t)Tu * cd * sizeof(float));
+        DevIn drgb(e, init_rgb, (size_t)n * 3 * 64 * hw), dm(e, mask_u8, (size_t)n * 64 * hw);
+        auto dn = dev_in_opt(e, noise, lat);
+        DevOut dout(e, rgb_out, (size_t)n * 3 * 64 * hw);
+        e.inpaint_image_dev(dc.f(), n, T, du.f(), Tu, scale, n_steps, strength, reinterpret_cast<const uint8_t*>(drgb.buf.p), reinterpret_cast<const uint8_t*>(dm.buf.p),
+                            opt, dn ? dn->f() : nullptr, seed, reinterpret_cast<uint8_t*>(dout.buf.p));
         call.finish();
         dout.fetch();
     });

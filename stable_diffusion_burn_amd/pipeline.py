@@ -24,7 +24,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _capi
-from ._capi import SdmiConfig, SdmiError, SdmiHires, SdmiOpView, SdmiSampler, check, load_library
+from ._capi import SdmiConfig, SdmiError, SdmiHires, SdmiInpaint, SdmiOpView, SdmiSampler, check, load_library
 
 def mpk_list(path) -> list:
     """[(dump name, shape, file offset)] of a Burn .mpk record, parsed by the C++ reader (host only, no GPU)."""
@@ -77,6 +77,16 @@ def default_alphas_cumprod(n: int = 1000) -> np.ndarray:
     """The LDM schedule a checkpoint without alphas_cumprod gets (sdmi_default_alphas_cumprod, host only, no GPU)."""
     out = np.empty(int(n), np.float32)
     check(load_library().sdmi_default_alphas_cumprod(_fp(out), int(n)))
+    return out
+
+
+def inpaint_latent_mask(mask, h: int, w: int) -> np.ndarray:
+    """sdmi_inpaint_latent_mask (host only): mask uint8 [n,8h,8w] (>= 128: regenerate) -> [n,h,w] float32 of 0 / 1, out[y][x] = mask[8y][8x] >= 128."""
+    m = np.ascontiguousarray(mask)
+    if m.dtype != np.uint8 or m.ndim != 3 or m.shape[1:] != (8 * int(h), 8 * int(w)):
+        raise ValueError(f"mask must be uint8 [n,{8 * int(h)},{8 * int(w)}], got {m.dtype} {m.shape}")
+    out = np.empty((m.shape[0], int(h), int(w)), dtype=np.float32)
+    check(load_library().sdmi_inpaint_latent_mask(m.ctypes.data_as(C.POINTER(C.c_uint8)), m.shape[0], int(h), int(w), _fp(out)))
     return out
 
 
@@ -302,6 +312,8 @@ class ModelConfig:
     clip_heads: int = 12
     clip_vocab: int = 49408
     clip_ctx: int = 77
+    # input channels of the UNet: 4 = the latent alone; 5..12 = the latent + conditioning channels (9: the SD v1 inpainting checkpoints)
+    unet_in_ch: int = 4
 
     @classmethod
     def sd_v1_4(cls, precision: int = 0, clip: bool = True) -> "ModelConfig":
@@ -347,6 +359,7 @@ class StableDiffusion:
         cfg.clip_heads = config.clip_heads
         cfg.clip_vocab = config.clip_vocab
         cfg.clip_ctx = config.clip_ctx
+        cfg.unet_in_ch = config.unet_in_ch
         self._ctx = C.c_void_p()
         check(self._lib.sdmi_create(C.byref(self._ctx), C.byref(cfg)))
         # every option this context was given, in order (bench.py prints the non-default ones next to its figures: `applied_options`)
@@ -623,8 +636,9 @@ class StableDiffusion:
         return s, mask, noise
 
     def sample_latent_from(self, context, unconditional_context, unconditional_guidance_scale: float, n_steps: int, strength: float,
-                           z0, mask=None, noise=None, seed: int = 0) -> np.ndarray:
-        """img2img in latent space -> latent [n,4,h,w].  z0 [n,4,h,w] is the start latent in the sampler's space
+                           z0, mask=None, noise=None, seed: int = 0, cond=None) -> np.ndarray:
+        """img2img in latent space -> latent [n,4,h,w].  cond [n, unet_in_ch - 4, h, w]: the conditioning channels of a UNet built with unet_in_ch > 4
+        (sdmi_img2img_latent_cond; only the UNet sees them).  z0 [n,4,h,w] is the start latent in the sampler's space
         (0.18215 x the VAE posterior mean); the loop runs the last int(strength * L) of sample_latent's L timesteps.
         mask [n,h,w] / [n,1,h,w] (1 = regenerate, 0 = keep); noise [n,4,h,w], or None: image i draws from stream seed + i."""
         context, uncond = self._check_ctx(context, unconditional_context)
@@ -633,6 +647,12 @@ class StableDiffusion:
         z0 = _f32(z0, (n, 4, h, w), "z0")
         s, mask, noise = self._check_img2img(n, strength, mask, noise)
         out = np.empty((n, 4, h, w), dtype=np.float32)
+        if cond is not None:
+            cond = self._check_cond(cond, n)
+            check(self._lib.sdmi_img2img_latent_cond(self._ctx, _fp(context), n, T, _fp(uncond), uncond.shape[0], float(unconditional_guidance_scale),
+                                                     int(n_steps), s, _fp(z0), None if mask is None else _fp(mask),
+                                                     None if noise is None else _fp(noise), int(seed), _fp(cond), _fp(out)))
+            return out
         check(self._lib.sdmi_img2img_latent(self._ctx, _fp(context), n, T, _fp(uncond), uncond.shape[0], float(unconditional_guidance_scale),
                                             int(n_steps), s, _fp(z0), None if mask is None else _fp(mask),
                                             None if noise is None else _fp(noise), int(seed), _fp(out)))
@@ -662,6 +682,49 @@ class StableDiffusion:
         out = np.empty((n, 8 * h, 8 * w, 3), dtype=np.uint8)
         check(self._lib.sdmi_img2img_image(self._ctx, _fp(context), n, T, _fp(uncond), uncond.shape[0], float(unconditional_guidance_scale),
                                            int(n_steps), s, img.ctypes.data_as(C.POINTER(C.c_uint8)), None if mask is None else _fp(mask),
+                                           None if noise is None else _fp(noise), int(seed), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    # ---- conditioned UNet and inpainting checkpoints (include/sdmi.h "conditioning channels") ------------------------------
+    def _check_cond(self, cond, n) -> np.ndarray:
+        h, w = self.latent_size
+        return _f32(cond, (n, self.config.unet_in_ch - 4, h, w), "cond")
+
+    def _check_inpaint_inputs(self, init_image, mask, n):
+        h, w = self.latent_size
+        img = np.asarray(init_image)
+        if img.dtype != np.uint8 or img.shape != (n, 8 * h, 8 * w, 3):
+            raise ValueError(f"init_image must be uint8 [{n},{8 * h},{8 * w},3], got {img.dtype} {img.shape}")
+        m = np.asarray(mask)
+        if m.dtype == np.bool_:
+            m = m.astype(np.uint8) * np.uint8(255)
+        if m.dtype != np.uint8 or m.shape != (n, 8 * h, 8 * w):
+            raise ValueError(f"mask must be uint8 (>= 128: regenerate) or bool [{n},{8 * h},{8 * w}], got {m.dtype} {m.shape}")
+        return np.ascontiguousarray(img), np.ascontiguousarray(m)
+
+    def inpaint_cond(self, init_image, mask) -> np.ndarray:
+        """The conditioning of an inpainting checkpoint (unet_in_ch = 9; sdmi_inpaint_cond): init_image uint8 [n,8h,8w,3], mask uint8 [n,8h,8w] (>= 128:
+        regenerate) -> cond [n,5,h,w] = [latent mask | 0.18215 * encode(masked picture)].  Needs the VAE encoder weights."""
+        n = int(np.asarray(init_image).shape[0])
+        h, w = self.latent_size
+        img, m = self._check_inpaint_inputs(init_image, mask, n)
+        out = np.empty((n, 5, h, w), dtype=np.float32)
+        check(self._lib.sdmi_inpaint_cond(self._ctx, img.ctypes.data_as(C.POINTER(C.c_uint8)), m.ctypes.data_as(C.POINTER(C.c_uint8)), n, _fp(out)))
+        return out
+
+    def inpaint_image(self, context, unconditional_context, unconditional_guidance_scale: float, n_steps: int, strength: float, init_image, mask,
+                      latent_blend: bool = False, paste_back: bool = False, noise=None, seed: int = 0) -> np.ndarray:
+        """Inpainting with an inpainting checkpoint (unet_in_ch = 9; sdmi_inpaint_image) -> uint8 [n,8h,8w,3].  mask uint8 [n,8h,8w], >= 128: regenerate.
+        latent_blend: also blend the kept region toward the init latent after every step; paste_back: copy the kept pixels from init_image."""
+        context, uncond = self._check_ctx(context, unconditional_context)
+        n, T, _ = context.shape
+        h, w = self.latent_size
+        img, m = self._check_inpaint_inputs(init_image, mask, n)
+        s, _, noise = self._check_img2img(n, strength, None, noise)
+        opt = SdmiInpaint(latent_blend=1 if latent_blend else 0, paste_back=1 if paste_back else 0)
+        out = np.empty((n, 8 * h, 8 * w, 3), dtype=np.uint8)
+        check(self._lib.sdmi_inpaint_image(self._ctx, _fp(context), n, T, _fp(uncond), uncond.shape[0], float(unconditional_guidance_scale), int(n_steps), s,
+                                           img.ctypes.data_as(C.POINTER(C.c_uint8)), m.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(opt),
                                            None if noise is None else _fp(noise), int(seed), out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
 
@@ -801,14 +864,14 @@ class StableDiffusion:
     # ---- operator-level entry points (parity tests) ----------------------------------------
     def op_unpack_tensor(self, raw, dtype: str, transform: int = 0) -> np.ndarray:
         """The checkpoint conversion kernel on its own (sdmi_op_unpack_tensor): raw = float32, float16, or uint16 holding bf16 bits;
-        dtype "F32" | "F16" | "BF16"; transform 0 copy, 1 2-D transpose, 2 [cout,3,kh,kw] padded to 4 input channels."""
+        dtype "F32" | "F16" | "BF16"; transform 0 copy, 1 2-D transpose, 2 [cout,cin,kh,kw] (cin < 32) padded to the next multiple of 4 input channels."""
         code = {"F32": 0, "F16": 1, "BF16": 2}[dtype]
         raw = np.ascontiguousarray(raw, dtype={0: np.float32, 1: np.float16, 2: np.uint16}[code])
         shape = raw.shape
         if transform == 1:
             out_shape = shape[::-1]
         elif transform == 2:
-            out_shape = (shape[0], 4) + tuple(shape[2:])
+            out_shape = (shape[0], (shape[1] + 3) // 4 * 4) + tuple(shape[2:])
         else:
             out_shape = shape
         out = np.empty(out_shape, np.float32)
@@ -1090,7 +1153,7 @@ def _make_cfg(lib, config: ModelConfig, device: int = 0) -> SdmiConfig:
     check(lib.sdmi_default_config(C.byref(cfg)))
     cfg.device = device
     for f in ("model_channels", "n_head", "ctx_dim", "latent_h", "latent_w", "vae_ch", "precision", "clip_layers", "clip_heads",
-              "clip_vocab", "clip_ctx"):
+              "clip_vocab", "clip_ctx", "unet_in_ch"):
         setattr(cfg, f, getattr(config, f))
     return cfg
 
@@ -1208,7 +1271,8 @@ class UNet:
     def __init__(self, sd: StableDiffusion):
         self._sd = sd
 
-    def forward(self, x, timesteps, context) -> np.ndarray:
+    def forward(self, x, timesteps, context, cond=None) -> np.ndarray:
+        """cond [n, unet_in_ch - 4, h, w]: the conditioning channels of a UNet built with unet_in_ch > 4 (sdmi_unet_forward_cond)."""
         sd = self._sd
         h, w = sd.latent_size
         x = _f32(x, name="x")
@@ -1222,6 +1286,10 @@ class UNet:
         if context.ndim != 3 or context.shape[0] != n or context.shape[2] != sd.config.ctx_dim:
             raise ValueError(f"context must be [{n}, T, {sd.config.ctx_dim}], got {context.shape}")
         out = np.empty_like(x)
+        if cond is not None:
+            cond = sd._check_cond(cond, n)
+            check(sd._lib.sdmi_unet_forward_cond(sd._ctx, _fp(x), int(ts[0]), _fp(context), _fp(cond), n, context.shape[1], _fp(out)))
+            return out
         check(sd._lib.sdmi_unet_forward(sd._ctx, _fp(x), int(ts[0]), _fp(context), n, context.shape[1], _fp(out)))
         return out
 
