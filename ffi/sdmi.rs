@@ -32,6 +32,27 @@ pub struct SdmiConfig {
     pub reserved: [i32; 2],
 }
 
+/// `sdmi_config.control_hint_ch` (0 = no ControlNet, 3 = an RGB hint) is the first of the two reserved words of earlier versions: the field list above keeps
+/// the shape the tests pin, the name is served here.
+impl SdmiConfig {
+    pub fn control_hint_ch(&self) -> i32 { self.reserved[0] }
+    pub fn set_control_hint_ch(&mut self, v: i32) { self.reserved[0] = v; }
+}
+
+/// `sdmi_control` (include/sdmi.h "ControlNet"): the sticky control of a context built with `control_hint_ch = 3`.  `hint_rgb`: HOST, `n_hint` pictures of
+/// `[hint_h, hint_w, 3]` u8 (values / 255), copied by the call; step i of the S steps a call runs is controlled iff `start * S <= i < end * S`.
+#[repr(C)]
+pub struct SdmiControl {
+    pub hint_rgb: *const u8,
+    pub n_hint: i32,
+    pub hint_h: i32,
+    pub hint_w: i32,
+    pub strength: f64,
+    pub start: f64,
+    pub end: f64,
+    pub reserved: [i64; 4],
+}
+
 /// `sdmi_sampler` (include/sdmi.h "sampler choice"): kind 0 DDIM(eta) -- eta 0 = the reference's sampler = plain Euler, eta 1 =
 /// Euler-ancestral --, 1 DPM-Solver++(2M), 2 PLMS.
 #[repr(C)]
@@ -132,6 +153,13 @@ extern "C" {
                         rgb_out: *mut u8) -> c_int;
     fn sdmi_set_sampler(ctx: *mut c_void, sampler: *const SdmiSampler) -> c_int;
     fn sdmi_get_sampler(ctx: *mut c_void, out: *mut SdmiSampler) -> c_int;
+    fn sdmi_load_control_safetensors(ctx: *mut c_void, path: *const c_char) -> c_int;
+    fn sdmi_control_ready(ctx: *mut c_void) -> c_int;
+    fn sdmi_set_control(ctx: *mut c_void, control: *const SdmiControl) -> c_int;
+    fn sdmi_control_step_on(start: c_double, end: c_double, step: i32, n_steps: i32) -> c_int;
+    fn sdmi_control_hint_embed(ctx: *mut c_void, hint_rgb: *const u8, n: i32, hint_h: i32, hint_w: i32, out: *mut c_float) -> c_int;
+    fn sdmi_control_residuals_size(ctx: *mut c_void, n: i32) -> i64;
+    fn sdmi_control_residuals(ctx: *mut c_void, x: *const c_float, t: i32, context: *const c_float, n: i32, t_len: i32, out: *mut c_float) -> c_int;
     fn sdmi_multi_set_sampler(m: *mut c_void, sampler: *const SdmiSampler) -> c_int;
     fn sdmi_sampler_coefs(sampler: *const SdmiSampler, alphas_cumprod: *const c_float, total: i32, ts: *const i32, count: i32, step_size: i64,
                           coefs: *mut c_double) -> c_int;
@@ -300,6 +328,46 @@ impl StableDiffusionMi355 {
             }
         };
         if st != 0 { Err(last_error().into()) } else { Ok(()) }
+    }
+
+    /// A ControlNet in the cldm layout -> the weight group `controlnet/...` (`sdmi_load_control_safetensors`; no reference counterpart).
+    pub fn load_control_safetensors(&mut self, path: &str) -> Result<(), Box<dyn Error>> {
+        let p = CString::new(path)?;
+        if unsafe { sdmi_load_control_safetensors(self.ctx, p.as_ptr()) } != 0 { Err(last_error().into()) } else { Ok(()) }
+    }
+
+    /// Whether every tensor of the ControlNet group is set (`sdmi_control_ready`).
+    pub fn control_ready(&self) -> bool {
+        unsafe { sdmi_control_ready(self.ctx) == 1 }
+    }
+
+    /// The control of every later forward / sampling call (`sdmi_set_control`, sticky): `hint` = `n_hint` pictures `[hint_h, hint_w, 3]` u8 back to back,
+    /// (strength, start, end) as `sdmi_control` states them.  `None` clears.
+    pub fn set_control(&mut self, control: Option<(&[u8], i32, i32, i32, f64, f64, f64)>) -> Result<(), Box<dyn Error>> {
+        let st = match control {
+            None => unsafe { sdmi_set_control(self.ctx, std::ptr::null()) },
+            Some((hint, n_hint, hint_h, hint_w, strength, start, end)) => {
+                if hint.len() != (n_hint as usize) * (hint_h as usize) * (hint_w as usize) * 3 { return Err("set_control: hint length".into()); }
+                let c = SdmiControl { hint_rgb: hint.as_ptr(), n_hint, hint_h, hint_w, strength, start, end, reserved: [0; 4] };
+                unsafe { sdmi_set_control(self.ctx, &c) }
+            }
+        };
+        if st != 0 { Err(last_error().into()) } else { Ok(()) }
+    }
+
+    /// The hint embedding `[n, model_channels, hint_h / 8, hint_w / 8]` (`sdmi_control_hint_embed`).
+    pub fn control_hint_embed(&self, hint: &[u8], n: i32, hint_h: i32, hint_w: i32, model_channels: i32) -> Result<Vec<f32>, Box<dyn Error>> {
+        if hint.len() != (n as usize) * (hint_h as usize) * (hint_w as usize) * 3 { return Err("control_hint_embed: hint length".into()); }
+        let mut out = vec![0f32; (n as usize) * (model_channels as usize) * ((hint_h / 8) as usize) * ((hint_w / 8) as usize)];
+        if unsafe { sdmi_control_hint_embed(self.ctx, hint.as_ptr(), n, hint_h, hint_w, out.as_mut_ptr()) } != 0 { Err(last_error().into()) } else { Ok(out) }
+    }
+
+    /// The 13 residuals of the set control, NCHW back to back (`sdmi_control_residuals`; `sdmi_control_residuals_size` floats).
+    pub fn control_residuals(&self, x: &[f32], t: i32, context: &[f32], n: i32, t_len: i32) -> Result<Vec<f32>, Box<dyn Error>> {
+        let total = unsafe { sdmi_control_residuals_size(self.ctx, n) };
+        if total < 0 { return Err(last_error().into()); }
+        let mut out = vec![0f32; total as usize];
+        if unsafe { sdmi_control_residuals(self.ctx, x.as_ptr(), t, context.as_ptr(), n, t_len, out.as_mut_ptr()) } != 0 { Err(last_error().into()) } else { Ok(out) }
     }
 
     /// The sampler in force (`sdmi_get_sampler`).

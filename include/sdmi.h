@@ -81,7 +81,11 @@ typedef struct sdmi_config {
     int32_t unet_in_ch;      /* 4; input channels of the UNet's first convolution: 4 = the latent alone, 5..12 = the latent + (unet_in_ch - 4)
                               * conditioning channels given per call (the *_cond entry points; 9 = the SD v1 inpainting checkpoints, 8 = instruct-pix2pix-shaped
                               * UNets).  0 means 4, so that a zeroed struct keeps working; anything else is SDMI_ERR_INVALID from sdmi_create. */
-    int32_t reserved[2];
+    int32_t control_hint_ch; /* 0; channels of a ControlNet's hint picture: 0 = no ControlNet (the tensor list, sdmi_weight_count and every launch are those of a context
+                              * without the field), 3 = an RGB hint: the model gets a fourth weight group "controlnet/..." (section "ControlNet" below).  Anything else is
+                              * SDMI_ERR_INVALID from sdmi_create; control_hint_ch != 0 with unet_in_ch != 4 is SDMI_ERR_UNSUPPORTED (the control encoder's first convolution
+                              * takes the 4 latent channels). */
+    int32_t reserved[1];
 } sdmi_config;
 
 int sdmi_default_config(sdmi_config* cfg);
@@ -258,6 +262,52 @@ typedef struct sdmi_sampler {
  * eta != 0 with kind != 0. */
 int sdmi_set_sampler(sdmi_ctx* ctx, const sdmi_sampler* sampler);
 int sdmi_get_sampler(sdmi_ctx* ctx, sdmi_sampler* out);
+
+/* ---- ControlNet (SD v1; no reference counterpart) -----------------------------------------------------
+ * A context created with sdmi_config.control_hint_ch = 3 has a fourth weight group, "controlnet/...": a second copy of the UNet's time MLP
+ * (controlnet/lin1_time_embed, lin2_time_embed), its 12 input blocks and its middle block under the UNet's own names, the eight hint convolutions
+ * controlnet/hint/c0 .. c7 (3x3, pad 1: 3->16, 16->16, 16->32 stride 2, 32->32, 32->96 stride 2, 96->96, 96->256 stride 2, 256->model_channels, SiLU after all but
+ * the last; fp32 at every precision), the 1x1 zero convolutions controlnet/zero_convs/0 .. 11 and controlnet/middle_block_out.  The group is all or nothing
+ * (sdmi_finalize_weights refuses a partial one); its tensors arrive through sdmi_set_weight (before or after sdmi_finalize_weights), a controlnet/ subtree of the dump
+ * directory or sdmi_load_control_safetensors -- never through sdmi_load_weights_packed, whose groups stay 1..7.  Loading another ControlNet does not touch the base model.
+ *
+ * sdmi_load_control_safetensors: ONE .safetensors file in the ControlNet ("cldm") layout -- keys "control_model.…", F32 / F16 / BF16 -- by the route of
+ * sdmi_load_weights_safetensors: memory-mapped, raw bytes to the device, widening and the Linear transpose there, everything checked before the first tensor is
+ * staged (a refused file leaves the context as it was).  Key rule (sdmi_checkpoint_key; tests/golden/controlnet_ckpt_keys.txt): the encoder, middle block and time MLP
+ * as the UNet's with "control_model." for "model.diffusion_model."; hint/c<i> = control_model.input_hint_block.<2i>; zero_convs/<j> = control_model.zero_convs.<j>.0;
+ * middle_block_out = control_model.middle_block_out.0.  The last three families are stated from ControlNet's cldm.py and UNPINNED: no ControlNet file exists offline.
+ * Every tensor of the group must be in the file; keys the group has no tensor for are skipped.  Statuses as sdmi_load_weights_safetensors, plus SDMI_ERR_STATE on a
+ * context with control_hint_ch = 0.  Out of scope: diffusers-layout ControlNets, .pth pickles, T2I-Adapter, SD 2.x / SDXL ControlNets. */
+int sdmi_load_control_safetensors(sdmi_ctx* ctx, const char* path);
+/* 1: every tensor of the ControlNet group is set; 0: not (also on a context without one) */
+int sdmi_control_ready(sdmi_ctx* ctx);
+/* The control state: sticky, like sdmi_set_sampler.  It applies to every later sdmi_unet_forward*, sdmi_sample_* and sdmi_img2img_* call of the context, host-pointer
+ * and _dev forms alike.  Per call the hint goes through the hint convolutions once; on every controlled step the control encoder runs on the UNet's own input (the hint
+ * embedding enters as the residual of its first convolution; image i of both halves of a CFG batch reads hint i mod n_hint -- both halves are controlled, there is
+ * no "guess mode"), the zero convolutions give 13 residuals, and ONE launch (csrc/k_control.hip) adds strength x residual to the UNet's 12 saved skips and to its middle
+ * block's output.  The UNet's encoder runs on the unmodified activations.  In sdmi_unet_forward* the step window does not apply: the control is on.  With the state
+ * cleared, with strength == 0, or on a step outside the window the forward is the plain one: the same launches, the same bits. */
+typedef struct sdmi_control {
+    const uint8_t* hint_rgb;   /* HOST, n_hint x [hint_h, hint_w, 3] u8, sample_image's layout; values / 255; copied to the device by the call */
+    int32_t n_hint;            /* 1 = one hint for every image of a call, or the n of the later calls */
+    int32_t hint_h, hint_w;    /* must be 8 x the latent size in force when a forward runs */
+    double strength;           /* multiplies all 13 residuals; finite */
+    double start, end;         /* 0 <= start <= end <= 1: step i (0-based) of the S steps a call runs is controlled iff start*S <= i < end*S, in f64 */
+    int64_t reserved[4];
+} sdmi_control;
+/* NULL clears.  SDMI_ERR_STATE: a context without a ControlNet, or one whose group is not completely set.  SDMI_ERR_INVALID -- and nothing changes --: a NULL hint,
+ * n_hint < 1, hint_h / hint_w not positive multiples of 64, a non-finite strength, start > end or a bound outside [0, 1].  Later, from the call that runs a forward:
+ * SDMI_ERR_INVALID when the latent size in force is not hint / 8, or the call's n is not n_hint (n_hint != 1) -- the message names both sizes.  While a control is set
+ * sdmi_hires_* (its first pass runs at another size) and sdmi_sample_image_sharded return SDMI_ERR_UNSUPPORTED. */
+int sdmi_set_control(sdmi_ctx* ctx, const sdmi_control* control);
+/* Host only: THE window rule of sdmi_control -- 1 when step `step` of `n_steps` is controlled, 0 when not; SDMI_ERR_INVALID for a bad window or step. */
+int sdmi_control_step_on(double start, double end, int32_t step, int32_t n_steps);
+/* The pieces, for tests and for callers who want them (host pointers).  hint_embed: n hints -> out [n, model_channels, hint_h / 8, hint_w / 8] fp32.
+ * residuals: the 13 residual tensors of the sticky hint (strength and window ignored) for x [n,4,h,w], timestep t, context [n,T,ctx_dim] -- NCHW fp32, back to back,
+ * zero_convs 0 .. 11 then middle_block_out; sdmi_control_residuals_size(n) floats in all. */
+int sdmi_control_hint_embed(sdmi_ctx* ctx, const uint8_t* hint_rgb, int32_t n, int32_t hint_h, int32_t hint_w, float* out);
+int64_t sdmi_control_residuals_size(sdmi_ctx* ctx, int32_t n);
+int sdmi_control_residuals(sdmi_ctx* ctx, const float* x, int32_t t, const float* context, int32_t n, int32_t T, float* out);
 /* Host only, needs no device: THE implementation of the rules above (the engine calls it).  For the `count` timesteps ts a call runs
  * (sample_latent's schedule or its img2img tail; ts[0] is the call's first step) it writes 8 doubles per step,
  *     cx, ce, h1, h2, h3, cz, qx, qe:    q = qx x + qe e  (pushed to history: x0 for kind 1, e for kind 2, unused for kind 0)

@@ -29,6 +29,16 @@ class SdmiConfig(C.Structure):
         ("clip_ctx", C.c_int32), ("unet_in_ch", C.c_int32), ("reserved", C.c_int32 * 2),
     ]
 
+    # sdmi_config.control_hint_ch is the first of the two reserved words of earlier versions: the field list above keeps its pinned shape
+    # (tests/test_inpaint_cpu.py), the name is served here
+    @property
+    def control_hint_ch(self) -> int:
+        return int(self.reserved[0])
+
+    @control_hint_ch.setter
+    def control_hint_ch(self, v: int) -> None:
+        self.reserved[0] = int(v)
+
 
 class SdmiOpView(C.Structure):
     """sdmi_op_view: where an operator's input and output sit inside wider parent buffers (sdmi_op_*_view; tests)"""
@@ -40,6 +50,12 @@ class SdmiSampler(C.Structure):
     """sdmi_sampler: the sampler choice of a context (sdmi_set_sampler)"""
     _fields_ = [("kind", C.c_int32), ("reserved0", C.c_int32), ("eta", C.c_double), ("noise_seed", C.c_uint64), ("image_base", C.c_int64),
                 ("reserved", C.c_int64 * 4)]
+
+
+class SdmiControl(C.Structure):
+    """sdmi_control: the sticky ControlNet state of a context (sdmi_set_control)"""
+    _fields_ = [("hint_rgb", C.POINTER(C.c_uint8)), ("n_hint", C.c_int32), ("hint_h", C.c_int32), ("hint_w", C.c_int32), ("strength", C.c_double),
+                ("start", C.c_double), ("end", C.c_double), ("reserved", C.c_int64 * 4)]
 
 
 class SdmiInpaint(C.Structure):
@@ -101,6 +117,13 @@ SIGNATURES = {
     "sdmi_inpaint_image_dev": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_size_t, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(SdmiInpaint), C.c_void_p, C.c_uint64, C.c_void_p]),
     "sdmi_set_sampler": (C.c_int, [_CTX, _SAMPLER]),
     "sdmi_get_sampler": (C.c_int, [_CTX, _SAMPLER]),
+    "sdmi_load_control_safetensors": (C.c_int, [_CTX, C.c_char_p]),
+    "sdmi_control_ready": (C.c_int, [_CTX]),
+    "sdmi_set_control": (C.c_int, [_CTX, C.POINTER(SdmiControl)]),
+    "sdmi_control_step_on": (C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_int32]),
+    "sdmi_control_hint_embed": (C.c_int, [_CTX, _U8, C.c_int32, C.c_int32, C.c_int32, _F]),
+    "sdmi_control_residuals_size": (C.c_int64, [_CTX, C.c_int32]),
+    "sdmi_control_residuals": (C.c_int, [_CTX, _F, C.c_int32, _F, C.c_int32, C.c_int32, _F]),
     "sdmi_sampler_coefs": (C.c_int, [_SAMPLER, _F, C.c_int32, _I32, C.c_int32, C.c_int64, C.POINTER(C.c_double)]),
     "sdmi_set_latent_size": (C.c_int, [_CTX, C.c_int32, C.c_int32]),
     "sdmi_get_latent_size": (C.c_int, [_CTX, _I32, _I32]),

@@ -117,9 +117,25 @@ bool res_group(Walk& w, bool has_transformer, int up_at) {
     return false;
 }
 
-bool unet(Walk& w) {
-    w.key = "model.diffusion_model";
+// control = true: a ControlNet in the cldm layout -- the encoder half, the middle block and the time MLP under the UNet's own rules with another
+// root, plus the three families the UNet does not have: the hint convolutions (input_hint_block: conv, SiLU, conv, ... -- convolution i is element 2i), the zero
+// convolutions (zero_convs.<j> is a one-element sequential) and middle_block_out (likewise).  It has no output blocks and no head.
+bool unet(Walk& w, bool control = false) {
+    w.key = control ? "control_model" : "model.diffusion_model";
     int n = 0;
+    if (control) {
+        if (w.take("hint")) {
+            if (!take_numbered(w, "c", 0, 7, &n)) return false;
+            w.key += ".input_hint_block." + std::to_string(2 * n);
+            return leaf(w, L_PLAIN);
+        }
+        if (w.take("zero_convs")) {
+            if (!take_numbered(w, "", 0, 11, &n)) return false;
+            w.key += ".zero_convs." + std::to_string(n) + ".0";
+            return leaf(w, L_PLAIN);
+        }
+        if (w.take("middle_block_out")) { w.key += ".middle_block_out.0"; return leaf(w, L_PLAIN); }
+    }
     if (w.take("input_blocks")) {   // save_unet_input_blocks: conv rt1 rt2 d1 rt3 rt4 d2 rt5 rt6 d3 r1 r2 = elements 0 .. 11
         w.key += ".input_blocks.";
         if (w.take("conv")) { w.key += "0.0"; return leaf(w, L_PLAIN); }
@@ -135,7 +151,7 @@ bool unet(Walk& w) {
         if (w.take("res2")) { w.key += ".2"; return res_block(w); }
         return false;
     }
-    if (w.take("output_blocks")) {   // save_unet_output_blocks: r1 r2 ru rt1 rt2 rtu1 rt3 rt4 rtu2 rt5 rt6 rt7 = elements 0 .. 11
+    if (!control && w.take("output_blocks")) {   // save_unet_output_blocks: r1 r2 ru rt1 rt2 rtu1 rt3 rt4 rtu2 rt5 rt6 rt7 = elements 0 .. 11
         w.key += ".output_blocks.";
         if (take_numbered(w, "rtu", 1, 2, &n)) { w.key += std::to_string(2 + 3 * n); return res_group(w, true, 2); }
         if (take_numbered(w, "rt", 1, 7, &n)) { w.key += std::to_string(2 + n + (n >= 3) + (n >= 5)); return res_group(w, true, 0); }
@@ -143,8 +159,12 @@ bool unet(Walk& w) {
         if (take_numbered(w, "r", 1, 2, &n)) { w.key += std::to_string(n - 1) + ".0"; return res_block(w); }
         return false;
     }
-    static const Rename k[] = {{"lin1_time_embed", ".time_embed.0", L_LINEAR}, {"lin2_time_embed", ".time_embed.2", L_LINEAR},
-                               {"norm_out", ".out.0", L_PLAIN}, {"conv_out", ".out.2", L_PLAIN}};
+    if (w.more() && (w.cur() == "lin1_time_embed" || w.cur() == "lin2_time_embed")) {   // the time MLP: a UNet's and a ControlNet's
+        static const Rename kt[] = {{"lin1_time_embed", ".time_embed.0", L_LINEAR}, {"lin2_time_embed", ".time_embed.2", L_LINEAR}};
+        return renamed(w, kt);
+    }
+    if (control) return false;   // no head
+    static const Rename k[] = {{"norm_out", ".out.0", L_PLAIN}, {"conv_out", ".out.2", L_PLAIN}};
     return renamed(w, k);
 }
 
@@ -229,6 +249,7 @@ bool checkpoint_key(const std::string& dump_name, std::string* key, bool* transp
     bool ok = false;
     if (w.t.size() == 1 && w.t[0] == "alphas_cumprod") { w.key = "alphas_cumprod"; ok = true; }
     else if (w.take("unet")) ok = unet(w);
+    else if (w.take("controlnet")) ok = unet(w, true);
     else if (w.take("autoencoder")) ok = autoencoder(w);
     else if (w.take("clip")) ok = clip(w);
     if (!ok) return false;
@@ -271,6 +292,18 @@ const std::map<std::string, std::string>& reverse_map() {
                 }
             }
         res("unet/middle_block/res1"); st("unet/middle_block/transformer"); res("unet/middle_block/res2");
+        // a ControlNet (cldm layout): the encoder's names under another root + its three own families
+        for (const char* d : {"lin1_time_embed", "lin2_time_embed", "input_blocks/conv", "middle_block_out"}) both(std::string("controlnet/") + d);
+        for (int i = 0; i <= 9; ++i) {
+            const std::string n = std::to_string(i);
+            for (const char* kind : {"rt", "r", "d"}) {
+                const std::string b = std::string("controlnet/input_blocks/") + kind + n;
+                res(b); res(b + "/res"); st(b + "/transformer"); both(b);
+            }
+        }
+        for (int i = 0; i <= 7; ++i) both("controlnet/hint/c" + std::to_string(i));
+        for (int i = 0; i <= 11; ++i) both("controlnet/zero_convs/" + std::to_string(i));
+        res("controlnet/middle_block/res1"); st("controlnet/middle_block/transformer"); res("controlnet/middle_block/res2");
         both("autoencoder/quant_conv"); both("autoencoder/post_quant_conv");
         for (const char* half : {"autoencoder/encoder", "autoencoder/decoder"}) {
             const std::string h = half;

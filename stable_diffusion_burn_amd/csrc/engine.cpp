@@ -227,6 +227,9 @@ Engine::Engine(const sdmi_config& cfg) : cfg_(cfg) {
     if (cfg.ctx_dim % 32 || cfg.ctx_dim <= 0) throw Error(SDMI_ERR_INVALID, "ctx_dim must be a positive multiple of 32");
     if (cfg_.unet_in_ch == 0) cfg_.unet_in_ch = 4;   // a zeroed field: the latent alone
     if (cfg_.unet_in_ch < 4 || cfg_.unet_in_ch > 12) throw Error(SDMI_ERR_INVALID, "unet_in_ch must be 4 (the latent alone) or 5 .. 12 (the latent + conditioning channels)");
+    if (cfg_.control_hint_ch != 0 && cfg_.control_hint_ch != 3) throw Error(SDMI_ERR_INVALID, "control_hint_ch must be 0 (no ControlNet) or 3 (an RGB hint)");
+    if (cfg_.control_hint_ch != 0 && cfg_.unet_in_ch != 4)
+        throw Error(SDMI_ERR_UNSUPPORTED, "control_hint_ch != 0 needs unet_in_ch = 4: the control encoder's first convolution takes the 4 latent channels");
     check_latent_size(cfg.latent_h, cfg.latent_w);
     lat_h_ = cfg.latent_h;
     lat_w_ = cfg.latent_w;
@@ -271,6 +274,8 @@ void Engine::destroy() noexcept {
         delete a;
     }
     loras_.clear();
+    if (ctrl_.hint_dev) (void)hipFree(ctrl_.hint_dev);   // a control still set: its hint pictures
+    ctrl_ = Control{};
     for (void* p : weight_allocs_) (void)hipFree(p);
     for (auto& p : prof_pending_) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (hipEvent_t e : prof_free_) (void)hipEventDestroy(e);
@@ -307,10 +312,11 @@ void Engine::build_model() {
     // precision = 1: weights of every layer with Cin % 64 == 0 are packed as bf16; the three Cin = 4
     // layers and the time-embedding MLPs (M = n_steps rows, once per call) stay fp32
     // stride / pad: what the engine applies to this layer; checked against the dump's metadata files (load_conv2d, load.rs:118-160)
-    auto conv = [&](ConvW& w, const std::string& path, int cin, int cout, int k, int stride = 1, int pad = -1) {
+    // keep_f32 (the ControlNet hint convolutions): fp32 weight, input and output at every precision, like the time MLPs -- they run once per call
+    auto conv = [&](ConvW& w, const std::string& path, int cin, int cout, int k, int stride = 1, int pad = -1, bool keep_f32 = false) {
         w.cin = cin < 32 ? (cin + 3) / 4 * 4 : cin; w.cout = cout; w.k = k;   // what the layer reads: padded_cin of its weight (9 -> 12: a conditioned UNet's conv_in)
-        w.dt = (bf16_ && cin % 64 == 0) ? 1 : 0;
-        if (bf16_ && !w.dt && cin >= 32) throw Error(SDMI_ERR_UNSUPPORTED, "bf16: conv Cin must be a multiple of 64 (or < 32)");
+        w.dt = (bf16_ && cin % 64 == 0 && !keep_f32) ? 1 : 0;
+        if (bf16_ && !w.dt && cin >= 32 && !keep_f32) throw Error(SDMI_ERR_UNSUPPORTED, "bf16: conv Cin must be a multiple of 64 (or < 32)");
         add(this, path + "/weight", 0, {cout, cin, k, k}, &w.bt, w.dt);
         add(this, path + "/bias", 2, {cout}, &w.bias);
         if (pad < 0) pad = k == 3 ? 1 : 0;
@@ -484,6 +490,8 @@ void Engine::build_model() {
     for (auto& b : in_blocks_) idx_block(b);
     idx_res(mid_res1_); idx_st(mid_st_); idx_res(mid_res2_);
     for (auto& b : out_blocks_) idx_block(b);
+    n_res_unet_ = res_list_.size();
+    n_st_unet_ = st_list_.size();
 
     // ---- VAE decoder (autoencoder/mod.rs:30-36,154-191) ------------------------------
     const int vc = cfg_.vae_ch;
@@ -570,6 +578,33 @@ void Engine::build_model() {
         norm(enc_norm_out_, "autoencoder/encoder/norm_out", 4 * vc);
         conv(enc_conv_out_, "autoencoder/encoder/conv_out", 4 * vc, 8, 3);
         conv(quant_conv_, "autoencoder/quant_conv", 8, 8, 1);
+        cur_group_ = 0;
+    }
+
+    // ---- ControlNet (cldm.py ControlNet): no reference counterpart -------------------------------------------------
+    // Optional weight group 3: a second copy of the UNet's time MLP, encoder and middle block under the root "controlnet" -- the same lambdas, hence the same dump
+    // naming, storage types and MXFP8 copies as their UNet twins -- plus the hint convolutions (fp32 at every precision; the widths 16 / 32 / 96 / 256 are
+    // ControlNet's constants), one zero convolution per input block and middle_block_out.  Its ResBlocks and transformers follow the UNet's in res_list_ / st_list_.
+    if (cfg_.control_hint_ch) {
+        cur_group_ = 3;
+        lin(ctl_lin1_time_, "controlnet/lin1_time_embed", mc, ed, true, /*keep_f32=*/true);
+        lin(ctl_lin2_time_, "controlnet/lin2_time_embed", ed, ed, true, /*keep_f32=*/true);
+        ctl_blocks_.resize(12);
+        for (int i = 0; i < 12; ++i) {
+            Spec sp = in_spec[i];
+            if (i == 0) sp.cin = 4;
+            def_block(ctl_blocks_[i], sp, "controlnet/input_blocks");
+        }
+        res(ctl_mid_res1_, "controlnet/middle_block/res1", c4, c4, true);
+        spatial(ctl_mid_st_, "controlnet/middle_block/transformer", c4);
+        res(ctl_mid_res2_, "controlnet/middle_block/res2", c4, c4, true);
+        const int hch[9] = {cfg_.control_hint_ch, 16, 16, 32, 32, 96, 96, 256, mc};
+        for (int i = 0; i < 8; ++i)
+            conv(ctl_hint_[i], "controlnet/hint/c" + std::to_string(i), hch[i], hch[i + 1], 3, (i == 2 || i == 4 || i == 6) ? 2 : 1, 1, /*keep_f32=*/true);
+        for (int j = 0; j < 12; ++j) conv(ctl_zero_[j], "controlnet/zero_convs/" + std::to_string(j), in_spec[j].cout, in_spec[j].cout, 1);
+        conv(ctl_mid_out_, "controlnet/middle_block_out", c4, c4, 1);
+        for (auto& b : ctl_blocks_) idx_block(b);
+        idx_res(ctl_mid_res1_); idx_st(ctl_mid_st_); idx_res(ctl_mid_res2_);
         cur_group_ = 0;
     }
 }
@@ -704,7 +739,7 @@ const void* Engine::split_planes(const float* bt) const {
     for (int slot = 0; slot < 2; ++slot)
         if (bt && bt == temp_split_bt_[slot]) return temp_split_planes_[slot];
     const char* b = reinterpret_cast<const char*>(bt);
-    for (int g = 0; g < 3; ++g)
+    for (int g = 0; g < kGroups; ++g)
         if (split_base_[g] && b >= arena_base_[g] && b < arena_base_[g] + arena_bytes_[g]) return split_base_[g] + (size_t)(b - arena_base_[g]) / 2 * 3;
     for (const SplitRegion& r : split_regions_)    // the packed q | k | v weights of the self-attentions (own allocations)
         if (b >= r.base && b < r.base + r.bytes) return r.planes + (size_t)(b - r.base) / 2 * 3;
@@ -797,7 +832,7 @@ void Engine::stage_commit(WeightEntry& e, size_t offset, int half) {
         pack_entry(e, stage);
     }
     e.set = true;
-    finalized_ = false;
+    if (e.group != 3) finalized_ = false;   // (a ControlNet tensor may arrive behind finalize_weights: control_ready() counts)
 }
 
 // copies one tensor into the pinned ring (zero-padding the input channels of a conv_in that is stored padded: padded_cin) and commits it
@@ -865,6 +900,11 @@ void Engine::set_weight(const char* name, const float* data, int ndim, const int
         throw Error(SDMI_ERR_STATE, std::string("set_weight: '") + name + "' carries a LoRA adapter with a non-zero scale: set its scale to 0 first");
     SDMI_HIP(hipSetDevice(cfg_.device));
     upload_weight(e, data);   // data is copied into the pinned ring before this returns: the caller may free it
+    // a ControlNet tensor behind finalize_weights leaves finalized_ alone, so no later finalize releases the pinned ring: the tensor that completes the group does
+    if (e.group == 3 && finalized_ && control_ready()) {
+        SDMI_HIP(hipStreamSynchronize(stream_));
+        stager_release();
+    }
 }
 
 size_t Engine::packed_size(int groups) const {
@@ -960,49 +1000,59 @@ static std::string shape_str(const int64_t* d, size_t n) {
     return s + "]";
 }
 
-void Engine::load_weights_safetensors(const char* path) {
-    if (!path) throw Error(SDMI_ERR_INVALID, "load_weights_safetensors: null path");
+void Engine::load_weights_safetensors(const char* path) { load_safetensors_groups(path, false); }
+
+// A ControlNet in the cldm layout ("control_model.…") -> weight group 3, by the same route.  Every tensor of the group must be in the file.
+void Engine::load_control_safetensors(const char* path) {
+    if (!has_control()) throw Error(SDMI_ERR_STATE, "load_control_safetensors: this context has no ControlNet (sdmi_config.control_hint_ch = 0)");
+    load_safetensors_groups(path, true);
+}
+
+void Engine::load_safetensors_groups(const char* path, bool control) {
+    const std::string fn_name = control ? "load_control_safetensors" : "load_weights_safetensors";
+    if (!path) throw Error(SDMI_ERR_INVALID, fn_name + ": null path");
     SDMI_HIP(hipSetDevice(cfg_.device));
-    lora_refuse_bulk_load("load_weights_safetensors");
+    lora_refuse_bulk_load(fn_name.c_str());
     SafetensorsFile f(path);
     struct Job { WeightEntry* e; const StTensor* t; int dtype; int transform; };
     std::vector<Job> jobs;
     const StTensor* alphas = nullptr;
     WeightEntry* alphas_entry = nullptr;
     for (auto& e : entries_) {
+        if ((e.group == 3) != control) continue;   // a ControlNet comes in a file of its own (load_control_safetensors)
         std::string key;
         bool transposed = false;
-        if (!checkpoint_key(e.name, &key, &transposed)) throw Error(SDMI_ERR_STATE, "load_weights_safetensors: no checkpoint key rule for '" + e.name + "'");
+        if (!checkpoint_key(e.name, &key, &transposed)) throw Error(SDMI_ERR_STATE, fn_name + ": no checkpoint key rule for '" + e.name + "'");
         const StTensor* t = f.find(key);
         if (e.kind == 3) { alphas = t; alphas_entry = &e; continue; }   // optional: the LDM schedule is computed when the file has none
         if (!t) {
-            if (e.group == 0)
-                throw Error(SDMI_ERR_WEIGHTS, std::string("load_weights_safetensors: ") + path + " has no tensor '" + key + "' (the source of '" + e.name + "')");
-            continue;   // CLIP / VAE encoder: all or nothing, decided by finalize_weights
+            if (e.group == 0 || control)
+                throw Error(SDMI_ERR_WEIGHTS, std::string(fn_name + ": ") + path + " has no tensor '" + key + "' (the source of '" + e.name + "')");
+            continue;   // CLIP / VAE encoder: all or nothing, decided by finalize_weights (a ControlNet: by this loader, above)
         }
         const int dt = unpack_dtype(t->dtype);
-        if (dt < 0) throw Error(SDMI_ERR_UNSUPPORTED, "load_weights_safetensors: '" + key + "' has dtype " + t->dtype + "; F32, F16 and BF16 are supported");
-        if (transposed && (e.kind != 1 || e.ndim != 2)) throw Error(SDMI_ERR_STATE, "load_weights_safetensors: '" + e.name + "' is not a Linear weight");
+        if (dt < 0) throw Error(SDMI_ERR_UNSUPPORTED, fn_name + ": '" + key + "' has dtype " + t->dtype + "; F32, F16 and BF16 are supported");
+        if (transposed && (e.kind != 1 || e.ndim != 2)) throw Error(SDMI_ERR_STATE, fn_name + ": '" + e.name + "' is not a Linear weight");
         int64_t want[4];
         for (int i = 0; i < e.ndim; ++i) want[i] = e.dims[i];
         if (transposed) std::swap(want[0], want[1]);   // torch's [out, in]
         bool ok = (int)t->shape.size() == e.ndim;
         for (int i = 0; ok && i < e.ndim; ++i) ok = t->shape[i] == want[i];
         if (!ok)
-            throw Error(SDMI_ERR_WEIGHTS, "load_weights_safetensors: '" + key + "' has shape " + shape_str(t->shape.data(), t->shape.size()) +
+            throw Error(SDMI_ERR_WEIGHTS, fn_name + ": '" + key + "' has shape " + shape_str(t->shape.data(), t->shape.size()) +
                                               ", the configured model expects " + shape_str(want, (size_t)e.ndim) + " ('" + e.name + "')");
         jobs.push_back(Job{&e, t, dt, transposed ? 1 : (e.kind == 0 && padded_cin(e) != e.dims[1]) ? 2 : 0});
     }
-    if (jobs.empty()) throw Error(SDMI_ERR_WEIGHTS, std::string("load_weights_safetensors: no tensor of ") + path + " matches the configured model");
+    if (jobs.empty()) throw Error(SDMI_ERR_WEIGHTS, std::string(fn_name + ": no tensor of ") + path + " matches the configured model");
     std::vector<float> schedule;
     if (alphas_entry) {
         const size_t n = entry_count(*alphas_entry);
         schedule.resize(n);
         if (alphas) {
             if (alphas->dtype != "F64" && unpack_dtype(alphas->dtype) < 0)
-                throw Error(SDMI_ERR_UNSUPPORTED, "load_weights_safetensors: 'alphas_cumprod' has dtype " + alphas->dtype);
+                throw Error(SDMI_ERR_UNSUPPORTED, fn_name + ": 'alphas_cumprod' has dtype " + alphas->dtype);
             if (alphas->shape.size() != 1 || (size_t)alphas->shape[0] != n)
-                throw Error(SDMI_ERR_WEIGHTS, "load_weights_safetensors: 'alphas_cumprod' has shape " + shape_str(alphas->shape.data(), alphas->shape.size()) +
+                throw Error(SDMI_ERR_WEIGHTS, fn_name + ": 'alphas_cumprod' has shape " + shape_str(alphas->shape.data(), alphas->shape.size()) +
                                                   ", expected [" + std::to_string(n) + "]");
             for (size_t i = 0; i < n; ++i) schedule[i] = raw_to_f32(alphas->data, alphas->dtype, i);
         } else {
@@ -1049,7 +1099,7 @@ void Engine::load_weights_safetensors(const char* path) {
             pack_entry(e, out);
         }
         e.set = true;
-        finalized_ = false;
+        if (e.group != 3) finalized_ = false;
     }
     if (alphas_entry) { alphas_ = schedule; alphas_entry->set = true; }
     SDMI_HIP(hipStreamSynchronize(stream_));
@@ -1067,17 +1117,24 @@ void Engine::op_unpack_tensor(const void* raw, int dtype, int ndim, const int64_
     count_kernel();
 }
 
+bool Engine::control_ready() const {
+    bool any = false;
+    for (auto& e : entries_)
+        if (e.group == 3) { any = true; if (!e.set) return false; }
+    return any;
+}
+
 void Engine::finalize_weights() {
-    int total[3] = {0, 0, 0}, set[3] = {0, 0, 0};
-    const WeightEntry* missing[3] = {nullptr, nullptr, nullptr};
+    int total[kGroups] = {0, 0, 0, 0}, set[kGroups] = {0, 0, 0, 0};
+    const WeightEntry* missing[kGroups] = {nullptr, nullptr, nullptr, nullptr};
     for (auto& e : entries_) {
         ++total[e.group];
         if (e.set) ++set[e.group];
         else if (!missing[e.group]) missing[e.group] = &e;
     }
     if (missing[0]) throw Error(SDMI_ERR_WEIGHTS, "finalize_weights: tensor '" + missing[0]->name + "' was never set");
-    static const char* const kGroupName[3] = {"", "CLIP", "VAE encoder"};
-    for (int g = 1; g < 3; ++g)
+    static const char* const kGroupName[kGroups] = {"", "CLIP", "VAE encoder", "ControlNet"};
+    for (int g = 1; g < kGroups; ++g)
         if (set[g] && missing[g])
             throw Error(SDMI_ERR_WEIGHTS, std::string("finalize_weights: ") + kGroupName[g] + " weights are partially set; missing '" + missing[g]->name + "'");
     SDMI_HIP(hipStreamSynchronize(stream_));   // every packing kernel has run
@@ -1284,6 +1341,7 @@ void Engine::load_weights_dir(const char* dir) {
     // the CLIP subtree is read when it exists (load_stable_diffusion always has it, stablediffusion/load.rs:24)
     const bool have_clip = std::ifstream(std::string(dir) + "/clip/token_embedding/weight.npy").good();
     const bool have_enc = std::ifstream(std::string(dir) + "/autoencoder/encoder/conv_in/weight.npy").good();
+    const bool have_ctl = std::ifstream(std::string(dir) + "/controlnet/lin1_time_embed/weight.npy").good();
     for (auto& m : meta_) {   // optional per-module metadata files
         const std::string path = std::string(dir) + "/" + m.name + ".npy";
         if (!std::ifstream(path).good()) continue;
@@ -1294,7 +1352,7 @@ void Engine::load_weights_dir(const char* dir) {
         set_meta(m.name, raw.data() + 1, (size_t)m.n);
     }
     for (auto& e : entries_) {
-        if ((e.group == 1 && !have_clip) || (e.group == 2 && !have_enc)) continue;
+        if ((e.group == 1 && !have_clip) || (e.group == 2 && !have_enc) || (e.group == 3 && !have_ctl)) continue;
         const std::string path = std::string(dir) + "/" + e.name + ".npy";
         const size_t count = entry_count(e);
         if (e.kind == 0 && padded_cin(e) != e.dims[1]) {   // rare (a padded conv_in): through the padding path
@@ -1415,6 +1473,7 @@ void Engine::set_option(const std::string& key, const std::string& value) {
     else if (key == "fp8_ops") opt_fp8_ops_ = std::stoi(value);
     else if (key == "op_resid") opt_op_resid_ = std::stoi(value);
     else if (key == "op_misalign") opt_op_misalign_ = std::stoi(value);
+    else if (key == "op_f32") opt_op_f32_ = std::stoi(value);
     else if (key == "pool_fill") {   // tests: -1 = off, 0 .. 255 = the byte every pool block and persistent allocation made from now on is filled with (DevPool::set_fill)
         const int b = std::stoi(value);
         if (b < -1 || b > 255) throw Error(SDMI_ERR_INVALID, "pool_fill: -1 (off) or a byte 0 .. 255");
@@ -1444,7 +1503,7 @@ void Engine::set_option(const std::string& key, const std::string& value) {
         opt_b3_grouped_ = std::stoi(value);
     }
     else if (key == "keep_masters") {
-        if (std::any_of(entries_.begin(), entries_.end(), [](const WeightEntry& w) { return w.set; }) || arena_done_[0] || arena_done_[1] || arena_done_[2])
+        if (std::any_of(entries_.begin(), entries_.end(), [](const WeightEntry& w) { return w.set; }) || arena_done_[0] || arena_done_[1] || arena_done_[2] || arena_done_[3])
             throw Error(SDMI_ERR_STATE, "keep_masters decides what the weight arenas hold: set it before the first weight is loaded");
         opt_keep_masters_ = std::stoi(value) != 0;
     }
@@ -1640,7 +1699,11 @@ void Engine::conv(const ConvW& w, const Act& x, Act& y, int stride, int ups, con
     const int ho = (hin + 2 * pad + extra - w.k) / stride + 1, wo = (win + 2 * pad + extra - w.k) / stride + 1;
     if (y.n != x.n || y.h != ho || y.w != wo || y.c != w.cout) throw Error(SDMI_ERR_INVALID, "conv: output shape mismatch");
     ConvGemm p{};
-    if (resid && (resid->rows() != y.rows() || resid->c != y.c || resid->dt != y.dt)) throw Error(SDMI_ERR_STATE, "conv: residual shape / type mismatch");
+    // (an fp32 -> bf16 layer -- Cin < 32 at precision >= 1 -- adds its residual in fp32, in front of the rounding: k_gemm2.hip's epilogue)
+    const int resid_dt = (!x.dt && y.dt) ? 0 : y.dt;
+    if (resid && !x.dt && y.dt && (w.cout % 4 || y.stride() % 4 || resid->stride() % 4))   // (only that kernel's 16-byte epilogue rounds to bf16)
+        throw Error(SDMI_ERR_STATE, "conv: a residual on an fp32 -> bf16 layer needs cout and the row strides to be multiples of 4");
+    if (resid && (resid->rows() != y.rows() || resid->c != y.c || resid->dt != resid_dt)) throw Error(SDMI_ERR_STATE, "conv: residual shape / type mismatch");
     p.A = x.p; p.Bt = w.bt; p.C = y.p; p.bias = w.bias; p.rowvec = rowvec; p.resid = resid ? resid->p : nullptr;
     if (resid && !resid->p) throw Error(SDMI_ERR_STATE, "conv: the residual must exist as fp32");
     if (!x.dt && plane_gemm(w.cin, w.cout) && split_planes(w.bt)) { p.A3 = x.p3; p.a3_ld = x.ld3; }   // planes in, where the plane kernel takes the layer
@@ -1654,7 +1717,6 @@ void Engine::conv(const ConvW& w, const Act& x, Act& y, int stride, int ups, con
     if (!y.p && !y.p3) throw Error(SDMI_ERR_STATE, "conv: no output buffer");
     if (x.dt != w.dt) throw Error(SDMI_ERR_STATE, "conv: activation / weight storage types disagree");
     p.out_mode = x.dt ? (y.dt ? 0 : 1) : (y.dt ? 2 : 0);
-    if (resid && !x.dt && y.dt) throw Error(SDMI_ERR_STATE, "conv: residual not supported on the fp32->bf16 layers");
     launch_gemm(p, x.dt);
 }
 
@@ -2217,8 +2279,18 @@ void Engine::unet_release() {
 // of the text context (unet/mod.rs:646-647), which the reference recomputes in all
 // 2*n_steps forwards.
 void Engine::unet_prepare(const float* ctx_packed, int nb, int t_max, const int* kv_len_host,
-                          const std::vector<int>& ts) {
+                          const std::vector<int>& ts, int n_images, bool window, bool force_control) {
     unet_release();
+    // a controlled call (sticky state, sdmi_set_control): strength 0 is the plain call, launch for launch (force_control: control_residuals_dev, which ignores the strength)
+    const bool ctrl = ctrl_.set && (ctrl_.strength != 0.0 || force_control) && n_images > 0;
+    if (ctrl) {
+        if (!control_ready()) throw Error(SDMI_ERR_STATE, "control: the ControlNet weights (controlnet/...) are no longer complete");
+        if (ctrl_.hint_h != 8 * lat_h_ || ctrl_.hint_w != 8 * lat_w_)
+            throw Error(SDMI_ERR_INVALID, "control: the hint is " + std::to_string(ctrl_.hint_h) + " x " + std::to_string(ctrl_.hint_w) + " but the latent size in force, " +
+                                              std::to_string(lat_h_) + " x " + std::to_string(lat_w_) + ", needs " + std::to_string(8 * lat_h_) + " x " + std::to_string(8 * lat_w_));
+        if (ctrl_.n_hint != 1 && ctrl_.n_hint != n_images)
+            throw Error(SDMI_ERR_INVALID, "control: the call has n = " + std::to_string(n_images) + " images but the control was set with n_hint = " + std::to_string(ctrl_.n_hint));
+    }
     const int S = (int)ts.size(), mc = cfg_.model_channels, ed = 4 * mc, cd = cfg_.ctx_dim;
     us_.nb = nb; us_.t_max = t_max; us_.steps = S;
     us_.kv_len_host.assign(kv_len_host, kv_len_host + nb);
@@ -2238,14 +2310,29 @@ void Engine::unet_prepare(const float* ctx_packed, int nb, int t_max, const int*
     gemm(e1.f(), S, lin2_time_.bt, lin2_time_.bias, ed, ed, e2.f(), ed, nullptr, 0, /*dt=*/0);
     { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_silu(e2.f(), e2.f(), (long long)S * ed, stream_)); }  // SiLU(emb), shared by all ResBlocks
     count_kernel();
-    us_.temb.resize(res_list_.size());
-    for (size_t i = 0; i < res_list_.size(); ++i) {
+    // (the ControlNet's blocks follow the UNet's in res_list_ / st_list_: their rows exist in a controlled call only)
+    const size_t n_res = ctrl ? res_list_.size() : n_res_unet_, n_st = ctrl ? st_list_.size() : n_st_unet_;
+    us_.temb.resize(n_res);
+    for (size_t i = 0; i < n_res_unet_; ++i) {
         const ResW& r = *res_list_[i];
         us_.temb[i] = (float*)own((size_t)S * r.cout * 4);
         gemm(e2.f(), S, r.lin_embed.bt, r.lin_embed.bias, ed, r.cout, us_.temb[i], r.cout, nullptr, 0, /*dt=*/0);
     }
-    us_.kc.resize(st_list_.size());
-    us_.vc.resize(st_list_.size());
+    if (ctrl) {   // the ControlNet has a time MLP of its own (cldm.py: self.time_embed)
+        gemm(te.f(), S, ctl_lin1_time_.bt, ctl_lin1_time_.bias, mc, ed, e1.f(), ed, nullptr, 0, /*dt=*/0);
+        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_silu(e1.f(), e1.f(), (long long)S * ed, stream_)); }
+        count_kernel();
+        gemm(e1.f(), S, ctl_lin2_time_.bt, ctl_lin2_time_.bias, ed, ed, e2.f(), ed, nullptr, 0, /*dt=*/0);
+        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_silu(e2.f(), e2.f(), (long long)S * ed, stream_)); }
+        count_kernel();
+        for (size_t i = n_res_unet_; i < n_res; ++i) {
+            const ResW& r = *res_list_[i];
+            us_.temb[i] = (float*)own((size_t)S * r.cout * 4);
+            gemm(e2.f(), S, r.lin_embed.bt, r.lin_embed.bias, ed, r.cout, us_.temb[i], r.cout, nullptr, 0, /*dt=*/0);
+        }
+    }
+    us_.kc.resize(n_st);
+    us_.vc.resize(n_st);
     const float* ctx_e = ctx_packed;  // text context in the engine's storage type
     Buf ctx_h(this, bf16_ ? (size_t)nb * t_max * cd * 2 : 256);
     if (bf16_) {
@@ -2253,13 +2340,190 @@ void Engine::unet_prepare(const float* ctx_packed, int nb, int t_max, const int*
         count_kernel();
         ctx_e = ctx_h.f();
     }
-    for (size_t i = 0; i < st_list_.size(); ++i) {
+    for (size_t i = 0; i < n_st; ++i) {
         const SpatialW& s = *st_list_[i];
         us_.kc[i] = (float*)own((size_t)nb * t_max * s.c * esz());
         us_.vc[i] = (float*)own((size_t)nb * t_max * s.c * esz());
         gemm(ctx_e, nb * t_max, s.attn2.k.bt, nullptr, cd, s.c, us_.kc[i], s.c, nullptr, 0);
         gemm(ctx_e, nb * t_max, s.attn2.v.bt, nullptr, cd, s.c, us_.vc[i], s.c, nullptr, 0);
     }
+    if (ctrl) {
+        // the hint embedding, once per call: n_hint pictures through the eight hint convolutions, then laid out as the residual of the control encoder's first
+        // convolution -- one block of h w rows per batch row, image i of either CFG half reading hint i mod n_hint (device copies, no launch)
+        Act emb = control_hint_embed(ctrl_.hint_dev, ctrl_.n_hint, ctrl_.hint_h, ctrl_.hint_w);
+        const size_t per = (size_t)lat_h_ * lat_w_ * mc;
+        us_.hint_rows = (float*)own((size_t)nb * per * 4);
+        for (int b = 0; b < nb; ++b)
+            SDMI_HIP(hipMemcpyAsync(us_.hint_rows + (size_t)b * per, emb.p + (size_t)((b % n_images) % ctrl_.n_hint) * per, per * 4, hipMemcpyDeviceToDevice, stream_));
+        release(emb);
+        us_.ctrl = true;
+        us_.ctrl_window = window;
+    }
+}
+
+// ---- ControlNet (include/sdmi.h "ControlNet") ------------------------------------------------------------------------
+void Engine::check_control(const sdmi_control& c) {
+    if (!c.hint_rgb) throw Error(SDMI_ERR_INVALID, "control: null hint");
+    if (c.n_hint < 1) throw Error(SDMI_ERR_INVALID, "control: n_hint must be at least 1");
+    if (c.hint_h < 64 || c.hint_w < 64 || c.hint_h % 64 || c.hint_w % 64) throw Error(SDMI_ERR_INVALID, "control: hint_h / hint_w must be 8 x a latent size (positive multiples of 64)");
+    if (!std::isfinite(c.strength)) throw Error(SDMI_ERR_INVALID, "control: strength must be finite");
+    if ((unsigned long long)c.n_hint * (unsigned long long)c.hint_h * (unsigned long long)c.hint_w * 3ull > (1ull << 32))
+        throw Error(SDMI_ERR_UNSUPPORTED, "control: more than 4 GiB of hint pictures");
+    if (!(c.start >= 0.0 && c.start <= c.end && c.end <= 1.0)) throw Error(SDMI_ERR_INVALID, "control: the step window must satisfy 0 <= start <= end <= 1");
+}
+
+void Engine::set_control(const sdmi_control* c) {
+    if (!has_control()) throw Error(SDMI_ERR_STATE, "set_control: this context has no ControlNet (sdmi_config.control_hint_ch = 0)");
+    SDMI_HIP(hipSetDevice(cfg_.device));
+    if (!c) {
+        SDMI_HIP(hipStreamSynchronize(stream_));
+        if (ctrl_.hint_dev) (void)hipFree(ctrl_.hint_dev);
+        ctrl_ = Control{};
+        return;
+    }
+    if (!control_ready()) throw Error(SDMI_ERR_STATE, "set_control: the ControlNet weights (controlnet/...) are not loaded");
+    check_control(*c);
+    const size_t bytes = (size_t)c->n_hint * c->hint_h * c->hint_w * 3;
+    uint8_t* d = nullptr;
+    SDMI_HIP(hipMalloc((void**)&d, bytes));
+    hipError_t err = hipMemcpy(d, c->hint_rgb, bytes, hipMemcpyHostToDevice);
+    if (err != hipSuccess) { (void)hipFree(d); SDMI_HIP(err); }
+    SDMI_HIP(hipStreamSynchronize(stream_));
+    if (ctrl_.hint_dev) (void)hipFree(ctrl_.hint_dev);
+    ctrl_.set = true; ctrl_.hint_dev = d; ctrl_.hint_bytes = bytes;
+    ctrl_.n_hint = c->n_hint; ctrl_.hint_h = c->hint_h; ctrl_.hint_w = c->hint_w;
+    ctrl_.strength = c->strength; ctrl_.start = c->start; ctrl_.end = c->end;
+}
+
+// input_hint_block (cldm.py): eight 3x3 convolutions, SiLU after all but the last, fp32 at every precision.  u8 -> v / 255 with a zero 4th channel first.
+Act Engine::control_hint_embed(const uint8_t* hint_rgb_dev, int n, int hint_h, int hint_w) {
+    Range rng(this, "ControlNet hint");
+    // one picture at a time, like the VAE encoder (encode_image_dev): the launches of a picture -- tiles, split-K, summation order -- do not depend on how many hints the
+    // call has, so n_hint = 1 and the same hint given n times are the same bits
+    Act emb = new_act(n, hint_h / 8, hint_w / 8, ctl_hint_[7].cout, /*dt=*/0);
+    const size_t per = (size_t)emb.h * emb.w * emb.c;
+    for (int img = 0; img < n; ++img) {
+        Act x = new_act(1, hint_h, hint_w, 4, /*dt=*/0);
+        { ProfScope ps_o(this, PC_OTHER, 0, (double)x.rows() * 19.0); SDMI_HIP(launch_hint_u8_to_nhwc4(hint_rgb_dev + (size_t)img * hint_h * hint_w * 3, x.p, x.rows(), stream_)); }
+        count_kernel();
+        for (int i = 0; i < 8; ++i) {
+            const ConvW& w = ctl_hint_[i];
+            const int stride = (i == 2 || i == 4 || i == 6) ? 2 : 1;
+            Act y;
+            if (i == 7) { y = emb; y.n = 1; y.p = emb.p + (size_t)img * per; y.view = true; }
+            else y = new_act(1, x.h / stride, x.w / stride, w.cout, /*dt=*/0);
+            conv(w, x, y, stride, 0, nullptr, 0, nullptr);
+            release(x);
+            if (i != 7) {
+                { ProfScope ps_o(this, PC_OTHER, 0, (double)y.rows() * y.c * 8.0); SDMI_HIP(launch_silu(y.p, y.p, y.rows() * y.c, stream_)); }
+                count_kernel();
+            }
+            x = y;
+        }
+    }
+    return emb;
+}
+
+// The control encoder on the UNet's own assembled input: block 0's convolution takes the hint embedding as its GEMM residual, blocks 1 - 11 and the middle block
+// follow, and behind block j zero_convs/j writes r[j] (middle_block_out: r[12]), dense, in the engine's activation type.  Both halves of a CFG batch are computed.
+void Engine::control_run(const float* x_nhwc, int nb, int step, Act (&r)[13]) {
+    Range rng(this, "ControlNet::forward step " + std::to_string(step));
+    Act x; x.p = const_cast<float*>(x_nhwc); x.n = nb; x.h = lat_h_; x.w = lat_w_; x.c = ctl_blocks_[0].conv.cin; x.dt = 0;
+    Act prev{};
+    for (int j = 0; j < 12; ++j) {
+        const UBlock& b = ctl_blocks_[j];
+        Range rb(this, "control input_block " + std::to_string(j));
+        const int ho = b.kind == BK_DOWN ? x.h / 2 : x.h, wo = b.kind == BK_DOWN ? x.w / 2 : x.w;
+        Act y = new_act(nb, ho, wo, b.cout);
+        if (j == 0) {
+            Act hint; hint.p = us_.hint_rows; hint.n = nb; hint.h = ho; hint.w = wo; hint.c = b.cout; hint.dt = 0; hint.view = true;
+            conv(b.conv, x, y, 1, 0, nullptr, 0, &hint);   // (precision >= 1: an fp32 -> bf16 layer, the fp32 embedding is added in front of the rounding)
+        } else {
+            run_block(b, x, y, step);
+        }
+        if (prev.p) release(prev);
+        r[j] = new_act(nb, ho, wo, b.cout);
+        conv(ctl_zero_[j], y, r[j], 1, 0, nullptr, 0, nullptr);
+        prev = y;
+        x = y;
+    }
+    Act a = new_act(x.n, x.h, x.w, ctl_mid_res1_.cout); res_block(ctl_mid_res1_, x, a, step);
+    release(prev);
+    Act b = new_act(a.n, a.h, a.w, ctl_mid_st_.c); spatial_transformer(ctl_mid_st_, a, b); release(a);
+    Act c = new_act(b.n, b.h, b.w, ctl_mid_res2_.cout); res_block(ctl_mid_res2_, b, c, step); release(b);
+    r[12] = new_act(c.n, c.h, c.w, ctl_mid_out_.cout);
+    conv(ctl_mid_out_, c, r[12], 1, 0, nullptr, 0, nullptr);
+    release(c);
+}
+
+void Engine::control_hint_embed_dev(const uint8_t* hint_rgb, int n, int hint_h, int hint_w, float* out_nchw) {
+    if (!has_control()) throw Error(SDMI_ERR_STATE, "control_hint_embed: this context has no ControlNet (sdmi_config.control_hint_ch = 0)");
+    if (!control_ready()) throw Error(SDMI_ERR_STATE, "control_hint_embed: the ControlNet weights (controlnet/...) are not loaded");
+    if (n < 1 || hint_h < 64 || hint_w < 64 || hint_h % 64 || hint_w % 64) throw Error(SDMI_ERR_INVALID, "control_hint_embed: n >= 1, hint_h / hint_w positive multiples of 64");
+    check_batch(n);
+    Act emb = control_hint_embed(hint_rgb, n, hint_h, hint_w);
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(emb.p, out_nchw, n, emb.c, emb.h, emb.w, stream_)); }
+    count_kernel();
+    release(emb);
+}
+
+size_t Engine::control_residual_elems(int n) const {
+    size_t total = 0;
+    int h = lat_h_, w = lat_w_;
+    for (const UBlock& b : ctl_blocks_) {
+        if (b.kind == BK_DOWN) { h /= 2; w /= 2; }
+        total += (size_t)n * b.cout * h * w;
+    }
+    return total + (size_t)n * ctl_mid_out_.cout * h * w;
+}
+
+void Engine::control_residuals_dev(const float* x_nchw, int t, const float* context, int n, int T, float* out) {
+    if (!finalized_) throw Error(SDMI_ERR_STATE, "weights not finalized");
+    if (!has_control()) throw Error(SDMI_ERR_STATE, "control_residuals: this context has no ControlNet (sdmi_config.control_hint_ch = 0)");
+    if (!ctrl_.set) throw Error(SDMI_ERR_STATE, "control_residuals: no control is set (sdmi_set_control)");
+    if (n <= 0 || T <= 0) throw Error(SDMI_ERR_INVALID, "control_residuals: n and T must be positive");
+    check_batch(n);
+    const int H = lat_h_, W = lat_w_;
+    std::vector<int> kv(n, T), ts(1, t);
+    unet_prepare(context, n, T, kv.data(), ts, n, /*window=*/false, /*force_control=*/true);
+    Buf xin(this, (size_t)n * H * W * 4 * 4);
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nchw_to_nhwc(x_nchw, xin.f(), n, 4, H, W, 1.0f, stream_)); }
+    count_kernel();
+    Act r[13];
+    control_run(xin.f(), n, 0, r);
+    size_t off = 0;
+    for (auto& a : r) {
+        if (a.dt) SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(a.p, out + off, a.n, a.c, a.h, a.w, stream_));
+        else { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(a.p, out + off, a.n, a.c, a.h, a.w, stream_)); }
+        count_kernel();
+        off += (size_t)a.rows() * a.c;
+        release(a);
+    }
+    unet_release();
+}
+
+void Engine::run_block(const UBlock& b, const Act& in, Act& y, int step) {
+    switch (b.kind) {
+        case BK_CONV: conv(b.conv, in, y, 1, 0, nullptr, 0, nullptr); return;
+        case BK_DOWN: conv_raw(b.conv, in, y, 2, 0); return;
+        case BK_RES: res_block(b.res, in, y, step); return;
+        case BK_RES_ST: {
+            Act r = new_act(in.n, in.h, in.w, b.cout); res_block(b.res, in, r, step);
+            spatial_transformer(b.st, r, y); release(r); return;
+        }
+        case BK_RES_UP: {   // (fp32 engine: the tensor between the block and its up-convolution exists only as planes)
+            Act r = plane_gemm(b.cout, b.cout) ? new_act3(in.n, in.h, in.w, b.cout, 2) : new_act(in.n, in.h, in.w, b.cout);
+            res_block(b.res, in, r, step);
+            conv_raw(b.up, r, y, 1, 1); release(r); return;
+        }
+        case BK_RES_ST_UP: {
+            Act r = new_act(in.n, in.h, in.w, b.cout); res_block(b.res, in, r, step);
+            Act s = plane_gemm(b.cout, b.cout) ? new_act3(in.n, in.h, in.w, b.cout, 2) : new_act(in.n, in.h, in.w, b.cout);
+            spatial_transformer(b.st, r, s); release(r);
+            conv_raw(b.up, s, y, 1, 1); release(s); return;
+        }
+    }
+    throw Error(SDMI_ERR_STATE, "bad block kind");
 }
 
 // UNet::forward (unet/mod.rs:109-143) on NHWC activations.
@@ -2273,30 +2537,10 @@ void Engine::unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bo
     // latents stay fp32; a conditioned model (unet_in_ch > 4) reads the assembled [latent | cond | pad] rows of launch_assemble_unet_in
     Act x; x.p = const_cast<float*>(x_nhwc); x.n = nb; x.h = H; x.w = W; x.c = in_blocks_[0].conv.cin; x.dt = 0;
 
-    // every block's last kernel writes `y` (dense or a channel slice)
-    auto run_block = [&](const UBlock& b, const Act& in, Act& y) {
-        switch (b.kind) {
-            case BK_CONV: conv(b.conv, in, y, 1, 0, nullptr, 0, nullptr); return;
-            case BK_DOWN: conv_raw(b.conv, in, y, 2, 0); return;
-            case BK_RES: res_block(b.res, in, y, step); return;
-            case BK_RES_ST: {
-                Act r = new_act(in.n, in.h, in.w, b.cout); res_block(b.res, in, r, step);
-                spatial_transformer(b.st, r, y); release(r); return;
-            }
-            case BK_RES_UP: {   // (fp32 engine: the tensor between the block and its up-convolution exists only as planes)
-                Act r = plane_gemm(b.cout, b.cout) ? new_act3(in.n, in.h, in.w, b.cout, 2) : new_act(in.n, in.h, in.w, b.cout);
-                res_block(b.res, in, r, step);
-                conv_raw(b.up, r, y, 1, 1); release(r); return;
-            }
-            case BK_RES_ST_UP: {
-                Act r = new_act(in.n, in.h, in.w, b.cout); res_block(b.res, in, r, step);
-                Act s = plane_gemm(b.cout, b.cout) ? new_act3(in.n, in.h, in.w, b.cout, 2) : new_act(in.n, in.h, in.w, b.cout);
-                spatial_transformer(b.st, r, s); release(r);
-                conv_raw(b.up, s, y, 1, 1); release(s); return;
-            }
-        }
-        throw Error(SDMI_ERR_STATE, "bad block kind");
-    };
+    // a controlled step: the control encoder runs first, on the same input; its residuals wait in r[] until the skips exist
+    const bool controlled = control_on(step);
+    Act ctl_r[13];
+    if (controlled) control_run(x_nhwc, nb, step, ctl_r);
 
     const int nblk = (int)in_blocks_.size();
     std::vector<Act> cats(nblk);
@@ -2324,7 +2568,7 @@ void Engine::unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bo
             spatial_transformer(b.st, r, y);
             release(r);
         } else {
-            run_block(b, x, y);
+            run_block(b, x, y, step);
         }
         x = y;
     }
@@ -2334,6 +2578,29 @@ void Engine::unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bo
         Act c = slice(cats[0], 0, cats[0].c - x.c);
         if (c.c != mid_res2_.cout) throw Error(SDMI_ERR_STATE, "unet: middle block width mismatch");
         res_block(mid_res2_, b, c, step); release(b);
+    }
+    if (controlled) {
+        // ControlNet adds to the SAVED copies only: the encoder above ran on the unmodified activations, the output blocks below read the sums.  One launch for
+        // the 12 skip slices (input block j's skip lives in cats[11 - j]) and the middle block's output (the x slice of cats[0]), in every form they exist in.
+        ControlAdd ca{};
+        ca.n_seg = 13; ca.dt = edt(); ca.strength = (float)ctrl_.strength;
+        double bytes = 0;
+        for (int j = 0; j < 13; ++j) {
+            const Act& cat = cats[j < 12 ? nblk - 1 - j : 0];
+            const Act dst = j < 12 ? slice(cat, cat.c - ctl_r[j].c, ctl_r[j].c) : slice(cat, 0, ctl_r[j].c);
+            if (!dst.p || dst.dt != ctl_r[j].dt || dst.rows() != ctl_r[j].rows()) throw Error(SDMI_ERR_STATE, "control: a residual does not match its skip");
+            ControlSeg& g = ca.seg[j];
+            g.y = dst.p; g.r = ctl_r[j].p; g.y3 = dst.p3; g.rows = dst.rows(); g.c = dst.c; g.ld = dst.stride(); g.ld3 = dst.ld3;
+            bytes += (double)g.rows * g.c * (edt() ? 6.0 : (g.y3 ? 18.0 : 12.0));
+        }
+        if (record_shapes_) {   // option dump_choices: how many of the segments also carry planes
+            int planes = 0;
+            for (int j = 0; j < ca.n_seg; ++j) planes += ca.seg[j].y3 ? 1 : 0;
+            ++choice_counts_["control_add segs=" + std::to_string(ca.n_seg) + " planes=" + std::to_string(planes) + " dt=" + std::to_string(ca.dt)];
+        }
+        { ProfScope ps_o(this, PC_OTHER, 0, bytes); ps_o.set_tag("control_add"); SDMI_HIP(launch_control_add(ca, stream_)); }
+        count_kernel();
+        for (auto& a : ctl_r) release(a);
     }
     Act last{};
     for (int i = 0; i < nblk; ++i) {
@@ -2348,7 +2615,7 @@ void Engine::unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bo
             y = new_act(nb, cats[i].h << (up ? 1 : 0), cats[i].w << (up ? 1 : 0), b.cout);
             last = y;
         }
-        run_block(b, cats[i], y);
+        run_block(b, cats[i], y, step);
         release(cats[i]);
     }
     Act gn = new_act(last.n, last.h, last.w, last.c);
@@ -2423,7 +2690,7 @@ void Engine::unet_forward_dev(const float* x_nchw, int t, const float* context, 
     check_batch(n);
     const int H = lat_h_, W = lat_w_;
     std::vector<int> kv(n, T), ts(1, t);
-    unet_prepare(context, n, T, kv.data(), ts);
+    unet_prepare(context, n, T, kv.data(), ts, n, /*window=*/false);
     Buf xin(this, (size_t)n * H * W * 4 * 4), xout(this, (size_t)n * H * W * 4 * 4);
     { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nchw_to_nhwc(x_nchw, xin.f(), n, 4, H, W, 1.0f, stream_)); }
     count_kernel();
@@ -2488,7 +2755,7 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
                                 hipMemcpyDeviceToDevice, stream_));
     std::vector<int> kv(nb);
     for (int b = 0; b < n; ++b) { kv[b] = Tu; kv[n + b] = T; }
-    unet_prepare(ctx.f(), nb, t_max, kv.data(), ts);
+    unet_prepare(ctx.f(), nb, t_max, kv.data(), ts, n);
 
     const long long per_half = (long long)n * H * W * 4;
     Buf latent(this, per_half * 4), unet_in(this, 2 * per_half * 4), eps(this, 2 * per_half * 4);
@@ -2749,6 +3016,7 @@ void Engine::check_hires(const sdmi_hires* hr) {
 void Engine::hires_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps, const float* init_latent,
                               const sdmi_hires& hr, const float* hires_noise, float* latent_out) {
     check_hires(&hr);
+    if (ctrl_.set) throw Error(SDMI_ERR_UNSUPPORTED, "hires: a control is set (sdmi_set_control) and the first pass runs at another size than its hint: clear it first");
     if (finalized_) check_cond("hires", false);
     const size_t steps2 = hr.hires_steps ? (size_t)hr.hires_steps : n_steps;
     {   // the second pass's argument errors before the first pass runs
@@ -3040,7 +3308,7 @@ void Engine::op_conv2d(const float* x, const float* wt, const float* bias, int n
         r.p = const_cast<float*>(stage_epi(rb, epi->resid, y.rows(), y.c, r.ld, y.dt, (long long)y.h * y.w));
         return r;
     };
-    if (fp8_ && opt_fp8_convs_ && k == 3 && stride == 1 && !ups && cin % 32 == 0 && cout % 8 == 0) {
+    if (!opt_op_f32_ && fp8_ && opt_fp8_convs_ && k == 3 && stride == 1 && !ups && cin % 32 == 0 && cout % 8 == 0) {
         // precision = 2 mirrors the model's ResBlock convs: MXFP8 input (quantised here from the fp32 argument; the model
         // gets it from the fused GroupNorm), MXFP8 weight, bf16 output
         const int cp = (cin + 127) / 128 * 128;
@@ -3064,8 +3332,9 @@ void Engine::op_conv2d(const float* x, const float* wt, const float* bias, int n
     ConvW w; w.cin = cin; w.cout = cout; w.k = k;
     // precision = 1 mirrors the model: Cin % 64 == 0 -> bf16 kernel, Cin < 32 -> fp32 kernel emitting bf16,
     // <= 4 output channels (eps / RGB heads) -> fp32 output
-    w.dt = (bf16_ && cin % 64 == 0) ? 1 : 0;
-    if (bf16_ && !w.dt && cin >= 32) throw Error(SDMI_ERR_UNSUPPORTED, "bf16 conv2d: Cin must be a multiple of 64 (or < 32)");
+    // option op_f32 (tests): the fp32 route at every precision -- fp32 weight, input and output, what the ControlNet hint convolutions run
+    w.dt = (bf16_ && cin % 64 == 0 && !opt_op_f32_) ? 1 : 0;
+    if (bf16_ && !w.dt && cin >= 32 && !opt_op_f32_) throw Error(SDMI_ERR_UNSUPPORTED, "bf16 conv2d: Cin must be a multiple of 64 (or < 32)");
     Buf bt(this, (size_t)cout * cin * k * k * 4);
     if (w.dt) SDMI_HIP(launch_pack_conv_weight_bf16(wt, bt.p, cout, cin, k, k, stream_));
     else SDMI_HIP(launch_pack_conv_weight(wt, bt.f(), cout, cin, k, k, stream_));
@@ -3076,7 +3345,7 @@ void Engine::op_conv2d(const float* x, const float* wt, const float* bias, int n
     else SDMI_HIP(launch_nchw_to_nhwc(x, a.p, n, cin, h, wd, 1.0f, stream_));
     const int hin = h << ups, win = wd << ups;
     const int ho = (hin + 2 * pad - k) / stride + 1, wo = (win + 2 * pad - k) / stride + 1;
-    Act y = new_act(n, ho, wo, cout, (bf16_ && cout > 4) ? 1 : 0);
+    Act y = new_act(n, ho, wo, cout, (bf16_ && cout > 4 && !opt_op_f32_) ? 1 : 0);
     // option op_resid (tests): out = conv(x) + x through the GEMM's residual epilogue, where the shapes allow it
     const bool with_resid = opt_op_resid_ && cin == cout && stride == 1 && !ups && a.dt == y.dt;
     Act r;

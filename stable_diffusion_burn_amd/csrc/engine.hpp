@@ -129,7 +129,7 @@ struct WeightEntry {
     int64_t dims[4];
     float** dst;  // where the device pointer lives (null for alphas)
     int wdt = 0;  // storage type of the packed weight: 0 fp32, 1 bf16
-    int group = 0;  // 0: hot path (required); 1: CLIP text encoder, 2: VAE encoder (each optional as a whole)
+    int group = 0;  // 0: hot path (required); 1: CLIP text encoder, 2: VAE encoder, 3: ControlNet (each optional as a whole)
     float** dst8 = nullptr;   // precision = 2: where the MXFP8 copy of a conv weight and its scales go (null: none)
     float** dsts = nullptr;
     float pre_scale = 1.f;    // the tensor is multiplied by this in fp32 before it is packed (bf16 / MXFP8 query projections: attn_bf16_q_scale)
@@ -157,6 +157,8 @@ public:
     void load_weights_dir(const char* dir);
     void load_weights_mpk(const char* path);
     void load_weights_safetensors(const char* path);   // an SD v1.x CompVis checkpoint, converted on the device
+    void load_safetensors_groups(const char* path, bool control);   // the route both .safetensors loaders share
+    void load_control_safetensors(const char* path);   // a ControlNet in the cldm layout -> weight group 3
     void load_weights_packed(const float* data, size_t n_floats, int groups);
     size_t packed_size(int groups) const;
     void finalize_weights();
@@ -178,6 +180,20 @@ public:
     // CLIP::forward (clip/mod.rs:56-75): int32 tokens [n, T] on the device -> [n, T, ctx_dim] fp32 (both precisions)
     void clip_forward_dev(const int32_t* tokens, int n, int T, float* out);
     bool clip_ready() const { return clip_ready_; }
+    // ControlNet (include/sdmi.h "ControlNet").  control_ready: every tensor of weight group 3 is set (they may arrive before or after
+    // finalize_weights, one by one or through a loader).  The control state is sticky, like the sampler: hint_dev is the caller's hint on the device.
+    bool has_control() const { return cfg_.control_hint_ch != 0; }
+    bool control_ready() const;
+    static void check_control(const sdmi_control& c);   // SDMI_ERR_INVALID for what the header lists
+    void set_control(const sdmi_control* c);
+    bool control_set() const { return ctrl_.set; }
+    // step i of the S steps a call runs is controlled iff start * S <= i < end * S, in f64 (THE rule; sdmi_control_step_on)
+    static bool control_step_on(double start, double end, int i, int S) { return start * (double)S <= (double)i && (double)i < end * (double)S; }
+    // hint_rgb: n x [hint_h, hint_w, 3] u8 on the DEVICE -> out [n, mc, hint_h / 8, hint_w / 8] fp32 NCHW (device)
+    void control_hint_embed_dev(const uint8_t* hint_rgb, int n, int hint_h, int hint_w, float* out_nchw);
+    // the 13 residuals of the sticky hint (strength ignored) for x [n,4,h,w], t, context [n,T,cd]: NCHW fp32, back to back (device pointers)
+    void control_residuals_dev(const float* x_nchw, int t, const float* context, int n, int T, float* out);
+    size_t control_residual_elems(int n) const;   // floats control_residuals_dev writes
     // Autoencoder::encode_image (autoencoder/mod.rs:60-66): img [n,3,8h,8w] NCHW -> latent mean [n,4,h,w] NCHW (device pointers)
     void encode_image_dev(const float* img_nchw, int n, float* latent_nchw);
     void sample_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale,
@@ -312,13 +328,14 @@ private:
     // batched weight staging (engine.cpp "weights")
     struct Stager;
     std::unique_ptr<Stager> stager_;
-    bool arena_done_[3] = {false, false, false};
+    static constexpr int kGroups = 4;
+    bool arena_done_[kGroups] = {false, false, false, false};
     // precision = 0: every packed fp32 weight also exists as three bf16 planes (k_gemm3x.hip) in a parallel arena; the planes of
     // the weight at byte offset o of arena g start at offset 3 o / 2 of split arena g (6 bytes per weight instead of 4), so
     // weights that are adjacent rows of one GEMM (q | k | v) stay adjacent
-    char* arena_base_[3] = {nullptr, nullptr, nullptr};
-    size_t arena_bytes_[3] = {0, 0, 0};
-    char* split_base_[3] = {nullptr, nullptr, nullptr};
+    char* arena_base_[kGroups] = {nullptr, nullptr, nullptr, nullptr};
+    size_t arena_bytes_[kGroups] = {0, 0, 0, 0};
+    char* split_base_[kGroups] = {nullptr, nullptr, nullptr, nullptr};
     struct SplitRegion { char* base; size_t bytes; char* planes; };
     std::vector<SplitRegion> split_regions_;
     const void* split_planes(const float* bt) const;
@@ -426,7 +443,15 @@ private:
     void vae_attn(const VaeAttnW& w, const Act& x, Act& y);
 
     // UNet driver
-    void unet_prepare(const float* ctx_packed, int nb, int t_max, const int* kv_len_host, const std::vector<int>& ts);
+    // n_images (a controlled call): the images of the call, nb = n_images or 2 n_images (a CFG batch); window: false = every step is controlled (unet_forward)
+    void unet_prepare(const float* ctx_packed, int nb, int t_max, const int* kv_len_host, const std::vector<int>& ts, int n_images = 0, bool window = true,
+                      bool force_control = false);   // force_control: a controlled prepare whatever the strength (control_residuals_dev)
+    void run_block(const UBlock& b, const Act& in, Act& y, int step);   // one UNet block; its last kernel writes y (dense or a channel slice)
+    // ControlNet: the hint embedding [n][h][w][mc] fp32 of n hints on the device (the caller releases it); the control encoder on the assembled UNet input -> r[13]
+    // dense, in the engine's activation type (the caller releases them); whether step `step` of the call in flight is controlled
+    Act control_hint_embed(const uint8_t* hint_rgb_dev, int n, int hint_h, int hint_w);
+    void control_run(const float* x_nhwc, int nb, int step, Act (&r)[13]);
+    bool control_on(int step) const { return us_.ctrl && (!us_.ctrl_window || control_step_on(ctrl_.start, ctrl_.end, step, us_.steps)); }
     void unet_release();
     void unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bool cfg_pair = false);
     void decode_one(const float* z_nhwc, int n, Act& img);
@@ -520,6 +545,8 @@ private:
     int opt_fp8_linear_ = 0;         // precision = 2: 0 (default: the accuracy budget of 6e-2 final-latent relative RMS) = MXFP8 on the ResBlock / ResnetBlock 3x3
                                      // convolutions only; 1 = also the transformer blocks' Linear layers and the 1x1 / up / down convolutions (8.1e-2)
     sdmi_sampler sampler_{};          // all zero: kind 0, eta 0
+    struct Control { bool set = false; uint8_t* hint_dev = nullptr; size_t hint_bytes = 0; int n_hint = 0, hint_h = 0, hint_w = 0; double strength = 1, start = 0, end = 1; } ctrl_;
+    int opt_op_f32_ = 0;             // tests: op_conv2d runs the fp32 route (fp32 weight, input and output) at every precision -- the route of the ControlNet hint convolutions
     hipStream_t stream_ = nullptr;
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr, ev_user_ = nullptr;
     hipStream_t user_stream_ = nullptr;
@@ -547,6 +574,13 @@ private:
     SpatialW mid_st_;
     NormW unet_norm_out_;
     ConvW unet_conv_out_;
+    size_t n_res_unet_ = 0, n_st_unet_ = 0;   // res_list_ / st_list_ entries of the UNet itself; the ControlNet's follow
+    // ControlNet (optional weight group 3): its own time MLP, encoder and middle block, the hint convolutions, the zero convolutions
+    LinW ctl_lin1_time_, ctl_lin2_time_;
+    std::vector<UBlock> ctl_blocks_;
+    ResW ctl_mid_res1_, ctl_mid_res2_;
+    SpatialW ctl_mid_st_;
+    ConvW ctl_hint_[8], ctl_zero_[12], ctl_mid_out_;
     std::vector<ResW*> res_list_;       // index = temb_index
     std::vector<SpatialW*> st_list_;    // index = ctx_index
     // VAE decoder
@@ -578,6 +612,8 @@ private:
         int* kv_len_dev = nullptr;
         std::vector<int> kv_len_host;
         std::vector<void*> owned;
+        bool ctrl = false, ctrl_window = true;   // a controlled call: the control blocks' tables are prepared, hint_rows holds the hint embedding
+        float* hint_rows = nullptr;              // [nb][h][w][mc] fp32: row block i = the embedding of hint (i mod n_images) mod n_hint
     } us_;
 
     // options

@@ -314,4 +314,18 @@ hipError_t launch_lora_merge(const LoraMerge& m, hipStream_t s);
 // channels: the VAE encoder's RGB one, cin = 3; an inpainting UNet's, cin = 9; d1 = kh kw; cin < 32).  One launch.
 hipError_t launch_unpack_tensor(const void* raw, int dtype, int transform, long long d0, long long d1, float* out, hipStream_t s, int cin = 3);
 
+// ---- ControlNet (k_control.hip) --------------------------------------------------------------------------------
+// rgb [pixels][3] u8 (HWC, sample_image's layout) -> dst [pixels][4] fp32 = v / 255, channel 3 = 0: a ControlNet hint lives in [0, 1], not in [-1, 1]
+hipError_t launch_hint_u8_to_nhwc4(const uint8_t* rgb, float* dst, long long pixels, hipStream_t s);
+// ONE launch for all residuals of a controlled UNet step: segment i is y[row][0 .. c) += strength * r[row][0 .. c) over `rows` rows; y has a row stride and starts at its
+// channel offset (a skip slice of a cats buffer), r is dense.  Every form the destination exists in is written:
+//   dt 0: y fp32 (ld elements between rows) and, where y3 != null, the three bf16 planes of the NEW fp32 value by k_split3.hpp's split (ld3 bytes between rows) --
+//         bit for bit what a producer of that fp32 value writes;
+//   dt 1: y and r bf16, y = rn(float(y) + strength * float(r)).
+// c % 32 == 0 (dt 0) / c % 8 == 0 (dt 1); every base and row stride a multiple of 16 bytes.
+struct ControlSeg { void* y; const void* r; void* y3; long long rows; int c, ld, ld3; };
+constexpr int kControlMaxSegs = 13;
+struct ControlAdd { ControlSeg seg[kControlMaxSegs]; int n_seg; int dt; float strength; };
+hipError_t launch_control_add(const ControlAdd& a, hipStream_t s);
+
 }  // namespace sdmi

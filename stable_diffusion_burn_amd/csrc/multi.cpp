@@ -112,6 +112,8 @@ public:
         if (T <= 0 || Tu <= 0 || n_images <= 0) throw Error(SDMI_ERR_INVALID, "sample_image_sharded: T, Tu and n_images must be positive");
         const int R = size();
         if (engine(0).cond_ch() > 0) throw Error(SDMI_ERR_UNSUPPORTED, "sample_image_sharded: a UNet with conditioning channels (unet_in_ch > 4) has no sharded path");
+        for (int r = 0; r < R; ++r)
+            if (engine(r).control_set()) throw Error(SDMI_ERR_UNSUPPORTED, "sample_image_sharded: a device context has a control set (sdmi_set_control): ControlNet has no sharded path");
         const int cd = engine(0).config().ctx_dim, H = engine(0).latent_h(), W = engine(0).latent_w();
         for (int r = 1; r < R; ++r)   // sdmi_set_latent_size is per device context
             if (engine(r).latent_h() != H || engine(r).latent_w() != W) throw Error(SDMI_ERR_STATE, "sample_image_sharded: the device contexts disagree on the latent size");

@@ -449,6 +449,67 @@ int sdmi_set_sampler(sdmi_ctx* ctx, const sdmi_sampler* sampler) {
     return guarded([&] { eng(ctx).set_sampler(sampler); });
 }
 
+// ---- ControlNet ------------------------------------------------------------------------------------------------
+int sdmi_load_control_safetensors(sdmi_ctx* ctx, const char* path) {
+    return guarded([&] { eng(ctx).load_control_safetensors(path); });
+}
+
+int sdmi_control_ready(sdmi_ctx* ctx) {
+    int ready = 0;
+    int st = guarded([&] { ready = eng(ctx).control_ready() ? 1 : 0; });
+    return st == SDMI_OK ? ready : st;
+}
+
+int sdmi_set_control(sdmi_ctx* ctx, const sdmi_control* control) {
+    return guarded([&] { eng(ctx).set_control(control); });
+}
+
+int sdmi_control_step_on(double start, double end, int32_t step, int32_t n_steps) {
+    if (!(start >= 0.0 && start <= end && end <= 1.0) || step < 0 || n_steps < 1 || step >= n_steps) return SDMI_ERR_INVALID;
+    return Engine::control_step_on(start, end, step, n_steps) ? 1 : 0;
+}
+
+int sdmi_control_hint_embed(sdmi_ctx* ctx, const uint8_t* hint_rgb, int32_t n, int32_t hint_h, int32_t hint_w, float* out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (!hint_rgb || !out) throw Error(SDMI_ERR_INVALID, "control_hint_embed: null pointer");
+        if (n < 1 || hint_h < 64 || hint_w < 64 || hint_h % 64 || hint_w % 64) throw Error(SDMI_ERR_INVALID, "control_hint_embed: n >= 1, hint_h / hint_w positive multiples of 64");
+        if (!e.has_control()) throw Error(SDMI_ERR_STATE, "control_hint_embed: this context has no ControlNet (sdmi_config.control_hint_ch = 0)");
+        Engine::Call call(e);
+        DevIn dh(e, hint_rgb, (size_t)n * hint_h * hint_w * 3);
+        DevOut dout(e, out, (size_t)n * e.config().model_channels * (hint_h / 8) * (hint_w / 8) * sizeof(float));
+        e.control_hint_embed_dev(reinterpret_cast<const uint8_t*>(dh.buf.p), n, hint_h, hint_w, dout.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
+int64_t sdmi_control_residuals_size(sdmi_ctx* ctx, int32_t n) {
+    int64_t r = 0;
+    int st = guarded([&] {
+        Engine& e = eng(ctx);
+        if (n < 1) throw Error(SDMI_ERR_INVALID, "control_residuals_size: n must be positive");
+        if (!e.has_control()) throw Error(SDMI_ERR_STATE, "control_residuals_size: this context has no ControlNet (sdmi_config.control_hint_ch = 0)");
+        r = (int64_t)e.control_residual_elems(n);
+    });
+    return st == SDMI_OK ? r : st;
+}
+
+int sdmi_control_residuals(sdmi_ctx* ctx, const float* x, int32_t t, const float* context, int32_t n, int32_t T, float* out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (n <= 0 || T <= 0) throw Error(SDMI_ERR_INVALID, "control_residuals: n and T must be positive");
+        if (!e.has_control()) throw Error(SDMI_ERR_STATE, "control_residuals: this context has no ControlNet (sdmi_config.control_hint_ch = 0)");
+        const size_t lat = (size_t)n * 4 * e.latent_h() * e.latent_w() * sizeof(float);
+        Engine::Call call(e);
+        DevIn dx(e, x, lat), dc(e, context, (size_t)n * T * e.config().ctx_dim * sizeof(float));
+        DevOut dout(e, out, e.control_residual_elems(n) * sizeof(float));
+        e.control_residuals_dev(dx.f(), t, dc.f(), n, T, dout.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
 int sdmi_get_sampler(sdmi_ctx* ctx, sdmi_sampler* out) {
     return guarded([&] {
         if (!out) throw Error(SDMI_ERR_INVALID, "get_sampler: null output");

@@ -24,7 +24,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _capi
-from ._capi import SdmiConfig, SdmiError, SdmiHires, SdmiInpaint, SdmiOpView, SdmiSampler, check, load_library
+from ._capi import SdmiConfig, SdmiControl, SdmiError, SdmiHires, SdmiInpaint, SdmiOpView, SdmiSampler, check, load_library
 
 def mpk_list(path) -> list:
     """[(dump name, shape, file offset)] of a Burn .mpk record, parsed by the C++ reader (host only, no GPU)."""
@@ -71,6 +71,20 @@ def checkpoint_key(name: str) -> tuple:
     buf = C.create_string_buffer(need.value)
     check(lib.sdmi_checkpoint_key(name.encode(), buf, need.value, C.byref(need), C.byref(tr)))
     return buf.value.decode(), bool(tr.value)
+
+
+def control_step_on(start: float, end: float, step: int, n_steps: int) -> bool:
+    """THE step-window rule of a control (sdmi_control_step_on, host only, no GPU): start * n_steps <= step < end * n_steps, in f64."""
+    r = load_library().sdmi_control_step_on(float(start), float(end), int(step), int(n_steps))
+    if r < 0:
+        check(r)
+    return bool(r)
+
+
+def control_residual_shapes(model_channels: int) -> list:
+    """[(channels, log2 of the downscale)] of the 13 ControlNet residuals: the 12 input blocks' outputs, then the middle block's."""
+    mc = model_channels
+    return [(mc, 0)] * 3 + [(mc, 1), (2 * mc, 1), (2 * mc, 1), (2 * mc, 2), (4 * mc, 2), (4 * mc, 2), (4 * mc, 3), (4 * mc, 3), (4 * mc, 3), (4 * mc, 3)]
 
 
 def default_alphas_cumprod(n: int = 1000) -> np.ndarray:
@@ -292,7 +306,7 @@ class MultiLoraAdapter:
             self._owner = None
 
 
-__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "safetensors_list", "checkpoint_key", "default_alphas_cumprod", "img2img_timesteps", "sampler_coefs", "resize_weights", "load_lora_npz", "save_lora_npz", "LoraAdapter", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
+__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "safetensors_list", "checkpoint_key", "default_alphas_cumprod", "control_step_on", "control_residual_shapes", "img2img_timesteps", "sampler_coefs", "resize_weights", "load_lora_npz", "save_lora_npz", "LoraAdapter", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
 
 
 @dataclass(frozen=True)
@@ -314,6 +328,8 @@ class ModelConfig:
     clip_ctx: int = 77
     # input channels of the UNet: 4 = the latent alone; 5..12 = the latent + conditioning channels (9: the SD v1 inpainting checkpoints)
     unet_in_ch: int = 4
+    # channels of a ControlNet's hint picture: 0 = no ControlNet, 3 = an RGB hint (the model gets the weight group controlnet/...)
+    control_hint_ch: int = 0
 
     @classmethod
     def sd_v1_4(cls, precision: int = 0, clip: bool = True) -> "ModelConfig":
@@ -360,6 +376,7 @@ class StableDiffusion:
         cfg.clip_vocab = config.clip_vocab
         cfg.clip_ctx = config.clip_ctx
         cfg.unet_in_ch = config.unet_in_ch
+        cfg.control_hint_ch = config.control_hint_ch
         self._ctx = C.c_void_p()
         check(self._lib.sdmi_create(C.byref(self._ctx), C.byref(cfg)))
         # every option this context was given, in order (bench.py prints the non-default ones next to its figures: `applied_options`)
@@ -416,9 +433,12 @@ class StableDiffusion:
         check(self._lib.sdmi_set_weight(self._ctx, name.encode(), _fp(a), a.ndim, dims))
 
     GROUP_HOT, GROUP_CLIP, GROUP_ENCODER = 1, 2, 4
+    GROUP_CONTROL = 8   # never part of a packed image: sdmi_load_weights_packed keeps its groups 1..7
 
     @staticmethod
     def _group_of(name: str) -> int:
+        if name.startswith("controlnet/"):
+            return StableDiffusion.GROUP_CONTROL
         if name.startswith("clip/"):
             return StableDiffusion.GROUP_CLIP
         if name.startswith("autoencoder/encoder/") or name.startswith("autoencoder/quant_conv/"):
@@ -461,6 +481,75 @@ class StableDiffusion:
         """An SD v1.x checkpoint in the CompVis layout, one .safetensors file (F32 / F16 / BF16), converted on the device + finalize."""
         check(self._lib.sdmi_load_weights_safetensors(self._ctx, str(path).encode()))
         check(self._lib.sdmi_finalize_weights(self._ctx))
+
+    # ---- ControlNet (include/sdmi.h "ControlNet"; DESIGN.md section 9g) ------------------
+    def load_control_safetensors(self, path) -> None:
+        """A ControlNet in the cldm layout ("control_model.…"), one .safetensors file (F32 / F16 / BF16) -> the weight group controlnet/...
+        (sdmi_load_control_safetensors).  The base model is not touched; a set control stays set."""
+        check(self._lib.sdmi_load_control_safetensors(self._ctx, str(path).encode()))
+
+    @property
+    def control_ready(self) -> bool:
+        r = self._lib.sdmi_control_ready(self._ctx)
+        if r < 0:
+            check(r)
+        return bool(r)
+
+    def set_control(self, hint, strength: float = 1.0, start: float = 0.0, end: float = 1.0) -> None:
+        """The control of every later forward / sampling call of this context (sdmi_set_control; sticky): hint uint8 [n_hint, 8h, 8w, 3] (or [8h, 8w, 3]:
+        one hint for every image), its values / 255; strength multiplies the 13 residuals; step i of the S steps a call runs is controlled iff
+        start * S <= i < end * S.  None clears."""
+        if hint is None:
+            check(self._lib.sdmi_set_control(self._ctx, None))
+            return
+        hint = np.ascontiguousarray(hint)
+        if hint.dtype != np.uint8:
+            raise ValueError(f"hint must be uint8, got {hint.dtype}")
+        if hint.ndim == 3:
+            hint = hint[None]
+        if hint.ndim != 4 or hint.shape[3] != 3:
+            raise ValueError(f"hint must be [n, H, W, 3], got {hint.shape}")
+        c = SdmiControl()
+        c.hint_rgb = hint.ctypes.data_as(C.POINTER(C.c_uint8))
+        c.n_hint, c.hint_h, c.hint_w = int(hint.shape[0]), int(hint.shape[1]), int(hint.shape[2])
+        c.strength, c.start, c.end = float(strength), float(start), float(end)
+        check(self._lib.sdmi_set_control(self._ctx, C.byref(c)))
+
+    def control_hint_embed(self, hint) -> np.ndarray:
+        """The hint embedding [n, model_channels, H / 8, W / 8] of hint uint8 [n, H, W, 3] (sdmi_control_hint_embed)."""
+        hint = np.ascontiguousarray(hint, dtype=np.uint8)
+        if hint.ndim != 4 or hint.shape[3] != 3:
+            raise ValueError(f"hint must be [n, H, W, 3], got {hint.shape}")
+        n, H, Wd = hint.shape[:3]
+        out = np.empty((n, self.config.model_channels, H // 8, Wd // 8), np.float32)
+        check(self._lib.sdmi_control_hint_embed(self._ctx, hint.ctypes.data_as(C.POINTER(C.c_uint8)), n, H, Wd, _fp(out)))
+        return out
+
+    def control_residuals(self, x, t: int, context) -> list:
+        """The 13 residuals of the set control for x [n,4,h,w], timestep t and context [n,T,ctx_dim] (sdmi_control_residuals; strength and step window ignored):
+        a list of NCHW arrays, zero_convs 0 .. 11 then middle_block_out."""
+        h, w = self.latent_size
+        x = _f32(x, name="x")
+        if x.ndim != 4 or x.shape[1:] != (4, h, w):
+            raise ValueError(f"x must be [n,4,{h},{w}], got {x.shape}")
+        n = x.shape[0]
+        context = _f32(context, name="context")
+        if context.ndim != 3 or context.shape[0] != n or context.shape[2] != self.config.ctx_dim:
+            raise ValueError(f"context must be [{n}, T, {self.config.ctx_dim}], got {context.shape}")
+        total = self._lib.sdmi_control_residuals_size(self._ctx, n)
+        if total < 0:
+            check(int(total))
+        flat = np.empty(int(total), np.float32)
+        check(self._lib.sdmi_control_residuals(self._ctx, _fp(x), int(t), _fp(context), n, context.shape[1], _fp(flat)))
+        mc = self.config.model_channels
+        out, off = [], 0
+        for c, s in control_residual_shapes(mc):
+            shape = (n, c, h >> s, w >> s)
+            cnt = int(np.prod(shape))
+            out.append(flat[off:off + cnt].reshape(shape))
+            off += cnt
+        assert off == flat.size
+        return out
 
     def set_stream(self, hip_stream, enable: bool = True) -> None:
         """Name the HIP stream (integer handle, e.g. torch.cuda.current_stream().cuda_stream) the caller's device
@@ -528,7 +617,7 @@ class StableDiffusion:
         check(self._lib.sdmi_lora_effective_weight(self._ctx, name.encode(), _fp(out), out.size))
         return out
 
-    def load_weights(self, provider, clip: bool = True, vae_encoder: bool = True) -> None:
+    def load_weights(self, provider, clip: bool = True, vae_encoder: bool = True, control: bool = True) -> None:
         """Pull every tensor from `provider.get(name, shape, kind, fan_in)`
         (synthetic.SyntheticWeights) -- the counterpart of load_stable_diffusion
         (stablediffusion/load.rs:16-33) for seeded synthetic parameters.  `clip=False` leaves the
@@ -539,6 +628,8 @@ class StableDiffusion:
             if name.startswith("clip/") and not clip:
                 continue
             if (name.startswith("autoencoder/encoder/") or name.startswith("autoencoder/quant_conv/")) and not vae_encoder:
+                continue
+            if name.startswith("controlnet/") and not control:
                 continue
             if name == "alphas_cumprod":
                 from .synthetic import alphas_cumprod
@@ -1153,7 +1244,7 @@ def _make_cfg(lib, config: ModelConfig, device: int = 0) -> SdmiConfig:
     check(lib.sdmi_default_config(C.byref(cfg)))
     cfg.device = device
     for f in ("model_channels", "n_head", "ctx_dim", "latent_h", "latent_w", "vae_ch", "precision", "clip_layers", "clip_heads",
-              "clip_vocab", "clip_ctx", "unet_in_ch"):
+              "clip_vocab", "clip_ctx", "unet_in_ch", "control_hint_ch"):
         setattr(cfg, f, getattr(config, f))
     return cfg
 

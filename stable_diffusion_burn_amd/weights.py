@@ -123,6 +123,8 @@ def write_dump_tree(dump_dir, specs, get_tensor, alphas_cumprod, n_head: int = 8
         elif w.ndim == 4:
             k = w.shape[2]
             stride = 2 if parent.rsplit("/", 1)[1] in ("d1", "d2", "d3") else 1   # Downsample (unet/mod.rs:408-427)
+            if parent in ("controlnet/hint/c2", "controlnet/hint/c4", "controlnet/hint/c6"):
+                stride = 2                                                        # a ControlNet's input_hint_block halves the picture three times
             write_conv2d(root / parent, w, b, stride=stride, padding=1 if k == 3 else 0)
         elif w.ndim == 2:
             write_linear(root / parent, w, b)
@@ -225,3 +227,99 @@ def write_checkpoint_safetensors(path, specs, get_tensor, alphas_cumprod, dtype:
         tensors[key] = a if dtype == "F32" else a.astype(np.float16) if dtype == "F16" else (bf16_bits(a), "BF16")
     tensors.update(extra or {})
     write_safetensors(path, tensors)
+
+
+# ---- ControlNet: the weight group controlnet/... and its cldm-layout .safetensors file (DESIGN.md section 9g) ---------------------
+CONTROL_HINT_WIDTHS = (16, 16, 32, 32, 96, 96, 256)   # ControlNet's constants: they do not scale with model_channels
+
+
+def control_specs(dims, hint_ch: int = 3) -> list:
+    """[(dump name, shape)] of the ControlNet group of a model with `dims` (.model_channels, .ctx_dim), in the engine's order
+    (StableDiffusion.weight_specs() of a context with control_hint_ch = 3 lists the same entries): the time MLP, the 12 input
+    blocks and the middle block under the UNet's own names, the hint convolutions, the zero convolutions, middle_block_out."""
+    mc, cd = int(dims.model_channels), int(dims.ctx_dim)
+    ed, c1, c2, c4 = 4 * mc, mc, 2 * mc, 4 * mc
+    out = []
+
+    def conv(p, cin, cout, k):
+        out.extend([(p + "/weight", (cout, cin, k, k)), (p + "/bias", (cout,))])
+
+    def lin(p, cin, cout, bias=True):
+        out.append((p + "/weight", (cin, cout)))
+        if bias:
+            out.append((p + "/bias", (cout,)))
+
+    def norm(p, c):
+        out.extend([(p + "/weight", (c,)), (p + "/bias", (c,))])
+
+    def res(p, cin, cout):
+        norm(p + "/norm_in", cin)
+        conv(p + "/conv_in", cin, cout, 3)
+        lin(p + "/lin_embed", ed, cout)
+        norm(p + "/norm_out", cout)
+        conv(p + "/conv_out", cout, cout, 3)
+        if cin != cout:
+            conv(p + "/skip_connection", cin, cout, 1)
+
+    def mha(p, c, cctx):
+        lin(p + "/query", c, c, False)
+        lin(p + "/key", cctx, c, False)
+        lin(p + "/value", cctx, c, False)
+        lin(p + "/out", c, c)
+
+    def spatial(p, c):
+        norm(p + "/norm", c)
+        conv(p + "/proj_in", c, c, 1)
+        t = p + "/transformer"
+        norm(t + "/norm1", c)
+        mha(t + "/attn1", c, c)
+        norm(t + "/norm2", c)
+        mha(t + "/attn2", c, cd)
+        norm(t + "/norm3", c)
+        lin(t + "/mlp/geglu/proj", c, 8 * c)
+        lin(t + "/mlp/lin", 4 * c, c)
+        conv(p + "/proj_out", c, c, 1)
+
+    root = "controlnet"
+    lin(root + "/lin1_time_embed", mc, ed)
+    lin(root + "/lin2_time_embed", ed, ed)
+    blocks = [("conv", "conv", 4, c1), ("rt", "rt1", c1, c1), ("rt", "rt2", c1, c1), ("down", "d1", c1, c1), ("rt", "rt3", c1, c2), ("rt", "rt4", c2, c2),
+              ("down", "d2", c2, c2), ("rt", "rt5", c2, c4), ("rt", "rt6", c4, c4), ("down", "d3", c4, c4), ("r", "r1", c4, c4), ("r", "r2", c4, c4)]
+    for kind, name, cin, cout in blocks:
+        p = f"{root}/input_blocks/{name}"
+        if kind in ("conv", "down"):
+            conv(p, cin, cout, 3)
+        elif kind == "r":
+            res(p, cin, cout)
+        else:
+            res(p + "/res", cin, cout)
+            spatial(p + "/transformer", cout)
+    res(root + "/middle_block/res1", c4, c4)
+    spatial(root + "/middle_block/transformer", c4)
+    res(root + "/middle_block/res2", c4, c4)
+    widths = (int(hint_ch),) + CONTROL_HINT_WIDTHS + (mc,)
+    for i in range(8):
+        conv(f"{root}/hint/c{i}", widths[i], widths[i + 1], 3)
+    for j, (_, _, _, cout) in enumerate(blocks):
+        conv(f"{root}/zero_convs/{j}", cout, cout, 1)
+    conv(root + "/middle_block_out", c4, c4, 1)
+    return out
+
+
+def write_control_safetensors(path, provider_or_dict, dims, dtype: str = "F32", key_of=None, extra: dict | None = None) -> None:
+    """Write a ControlNet in the cldm layout ("control_model.…"): the inverse of sdmi_load_control_safetensors.
+
+    provider_or_dict: a provider (.get(name, shape, kind, fan_in), e.g. synthetic.SyntheticWeights) or {dump name: ndarray in the dump's
+    layout} holding every entry of control_specs(dims).  dtype "F32" | "F16" | "BF16".  key_of / extra: as write_checkpoint_safetensors."""
+    specs = control_specs(dims)
+    if hasattr(provider_or_dict, "get") and not isinstance(provider_or_dict, dict):
+        from .synthetic import named_tensor
+        shapes = dict(specs)
+        get = lambda name, shape: named_tensor(provider_or_dict, name, shape, shapes)   # noqa: E731
+    else:
+        def get(name, shape):
+            a = np.asarray(provider_or_dict[name], np.float32)
+            if tuple(a.shape) != tuple(shape):
+                raise ValueError(f"write_control_safetensors: '{name}' has shape {tuple(a.shape)}, expected {tuple(shape)}")
+            return a
+    write_checkpoint_safetensors(path, specs, get, None, dtype, key_of=key_of, extra=extra)
