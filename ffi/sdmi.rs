@@ -173,6 +173,18 @@ extern "C" {
     fn sdmi_tokenizer_destroy(tok: *mut c_void);
     fn sdmi_tokenizer_encode(tok: *const c_void, text: *const c_char, ids: *mut i32, capacity: i32, n_ids: *mut i32) -> c_int;
     fn sdmi_context(ctx: *mut c_void, tok: *const c_void, text: *const c_char, out: *mut c_float, capacity_tokens: i32, t: *mut i32) -> c_int;
+    // web-UI prompt encoding (include/sdmi.h).  opts: *const SdmiPromptOpts = [emphasis, clip_skip, min_chunks, 0, 0, 0, 0, 0] as [i32; 8], or null
+    fn sdmi_prompt_parse(text: *const c_char, out: *mut c_char, capacity: usize, needed: *mut usize) -> c_int;
+    fn sdmi_prompt_chunks(tok: *const c_void, text: *const c_char, clip_ctx: i32, emphasis: i32, min_chunks: i32, emb_names: *const *const c_char,
+                          emb_vectors: *const i32, n_emb: i32, ids: *mut i32, weights: *mut c_float, emb_row: *mut i32, capacity_chunks: i32, n_chunks: *mut i32) -> c_int;
+    fn sdmi_clip_forward_ex(ctx: *mut c_void, tokens: *const i32, emb_row: *const i32, weights: *const c_float, n: i32, seq_len: i32, clip_skip: i32,
+                            out: *mut c_float) -> c_int;
+    fn sdmi_embedding_add(ctx: *mut c_void, tok: *const c_void, name: *const c_char, vectors: *const c_float, n_vectors: i32) -> c_int;
+    fn sdmi_embedding_load_safetensors(ctx: *mut c_void, tok: *const c_void, name: *const c_char, path: *const c_char) -> c_int;
+    fn sdmi_embedding_remove(ctx: *mut c_void, name: *const c_char) -> c_int;
+    fn sdmi_embedding_list(ctx: *mut c_void, out: *mut c_char, capacity: usize, needed: *mut usize) -> c_int;
+    fn sdmi_encode_prompt(ctx: *mut c_void, tok: *const c_void, text: *const c_char, opts: *const [i32; 8], out: *mut c_float, capacity_tokens: i32,
+                          t: *mut i32) -> c_int;
     fn sdmi_write_png(path: *const c_char, rgb: *const u8, width: i32, height: i32) -> c_int;
     fn sdmi_qkv_attention(ctx: *mut c_void, q: *const c_float, k: *const c_float, v: *const c_float, mask: *const c_float,
                           mask_ld: i32, n: i32, nq: i32, nk: i32, n_state: i32, n_head: i32, out: *mut c_float) -> c_int;

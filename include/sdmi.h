@@ -484,6 +484,56 @@ int sdmi_clip_forward(sdmi_ctx* ctx, const int32_t* tokens, int32_t n, int32_t s
  * (:194-196) is context(""), T = 2. */
 int sdmi_context(sdmi_ctx* ctx, const sdmi_tokenizer* tok, const char* text, float* out, int32_t capacity_tokens, int32_t* T);
 
+/* ---- web-UI prompt encoding: padded chunks, emphasis, textual-inversion embeddings, CLIP skip (no reference counterpart) ----
+ * sdmi_context keeps the reference's rule (unpadded, at most clip_ctx tokens).  The calls below encode a prompt the way the SD v1 front-ends do: the text is
+ * parsed for emphasis, cut into chunks of clip_ctx - 2 content tokens, every chunk is "<|startoftext|>" + content + "<|endoftext|>" padded to clip_ctx, all
+ * chunks go through CLIP in one batch and their outputs follow one another: T = k * clip_ctx context rows, which every sampling call takes as they are.
+ *
+ * sdmi_prompt_parse (host only): the A1111 web UI's parse_prompt_attention.  "(" opens a x1.1 span, "[" a /1.1 span, ":<number>)" closes the innermost round
+ * span with that factor, "\(", "\)", "\[", "\]", "\\" are literal, a lone "\" is dropped, spans open at the end run to the end, "BREAK" as a word of its own
+ * outside every span gives the marker ("BREAK", -1), neighbours of equal weight are merged, weights are f64.  Writes one "weight<TAB>fragment" line per item
+ * ("%.17g"; backslash, tab, newline and control characters of the fragment as JSON escapes) by the convention of sdmi_mpk_list: *needed is always set to the
+ * bytes required, terminator included; out may be NULL with capacity 0.  SDMI_ERR_INVALID for a weight that is no complete number ("(y:.)"). */
+int sdmi_prompt_parse(const char* text, char* out, size_t capacity, size_t* needed);
+/* The chunks of a prompt (host only): ids, weights, emb_row [k, clip_ctx].  emphasis = 0: the text is one fragment of weight 1, brackets and BREAK are literal.
+ * Fragments are tokenised one by one and every token takes its fragment's weight; start, end and padding positions have weight 1 and emb_row -1.  A chunk that is
+ * full closes when the next token arrives; every BREAK marker closes the current chunk, an empty one too; after the last fragment the current chunk closes if it
+ * has content or no chunk exists; then empty chunks are appended until k >= min_chunks.  The n_emb embeddings (name, vectors) are matched on the token ids of
+ * their names, the longest name first: a match takes emb_vectors[i] content positions with ids = <|endoftext|>, emb_row = first_row(i) + j (rows numbered over
+ * the list in order) and the fragment's weight, and moves to a new chunk when it does not fit the current one.  *n_chunks is always set; SDMI_ERR_INVALID for a
+ * smaller capacity_chunks (nothing is written), clip_ctx < 3, an empty name, a name without tokens, emb_vectors[i] outside 1 .. clip_ctx - 2. */
+int sdmi_prompt_chunks(const sdmi_tokenizer* tok, const char* text, int32_t clip_ctx, int32_t emphasis, int32_t min_chunks, const char* const* emb_names,
+                       const int32_t* emb_vectors, int32_t n_emb, int32_t* ids, float* weights, int32_t* emb_row, int32_t capacity_chunks, int32_t* n_chunks);
+/* sdmi_clip_forward with three additions; tokens, emb_row (or NULL), weights (or NULL): host arrays [n, seq_len].
+ *   emb_row >= 0: that position's token vector is row emb_row of the context's embedding bank (sdmi_embedding_add) instead of the token table's row;
+ *   clip_skip = s, 1 <= s <= clip_layers: the first clip_layers - s + 1 blocks, then the final LayerNorm (the web UI's "CLIP skip"; 1 = sdmi_clip_forward);
+ *   weights: out[b][t][c] = (z[b][t][c] * w[b][t]) * r_b with r_b = (float)(sum z[b] / sum (z[b] * w[b])) over the seq_len x ctx_dim elements of chunk b --
+ *   products fp32, sums f64, r_b = 1 where the weighted sum is exactly 0.  One more launch, and only when some weight differs from 1.
+ * With no row >= 0, every weight 1 and clip_skip 1 the call issues the launches of sdmi_clip_forward and returns its bits.  SDMI_ERR_INVALID: a token id or a
+ * row out of range (rows: -1 .. bank rows - 1), clip_skip outside 1 .. clip_layers, seq_len > clip_ctx. */
+int sdmi_clip_forward_ex(sdmi_ctx* ctx, const int32_t* tokens, const int32_t* emb_row, const float* weights, int32_t n, int32_t seq_len, int32_t clip_skip,
+                         float* out);
+/* Textual-inversion embeddings of a context: vectors [n_vectors, ctx_dim] fp32 copied to the device bank, the name recorded with its token ids.  Rows are
+ * numbered over the embeddings in the order they were added.  SDMI_ERR_INVALID: an empty name, a name without tokens, n_vectors outside 1 .. clip_ctx - 2, a
+ * name the context already has.  SDMI_ERR_STATE: clip_layers = 0. */
+int sdmi_embedding_add(sdmi_ctx* ctx, const sdmi_tokenizer* tok, const char* name, const float* vectors, int32_t n_vectors);
+/* The same from a .safetensors file: the tensor "emb_params", or else the file's only tensor, of shape [ctx_dim] or [v, ctx_dim] in F32 / F16 / BF16, widened on
+ * the device.  Another last dimension is SDMI_ERR_INVALID; a malformed file is refused as a checkpoint is (SDMI_ERR_WEIGHTS / SDMI_ERR_IO). */
+int sdmi_embedding_load_safetensors(sdmi_ctx* ctx, const sdmi_tokenizer* tok, const char* name, const char* path);
+int sdmi_embedding_remove(sdmi_ctx* ctx, const char* name);   /* SDMI_ERR_INVALID: no such name.  Later embeddings move down in the bank. */
+/* one "name<TAB>n_vectors" line per embedding, in bank order (convention of sdmi_mpk_list) */
+int sdmi_embedding_list(sdmi_ctx* ctx, char* out, size_t capacity, size_t* needed);
+typedef struct sdmi_prompt_opts {
+    int32_t emphasis;      /* 1: parse brackets, weights and BREAK; 0: the text is literal                                  */
+    int32_t clip_skip;     /* 1 .. clip_layers                                                                              */
+    int32_t min_chunks;    /* empty chunks are appended up to this count (a negative prompt brought to the positive's length) */
+    int32_t reserved[5];   /* must be zero                                                                                  */
+} sdmi_prompt_opts;
+/* prompt -> context: sdmi_prompt_chunks with the context's embeddings, one batched sdmi_clip_forward_ex over the k chunks.  out holds capacity_tokens x ctx_dim
+ * floats and receives [k * clip_ctx, ctx_dim]; *T = k * clip_ctx is always set; SDMI_ERR_INVALID if it exceeds capacity_tokens.  opts NULL: {1, 1, 1}.
+ * SDMI_ERR_STATE without the CLIP weights, like sdmi_context. */
+int sdmi_encode_prompt(sdmi_ctx* ctx, const sdmi_tokenizer* tok, const char* text, const sdmi_prompt_opts* opts, float* out, int32_t capacity_tokens, int32_t* T);
+
 /* save_images (src/bin/sample/main.rs:118-125; image::save_buffer(.., Rgb8)): one 8-bit RGB image
  * [height, width, 3] -> PNG file.  Host code. */
 int sdmi_write_png(const char* path, const uint8_t* rgb, int32_t width, int32_t height);

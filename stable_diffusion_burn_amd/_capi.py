@@ -69,6 +69,11 @@ class SdmiHires(C.Structure):
                 ("strength", C.c_double), ("hires_seed", C.c_uint64), ("reserved", C.c_int64 * 4)]
 
 
+class SdmiPromptOpts(C.Structure):
+    """sdmi_prompt_opts: the options of sdmi_encode_prompt"""
+    _fields_ = [("emphasis", C.c_int32), ("clip_skip", C.c_int32), ("min_chunks", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
 _F = C.POINTER(C.c_float)
 _HIRES = C.POINTER(SdmiHires)
 _SAMPLER = C.POINTER(SdmiSampler)
@@ -149,6 +154,14 @@ SIGNATURES = {
     "sdmi_tokenizer_decode": (C.c_int, [_TOK, _I32, C.c_int32, C.c_char_p, C.c_int32, _I32]),
     "sdmi_clip_forward": (C.c_int, [_CTX, _I32, C.c_int32, C.c_int32, _F]),
     "sdmi_context": (C.c_int, [_CTX, _TOK, C.c_char_p, _F, C.c_int32, _I32]),
+    "sdmi_prompt_parse": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sdmi_prompt_chunks": (C.c_int, [_TOK, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), _I32, C.c_int32, _I32, _F, _I32, C.c_int32, _I32]),
+    "sdmi_clip_forward_ex": (C.c_int, [_CTX, _I32, _I32, _F, C.c_int32, C.c_int32, C.c_int32, _F]),
+    "sdmi_embedding_add": (C.c_int, [_CTX, _TOK, C.c_char_p, _F, C.c_int32]),
+    "sdmi_embedding_load_safetensors": (C.c_int, [_CTX, _TOK, C.c_char_p, C.c_char_p]),
+    "sdmi_embedding_remove": (C.c_int, [_CTX, C.c_char_p]),
+    "sdmi_embedding_list": (C.c_int, [_CTX, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sdmi_encode_prompt": (C.c_int, [_CTX, _TOK, C.c_char_p, C.POINTER(SdmiPromptOpts), _F, C.c_int32, _I32]),
     "sdmi_encode_image": (C.c_int, [_CTX, _F, C.c_int32, _F]),
     "sdmi_write_png": (C.c_int, [C.c_char_p, _U8, C.c_int32, C.c_int32]),
     "sdmi_sample_latent_dev": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_size_t, C.c_void_p, C.c_void_p]),

@@ -274,6 +274,8 @@ void Engine::destroy() noexcept {
         delete a;
     }
     loras_.clear();
+    if (emb_bank_) (void)hipFree(emb_bank_);
+    emb_bank_ = nullptr; emb_rows_ = 0; embeddings_.clear();
     if (ctrl_.hint_dev) (void)hipFree(ctrl_.hint_dev);   // a control still set: its hint pictures
     ctrl_ = Control{};
     for (void* p : weight_allocs_) (void)hipFree(p);
@@ -2628,19 +2630,27 @@ void Engine::unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bo
 
 // CLIP::forward (clip/mod.rs:56-75) with ResidualDecoderAttentionBlock (:110-114), MultiHeadSelfAttention
 // (:158-180), MLP + QuickGELU (:207-226) and attn_decoder_mask (backend.rs:130-139).  fp32 in both precisions.
-void Engine::clip_forward_dev(const int32_t* tokens, int n, int T, float* out) {
+void Engine::clip_forward_dev(const int32_t* tokens, int n, int T, float* out) { clip_forward_dev(tokens, nullptr, nullptr, n, T, 1, out); }
+
+void Engine::clip_forward_dev(const int32_t* tokens, const int32_t* emb_row, const float* weights, int n, int T, int clip_skip, float* out) {
     if (!finalized_) throw Error(SDMI_ERR_STATE, "weights not finalized");
     if (!clip_ready_) throw Error(SDMI_ERR_STATE, "CLIP weights are not loaded (clip/... tensors; clip_layers > 0 in the config)");
     if (n <= 0 || T <= 0) throw Error(SDMI_ERR_INVALID, "clip_forward: n and seq_len must be positive");
     if (T > cfg_.clip_ctx) throw Error(SDMI_ERR_INVALID, "clip_forward: sequence longer than n_ctx");  // reference: slice panics
+    if (clip_skip < 1 || clip_skip > cfg_.clip_layers)
+        throw Error(SDMI_ERR_INVALID, "clip_forward: clip_skip must be 1 .. clip_layers = " + std::to_string(cfg_.clip_layers) + ", got " + std::to_string(clip_skip));
+    if (emb_row && !emb_bank_) throw Error(SDMI_ERR_INVALID, "clip_forward: embedding rows given, but the context has no embeddings");
     const int C = cfg_.ctx_dim, H = cfg_.clip_heads;
     const long long M = (long long)n * T;
     Buf x(this, (size_t)M * C * 4), h(this, (size_t)M * C * 4), qkv(this, (size_t)M * 3 * C * 4), a(this, (size_t)M * C * 4);
     Buf f(this, (size_t)M * 4 * C * 4), mask(this, (size_t)T * T * 4);
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_clip_embed(tokens, clip_tok_, clip_pos_, x.f(), n, T, C, stream_)); }
+    if (emb_row) { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_clip_embed_bank(tokens, emb_row, clip_tok_, emb_bank_, clip_pos_, x.f(), n, T, C, stream_)); }
+    else { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_clip_embed(tokens, clip_tok_, clip_pos_, x.f(), n, T, C, stream_)); }
     { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_causal_mask(mask.f(), T, stream_)); }
     count_kernel(); count_kernel();
-    for (const ClipBlockW& b : clip_blocks_) {
+    const int n_blocks = cfg_.clip_layers - clip_skip + 1;   // the web UI's "CLIP skip s": hidden_states[-s] through the final LayerNorm
+    for (int bi = 0; bi < n_blocks; ++bi) {
+        const ClipBlockW& b = clip_blocks_[bi];
         layer_norm(b.attn_ln, x.f(), M, h.f(), 0);
         gemm(h.f(), (int)M, b.q.bt, b.q.bias, C, 3 * C, qkv.f(), 3 * C, nullptr, 0, 0);       // query | key | value, one GEMM
         attention(qkv.f(), 3 * C, (long long)T * 3 * C, qkv.f() + C, 3 * C, (long long)T * 3 * C, qkv.f() + 2 * C, 3 * C,
@@ -2653,6 +2663,87 @@ void Engine::clip_forward_dev(const int32_t* tokens, int n, int T, float* out) {
         gemm(f.f(), (int)M, b.fc2.bt, b.fc2.bias, 4 * C, C, x.f(), C, x.f(), C, 0);           // x += fc2(gelu(fc1))
     }
     layer_norm(clip_ln_, x.f(), M, out, 0);
+    if (weights) {
+        { ProfScope ps_o(this, PC_OTHER, 0, (double)M * C * 12.0); ps_o.set_tag("clip_reweight"); SDMI_HIP(launch_clip_reweight(out, weights, n, T, C, stream_)); }
+        count_kernel();
+    }
+}
+
+// ---- textual-inversion embeddings (include/sdmi.h "web-UI prompt encoding") ------------------------------------------------
+// The bank is one allocation of exactly the rows in use: adding or removing an embedding builds the new bank beside the old one and swaps.  These are
+// rare, blocking calls; no forward is in flight when they return.
+void Engine::embedding_add(const std::string& name, const std::vector<int32_t>& ids, const float* vectors, int n_vectors, bool on_device) {
+    if (cfg_.clip_layers <= 0) throw Error(SDMI_ERR_STATE, "embedding_add: this context has no text encoder (clip_layers = 0)");
+    if (name.empty() || name.find_first_of("\t\n") != std::string::npos) throw Error(SDMI_ERR_INVALID, "embedding_add: the name must not be empty or hold a tab or a newline");
+    if (ids.empty()) throw Error(SDMI_ERR_INVALID, "embedding_add: the tokenizer gives the name '" + name + "' no tokens");
+    if (!vectors) throw Error(SDMI_ERR_INVALID, "embedding_add: null vectors");
+    const int L = cfg_.clip_ctx - 2;
+    if (n_vectors < 1 || n_vectors > L)
+        throw Error(SDMI_ERR_INVALID, "embedding_add: '" + name + "' has " + std::to_string(n_vectors) + " vectors; 1 .. clip_ctx - 2 = " + std::to_string(L) + " fit a chunk");
+    for (const Embedding& e : embeddings_)
+        if (e.name == name) throw Error(SDMI_ERR_INVALID, "embedding_add: the context already has an embedding named '" + name + "'");
+    SDMI_HIP(hipSetDevice(cfg_.device));
+    const size_t row = (size_t)cfg_.ctx_dim * sizeof(float);
+    float* bank = nullptr;
+    SDMI_HIP(hipMalloc(reinterpret_cast<void**>(&bank), (size_t)(emb_rows_ + n_vectors) * row));
+    hipError_t st = hipSuccess;
+    if (emb_rows_) st = hipMemcpyAsync(bank, emb_bank_, (size_t)emb_rows_ * row, hipMemcpyDeviceToDevice, stream_);
+    if (st == hipSuccess)
+        st = hipMemcpyAsync(bank + (size_t)emb_rows_ * cfg_.ctx_dim, vectors, (size_t)n_vectors * row, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_);
+    if (st == hipSuccess) st = hipStreamSynchronize(stream_);
+    if (st != hipSuccess) { (void)hipFree(bank); SDMI_HIP(st); }
+    if (emb_bank_) (void)hipFree(emb_bank_);
+    emb_bank_ = bank;
+    emb_rows_ += n_vectors;
+    embeddings_.push_back(Embedding{name, ids, n_vectors});
+}
+
+void Engine::embedding_remove(const std::string& name) {
+    size_t at = 0;
+    int first = 0;
+    while (at < embeddings_.size() && embeddings_[at].name != name) first += embeddings_[at++].n_vectors;
+    if (at == embeddings_.size()) throw Error(SDMI_ERR_INVALID, "embedding_remove: the context has no embedding named '" + name + "'");
+    SDMI_HIP(hipSetDevice(cfg_.device));
+    SDMI_HIP(hipStreamSynchronize(stream_));
+    const int v = embeddings_[at].n_vectors, after = emb_rows_ - first - v;
+    const size_t row = (size_t)cfg_.ctx_dim * sizeof(float);
+    float* bank = nullptr;
+    if (emb_rows_ - v > 0) {
+        SDMI_HIP(hipMalloc(reinterpret_cast<void**>(&bank), (size_t)(emb_rows_ - v) * row));
+        hipError_t st = hipSuccess;
+        if (first) st = hipMemcpy(bank, emb_bank_, (size_t)first * row, hipMemcpyDeviceToDevice);
+        if (st == hipSuccess && after)
+            st = hipMemcpy(bank + (size_t)first * cfg_.ctx_dim, emb_bank_ + (size_t)(first + v) * cfg_.ctx_dim, (size_t)after * row, hipMemcpyDeviceToDevice);
+        if (st != hipSuccess) { (void)hipFree(bank); SDMI_HIP(st); }
+    }
+    (void)hipFree(emb_bank_);
+    emb_bank_ = bank;
+    emb_rows_ -= v;
+    embeddings_.erase(embeddings_.begin() + (long)at);
+}
+
+// A textual-inversion file: the tensor "emb_params" or else the file's only tensor, [C] or [v, C] in F32 / F16 / BF16, through the mapped reader and
+// k_unpack.hip's widening (the route checkpoints take).  Runs inside the caller's Call.
+void Engine::embedding_load_safetensors(const std::string& name, const std::vector<int32_t>& ids, const char* path) {
+    if (!path) throw Error(SDMI_ERR_INVALID, "embedding_load_safetensors: null path");
+    if (cfg_.clip_layers <= 0) throw Error(SDMI_ERR_STATE, "embedding_load_safetensors: this context has no text encoder (clip_layers = 0)");
+    SafetensorsFile f(path);
+    const StTensor* t = f.find("emb_params");
+    if (!t && f.tensors().size() == 1) t = &f.tensors()[0];
+    if (!t) throw Error(SDMI_ERR_WEIGHTS, std::string("embedding_load_safetensors: ") + path + " has no tensor 'emb_params' and " + std::to_string(f.tensors().size()) + " tensors to choose from");
+    const int dt = unpack_dtype(t->dtype);
+    if (dt < 0) throw Error(SDMI_ERR_UNSUPPORTED, "embedding_load_safetensors: '" + t->key + "' has dtype " + t->dtype + "; F32, F16 and BF16 are supported");
+    const size_t nd = t->shape.size();
+    if (nd < 1 || nd > 2 || t->shape[nd - 1] != cfg_.ctx_dim || t->count == 0)
+        throw Error(SDMI_ERR_INVALID, "embedding_load_safetensors: '" + t->key + "' has shape " + shape_str(t->shape.data(), nd) + ", expected [" +
+                                          std::to_string(cfg_.ctx_dim) + "] or [v, " + std::to_string(cfg_.ctx_dim) + "]");
+    const int64_t v = nd == 2 ? t->shape[0] : 1;
+    if (v > cfg_.clip_ctx - 2) throw Error(SDMI_ERR_INVALID, "embedding_load_safetensors: '" + t->key + "' has " + std::to_string(v) + " vectors; at most clip_ctx - 2 fit a chunk");
+    Buf raw(this, t->nbytes), wide(this, t->count * sizeof(float));
+    SDMI_HIP(hipMemcpyAsync(raw.p, t->data, t->nbytes, hipMemcpyHostToDevice, stream_));
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_unpack_tensor(raw.p, dt, 0, (long long)t->count, 1, wide.f(), stream_)); }
+    count_kernel();
+    embedding_add(name, ids, wide.f(), (int)v, true);   // synchronises: the mapping and the two buffers outlive the copies
 }
 
 // ---- conditioned UNet input (unet_in_ch > 4; include/sdmi.h "conditioned UNet") ---------------------------------------

@@ -179,6 +179,19 @@ public:
     void check_cond(const char* entry, bool given) const;
     // CLIP::forward (clip/mod.rs:56-75): int32 tokens [n, T] on the device -> [n, T, ctx_dim] fp32 (both precisions)
     void clip_forward_dev(const int32_t* tokens, int n, int T, float* out);
+    // The extended form (include/sdmi.h "web-UI prompt encoding"): emb_row [n, T] (null: none) takes rows of the embedding bank where
+    // >= 0, clip_skip = s runs the first clip_layers - s + 1 blocks before the final LayerNorm, weights [n, T] (null: none) re-weights every chunk in one
+    // more launch.  Device pointers; the caller has range-checked tokens and emb_row.  (null, null, 1) issues exactly the launches of the form above.
+    void clip_forward_dev(const int32_t* tokens, const int32_t* emb_row, const float* weights, int n, int T, int clip_skip, float* out);
+    // Textual-inversion embeddings: a device bank [rows, ctx_dim] fp32, rows numbered over the list in order.  ids = the tokenizer's encoding of the name.
+    struct Embedding { std::string name; std::vector<int32_t> ids; int n_vectors; };
+    const std::vector<Embedding>& embeddings() const { return embeddings_; }
+    int embedding_rows() const { return emb_rows_; }
+    // vectors [n_vectors, ctx_dim] fp32 on the host, or on the device (on_device; enqueued on stream_ by the caller).  SDMI_ERR_INVALID: an empty name, no
+    // ids, n_vectors outside 1 .. clip_ctx - 2, a name the context already has.  SDMI_ERR_STATE: a context without a text encoder (clip_layers = 0).
+    void embedding_add(const std::string& name, const std::vector<int32_t>& ids, const float* vectors, int n_vectors, bool on_device = false);
+    void embedding_load_safetensors(const std::string& name, const std::vector<int32_t>& ids, const char* path);
+    void embedding_remove(const std::string& name);
     bool clip_ready() const { return clip_ready_; }
     // ControlNet (include/sdmi.h "ControlNet").  control_ready: every tensor of weight group 3 is set (they may arrive before or after
     // finalize_weights, one by one or through a loader).  The control state is sticky, like the sampler: hint_dev is the caller's hint on the device.
@@ -595,6 +608,9 @@ private:
     std::vector<ClipBlockW> clip_blocks_;
     NormW clip_ln_;
     bool clip_ready_ = false;
+    std::vector<Embedding> embeddings_;
+    float* emb_bank_ = nullptr;   // [emb_rows_, ctx_dim], one allocation, rebuilt by embedding_add / embedding_remove
+    int emb_rows_ = 0;
     // VAE encoder (optional weight group)
     struct EncBlockW { ResW res[2]; ConvW down; bool has_down = false; int cin = 0, cout = 0; };
     ConvW enc_conv_in_, enc_conv_out_, quant_conv_;

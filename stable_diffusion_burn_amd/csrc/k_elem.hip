@@ -11,6 +11,8 @@
 //  * image post-processing to u8 (stablediffusion/mod.rs:79-99)
 // All are HBM/latency bound and tiny next to the convolutions; they use 16-byte
 // accesses and grid-stride loops.
+#include <climits>
+
 #include "kernels.hpp"
 #include "k_sample.hpp"
 #include "k_split3.hpp"
@@ -130,6 +132,59 @@ __global__ void clip_embed_kernel(const int* __restrict__ tokens, const float* _
         const float4 a = reinterpret_cast<const float4*>(tok_table + (long long)tokens[row] * C)[c4];
         const float4 b = reinterpret_cast<const float4*>(pos_table + (long long)t * C)[c4];
         reinterpret_cast<float4*>(out + row * C)[c4] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+    }
+}
+
+// The embedding of the extended CLIP forward: where emb_row[b, t] >= 0 the row comes from the context's bank of textual-inversion
+// vectors [rows, C] instead of the token table.  Same accesses and grid as clip_embed_kernel; the host has range-checked both index arrays.
+__global__ void clip_embed_bank_kernel(const int* __restrict__ tokens, const int* __restrict__ emb_row, const float* __restrict__ tok_table,
+                                       const float* __restrict__ bank, const float* __restrict__ pos_table, float* __restrict__ out, int n, int T, int C) {
+    const long long total = (long long)n * T * (C / 4);
+    GRID_STRIDE(i, total) {
+        const int c4 = (int)(i % (C / 4));
+        const long long row = i / (C / 4);
+        const int t = (int)(row % T);
+        const int er = emb_row[row];
+        const float* src = er >= 0 ? bank + (long long)er * C : tok_table + (long long)tokens[row] * C;
+        const float4 a = reinterpret_cast<const float4*>(src)[c4];
+        const float4 b = reinterpret_cast<const float4*>(pos_table + (long long)t * C)[c4];
+        reinterpret_cast<float4*>(out + row * C)[c4] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+    }
+}
+
+// Prompt emphasis: z [n][T][C] in place, w [n][T].  One workgroup per chunk b:
+//     z[b][t][c] = (z[b][t][c] * w[b][t]) * r_b,   r_b = (float)(sum z[b] / sum fl32(z[b] * w[b])),   r_b = 1 when the weighted sum is exactly 0,
+// the products in fp32, both sums in f64.  Every thread adds its elements in index order and the partial sums meet in a fixed LDS tree: no atomics, the
+// same bits on every run.  A chunk whose weights are all 1 has two equal sums, r_b exactly 1, and keeps its bits.
+constexpr int kReweightThreads = 1024;
+__global__ __launch_bounds__(kReweightThreads) void clip_reweight_kernel(float* __restrict__ z, const float* __restrict__ w, int T, int C4) {
+    __shared__ double s_z[kReweightThreads], s_zw[kReweightThreads];
+    const int total4 = T * C4;
+    float4* zc = reinterpret_cast<float4*>(z) + (long long)blockIdx.x * total4;
+    const float* wc = w + (long long)blockIdx.x * T;
+    double a = 0.0, b = 0.0;
+    for (int i = threadIdx.x; i < total4; i += kReweightThreads) {
+        const float4 v = zc[i];
+        const float wt = wc[i / C4];
+        a += (double)v.x; a += (double)v.y; a += (double)v.z; a += (double)v.w;
+        b += (double)__fmul_rn(v.x, wt); b += (double)__fmul_rn(v.y, wt); b += (double)__fmul_rn(v.z, wt); b += (double)__fmul_rn(v.w, wt);
+    }
+    s_z[threadIdx.x] = a;
+    s_zw[threadIdx.x] = b;
+    __syncthreads();
+    for (int half = kReweightThreads / 2; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) {
+            s_z[threadIdx.x] += s_z[threadIdx.x + half];
+            s_zw[threadIdx.x] += s_zw[threadIdx.x + half];
+        }
+        __syncthreads();
+    }
+    const float r = s_zw[0] == 0.0 ? 1.0f : (float)(s_z[0] / s_zw[0]);
+    for (int i = threadIdx.x; i < total4; i += kReweightThreads) {
+        const float4 v = zc[i];
+        const float wt = wc[i / C4];
+        zc[i] = make_float4(__fmul_rn(__fmul_rn(v.x, wt), r), __fmul_rn(__fmul_rn(v.y, wt), r), __fmul_rn(__fmul_rn(v.z, wt), r),
+                            __fmul_rn(__fmul_rn(v.w, wt), r));
     }
 }
 
@@ -284,6 +339,18 @@ hipError_t launch_clip_embed(const int* tokens, const float* tok_table, const fl
     if (C % 4) return hipErrorInvalidValue;
     hipLaunchKernelGGL(clip_embed_kernel, dim3(blocks_for((long long)n * T * (C / 4))), dim3(256), 0, s, tokens, tok_table, pos_table,
                        out, n, T, C);
+    return hipGetLastError();
+}
+hipError_t launch_clip_embed_bank(const int* tokens, const int* emb_row, const float* tok_table, const float* bank, const float* pos_table, float* out, int n,
+                                  int T, int C, hipStream_t s) {
+    if (C % 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(clip_embed_bank_kernel, dim3(blocks_for((long long)n * T * (C / 4))), dim3(256), 0, s, tokens, emb_row, tok_table, bank, pos_table,
+                       out, n, T, C);
+    return hipGetLastError();
+}
+hipError_t launch_clip_reweight(float* z, const float* w, int n, int T, int C, hipStream_t s) {
+    if (C % 4 || n < 1 || (long long)T * (C / 4) > INT_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(clip_reweight_kernel, dim3(n), dim3(kReweightThreads), 0, s, z, w, T, C / 4);
     return hipGetLastError();
 }
 hipError_t launch_causal_mask(float* mask, int T, hipStream_t s) {

@@ -207,6 +207,11 @@ hipError_t launch_quick_gelu(float* x, long long n, hipStream_t s);
 hipError_t launch_clip_embed(const int* tokens, const float* tok_table, const float* pos_table, float* out, int n, int T, int C,
                              hipStream_t s);
 hipError_t launch_causal_mask(float* mask, int T, hipStream_t s);
+// the extended CLIP forward: rows of the textual-inversion bank [rows, C] where emb_row >= 0; emphasis weights w [n][T] applied to
+// z [n][T][C] in place, one workgroup per chunk, each renormalised to its unweighted sum
+hipError_t launch_clip_embed_bank(const int* tokens, const int* emb_row, const float* tok_table, const float* bank, const float* pos_table, float* out, int n,
+                                  int T, int C, hipStream_t s);
+hipError_t launch_clip_reweight(float* z, const float* w, int n, int T, int C, hipStream_t s);
 // dst[c][r] = src[r*src_ld + c]
 hipError_t launch_transpose2d(const float* src, float* dst, int rows, int cols, int src_ld, hipStream_t s);
 // out[s][0:half] = cos(t_s * f_i), out[s][half:dim] = sin(t_s * f_i)  (unet/mod.rs:19-30)

@@ -13,6 +13,9 @@
 //   * the reference's noise is unseeded; here SDMI_SEED (default 0) seeds the device generator;
 //   * the merges file is $SDMI_BPE_VOCAB, default "bpe_simple_vocab_16e6.txt" in the working directory (tokenizer.rs:91);
 //   * SDMI_CONFIG="key=value,..." overrides model dimensions (tests use a small model).
+//   * SDMI_PROMPT_STYLE=webui (no reference counterpart; unset: everything as above) encodes the prompt and the negative prompt with sdmi_encode_prompt --
+//     chunks padded to clip_ctx tokens, emphasis, BREAK, no length limit.  In that mode only, SDMI_NEGATIVE_PROMPT (default "") replaces the empty prompt and
+//     SDMI_CLIP_SKIP (default 1) is passed on; the negative prompt is brought to the prompt's chunk count.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -103,8 +106,33 @@ int main(int argc, char** argv) {
     const int cd = cfg.ctx_dim, cap = cfg.clip_ctx;
     std::vector<float> uncond((size_t)cap * cd), context((size_t)cap * cd);
     int32_t Tu = 0, T = 0;
-    if (sdmi_context(ctx, tok, "", uncond.data(), cap, &Tu) != SDMI_OK) die("Error encoding the empty prompt");
-    if (sdmi_context(ctx, tok, prompt.c_str(), context.data(), cap, &T) != SDMI_OK) die("Error encoding the prompt");
+    const char* style = std::getenv("SDMI_PROMPT_STYLE");
+    if (style && std::strcmp(style, "webui") == 0) {
+        const char* negative = std::getenv("SDMI_NEGATIVE_PROMPT");
+        const char* skip = std::getenv("SDMI_CLIP_SKIP");
+        sdmi_prompt_opts opts;
+        std::memset(&opts, 0, sizeof opts);
+        opts.emphasis = 1;
+        opts.clip_skip = skip ? std::atoi(skip) : 1;
+        opts.min_chunks = 1;
+        if (sdmi_encode_prompt(ctx, tok, prompt.c_str(), &opts, context.data(), cap, &T) != SDMI_OK) {
+            if (T <= cap) die("Error encoding the prompt");
+            context.resize((size_t)T * cd);   // more than one chunk: *T says how many rows
+            if (sdmi_encode_prompt(ctx, tok, prompt.c_str(), &opts, context.data(), T, &T) != SDMI_OK) die("Error encoding the prompt");
+        }
+        opts.min_chunks = T / cap;
+        if (sdmi_encode_prompt(ctx, tok, negative ? negative : "", &opts, uncond.data(), cap, &Tu) != SDMI_OK) {
+            if (Tu <= cap) die("Error encoding the negative prompt");
+            uncond.resize((size_t)Tu * cd);
+            if (sdmi_encode_prompt(ctx, tok, negative ? negative : "", &opts, uncond.data(), Tu, &Tu) != SDMI_OK) die("Error encoding the negative prompt");
+        }
+    } else if (style && *style) {
+        std::fprintf(stderr, "SDMI_PROMPT_STYLE: unknown style %s (webui, or unset for the reference's rule)\n", style);
+        return 1;
+    } else {
+        if (sdmi_context(ctx, tok, "", uncond.data(), cap, &Tu) != SDMI_OK) die("Error encoding the empty prompt");
+        if (sdmi_context(ctx, tok, prompt.c_str(), context.data(), cap, &T) != SDMI_OK) die("Error encoding the prompt");
+    }
 
     std::printf("Sampling image...\n");
     const int H = 8 * cfg.latent_h, W = 8 * cfg.latent_w;

@@ -15,6 +15,7 @@
 #include "engine.hpp"
 #include "ckpt_keys.hpp"
 #include "mpk_reader.hpp"
+#include "prompt.hpp"
 #include "safetensors_reader.hpp"
 #include "tokenizer.hpp"
 
@@ -377,6 +378,133 @@ int sdmi_context(sdmi_ctx* ctx, const sdmi_tokenizer* tok, const char* text, flo
         *T = (int32_t)ids.size();
         if ((int64_t)ids.size() > capacity_tokens) throw Error(SDMI_ERR_INVALID, "context: capacity_tokens too small");
         clip_forward_host(e, ids.data(), 1, (int)ids.size(), out);
+    });
+}
+
+// ---- web-UI prompt encoding ---------------------------------------------------------------------------------------
+int sdmi_prompt_parse(const char* text, char* out, size_t capacity, size_t* needed) {
+    return guarded([&] {
+        if (!text || !needed) throw Error(SDMI_ERR_INVALID, "prompt_parse: null argument");
+        std::string s;
+        for (const sdmi::PromptFragment& f : sdmi::parse_prompt(text)) {
+            char w[40];
+            std::snprintf(w, sizeof w, "%.17g", f.weight);
+            s += std::string(w) + "\t" + listing_escape(f.text) + "\n";
+        }
+        text_out(s, out, capacity, needed, "prompt_parse");
+    });
+}
+
+static void chunks_out(const sdmi::PromptChunks& c, int clip_ctx, int32_t* ids, float* weights, int32_t* emb_row, int32_t capacity_chunks, int32_t* n_chunks) {
+    *n_chunks = c.k;
+    if (c.k > capacity_chunks) throw Error(SDMI_ERR_INVALID, "prompt_chunks: capacity_chunks too small");
+    if (!ids || !weights || !emb_row) throw Error(SDMI_ERR_INVALID, "prompt_chunks: null output");
+    const size_t n = (size_t)c.k * clip_ctx;
+    std::copy(c.ids.begin(), c.ids.begin() + n, ids);
+    std::copy(c.weights.begin(), c.weights.begin() + n, weights);
+    std::copy(c.emb_row.begin(), c.emb_row.begin() + n, emb_row);
+}
+
+int sdmi_prompt_chunks(const sdmi_tokenizer* tok, const char* text, int32_t clip_ctx, int32_t emphasis, int32_t min_chunks, const char* const* emb_names,
+                       const int32_t* emb_vectors, int32_t n_emb, int32_t* ids, float* weights, int32_t* emb_row, int32_t capacity_chunks, int32_t* n_chunks) {
+    return guarded([&] {
+        if (!tok || !text || !n_chunks) throw Error(SDMI_ERR_INVALID, "prompt_chunks: null argument");
+        if (n_emb < 0 || (n_emb > 0 && (!emb_names || !emb_vectors))) throw Error(SDMI_ERR_INVALID, "prompt_chunks: n_emb embeddings need their names and vector counts");
+        std::vector<sdmi::PromptEmbedding> embs;
+        for (int i = 0; i < n_emb; ++i) {
+            if (!emb_names[i] || !*emb_names[i]) throw Error(SDMI_ERR_INVALID, "prompt_chunks: an embedding's name is empty");
+            embs.push_back({tok->tok.encode(emb_names[i]), emb_vectors[i]});
+        }
+        const sdmi::PromptChunks c = sdmi::prompt_chunks(tok->tok, text, clip_ctx, emphasis != 0, min_chunks, embs);
+        chunks_out(c, clip_ctx, ids, weights, emb_row, capacity_chunks, n_chunks);
+    });
+}
+
+// tokens / emb_row / weights: host arrays [n, T].  The host decides what the device runs: rows only when some emb_row >= 0, the weighting launch only when
+// some weight differs from 1 -- a call without either and with clip_skip = 1 is sdmi_clip_forward, launch for launch.
+static void clip_forward_ex_host(Engine& e, const int32_t* tokens, const int32_t* emb_row, const float* weights, int n, int T, int clip_skip, float* out) {
+    if (!tokens || !out) throw Error(SDMI_ERR_INVALID, "clip_forward: null argument");
+    if (n <= 0 || T <= 0) throw Error(SDMI_ERR_INVALID, "clip_forward: n and seq_len must be positive");
+    const long long M = (long long)n * T;
+    const int vocab = e.config().clip_vocab, rows = e.embedding_rows();
+    bool any_row = false, any_weight = false;
+    for (long long i = 0; i < M; ++i) {
+        if (tokens[i] < 0 || tokens[i] >= vocab) throw Error(SDMI_ERR_INVALID, "clip_forward: token id outside the vocabulary");
+        if (emb_row) {
+            if (emb_row[i] < -1 || emb_row[i] >= rows)
+                throw Error(SDMI_ERR_INVALID, "clip_forward: embedding row " + std::to_string(emb_row[i]) + " outside the context's " + std::to_string(rows) + " rows");
+            any_row |= emb_row[i] >= 0;
+        }
+        if (weights) any_weight |= !(weights[i] == 1.0f);
+    }
+    Engine::Call call(e);
+    DevIn dt(e, tokens, (size_t)M * sizeof(int32_t));
+    std::unique_ptr<DevIn> dr, dw;
+    if (any_row) dr.reset(new DevIn(e, emb_row, (size_t)M * sizeof(int32_t)));
+    if (any_weight) dw.reset(new DevIn(e, weights, (size_t)M * sizeof(float)));
+    DevOut dout(e, out, (size_t)M * e.config().ctx_dim * sizeof(float));
+    e.clip_forward_dev(reinterpret_cast<const int32_t*>(dt.buf.p), dr ? reinterpret_cast<const int32_t*>(dr->buf.p) : nullptr, dw ? dw->f() : nullptr, n, T,
+                       clip_skip, dout.f());
+    call.finish();
+    dout.fetch();
+}
+
+int sdmi_clip_forward_ex(sdmi_ctx* ctx, const int32_t* tokens, const int32_t* emb_row, const float* weights, int32_t n, int32_t seq_len, int32_t clip_skip,
+                         float* out) {
+    return guarded([&] { clip_forward_ex_host(eng(ctx), tokens, emb_row, weights, n, seq_len, clip_skip, out); });
+}
+
+int sdmi_embedding_add(sdmi_ctx* ctx, const sdmi_tokenizer* tok, const char* name, const float* vectors, int32_t n_vectors) {
+    return guarded([&] {
+        if (!tok || !name) throw Error(SDMI_ERR_INVALID, "embedding_add: null argument");
+        eng(ctx).embedding_add(name, tok->tok.encode(name), vectors, n_vectors);
+    });
+}
+
+int sdmi_embedding_load_safetensors(sdmi_ctx* ctx, const sdmi_tokenizer* tok, const char* name, const char* path) {
+    return guarded([&] {
+        if (!tok || !name) throw Error(SDMI_ERR_INVALID, "embedding_load_safetensors: null argument");
+        Engine& e = eng(ctx);
+        Engine::Call call(e);
+        e.embedding_load_safetensors(name, tok->tok.encode(name), path);
+        call.finish();
+    });
+}
+
+int sdmi_embedding_remove(sdmi_ctx* ctx, const char* name) {
+    return guarded([&] {
+        if (!name) throw Error(SDMI_ERR_INVALID, "embedding_remove: null argument");
+        eng(ctx).embedding_remove(name);
+    });
+}
+
+int sdmi_embedding_list(sdmi_ctx* ctx, char* out, size_t capacity, size_t* needed) {
+    return guarded([&] {
+        if (!needed) throw Error(SDMI_ERR_INVALID, "embedding_list: null argument");
+        std::string s;
+        for (const Engine::Embedding& em : eng(ctx).embeddings()) s += listing_escape(em.name) + "\t" + std::to_string(em.n_vectors) + "\n";
+        text_out(s, out, capacity, needed, "embedding_list");
+    });
+}
+
+int sdmi_encode_prompt(sdmi_ctx* ctx, const sdmi_tokenizer* tok, const char* text, const sdmi_prompt_opts* opts, float* out, int32_t capacity_tokens, int32_t* T) {
+    return guarded([&] {
+        if (!tok || !text || !T) throw Error(SDMI_ERR_INVALID, "encode_prompt: null argument");
+        *T = 0;
+        Engine& e = eng(ctx);
+        sdmi_prompt_opts o{1, 1, 1, {0, 0, 0, 0, 0}};
+        if (opts) o = *opts;
+        for (int32_t r : o.reserved)
+            if (r) throw Error(SDMI_ERR_INVALID, "encode_prompt: sdmi_prompt_opts.reserved must be zero");
+        if (e.config().clip_layers <= 0 || !e.clip_ready()) throw Error(SDMI_ERR_STATE, "encode_prompt: CLIP weights are not loaded (clip/... tensors; clip_layers > 0 in the config)");
+        std::vector<sdmi::PromptEmbedding> embs;
+        for (const Engine::Embedding& em : e.embeddings()) embs.push_back({em.ids, em.n_vectors});
+        const int cc = e.config().clip_ctx;
+        const sdmi::PromptChunks c = sdmi::prompt_chunks(tok->tok, text, cc, o.emphasis != 0, o.min_chunks, embs);
+        if ((int64_t)c.k * cc > INT32_MAX) throw Error(SDMI_ERR_INVALID, "encode_prompt: too many chunks");
+        *T = c.k * cc;
+        if (*T > capacity_tokens) throw Error(SDMI_ERR_INVALID, "encode_prompt: capacity_tokens too small");
+        clip_forward_ex_host(e, c.ids.data(), c.emb_row.data(), c.weights.data(), c.k, cc, o.clip_skip, out);
     });
 }
 

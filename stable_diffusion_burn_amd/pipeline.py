@@ -24,7 +24,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _capi
-from ._capi import SdmiConfig, SdmiControl, SdmiError, SdmiHires, SdmiInpaint, SdmiOpView, SdmiSampler, check, load_library
+from ._capi import SdmiConfig, SdmiControl, SdmiError, SdmiHires, SdmiInpaint, SdmiOpView, SdmiPromptOpts, SdmiSampler, check, load_library
 
 def mpk_list(path) -> list:
     """[(dump name, shape, file offset)] of a Burn .mpk record, parsed by the C++ reader (host only, no GPU)."""
@@ -60,6 +60,21 @@ def safetensors_list(path) -> list:
         key, dtype, shape, off, name = line.rsplit("\t", 4)
         key = re.sub(r"\\(u[0-9a-f]{4}|.)", lambda m: {"t": "\t", "n": "\n"}.get(m.group(1), chr(int(m.group(1)[1:], 16)) if len(m.group(1)) == 5 else m.group(1)), key)
         out.append((key, dtype, tuple(int(v) for v in shape.split(",")) if shape else (), int(off), None if name == "-" else name))
+    return out
+
+
+def _listing_unescape(field: str) -> str:
+    """a field of a tab-separated listing line: the JSON escapes of backslash and control characters undone"""
+    return re.sub(r"\\(u[0-9a-f]{4}|.)", lambda m: {"t": "\t", "n": "\n"}.get(m.group(1), chr(int(m.group(1)[1:], 16)) if len(m.group(1)) == 5 else m.group(1)), field)
+
+
+def parse_prompt(text: str) -> list:
+    """[(fragment, weight)] of a prompt with the web UI's emphasis syntax -- "(a)", "[a]", "(a:1.3)", backslash escapes, BREAK -- parsed by the C++
+    parser (sdmi_prompt_parse, host only, no GPU).  A BREAK marker is ("BREAK", -1).  SdmiError for a weight that is no number."""
+    out = []
+    for line in _text_query(load_library().sdmi_prompt_parse, text.encode("utf-8")).split("\n")[:-1]:
+        w, frag = line.split("\t", 1)
+        out.append((_listing_unescape(frag), float(w)))
     return out
 
 
@@ -652,6 +667,46 @@ class StableDiffusion:
     def unconditional_context(self, tokenizer: "SimpleTokenizer") -> np.ndarray:
         """StableDiffusion::unconditional_context (:194-196): context("") squeezed to [2, ctx_dim]."""
         return self.context(tokenizer, "")[0]
+
+    # ---- web-UI prompt encoding (no reference counterpart; DESIGN.md section 9h) ----
+    def encode_prompt(self, tokenizer: "SimpleTokenizer", text: str, emphasis: bool = True, clip_skip: int = 1, min_chunks: int = 1) -> np.ndarray:
+        """The prompt as the SD v1 front-ends encode it: [1, k * clip_ctx, ctx_dim] -- k chunks padded to clip_ctx tokens, with emphasis weights, the
+        context's textual-inversion embeddings and CLIP skip applied.  encode_prompt(...)[0] is a valid unconditional_context."""
+        opts = SdmiPromptOpts(int(bool(emphasis)), int(clip_skip), int(min_chunks))
+        T = C.c_int32()
+        cap = self.config.clip_ctx * max(1, int(min_chunks), len(text.encode("utf-8")) // 8 + 2)
+        while True:
+            out = np.empty((cap, self.config.ctx_dim), dtype=np.float32)
+            st = self._lib.sdmi_encode_prompt(self._ctx, tokenizer._tok, text.encode("utf-8"), C.byref(opts), _fp(out), cap, C.byref(T))
+            if st != 0 and T.value > cap:   # *T is always set: the one retry has the room
+                cap = T.value
+                continue
+            check(st)
+            return out[None, :T.value].copy()
+
+    def add_embedding(self, tokenizer: "SimpleTokenizer", name: str, vectors) -> None:
+        """A textual-inversion embedding: vectors [v, ctx_dim] (or [ctx_dim]) that stand for `name` wherever encode_prompt meets its tokens."""
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        if v.ndim == 1:
+            v = v[None]
+        if v.ndim != 2 or v.shape[1] != self.config.ctx_dim:
+            raise ValueError(f"vectors must be [v, {self.config.ctx_dim}], got {v.shape}")
+        check(self._lib.sdmi_embedding_add(self._ctx, tokenizer._tok, name.encode("utf-8"), _fp(v), v.shape[0]))
+
+    def load_embedding(self, tokenizer: "SimpleTokenizer", name: str, path) -> None:
+        """add_embedding from a .safetensors file (tensor "emb_params" or the only tensor; F32 / F16 / BF16), converted on the device"""
+        check(self._lib.sdmi_embedding_load_safetensors(self._ctx, tokenizer._tok, name.encode("utf-8"), str(path).encode()))
+
+    def remove_embedding(self, name: str) -> None:
+        check(self._lib.sdmi_embedding_remove(self._ctx, name.encode("utf-8")))
+
+    def embeddings(self) -> list:
+        """[(name, n_vectors)] in bank order"""
+        out = []
+        for line in _text_query(self._lib.sdmi_embedding_list, self._ctx).split("\n")[:-1]:
+            name, v = line.rsplit("\t", 1)
+            out.append((_listing_unescape(name), int(v)))
+        return out
 
     def load_weights_dir(self, dump_dir: str) -> None:
         """npy-dump tree written by the reference's python/ exporters
@@ -1391,13 +1446,23 @@ class CLIP:
     def __init__(self, sd: StableDiffusion):
         self._sd = sd
 
-    def forward(self, tokens) -> np.ndarray:
+    def forward(self, tokens, emb_row=None, weights=None, clip_skip: int = 1) -> np.ndarray:
+        """emb_row / weights [n, T] and clip_skip: the extended forward of the web-UI prompt encoding (sdmi_clip_forward_ex)"""
         sd = self._sd
         t = np.ascontiguousarray(tokens, dtype=np.int32)
         if t.ndim != 2:
             raise ValueError(f"tokens must be [n, seq_len], got {t.shape}")
         out = np.empty(t.shape + (sd.config.ctx_dim,), dtype=np.float32)
-        check(sd._lib.sdmi_clip_forward(sd._ctx, t.ctypes.data_as(C.POINTER(C.c_int32)), t.shape[0], t.shape[1], _fp(out)))
+        if emb_row is None and weights is None and clip_skip == 1:
+            check(sd._lib.sdmi_clip_forward(sd._ctx, t.ctypes.data_as(C.POINTER(C.c_int32)), t.shape[0], t.shape[1], _fp(out)))
+            return out
+        r = None if emb_row is None else np.ascontiguousarray(emb_row, dtype=np.int32)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
+        for a, what in ((r, "emb_row"), (w, "weights")):
+            if a is not None and a.shape != t.shape:
+                raise ValueError(f"{what} must have the shape of tokens {t.shape}, got {a.shape}")
+        check(sd._lib.sdmi_clip_forward_ex(sd._ctx, t.ctypes.data_as(C.POINTER(C.c_int32)), None if r is None else r.ctypes.data_as(C.POINTER(C.c_int32)),
+                                           None if w is None else _fp(w), t.shape[0], t.shape[1], int(clip_skip), _fp(out)))
         return out
 
 
@@ -1433,6 +1498,26 @@ class SimpleTokenizer:
         ids = (C.c_int32 * cap)()
         check(self._lib.sdmi_tokenizer_encode(self._tok, data, ids, cap, C.byref(n)))
         return [int(ids[i]) for i in range(n.value)]
+
+    def prompt_chunks(self, text: str, clip_ctx: int, emphasis: bool = True, min_chunks: int = 1, embeddings=()):
+        """(ids, weights, emb_row), each [k, clip_ctx]: the padded chunks of a prompt (sdmi_prompt_chunks, host only).
+        embeddings: [(name, n_vectors)]; emb_row numbers their vectors over the list in order, -1 elsewhere."""
+        embeddings = list(embeddings)
+        names = (C.c_char_p * max(1, len(embeddings)))(*[n.encode("utf-8") for n, _ in embeddings])
+        counts = (C.c_int32 * max(1, len(embeddings)))(*[int(v) for _, v in embeddings])
+        data = text.encode("utf-8")
+        k, cap = C.c_int32(), max(1, int(min_chunks))
+        while True:
+            ids = np.empty((cap, clip_ctx), np.int32)
+            w = np.empty((cap, clip_ctx), np.float32)
+            rows = np.empty((cap, clip_ctx), np.int32)
+            st = self._lib.sdmi_prompt_chunks(self._tok, data, int(clip_ctx), int(bool(emphasis)), int(min_chunks), names, counts, len(embeddings),
+                                              ids.ctypes.data_as(C.POINTER(C.c_int32)), _fp(w), rows.ctypes.data_as(C.POINTER(C.c_int32)), cap, C.byref(k))
+            if st != 0 and k.value > cap:   # *n_chunks is always set: the one retry has the room
+                cap = k.value
+                continue
+            check(st)
+            return ids[:k.value].copy(), w[:k.value].copy(), rows[:k.value].copy()
 
     def decode(self, tokens) -> str:
         t = np.ascontiguousarray(tokens, dtype=np.int32)
