@@ -447,7 +447,16 @@ int sdmi_lora_effective_weight(sdmi_ctx* ctx, const char* name, float* out, size
 /* qkv_attention (src/model/attention.rs:5-45 == src/backend.rs:88-128; the
  * operator seam of the commented-out `trait Backend`, backend.rs:4-84).
  * q [n,nq,n_state], k,v [n,nk,n_state], mask [>=nq, mask_ld>=nk] additive or
- * NULL -> out [n,nq,n_state]. */
+ * NULL -> out [n,nq,n_state].
+ * The mask is added to the scaled scores before the softmax, in natural-log units
+ * (softmax(q k^T s^2 + mask)), and is shared by every sample and head: row r of the
+ * mask, mask[r * mask_ld .. + nk), serves query r of all of them.  nq rows of mask_ld
+ * floats are read, so the array must cover at least nq rows (the library cannot see
+ * where it ends); mask_ld < nk is SDMI_ERR_INVALID, a mask on a head dim without a
+ * fused kernel (not 40 / 64 / 80 / 160) SDMI_ERR_UNSUPPORTED.  -inf entries are
+ * allowed; a row without a live key yields NaN, as the reference's softmax does.
+ * A masked call runs the fp32 kernel at every precision
+ * (tests/test_attention_mask_gpu.py). */
 int sdmi_qkv_attention(sdmi_ctx* ctx, const float* q, const float* k, const float* v,
                        const float* mask, int32_t mask_ld, int32_t n, int32_t nq, int32_t nk,
                        int32_t n_state, int32_t n_head, float* out);

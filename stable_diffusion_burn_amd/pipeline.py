@@ -1263,7 +1263,12 @@ class StableDiffusion:
         return out
 
     def qkv_attention(self, q, k, v, mask, n_head: int):
-        """attention.rs:5-45: q [n,nq,c], k,v [n,nk,c], mask [>=nq, >=nk] or None."""
+        """attention.rs:5-45: q [n,nq,c], k,v [n,nk,c], mask [>=nq, >=nk] or None.
+
+        The mask is additive, in natural-log units (added to the scores before the softmax), and shared by every sample and head; its row
+        stride goes down as mask_ld, so an over-sized mask is passed as it is.  -inf is allowed; a row without a live key comes back NaN,
+        as in the reference.  The library reads nq rows of mask_ld floats and cannot see where the array ends, so a mask that is not
+        two-dimensional or has fewer than nq rows is refused here (SdmiError, SDMI_ERR_INVALID); one narrower than nk is refused by the library."""
         q, k, v = _f32(q), _f32(k), _f32(v)
         n, nq, c = q.shape
         nk = k.shape[1]
@@ -1271,6 +1276,8 @@ class StableDiffusion:
             raise ValueError("qkv_attention: q/k/v shapes disagree")
         out = np.empty_like(q)
         m = None if mask is None else _f32(mask)
+        if m is not None and (m.ndim != 2 or m.shape[0] < nq):
+            raise SdmiError(-1, f"qkv_attention: mask must be [>= nq = {nq}, >= nk = {nk}], got {m.shape}")
         check(self._lib.sdmi_qkv_attention(self._ctx, _fp(q), _fp(k), _fp(v), None if m is None else _fp(m),
                                            0 if m is None else m.shape[1], n, nq, nk, c, n_head, _fp(out)))
         return out

@@ -3,6 +3,10 @@
 //
 //   attn_plan <fixture>      exit 0 when every line is reproduced, 1 with the first differing lines otherwise
 //   attn_plan                prints the lines (how the fixture was written -- by the code BEFORE the planner was restructured)
+//   attn_plan --replay <f>   plans the cases a fixture NAMES: every line of <f> that is no comment is parsed back into its case
+//                            ("f32|bf16 [mask] [planes] [unaligned] d<D> n<N> h<H> q<NQ> k<NK>:", the words setting has_mask, planes_out and
+//                            !rows_aligned), planned under every option variant and compared with the line.  No grid, no form census:
+//                            tests/golden/attn_plan_masked_cases.txt, the shapes of tests/test_attention_mask_gpu.py
 //
 // One line per (storage, d, n, heads, nq, nk), one token per option variant in the order of variants() below; equal neighbours are
 // folded into "token*count".  A token is
@@ -106,7 +110,41 @@ static void line(std::ostream& os, const AttnPlanIn& in, const char* note = "") 
     os << "\n";
 }
 
+// --replay: the fixture names its cases, see the head of this file
+static int replay(const char* path) {
+    std::ifstream f(path);
+    if (!f) { std::fprintf(stderr, "cannot read %s\n", path); return 2; }
+    std::string a;
+    int ln = 0, cases = 0, bad = 0;
+    while (std::getline(f, a)) {
+        ++ln;
+        if (a.empty() || a[0] == '#') continue;
+        std::istringstream hs(a.substr(0, a.find(':')));
+        std::string w, note;
+        bool bf16 = false, mask = false, planes = false, aligned = true, ok = (bool)(hs >> w) && (w == "f32" || w == "bf16") && a.find(':') != std::string::npos;
+        bf16 = w == "bf16";
+        int val[5] = {0, 0, 0, 0, 0}, seen = 0;   // d n h q k, in this order
+        while (ok && hs >> w) {
+            if (w == "mask") mask = true;
+            else if (w == "planes") planes = true;
+            else if (w == "unaligned") aligned = false;
+            else if (seen < 5 && w.size() > 1 && w[0] == "dnhqk"[seen] && w.find_first_not_of("0123456789", 1) == std::string::npos && w.size() < 9) { val[seen++] = std::atoi(w.c_str() + 1); continue; }
+            else ok = false;
+            if (seen) ok = false;   // the words come before the numbers
+            note += " " + w;
+        }
+        if (!ok || seen != 5) { std::fprintf(stderr, "line %d is no case: %s\n", ln, a.c_str()); return 2; }
+        std::ostringstream os;
+        line(os, make_in(bf16, val[0], val[1], val[2], val[3], val[4], mask, planes, aligned), note.c_str());
+        ++cases;
+        if (os.str() != a + "\n" && ++bad <= 5) std::fprintf(stderr, "line %d differs:\n  fixture: %s\n  planner: %s", ln, a.c_str(), os.str().c_str());
+    }
+    std::printf("%d cases, %d differ\n", cases, bad);
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc == 3 && std::string(argv[1]) == "--replay") return replay(argv[2]);
     std::ostringstream os;
     os << "# written by the planner's first form, Engine::attention's and the launchers' rules moved out verbatim; never regenerated since\n";
     for (int bf16 = 0; bf16 < 2; ++bf16) {
