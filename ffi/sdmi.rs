@@ -165,6 +165,11 @@ extern "C" {
                           coefs: *mut c_double) -> c_int;
     fn sdmi_lora_create(ctx: *mut c_void, out: *mut *mut c_void) -> c_int;
     fn sdmi_lora_add(a: *mut c_void, target: *const c_char, down: *const c_float, up: *const c_float, rank: i32, alpha: c_float) -> c_int;
+    fn sdmi_lora_load_safetensors(ctx: *mut c_void, path: *const c_char, which: i32, flags: i32, out: *mut *mut c_void, n_targets: *mut i32, n_skipped: *mut i32) -> c_int;
+    fn sdmi_lora_factor_bytes(a: *mut c_void, bytes: *mut usize) -> c_int;
+    fn sdmi_lora_module_name(dump_name: *const c_char, buf: *mut c_char, n: usize) -> c_int;
+    fn sdmi_lora_check_safetensors(path: *const c_char, names: *const *const c_char, ndims: *const i32, dims: *const i64, n_entries: i32, which: i32, flags: i32,
+                                   n_targets: *mut i32, n_skipped: *mut i32) -> c_int;
     fn sdmi_lora_set_scale(a: *mut c_void, scale: c_double) -> c_int;
     fn sdmi_lora_get_scale(a: *mut c_void, scale: *mut c_double, n_targets: *mut i32) -> c_int;
     fn sdmi_lora_destroy(a: *mut c_void) -> c_int;
@@ -232,6 +237,10 @@ impl Drop for TokenizerMi355 {
     }
 }
 
+pub const LORA_UNET: i32 = 1;
+pub const LORA_TE: i32 = 2;
+pub const LORA_SKIP_UNKNOWN: i32 = 1;
+
 /// One attached LoRA adapter (`sdmi_lora`).  It borrows its context, so it cannot outlive it; dropping it detaches it (`sdmi_lora_destroy` = scale 0 + free).
 pub struct LoraMi355<'a> {
     a: *mut c_void,
@@ -242,6 +251,12 @@ impl<'a> LoraMi355<'a> {
     /// Re-merges and re-packs every target of the adapter (`sdmi_lora_set_scale`); blocks until done.
     pub fn set_scale(&self, scale: f64) -> Result<(), Box<dyn Error>> {
         if unsafe { sdmi_lora_set_scale(self.a, scale) } != 0 { Err(last_error().into()) } else { Ok(()) }
+    }
+
+    /// Device bytes held by the raw factors of a file-loaded adapter (`sdmi_lora_factor_bytes`).
+    pub fn factor_bytes(&self) -> Result<usize, Box<dyn Error>> {
+        let mut b = 0usize;
+        if unsafe { sdmi_lora_factor_bytes(self.a, &mut b) } != 0 { Err(last_error().into()) } else { Ok(b) }
     }
 
     /// (scale, number of targets) (`sdmi_lora_get_scale`).
@@ -407,6 +422,30 @@ impl StableDiffusionMi355 {
         }
         lora.set_scale(scale)?;
         Ok(lora)
+    }
+
+    /// A kohya-ss / LyCORIS `.safetensors` adapter (`sdmi_lora_load_safetensors`) merged at `scale`: `which` = `LORA_UNET`, `LORA_TE` or both,
+    /// `flags` = 0 or `LORA_SKIP_UNKNOWN`.  Returns the adapter and the number of modules passed over.
+    pub fn lora_load_safetensors(&self, path: &str, which: i32, flags: i32, scale: f64) -> Result<(LoraMi355<'_>, i32), Box<dyn Error>> {
+        let p = CString::new(path)?;
+        let mut a: *mut c_void = std::ptr::null_mut();
+        let (mut n, mut skipped) = (0i32, 0i32);
+        if unsafe { sdmi_lora_load_safetensors(self.ctx, p.as_ptr(), which, flags, &mut a, &mut n, &mut skipped) } != 0 {
+            return Err(last_error().into());
+        }
+        let lora = LoraMi355 { a, _ctx: std::marker::PhantomData };
+        lora.set_scale(scale)?;
+        Ok((lora, skipped))
+    }
+
+    /// The kohya module name of a conv / Linear weight of the UNet or the text encoder (`sdmi_lora_module_name`, host only).
+    pub fn lora_module_name(dump_name: &str) -> Result<String, Box<dyn Error>> {
+        let c = CString::new(dump_name)?;
+        let mut buf = vec![0 as c_char; 256];
+        if unsafe { sdmi_lora_module_name(c.as_ptr(), buf.as_mut_ptr(), buf.len()) } != 0 {
+            return Err(last_error().into());
+        }
+        Ok(unsafe { CStr::from_ptr(buf.as_ptr()) }.to_string_lossy().into_owned())
     }
 
     /// The fp32 tensor (reference layout, `n` elements) currently packed for a conv / Linear weight (`sdmi_lora_effective_weight`).

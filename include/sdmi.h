@@ -425,7 +425,8 @@ int sdmi_inpaint_image_dev(sdmi_ctx* ctx, const float* context, int32_t n, int32
  * otherwise holds W0 already rounded to bf16 / MXFP8, to which no delta can be added exactly.  A merge is not part of sampling: no launch of a
  * sampling call changes, and a tensor without an active adapter is re-packed from W0 itself (scale 0 restores the loaded model bit for bit).
  * Factor shapes: Linear [in,out]: down [rank,in], up [out,rank].  Conv [cout,cin,k,k]: down [rank,cin,k,k], up [cout,rank].
- * Adapters belong to one context (with sdmi_multi: attach to every sdmi_multi_ctx); several may share a target, their deltas add. */
+ * Adapters belong to one context (with sdmi_multi: attach to every sdmi_multi_ctx); several may share a target, their deltas add.
+ * An adapter is built target by target from fp32 factors (sdmi_lora_add) or read from a kohya-ss / LyCORIS .safetensors file (sdmi_lora_load_safetensors). */
 typedef struct sdmi_lora sdmi_lora;      /* owned by its context; freed by sdmi_lora_destroy or sdmi_destroy */
 /* A new adapter with no targets at scale 0.  SDMI_ERR_STATE unless the weights are finalized and "keep_masters=1" was set before they were loaded. */
 int sdmi_lora_create(sdmi_ctx* ctx, sdmi_lora** out);
@@ -434,6 +435,39 @@ int sdmi_lora_create(sdmi_ctx* ctx, sdmi_lora** out);
  * to get right: the pointers carry none).  SDMI_ERR_UNSUPPORTED: a conv_in packed with padded input channels -- the 3-channel RGB one of the VAE encoder, the
  * 9-channel one of an inpainting UNet (an 8-channel one is stored as it is: an ordinary target). */
 int sdmi_lora_add(sdmi_lora* a, const char* target, const float* down, const float* up, int32_t rank, float alpha);
+/* A kohya-ss / LyCORIS LoRA file (.safetensors), the format adapters are distributed in (DESIGN.md section 9c "files"): a new adapter at scale 0 with one target per
+ * module of the file.  Modules are named after the *diffusers* module path -- "lora_unet_down_blocks_0_attentions_0_transformer_blocks_0_attn1_to_q",
+ * "lora_te_text_model_encoder_layers_11_mlp_fc2" -- or, by some tools, after the CompVis key ("lora_unet_input_blocks_1_1_proj_in"); both are looked up in a table
+ * made from this model's conv / Linear entries (sdmi_lora_module_name; tests/golden/kohya_lora_keys.txt).  Keys of a module X:
+ *   X.lora_down.weight [r, in] / [r, cin, k, k], X.lora_up.weight [out, r] / [out, r, 1, 1]                     LoRA, LoCon
+ *   X.hada_w1_a, X.hada_w2_a [out, r]; X.hada_w1_b, X.hada_w2_b [r, in] / [r, cin k k] / [r, cin, k, k]         LoHa: delta = (w1_a . w1_b) o (w2_a . w2_b)
+ *   X.alpha                    one number of any float dtype; absent: alpha = r                                  c = (float)(s alpha / r), as above
+ * in F32, F16 or BF16.  The RAW bytes of each factor go to the device as the file holds them -- one allocation per target, no host widening, no transposed copy:
+ * half the memory of sdmi_lora_add's fp32 copies for an F16 file -- and the merge kernel widens them exactly while it reads, so the result is, bit for bit, what
+ * sdmi_lora_add of the host-widened factors gives.  A LoHa product is d1 = sum_j w1_a w1_b, d2 = sum_j w2_a w2_b (each an fp32 FMA chain), d1 * d2 rounded once.
+ * `which`: SDMI_LORA_UNET, SDMI_LORA_TE or both; modules of the other half are passed over (two adapters from one file carry the two scales of "<lora:name:unet:te>").
+ * The whole file is checked against the entries' dims before anything is uploaded, and a refused file leaves the context as it was:
+ *   SDMI_ERR_UNSUPPORTED  (the first offending key is named) a Tucker core (lora_mid, hada_t1 / hada_t2), lokr_*, dora_scale, diff / diff_b or any other key kind; a dtype
+ *                         other than the three; a rank above 256; a padded conv_in (sdmi_lora_add); a module no entry of THIS model answers to -- a text-encoder layer
+ *                         beyond clip_layers, an SDXL name -- unless flags has SDMI_LORA_SKIP_UNKNOWN, which passes such modules (and modules of a weight group that is
+ *                         not loaded) over and counts them in *n_skipped;
+ *   SDMI_ERR_WEIGHTS      a factor whose shape does not fit the entry, a module with half its factors, a non-finite alpha, a malformed file;
+ *   SDMI_ERR_IO           an unreadable file;  SDMI_ERR_STATE  as sdmi_lora_create, and a target whose weight group is not loaded (without the skip flag).
+ * The call selects the context's device itself (hipSetDevice), like sdmi_lora_add and sdmi_lora_set_scale: with an sdmi_multi it may be made for one sdmi_multi_ctx after
+ * the other from one thread.  n_targets / n_skipped may be NULL.  Not read: Tucker, LoKr, DoRA, the PEFT lora_A / lora_B spelling, SDXL / SD 2 names, pickle files. */
+#define SDMI_LORA_UNET 1
+#define SDMI_LORA_TE 2
+#define SDMI_LORA_SKIP_UNKNOWN 1
+int sdmi_lora_load_safetensors(sdmi_ctx* ctx, const char* path, int32_t which, int32_t flags, sdmi_lora** out, int32_t* n_targets, int32_t* n_skipped);
+/* device bytes held by the raw factors of a file-loaded adapter (0 for one built with sdmi_lora_add) */
+int sdmi_lora_factor_bytes(sdmi_lora* a, size_t* bytes);
+/* Host only: the kohya module name of the conv / Linear weight `dump_name` ("unet/.../weight", "clip/.../weight") into buf[n], terminator included.
+ * SDMI_ERR_INVALID: any other name (a bias, a norm, an embedding, the VAE, a ControlNet), or n too small. */
+int sdmi_lora_module_name(const char* dump_name, char* buf, size_t n);
+/* Host only, no context: the checks of sdmi_lora_load_safetensors that need no device, against a caller's list of entries -- names[i] a dump name with ndims[i]
+ * (4: conv, 2: Linear) dims at dims[4 i ..].  Statuses as above; *n_targets / *n_skipped what a load would report. */
+int sdmi_lora_check_safetensors(const char* path, const char* const* names, const int32_t* ndims, const int64_t* dims, int32_t n_entries, int32_t which, int32_t flags,
+                                int32_t* n_targets, int32_t* n_skipped);
 /* Re-merges and re-packs every target of `a` with ALL adapters active on it; blocks until done.  A non-finite scale is SDMI_ERR_INVALID and changes nothing. */
 int sdmi_lora_set_scale(sdmi_lora* a, double scale);
 int sdmi_lora_get_scale(sdmi_lora* a, double* scale, int32_t* n_targets);

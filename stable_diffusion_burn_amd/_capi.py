@@ -142,6 +142,10 @@ SIGNATURES = {
     "sdmi_multi_set_sampler": (C.c_int, [C.c_void_p, _SAMPLER]),
     "sdmi_lora_create": (C.c_int, [_CTX, C.POINTER(C.c_void_p)]),
     "sdmi_lora_add": (C.c_int, [C.c_void_p, C.c_char_p, _F, _F, C.c_int32, C.c_float]),
+    "sdmi_lora_load_safetensors": (C.c_int, [_CTX, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), _I32, _I32]),
+    "sdmi_lora_factor_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "sdmi_lora_module_name": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
+    "sdmi_lora_check_safetensors": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), _I32, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32, _I32, _I32]),
     "sdmi_lora_set_scale": (C.c_int, [C.c_void_p, C.c_double]),
     "sdmi_lora_get_scale": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), _I32]),
     "sdmi_lora_destroy": (C.c_int, [C.c_void_p]),

@@ -2,6 +2,7 @@
 // Gadersd/stable-diffusion-burn (src/model/...).
 #include "engine.hpp"
 #include "ckpt_keys.hpp"
+#include "lora_keys.hpp"
 #include "mpk_reader.hpp"
 #include "safetensors_reader.hpp"
 
@@ -756,8 +757,10 @@ static size_t entry_count(const WeightEntry& e) {
 
 // THE rule for a convolution's stored input channels: Cin < 32 is kept as one channel slice, which the GEMM kernels read in 16-byte pieces, so it is zero-padded
 // up to the next multiple of 4 (the RGB conv_in of the VAE encoder 3 -> 4, the 9-channel conv_in of an inpainting UNet 9 -> 12; 4 and 8 stay).
+int64_t Engine::padded_conv_cin(int64_t cin) { return cin < 32 ? (cin + 3) / 4 * 4 : cin; }
+
 int Engine::padded_cin(const WeightEntry& e) {
-    return (e.kind == 0 && e.dims[1] < 32) ? (int)((e.dims[1] + 3) / 4 * 4) : (int)e.dims[1];
+    return e.kind == 0 ? (int)padded_conv_cin(e.dims[1]) : (int)e.dims[1];
 }
 
 size_t Engine::stage_elems(const WeightEntry& e) {
@@ -1209,6 +1212,51 @@ void Engine::lora_add(sdmi_lora* a, const char* target, const float* down, const
     a->targets.push_back(LoraTarget{it->second, rank, (double)alpha, dev, dev + (size_t)rank * n_in});
 }
 
+sdmi_lora* Engine::lora_load_safetensors(const char* path, int which, int flags, int* n_skipped) {
+    if (!path) throw Error(SDMI_ERR_INVALID, "lora_load_safetensors: null path");
+    if (!finalized_) throw Error(SDMI_ERR_STATE, "lora_load_safetensors: weights not finalized");
+    if (!opt_keep_masters_) throw Error(SDMI_ERR_STATE, "lora_load_safetensors: the context keeps no fp32 master weights (option keep_masters=1, set before the weights are loaded)");
+    SDMI_HIP(hipSetDevice(cfg_.device));   // the allocations and copies below go to this context's device, whatever the calling thread used last
+    SafetensorsFile f(path);
+    std::vector<LoraEntryDesc> descs(entries_.size());
+    for (size_t i = 0; i < entries_.size(); ++i) {
+        const WeightEntry& e = entries_[i];
+        descs[i].name = e.name; descs[i].kind = e.kind;
+        for (int k = 0; k < 4; ++k) descs[i].dims[k] = k < e.ndim ? e.dims[k] : 1;
+        descs[i].padded = e.kind == 0 && padded_cin(e) != e.dims[1];
+    }
+    LoraFilePlan plan = lora_plan_file(f.tensors(), descs, which, flags);
+    // a weight group that was never loaded (a context without the text encoder's weights) is no target either
+    std::vector<LoraFileTarget> targets;
+    for (const LoraFileTarget& t : plan.targets) {
+        const WeightEntry& e = entries_[t.entry];
+        if (e.master && e.set) { targets.push_back(t); continue; }
+        if (!(flags & kLoraSkipUnknown)) throw Error(SDMI_ERR_STATE, std::string("lora_load_safetensors: '") + e.name + "' (module '" + t.module + "') is not loaded");
+        plan.skipped.push_back(t.module);
+    }
+    if (n_skipped) *n_skipped = (int)plan.skipped.size();
+    // nothing below depends on the file's contents any more: only an allocation or a copy can fail, and then the adapter goes as a whole
+    sdmi_lora* a = lora_create();
+    try {
+        for (const LoraFileTarget& t : targets) {
+            const int nf = t.kind == 1 ? 4 : 2;
+            size_t off[4], bytes = 0;   // each factor's raw bytes at a 16-byte aligned offset of one allocation
+            for (int i = 0; i < nf; ++i) { off[i] = bytes; bytes += (t.f[i]->nbytes + 15) / 16 * 16; }
+            char* dev = static_cast<char*>(persistent_alloc(bytes, /*weight_buffer=*/false));
+            a->allocs.push_back(dev);
+            a->factor_bytes += bytes;
+            for (int i = 0; i < nf; ++i) SDMI_HIP(hipMemcpy(dev + off[i], t.f[i]->data, t.f[i]->nbytes, hipMemcpyHostToDevice));
+            LoraTarget lt{t.entry, t.rank, t.alpha, dev + off[0], dev + off[1], t.dtype, t.kind};
+            if (t.kind == 1) { lt.down2 = dev + off[2]; lt.up2 = dev + off[3]; }
+            a->targets.push_back(lt);
+        }
+    } catch (...) {
+        try { lora_destroy(a); } catch (...) {}
+        throw;
+    }
+    return a;
+}
+
 void Engine::lora_compose(int entry, float* dst) {
     const WeightEntry& e = entries_[entry];
     const size_t n = stage_elems(e);
@@ -1218,7 +1266,11 @@ void Engine::lora_compose(int entry, float* dst) {
     m.W0 = e.master; m.W = dst;
     bool any = false;
     auto flush = [&] {
-        SDMI_HIP(launch_lora_merge(m, stream_));
+        {
+            ProfScope ps(this, PC_OTHER, 0, 2.0 * (double)n * sizeof(float));   // the master read + the result written; the factors are a few per cent of that
+            ps.set_tag("lora_merge %s%s %dx%d terms %d", m.t[0].dtype == 0 ? "F32" : m.t[0].dtype == 1 ? "F16" : "BF16", m.t[0].kind ? " loha" : "", m.R, m.Cc, m.n_terms);
+            SDMI_HIP(launch_lora_merge(m, stream_));
+        }
         m.W0 = dst;   // more than kLoraMaxTerms active adapters on one tensor: the next launch continues the sum in place
         m.n_terms = 0;
         any = true;
@@ -1228,14 +1280,21 @@ void Engine::lora_compose(int entry, float* dst) {
             if (t.entry != entry) continue;
             const float coef = (float)(a->scale * t.alpha / (double)t.rank);
             if (coef == 0.f) continue;
+            // a launch takes terms of one factor dtype and one kind: a change continues the sum in place, like a ninth term
+            if (m.n_terms && (m.t[0].dtype != t.dtype || m.t[0].kind != t.kind)) flush();
             LoraTerm& lt = m.t[m.n_terms++];
-            lt.rank = t.rank; lt.coef = coef;
+            lt = LoraTerm{};
+            lt.rank = t.rank; lt.coef = coef; lt.dtype = t.dtype; lt.kind = t.kind;
             if (e.kind == 0) {   // rows = cout: P = up [cout][rank], Q = down [rank][Cc]
                 lt.P = t.up; lt.p_rs = t.rank; lt.p_js = 1;
                 lt.Q = t.down; lt.q_js = m.Cc; lt.q_cs = 1;
             } else {             // rows = in: P(i, j) = down[j][i], Q(j, o) = up[o][j]
                 lt.P = t.down; lt.p_rs = 1; lt.p_js = m.R;
                 lt.Q = t.up; lt.q_js = 1; lt.q_cs = t.rank;
+            }
+            if (t.kind == 1) {   // LoHa: the second pair, stored the same way
+                lt.P2 = e.kind == 0 ? t.up2 : t.down2; lt.Q2 = e.kind == 0 ? t.down2 : t.up2;
+                lt.p2_rs = lt.p_rs; lt.p2_js = lt.p_js; lt.q2_js = lt.q_js; lt.q2_cs = lt.q_cs;
             }
             if (m.n_terms == kLoraMaxTerms) flush();
         }

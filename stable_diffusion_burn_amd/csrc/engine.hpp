@@ -138,8 +138,9 @@ struct WeightEntry {
 };
 
 // One target of a LoRA adapter (sdmi_lora_add): the factors on the device as the caller stored them -- down [rank][in] / [rank][cin k k],
-// up [out][rank] / [cout][rank] -- in one allocation.
-struct LoraTarget { int entry; int rank; double alpha; float* down; float* up; };
+// up [out][rank] / [cout][rank] -- in one allocation.  dtype: what the factors are stored as (0 F32: sdmi_lora_add; 1 F16 / 2 BF16: the raw bytes of a file,
+// sdmi_lora_load_safetensors).  kind 1 (LoHa): a second pair down2 / up2 (hada_w2_b / hada_w2_a next to hada_w1_b / hada_w1_a), the delta their Hadamard product.
+struct LoraTarget { int entry; int rank; double alpha; const void* down; const void* up; int dtype = 0; int kind = 0; const void* down2 = nullptr; const void* up2 = nullptr; };
 
 // Per-module scalar / 2-vector files of the dump tree that are not tensors (python/save.py:23-68): `store` != null: the value
 // is honoured (a norm's eps); otherwise it must equal `expect` (the hyper-parameters this engine hard-wires).
@@ -168,6 +169,11 @@ public:
     void lora_add(sdmi_lora* a, const char* target, const float* down, const float* up, int rank, float alpha);
     void lora_set_scale(sdmi_lora* a, double scale);
     void lora_destroy(sdmi_lora* a);
+    // a kohya-ss / LyCORIS file (csrc/lora_keys.hpp): a new adapter at scale 0 holding every module of the halves `which` selects; the whole file is checked against
+    // the entries' dims before the first byte is uploaded, and a refused file leaves the context as it was.  *n_skipped: modules passed over (SDMI_LORA_SKIP_UNKNOWN)
+    sdmi_lora* lora_load_safetensors(const char* path, int which, int flags, int* n_skipped);
+    // THE rule for a convolution's stored input channels as a function of cin alone (padded_cin(e) applies it to an entry); public for the host-only file check
+    static int64_t padded_conv_cin(int64_t cin);
     void effective_weight(const char* name, float* out, size_t n);
 
     // hot path (device pointers, reference layouts)
@@ -674,4 +680,5 @@ struct sdmi_lora {
     double scale = 0;
     std::vector<sdmi::LoraTarget> targets;
     std::vector<void*> allocs;   // device memory of the factors
+    size_t factor_bytes = 0;     // of a file's raw factors (sdmi_lora_load_safetensors); 0 for sdmi_lora_add targets
 };

@@ -11,6 +11,21 @@
 //
 // Order of operations (the rounding bound of tests/test_lora_gpu.py rests on it): per term d = fma(P(r, j), Q(j, c), d) for j = 0 .. rank - 1
 // from d = 0, then w = fma(coef, d, w), terms in the order given, w starting at W0.  Rank columns past `rank` are staged as zeros (d + 0 * 0).
+//
+// Factor dtype (a kohya .safetensors file holds its factors as F16, mostly): the two staging loops widen a 16-bit element exactly, on its bit pattern
+// (k_widen.hpp, the conversions of k_unpack.hip), while they fill Ps / Qs; the FMA loop never sees the storage type.  The type is a template parameter, not a
+// branch: lora_merge_kernel, the F32 instance, is the kernel as it was -- 118 VGPRs, 10560 bytes of LDS, no scratch; tests/test_lora_file_cpu.py holds the
+// figures -- and the five instances a file brings are lora_factor_merge_kernel<DT, HADA>, all stamped from one body (k_lora_tile.inc), so every
+// launch that sdmi_lora_add feeds produces the bits it always did.  16-bit elements are read one at a time: along the unit-stride index consecutive lanes read
+// consecutive 2-byte elements (whole contiguous segments per wave, half the bytes of fp32), and a row of odd length may start at any 2-byte offset.
+//
+// LoHa terms (HADA = true; LoraTerm::kind 1): W += coef (P Q) o (P2 Q2).  Both products share the rank chunk loop and are staged side by side, so LDS doubles to
+// 2 x 10560 = 21120 bytes and the accumulators to 64 registers (120 VGPRs in the build, no scratch): still several workgroups per CU, and occupancy is no concern
+// for a kernel that streams the master once.  Order of operations (the bound of tests/lora_file_ref.py rests on it): d1 and d2 are each the FMA chain above over
+// j = 0 .. rank - 1 from 0, h = d1 * d2 rounded once, w = fma(coef, h, w).  A launch holds terms of one dtype and one kind; the engine cuts a mixed list into
+// launches that continue in place (as it does after kLoraMaxTerms terms), which changes no element's order of operations.  LoraMerge is a by-value kernel
+// argument: 32 + 8 x 112 = 928 bytes of the 4 KB segment (static_assert in kernels.hpp).
+#include "k_widen.hpp"
 #include "kernels.hpp"
 
 namespace sdmi {
@@ -19,102 +34,52 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 constexpr int kTR = 32, kTC = 128, kJC = 16;
+
+// element i of a factor stored as DT (0 F32, 1 F16, 2 BF16): 16-bit elements are read one by one -- consecutive lanes read consecutive 2-byte elements
+// along the unit-stride index, so a wave's request is still whole contiguous segments, and no row has to start 4-byte aligned
+template <int DT>
+__device__ __forceinline__ float factor_at(const void* f, long long i) {
+    if (DT == 0) return reinterpret_cast<const float*>(f)[i];
+    return half_bits_to_f32<DT>(reinterpret_cast<const unsigned short*>(f)[i]);
+}
+}  // namespace
+
+// F32 factors, plain terms: the kernel every sdmi_lora_add launch runs, under the name and with the resources it always had
+__global__ __launch_bounds__(256) void lora_merge_kernel(LoraMerge m) {
+    constexpr int DT = 0;
+    constexpr bool HADA = false;
+#include "k_lora_tile.inc"
 }
 
-__global__ __launch_bounds__(256) void lora_merge_kernel(LoraMerge m) {
-    __shared__ float Ps[kJC][kTR + 1];
-    __shared__ __attribute__((aligned(16))) float Qs[kJC][kTC + 4];
-    const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
-    const int r0 = blockIdx.y * kTR, c0 = blockIdx.x * kTC;
-    const int c = c0 + tx * 4;
-    const bool vec = (m.Cc & 3) == 0;   // then a thread's four columns are inside or outside together and every row starts 16-byte aligned
-
-    f32x4 w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = r0 + ty + 8 * i;
-        w[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (r >= m.R) continue;
-        const float* src = m.W0 + (long long)r * m.Cc + c;
-        if (vec) {
-            if (c < m.Cc) w[i] = *reinterpret_cast<const f32x4*>(src);
-        } else {
-            if (c + 0 < m.Cc) w[i].x = src[0];
-            if (c + 1 < m.Cc) w[i].y = src[1];
-            if (c + 2 < m.Cc) w[i].z = src[2];
-            if (c + 3 < m.Cc) w[i].w = src[3];
-        }
-    }
-
-    for (int t = 0; t < m.n_terms; ++t) {
-        const LoraTerm& lt = m.t[t];
-        f32x4 d[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) d[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int j0 = 0; j0 < lt.rank; j0 += kJC) {
-            __syncthreads();   // the previous chunk has been consumed
-            for (int e = tid; e < kJC * kTR; e += 256) {
-                int j, r;
-                if (lt.p_js == 1) { j = e % kJC; r = e / kJC; } else { r = e % kTR; j = e / kTR; }
-                float v = 0.f;
-                if (r0 + r < m.R && j0 + j < lt.rank) v = lt.P[(long long)(r0 + r) * lt.p_rs + (long long)(j0 + j) * lt.p_js];
-                Ps[j][r] = v;
-            }
-            for (int e = tid; e < kJC * kTC; e += 256) {
-                int j, cc;
-                if (lt.q_cs == 1) { cc = e % kTC; j = e / kTC; } else { j = e % kJC; cc = e / kJC; }
-                float v = 0.f;
-                if (c0 + cc < m.Cc && j0 + j < lt.rank) v = lt.Q[(long long)(j0 + j) * lt.q_js + (long long)(c0 + cc) * lt.q_cs];
-                Qs[j][cc] = v;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < kJC; ++j) {
-                const f32x4 q = *reinterpret_cast<const f32x4*>(&Qs[j][tx * 4]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float p = Ps[j][ty + 8 * i];
-                    d[i].x = __fmaf_rn(p, q.x, d[i].x);
-                    d[i].y = __fmaf_rn(p, q.y, d[i].y);
-                    d[i].z = __fmaf_rn(p, q.z, d[i].z);
-                    d[i].w = __fmaf_rn(p, q.w, d[i].w);
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            w[i].x = __fmaf_rn(lt.coef, d[i].x, w[i].x);
-            w[i].y = __fmaf_rn(lt.coef, d[i].y, w[i].y);
-            w[i].z = __fmaf_rn(lt.coef, d[i].z, w[i].z);
-            w[i].w = __fmaf_rn(lt.coef, d[i].w, w[i].w);
-        }
-    }
-
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = r0 + ty + 8 * i;
-        if (r >= m.R) continue;
-        float* dst = m.W + (long long)r * m.Cc + c;
-        if (vec) {
-            if (c < m.Cc) *reinterpret_cast<f32x4*>(dst) = w[i];
-        } else {
-            if (c + 0 < m.Cc) dst[0] = w[i].x;
-            if (c + 1 < m.Cc) dst[1] = w[i].y;
-            if (c + 2 < m.Cc) dst[2] = w[i].z;
-            if (c + 3 < m.Cc) dst[3] = w[i].w;
-        }
-    }
+// the instances a file brings: 16-bit factors, LoHa terms
+template <int DT, bool HADA>
+__global__ __launch_bounds__(256) void lora_factor_merge_kernel(LoraMerge m) {
+#include "k_lora_tile.inc"
 }
 
 hipError_t launch_lora_merge(const LoraMerge& m, hipStream_t s) {
     if (!m.W0 || !m.W || m.R <= 0 || m.Cc <= 0 || m.n_terms < 0 || m.n_terms > kLoraMaxTerms) return hipErrorInvalidValue;
     if ((m.Cc & 3) == 0 && ((reinterpret_cast<uintptr_t>(m.W0) | reinterpret_cast<uintptr_t>(m.W)) & 15)) return hipErrorInvalidValue;
-    for (int t = 0; t < m.n_terms; ++t)
-        if (!m.t[t].P || !m.t[t].Q || m.t[t].rank < 1) return hipErrorInvalidValue;
+    const int dtype = m.n_terms ? m.t[0].dtype : 0, kind = m.n_terms ? m.t[0].kind : 0;
+    if (dtype < 0 || dtype > 2 || kind < 0 || kind > 1) return hipErrorInvalidValue;
+    for (int t = 0; t < m.n_terms; ++t) {
+        const LoraTerm& lt = m.t[t];
+        if (!lt.P || !lt.Q || lt.rank < 1 || lt.dtype != dtype || lt.kind != kind) return hipErrorInvalidValue;
+        if (kind == 1 && (!lt.P2 || !lt.Q2)) return hipErrorInvalidValue;
+        const uintptr_t all = reinterpret_cast<uintptr_t>(lt.P) | reinterpret_cast<uintptr_t>(lt.Q) | reinterpret_cast<uintptr_t>(lt.P2) | reinterpret_cast<uintptr_t>(lt.Q2);
+        if (all & (dtype == 0 ? 3u : 1u)) return hipErrorInvalidValue;   // an element is read with one aligned load
+    }
     const long long gy = ((long long)m.R + kTR - 1) / kTR;
     if (gy > 65535) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((m.Cc + kTC - 1) / kTC), (unsigned)gy);
-    hipLaunchKernelGGL(lora_merge_kernel, grid, dim3(256), 0, s, m);
+    switch (2 * dtype + kind) {
+        case 0: hipLaunchKernelGGL(lora_merge_kernel, grid, dim3(256), 0, s, m); break;
+        case 1: hipLaunchKernelGGL((lora_factor_merge_kernel<0, true>), grid, dim3(256), 0, s, m); break;
+        case 2: hipLaunchKernelGGL((lora_factor_merge_kernel<1, false>), grid, dim3(256), 0, s, m); break;
+        case 3: hipLaunchKernelGGL((lora_factor_merge_kernel<1, true>), grid, dim3(256), 0, s, m); break;
+        case 4: hipLaunchKernelGGL((lora_factor_merge_kernel<2, false>), grid, dim3(256), 0, s, m); break;
+        default: hipLaunchKernelGGL((lora_factor_merge_kernel<2, true>), grid, dim3(256), 0, s, m); break;
+    }
     return hipGetLastError();
 }
 

@@ -307,9 +307,19 @@ hipError_t launch_softmax_rows_f32_to_bf16(const float* x, void* y, int rows, in
 // W[r][c] = W0[r][c] + sum_t coef_t * sum_j P_t(r, j) Q_t(j, c) over a row-major [R][Cc] fp32 tensor, terms in order, fp32 throughout.
 // P_t(r, j) = P[r * p_rs + j * p_js], Q_t(j, c) = Q[j * q_js + c * q_cs] (element strides: the factors are read as the caller stored them,
 // whichever way the target's layout turns them).  W may be W0 (every element is read and written by one thread).
-struct LoraTerm { const float* P; const float* Q; long long p_rs, p_js, q_js, q_cs; int rank; float coef; };
+// dtype: what the factors are stored as -- 0 F32, 1 F16, 2 BF16 (element strides count elements of that type); a 16-bit factor is widened exactly, on its bit
+// pattern (k_widen.hpp), while it is staged.  kind 0: the product above.  kind 1 (LoHa): a second pair P2 / Q2 of the same rank with strides of its own, and the
+// term is coef_t * (sum_j P Q) * (sum_j P2 Q2): d1 and d2 each the FMA chain over j from 0, h = d1 * d2 rounded once, w = fma(coef, h, w).
+// All terms of one launch share dtype and kind (anything else is hipErrorInvalidValue): the caller splits a mixed list into launches that continue in place,
+// which leaves every element's order of operations as it is.
+struct LoraTerm {
+    const void* P; const void* Q; long long p_rs, p_js, q_js, q_cs; int rank; float coef;
+    int dtype, kind;
+    const void* P2; const void* Q2; long long p2_rs, p2_js, q2_js, q2_cs;
+};
 constexpr int kLoraMaxTerms = 8;
 struct LoraMerge { const float* W0; float* W; int R, Cc, n_terms; LoraTerm t[kLoraMaxTerms]; };
+static_assert(sizeof(LoraMerge) <= 4096, "LoraMerge is passed by value: it must fit the 4 KB kernel-argument segment (lower kLoraMaxTerms)");
 hipError_t launch_lora_merge(const LoraMerge& m, hipStream_t s);
 
 // ---- checkpoint tensors (k_unpack.hip) ---------------------------------------------------

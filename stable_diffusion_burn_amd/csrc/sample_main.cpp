@@ -16,6 +16,9 @@
 //   * SDMI_PROMPT_STYLE=webui (no reference counterpart; unset: everything as above) encodes the prompt and the negative prompt with sdmi_encode_prompt --
 //     chunks padded to clip_ctx tokens, emphasis, BREAK, no length limit.  In that mode only, SDMI_NEGATIVE_PROMPT (default "") replaces the empty prompt and
 //     SDMI_CLIP_SKIP (default 1) is passed on; the negative prompt is brought to the prompt's chunk count.
+//   * SDMI_LORA=<file>[:scale[:te_scale]] (no reference counterpart) attaches a kohya-ss / LyCORIS LoRA .safetensors file before the prompt is encoded
+//     (sdmi_lora_load_safetensors): scale defaults to 1, te_scale -- the text encoder's -- to scale.  It sets the engine option keep_masters itself.  Only finite
+//     decimal numbers are scales; a file name that itself ends in ":<number>" needs its scale spelled out ("name:2:1").
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -56,6 +59,47 @@ static void apply_overrides(sdmi_config& cfg, const char* spec) {
     }
 }
 
+// a complete, finite decimal number ("0.8", "-1", "1e-1"): nothing strtod would also take -- "inf", "nan", hexadecimal floats -- counts as a scale
+static bool decimal_scale(const char* s, double* v) {
+    if (!*s || std::strspn(s, "0123456789+-.eE") != std::strlen(s)) return false;
+    char* end = nullptr;
+    *v = std::strtod(s, &end);
+    return end != s && *end == '\0' && *v - *v == 0.0;
+}
+
+// "<file>[:scale[:te_scale]]": up to two trailing ':'-separated fields that are decimal numbers are scales, the rest is the path (which may hold ':' itself).
+// A path whose own last field is a decimal number ("dir:2") is therefore written with its scale: "dir:2:1".
+static std::string parse_lora_spec(const char* spec, double* scale, double* te_scale, bool* has_te) {
+    std::string path(spec);
+    double found[2];
+    int n = 0;
+    while (n < 2) {
+        const size_t colon = path.rfind(':');
+        double v;
+        if (colon == std::string::npos || colon == 0 || !decimal_scale(path.c_str() + colon + 1, &v)) break;
+        found[n++] = v;
+        path.resize(colon);
+    }
+    *scale = n ? found[n - 1] : 1.0;
+    *has_te = n == 2;
+    *te_scale = n == 2 ? found[0] : *scale;
+    return path;
+}
+
+static void attach_lora(sdmi_ctx* ctx, const char* spec) {
+    double scale, te_scale;
+    bool has_te;
+    const std::string path = parse_lora_spec(spec, &scale, &te_scale, &has_te);
+    const int32_t which[2] = {has_te ? SDMI_LORA_UNET : (SDMI_LORA_UNET | SDMI_LORA_TE), SDMI_LORA_TE};
+    const double scales[2] = {scale, te_scale};
+    for (int i = 0; i < (has_te ? 2 : 1); ++i) {
+        sdmi_lora* a = nullptr;   // owned by the context: freed by sdmi_destroy
+        int32_t n = 0, skipped = 0;
+        if (sdmi_lora_load_safetensors(ctx, path.c_str(), which[i], 0, &a, &n, &skipped) != SDMI_OK || sdmi_lora_set_scale(a, scales[i]) != SDMI_OK) die("Error loading LoRA");
+        std::printf("LoRA %s: %d targets at scale %g\n", path.c_str(), (int)n, scales[i]);
+    }
+}
+
 int main(int argc, char** argv) {
     if (argc != 7 && argc != 8) {
         std::fprintf(stderr, "Usage: %s <model_type(burn, dump or safetensors)> <model_name> <unconditional_guidance_scale> <n_diffusion_steps> <prompt> <output_image_name> [device(hip, hip:N)]\n", argv[0]);
@@ -92,6 +136,8 @@ int main(int argc, char** argv) {
     std::printf("Loading model...\n");
     sdmi_ctx* ctx = nullptr;
     if (sdmi_create(&ctx, &cfg) != SDMI_OK) die("Error creating device context");
+    const char* lora = std::getenv("SDMI_LORA");
+    if (lora && *lora && sdmi_set_option(ctx, "keep_masters", "1") != SDMI_OK) die("Error setting keep_masters");
     if (model_type == "burn") {
         std::string file = model_name;
         if (file.size() < 4 || file.compare(file.size() - 4, 4, ".mpk") != 0) file += ".mpk";   // FileRecorder::load sets the extension
@@ -101,6 +147,7 @@ int main(int argc, char** argv) {
     } else if (sdmi_load_weights_dir(ctx, model_name.c_str()) != SDMI_OK || sdmi_finalize_weights(ctx) != SDMI_OK) {
         die("Error loading model dump");
     }
+    if (lora && *lora) attach_lora(ctx, lora);
 
     // sd.unconditional_context(&tokenizer); sd.context(&tokenizer, prompt)   (main.rs:100-101)
     const int cd = cfg.ctx_dim, cap = cfg.clip_ctx;

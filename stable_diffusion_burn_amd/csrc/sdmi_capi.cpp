@@ -17,6 +17,7 @@
 #include "mpk_reader.hpp"
 #include "prompt.hpp"
 #include "safetensors_reader.hpp"
+#include "lora_keys.hpp"
 #include "tokenizer.hpp"
 
 using sdmi::Engine;
@@ -900,6 +901,57 @@ int sdmi_lora_create(sdmi_ctx* ctx, sdmi_lora** out) {
 
 int sdmi_lora_add(sdmi_lora* a, const char* target, const float* down, const float* up, int32_t rank, float alpha) {
     return guarded([&] { lora(a).engine->lora_add(a, target, down, up, rank, alpha); });
+}
+
+int sdmi_lora_load_safetensors(sdmi_ctx* ctx, const char* path, int32_t which, int32_t flags, sdmi_lora** out, int32_t* n_targets, int32_t* n_skipped) {
+    if (!out) { g_last_error = "sdmi_lora_load_safetensors: null argument"; return SDMI_ERR_INVALID; }
+    *out = nullptr;
+    if (n_targets) *n_targets = 0;
+    if (n_skipped) *n_skipped = 0;
+    return guarded([&] {
+        int skipped = 0;
+        sdmi_lora* a = eng(ctx).lora_load_safetensors(path, which, flags, &skipped);
+        *out = a;
+        if (n_targets) *n_targets = (int32_t)a->targets.size();
+        if (n_skipped) *n_skipped = skipped;
+    });
+}
+
+int sdmi_lora_factor_bytes(sdmi_lora* a, size_t* bytes) {
+    return guarded([&] {
+        if (!bytes) throw Error(SDMI_ERR_INVALID, "lora_factor_bytes: null argument");
+        *bytes = lora(a).factor_bytes;
+    });
+}
+
+int sdmi_lora_module_name(const char* dump_name, char* buf, size_t n) {
+    return guarded([&] {
+        if (!dump_name || !buf) throw Error(SDMI_ERR_INVALID, "lora_module_name: null argument");
+        std::string name;
+        if (!sdmi::lora_module_name(dump_name, &name)) throw Error(SDMI_ERR_INVALID, std::string("lora_module_name: '") + dump_name + "' is no conv / Linear weight of the UNet or the text encoder");
+        if (n < name.size() + 1) throw Error(SDMI_ERR_INVALID, "lora_module_name: capacity too small");
+        std::memcpy(buf, name.c_str(), name.size() + 1);
+    });
+}
+
+int sdmi_lora_check_safetensors(const char* path, const char* const* names, const int32_t* ndims, const int64_t* dims, int32_t n_entries, int32_t which, int32_t flags,
+                                int32_t* n_targets, int32_t* n_skipped) {
+    return guarded([&] {
+        if (!path || !names || !ndims || !dims || n_entries < 0) throw Error(SDMI_ERR_INVALID, "lora_check_safetensors: null argument");
+        std::vector<sdmi::LoraEntryDesc> descs((size_t)n_entries);
+        for (int32_t i = 0; i < n_entries; ++i) {
+            if (!names[i]) throw Error(SDMI_ERR_INVALID, "lora_check_safetensors: null name");
+            sdmi::LoraEntryDesc& d = descs[(size_t)i];
+            d.name = names[i];
+            d.kind = ndims[i] == 4 ? 0 : ndims[i] == 2 ? 1 : 2;
+            for (int k = 0; k < 4; ++k) d.dims[k] = k < ndims[i] ? dims[4 * (size_t)i + k] : 1;
+            d.padded = d.kind == 0 && Engine::padded_conv_cin(d.dims[1]) != d.dims[1];
+        }
+        sdmi::SafetensorsFile f(path);
+        const sdmi::LoraFilePlan plan = sdmi::lora_plan_file(f.tensors(), descs, which, flags);
+        if (n_targets) *n_targets = (int32_t)plan.targets.size();
+        if (n_skipped) *n_skipped = (int32_t)plan.skipped.size();
+    });
 }
 
 int sdmi_lora_set_scale(sdmi_lora* a, double scale) {

@@ -260,12 +260,38 @@ def check_lora_tensors(tensors, shapes: dict) -> list:
     return out
 
 
+LORA_UNET, LORA_TE = 1, 2          # sdmi_lora_load_safetensors `which`
+LORA_SKIP_UNKNOWN = 1               # ... and its flag
+
+
+def lora_module_name(name: str) -> str:
+    """The kohya-ss module name of the conv / Linear weight `name` of the UNet or the text encoder ("unet/.../weight", "clip/.../weight"):
+    "lora_unet_" / "lora_te_" + its diffusers module path with "_" for "." (sdmi_lora_module_name, host only, no GPU).  SdmiError for any other name."""
+    buf = C.create_string_buffer(256)
+    check(load_library().sdmi_lora_module_name(name.encode(), buf, 256))
+    return buf.value.decode()
+
+
+def lora_check_safetensors(path, specs, which: int = LORA_UNET | LORA_TE, skip_unknown: bool = False) -> tuple:
+    """The checks of lora_load_safetensors that need no device (sdmi_lora_check_safetensors, host only): the kohya file `path` against
+    specs = [(dump name, shape)] (weight_specs()).  Returns (n_targets, n_skipped); SdmiError as the loader raises it."""
+    specs = [(n, tuple(int(d) for d in shp)) for n, shp in specs if len(shp) in (2, 4)]
+    names = (C.c_char_p * len(specs))(*[n.encode() for n, _ in specs])
+    ndims = (C.c_int32 * len(specs))(*[len(shp) for _, shp in specs])
+    dims = (C.c_int64 * (4 * len(specs)))(*[(shp + (1, 1))[k] for _, shp in specs for k in range(4)])
+    nt, ns = C.c_int32(), C.c_int32()
+    check(load_library().sdmi_lora_check_safetensors(str(path).encode(), names, ndims, dims, len(specs), int(which), LORA_SKIP_UNKNOWN if skip_unknown else 0,
+                                                     C.byref(nt), C.byref(ns)))
+    return nt.value, ns.value
+
+
 class LoraAdapter:
     """One adapter attached to a StableDiffusion (sdmi_lora): .set_scale(s) re-merges its targets on the device, .scale reads it back,
     .detach() restores the targets and frees it.  Owned by the context: closing the StableDiffusion invalidates it."""
 
-    def __init__(self, sd: "StableDiffusion", handle):
+    def __init__(self, sd: "StableDiffusion", handle, n_skipped: int = 0):
         self._sd, self._a = sd, handle
+        self.n_skipped = n_skipped   # modules of a file that were passed over (lora_load_safetensors(skip_unknown=True))
 
     def _handle(self):
         if self._a is None or not self._sd._ctx.value:
@@ -290,11 +316,51 @@ class LoraAdapter:
         check(self._sd._lib.sdmi_lora_get_scale(self._handle(), C.byref(s), C.byref(n)))
         return n.value
 
+    @property
+    def factor_bytes(self) -> int:
+        """device bytes held by the raw factors of a file-loaded adapter (0 for lora_attach's)"""
+        b = C.c_size_t()
+        check(self._sd._lib.sdmi_lora_factor_bytes(self._handle(), C.byref(b)))
+        return b.value
+
     def detach(self) -> None:
         if self._a is not None and self._sd._ctx.value:
             a, self._a = self._a, None
             check(self._sd._lib.sdmi_lora_destroy(a))
         self._a = None
+
+
+class LoraFileAdapter:
+    """The two halves of one kohya file as two adapters (lora_load_safetensors(te_scale=...)): the "<lora:name:unet:te>" of the front-ends.
+    .set_scale(unet, te) re-merges each half at its own scale, .scale reads (unet, te) back, .detach() frees both."""
+
+    def __init__(self, unet: LoraAdapter, te: LoraAdapter):
+        self.unet, self.te = unet, te
+        self._sd = unet._sd
+
+    def set_scale(self, unet: float, te: float = None) -> None:
+        self.unet.set_scale(unet)
+        self.te.set_scale(unet if te is None else te)
+
+    @property
+    def scale(self) -> tuple:
+        return self.unet.scale, self.te.scale
+
+    @property
+    def n_targets(self) -> int:
+        return self.unet.n_targets + self.te.n_targets
+
+    @property
+    def n_skipped(self) -> int:
+        return self.unet.n_skipped + self.te.n_skipped
+
+    @property
+    def factor_bytes(self) -> int:
+        return self.unet.factor_bytes + self.te.factor_bytes
+
+    def detach(self) -> None:
+        self.te.detach()
+        self.unet.detach()
 
 
 class MultiLoraAdapter:
@@ -304,9 +370,9 @@ class MultiLoraAdapter:
         self._parts = list(parts)
         self._owner = owner
 
-    def set_scale(self, scale: float) -> None:
+    def set_scale(self, *scale) -> None:
         for p in self._parts:
-            p.set_scale(scale)
+            p.set_scale(*scale)
 
     @property
     def scale(self) -> float:
@@ -321,7 +387,7 @@ class MultiLoraAdapter:
             self._owner = None
 
 
-__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "safetensors_list", "checkpoint_key", "default_alphas_cumprod", "control_step_on", "control_residual_shapes", "img2img_timesteps", "sampler_coefs", "resize_weights", "load_lora_npz", "save_lora_npz", "LoraAdapter", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
+__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "safetensors_list", "checkpoint_key", "default_alphas_cumprod", "control_step_on", "control_residual_shapes", "img2img_timesteps", "sampler_coefs", "resize_weights", "load_lora_npz", "save_lora_npz", "lora_module_name", "lora_check_safetensors", "LoraAdapter", "LoraFileAdapter", "LORA_UNET", "LORA_TE", "LORA_SKIP_UNKNOWN", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
 
 
 @dataclass(frozen=True)
@@ -621,6 +687,37 @@ class StableDiffusion:
             adapter.detach()
             raise
         return adapter
+
+    def _lora_load(self, path, which: int, skip_unknown: bool, scale: float) -> LoraAdapter:
+        h, nt, ns = C.c_void_p(), C.c_int32(), C.c_int32()
+        check(self._lib.sdmi_lora_load_safetensors(self._ctx, str(path).encode(), which, LORA_SKIP_UNKNOWN if skip_unknown else 0, C.byref(h), C.byref(nt), C.byref(ns)))
+        adapter = LoraAdapter(self, h, ns.value)
+        try:
+            adapter.set_scale(scale)
+        except Exception:
+            adapter.detach()
+            raise
+        return adapter
+
+    def lora_load_safetensors(self, path, scale: float = 1.0, te_scale: float = None, skip_unknown: bool = False):
+        """Attach a kohya-ss / LyCORIS LoRA file (.safetensors: LoRA, LoCon and LoHa modules in F32 / F16 / BF16, named after diffusers modules) and merge it
+        at `scale` (sdmi_lora_load_safetensors): the factors go to the device as the file holds them and are widened by the merge kernel.  te_scale=None: one
+        LoraAdapter over the UNet and the text encoder.  Otherwise a LoraFileAdapter whose two halves carry their own scales (.set_scale(unet, te)).
+        skip_unknown: modules this model has no tensor for (a text-encoder layer it lacks, a weight group that is not loaded) are passed over and counted in
+        .n_skipped instead of refusing the file.  Needs set_option("keep_masters", 1) before the weights were loaded."""
+        s = float(scale)
+        t = s if te_scale is None else float(te_scale)
+        if not (np.isfinite(s) and np.isfinite(t)):
+            raise ValueError(f"lora scales must be finite, got {scale}, {te_scale}")
+        if te_scale is None:
+            return self._lora_load(path, LORA_UNET | LORA_TE, skip_unknown, s)
+        unet = self._lora_load(path, LORA_UNET, skip_unknown, s)
+        try:
+            te = self._lora_load(path, LORA_TE, skip_unknown, t)
+        except Exception:
+            unet.detach()
+            raise
+        return LoraFileAdapter(unet, te)
 
     def effective_weight(self, name: str) -> np.ndarray:
         """The fp32 tensor (reference layout) currently packed for the conv / Linear weight `name`: the loaded one, or the merge of the
@@ -1407,6 +1504,19 @@ class MultiStableDiffusion:
         try:
             for i in range(len(self.devices)):
                 parts.append(self.device_view(i).lora_attach(tensors, scale))
+        except Exception:
+            for p in parts:
+                p.detach()
+            raise
+        self._lora_views.extend(p._sd for p in parts)
+        return MultiLoraAdapter(parts, self)
+
+    def lora_load_safetensors(self, path, scale: float = 1.0, te_scale: float = None, skip_unknown: bool = False) -> MultiLoraAdapter:
+        """StableDiffusion.lora_load_safetensors on every device."""
+        parts = []
+        try:
+            for i in range(len(self.devices)):
+                parts.append(self.device_view(i).lora_load_safetensors(path, scale, te_scale, skip_unknown))
         except Exception:
             for p in parts:
                 p.detach()

@@ -229,6 +229,49 @@ def write_checkpoint_safetensors(path, specs, get_tensor, alphas_cumprod, dtype:
     write_safetensors(path, tensors)
 
 
+def write_lora_safetensors(path, tensors: dict, dtype: str = "F16", style: str = "kohya", extra: dict | None = None) -> None:
+    """Write an adapter as a kohya-ss / LyCORIS .safetensors file: the inverse of StableDiffusion.lora_load_safetensors (and the way to convert an .npz:
+    write_lora_safetensors(path, load_lora_npz(npz))).
+
+    tensors: {dump target: (down, up, alpha)} as lora_attach takes them -- written as "<module>.lora_down.weight" ([r, in], a conv's [r, cin, k, k]),
+    "<module>.lora_up.weight" ([out, r], a conv's [out, r, 1, 1]) and "<module>.alpha" (left out when alpha is None: the loader then takes alpha = r) -- or
+    {dump target: (w1_a, w1_b, w2_a, w2_b, alpha)}, a LoHa module: "<module>.hada_w1_a" [out, r], "hada_w1_b" [r, in] (a conv's [r, cin k k]), and w2 alike.
+    dtype "F32" | "F16" | "BF16" for the factors; alpha is one number of the same dtype, as the trainers write it.  style "kohya": modules named after
+    the diffusers path (pipeline.lora_module_name); "compvis": after the CompVis key with "_" for ".".  extra: further {key: tensor} entries."""
+    if dtype not in ("F32", "F16", "BF16"):
+        raise ValueError(f"write_lora_safetensors: dtype must be F32, F16 or BF16, got {dtype!r}")
+    if style not in ("kohya", "compvis"):
+        raise ValueError(f"write_lora_safetensors: style must be 'kohya' or 'compvis', got {style!r}")
+    from .pipeline import checkpoint_key, lora_module_name
+
+    def stored(a):
+        a = np.asarray(a, np.float32)   # (a 0-d alpha stays 0-d: kohya-ss writes a scalar)
+        return a if dtype == "F32" else a.astype(np.float16) if dtype == "F16" else (bf16_bits(a).reshape(a.shape), "BF16")
+
+    out = {}
+    for target, item in tensors.items():
+        module = lora_module_name(target)
+        if style == "compvis" and module.startswith("lora_unet_"):
+            module = "lora_unet_" + checkpoint_key(target)[0][len("model.diffusion_model."):-len(".weight")].replace(".", "_")
+        if len(item) == 3:
+            down, up, alpha = item
+            down, up = np.asarray(down, np.float32), np.asarray(up, np.float32)
+            if down.ndim == 4:
+                up = up.reshape(up.shape[0], up.shape[1], 1, 1)
+            out[module + ".lora_down.weight"], out[module + ".lora_up.weight"] = stored(down), stored(up)
+        elif len(item) == 5:
+            w1_a, w1_b, w2_a, w2_b, alpha = item
+            for key, w in (("hada_w1_a", w1_a), ("hada_w1_b", w1_b), ("hada_w2_a", w2_a), ("hada_w2_b", w2_b)):
+                w = np.asarray(w, np.float32)
+                out[f"{module}.{key}"] = stored(w.reshape(w.shape[0], -1))
+        else:
+            raise ValueError(f"write_lora_safetensors: '{target}': expected (down, up, alpha) or (w1_a, w1_b, w2_a, w2_b, alpha)")
+        if alpha is not None:
+            out[module + ".alpha"] = stored(np.float32(alpha))
+    out.update(extra or {})
+    write_safetensors(path, out)
+
+
 # ---- ControlNet: the weight group controlnet/... and its cldm-layout .safetensors file (DESIGN.md section 9g) ---------------------
 CONTROL_HINT_WIDTHS = (16, 16, 32, 32, 96, 96, 256)   # ControlNet's constants: they do not scale with model_channels
 
