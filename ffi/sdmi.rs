@@ -103,6 +103,11 @@ extern "C" {
     fn sdmi_op_unpack_tensor(ctx: *mut c_void, raw: *const c_void, dtype: i32, ndim: i32, dims: *const i64, transform: i32, out: *mut c_float) -> c_int;
     fn sdmi_op_conv2d_pair(ctx: *mut c_void, x: *const c_float, h: *const c_float, w_skip: *const c_float, b_skip: *const c_float, w_out: *const c_float,
                            b_out: *const c_float, n: i32, cin_x: i32, cout: i32, hh: i32, ww: i32, out: *mut c_float, out_planes: *mut c_float) -> c_int;
+    fn sdmi_op_linear_pair(ctx: *mut c_void, u: *const c_float, h: *const c_float, w_main: *const c_float, b_main: *const c_float, w_aux: *const c_float,
+                           b_aux: *const c_float, resid: *const c_float, resid_ld: i32, rows: i32, k_main: i32, k_aux: i32, cout: i32, out_ld: i32,
+                           out: *mut c_float, out_planes: *mut c_float) -> c_int;
+    fn sdmi_op_linear_fold(ctx: *mut c_void, w_lin: *const c_float, b_lin: *const c_float, w_proj: *const c_float, k_main: i32, cmid: i32, cout: i32,
+                           wf: *mut c_float, bf: *mut c_float) -> c_int;
     fn sdmi_finalize_weights(ctx: *mut c_void) -> c_int;
     fn sdmi_set_option(ctx: *mut c_void, key: *const c_char, value: *const c_char) -> c_int;
     fn sdmi_create_multi(out: *mut *mut c_void, cfg: *const SdmiConfig, devices: *const i32, n_devices: i32) -> c_int;
@@ -567,6 +572,29 @@ impl StableDiffusionMi355 {
         let st = unsafe { sdmi_op_conv2d_pair(self.ctx, x.as_ptr(), h.as_ptr(), w_skip.as_ptr(), b_skip.as_ptr(), w_out.as_ptr(), b_out.as_ptr(), n, cin_x, cout, hh, ww,
                                               out.as_mut_ptr(), std::ptr::null_mut()) };
         if st != 0 { Err(last_error().into()) } else { Ok(out) }
+    }
+
+    /// The tail of a transformer block with `proj_out` folded into the MLP's output Linear (`sdmi_op_linear_pair`): `u w_main + b_main + h w_aux + b_aux + resid`,
+    /// row-major `[rows, cout]`.  Option `proj_out_fold` = 1: one split-K launch carrying `h w_aux` on extra K slices; 0: two launches.
+    #[allow(clippy::too_many_arguments)]
+    pub fn op_linear_pair(&self, u: &[f32], h: &[f32], w_main: &[f32], b_main: &[f32], w_aux: &[f32], b_aux: &[f32], resid: Option<&[f32]>, rows: i32, k_main: i32,
+                          k_aux: i32, cout: i32) -> Result<Vec<f32>, Box<dyn Error>> {
+        let (r, km, ka, n) = (rows as usize, k_main as usize, k_aux as usize, cout as usize);
+        if u.len() != r * km || h.len() != r * ka || w_main.len() != km * n || w_aux.len() != ka * n || b_main.len() != n || b_aux.len() != n
+            || resid.map_or(false, |x| x.len() != r * n) { return Err("op_linear_pair: slices do not match the dims".into()); }
+        let mut out = vec![0f32; r * n];
+        let st = unsafe { sdmi_op_linear_pair(self.ctx, u.as_ptr(), h.as_ptr(), w_main.as_ptr(), b_main.as_ptr(), w_aux.as_ptr(), b_aux.as_ptr(),
+                                              resid.map_or(std::ptr::null(), |x| x.as_ptr()), 0, rows, k_main, k_aux, cout, 0, out.as_mut_ptr(), std::ptr::null_mut()) };
+        if st != 0 { Err(last_error().into()) } else { Ok(out) }
+    }
+
+    /// The folded weights of that tail (`sdmi_op_linear_fold`): `(w_proj w_lin^T [cout, k_main], w_proj b_lin [cout])`, fp64 accumulation, rounded once.
+    pub fn op_linear_fold(&self, w_lin: &[f32], b_lin: &[f32], w_proj: &[f32], k_main: i32, cmid: i32, cout: i32) -> Result<(Vec<f32>, Vec<f32>), Box<dyn Error>> {
+        let (km, c, n) = (k_main as usize, cmid as usize, cout as usize);
+        if w_lin.len() != km * c || b_lin.len() != c || w_proj.len() != n * c { return Err("op_linear_fold: slices do not match the dims".into()); }
+        let (mut wf, mut bf) = (vec![0f32; n * km], vec![0f32; n]);
+        let st = unsafe { sdmi_op_linear_fold(self.ctx, w_lin.as_ptr(), b_lin.as_ptr(), w_proj.as_ptr(), k_main, cmid, cout, wf.as_mut_ptr(), bf.as_mut_ptr()) };
+        if st != 0 { Err(last_error().into()) } else { Ok((wf, bf)) }
     }
 
     /// `context(&tokenizer, text)` (stablediffusion/mod.rs:198-210): `[T, ctx_dim]` row-major, T = tokens + 2.

@@ -681,6 +681,22 @@ int sdmi_op_conv2d_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, 
  * launch wrote as bf16 planes, joined back to fp32. */
 int sdmi_op_conv2d_pair(sdmi_ctx* ctx, const float* x, const float* h, const float* w_skip, const float* b_skip, const float* w_out,
                         const float* b_out, int32_t n, int32_t cin_x, int32_t cout, int32_t hh, int32_t ww, float* out, float* out_planes);
+/* The tail of a transformer block with proj_out folded into the MLP's output Linear (no reference counterpart; for tests; precision 0 only, k_main and k_aux
+ * multiples of 32): out = u x w_main + b_main + h x w_aux + b_aux + resid.  u [rows,k_main], h [rows,k_aux], w_main [k_main,cout] and w_aux [k_aux,cout] in the
+ * Linear layout, biases [cout] or NULL, resid [rows,cout] or NULL, kept as rows resid_ld (0: cout) elements apart.  Both inputs reach the engine as bf16 planes,
+ * as in the model.  Option proj_out_fold = 1: ONE split-K launch whose extra K slices compute h x w_aux, plus its reduce, which adds both biases and the residual
+ * (an error where that form does not apply); 0: the auxiliary Linear with the residual, then the main one with that as its residual (out_ld must be 0 or cout).
+ * Options gemm_tile / splitk / splitk_aux force the tile and request the (main, auxiliary) slice counts.  The engine keeps the result as rows out_ld (0: cout)
+ * elements apart; out [rows,cout] (NULL: none) receives the fp32 result, out_planes (NULL: none; cout and out_ld multiples of 32) the one the same launch wrote
+ * as bf16 planes, joined back to fp32.  At least one of the two is given. */
+int sdmi_op_linear_pair(sdmi_ctx* ctx, const float* u, const float* h, const float* w_main, const float* b_main, const float* w_aux, const float* b_aux,
+                        const float* resid, int32_t resid_ld, int32_t rows, int32_t k_main, int32_t k_aux, int32_t cout, int32_t out_ld, float* out,
+                        float* out_planes);
+/* The folded weights of a transformer block's tail, through the kernel the loader uses (for tests): w_lin [k_main,cmid] and b_lin [cmid] (NULL: zeros) a Linear
+ * in the reference layout, w_proj [cout,cmid] a 1x1 convolution -> wf [cout,k_main] = w_proj x w_lin^T (the packed layout) and bf [cout] = w_proj x b_lin, both
+ * accumulated in fp64 and rounded once to fp32. */
+int sdmi_op_linear_fold(sdmi_ctx* ctx, const float* w_lin, const float* b_lin, const float* w_proj, int32_t k_main, int32_t cmid, int32_t cout, float* wf,
+                        float* bf);
 /* sdmi_op_linear + resid [rows,cout] (NULL: none), kept as rows resid_ld (0: cout) elements apart like sdmi_op_conv2d_epilogue's. */
 int sdmi_op_linear_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, const float* resid,
                             int32_t resid_ld, int32_t rows, int32_t cin, int32_t cout, float* out);

@@ -190,6 +190,8 @@ SIGNATURES = {
     "sdmi_op_conv2d_epilogue": (C.c_int, [_CTX, _F, _F, _F, _F, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_int32, _F]),
     "sdmi_op_conv2d_pair": (C.c_int, [_CTX, _F, _F, _F, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _F]),
+    "sdmi_op_linear_pair": (C.c_int, [_CTX, _F, _F, _F, _F, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F, _F]),
+    "sdmi_op_linear_fold": (C.c_int, [_CTX, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, _F, _F]),
     "sdmi_op_linear_epilogue": (C.c_int, [_CTX, _F, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),
     "sdmi_op_conv2d_view": (C.c_int, [_CTX, _F, _F, _F, _F, C.c_int32, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, _VIEW, _F, _F]),

@@ -441,6 +441,10 @@ void Engine::build_model() {
         fp8_copy(s.proj_out, path + "/proj_out/weight");
         fp8_copy_lin(s.geglu_proj, t + "/mlp/geglu/proj/weight");
         fp8_copy_lin(s.mlp_lin, t + "/mlp/lin/weight");
+        // the entries the folded weights are derived from (rebuild_folds); idx_st ties them to the block
+        s.fold_entries[0] = entry_index_.at(t + "/mlp/lin/weight");
+        s.fold_entries[1] = entry_index_.at(t + "/mlp/lin/bias");
+        s.fold_entries[2] = entry_index_.at(path + "/proj_out/weight");
     };
 
     add(this, "alphas_cumprod", 3, {1000}, nullptr);
@@ -484,7 +488,11 @@ void Engine::build_model() {
 
     // index ResBlocks / SpatialTransformers for the hoisted per-call tables
     auto idx_res = [&](ResW& r) { r.temb_index = (int)res_list_.size(); res_list_.push_back(&r); };
-    auto idx_st = [&](SpatialW& s) { s.ctx_index = (int)st_list_.size(); st_list_.push_back(&s); };
+    auto idx_st = [&](SpatialW& s) {
+        s.ctx_index = (int)st_list_.size();
+        st_list_.push_back(&s);
+        for (int i : s.fold_entries) entries_[(size_t)i].fold_st = s.ctx_index;
+    };
     auto idx_block = [&](UBlock& b) {
         if (b.kind == BK_CONV || b.kind == BK_DOWN) return;
         idx_res(b.res);
@@ -770,6 +778,7 @@ size_t Engine::stage_elems(const WeightEntry& e) {
 
 void Engine::pack_entry(WeightEntry& e, float* stage) {
     const size_t n_stage = stage_elems(e);
+    fold_touch(e);
     if (e.pre_scale != 1.f) SDMI_HIP(launch_scale_f32(stage, (long long)n_stage, e.pre_scale, stream_));
     hipError_t err;
     if (e.kind == 0) {
@@ -828,6 +837,7 @@ void Engine::stage_commit(WeightEntry& e, size_t offset, int half) {
     }
     ensure_arena(e.group);
     if (e.kind == 2) {
+        fold_touch(e);
         SDMI_HIP(hipMemcpyAsync(*e.dst, host, count * sizeof(float), hipMemcpyHostToDevice, stream_));
     } else {
         float* stage = reinterpret_cast<float*>(st.dev[half] + offset);
@@ -907,6 +917,7 @@ void Engine::set_weight(const char* name, const float* data, int ndim, const int
     upload_weight(e, data);   // data is copied into the pinned ring before this returns: the caller may free it
     // a ControlNet tensor behind finalize_weights leaves finalized_ alone, so no later finalize releases the pinned ring: the tensor that completes the group does
     if (e.group == 3 && finalized_ && control_ready()) {
+        rebuild_folds();
         SDMI_HIP(hipStreamSynchronize(stream_));
         stager_release();
     }
@@ -1089,6 +1100,7 @@ void Engine::load_safetensors_groups(const char* path, bool control) {
         char* dev = stager_->dev[half] + off;
         SDMI_HIP(hipMemcpyAsync(dev, pinned, j.t->nbytes, hipMemcpyHostToDevice, stream_));
         float* out = e.kind <= 1 ? static_cast<float*>(conv_stage.p) : *e.dst;
+        fold_touch(e);
         long long d0, d1;
         if (j.transform == 1) { d0 = e.dims[1]; d1 = e.dims[0]; }
         else if (j.transform == 2) { d0 = e.dims[0]; d1 = e.dims[2] * e.dims[3]; }
@@ -1107,6 +1119,7 @@ void Engine::load_safetensors_groups(const char* path, bool control) {
         if (e.group != 3) finalized_ = false;
     }
     if (alphas_entry) { alphas_ = schedule; alphas_entry->set = true; }
+    if (control && finalized_) rebuild_folds();   // a ControlNet loaded behind finalize_weights: its folds are built here (the UNet's: by finalize_weights)
     SDMI_HIP(hipStreamSynchronize(stream_));
     if (profiling_) prof_flush();
     stager_release();
@@ -1142,6 +1155,7 @@ void Engine::finalize_weights() {
     for (int g = 1; g < kGroups; ++g)
         if (set[g] && missing[g])
             throw Error(SDMI_ERR_WEIGHTS, std::string("finalize_weights: ") + kGroupName[g] + " weights are partially set; missing '" + missing[g]->name + "'");
+    rebuild_folds();                           // the one thing derived from more than one entry (see "LoRA adapters" below)
     SDMI_HIP(hipStreamSynchronize(stream_));   // every packing kernel has run
     stager_release();
     clip_ready_ = total[1] > 0 && set[1] == total[1];
@@ -1154,9 +1168,45 @@ void Engine::finalize_weights() {
 // =============================================================================
 // A merge rewrites packed weights outside any sampling call: W0 (the fp32 master, option keep_masters) + the deltas of the adapters active on a tensor go
 // through launch_lora_merge into a pool buffer, and pack_entry -- the loader's own routine -- packs that buffer.  finalized_ / clip_ready_ / enc_ready_ are
-// not touched, the pinned ring (released by finalize_weights) is not used.  No device tensor is derived from more than one entry at load time (the packed
-// q | k | v regions are three entries' slots side by side, each with its own planes / MXFP8 rows; finalize_weights derives nothing), so re-packing the
-// entry is all there is to re-derive.
+// not touched, the pinned ring (released by finalize_weights) is not used.  ONE kind of device tensor is derived from more than one entry: the folded weights of
+// a fp32 engine's transformer blocks (SpatialW::fold_bt / fold_bias = proj_out x mlp_lin, built by rebuild_folds at the end of finalize_weights).  pack_entry and
+// every other write of one of the three entries clears SpatialW::fold_fresh (fold_touch), a block whose fold is not fresh runs its two launches and never the stale
+// product, and lora_set_scale re-derives the stale folds behind its re-packs, outside any sampling call -- so the packed weights, the folds, get_scale and
+// effective_weight agree whenever a call can run.  Everything else is per entry (the packed q | k | v regions are three entries' slots side by side, each with its
+// own planes / MXFP8 rows): re-packing the entry is all there is to re-derive.
+
+// out = the product of two packed fp32 weights in fp64, rounded once (k_gemm.hip fold_matmul_f64_kernel)
+void Engine::fold_weights(const float* proj_bt, const float* lin_bt, const float* lin_bias, int cout, int cmid, int k_main, float* wf, float* bf) {
+    ProfScope ps(this, PC_OTHER, 2.0 * cout * (double)cmid * k_main, ((double)cout * cmid + (double)cmid * k_main + (double)cout * k_main) * 4.0);
+    ps.set_tag("fold %d,%d,%d", cout, k_main, cmid);
+    SDMI_HIP(launch_fold_matmul_f64(proj_bt, lin_bt, wf, cout, cmid, k_main, cmid, k_main, k_main, stream_));
+    if (lin_bias) SDMI_HIP(launch_fold_matmul_f64(proj_bt, lin_bias, bf, cout, cmid, 1, cmid, 1, 1, stream_));
+    else SDMI_HIP(hipMemsetAsync(bf, 0, (size_t)cout * sizeof(float), stream_));
+}
+
+void Engine::rebuild_folds() {
+    if (bf16_) return;
+    for (SpatialW* s : st_list_) {
+        if (s->fold_fresh || s->fold_entries[0] < 0) continue;
+        bool ready = true;
+        for (int i : s->fold_entries) ready = ready && entries_[(size_t)i].set;
+        const int C = s->c;
+        if (!ready || C % 32 || !split_planes(s->proj_out.bt) || !split_planes(s->mlp_lin.bt)) continue;
+        const size_t w_bytes = (size_t)C * 4 * C * sizeof(float);
+        if (!s->fold_bt) {   // Wf | bf in one allocation, the planes of Wf in a second: a split region, like the packed q | k | v weights
+            char* base = static_cast<char*>(persistent_alloc(w_bytes + (size_t)C * sizeof(float)));
+            weight_allocs_.push_back(base);
+            char* planes = static_cast<char*>(persistent_alloc(w_bytes / 2 * 3));
+            weight_allocs_.push_back(planes);
+            split_regions_.push_back(SplitRegion{base, w_bytes, planes});
+            s->fold_bt = reinterpret_cast<float*>(base);
+            s->fold_bias = reinterpret_cast<float*>(base + w_bytes);
+        }
+        fold_weights(s->proj_out.bt, s->mlp_lin.bt, s->mlp_lin.bias, C, C, 4 * C, s->fold_bt, s->fold_bias);
+        SDMI_HIP(launch_pack_split3(s->fold_bt, const_cast<void*>(split_planes(s->fold_bt)), C, 4 * C, stream_, b3_grouped(C)));
+        s->fold_fresh = true;
+    }
+}
 bool Engine::lora_owned(const sdmi_lora* a) const { return a && std::find(loras_.begin(), loras_.end(), a) != loras_.end(); }
 
 bool Engine::lora_active_on(int entry) const {
@@ -1320,6 +1370,7 @@ void Engine::lora_set_scale(sdmi_lora* a, double scale) {
     size_t done = 0;
     try {
         for (; done < a->targets.size(); ++done) lora_repack(a->targets[done].entry);
+        rebuild_folds();   // the folds the re-packs left stale
         SDMI_HIP(hipStreamSynchronize(stream_));
     } catch (...) {
         // back to the old scale: the targets already re-packed (and the one that failed) are re-packed at it, so that the packed weights, get_scale and
@@ -1328,6 +1379,7 @@ void Engine::lora_set_scale(sdmi_lora* a, double scale) {
         for (size_t i = 0; i <= done && i < a->targets.size(); ++i) {
             try { lora_repack(a->targets[i].entry); } catch (...) {}
         }
+        try { rebuild_folds(); } catch (...) {}   // (a fold that cannot be rebuilt stays stale: its block runs the two launches)
         (void)hipStreamSynchronize(stream_);
         throw;
     }
@@ -1527,6 +1579,7 @@ void Engine::set_option(const std::string& key, const std::string& value) {
     else if (key == "splitk") gopt_.force_splits = std::stoi(value);
     else if (key == "splitk_aux") opt_splitk_aux_ = std::stoi(value);
     else if (key == "skip_slices") opt_skip_slices_ = std::stoi(value);
+    else if (key == "proj_out_fold") opt_proj_out_fold_ = std::stoi(value);
     else if (key == "roctx") roctx_enable(std::stoi(value) != 0);
     else if (key == "fp8_convs") opt_fp8_convs_ = std::stoi(value);
     else if (key == "fp8_min_rows") opt_fp8_min_rows_ = std::stoi(value);
@@ -1845,6 +1898,63 @@ static ConvGemm linear_gemm(const float* A, int rows, const float* bt, const flo
     p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.ups = 0;
     p.ldc = ldc; p.ldr = ldr; p.a_ld = cin; p.b_ld = cin; p.rowvec_stride = 0; p.CS = 32;
     return p;
+}
+
+// conv_pair with a Linear main problem: y = u x bt^T + bias + h x bt_aux^T + bias_aux + resid as ONE split-K plane launch + its reduce.  The transformer block's
+// tail (spatial_transformer, option proj_out_fold): with bt = proj_out x mlp_lin folded at load (rebuild_folds), u the gated MLP hidden state, h the hidden state in
+// front of the MLP and resid the block input, this is proj_out(h + mlp_lin(u)) + x -- proj_out's launch, its reduce where it is split and the write + read of the
+// planes between the two layers are gone.  The residual is the reduce's to add (bias + bias_aux, then the residual: k_gemm.hip).
+bool Engine::linear_pair(const LinearPair& a, bool plan_only) {
+    if (bf16_ || probe_buf_ || a.rows <= 0 || a.cout <= 0 || a.k_main <= 0 || a.k_aux <= 0) return false;
+    if (!plane_gemm(a.k_main, a.cout) || !plane_gemm(a.k_aux, a.cout) || !a.u3 || !a.h3 || (!a.C && !a.C3)) return false;
+    if (gopt_.force_splits > 0 && opt_splitk_aux_ <= 0) return false;   // option splitk alone forces the slices of ordinary launches: those run
+    const int ldc = a.C ? a.ldc : a.cout;
+    ConvGemm p = linear_gemm(nullptr, a.rows, a.bt, a.bias, a.k_main, a.cout, a.C, ldc, a.resid, a.resid ? a.ldr : ldc);
+    p.bias_aux = a.bias_aux;
+    p.Bt3 = split_planes(a.bt); p.Bt3_aux = split_planes(a.bt_aux);
+    if (!p.Bt3 || !p.Bt3_aux) return false;
+    p.A3 = a.u3; p.a3_ld = a.u3_ld; p.A3_aux = a.h3; p.a3_ld_aux = a.h3_ld;
+    p.C3 = a.C3; p.ldc3 = a.ldc3;
+    p.kt_total = a.k_main / 32; p.Cin_aux = a.k_aux; p.kt_total_aux = a.k_aux / 32;
+    p.b3_grouped = b3_grouped(p.N) ? 1 : 0;
+    p.variant = opt_gemm3x_variant_;
+    p.zero_page = zero_page_;
+    if (p.a3_ld < p.kt_total * 192 || p.a3_ld % 192 || p.a3_ld_aux < p.kt_total_aux * 192 || p.a3_ld_aux % 192) return false;
+    // the output conditions of launch_gemm's native plane output, on the reduce's 16-byte path (the only one that writes planes or adds two biases at once)
+    if (!splitk_reduce_vec(p, false) || ((uintptr_t)p.bias_aux & 15) || (p.C3 && (p.N % 32 || p.ldc3 % 192 || p.ldc3 < p.N / 32 * 192))) return false;
+    const GemmPlanIn in = gemm_plan_in(p, 0, -1, 0);
+    if (!in.p_ok) return false;
+    if ((unsigned long long)p.N * (unsigned long long)p.kt_total_aux * 192ull >= 0xFFFFFF00ull || (unsigned long long)a.rows * (unsigned long long)p.a3_ld_aux >= 0xFFFFFF00ull) return false;
+    if (a.measured_only) {
+        char key[80];
+        std::snprintf(key, sizeof key, "%d,%d,%d+%d", p.M, p.N, p.K, a.k_aux);
+        if (!tuning_.pairs.count(key)) return false;
+    }
+    const GemmPairPlan g = plan_gemm_pair(in, a.k_aux, p.kt_total_aux, gopt_, tuning_, opt_splitk_aux_ > 0 ? std::max(gopt_.force_splits, 1) : 0, std::max(opt_splitk_aux_, 0));
+    if (!g.pair) return false;
+    if (plan_only) return true;
+    p.kt_per_split = g.kt_per_split; p.splits = g.splits_main + g.splits_aux; p.z_aux = g.splits_main;
+    if (record_shapes_) {
+        char note[48];
+        std::snprintf(note, sizeof note, " +aux K%d z%d", a.k_aux, p.z_aux);
+        record_choice(p, " fold", g.cfg, note);   // (" pair" names a ResBlock's: conv_pair)
+    }
+    p.slab_stride = (long long)p.M * p.N;
+    Buf slab(this, (size_t)p.splits * p.slab_stride * sizeof(float));
+    p.slabs = slab.f();
+    const double flops = 2.0 * p.M * (double)p.N * ((double)p.K + a.k_aux);
+    const double bytes = (double)p.M * (a.k_main + a.k_aux) * 6.0 + (double)p.N * (p.K + a.k_aux) * 6.0 + (double)p.M * p.N * ((p.C ? 4.0 : 0.0) + (p.C3 ? 6.0 : 0.0) + (p.resid ? 4.0 : 0.0));
+    {
+        ProfScope ps(this, PC_CONV_SPLIT, flops, bytes);
+        ps.set_tag("gemm %d,%d,%d+%d k1+1%s cfg=%d splits=%d+%d", p.M, p.N, p.K, a.k_aux, p.resid ? " resid" : "", g.cfg, g.splits_main, g.splits_aux);
+        SDMI_HIP(launch_conv_gemm3p(p, g.tile.index, stream_));
+    }
+    count_kernel(flops);
+    ProfScope ps(this, PC_SPLITK_REDUCE, 0, (double)(p.splits + 1) * p.slab_stride * 4.0);
+    ps.set_tag("reduce %d,%d,%d+%d k1+1 cfg=%d splits=%d+%d", p.M, p.N, p.K, a.k_aux, g.cfg, g.splits_main, g.splits_aux);
+    SDMI_HIP(launch_splitk_reduce(p, stream_));
+    count_kernel();
+    return true;
 }
 
 void Engine::gemm(const float* A, int a_rows, const float* bt, const float* bias, int cin, int cout, float* C, int ldc,
@@ -2258,8 +2368,9 @@ void Engine::spatial_transformer(const SpatialW& w, const Act& x, Act& y) {
     Act h = new_act(x.n, x.h, x.w, C);
     conv(w.proj_in, g, h, 1, 0, nullptr, 0, nullptr);
     release(g);
-    Act hp = pl ? new_act3(nb, x.h, x.w, C, 2) : Act{};      // the hidden state after the MLP: read by proj_out only
+    Act hp{};                                                 // (pl) the hidden state after the MLP as planes: read by proj_out only
     Act x2{};                                                 // shared prefix: the block input once per half (proj_out's residual)
+    bool folded = false;                                      // mlp_lin + proj_out ran as one paired launch (option proj_out_fold)
     {
         const size_t es = esz();
         const size_t row3 = (size_t)(C / 32) * 192;
@@ -2290,19 +2401,35 @@ void Engine::spatial_transformer(const SpatialW& w, const Act& x, Act& y) {
         const long long cbs = (long long)us_.t_max * C;
         attention(q.f(), C, (long long)hw * C, us_.kc.at(w.ctx_index), C, cbs, us_.vc.at(w.ctx_index), C, cbs, af,
                   C, (long long)hw * C, nb, hw, us_.t_max, heads, d, us_.kv_len_dev, us_.kv_len_host.data(), nullptr, 0, -1, a3, q_prescaled(edt(), d));
-        gemm(af, (int)M, w.attn2.out.bt, w.attn2.out.bias, C, C, h.p, C, h.p, C, -1, 0, a3);
+        // Option proj_out_fold: y = x + proj_out(h + mlp_lin(u)) has no nonlinearity between its two layers, so with Wf = proj_out x mlp_lin folded at load
+        // (rebuild_folds) it is y = x + Wf u + proj_out h + (bf + b_proj): ONE paired launch (linear_pair) whose extra K slices carry proj_out h.  h is then needed
+        // as planes: the cross attention's output projection writes them next to its fp32 result.  A block whose fold is not fresh, or whose shape the planner does
+        // not pair, runs the two launches.
+        const Act& xr = share ? x2 : x;
+        std::unique_ptr<Buf> h3;
+        if (pl && opt_proj_out_fold_ && w.fold_fresh) h3.reset(new Buf(this, (size_t)M * row3));
+        void* const h3p = h3 ? h3->p : nullptr;
+        LinearPair lp{h3p /* (for the plan: any plane buffer) */, (int)(4 * row3), w.fold_bt, w.fold_bias, 4 * C, h3p, (int)row3, w.proj_out.bt, w.proj_out.bias, C,
+                      (int)M, C, xr.p, xr.stride(), y.p, y.stride(), y.p3, y.ld3, opt_proj_out_fold_ == 2};
+        const bool fold = h3p && xr.p && !xr.dt && !y.dt && xr.rows() == M && xr.c == C && y.rows() == M && y.c == C && linear_pair(lp, /*plan_only=*/true);
+        gemm(af, (int)M, w.attn2.out.bt, w.attn2.out.bias, C, C, h.p, C, h.p, C, -1, 0, a3, fold ? h3p : nullptr);
         // GEGLU MLP
         layer_norm(w.ln3, h.p, M, lnf, -1, ln3);
         {
             Buf u(this, pl ? (size_t)M * 4 * row3 : (size_t)M * 4 * C * es);
             gemm_geglu(lnf, M, w.geglu_proj.bt, w.geglu_proj.bias, C, 4 * C, pl ? nullptr : u.f(), -1, ln3, pl ? u.p : nullptr);
-            if (pl) gemm(nullptr, (int)M, w.mlp_lin.bt, w.mlp_lin.bias, 4 * C, C, nullptr, C, h.p, C, -1, 0, u.p, hp.p3);   // h + mlp -> planes only
+            lp.u3 = u.p;
+            if (fold && linear_pair(lp)) folded = true;
+            else if (pl) {
+                hp = new_act3(nb, x.h, x.w, C, 2);
+                gemm(nullptr, (int)M, w.mlp_lin.bt, w.mlp_lin.bias, 4 * C, C, nullptr, C, h.p, C, -1, 0, u.p, hp.p3);   // h + mlp -> planes only
+            }
             else gemm(u.f(), (int)M, w.mlp_lin.bt, w.mlp_lin.bias, 4 * C, C, h.p, C, h.p, C);
         }
     }
     const Act& xr = share ? x2 : x;
-    if (pl) { conv(w.proj_out, hp, y, 1, 0, nullptr, 0, &xr); release(hp); }
-    else conv(w.proj_out, h, y, 1, 0, nullptr, 0, &xr);
+    if (pl && !folded) { conv(w.proj_out, hp, y, 1, 0, nullptr, 0, &xr); release(hp); }
+    else if (!folded) conv(w.proj_out, h, y, 1, 0, nullptr, 0, &xr);
     release(h);
     if (share) release(x2);
 }
@@ -3813,6 +3940,50 @@ void Engine::op_geglu_forward(const float* x, const float* wt, const float* bias
         return;
     }
     gemm_geglu(x, rows, bt.f(), bias, cin, hidden, out, 0);
+}
+
+// out = u x w_main + b_main + h x w_aux + b_aux + resid as Engine::spatial_transformer computes the tail of a transformer block: both inputs as planes, option
+// proj_out_fold = 1 -> linear_pair (an error where it declines: no quiet other path), 0 -> two launches (the auxiliary Linear with the residual, then the main one with
+// that as its residual).  The result is kept at rows out_ld floats (planes: out_ld / 32 * 192 bytes) apart and returned dense.
+void Engine::op_linear_pair(const float* u, const float* h, const float* w_main, const float* b_main, const float* w_aux, const float* b_aux, const float* resid, int resid_ld,
+                            int rows, int k_main, int k_aux, int cout, int out_ld, float* out, float* out3) {
+    if (rows <= 0 || k_main <= 0 || k_aux <= 0 || cout <= 0) throw Error(SDMI_ERR_INVALID, "linear_pair: bad shape");
+    if (bf16_ || !plane_gemm(k_main, cout) || !plane_gemm(k_aux, cout)) throw Error(SDMI_ERR_UNSUPPORTED, "linear_pair: the fp32 plane kernels only (in_features in multiples of 32)");
+    if (!out_ld) out_ld = cout;
+    if (out_ld < cout || (!out && !out3)) throw Error(SDMI_ERR_INVALID, "linear_pair: out_ld below cout, or no output asked for");
+    if (out3 && (cout % 32 || out_ld % 32)) throw Error(SDMI_ERR_UNSUPPORTED, "linear_pair: a plane output needs cout and out_ld in multiples of 32");
+    Buf bt_m(this, (size_t)cout * k_main * 4), bt_a(this, (size_t)cout * k_aux * 4);
+    SDMI_HIP(launch_pack_linear_weight(w_main, bt_m.f(), k_main, cout, stream_));
+    SDMI_HIP(launch_pack_linear_weight(w_aux, bt_a.f(), k_aux, cout, stream_));
+    TempSplit pm(this, bt_m.f(), cout, k_main), pa(this, bt_a.f(), cout, k_aux);
+    const int u_ld = k_main / 32 * 192, h_ld = k_aux / 32 * 192, ld3 = out_ld / 32 * 192;
+    Buf u3(this, (size_t)rows * u_ld), h3(this, (size_t)rows * h_ld);
+    SDMI_HIP(launch_split3_rows(u, u3.p, rows, k_main, k_main, u_ld, stream_));
+    SDMI_HIP(launch_split3_rows(h, h3.p, rows, k_aux, k_aux, h_ld, stream_));
+    std::unique_ptr<Buf> y, y3;
+    if (out) y.reset(new Buf(this, (size_t)rows * out_ld * 4));
+    if (out3) y3.reset(new Buf(this, (size_t)rows * ld3));
+    if (opt_proj_out_fold_) {
+        const LinearPair lp{u3.p, u_ld, bt_m.f(), b_main, k_main, h3.p, h_ld, bt_a.f(), b_aux, k_aux, rows, cout, resid, resid_ld ? resid_ld : cout,
+                            y ? y->f() : nullptr, out_ld, y3 ? y3->p : nullptr, ld3};
+        if (!linear_pair(lp)) throw Error(SDMI_ERR_UNSUPPORTED, "linear_pair: this shape / these options do not pair (proj_out_fold=0 runs the two launches)");
+    } else {
+        if (out_ld != cout) throw Error(SDMI_ERR_UNSUPPORTED, "linear_pair: the two launches keep the result dense (out_ld = cout)");
+        Buf t(this, (size_t)rows * cout * 4);
+        gemm(nullptr, rows, bt_a.f(), b_aux, k_aux, cout, t.f(), cout, resid, resid_ld ? resid_ld : cout, 0, 0, h3.p);
+        gemm(nullptr, rows, bt_m.f(), b_main, k_main, cout, y ? y->f() : nullptr, cout, t.f(), cout, 0, 0, u3.p, y3 ? y3->p : nullptr);
+    }
+    if (y) SDMI_HIP(hipMemcpy2DAsync(out, (size_t)cout * 4, y->p, (size_t)out_ld * 4, (size_t)cout * 4, (size_t)rows, hipMemcpyDeviceToDevice, stream_));
+    if (y3) SDMI_HIP(launch_join3_rows(y3->p, out3, rows, cout, ld3, cout, stream_));
+}
+
+void Engine::op_linear_fold(const float* w_lin, const float* b_lin, const float* w_proj, int k_main, int cmid, int cout, float* wf, float* bf) {
+    if (k_main <= 0 || cmid <= 0 || cout <= 0) throw Error(SDMI_ERR_INVALID, "linear_fold: bad shape");
+    if (!(cmid % 32 == 0 || (cmid < 32 && cmid % 4 == 0))) throw Error(SDMI_ERR_UNSUPPORTED, "linear_fold: the inner width must be a multiple of 32, or < 32 and a multiple of 4");
+    Buf bt_l(this, (size_t)cmid * k_main * 4), bt_p(this, (size_t)cout * cmid * 4);
+    SDMI_HIP(launch_pack_linear_weight(w_lin, bt_l.f(), k_main, cmid, stream_));     // [cmid][k_main]
+    SDMI_HIP(launch_pack_conv_weight(w_proj, bt_p.f(), cout, cmid, 1, 1, stream_));   // [cout][cmid]
+    fold_weights(bt_p.f(), bt_l.f(), b_lin, cout, cmid, k_main, wf, bf);
 }
 
 void Engine::op_geglu(const float* proj, int rows, int hidden, float* out) {

@@ -112,6 +112,12 @@ struct MhaW { LinW q, k, v, out; };
 struct SpatialW {  // SpatialTransformer + TransformerBlock (unet/mod.rs:454-527)
     NormW norm; ConvW proj_in, proj_out; NormW ln1, ln2, ln3; MhaW attn1, attn2; LinW geglu_proj, mlp_lin;
     int c = 0, ctx_index = -1;
+    // fp32 engine (option proj_out_fold; Engine::rebuild_folds): fold_bt = proj_out x mlp_lin as a packed Linear weight [c][4c] with its planes, fold_bias =
+    // proj_out x mlp_lin.bias [c].  fold_fresh: both are the product of what the three entries fold_entries (mlp_lin weight and bias, proj_out weight) hold NOW;
+    // every re-pack or re-set of one of them clears it, and a block whose fold is not fresh runs mlp_lin and proj_out as two launches.
+    float* fold_bt = nullptr; float* fold_bias = nullptr;
+    bool fold_fresh = false;
+    int fold_entries[3] = {-1, -1, -1};
 };
 enum BlockKind { BK_CONV, BK_DOWN, BK_RES, BK_RES_ST, BK_RES_UP, BK_RES_ST_UP };
 struct UBlock { BlockKind kind; int cin, cout; ConvW conv; ResW res; SpatialW st; ConvW up; };
@@ -134,6 +140,7 @@ struct WeightEntry {
     float** dsts = nullptr;
     float pre_scale = 1.f;    // the tensor is multiplied by this in fp32 before it is packed (bf16 / MXFP8 query projections: attn_bf16_q_scale)
     bool set = false;
+    int fold_st = -1;         // index in st_list_ of the SpatialTransformer whose folded weights (SpatialW::fold_bt) are derived from this entry; -1: none
     float* master = nullptr;  // option keep_masters, kind 0 / 1: the fp32 tensor as the packing kernels read it (reference layout, a conv_in's input channels padded by padded_cin, before pre_scale)
 };
 
@@ -273,6 +280,13 @@ public:
     // the tail of a ResBlock with a shortcut (tests: sdmi_op_conv2d_pair): conv3x3(h, w_out) + b_out + conv1x1(x, w_skip) + b_skip; out3: the planes output, joined
     void op_conv2d_pair(const float* x, const float* h, const float* w_skip, const float* b_skip, const float* w_out, const float* b_out, int n, int cin_x, int cout,
                         int hh, int wd, float* out, float* out3);
+    // tests (sdmi_op_linear_pair): out [rows][cout] = u [rows][k_main] x w_main [k_main][cout] + b_main + h [rows][k_aux] x w_aux [k_aux][cout] + b_aux + resid, the
+    // inputs as planes; option proj_out_fold = 1: linear_pair (an error where it declines), 0: two launches.  resid_ld / out_ld (0: cout): the row strides the engine
+    // keeps the residual and the result at; out (may be null: planes only) / out3 (may be null): the fp32 result / the plane output of the same launch, joined
+    void op_linear_pair(const float* u, const float* h, const float* w_main, const float* b_main, const float* w_aux, const float* b_aux, const float* resid, int resid_ld,
+                        int rows, int k_main, int k_aux, int cout, int out_ld, float* out, float* out3);
+    // tests (sdmi_op_linear_fold): w_lin [k_main][cmid] / b_lin [cmid] (a Linear in the reference layout), w_proj [cout][cmid] (a 1x1 convolution) -> wf [cout][k_main], bf [cout]
+    void op_linear_fold(const float* w_lin, const float* b_lin, const float* w_proj, int k_main, int cmid, int cout, float* wf, float* bf);
     void op_geglu(const float* proj, int rows, int hidden, float* out);
     // the same operators on channel-slice VIEWS, built with slice() on real Acts as unet_run builds the halves of a Tensor::cat (tests: sdmi_op_*_view).
     // xp: the input's parent [rows][in_ld] fp32 NHWC on the device (the slice's columns hold x, the others the caller's filler); yp: the output's
@@ -410,6 +424,21 @@ private:
               const Act* resid, bool pad_br = false);
     // conv3x3(h, w_out) + conv1x1(x, w_skip) + both biases as one split-K plane launch (ConvGemm::z_aux) + reduce; false: not launched (see engine.cpp)
     bool conv_pair(const ConvW& w_out, const Act& h, const ConvW& w_skip, const Act& x, Act& y);
+    // conv_pair for a Linear main problem: C / C3 [rows][cout] = u x bt^T + bias + h x bt_aux^T + bias_aux + resid as one split-K plane launch + reduce.  u3 / h3: the
+    // two activation matrices as planes (pixels u3_ld / h3_ld bytes apart), bt [cout][k_main] / bt_aux [cout][k_aux] packed weights with planes, resid (may be null)
+    // rows ldr floats apart, C and / or C3 with their own strides.  false: not launched, in the situations conv_pair declines in.  plan_only: nothing is launched
+    // either way; true = a call with these arguments would launch.
+    struct LinearPair {
+        const void* u3; int u3_ld; const float* bt; const float* bias; int k_main;
+        const void* h3; int h3_ld; const float* bt_aux; const float* bias_aux; int k_aux;
+        int rows, cout; const float* resid; int ldr; float* C; int ldc; void* C3; int ldc3;
+        bool measured_only = false;   // decline a shape without a row in the pairs table (option proj_out_fold = 2)
+    };
+    bool linear_pair(const LinearPair& a, bool plan_only = false);
+    // wf [cout][k_main] = proj_bt [cout][cmid] x lin_bt [cmid][k_main], bf [cout] = proj_bt x lin_bias (zeros without one): fp64 accumulation, rounded once
+    void fold_weights(const float* proj_bt, const float* lin_bt, const float* lin_bias, int cout, int cmid, int k_main, float* wf, float* bf);
+    void rebuild_folds();                        // every SpatialW whose fold is not fresh and whose three entries are set (precision 0 only); enqueues on stream_
+    void fold_touch(const WeightEntry& e) { if (e.fold_st >= 0) st_list_[(size_t)e.fold_st]->fold_fresh = false; }
     static Act slice(const Act& parent, int c_off, int c);   // channel-slice view
     // A3 / C3: the input / output as three bf16 planes (dense rows: 192 bytes per 32 channels); A and / or C may then be null
     void gemm(const float* A, int a_rows, const float* bt, const float* bias, int cin, int cout, float* C, int ldc,
@@ -557,6 +586,9 @@ private:
     AttnPlanOpts aopt_;              // options attn_split, attn_bf16, attn_bf16_variant, attn_pack_tail, attn_kv_splits, attn_kv_prefer8 (attn_plan.hpp)
     int opt_cfg_share_ = 1;          // sample_latent: the part of the UNet in front of the first cross attention is computed once for the two identical halves of a CFG step (unet_run)
     int opt_skip_slices_ = 1;        // fp32 ResBlocks with a 1x1 shortcut: 1 = the shortcut runs on extra K slices of conv_out's split-K launch (conv_pair); 0 = its own launches
+    // fp32 transformer blocks: mlp_lin + proj_out as one paired launch on the folded weight (linear_pair).  0 = their own launches; 1 = every
+    // shape the pair planner pairs; 2 = only shapes with a measured row in the pairs table (an unmeasured pair has not been shown to beat its two launches)
+    int opt_proj_out_fold_ = 2;
     int opt_splitk_aux_ = 0;         // tests (with splitk): requested slice count of the auxiliary problem of a paired launch; 0 = planned
     int opt_op_resid_ = 0;           // tests: op_conv2d / op_linear add their input as the residual (cin == cout) through the GEMM epilogue
     int opt_op_misalign_ = 0;        // tests: stage_epi starts the device copies of bias, time-embedding row and residual one element past an aligned address

@@ -164,11 +164,42 @@ __global__ void pack_linear_weight_kernel(const float* __restrict__ w, float* __
     }
 }
 
+// ---- folded weights ---------------------------------------------------------------------
+// out[n][k] = fp32(sum_c a[n][c] b[c][k]): the product of two packed fp32 weights (Engine::rebuild_folds: proj_out [C][C] x mlp_lin [C][4C], and with K = 1 the
+// bias proj_out x mlp_lin.bias), accumulated in fp64 in ascending c and rounded once.  Runs at load and behind a LoRA re-merge only: 16 x 16 outputs per workgroup,
+// one per thread, the operands through LDS.
+__global__ __launch_bounds__(256) void fold_matmul_f64_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int N, int Cn, int K,
+                                                             long long lda, long long ldb, long long ldo) {
+    __shared__ float ta[16][17], tb[16][17];
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int n = blockIdx.y * 16 + ty, k = blockIdx.x * 16 + tx;
+    double acc = 0.0;
+    for (int c0 = 0; c0 < Cn; c0 += 16) {
+        ta[ty][tx] = (n < N && c0 + tx < Cn) ? a[(long long)n * lda + c0 + tx] : 0.f;
+        tb[ty][tx] = (c0 + ty < Cn && k < K) ? b[(long long)(c0 + ty) * ldb + k] : 0.f;
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < 16; ++c) acc += (double)ta[ty][c] * (double)tb[c][tx];
+        __syncthreads();
+    }
+    if (n < N && k < K) out[(long long)n * ldo + k] = (float)acc;
+}
+
 // ---- host side ----------------------------------------------------------------------
+hipError_t launch_fold_matmul_f64(const float* a, const float* b, float* out, int N, int Cn, int K, long long lda, long long ldb, long long ldo, hipStream_t s) {
+    if (N <= 0 || Cn <= 0 || K <= 0 || lda < Cn || ldb < K || ldo < K) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((K + 15) / 16), (unsigned)((N + 15) / 16));
+    if (grid.y > 65535u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fold_matmul_f64_kernel, grid, dim3(256), 0, s, a, b, out, N, Cn, K, lda, ldb, ldo);
+    return hipGetLastError();
+}
+
 hipError_t launch_splitk_reduce(const ConvGemm& p, hipStream_t stream) {
     const bool vec = splitk_reduce_vec(p, false);
     if (!vec && (p.C3 || !p.C)) return hipErrorInvalidValue;   // the plane output is part of the 16-byte path only
-    if (p.z_aux && (p.resid || p.rowvec)) return hipErrorInvalidValue;   // a paired launch: the shortcut IS the residual
+    // a paired launch: bias + bias_aux, then the residual (Engine::linear_pair: the block input behind the folded proj_out); a ResBlock's shortcut IS its residual.
+    // No paired launch carries a time-embedding row.
+    if (p.z_aux && p.rowvec) return hipErrorInvalidValue;
     if (p.bias_aux && vec && ((uintptr_t)p.bias_aux & 15)) return hipErrorInvalidValue;
     const long long work = ((long long)p.M * p.N + 3) / 4;
     // lanes per output: enough threads to cover the chip (>= 256 K) while every lane still has two slabs to sum

@@ -365,7 +365,7 @@ hipError_t launch_conv_gemm3p(const ConvGemm& p, int cfg, hipStream_t stream) {
     if (p.z_aux) {
         // the auxiliary problem reads source pixel = output pixel: the main one must be stride 1 without upsampling; same checks on its operands; slices [0, z_aux)
         // are exactly the main problem's and [z_aux, splits) exactly the auxiliary one's -- none empty, none straddling, no k tile left out
-        if (p.stride != 1 || p.ups != 0 || p.Hs != p.Ho || p.Ws != p.Wo || p.geglu || p.probe || p.rowvec || p.resid) return hipErrorInvalidValue;
+        if (p.stride != 1 || p.ups != 0 || p.Hs != p.Ho || p.Ws != p.Wo || p.geglu || p.probe || p.rowvec) return hipErrorInvalidValue;   // (a residual is the reduce's to add: the slices write raw slabs)
         if (!p.A3_aux || !p.Bt3_aux || p.Cin_aux <= 0 || (p.Cin_aux % 32) || p.kt_total_aux != p.Cin_aux / 32 || p.a3_ld_aux < p.kt_total_aux * 192 || (p.a3_ld_aux % 192)) return hipErrorInvalidValue;
         if (p.kt_per_split <= 0 || p.z_aux != (p.kt_total + p.kt_per_split - 1) / p.kt_per_split ||
             p.splits - p.z_aux != (p.kt_total_aux + p.kt_per_split - 1) / p.kt_per_split || !p.slabs) return hipErrorInvalidValue;

@@ -63,7 +63,8 @@ struct ConvGemm {
     // same M output rows and the same N, its own activation planes and weight planes -- the ResBlock shortcut riding in conv_out's launch (Engine::conv_pair).  The main
     // problem must be stride 1 without upsampling (source pixel = output pixel).  Slices [0, z_aux) cover the kt_total k tiles of the main problem, slice z >= z_aux the
     // k tiles [(z - z_aux) kt_per_split, ...) of the kt_total_aux auxiliary ones: no slice holds tiles of both.  Slabs are indexed by z; launch_splitk_reduce sums all
-    // `splits` of them in slice order and adds bias + bias_aux.
+    // `splits` of them in slice order and adds bias + bias_aux, then the residual where there is one (Engine::linear_pair; a ResBlock's pair has none: its
+    // shortcut IS the residual).  The main problem may be a Linear layer (NB = 1, Hs = 1, Ws = rows, one tap).
     const void* A3_aux;         // [NB][Hs][Ws][a3_ld_aux / 192 slices][3][32]
     int a3_ld_aux;
     const void* Bt3_aux;        // [N][Cin_aux / 32][3][32], in the layout b3_grouped names (it depends on N only)
@@ -136,6 +137,8 @@ __host__ __device__ inline bool splitk_reduce_vec(const ConvGemm& p, bool bf16) 
 // weight packing (done once at load)
 hipError_t launch_pack_conv_weight(const float* w_oihw, float* bt, int cout, int cin, int kh, int kw, hipStream_t s);
 hipError_t launch_pack_linear_weight(const float* w_in_out, float* bt, int cin, int cout, hipStream_t s);
+// out [N][K] (rows ldo apart) = fp32(a [N][Cn] x b [Cn][K]) with fp64 accumulation, rounded once: the folded weights of Engine::rebuild_folds (load time only)
+hipError_t launch_fold_matmul_f64(const float* a, const float* b, float* out, int N, int Cn, int K, long long lda, long long ldb, long long ldo, hipStream_t s);
 
 // ---- flash-style attention on fp32 MFMA ---------------------------------------
 struct AttnParams {

@@ -1392,6 +1392,46 @@ int sdmi_op_linear_epilogue(sdmi_ctx* ctx, const float* x, const float* weight, 
     });
 }
 
+int sdmi_op_linear_pair(sdmi_ctx* ctx, const float* u, const float* h, const float* w_main, const float* b_main, const float* w_aux, const float* b_aux,
+                        const float* resid, int32_t resid_ld, int32_t rows, int32_t k_main, int32_t k_aux, int32_t cout, int32_t out_ld, float* out, float* out_planes) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (rows <= 0 || k_main <= 0 || k_aux <= 0 || cout <= 0 || resid_ld < 0 || out_ld < 0 || (resid_ld && resid_ld < cout) || (out_ld && out_ld < cout))
+            throw Error(SDMI_ERR_INVALID, "linear_pair: bad shape");
+        if (!out && !out_planes) throw Error(SDMI_ERR_INVALID, "linear_pair: no output pointer");
+        Engine::Call call(e);
+        DevIn du(e, u, (size_t)rows * k_main * sizeof(float)), dh(e, h, (size_t)rows * k_aux * sizeof(float));
+        DevIn dwm(e, w_main, (size_t)k_main * cout * sizeof(float)), dwa(e, w_aux, (size_t)k_aux * cout * sizeof(float));
+        std::unique_ptr<Engine::Buf> dbm, dba, dr;
+        const float* bm = b_main ? e.stage_epi(dbm, b_main, 1, cout, cout, 0) : nullptr;
+        const float* ba = b_aux ? e.stage_epi(dba, b_aux, 1, cout, cout, 0) : nullptr;
+        const float* r = resid ? e.stage_epi(dr, resid, rows, cout, resid_ld ? resid_ld : cout, 0) : nullptr;
+        std::unique_ptr<DevOut> dout, dout3;
+        if (out) dout.reset(new DevOut(e, out, (size_t)rows * cout * sizeof(float)));
+        if (out_planes) dout3.reset(new DevOut(e, out_planes, (size_t)rows * cout * sizeof(float)));
+        e.op_linear_pair(du.f(), dh.f(), dwm.f(), bm, dwa.f(), ba, r, resid_ld, rows, k_main, k_aux, cout, out_ld, dout ? dout->f() : nullptr, dout3 ? dout3->f() : nullptr);
+        call.finish();
+        if (dout) dout->fetch();
+        if (dout3) dout3->fetch();
+    });
+}
+
+int sdmi_op_linear_fold(sdmi_ctx* ctx, const float* w_lin, const float* b_lin, const float* w_proj, int32_t k_main, int32_t cmid, int32_t cout, float* wf, float* bf) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (k_main <= 0 || cmid <= 0 || cout <= 0) throw Error(SDMI_ERR_INVALID, "linear_fold: bad shape");
+        Engine::Call call(e);
+        DevIn dl(e, w_lin, (size_t)k_main * cmid * sizeof(float)), dp(e, w_proj, (size_t)cout * cmid * sizeof(float));
+        std::unique_ptr<DevIn> db;
+        if (b_lin) db.reset(new DevIn(e, b_lin, (size_t)cmid * sizeof(float)));
+        DevOut dwf(e, wf, (size_t)cout * k_main * sizeof(float)), dbf(e, bf, (size_t)cout * sizeof(float));
+        e.op_linear_fold(dl.f(), db ? db->f() : nullptr, dp.f(), k_main, cmid, cout, dwf.f(), dbf.f());
+        call.finish();
+        dwf.fetch();
+        dbf.fetch();
+    });
+}
+
 // ---- the operators on channel-slice views ---------------------------------------------------------------------------------
 namespace {
 // x [n,c,h,w] -> the host image of its parent: NHWC rows ld wide, x at columns [off, off + c), `fill` elsewhere

@@ -1239,6 +1239,46 @@ class StableDiffusion:
                                             n, cin_x, cout, hh, ww, _fp(out), None if out3 is None else _fp(out3)))
         return (out, out3) if planes else out
 
+    def op_linear_pair(self, u, h, w_main, b_main, w_aux, b_aux, resid=None, resid_ld=0, out_ld=0, out="f32"):
+        """u @ w_main + b_main + h @ w_aux + b_aux + resid, the tail of a transformer block with proj_out folded into the MLP's output Linear (tests; precision 0).
+        Option proj_out_fold=1: one split-K launch carrying h @ w_aux on extra K slices; 0: two launches.  resid_ld / out_ld (0: cout): the row strides the engine
+        keeps the residual and the result at.  out: "f32", "planes" (the bf16-plane output, joined) or "both" (a pair)."""
+        u = _f32(u)
+        h = _f32(h)
+        rows, k_main = u.shape
+        k_aux = h.shape[1]
+        if h.shape[0] != rows:
+            raise ValueError("linear_pair: u and h must have the same rows")
+        wm = _f32(w_main)
+        cout = wm.shape[1]
+        wm = _f32(wm, (k_main, cout))
+        wa = _f32(w_aux, (k_aux, cout))
+        bm = None if b_main is None else _f32(b_main, (cout,))
+        ba = None if b_aux is None else _f32(b_aux, (cout,))
+        r = None if resid is None else _f32(resid, (rows, cout))
+        if out not in ("f32", "planes", "both"):
+            raise ValueError("linear_pair: out is 'f32', 'planes' or 'both'")
+        o = np.empty((rows, cout), dtype=np.float32) if out != "planes" else None
+        o3 = np.empty((rows, cout), dtype=np.float32) if out != "f32" else None
+        check(self._lib.sdmi_op_linear_pair(self._ctx, _fp(u), _fp(h), _fp(wm), None if bm is None else _fp(bm), _fp(wa), None if ba is None else _fp(ba),
+                                            None if r is None else _fp(r), resid_ld, rows, k_main, k_aux, cout, out_ld, None if o is None else _fp(o),
+                                            None if o3 is None else _fp(o3)))
+        return o if out == "f32" else o3 if out == "planes" else (o, o3)
+
+    def op_linear_fold(self, w_lin, b_lin, w_proj):
+        """(wf [cout, k_main], bf [cout]) = (w_proj @ w_lin.T, w_proj @ b_lin) through the loader's fold kernel (tests): w_lin [k_main, cmid] a Linear weight in the
+        reference layout, b_lin [cmid] or None, w_proj [cout, cmid] a 1x1 convolution."""
+        wl = _f32(w_lin)
+        k_main, cmid = wl.shape
+        wp = _f32(w_proj)
+        cout = wp.shape[0]
+        wp = _f32(wp, (cout, cmid))
+        bl = None if b_lin is None else _f32(b_lin, (cmid,))
+        wf = np.empty((cout, k_main), dtype=np.float32)
+        bf = np.empty((cout,), dtype=np.float32)
+        check(self._lib.sdmi_op_linear_fold(self._ctx, _fp(wl), None if bl is None else _fp(bl), _fp(wp), k_main, cmid, cout, _fp(wf), _fp(bf)))
+        return wf, bf
+
     def op_linear_epilogue(self, x, weight, bias=None, resid=None, resid_ld=0):
         """op_linear + resid [rows, cout] through the GEMM epilogue (tests); resid_ld (0: cout) is the row stride the engine keeps it at."""
         x = _f32(x)
