@@ -1990,7 +1990,8 @@ void Engine::gemm_geglu(const float* x, long long rows, const float* bt, const f
         {
             ProfScope ps(this, PC_GEGLU, 0, (double)rows * hidden * (8.0 + (out3 ? 6.0 : 4.0)));
             if (out3) SDMI_HIP(launch_geglu_planes(proj.f(), out3, rows, hidden, stream_));
-            else SDMI_HIP(launch_geglu(proj.f(), out, rows, hidden, stream_));
+            // (both asked for -- op_geglu_forward with geglu_fuse = 8: the fused launch above writes both, so must this form; the model asks for one)
+            if (out) { SDMI_HIP(launch_geglu(proj.f(), out, rows, hidden, stream_)); if (out3) count_kernel(); }
         }
         count_kernel();
         return;
