@@ -768,7 +768,9 @@ int sdmi_op_timestep_embedding(sdmi_ctx* ctx, int32_t t, int32_t dim, float* out
  * profiling and dump switches -- is DESIGN.md section 11, one line per key. */
 int sdmi_set_option(sdmi_ctx* ctx, const char* key, const char* value);
 /* time (ms, HIP events on the context stream) and kernel count of the last
- * hot-path call; flops = algorithmic FLOPs it executed (2*MAC of conv/GEMM/attention). */
+ * hot-path call; flops = the FLOPs it EXECUTED (2*MAC of conv/GEMM/attention as launched: an
+ * up-convolution run as four folded 2x2 phase convolutions -- option ups_phase -- counts 4/9 of the
+ * layer's 2*MAC, a paired launch both of its problems). */
 int sdmi_last_call_stats(sdmi_ctx* ctx, double* gpu_ms, int64_t* n_kernels, double* flops);
 /* Per-kernel-class timing collected while option "profile" = "1": HIP events around every
  * launch on the context stream.  cls: 0 conv_gemm (implicit-GEMM conv/linear), 1 splitk_reduce,

@@ -478,11 +478,19 @@ void Engine::build_model() {
                 if (s.kind == BK_RES_UP || s.kind == BK_RES_ST_UP) { conv(b.up, path + "/upsample/conv", s.cout, s.cout, 3); fp8_copy(b.up, path + "/upsample/conv/weight"); }
         }
     };
+    // an up-convolution: its phase weights are derived from its weight entry (rebuild_folds)
+    auto reg_up = [&](ConvW& w, const std::string& weight_name) {
+        w.up_entry = entry_index_.at(weight_name);
+        entries_[(size_t)w.up_entry].fold_up = (int)up_list_.size();
+        up_list_.push_back(&w);
+    };
     for (int i = 0; i < 12; ++i) def_block(in_blocks_[i], in_spec[i], "unet/input_blocks");
     res(mid_res1_, "unet/middle_block/res1", c4, c4, true);
     spatial(mid_st_, "unet/middle_block/transformer", c4);
     res(mid_res2_, "unet/middle_block/res2", c4, c4, true);
     for (int i = 0; i < 12; ++i) def_block(out_blocks_[i], out_spec[i], "unet/output_blocks");
+    for (int i = 0; i < 12; ++i)
+        if (out_spec[i].kind == BK_RES_UP || out_spec[i].kind == BK_RES_ST_UP) reg_up(out_blocks_[i].up, std::string("unet/output_blocks/") + out_spec[i].name + "/upsample/conv/weight");
     norm(unet_norm_out_, "unet/norm_out", c1);
     conv(unet_conv_out_, "unet/conv_out", c1, 4, 3);
 
@@ -524,7 +532,7 @@ void Engine::build_model() {
         res(b.res[0], bp + "/res1", b.cin, b.cout, false);
         res(b.res[1], bp + "/res2", b.cout, b.cout, false);
         res(b.res[2], bp + "/res3", b.cout, b.cout, false);
-        if (b.has_up) conv(b.upsampler, bp + "/upsampler", b.cout, b.cout, 3);
+        if (b.has_up) { conv(b.upsampler, bp + "/upsampler", b.cout, b.cout, 3); reg_up(b.upsampler, bp + "/upsampler/weight"); }
     }
     norm(dec_norm_out_, "autoencoder/decoder/norm_out", vc);
     conv(dec_conv_out_, "autoencoder/decoder/conv_out", vc, 3, 3);
@@ -1206,7 +1214,43 @@ void Engine::rebuild_folds() {
         SDMI_HIP(launch_pack_split3(s->fold_bt, const_cast<void*>(split_planes(s->fold_bt)), C, 4 * C, stream_, b3_grouped(C)));
         s->fold_fresh = true;
     }
+    // the phase weights of the up-convolutions (ConvW::up3): derived from ONE entry each, but not by pack_entry -- they live here so that one rule covers both kinds of
+    // derived tensor (stale after any write of the entry, re-derived at finalize_weights and behind lora_set_scale, never run stale)
+    for (ConvW* w : up_list_) {
+        if (w->up_fresh || w->up_entry < 0 || !entries_[(size_t)w->up_entry].set || !opt_ups_phase_ || !up_fold_supported(w->cin, w->cout) || !split_planes(w->bt)) continue;
+        if (!w->up3) {
+            w->up3 = persistent_alloc((size_t)w->cout * w->cin * 96);
+            weight_allocs_.push_back(w->up3);
+        }
+        build_up_fold(w->bt, w->up3, w->cout, w->cin);
+        w->up_fresh = true;
+    }
 }
+
+// what the plane kernel's phase mode reads: fp32 weights with planes, whole 32-channel slices, 32-bit piece offsets within a phase image
+bool Engine::up_fold_supported(int cin, int cout) const {
+    return !bf16_ && cin % 32 == 0 && cout >= 32 && (unsigned long long)cout * (unsigned long long)(cin / 8) * 192ull < 0xFFFFFF00ull;
+}
+
+void Engine::build_up_fold(const float* bt, void* up3, int cout, int cin) {
+    // the fp32 image of a phase [cout][4 cin] is needed only until its planes exist: one pool buffer, reused by the four phases (stream order)
+    Buf img(this, (size_t)4 * cout * cin * sizeof(float));
+    ProfScope ps(this, PC_OTHER, 0, ((double)9 + 16 + 16 + 24) * cout * cin * 4.0);
+    ps.set_tag("fold ups_phase %d,%d", cout, cin);
+    for (int ph = 0; ph < 4; ++ph) {
+        SDMI_HIP(launch_fold_ups_phase_f64(bt, img.f(), cout, cin, ph, 1, stream_));
+        // each image is a weight of cout rows in the layout b3_grouped(cout) names -- the rule the launch reads the layout by
+        SDMI_HIP(launch_pack_split3(img.f(), static_cast<char*>(up3) + (size_t)ph * cout * cin * 24, cout, 4 * cin, stream_, b3_grouped(cout)));
+    }
+}
+
+Engine::TempUpFold::TempUpFold(Engine* e_, ConvW& w, int stride, int ups) : e(e_) {
+    if (!e->opt_ups_phase_ || w.dt || w.k != 3 || stride != 1 || ups != 1 || !e->up_fold_supported(w.cin, w.cout) || !e->split_planes(w.bt)) return;
+    up3 = e->pool_.alloc((size_t)w.cout * w.cin * 96);
+    try { e->build_up_fold(w.bt, up3, w.cout, w.cin); } catch (...) { e->pool_.free(up3); up3 = nullptr; throw; }
+    w.up3 = up3; w.up_fresh = true;
+}
+Engine::TempUpFold::~TempUpFold() { if (up3) e->pool_.free(up3); }
 bool Engine::lora_owned(const sdmi_lora* a) const { return a && std::find(loras_.begin(), loras_.end(), a) != loras_.end(); }
 
 bool Engine::lora_active_on(int entry) const {
@@ -1642,6 +1686,16 @@ void Engine::set_option(const std::string& key, const std::string& value) {
     else if (key == "gemm3x_variant") opt_gemm3x_variant_ = (value == "default") ? kGemm3xVariantDefault : std::stoi(value);
     else if (key == "gemm_bf16x_variant") opt_gemm_bf16x_variant_ = (value == "default") ? kGemmBf16xVariantDefault : std::stoi(value);
     else if (key == "geglu_fuse") opt_geglu_fuse_ = std::stoi(value);
+    else if (key == "ups_phase") {
+        const int v = (value == "default") ? 2 : std::stoi(value);
+        if (v < 0 || v > 2) throw Error(SDMI_ERR_INVALID, "ups_phase: 0 (never), 1 (wherever supported) or 2 (where the planner takes it)");
+        opt_ups_phase_ = v;
+        if (v && finalized_) {   // switched on behind finalize_weights: the phase weights that were never built
+            SDMI_HIP(hipSetDevice(cfg_.device));
+            rebuild_folds();
+            SDMI_HIP(hipStreamSynchronize(stream_));
+        }
+    }
     else if (key == "record_shapes") { record_shapes_ = std::stoi(value) != 0; if (record_shapes_) { shape_counts_.clear(); choice_counts_.clear(); } }
     else if (key == "dump_shapes") {
         std::ofstream f(value);
@@ -1812,6 +1866,7 @@ void Engine::conv(const ConvW& w, const Act& x, Act& y, int stride, int ups, con
     const int extra = pad_br ? 1 : 0;
     const int ho = (hin + 2 * pad + extra - w.k) / stride + 1, wo = (win + 2 * pad + extra - w.k) / stride + 1;
     if (y.n != x.n || y.h != ho || y.w != wo || y.c != w.cout) throw Error(SDMI_ERR_INVALID, "conv: output shape mismatch");
+    if (ups == 1 && stride == 1 && w.k == 3 && !pad_br && conv_ups_phase(w, x, y, rowvec, resid)) return;   // four folded 2x2 phase convolutions instead
     ConvGemm p{};
     // (an fp32 -> bf16 layer -- Cin < 32 at precision >= 1 -- adds its residual in fp32, in front of the rounding: k_gemm2.hip's epilogue)
     const int resid_dt = (!x.dt && y.dt) ? 0 : y.dt;
@@ -1832,6 +1887,81 @@ void Engine::conv(const ConvW& w, const Act& x, Act& y, int stride, int ups, con
     if (x.dt != w.dt) throw Error(SDMI_ERR_STATE, "conv: activation / weight storage types disagree");
     p.out_mode = x.dt ? (y.dt ? 0 : 1) : (y.dt ? 2 : 0);
     launch_gemm(p, x.dt);
+}
+
+// y = conv3x3(nearest_2x(x), w) + bias as ONE plane launch over the SOURCE grid: four 2x2 convolutions, one per output pixel phase, with the weights folded at load
+// (ConvW::up3, rebuild_folds; kernels.hpp ConvGemm::phases).  Of the nine taps of an output pixel only four distinct source pixels are read, so the K = 9 cin launch
+// multiplies duplicated activations in 5/9 of its matrix instructions; this one executes 2 . 4 . (M / 4) . N . 4 cin flops.  Returns false -- nothing launched, the
+// caller runs the K = 9 cin launch -- when the option, the layer, the fold's freshness, the buffers or the planner (plan_ups_phase) do not allow it.  ups_phase = 1
+// (tests) with a time-embedding row or a residual is an error: a phase launch carries the bias only, and a forced arm has no quiet other path.
+bool Engine::conv_ups_phase(const ConvW& w, const Act& x, Act& y, const float* rowvec, const Act* resid) {
+    if (!opt_ups_phase_ || bf16_ || x.dt || y.dt || w.dt || w.k != 3 || !w.up3 || !w.up_fresh || probe_buf_) return false;
+    if (x.c != w.cin || !plane_gemm(w.cin, w.cout) || !up_fold_supported(w.cin, w.cout) || (!x.p3 && !x.p) || (!y.p && !y.p3)) return false;
+    ConvGemm p{};
+    p.A = x.p; p.Bt = w.bt; p.bias = w.bias;
+    p.Bt3 = split_planes(w.bt);
+    if (!p.Bt3) return false;
+    p.A3 = x.p3; p.a3_ld = x.ld3;
+    p.C = y.p; p.C3 = y.p3; p.ldc3 = y.ld3;
+    p.M = (int)y.rows(); p.N = w.cout; p.K = w.cin * 9;            // the layer, as the planner and the records see it
+    p.NB = x.n; p.Hs = x.h; p.Ws = x.w; p.Cin = w.cin; p.Ho = 2 * x.h; p.Wo = 2 * x.w;
+    p.KH = 3; p.KW = 3; p.stride = 1; p.pad = 1; p.ups = 1;
+    p.ldc = y.p ? y.stride() : p.N; p.ldr = p.ldc; p.a_ld = x.stride(); p.b_ld = p.K; p.CS = 32;
+    p.kt_total = p.K / 32;
+    p.variant = opt_gemm3x_variant_;
+    p.zero_page = zero_page_;
+    const GemmPlanIn in = gemm_plan_in(p, 0, -1, 0);
+    const UpsPhasePlan g = plan_ups_phase(in, w.up_fresh, opt_ups_phase_, gopt_, tuning_);
+    if (!g.take) return false;
+    // the native plane output of launch_gemm: 16-byte stores
+    if ((p.N % 4) || (p.C && p.ldc % 4)) { if (p.C3 || opt_ups_phase_ != 1) return false; }
+    if (rowvec || resid) {
+        if (opt_ups_phase_ != 1) return false;
+        throw Error(SDMI_ERR_INVALID, "conv: ups_phase=1 with a time-embedding row or a residual: a phase launch carries the bias only");
+    }
+    if (record_shapes_) {
+        char sk[96];
+        std::snprintf(sk, sizeof sk, "%d,%d,%d,%d,%d,%d,%d,%d", p.NB, p.Cin, p.Hs, p.Ws, p.N, 3, 1, 1);
+        ++shape_counts_[sk];
+        p.splits = g.splits;
+        record_choice(p, " phase", g.cfg, "");
+    }
+    std::unique_ptr<Buf> a3_tmp;
+    if (!p.A3) {   // ups_phase = 1 on an fp32 source: split once for this launch, as launch_gemm does for a plane tile
+        const long long rows = (long long)p.NB * p.Hs * p.Ws;
+        p.a3_ld = (p.Cin / 32) * 192;
+        a3_tmp.reset(new Buf(this, (size_t)rows * p.a3_ld));
+        ProfScope ps(this, PC_SPLIT_ROWS, 0, (double)rows * p.Cin * 10.0);
+        SDMI_HIP(launch_split3_rows(p.A, a3_tmp->p, rows, p.Cin, p.a_ld, p.a3_ld, stream_));
+        count_kernel();
+        p.A3 = a3_tmp->p;
+    }
+    // from here on the struct describes the phase launch: M = the rows of one phase, K = 4 cin
+    p.Bt3 = w.up3; p.phases = 4; p.phase_stride = (long long)w.cout * w.cin * 24;
+    p.b3_grouped = b3_grouped(p.N) ? 1 : 0;
+    p.M = g.M; p.K = g.K; p.kt_total = g.kt_total; p.b_ld = p.K;
+    p.kt_per_split = g.kt_per_split; p.splits = g.splits;
+    const double flops = 2.0 * 4.0 * p.M * (double)p.N * p.K;      // executed
+    const double bytes = (double)p.M * p.Cin * 6.0 + 4.0 * p.N * (double)p.K * 6.0 + 4.0 * p.M * (double)p.N * ((p.C ? 4.0 : 0.0) + (p.C3 ? 6.0 : 0.0));
+    std::unique_ptr<Buf> slab;
+    if (p.splits > 1) {
+        p.slab_stride = 4ll * p.M * p.N;
+        slab.reset(new Buf(this, (size_t)p.splits * p.slab_stride * sizeof(float)));
+        p.slabs = slab->f();
+    }
+    {
+        ProfScope ps(this, PC_CONV_SPLIT, flops, bytes);
+        ps.set_tag("gemm 4x%d,%d,%d k3 phase cfg=%d splits=%d", p.M, p.N, p.K, g.cfg, p.splits);
+        SDMI_HIP(launch_conv_gemm3p(p, g.tile.index, stream_));
+    }
+    count_kernel(flops);
+    if (p.splits > 1) {
+        ProfScope ps(this, PC_SPLITK_REDUCE, 0, (double)(p.splits + 1) * p.slab_stride * 4.0);
+        ps.set_tag("reduce 4x%d,%d,%d k3 phase cfg=%d splits=%d", p.M, p.N, p.K, g.cfg, p.splits);
+        SDMI_HIP(launch_splitk_reduce(p, stream_));
+        count_kernel();
+    }
+    return true;
 }
 
 // y = conv3x3(h, w_out) + conv1x1(x, w_skip) as ONE split-K plane launch + its reduce: the 1x1 shortcut of a ResBlock runs on extra K slices of conv_out's grid
@@ -3618,6 +3748,7 @@ void Engine::op_conv2d(const float* x, const float* wt, const float* bias, int n
     else SDMI_HIP(launch_pack_conv_weight(wt, bt.f(), cout, cin, k, k, stream_));
     TempSplit planes(this, bt.f(), w.dt ? 0 : cout, (long long)cin * k * k);
     w.bt = bt.f(); w.bias = const_cast<float*>(bias);
+    TempUpFold up_fold(this, w, stride, ups);   // an up-convolution: its phase weights, as rebuild_folds derives the model's
     Act a = new_act(n, h, wd, cin, w.dt);
     if (w.dt) SDMI_HIP(launch_nchw_f32_to_nhwc_bf16(x, a.p, n, cin, h, wd, 1.0f, stream_));
     else SDMI_HIP(launch_nchw_to_nhwc(x, a.p, n, cin, h, wd, 1.0f, stream_));
@@ -3778,6 +3909,7 @@ void Engine::op_conv2d_view(const float* xp, const float* wt, const float* bias,
             else SDMI_HIP(launch_pack_conv_weight(wt, bt.f(), cout, cin, k, k, stream_));
             TempSplit planes(this, bt.f(), w.dt ? 0 : cout, (long long)cin * k * k);
             w.bt = bt.f(); w.bias = const_cast<float*>(bias);
+            TempUpFold up_fold(this, w, stride, ups);
             conv(w, xs, ys, stride, ups, temb, epi ? epi->temb_stride : 0, r.p ? &r : nullptr);
         }
     } catch (...) {
@@ -4105,6 +4237,7 @@ double Engine::bench_conv(int n, int cin, int h, int w, int cout, int k, int str
         SDMI_HIP(launch_split3_rows(a.p, a.p3, a.rows(), cin, cin, a.ld3, stream_));
     }
     ConvW cw; cw.cin = cin; cw.cout = cout; cw.k = k; cw.bt = bt.f(); cw.bias = bias.f(); cw.dt = wdt;
+    TempUpFold up_fold(this, cw, stride, ups);   // (option ups_phase = 1 times the phase launch of an up-convolution on the forced plane tile / split count)
     const OptRestore r1{gopt_.force_tile}, r2{gopt_.force_splits}, r3{gopt_.gemm_planes};
     gopt_.force_tile = tile_cfg; gopt_.force_splits = splitk;
     if (plane_tile && !gopt_.gemm_planes) gopt_.gemm_planes = 2;

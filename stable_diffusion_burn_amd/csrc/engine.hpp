@@ -93,7 +93,13 @@ struct Act {
 };
 
 // bt8 / bs8 (precision = 2 only): the same weight as MXFP8 -- e4m3 [cout][Kp] + E8M0 scales [cout][Kp / 32] (k_fp8.hip)
-struct ConvW { float* bt = nullptr; float* bias = nullptr; int cin = 0, cout = 0, k = 1; int dt = 0; float* bt8 = nullptr; float* bs8 = nullptr; };
+// up3 / up_fresh (fp32 engine, the 3x3 convolution of an Upsample layer; Engine::rebuild_folds): the planes of the four folded 2x2 phase weights [4][cout][4 cin]
+// (kernels.hpp, ConvGemm::phases), phase images cout * cin * 24 bytes apart.  up_fresh: they are derived from what the weight entry up_entry holds NOW -- handled exactly
+// like SpatialW::fold_fresh: every write or re-pack of the entry clears it (fold_touch), and a layer whose fold is not fresh runs the K = 9 cin launch.
+struct ConvW {
+    float* bt = nullptr; float* bias = nullptr; int cin = 0, cout = 0, k = 1; int dt = 0; float* bt8 = nullptr; float* bs8 = nullptr;
+    void* up3 = nullptr; bool up_fresh = false; int up_entry = -1;
+};
 // an MXFP8 activation: e4m3 [n][h][w][cp] + E8M0 scales [n][h][w][cp / 32], cp = c rounded up to 128 (zero padded)
 struct ActQ {
     void* q = nullptr; void* s = nullptr;
@@ -141,6 +147,7 @@ struct WeightEntry {
     float pre_scale = 1.f;    // the tensor is multiplied by this in fp32 before it is packed (bf16 / MXFP8 query projections: attn_bf16_q_scale)
     bool set = false;
     int fold_st = -1;         // index in st_list_ of the SpatialTransformer whose folded weights (SpatialW::fold_bt) are derived from this entry; -1: none
+    int fold_up = -1;         // index in up_list_ of the up-convolution whose phase weights (ConvW::up3) are derived from this entry; -1: none
     float* master = nullptr;  // option keep_masters, kind 0 / 1: the fp32 tensor as the packing kernels read it (reference layout, a conv_in's input channels padded by padded_cin, before pre_scale)
 };
 
@@ -438,7 +445,28 @@ private:
     // wf [cout][k_main] = proj_bt [cout][cmid] x lin_bt [cmid][k_main], bf [cout] = proj_bt x lin_bias (zeros without one): fp64 accumulation, rounded once
     void fold_weights(const float* proj_bt, const float* lin_bt, const float* lin_bias, int cout, int cmid, int k_main, float* wf, float* bf);
     void rebuild_folds();                        // every SpatialW whose fold is not fresh and whose three entries are set (precision 0 only); enqueues on stream_
-    void fold_touch(const WeightEntry& e) { if (e.fold_st >= 0) st_list_[(size_t)e.fold_st]->fold_fresh = false; }
+    void fold_touch(const WeightEntry& e) {
+        if (e.fold_st >= 0) st_list_[(size_t)e.fold_st]->fold_fresh = false;
+        if (e.fold_up >= 0) up_list_[(size_t)e.fold_up]->up_fresh = false;
+    }
+    std::vector<ConvW*> up_list_;                // the up-convolutions (UNet Upsample, VAE decoder upsampler), in model order
+    // option ups_phase (fp32 engine): conv3x3(nearest_2x(x)) as four folded 2x2 phase convolutions in one plane launch.  0 = never (the A/B arm), 1 = wherever supported
+    // (tests), 2 = where the planner takes it (plan_ups_phase)
+    int opt_ups_phase_ = 2;
+    // planes of the four phase weights of the packed 3x3 weight bt [cout][9 cin] -> up3 (cout * cin * 96 bytes): launch_fold_ups_phase_f64 into a pool buffer, then
+    // launch_pack_split3 per the layout b3_grouped(cout) names.  Enqueues on stream_.
+    void build_up_fold(const float* bt, void* up3, int cout, int cin);
+    bool up_fold_supported(int cin, int cout) const;
+    // the phase launch of an up-convolution (+ its reduce); false: not launched, the caller runs the K = 9 cin launch (see engine.cpp)
+    bool conv_ups_phase(const ConvW& w, const Act& x, Act& y, const float* rowvec, const Act* resid);
+    // operator-level calls: the phase weights of a temporary 3x3 weight, for the duration of the call (like TempSplit)
+    struct TempUpFold {
+        Engine* e; void* up3 = nullptr;
+        TempUpFold(Engine* e_, ConvW& w, int stride, int ups);
+        ~TempUpFold();
+        TempUpFold(const TempUpFold&) = delete;
+        TempUpFold& operator=(const TempUpFold&) = delete;
+    };
     static Act slice(const Act& parent, int c_off, int c);   // channel-slice view
     // A3 / C3: the input / output as three bf16 planes (dense rows: 192 bytes per 32 channels); A and / or C may then be null
     void gemm(const float* A, int a_rows, const float* bt, const float* bias, int cin, int cout, float* C, int ldc,

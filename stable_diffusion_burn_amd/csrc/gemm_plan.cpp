@@ -25,6 +25,11 @@ static const TuneRow kPairRows[] = {
 #include "tuning_table_pairs.inc"
     {nullptr, 0, 0}};
 
+// tuning/gfx950_fp32_phases.txt: the phase shape "M/4,N,4Cin" of an up-convolution -> (plane tile, split count; 0 = keep the K = 9 Cin launch)
+static const TuneRow kPhaseRows[] = {
+#include "tuning_table_phases.inc"
+    {nullptr, 0, 0}};
+
 // ---- cost model of the five MFMA families ------------------------------------------------------------------------------
 // Cycles per CU: (rounds of workgroups on 256 CUs) x (k loop of one workgroup / tile efficiency + per-workgroup overhead)
 // + split-K reduce launch and slab traffic.  A k tile of a bm x bn block is bm * bn * flop / rate cycles: fp32 MFMA 32 * 2 flop at
@@ -44,8 +49,9 @@ static const CostRow kCost[] = {
     {1, kFamX, kNumGemmTilesX, {0.54, 0.46, 0.38, 0.48}, 128.0, 4096.0, 6000.0, 2.0, 20.0}};
 static const int kSplitOpts[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48};
 
-// the cheapest (tile, split count) among the families of `families` (bit per GemmFamily); pairs_only: tiles with geglu_pairs
-static TileChoice cost_model(int bf16, unsigned families, int M, int N, int kt_total, bool pairs_only) {
+// the cheapest (tile, split count) among the families of `families` (bit per GemmFamily); pairs_only: tiles with geglu_pairs; phases: the launch holds that many
+// problems of the shape, each with its own M tiles (plan_ups_phase)
+static TileChoice cost_model(int bf16, unsigned families, int M, int N, int kt_total, bool pairs_only, int phases = 1) {
     const int n_cu = 256;
     double best = 1e300;
     TileChoice bc{0, 1};
@@ -55,7 +61,7 @@ static TileChoice cost_model(int bf16, unsigned families, int M, int N, int kt_t
             const GemmTileInfo& ti = kGemmFamilies[r.family].tiles[c];
             if (pairs_only && !ti.geglu_pairs) continue;
             const int bm = ti.bm, bn = ti.bn;
-            const long long tiles = (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+            const long long tiles = (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn) * phases;
             const double overhead = r.wg + bm * bn * r.area_num / r.area_den;
             for (int s : kSplitOpts) {
                 if (s > 1 && kt_total / s < 4) break;
@@ -63,7 +69,7 @@ static TileChoice cost_model(int bf16, unsigned families, int M, int N, int kt_t
                 const long long wgs = tiles * ((kt_total + kt_per - 1) / kt_per);
                 const double per_cu = (double)((wgs + n_cu - 1) / n_cu);
                 double t = per_cu * ((double)bm * bn * kt_per * r.flop / r.rate / r.eff[c] + overhead);
-                if (s > 1) t += 8000.0 + (double)M * N * 4.0 * (s + 1) / (5.0e12 / 2.4e9);  // reduce launch + slab traffic
+                if (s > 1) t += 8000.0 + (double)M * phases * N * 4.0 * (s + 1) / (5.0e12 / 2.4e9);  // reduce launch + slab traffic
                 if (t < best) { best = t; bc = {kGemmFamilies[r.family].base + c, s}; }
             }
         }
@@ -100,6 +106,8 @@ void GemmTuning::load_builtin() {
         else ++t;
     for (const TuneRow& r : kPairRows)
         if (r.key) pairs[r.key] = TileChoice{r.cfg, r.splits};
+    for (const TuneRow& r : kPhaseRows)
+        if (r.key) phases[r.key] = TileChoice{r.cfg, r.splits};
 }
 
 void GemmTuning::set(const std::string& value, bool b16) {
@@ -110,6 +118,12 @@ void GemmTuning::set(const std::string& value, bool b16) {
         if (std::sscanf(value.c_str() + eq + 1, "%d,%d", &tc.cfg, &tc.splits) != 2 || tc.splits < 0 || gemm_tile_id(tc.cfg).family != kFamP || !gemm_tile_id(tc.cfg).in_range(false))
             throw Error(SDMI_ERR_INVALID, "tune: a pair row is M,N,Kmain+Kaux=cfg,kt_per_split with a plane tile (300 + x)");
         pairs[value.substr(0, eq)] = tc;
+        return;
+    }
+    if (!b16 && value.compare(0, 3, "ph:") == 0) {   // a row of the phase table (plan_ups_phase): the phase shape, a plane tile, splits = 0: decline the shape
+        if (std::sscanf(value.c_str() + eq + 1, "%d,%d", &tc.cfg, &tc.splits) != 2 || tc.splits < 0 || gemm_tile_id(tc.cfg).family != kFamP || !gemm_tile_id(tc.cfg).in_range(false))
+            throw Error(SDMI_ERR_INVALID, "tune: a phase row is ph:M/4,N,4Cin=cfg,splits with a plane tile (300 + x)");
+        phases[value.substr(3, eq - 3)] = tc;
         return;
     }
     if (std::sscanf(value.c_str() + eq + 1, "%d,%d", &tc.cfg, &tc.splits) != 2 || tc.cfg < 0 || tc.splits < 1 || !gemm_tile_id(tc.cfg).in_range(b16))
@@ -206,6 +220,37 @@ GemmPairPlan plan_gemm_pair(const GemmPlanIn& main, int k_aux, int kt_aux, const
     pp.splits_main = slices(ktm, kt);
     pp.splits_aux = slices(kt_aux, kt);
     pp.pair = true;
+    return pp;
+}
+
+UpsPhasePlan plan_ups_phase(const GemmPlanIn& layer, bool fold_fresh, int ups_phase, const GemmPlanOpts& o, const GemmTuning& t) {
+    UpsPhasePlan pp{};
+    if (ups_phase == 0 || !fold_fresh) return pp;
+    if (layer.bf16 || layer.geglu || layer.out_mode != 0 || layer.KH != 3 || layer.KW != 3 || layer.stride != 1 || layer.pad != 1 || layer.ups != 1) return pp;
+    if (!layer.p_ok || !o.gemm_planes || !o.gemm_f32s || layer.Cin % 32 || layer.Ho != 2 * layer.Hs || layer.Wo != 2 * layer.Ws || layer.M % 4) return pp;
+    const int forced = layer.force_cfg >= 0 ? layer.force_cfg : o.force_tile;
+    if (forced >= 0 && gemm_tile_id(forced).family != kFamP) return pp;
+    if (ups_phase != 1 && (!layer.from_planes || forced >= 0)) return pp;
+    pp.M = layer.M / 4; pp.K = 4 * layer.Cin; pp.kt_total = layer.Cin / 8;
+    char key[64];
+    std::snprintf(key, sizeof key, "%d,%d,%d", pp.M, layer.N, pp.K);
+    TileChoice tc;
+    if (const TileChoice* row = find(t.phases, key)) {
+        if (row->splits <= 0 && ups_phase != 1) return pp;
+        tc = *row;
+        if (tc.splits <= 0) tc.splits = 1;
+    } else {
+        if (ups_phase != 1 && pp.M < kUpsPhaseMinRows) return pp;
+        tc = cost_model(0, 1u << kFamP, pp.M, layer.N, pp.kt_total, false, 4);
+    }
+    if (forced >= 0) tc.cfg = forced;
+    if (o.force_splits > 0) tc.splits = o.force_splits;
+    if (layer.force_splits > 0) tc.splits = layer.force_splits;
+    const GemmTileId tile = gemm_tile_id(tc.cfg);
+    if (tile.family != kFamP || !tile.in_range(false)) throw Error(SDMI_ERR_INVALID, "gemm: a phase launch needs a plane tile (300 + x)");
+    pp.tile = tile; pp.cfg = tile.cfg();
+    pp.splits = clamp_splits(tc.splits, pp.kt_total, &pp.kt_per_split);
+    pp.take = true;
     return pp;
 }
 

@@ -45,7 +45,10 @@ struct GemmTuning {
     std::map<std::string, TileChoice> pairs;
     void load_builtin();
     void set(const std::string& value, bool b16);   // "M,N,K=cfg,splits"; "M,N,Kmain+Kaux=cfg,kt_per_split" goes to pairs
-    void clear() { f32.clear(); mfma.clear(); planes.clear(); bf16.clear(); pairs.clear(); }
+    // phase launches of up-convolutions (plan_ups_phase), the PHASE shape "M/4,N,4Cin" -> (plane tile, splits; 0 = do not take): tuning/gfx950_fp32_phases.txt.  A map of
+    // its own, so a phase shape cannot collide with a plain shape of `planes`; option tune writes it through the key "ph:M/4,N,4Cin"
+    std::map<std::string, TileChoice> phases;
+    void clear() { f32.clear(); mfma.clear(); planes.clear(); bf16.clear(); pairs.clear(); phases.clear(); }
 };
 
 struct GemmPlan { GemmTileId tile; int cfg, splits, kt_per_split; bool tile_forced; };   // cfg = tile.cfg(); tile_forced: by option gemm_tile or by the caller
@@ -63,6 +66,20 @@ struct GemmPairPlan { bool pair; GemmTileId tile; int cfg, kt_per_split, splits_
 // force_main / force_aux > 0 (tests, with option gemm_tile for the tile): requested slice counts.  Both problems share kt_per_split, so the request is met as
 // kt = max(ceil(kt_main / force_main), ceil(kt_aux / force_aux)) and the counts that follow from it; it pairs whatever today's split count is.
 GemmPairPlan plan_gemm_pair(const GemmPlanIn& main, int k_aux, int kt_aux, const GemmPlanOpts& o, const GemmTuning& t, int force_main = 0, int force_aux = 0);   // throws Error
+// conv3x3(nearest_2x(x)) as four folded 2x2 phase convolutions in one plane launch (kernels.hpp, ConvGemm::phases).  `layer`: the up-convolution as plan_gemm would see
+// it (M = NB 2Hs 2Ws rows, K = 9 Cin).  The phase shape is 4 x [M / 4, N, 4 Cin], kt = Cin / 8 k tiles; M, K, kt_per_split of the plan are the phase shape's.
+// take = false ("run today's launch") when
+//   * ups_phase = 0, the fold is not fresh, the layer is not 3x3 / stride 1 / pad 1 / ups 1 in fp32 with plain output, or the plane kernel does not take it (p_ok,
+//     gemm_planes = 0, gemm_f32s = 0, a forced tile of another family);
+//   * ups_phase = 2 (default) and: the activations do not arrive as planes, a tile is forced (option gemm_tile or the caller), the phase table says splits = 0 for
+//     the shape, or -- without a row -- a phase has fewer than kUpsPhaseMinRows rows: one M tile per phase then streams the 16 Cin N folded weights where today's
+//     launch streams 9 Cin N, and launches that small run at the weight stream's rate, not the matrix pipe's.
+// ups_phase = 1 (tests): wherever supported; option gemm_tile = 30x and option splitk are honoured.
+// Tile and split count: the phase table (GemmTuning::phases, keyed by the phase shape in a map of its own: no collision with a plain "M,N,K" row), else the cost model
+// over the plane tiles with 4 x the M tiles.  No slice is empty (clamp as plan_gemm).
+constexpr int kUpsPhaseMinRows = 256;
+struct UpsPhasePlan { bool take; GemmTileId tile; int cfg, splits, kt_per_split, M, K, kt_total; };
+UpsPhasePlan plan_ups_phase(const GemmPlanIn& layer, bool fold_fresh, int ups_phase, const GemmPlanOpts& o, const GemmTuning& t);
 // MXFP8 (k_fp8.hip): tile index (fp8_tile >= 0 forces it) and split count
 TileChoice plan_gemm_fp8(int M, int N, int kt_total, int fp8_tile, int force_splits, int* kt_per_split);
 // the plane tile the GEGLU projection [rows, 2 hidden] takes with the gate split by wave column in its epilogue, or -1 (unfused)

@@ -291,7 +291,7 @@ static hipError_t launch_cfg_fp8x(const ConvGemm& p, dim3 grid, hipStream_t stre
 }
 
 hipError_t launch_conv_gemm_fp8x(const ConvGemm& p, int cfg, hipStream_t stream) {
-    if (p.z_aux) return hipErrorInvalidValue;   // an auxiliary problem on extra slices: k_gemm3p.hip only
+    if (p.z_aux || p.phases) return hipErrorInvalidValue;   // an auxiliary problem on extra slices / a phase launch: k_gemm3p.hip only
     if (cfg < 0 || cfg >= kNumGemmTilesQ) return hipErrorInvalidValue;
     if ((p.a_ld % 128) || (p.b_ld % 128) || !p.zero_page || !p.a_scale || !p.b_scale || p.geglu) return hipErrorInvalidValue;
     if ((p.N & 7) || (p.ldc & 7) || (p.resid && (p.ldr & 7))) return hipErrorInvalidValue;   // 16-byte epilogue only

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvGemm p) {
     const bool vec_ok = splitk_reduce_vec(p, false);
     if (vec_ok) {
         const int n4 = p.N >> 2;
-        const long long total = (long long)p.M * n4;              // 16-byte outputs
+        const long long total = (long long)p.M * (p.phases ? p.phases : 1) * n4;   // 16-byte outputs (a phase launch: slabs of 4 M rows, phase-major)
         const long long rounded = (total * G + 255) / 256 * 256;   // whole workgroups take part in the shuffles
         for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < rounded; t += (long long)gridDim.x * blockDim.x) {
             const long long i = t / G;
@@ -79,6 +79,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvGemm p) {
             const int m = (int)(ii / n4);
             const int n = (int)(ii - (long long)m * n4) * 4;
             const long long off = (long long)m * p.N + n;
+            long long mo = m;                                   // output row: a phase launch writes through its row map
+            if (p.phases) { const int ph = m / p.M; mo = ups_phase_row(m - ph * p.M, ph, p.Hs, p.Ws); }
             // round 6: the bias / time-embedding row / residual of this output are requested BEFORE the slab loads, not behind the shuffles -- the launch is one memory round
             // trip deep instead of two (2 427 launches of 6 ... 10 us per batch-1 image); added in the same order as before: bit-identical results
             f32x4 eb = {0.f, 0.f, 0.f, 0.f}, ev = eb, er = eb;
@@ -107,12 +109,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvGemm p) {
                 if (p.bias || p.bias_aux) v += eb;
                 if (p.rowvec) v += ev;
                 if (p.resid) v += er;
-                if (C) *reinterpret_cast<f32x4*>(C + (long long)m * p.ldc + n) = v;
-                if (p.C3) s3_store4(reinterpret_cast<unsigned char*>(p.C3) + (long long)m * p.ldc3, n, v);
+                if (C) *reinterpret_cast<f32x4*>(C + mo * p.ldc + n) = v;
+                if (p.C3) s3_store4(reinterpret_cast<unsigned char*>(p.C3) + mo * p.ldc3, n, v);
             }
         }
     } else {
-        const long long total = (long long)p.M * p.N;
+        const long long total = (long long)p.M * (p.phases ? p.phases : 1) * p.N;
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
              i += (long long)gridDim.x * blockDim.x) {
             const int m = (int)(i / p.N);
@@ -123,7 +125,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvGemm p) {
             else if (p.bias) v += p.bias[n];
             if (p.rowvec) v += p.rowvec[(long long)(m / HoWo) * p.rowvec_stride + n];
             if (p.resid) v += p.resid[(long long)m * p.ldr + n];
-            C[(long long)m * p.ldc + n] = v;
+            long long mo = m;
+            if (p.phases) { const int ph = m / p.M; mo = ups_phase_row(m - ph * p.M, ph, p.Hs, p.Ws); }
+            C[mo * p.ldc + n] = v;
         }
     }
 }
@@ -185,7 +189,38 @@ __global__ __launch_bounds__(256) void fold_matmul_f64_kernel(const float* __res
     if (n < N && k < K) out[(long long)n * ldo + k] = (float)acc;
 }
 
+// The folded 2x2 weights of the four pixel phases of an up-convolution (kernels.hpp, launch_fold_ups_phase_f64).  Load time and behind a LoRA re-merge only: one
+// thread per output.
+__global__ __launch_bounds__(256) void fold_ups_phase_f64_kernel(const float* __restrict__ bt, float* __restrict__ out, int N, int Cin, int ph0, int nph) {
+    const long long K4 = 4ll * Cin, K9 = 9ll * Cin;
+    const long long total = (long long)nph * N * K4;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int pi = (int)(i / (N * K4));
+        const long long r = i - pi * (N * K4);
+        const int ph = ph0 + pi;
+        const int n = (int)(r / K4), k = (int)(r - n * K4);
+        const int sl = k >> 5, ci = k & 31, cs = sl >> 2, a = (sl >> 1) & 1, b = sl & 1;
+        const int py = ph >> 1, px = ph & 1;
+        // R_0 = [[1,0,0],[0,1,1]]: a = 0 -> {0}, a = 1 -> {1, 2};  R_1 = [[1,1,0],[0,0,1]]: a = 0 -> {0, 1}, a = 1 -> {2}
+        const int ky0 = a ? (py ? 2 : 1) : 0, ky1 = a ? 2 : (py ? 1 : 0);
+        const int kx0 = b ? (px ? 2 : 1) : 0, kx1 = b ? 2 : (px ? 1 : 0);
+        double acc = 0.0;
+        for (int ky = ky0; ky <= ky1; ++ky)
+            for (int kx = kx0; kx <= kx1; ++kx) acc += (double)bt[n * K9 + (long long)(cs * 9 + ky * 3 + kx) * 32 + ci];
+        out[i] = (float)acc;
+    }
+}
+
 // ---- host side ----------------------------------------------------------------------
+hipError_t launch_fold_ups_phase_f64(const float* bt, float* out, int N, int Cin, int ph0, int nph, hipStream_t s) {
+    if (N <= 0 || Cin <= 0 || (Cin % 32) || ph0 < 0 || nph < 1 || ph0 + nph > 4) return hipErrorInvalidValue;
+    const long long total = 4ll * nph * N * Cin;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(fold_ups_phase_f64_kernel, dim3((unsigned)blocks), dim3(256), 0, s, bt, out, N, Cin, ph0, nph);
+    return hipGetLastError();
+}
+
 hipError_t launch_fold_matmul_f64(const float* a, const float* b, float* out, int N, int Cn, int K, long long lda, long long ldb, long long ldo, hipStream_t s) {
     if (N <= 0 || Cn <= 0 || K <= 0 || lda < Cn || ldb < K || ldo < K) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((K + 15) / 16), (unsigned)((N + 15) / 16));
@@ -201,7 +236,9 @@ hipError_t launch_splitk_reduce(const ConvGemm& p, hipStream_t stream) {
     // No paired launch carries a time-embedding row.
     if (p.z_aux && p.rowvec) return hipErrorInvalidValue;
     if (p.bias_aux && vec && ((uintptr_t)p.bias_aux & 15)) return hipErrorInvalidValue;
-    const long long work = ((long long)p.M * p.N + 3) / 4;
+    // a phase launch (ConvGemm::phases): bias only, slabs of 4 M rows
+    if (p.phases && (p.phases != 4 || p.rowvec || p.resid || p.z_aux || p.bias_aux || p.slab_stride != 4ll * p.M * p.N)) return hipErrorInvalidValue;
+    const long long work = ((long long)p.M * (p.phases ? p.phases : 1) * p.N + 3) / 4;
     // lanes per output: enough threads to cover the chip (>= 256 K) while every lane still has two slabs to sum
     int g = 1;
     if (vec)

@@ -304,7 +304,7 @@ static hipError_t launch_cfg2(const ConvGemm& p, size_t lds, dim3 grid, hipStrea
 }
 
 hipError_t launch_conv_gemm2(const ConvGemm& p, int cfg, hipStream_t stream) {
-    if (p.z_aux) return hipErrorInvalidValue;   // an auxiliary problem on extra slices: k_gemm3p.hip only
+    if (p.z_aux || p.phases) return hipErrorInvalidValue;   // an auxiliary problem on extra slices / a phase launch: k_gemm3p.hip only
     if (cfg < 0 || cfg >= kNumGemmTiles) return hipErrorInvalidValue;
     const int bm = gemm_tile_info(cfg).bm, bn = gemm_tile_info(cfg).bn;
     const int MT = (p.M + bm - 1) / bm, NT = (p.N + bn - 1) / bn;

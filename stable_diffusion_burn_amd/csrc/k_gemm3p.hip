@@ -18,6 +18,10 @@
 // activation fragment groups, so the gather arithmetic (tap, padding, nearest-2x upsample, zero page) is done once per group.
 // Everything else -- XCD-aware tile map, deterministic split-K slabs, the epilogue (k_gemm_epi.hpp), the k order (channel slice outer,
 // taps inner, chunk g of a plane row = elements 4g..4g+3, 16+4g..16+4g+3) -- is shared with k_gemm3x.hip, so both read the same weight planes.
+//
+// Phase mode (ConvGemm::phases, kernels.hpp): conv3x3(nearest_2x(x)) as four 2x2 convolutions over the source grid, one per output pixel phase, on weights folded at
+// load.  The M tiles are laid phase-major, a tile's phase selects its first tap and its weight image in front of the first DMA, and the epilogue / the reduce write
+// through ups_phase_row.  The k loop is the one below, unchanged.
 #include "kernels.hpp"
 #include "k_common.hpp"
 #include "k_gemm_epi.hpp"
@@ -191,10 +195,14 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm3p_kernel(const Conv
     const int BNO = geglu ? BN / 2 : BN;
     const int MT = (p.M + BM - 1) / BM;
     const int NT = (p.N + BNO - 1) / BNO;
-    const GemmWork gw = gemm_work_of_block(p, MT, NT);
+    // A phase launch (ConvGemm::phases): the M tiles are laid phase-major, MT per phase, so a tile never holds two phases.  Like the aux selects below, everything that
+    // depends on the phase is wave-uniform and sits in front of the first DMA: the k loop runs a 2x2 / stride-1 convolution over the source grid and does not know.
+    const bool phased = p.phases != 0;
+    const GemmWork gw = gemm_work_of_block(p, phased ? p.phases * MT : MT, NT);
     if (!gw.live) return;
     const int lid = gw.lid;
-    const int m0 = gw.tm * BM;
+    const int phase = phased ? gw.tm / MT : 0;
+    const int m0 = (gw.tm - phase * MT) * BM;
     const int n0 = gw.tn * BNO;
     const int z = gw.z;
     // Slices [z_aux, splits) of a paired launch (ConvGemm::z_aux != 0) work on the auxiliary 1x1 problem: other planes, other k range, one tap, no padding.  blockIdx.z
@@ -204,21 +212,24 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm3p_kernel(const Conv
     const int kt_begin = (aux ? z - p.z_aux : z) * p.kt_per_split;
     const int kt_end = min(kt_begin + p.kt_per_split, kt_total);
     const int n_t = kt_end - kt_begin;
-    const int KH = aux ? 1 : p.KH, KW = aux ? 1 : p.KW, pad = aux ? 0 : p.pad;
+    const int KH = aux ? 1 : phased ? 2 : p.KH, KW = aux ? 1 : phased ? 2 : p.KW;
+    const int pad_y = aux ? 0 : phased ? 1 - (phase >> 1) : p.pad, pad_x = aux ? 0 : phased ? 1 - (phase & 1) : p.pad;   // phase (py, px): taps start at source pixel (y - 1 + py, x - 1 + px)
+    const int stride = phased ? 1 : p.stride, ups = phased ? 0 : p.ups;
+    const int Wo = phased ? p.Ws : p.Wo;
     const int T = KH * KW;
-    const int HoWo = p.Ho * p.Wo;
+    const int HoWo = phased ? p.Hs * p.Ws : p.Ho * p.Wo;     // rows of a sample (of one phase)
 
     P3Wave<MI, NI, NAG, NBW, A_BYTES, NWV> w;
-    w.Hin = p.Hs << p.ups;
-    w.Win = p.Ws << p.ups;
-    w.ups = p.ups;
+    w.Hin = p.Hs << ups;
+    w.Win = p.Ws << ups;
+    w.ups = ups;
     w.Ws = p.Ws;
     w.KH = KH;
     w.KW = KW;
     w.wave = wave;
     w.pix_bytes = (unsigned)(aux ? p.a3_ld_aux : p.a3_ld);
     w.Abase = reinterpret_cast<const char*>(aux ? p.A3_aux : p.A3);
-    w.Wbase = reinterpret_cast<const char*>(aux ? p.Bt3_aux : p.Bt3);
+    w.Wbase = reinterpret_cast<const char*>(aux ? p.Bt3_aux : p.Bt3) + (phased ? phase * p.phase_stride : 0ll);
     w.zero = reinterpret_cast<const char*>(p.zero_page);
     w.a_src = w.zero;
 
@@ -232,11 +243,11 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm3p_kernel(const Conv
         const int mm = ok ? m : 0;
         const int nb = mm / HoWo;
         const int rem = mm - nb * HoWo;
-        const int oy = rem / p.Wo;
-        const int ox = rem - oy * p.Wo;
+        const int oy = rem / Wo;
+        const int ox = rem - oy * Wo;
         w.a_off[j] = (unsigned)nb * (unsigned)(p.Hs * p.Ws) * w.pix_bytes + ch * 16;
-        w.a_iy0[j] = ok ? oy * p.stride - pad : -(1 << 28);   // rows past M: never in range -> zero page
-        w.a_ix0[j] = ox * p.stride - pad;
+        w.a_iy0[j] = ok ? oy * stride - pad_y : -(1 << 28);   // rows past M: never in range -> zero page
+        w.a_ix0[j] = ox * stride - pad_x;
     }
     const unsigned w_row_bytes = (unsigned)kt_total * 192u;
 #pragma unroll
@@ -328,7 +339,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm3p_kernel(const Conv
     unsigned long long pt2 = 0, pc2 = 0;
     if constexpr (PROBE) { pt2 = __builtin_amdgcn_s_memrealtime(); pc2 = __builtin_amdgcn_s_memtime(); }
 
-    gemm_epilogue_f32<MI, NI, WM, WN>(p, w.acc, smem_p3, m0, n0, z, lid, wave, lane, HoWo);
+    gemm_epilogue_f32<MI, NI, WM, WN, true>(p, w.acc, smem_p3, m0, n0, z, lid, wave, lane, HoWo, phase);
     if constexpr (PROBE) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's stores have been acknowledged
         __syncthreads();
@@ -372,9 +383,18 @@ hipError_t launch_conv_gemm3p(const ConvGemm& p, int cfg, hipStream_t stream) {
         if ((unsigned long long)p.N * (unsigned long long)p.kt_total_aux * 192ull >= 0xFFFFFF00ull) return hipErrorInvalidValue;
         if ((unsigned long long)p.NB * p.Hs * p.Ws * (unsigned long long)p.a3_ld_aux >= 0xFFFFFF00ull) return hipErrorInvalidValue;
     }
+    if (p.phases) {
+        // the layer is conv3x3(nearest_2x(x)), M the rows of one phase, the k tiles those of the folded 2x2 weights; bias only (kernels.hpp, ConvGemm::phases)
+        if (p.phases != 4 || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.ups != 1 || p.Ho != 2 * p.Hs || p.Wo != 2 * p.Ws) return hipErrorInvalidValue;
+        if ((long long)p.M != (long long)p.NB * p.Hs * p.Ws || p.kt_total != p.Cin / 8 || p.K != 4 * p.Cin) return hipErrorInvalidValue;
+        if (p.rowvec || p.resid || p.geglu || p.z_aux || p.probe) return hipErrorInvalidValue;
+        if (p.phase_stride < (long long)p.N * p.kt_total * 192ll || (p.phase_stride % 16)) return hipErrorInvalidValue;
+        if (p.splits > 1 && (!p.slabs || p.slab_stride != 4ll * p.M * p.N)) return hipErrorInvalidValue;
+        if ((!p.C && !p.C3) || 4ll * p.M >= (1ll << 31)) return hipErrorInvalidValue;
+    }
     const int bm = kTilesP[cfg].bm, bn = kTilesP[cfg].bn;
     const int bno = p.geglu ? bn / 2 : bn;
-    const int MT = (p.M + bm - 1) / bm, NT = (p.N + bno - 1) / bno;
+    const int MT = ((p.M + bm - 1) / bm) * (p.phases ? p.phases : 1), NT = (p.N + bno - 1) / bno;
     const dim3 grid = gemm_grid(p, MT * NT);
     if (p.probe) {   // diagnostic instantiations (option gemm_probe): the three 8-wave tiles the batch-1 model uses most
         if ((unsigned long long)grid.x * grid.z > (unsigned long long)kGemmProbeBlocks) return hipErrorInvalidValue;   // the stamps would run past the buffer

@@ -336,7 +336,7 @@ static hipError_t launch_cfg_3x(const ConvGemm& p, dim3 grid, hipStream_t stream
 }
 
 hipError_t launch_conv_gemm3x(const ConvGemm& p, int cfg, hipStream_t stream) {
-    if (p.z_aux) return hipErrorInvalidValue;   // an auxiliary problem on extra slices: k_gemm3p.hip only
+    if (p.z_aux || p.phases) return hipErrorInvalidValue;   // an auxiliary problem on extra slices / a phase launch: k_gemm3p.hip only
     if (cfg < 0 || cfg >= kNumGemmTilesS) return hipErrorInvalidValue;
     if ((p.Cin % 32) || p.CS != 32 || !p.zero_page || !p.Bt3 || p.out_mode != 0) return hipErrorInvalidValue;
     const bool odd_ni = (cfg == 0 || cfg == 1 || cfg == 4);

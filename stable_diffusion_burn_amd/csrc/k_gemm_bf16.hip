@@ -397,7 +397,7 @@ static hipError_t launch_cfg_bf16(const ConvGemm& p, size_t lds, dim3 grid, hipS
 }
 
 hipError_t launch_conv_gemm_bf16(const ConvGemm& p, int cfg, hipStream_t stream) {
-    if (p.z_aux) return hipErrorInvalidValue;   // an auxiliary problem on extra slices: k_gemm3p.hip only
+    if (p.z_aux || p.phases) return hipErrorInvalidValue;   // an auxiliary problem on extra slices / a phase launch: k_gemm3p.hip only
     if (cfg < 0 || cfg >= kNumGemmTiles) return hipErrorInvalidValue;
     if (p.Cin % 64) return hipErrorInvalidValue;
     const int bm = gemm_tile_info(cfg).bm, bn = gemm_tile_info(cfg).bn;
@@ -421,7 +421,7 @@ hipError_t launch_conv_gemm_bf16(const ConvGemm& p, int cfg, hipStream_t stream)
 }
 
 hipError_t launch_splitk_reduce_bf16(const ConvGemm& p, hipStream_t stream) {
-    if (p.z_aux) return hipErrorInvalidValue;   // an auxiliary problem on extra slices: k_gemm3p.hip + launch_splitk_reduce only
+    if (p.z_aux || p.phases) return hipErrorInvalidValue;   // an auxiliary problem on extra slices / a phase launch: k_gemm3p.hip + launch_splitk_reduce only
     const bool vec = splitk_reduce_vec(p, true);    // the kernel's 16-byte path: four outputs per thread
     const long long work = (long long)p.M * p.N / (vec ? 4 : 1);
     int blocks = (int)((work + 255) / 256);

@@ -219,7 +219,7 @@ static hipError_t launch_cfg_bf16t(const ConvGemm& p, dim3 grid, hipStream_t str
 }
 
 hipError_t launch_conv_gemm_bf16t(const ConvGemm& p, int cfg, hipStream_t stream) {
-    if (p.z_aux) return hipErrorInvalidValue;   // an auxiliary problem on extra slices: k_gemm3p.hip only
+    if (p.z_aux || p.phases) return hipErrorInvalidValue;   // an auxiliary problem on extra slices / a phase launch: k_gemm3p.hip only
     if (cfg < 0 || cfg >= kNumGemmTilesT || !conv_gemm_bf16t_supported(p, p.kt_per_split)) return hipErrorInvalidValue;
     const int bm = gemm_tile_info_t(cfg).bm, bn = gemm_tile_info_t(cfg).bn;
     const int MT = p.M / bm, NT = (p.N + bn - 1) / bn;

@@ -383,7 +383,7 @@ int conv_gemm_bf16x_persistent_mode(const ConvGemm& p, int cfg) {
 }
 
 hipError_t launch_conv_gemm_bf16x(const ConvGemm& p, int cfg, hipStream_t stream) {
-    if (p.z_aux) return hipErrorInvalidValue;   // an auxiliary problem on extra slices: k_gemm3p.hip only
+    if (p.z_aux || p.phases) return hipErrorInvalidValue;   // an auxiliary problem on extra slices / a phase launch: k_gemm3p.hip only
     if (cfg < 0 || cfg >= kNumGemmTilesX) return hipErrorInvalidValue;
     if ((p.Cin % 64) || !p.zero_page) return hipErrorInvalidValue;
     if (p.geglu && (cfg == 0 || cfg == 3 || p.splits != 1 || (p.N & 7) || (p.ldc & 7) || p.rowvec || p.resid)) return hipErrorInvalidValue;  // needs an even NI

@@ -14,10 +14,13 @@ namespace sdmi {
 
 typedef float epi_f32x4 __attribute__((ext_vector_type(4)));
 
-template <int MI, int NI, int WM, int WN>
+// PH (k_gemm3p.hip): the kernel may run a phase launch (ConvGemm::phases; `phase` = the tile's phase, m0 a row of that phase).  Its slab rows are phase * M + m, and its
+// output rows go through ups_phase_row -- 2 ldc apart within a scanline, jumping at the end of a scanline, of a sample and of a phase -- so a phase launch takes the
+// general form below, whose stores compute their row address one by one, and never the lean form's uniform row pointer.
+template <int MI, int NI, int WM, int WN, bool PH = false>
 __device__ __forceinline__ void gemm_epilogue_f32(const ConvGemm& p, epi_f32x4 (&acc)[MI][NI], unsigned char* smem_x32, const int m0,
                                                   const int n0, const int z, const int lid, const int wave, const int lane,
-                                                  const int HoWo) {
+                                                  const int HoWo, const int phase = 0) {
     typedef epi_f32x4 f32x4;
     constexpr int BM = 16 * MI * WM;
     constexpr int BN = 16 * NI * WN;
@@ -30,7 +33,9 @@ __device__ __forceinline__ void gemm_epilogue_f32(const ConvGemm& p, epi_f32x4 (
     // Each wave transposes one 16-row fragment group at a time through its own LDS scratch (the stages are free
     // now) and writes whole 320-byte row segments with 16-byte lanes; the residual is read the same way.
     const bool split = p.splits > 1;
-    float* Cf = split ? (p.slabs + (long long)z * p.slab_stride) : p.C;
+    bool phased = false;
+    if constexpr (PH) phased = p.phases != 0;
+    float* Cf = split ? (p.slabs + (long long)z * p.slab_stride + (phased ? (long long)phase * p.M * p.N : 0ll)) : p.C;
     const int ldc = split ? p.N : p.ldc;
     const bool has_resid = !split && p.resid;
     const bool vec_ok = ((p.N & 3) == 0) && ((ldc & 3) == 0) && ((p.ldr & 3) == 0 || !has_resid);
@@ -133,7 +138,7 @@ __device__ __forceinline__ void gemm_epilogue_f32(const ConvGemm& p, epi_f32x4 (
     // the planes -- against wave-uniform row pointers that advance by 16 rows per group; the residual of group mi + 1 is requested before group mi is stored.  The general
     // form below executed ~3x the instructions per group and waited out every time-embedding load where it was issued.  Same values in the same order: acc + (bias + row)
 // (+ residual) in both forms.
-    if (!(p.variant & 64) && vec_ok && m0 + BM <= p.M && n0 + BN <= p.N) {
+    if (!(p.variant & 64) && !phased && vec_ok && m0 + BM <= p.M && n0 + BN <= p.N) {
         int smp0 = 0;
         bool one_smp = true;
         if (!split && p.rowvec) {
@@ -287,8 +292,9 @@ __device__ __forceinline__ void gemm_epilogue_f32(const ConvGemm& p, epi_f32x4 (
                     }
                     if (split) *reinterpret_cast<f32x4*>(Cf + (long long)m * ldc + n) = v;     // (Cf = this k slice's slab)
                     else {
-                        if (Cf) *reinterpret_cast<f32x4*>(Cf + (long long)m * ldc + n) = v;
-                        if (p.C3) s3_store4(reinterpret_cast<unsigned char*>(p.C3) + (long long)m * p.ldc3, n, v);
+                        const long long mo = phased ? ups_phase_row(m, phase, p.Hs, p.Ws) : (long long)m;
+                        if (Cf) *reinterpret_cast<f32x4*>(Cf + mo * ldc + n) = v;
+                        if (p.C3) s3_store4(reinterpret_cast<unsigned char*>(p.C3) + mo * p.ldc3, n, v);
                     }
                 }
             }
@@ -301,6 +307,7 @@ __device__ __forceinline__ void gemm_epilogue_f32(const ConvGemm& p, epi_f32x4 (
         const int m = m0 + (wm * MI + mi) * 16 + c15;
         if (m >= p.M) continue;
         const int smp = m / HoWo;
+        const long long mo = (phased && !split) ? ups_phase_row(m, phase, p.Hs, p.Ws) : (long long)m;
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
             const int n = n0 + (wn * NI + ni) * 16 + g4 * 4;
@@ -317,7 +324,7 @@ __device__ __forceinline__ void gemm_epilogue_f32(const ConvGemm& p, epi_f32x4 (
                         sv += cv;
                         if (p.resid) sv += p.resid[(long long)m * p.ldr + n + r];
                     }
-                    Cf[(long long)m * ldc + n + r] = sv;
+                    Cf[mo * ldc + n + r] = sv;
                 }
             }
         }

@@ -71,7 +71,23 @@ struct ConvGemm {
     int Cin_aux, kt_total_aux;
     int z_aux;                  // first slice of the auxiliary problem; 0: none
     const float* bias_aux;      // [N] or null
+    // Phase mode (k_gemm3p.hip only; every other launcher refuses phases != 0): conv3x3(nearest_2x(x)) as four 2x2 convolutions over the SOURCE grid, one per output pixel
+    // phase ph = py * 2 + px, each with its own folded weights (Engine::rebuild_folds: [4][N][4 Cin], k = (channel slice, tap a * 2 + b, 32 channels)).  The struct keeps the
+    // layer's description (KH = KW = 3, ups = 1, Ho = 2 Hs, Wo = 2 Ws) except: M = NB Hs Ws, the rows of ONE phase, and K = 4 Cin, kt_total = Cin / 8.  The M tiles are laid
+    // phase-major, ceil(M / BM) per phase, so no tile holds two phases; row m = (nb, y, x) of phase ph reads source pixels (y - 1 + py + a, x - 1 + px + b) and is output
+    // row ups_phase_row(m, ph, Hs, Ws).  Bias only: no rowvec / resid / geglu / z_aux / probe.  splits > 1: slabs [splits][4][M][N], slab_stride = 4 M N.
+    int phases;                 // 0 or 4
+    long long phase_stride;     // bytes between the phase images of Bt3
 };
+
+// output row of row m = (nb, y, x) of phase ph = py * 2 + px: pixel (2 y + py, 2 x + px) of sample nb in the [NB][2 Hs][2 Ws] result.  THE row map of a phase launch:
+// the epilogue (k_gemm_epi.hpp) and the split-K reduce (k_gemm.hip) both write through it.
+__host__ __device__ inline long long ups_phase_row(int m, int ph, int Hs, int Ws) {
+    const int hw = Hs * Ws;
+    const int nb = m / hw, rem = m - nb * hw;
+    const int y = rem / Ws, x = rem - y * Ws;
+    return ((long long)nb * (2 * Hs) + 2 * y + (ph >> 1)) * (2 * Ws) + 2 * x + (ph & 1);
+}
 
 // capacity of ConvGemm::probe in workgroups (24 words each); launch_conv_gemm3p refuses a probe launch with a larger grid
 constexpr int kGemmProbeBlocks = 1 << 13;
@@ -139,6 +155,10 @@ hipError_t launch_pack_conv_weight(const float* w_oihw, float* bt, int cout, int
 hipError_t launch_pack_linear_weight(const float* w_in_out, float* bt, int cin, int cout, hipStream_t s);
 // out [N][K] (rows ldo apart) = fp32(a [N][Cn] x b [Cn][K]) with fp64 accumulation, rounded once: the folded weights of Engine::rebuild_folds (load time only)
 hipError_t launch_fold_matmul_f64(const float* a, const float* b, float* out, int N, int Cn, int K, long long lda, long long ldb, long long ldo, hipStream_t s);
+// bt: a packed 3x3 weight [N][9 Cin] (Cin % 32 == 0) -> out [nph][N][4 Cin], the images of phases ph0 .. ph0 + nph - 1 of the phase image [4][N][4 Cin]: the folded 2x2 weights of the four pixel phases of conv3x3(nearest_2x(x)) (ConvGemm::phases):
+// out[py * 2 + px][n][(cs * 4 + a * 2 + b) * 32 + ci] = sum of the 1, 2 or 4 taps (ky, kx) with R_py[a][ky] = R_px[b][kx] = 1, R_0 = [[1,0,0],[0,1,1]], R_1 = [[1,1,0],[0,0,1]],
+// in fp64 (ky outer, kx inner), rounded once
+hipError_t launch_fold_ups_phase_f64(const float* bt, float* out, int N, int Cin, int ph0, int nph, hipStream_t s);
 
 // ---- flash-style attention on fp32 MFMA ---------------------------------------
 struct AttnParams {
