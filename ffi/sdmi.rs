@@ -65,6 +65,22 @@ pub struct SdmiSampler {
     pub reserved: [i64; 4],
 }
 
+/// `sdmi_ksampler` (include/sdmi.h "sigma-schedule samplers"): kind 0 euler (eta), 1 dpmpp_2m, 2 heun, 3 dpm2, 4 dpmpp_2s (eta), 5 dpmpp_sde (eta),
+/// 6 dpmpp_2m_sde (eta); schedule 0 model, 1 karras, 2 exponential, 3 uniform; rho 0 = 7; sigma_min / sigma_max 0 = the model's.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct SdmiKSampler {
+    pub kind: i32,
+    pub schedule: i32,
+    pub eta: f64,
+    pub rho: f64,
+    pub sigma_min: f64,
+    pub sigma_max: f64,
+    pub noise_seed: u64,
+    pub image_base: i64,
+    pub reserved: [i64; 4],
+}
+
 /// `sdmi_hires` (include/sdmi.h "hires fix"): the first pass's latent size, the resampling mode (0 nearest-exact, 1 bilinear, 2 bicubic;
 /// antialias for modes 1 and 2) and the img2img tail of the second pass (`hires_steps` 0 = n_steps, 0 < strength <= 1, noise stream `hires_seed + i`).
 #[repr(C)]
@@ -158,6 +174,15 @@ extern "C" {
                         rgb_out: *mut u8) -> c_int;
     fn sdmi_set_sampler(ctx: *mut c_void, sampler: *const SdmiSampler) -> c_int;
     fn sdmi_get_sampler(ctx: *mut c_void, out: *mut SdmiSampler) -> c_int;
+    fn sdmi_set_ksampler(ctx: *mut c_void, ksampler: *const SdmiKSampler) -> c_int;
+    fn sdmi_get_ksampler(ctx: *mut c_void, out: *mut SdmiKSampler, is_set: *mut i32) -> c_int;
+    fn sdmi_multi_set_ksampler(m: *mut c_void, ksampler: *const SdmiKSampler) -> c_int;
+    fn sdmi_ksampler_sigmas(ksampler: *const SdmiKSampler, alphas_cumprod: *const c_float, total: i32, n_steps: usize, sigmas: *mut c_double, capacity: i32,
+                            count: *mut i32) -> c_int;
+    fn sdmi_sigma_to_t(alphas_cumprod: *const c_float, total: i32, sigma: c_double, t: *mut c_double) -> c_int;
+    fn sdmi_ksampler_plan(ksampler: *const SdmiKSampler, alphas_cumprod: *const c_float, total: i32, n_steps: usize, strength: c_double, rows: *mut c_double,
+                          capacity: i32, count: *mut i32) -> c_int;
+    fn sdmi_op_timestep_embedding_f(ctx: *mut c_void, t: c_double, dim: i32, out: *mut c_float) -> c_int;
     fn sdmi_load_control_safetensors(ctx: *mut c_void, path: *const c_char) -> c_int;
     fn sdmi_control_ready(ctx: *mut c_void) -> c_int;
     fn sdmi_set_control(ctx: *mut c_void, control: *const SdmiControl) -> c_int;
@@ -407,6 +432,56 @@ impl StableDiffusionMi355 {
         let mut s = SdmiSampler { kind: 0, reserved0: 0, eta: 0.0, noise_seed: 0, image_base: 0, reserved: [0; 4] };
         check(unsafe { sdmi_get_sampler(self.ctx, &mut s) });
         s
+    }
+
+    /// A sigma-schedule sampler for every later sampling call (`sdmi_set_ksampler`, sticky; `None` clears).  It resets `set_sampler`'s choice, and any
+    /// `set_sampler` call clears it.
+    pub fn set_ksampler(&mut self, ksampler: Option<&SdmiKSampler>) -> Result<(), Box<dyn Error>> {
+        let st = unsafe { sdmi_set_ksampler(self.ctx, ksampler.map_or(std::ptr::null(), |k| k as *const SdmiKSampler)) };
+        if st != 0 { Err(last_error().into()) } else { Ok(()) }
+    }
+
+    /// The k-sampler in force, if one is set (`sdmi_get_ksampler`).
+    pub fn ksampler(&self) -> Option<SdmiKSampler> {
+        let mut k = SdmiKSampler::default();
+        let mut is_set = 0i32;
+        check(unsafe { sdmi_get_ksampler(self.ctx, &mut k, &mut is_set) });
+        if is_set != 0 { Some(k) } else { None }
+    }
+
+    /// The steps + 1 sigmas of `n_steps`, the last 0 (`sdmi_ksampler_sigmas`, host only).
+    pub fn ksampler_sigmas(ksampler: &SdmiKSampler, alphas_cumprod: &[f32], n_steps: usize) -> Result<Vec<f64>, Box<dyn Error>> {
+        let mut out = vec![0f64; alphas_cumprod.len() + 2];
+        let mut count = 0i32;
+        let st = unsafe { sdmi_ksampler_sigmas(ksampler, alphas_cumprod.as_ptr(), alphas_cumprod.len() as i32, n_steps, out.as_mut_ptr(), out.len() as i32, &mut count) };
+        if st != 0 { return Err(last_error().into()); }
+        out.truncate(count as usize);
+        Ok(out)
+    }
+
+    /// The fractional timestep of `sigma` (`sdmi_sigma_to_t`, host only).
+    pub fn sigma_to_t(alphas_cumprod: &[f32], sigma: f64) -> Result<f64, Box<dyn Error>> {
+        let mut t = 0f64;
+        if unsafe { sdmi_sigma_to_t(alphas_cumprod.as_ptr(), alphas_cumprod.len() as i32, sigma, &mut t) } != 0 { Err(last_error().into()) } else { Ok(t) }
+    }
+
+    /// One row per UNet evaluation: step, stage, t, sigma, cx, ce, h1, cz, cz2, qx, qe, a_end (`sdmi_ksampler_plan`, host only).
+    pub fn ksampler_plan(ksampler: &SdmiKSampler, alphas_cumprod: &[f32], n_steps: usize, strength: f64) -> Result<Vec<[f64; 12]>, Box<dyn Error>> {
+        let cap = 2 * (alphas_cumprod.len() + 1);
+        let mut out = vec![[0f64; 12]; cap];
+        let mut count = 0i32;
+        let st = unsafe {
+            sdmi_ksampler_plan(ksampler, alphas_cumprod.as_ptr(), alphas_cumprod.len() as i32, n_steps, strength, out.as_mut_ptr() as *mut c_double, cap as i32, &mut count)
+        };
+        if st != 0 { return Err(last_error().into()); }
+        out.truncate(count as usize);
+        Ok(out)
+    }
+
+    /// timestep_embedding at a fractional `t` (`sdmi_op_timestep_embedding_f`).
+    pub fn op_timestep_embedding_f(&mut self, t: f64, dim: i32) -> Result<Vec<f32>, Box<dyn Error>> {
+        let mut out = vec![0f32; dim.max(0) as usize];
+        if unsafe { sdmi_op_timestep_embedding_f(self.ctx, t, dim, out.as_mut_ptr()) } != 0 { Err(last_error().into()) } else { Ok(out) }
     }
 
     /// A LoRA adapter merged into the packed weights on the device (`sdmi_lora_*`; no reference counterpart).  The context must
@@ -754,6 +829,12 @@ impl StableDiffusionMi355Node {
             }
             Ok(Self { m, ctx_dim: cfg.ctx_dim as usize, image_bytes: 3 * 64 * (cfg.latent_h * cfg.latent_w) as usize })
         }
+    }
+
+    /// `StableDiffusionMi355::set_ksampler` on every device (`sdmi_multi_set_ksampler`); image_base per shard, as `set_sampler`.
+    pub fn set_ksampler(&mut self, ksampler: Option<&SdmiKSampler>) -> Result<(), Box<dyn Error>> {
+        let st = unsafe { sdmi_multi_set_ksampler(self.m, ksampler.map_or(std::ptr::null(), |k| k as *const SdmiKSampler)) };
+        if st != 0 { Err(last_error().into()) } else { Ok(()) }
     }
 
     /// `StableDiffusionMi355::set_sampler` on every device; each shard's image_base is the global index of its first image.

@@ -263,6 +263,62 @@ typedef struct sdmi_sampler {
 int sdmi_set_sampler(sdmi_ctx* ctx, const sdmi_sampler* sampler);
 int sdmi_get_sampler(sdmi_ctx* ctx, sdmi_sampler* out);
 
+/* ---- sigma-schedule samplers: Karras / exponential / uniform spacing, Heun, DPM2, DPM++ 2S / SDE / 2M SDE (no reference counterpart;
+ * DESIGN.md section 9i) ----
+ * The samplers of k-diffusion on a continuous sigma schedule, sigma(a) = sqrt((1 - a) / a), with fractional timesteps.  The engine keeps the VP latent
+ * x = x_k / sqrt(1 + sigma^2); in k-space, with D = x_k - sigma e, a step s -> s' and anc(s, s', eta): up = min(s', eta sqrt(s'^2 (s^2 - s'^2) / s^2)),
+ * down = sqrt(s'^2 - up^2):
+ *   0 euler(eta)        (d, u) = anc(s, s', eta); x_k' = x_k + e (d - s) + u z             (eta 0: Euler, eta 1: Euler-ancestral)
+ *   1 dpmpp_2m          sdmi_sampler's kind 1 on the schedule's sigmas, h = ln s - ln s'
+ *   2 heun              x2 = x_k + e1 (s' - s); e2 at s'; x_k' = x_k + (e1 + e2) / 2 (s' - s)
+ *   3 dpm2              s_m = sqrt(s s'); x2 = x_k + e1 (s_m - s); e2 at s_m; x_k' = x_k + e2 (s' - s)
+ *   4 dpmpp_2s(eta)     (d, u) = anc(s, s', eta), s_m = sqrt(s d); x2 = (s_m / s) x_k + (1 - s_m / s) D1; D2 at s_m; x_k' = (d / s) x_k + (1 - d / s) D2 + u z
+ *   5 dpmpp_sde(eta)    s_m = sqrt(s s'); (d1, u1) = anc(s, s_m, eta): x2 = (d1 / s) x_k + (1 - d1 / s) D1 + u1 z_a; D2 at s_m; (d2, u2) = anc(s, s', eta):
+ *                       x_k' = (d2 / s) x_k + (1 - d2 / s) D2 + u2 (alpha z_a + beta z_b), alpha = sqrt((s - s_m) / (s - s')), beta = sqrt((s_m - s') / (s - s')):
+ *                       the two increments of one Brownian path in sigma (k-diffusion's law at r = 1/2, not its numbers)
+ *   6 dpmpp_2m_sde(eta) h = ln s - ln s', g = eta h, B = -expm1(-h - g): x_k' = (s' / s) e^-g x_k + B D + [B / (2r) (D - D_last), r = h_last / h] + s' sqrt(-expm1(-2g)) z
+ * Where s' = 0 every kind takes the single evaluation x_k' = D, without noise.  Kinds 2 - 5 spend two UNet evaluations on each of the other steps.  History (depth 1,
+ * empty at the first step of a call): D for kinds 1 and 6, stage 1's e for 2 and 3, the step's start latent for 4 and 5.
+ * Schedules: n steps give n + 1 sigmas, the last 0.  With S_j = sigma(a[j]), smax / smin = sigma_max / sigma_min or S_total-1 / S_0:
+ *   0 model        sigma(a[ts_j]) over sdmi_sample_latent's own timesteps (quirk Q5: more than n of them where n does not divide total); sigma_min / sigma_max unused
+ *   1 karras       (smax^(1/rho) + i / (n - 1) (smin^(1/rho) - smax^(1/rho)))^rho, i = 0 .. n - 1 (n = 1: smax alone)
+ *   2 exponential  exp(linspace(ln smax, ln smin, n))
+ *   3 uniform      k-diffusion's get_sigmas: t = linspace(total - 1, 0, n), ln sigma = ln S interpolated linearly in t; sigma_min / sigma_max unused
+ * The UNet is evaluated at t = sdmi_sigma_to_t(sigma), a fraction (on schedule 0 the integer ts_j itself).
+ * Step noise: draw r of step s of the FULL schedule is the stream  noise_seed + image_base + b + ((uint64_t)(s + 1) << 32) + ((uint64_t)r << 62);  r = 0 is
+ * sdmi_sampler's rule, z_b of kind 5 is r = 1 (its z_a is drawn again from r = 0 in the second stage, never stored).
+ * img2img: with L steps the call runs the last k = min(L, (size_t)(strength L)) of them from x = sqrt(a0) z0 + sqrt(1 - a0) eps, a0 = 1 / (1 + sigma_start^2); the mask
+ * blend follows a step's LAST evaluation, with 1 / (1 + s'^2) for a_prev.  sdmi_sample_latent's init_latent is the VP latent at the schedule's first sigma.
+ * The two sticky states exclude each other: a successful sdmi_set_ksampler(non-NULL) resets the sdmi_sampler to its default, and any sdmi_set_sampler call (NULL included)
+ * clears the k-sampler.  With no k-sampler set every call runs the launches and gives the bits it gave before.  A ControlNet window counts the call's STEPS: both
+ * evaluations of a step agree.  Out of scope: LMS / PLMS on non-uniform schedules, UniPC, s_churn, v-prediction, bit-compatibility with k-diffusion's noise. */
+typedef struct sdmi_ksampler {
+    int32_t kind;      /* 0 euler (eta), 1 dpmpp_2m, 2 heun, 3 dpm2, 4 dpmpp_2s (eta), 5 dpmpp_sde (eta), 6 dpmpp_2m_sde (eta) */
+    int32_t schedule;  /* 0 model (the reference's integer timesteps), 1 karras, 2 exponential, 3 uniform */
+    double eta;        /* 0..1; must be 0 for kinds 1, 2, 3 */
+    double rho;        /* karras only; 0 = 7 */
+    double sigma_min, sigma_max;   /* 0 = the model's sigma(a[0]) / sigma(a[total-1]); else inside that range, min < max */
+    uint64_t noise_seed; int64_t image_base; int64_t reserved[4];
+} sdmi_ksampler;
+/* Sticky; NULL clears.  SDMI_ERR_INVALID -- and nothing changes -- for an unknown kind or schedule, eta outside [0, 1] or NaN, eta != 0 for kinds 1 - 3, rho < 0 or
+ * not finite, a sigma bound that is negative, not finite, outside the model's range or min >= max. */
+int sdmi_set_ksampler(sdmi_ctx* ctx, const sdmi_ksampler* ksampler);
+/* *is_set = 1 and *out = the k-sampler in force, or *is_set = 0 and *out zeroed */
+int sdmi_get_ksampler(sdmi_ctx* ctx, sdmi_ksampler* out, int32_t* is_set);
+/* Host only, f64, no device: THE implementation of the schedules and samplers above (the engine calls it).
+ * sigmas: the *count = steps + 1 sigmas of n_steps, the last 0.  sigma_to_t: k-diffusion's rule -- low = the last j <= total - 2 with ln S_j <= ln sigma,
+ * w = clamp((ln S_low - ln sigma) / (ln S_low - ln S_low+1), 0, 1), t = low + w; exactly j at S_j.
+ * plan: one row of 12 doubles per UNet evaluation of the call (strength 1: txt2img; else the img2img tail),
+ *     step (index in the full schedule), stage (0 / 1), t, sigma, cx, ce, h1, cz, cz2, qx, qe, a_end:
+ *     q = qx x + qe e (pushed to the one history slot);  x' = cx x + ce e + h1 q_-1 + cz z + cz2 z2  on the VP latent, z = draw 0 and z2 = draw 1 of the row's step;
+ *     a_end = 1 / (1 + s'^2) on a step's last evaluation, -1 otherwise.
+ * SDMI_ERR_INVALID: a struct sdmi_set_ksampler refuses, n_steps outside 1 .. total, strength outside (0, 1] or leaving no step, capacity too small (in entries of the
+ * output: sigmas, or rows; *count still receives the number needed), a null pointer. */
+int sdmi_ksampler_sigmas(const sdmi_ksampler* ksampler, const float* alphas_cumprod, int32_t total, size_t n_steps, double* sigmas, int32_t capacity, int32_t* count);
+int sdmi_sigma_to_t(const float* alphas_cumprod, int32_t total, double sigma, double* t);
+int sdmi_ksampler_plan(const sdmi_ksampler* ksampler, const float* alphas_cumprod, int32_t total, size_t n_steps, double strength, double* rows, int32_t capacity,
+                       int32_t* count);
+
 /* ---- ControlNet (SD v1; no reference counterpart) -----------------------------------------------------
  * A context created with sdmi_config.control_hint_ch = 3 has a fourth weight group, "controlnet/...": a second copy of the UNet's time MLP
  * (controlnet/lin1_time_embed, lin2_time_embed), its 12 input blocks and its middle block under the UNet's own names, the eight hint convolutions
@@ -626,6 +682,8 @@ int sdmi_sample_image_sharded(sdmi_multi* m, const float* context, int32_t T, co
 /* sdmi_set_sampler on every device context; each shard's image_base is overridden with the global index of its first image, so the
  * step noise, like the start noise, does not depend on the device count.  NULL restores the default. */
 int sdmi_multi_set_sampler(sdmi_multi* m, const sdmi_sampler* sampler);
+/* sdmi_set_ksampler on every device context (checked once; NULL clears); image_base per shard, as sdmi_multi_set_sampler */
+int sdmi_multi_set_ksampler(sdmi_multi* m, const sdmi_ksampler* ksampler);
 /* the contiguous global image range [begin, end) device `rank` of `n_ranks` samples (host only): the partition rule of
  * sdmi_sample_image_sharded, and of the one-process-per-GPU launcher (bench.py / sharding.py use the same rule) */
 int sdmi_shard_range(int32_t n_images, int32_t rank, int32_t n_ranks, int32_t* begin, int32_t* end);
@@ -759,6 +817,8 @@ int sdmi_op_unpack_tensor(sdmi_ctx* ctx, const void* raw, int32_t dtype, int32_t
 int sdmi_op_geglu_forward(sdmi_ctx* ctx, const float* x, const float* weight, const float* bias, int32_t rows, int32_t cin,
                           int32_t hidden, float* out);
 int sdmi_op_timestep_embedding(sdmi_ctx* ctx, int32_t t, int32_t dim, float* out);
+/* the same for a fractional t (the k-samplers' evaluation times): t is narrowed to f32 once on the host; at an integer t the bits of the call above */
+int sdmi_op_timestep_embedding_f(sdmi_ctx* ctx, double t, int32_t dim, float* out);
 
 /* ---- tuning / introspection ---------------------------------------------------- */
 /* "key=value" option of one context (Engine::set_option), e.g. "profile=1", "gemm_tile=auto".  No reference counterpart (the

@@ -52,6 +52,12 @@ class SdmiSampler(C.Structure):
                 ("reserved", C.c_int64 * 4)]
 
 
+class SdmiKSampler(C.Structure):
+    """sdmi_ksampler: a sigma-schedule sampler (sdmi_set_ksampler)"""
+    _fields_ = [("kind", C.c_int32), ("schedule", C.c_int32), ("eta", C.c_double), ("rho", C.c_double), ("sigma_min", C.c_double), ("sigma_max", C.c_double),
+                ("noise_seed", C.c_uint64), ("image_base", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+
 class SdmiControl(C.Structure):
     """sdmi_control: the sticky ControlNet state of a context (sdmi_set_control)"""
     _fields_ = [("hint_rgb", C.POINTER(C.c_uint8)), ("n_hint", C.c_int32), ("hint_h", C.c_int32), ("hint_w", C.c_int32), ("strength", C.c_double),
@@ -77,6 +83,8 @@ class SdmiPromptOpts(C.Structure):
 _F = C.POINTER(C.c_float)
 _HIRES = C.POINTER(SdmiHires)
 _SAMPLER = C.POINTER(SdmiSampler)
+_KSAMPLER = C.POINTER(SdmiKSampler)
+_F64 = C.POINTER(C.c_double)
 _VIEW = C.POINTER(SdmiOpView)
 _U8 = C.POINTER(C.c_uint8)
 _CTX = C.c_void_p
@@ -122,6 +130,11 @@ SIGNATURES = {
     "sdmi_inpaint_image_dev": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_size_t, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(SdmiInpaint), C.c_void_p, C.c_uint64, C.c_void_p]),
     "sdmi_set_sampler": (C.c_int, [_CTX, _SAMPLER]),
     "sdmi_get_sampler": (C.c_int, [_CTX, _SAMPLER]),
+    "sdmi_set_ksampler": (C.c_int, [_CTX, _KSAMPLER]),
+    "sdmi_get_ksampler": (C.c_int, [_CTX, _KSAMPLER, C.POINTER(C.c_int32)]),
+    "sdmi_ksampler_sigmas": (C.c_int, [_KSAMPLER, _F, C.c_int32, C.c_size_t, _F64, C.c_int32, C.POINTER(C.c_int32)]),
+    "sdmi_sigma_to_t": (C.c_int, [_F, C.c_int32, C.c_double, _F64]),
+    "sdmi_ksampler_plan": (C.c_int, [_KSAMPLER, _F, C.c_int32, C.c_size_t, C.c_double, _F64, C.c_int32, C.POINTER(C.c_int32)]),
     "sdmi_load_control_safetensors": (C.c_int, [_CTX, C.c_char_p]),
     "sdmi_control_ready": (C.c_int, [_CTX]),
     "sdmi_set_control": (C.c_int, [_CTX, C.POINTER(SdmiControl)]),
@@ -140,6 +153,7 @@ SIGNATURES = {
     "sdmi_op_resize": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),
     "sdmi_op_unpack_tensor": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, _F]),
     "sdmi_multi_set_sampler": (C.c_int, [C.c_void_p, _SAMPLER]),
+    "sdmi_multi_set_ksampler": (C.c_int, [C.c_void_p, _KSAMPLER]),
     "sdmi_lora_create": (C.c_int, [_CTX, C.POINTER(C.c_void_p)]),
     "sdmi_lora_add": (C.c_int, [C.c_void_p, C.c_char_p, _F, _F, C.c_int32, C.c_float]),
     "sdmi_lora_load_safetensors": (C.c_int, [_CTX, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), _I32, _I32]),
@@ -203,6 +217,7 @@ SIGNATURES = {
     "sdmi_op_geglu": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F]),
     "sdmi_op_qkv_attention_ragged": (C.c_int, [_CTX, _F, _F, _F, _I32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),
     "sdmi_op_timestep_embedding": (C.c_int, [_CTX, C.c_int32, C.c_int32, _F]),
+    "sdmi_op_timestep_embedding_f": (C.c_int, [_CTX, C.c_double, C.c_int32, _F]),
     "sdmi_set_option": (C.c_int, [_CTX, C.c_char_p, C.c_char_p]),
     "sdmi_last_call_stats": (C.c_int, [_CTX, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "sdmi_profile_stats": (C.c_int, [_CTX, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -2599,6 +2599,22 @@ void Engine::unet_release() {
 // 2*n_steps forwards.
 void Engine::unet_prepare(const float* ctx_packed, int nb, int t_max, const int* kv_len_host,
                           const std::vector<int>& ts, int n_images, bool window, bool force_control) {
+    unet_prepare_rows(ctx_packed, nb, t_max, kv_len_host, ts.data(), nullptr, (int)ts.size(), n_images, window, force_control);
+}
+
+void Engine::unet_prepare(const float* ctx_packed, int nb, int t_max, const int* kv_len_host, const std::vector<double>& tf, const std::vector<int>& eval_step,
+                          int call_steps, int n_images) {
+    if (tf.empty() || eval_step.size() != tf.size() || call_steps < 1) throw Error(SDMI_ERR_STATE, "unet_prepare: bad evaluation plan");
+    std::vector<float> t32(tf.size());
+    for (size_t i = 0; i < tf.size(); ++i) t32[i] = (float)tf[i];   // THE narrowing of the evaluation times
+    unet_prepare_rows(ctx_packed, nb, t_max, kv_len_host, nullptr, t32.data(), (int)t32.size(), n_images, /*window=*/true, /*force_control=*/false);
+    us_.eval_step = eval_step;
+    us_.call_steps = call_steps;
+}
+
+// ti: S integer timesteps, or null and tf: S fractional ones -- one row of every per-step table each
+void Engine::unet_prepare_rows(const float* ctx_packed, int nb, int t_max, const int* kv_len_host, const int* ti, const float* tf, int S, int n_images, bool window,
+                               bool force_control) {
     unet_release();
     // a controlled call (sticky state, sdmi_set_control): strength 0 is the plain call, launch for launch (force_control: control_residuals_dev, which ignores the strength)
     const bool ctrl = ctrl_.set && (ctrl_.strength != 0.0 || force_control) && n_images > 0;
@@ -2610,18 +2626,20 @@ void Engine::unet_prepare(const float* ctx_packed, int nb, int t_max, const int*
         if (ctrl_.n_hint != 1 && ctrl_.n_hint != n_images)
             throw Error(SDMI_ERR_INVALID, "control: the call has n = " + std::to_string(n_images) + " images but the control was set with n_hint = " + std::to_string(ctrl_.n_hint));
     }
-    const int S = (int)ts.size(), mc = cfg_.model_channels, ed = 4 * mc, cd = cfg_.ctx_dim;
+    const int mc = cfg_.model_channels, ed = 4 * mc, cd = cfg_.ctx_dim;
     us_.nb = nb; us_.t_max = t_max; us_.steps = S;
     us_.kv_len_host.assign(kv_len_host, kv_len_host + nb);
     auto own = [&](size_t bytes) { void* p = pool_.alloc(bytes); us_.owned.push_back(p); return p; };
     us_.kv_len_dev = (int*)own(nb * sizeof(int));
+    static_assert(sizeof(int) == sizeof(float), "one buffer serves both forms of the timesteps");
     int* t_dev = (int*)own(S * sizeof(int));
     SDMI_HIP(hipMemcpyAsync(us_.kv_len_dev, us_.kv_len_host.data(), nb * sizeof(int), hipMemcpyHostToDevice, stream_));
-    SDMI_HIP(hipMemcpyAsync(t_dev, ts.data(), S * sizeof(int), hipMemcpyHostToDevice, stream_));
+    SDMI_HIP(hipMemcpyAsync(t_dev, ti ? (const void*)ti : (const void*)tf, S * sizeof(int), hipMemcpyHostToDevice, stream_));
     SDMI_HIP(hipStreamSynchronize(stream_));  // host vectors may go away; once per call, outside the step loop
 
     Buf te(this, (size_t)S * mc * 4), e1(this, (size_t)S * ed * 4), e2(this, (size_t)S * ed * 4);
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_timestep_embedding(t_dev, S, mc, te.f(), stream_)); }
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(ti ? launch_timestep_embedding(t_dev, S, mc, te.f(), stream_)
+                                                  : launch_timestep_embedding_f(reinterpret_cast<const float*>(t_dev), S, mc, te.f(), stream_)); }
     count_kernel();
     gemm(te.f(), S, lin1_time_.bt, lin1_time_.bias, mc, ed, e1.f(), ed, nullptr, 0, /*dt=*/0);
     { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_silu(e1.f(), e1.f(), (long long)S * ed, stream_)); }
@@ -3128,11 +3146,13 @@ void Engine::sample_latent_dev(const float* context, int n, int T, const float* 
     const size_t step_size = total / n_steps;                       // :111
     std::vector<int> ts;
     for (long long t = (long long)total - 1; t >= 0; t -= (long long)step_size) ts.push_back((int)t);  // :123
+    std::vector<double> kplan;   // a k-sampler plans its own schedule; init_latent is the VP latent at its first sigma
+    if (kset_) kplan = kplan_for(n_steps, 1.0, nullptr);
     sample_loop(context, n, T, uncond, Tu, scale, ts, step_size, [&](float* latent, float* unet_in, long long per_half) {
         SDMI_HIP(launch_nchw_to_nhwc(init_latent, latent, n, 4, H, W, 1.0f, stream_));
         { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_dup_latent(latent, unet_in, per_half, stream_)); }
         count_kernel(); count_kernel();
-    }, nullptr, latent_out, out_nhwc);
+    }, nullptr, latent_out, out_nhwc, nullptr, kset_ ? &kplan : nullptr);
 }
 
 void Engine::check_sampler(const sdmi_sampler& s) {
@@ -3142,14 +3162,30 @@ void Engine::check_sampler(const sdmi_sampler& s) {
 }
 
 void Engine::set_sampler(const sdmi_sampler* s) {
-    if (!s) { sampler_ = sdmi_sampler{}; return; }
-    check_sampler(*s);
-    sampler_ = *s;
+    if (s) check_sampler(*s);
+    sampler_ = s ? *s : sdmi_sampler{};
+    ksampler_ = sdmi_ksampler{};   // the two sticky states exclude each other
+    kset_ = false;
+}
+
+void Engine::set_ksampler(const sdmi_ksampler* k) {
+    if (!k) { ksampler_ = sdmi_ksampler{}; kset_ = false; return; }
+    check_ksampler(*k, alphas_.empty() ? nullptr : alphas_.data(), (int)alphas_.size());
+    ksampler_ = *k;
+    kset_ = true;
+    sampler_ = sdmi_sampler{};
+}
+
+std::vector<double> Engine::kplan_for(size_t n_steps, double strength, double* a0) const {
+    std::vector<double> rows = ksampler_plan(ksampler_, alphas_.data(), (int)alphas_.size(), n_steps, strength);
+    const double s0 = rows[KP_SIGMA];
+    if (a0) *a0 = 1.0 / (1.0 + s0 * s0);
+    return rows;
 }
 
 void Engine::sample_loop(const float* context, int n, int T, const float* uncond, int Tu, double scale, const std::vector<int>& ts,
                          size_t step_size, const std::function<void(float* latent, float* unet_in, long long per_half)>& start,
-                         const Blend* blend, float* latent_out, bool out_nhwc, const float* cond_nhwc) {
+                         const Blend* blend, float* latent_out, bool out_nhwc, const float* cond_nhwc, const std::vector<double>* kplan) {
     const int H = lat_h_, W = lat_w_, cd = cfg_.ctx_dim;
     const int nb = 2 * n, t_max = std::max(T, Tu);
 
@@ -3163,6 +3199,17 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
                                 hipMemcpyDeviceToDevice, stream_));
     std::vector<int> kv(nb);
     for (int b = 0; b < n; ++b) { kv[b] = Tu; kv[n + b] = T; }
+    const size_t n_eval = kplan ? kplan->size() / KPLAN_COLS : 0;
+    if (kplan) {   // a k-sampler: one row of the time tables per UNet evaluation, at the plan's fractional times
+        std::vector<double> tf(n_eval);
+        std::vector<int> eval_step(n_eval);
+        const int first_step = (int)(*kplan)[KP_STEP];
+        for (size_t i = 0; i < n_eval; ++i) {
+            tf[i] = (*kplan)[i * KPLAN_COLS + KP_T];
+            eval_step[i] = (int)(*kplan)[i * KPLAN_COLS + KP_STEP] - first_step;
+        }
+        unet_prepare(ctx.f(), nb, t_max, kv.data(), tf, eval_step, eval_step.back() + 1, n);
+    } else
     unet_prepare(ctx.f(), nb, t_max, kv.data(), ts, n);
 
     const long long per_half = (long long)n * H * W * 4;
@@ -3171,7 +3218,7 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
     std::unique_ptr<Buf> unet_in_c;
     if (cond_nhwc) unet_in_c.reset(new Buf(this, (size_t)(2 * per_half / 4) * unet_in_padded() * 4));
     // sampler choice: the coefficient table of the call and its history slots (x0 for DPM-Solver++(2M), three e for PLMS)
-    const bool custom = sampler_.kind != 0 || sampler_.eta != 0.0;
+    const bool custom = !kplan && (sampler_.kind != 0 || sampler_.eta != 0.0);
     const int depth = !custom ? 0 : sampler_.kind == 1 ? 1 : sampler_.kind == 2 ? 3 : 0;
     std::vector<double> coefs;
     std::unique_ptr<Buf> hist[3];
@@ -3181,8 +3228,29 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
         if (st != SDMI_OK) throw Error(st, "sample_loop: sdmi_sampler_coefs refused the schedule");
         for (int k = 0; k < depth; ++k) hist[k].reset(new Buf(this, per_half * 4));
     }
+    if (kplan && ksampler_.kind != 0) hist[0].reset(new Buf(this, per_half * 4));   // depth 1 everywhere; euler keeps nothing
     start(latent.f(), unet_in.f(), per_half);
-    for (size_t s = 0; s < ts.size(); ++s) {
+    for (size_t i = 0; i < n_eval; ++i) {   // the k-sampler's loop: one UNet run and ONE update launch per evaluation
+        const double* k = &(*kplan)[i * KPLAN_COLS];
+        if (cond_nhwc) assemble_unet_in(unet_in.f(), cond_nhwc, nb, n, unet_in_c->f());
+        unet_run(cond_nhwc ? unet_in_c->f() : unet_in.f(), nb, (int)i, eps.f(), opt_cfg_share_ != 0);
+        const int depth = hist[0] ? 1 : 0;
+        SamplerStep p{};
+        p.scale = (float)scale;
+        p.cx = (float)k[KP_CX]; p.ce = (float)k[KP_CE]; p.h[0] = (float)k[KP_H1]; p.cz = (float)k[KP_CZ]; p.cz2 = (float)k[KP_CZ2];
+        p.qx = (float)k[KP_QX]; p.qe = (float)k[KP_QE];
+        p.n_hist = (depth && i > 0) ? 1 : 0;   // (history starts empty; where the row's h1 is 0 the slot is read and weighs nothing)
+        const bool last = k[KP_AEND] >= 0.0;   // the mask blend follows a step's last evaluation only
+        if (last) { p.blend_prev = (float)std::sqrt(k[KP_AEND]); p.blend_dir = (float)std::sqrt(1.0 - k[KP_AEND]); }
+        const float* q_prev[3] = {p.n_hist ? hist[0]->f() : nullptr, nullptr, nullptr};
+        const uint64_t key = ksampler_.noise_seed + (uint64_t)ksampler_.image_base + (((uint64_t)k[KP_STEP] + 1) << 32);
+        const bool bl = blend && last;
+        { ProfScope ps_o(this, PC_OTHER);
+          SDMI_HIP(launch_sampler_step(eps.f(), latent.f(), unet_in.f(), per_half, (long long)H * W, p, depth, q_prev, depth ? hist[0]->f() : nullptr, key,
+                                       key + (1ull << 62), bl ? blend->mask : nullptr, bl ? blend->z0 : nullptr, bl ? blend->eps : nullptr, stream_)); }
+        count_kernel();
+    }
+    for (size_t s = 0; s < (kplan ? 0 : ts.size()); ++s) {
         const size_t t = (size_t)ts[s];
         const double cur = (double)alphas_[t];                                           // :124-129
         const double prev = t >= step_size ? (double)alphas_[t - step_size] : 1.0;       // :131-140
@@ -3210,7 +3278,7 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
             const uint64_t s_full = (uint64_t)((alphas_.size() - 1 - t) / step_size);
             const uint64_t key = sampler_.noise_seed + (uint64_t)sampler_.image_base + ((s_full + 1) << 32);
             ProfScope ps_o(this, PC_OTHER);
-            SDMI_HIP(launch_sampler_step(eps.f(), latent.f(), unet_in.f(), per_half, (long long)H * W, p, depth, q_prev, q_out, key,
+            SDMI_HIP(launch_sampler_step(eps.f(), latent.f(), unet_in.f(), per_half, (long long)H * W, p, depth, q_prev, q_out, key, 0,
                                          blend ? blend->mask : nullptr, blend ? blend->z0 : nullptr, blend ? blend->eps : nullptr, stream_));
         } else
         if (blend) { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_cfg_ddim_masked(eps.f(), latent.f(), unet_in.f(), per_half, c, blend->mask, blend->z0, blend->eps, stream_)); }
@@ -3233,6 +3301,11 @@ std::vector<int> Engine::img2img_schedule(int n, int T, int Tu, size_t n_steps, 
     check_batch(n);
     const size_t total = alphas_.size();
     if (n_steps == 0 || n_steps > total) throw Error(SDMI_ERR_INVALID, "img2img: n_steps out of range");
+    *step_size = total / n_steps;
+    if (kset_) {   // a k-sampler applies the strength rule to its own steps: kplan_for refuses what leaves none; ts is unused then
+        (void)kplan_for(n_steps, strength, nullptr);
+        return std::vector<int>(1, 0);
+    }
     std::vector<int> ts(total);
     int32_t count = 0;
     const int st = sdmi_img2img_timesteps((int32_t)total, n_steps, strength, ts.data(), (int32_t)total, &count);
@@ -3250,7 +3323,9 @@ void Engine::img2img_latent_dev(const float* context, int n, int T, const float*
     struct PoolPtr { DevPool& pool; float* p; ~PoolPtr() { if (p) pool.free(p); } } cond{pool_, nullptr};
     if (cond_nchw) cond.p = cond_to_nhwc(cond_nchw, n);
     const long long hw = (long long)lat_h_ * lat_w_, elems = (long long)n * hw * 4;
-    const double a0 = (double)alphas_[ts[0]];
+    double a0 = (double)alphas_[ts[0]];
+    std::vector<double> kplan;
+    if (kset_) kplan = kplan_for(n_steps, strength, &a0);
     const float sqrt_a = (float)std::sqrt(a0), sqrt_1ma = (float)std::sqrt(1.0 - a0);
     Buf z0k(this, mask ? elems * 4 : 256), e0k(this, mask ? elems * 4 : 256);   // z0 and eps for the blend (NHWC)
     const Blend blend{mask, z0k.f(), e0k.f()};
@@ -3258,7 +3333,7 @@ void Engine::img2img_latent_dev(const float* context, int n, int T, const float*
         { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_img2img_start(z0, false, noise, seed, sqrt_a, sqrt_1ma, latent, unet_in, per_half,
                                                                         mask ? z0k.f() : nullptr, mask ? e0k.f() : nullptr, n, hw, stream_)); }
         count_kernel();
-    }, mask ? &blend : nullptr, latent_out, false, cond.p);
+    }, mask ? &blend : nullptr, latent_out, false, cond.p, kset_ ? &kplan : nullptr);
 }
 
 void Engine::img2img_image_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps,
@@ -3269,7 +3344,9 @@ void Engine::img2img_image_dev(const float* context, int n, int T, const float* 
     const std::vector<int> ts = img2img_schedule(n, T, Tu, n_steps, strength, &step_size);
     const int H = lat_h_, W = lat_w_;
     const long long hw = (long long)H * W, elems = (long long)n * hw * 4;
-    const double a0 = (double)alphas_[ts[0]];
+    double a0 = (double)alphas_[ts[0]];
+    std::vector<double> kplan;
+    if (kset_) kplan = kplan_for(n_steps, strength, &a0);
     const float sqrt_a = (float)std::sqrt(a0), sqrt_1ma = (float)std::sqrt(1.0 - a0);
     Buf z0k(this, mask ? elems * 4 : 256), e0k(this, mask ? elems * 4 : 256);
     const Blend blend{mask, z0k.f(), e0k.f()};
@@ -3286,7 +3363,7 @@ void Engine::img2img_image_dev(const float* context, int n, int T, const float* 
             count_kernel();
             release(q8);
         }
-    }, mask ? &blend : nullptr, latent_out, false, cond_nhwc);
+    }, mask ? &blend : nullptr, latent_out, false, cond_nhwc, kset_ ? &kplan : nullptr);
 }
 
 // ---- inpainting (unet_in_ch = 9; include/sdmi.h "inpainting") ---------------------------------------------------------
@@ -4143,6 +4220,15 @@ void Engine::op_geglu(const float* proj, int rows, int hidden, float* out) {
         return;
     }
     SDMI_HIP(launch_geglu(proj, out, rows, hidden, stream_));
+}
+
+void Engine::op_timestep_embedding_f(double t, int dim, float* out) {
+    const float tf = (float)t;
+    Buf td(this, sizeof(float));
+    SDMI_HIP(hipMemcpyAsync(td.p, &tf, sizeof(float), hipMemcpyHostToDevice, stream_));
+    SDMI_HIP(hipStreamSynchronize(stream_));
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_timestep_embedding_f((const float*)td.p, 1, dim, out, stream_)); }
+    SDMI_HIP(hipStreamSynchronize(stream_));
 }
 
 void Engine::op_timestep_embedding(int t, int dim, float* out) {

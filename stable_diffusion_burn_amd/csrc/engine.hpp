@@ -10,6 +10,7 @@
 // projections and cross-attention K/V are hoisted out of the step loop, and all
 // launches go to one HIP stream with no host synchronisation inside the loop.
 #pragma once
+#include "ksampler.hpp"
 #include <hip/hip_runtime.h>
 
 #include <functional>
@@ -265,6 +266,14 @@ public:
     static void check_sampler(const sdmi_sampler& s);
     void set_sampler(const sdmi_sampler* s);
     const sdmi_sampler& sampler() const { return sampler_; }
+    // sigma-schedule samplers (sdmi_set_ksampler; ksampler.hpp): the second sticky state, read wherever sampler_ is.  The two exclude each
+    // other: setting one resets the other (set_sampler, null included, clears this one).  set_image_base: the sharded path's per-shard key offset, on whichever is set.
+    void set_ksampler(const sdmi_ksampler* k);
+    bool ksampler_set() const { return kset_; }
+    const sdmi_ksampler& ksampler() const { return ksampler_; }
+    void set_image_base(int64_t base) { sampler_.image_base = base; ksampler_.image_base = base; }
+    const std::vector<float>& alphas() const { return alphas_; }
+    void op_timestep_embedding_f(double t, int dim, float* out);
     void decode_latent_dev(const float* latent_nchw, int n, float in_scale, float* img_nchw, uint8_t* rgb_u8);
     // kv_len_host: null, or a HOST array [n] of per-sample key counts (1 .. nk; the CFG batch's cross attention, Engine::attention's kv_len)
     void qkv_attention_dev(const float* q, const float* k, const float* v, const float* mask, int mask_ld, int n,
@@ -522,12 +531,22 @@ private:
     // n_images (a controlled call): the images of the call, nb = n_images or 2 n_images (a CFG batch); window: false = every step is controlled (unet_forward)
     void unet_prepare(const float* ctx_packed, int nb, int t_max, const int* kv_len_host, const std::vector<int>& ts, int n_images = 0, bool window = true,
                       bool force_control = false);   // force_control: a controlled prepare whatever the strength (control_residuals_dev)
+    // the k-samplers' form: one row per UNet EVALUATION at the fractional times tf (f64 narrowed once); eval_step[i] = the step of the call
+    // evaluation i belongs to, of call_steps -- what the ControlNet window counts, so that both evaluations of a step agree
+    void unet_prepare(const float* ctx_packed, int nb, int t_max, const int* kv_len_host, const std::vector<double>& tf, const std::vector<int>& eval_step, int call_steps,
+                      int n_images);
+    void unet_prepare_rows(const float* ctx_packed, int nb, int t_max, const int* kv_len_host, const int* ti, const float* tf, int S, int n_images, bool window,
+                           bool force_control);
     void run_block(const UBlock& b, const Act& in, Act& y, int step);   // one UNet block; its last kernel writes y (dense or a channel slice)
     // ControlNet: the hint embedding [n][h][w][mc] fp32 of n hints on the device (the caller releases it); the control encoder on the assembled UNet input -> r[13]
     // dense, in the engine's activation type (the caller releases them); whether step `step` of the call in flight is controlled
     Act control_hint_embed(const uint8_t* hint_rgb_dev, int n, int hint_h, int hint_w);
     void control_run(const float* x_nhwc, int nb, int step, Act (&r)[13]);
-    bool control_on(int step) const { return us_.ctrl && (!us_.ctrl_window || control_step_on(ctrl_.start, ctrl_.end, step, us_.steps)); }
+    bool control_on(int step) const {
+        if (!us_.ctrl || !us_.ctrl_window) return us_.ctrl;
+        if (!us_.eval_step.empty()) return control_step_on(ctrl_.start, ctrl_.end, us_.eval_step[(size_t)step], us_.call_steps);
+        return control_step_on(ctrl_.start, ctrl_.end, step, us_.steps);
+    }
     void unet_release();
     void unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bool cfg_pair = false);
     void decode_one(const float* z_nhwc, int n, Act& img);
@@ -541,7 +560,10 @@ private:
     struct Blend { const float* mask; const float* z0; const float* eps; };
     void sample_loop(const float* context, int n, int T, const float* uncond, int Tu, double scale, const std::vector<int>& ts,
                      size_t step_size, const std::function<void(float* latent, float* unet_in, long long per_half)>& start,
-                     const Blend* blend, float* latent_out, bool out_nhwc = false, const float* cond_nhwc = nullptr);
+                     const Blend* blend, float* latent_out, bool out_nhwc = false, const float* cond_nhwc = nullptr, const std::vector<double>* kplan = nullptr);
+    // kplan (a k-sampler is set): the rows of ksampler_plan for the call -- the loop walks its evaluations instead of ts, which is unused then.
+    // kplan_for: the plan of a call of n_steps at `strength`, *a0 = 1 / (1 + sigma_start^2), the alpha of the img2img start.
+    std::vector<double> kplan_for(size_t n_steps, double strength, double* a0) const;
     // cond_nhwc (a conditioned model): [n][hw][padded_in_ch - 4]; every unet_run is preceded by assemble_unet_in into a buffer of the call
     float* cond_to_nhwc(const float* cond_nchw, int n);
     void assemble_unet_in(const float* unet_in, const float* cond_nhwc, int rows, int n, float* dst);
@@ -624,6 +646,8 @@ private:
     int opt_fp8_linear_ = 0;         // precision = 2: 0 (default: the accuracy budget of 6e-2 final-latent relative RMS) = MXFP8 on the ResBlock / ResnetBlock 3x3
                                      // convolutions only; 1 = also the transformer blocks' Linear layers and the 1x1 / up / down convolutions (8.1e-2)
     sdmi_sampler sampler_{};          // all zero: kind 0, eta 0
+    sdmi_ksampler ksampler_{};        // the k-sampler in force where kset_
+    bool kset_ = false;
     struct Control { bool set = false; uint8_t* hint_dev = nullptr; size_t hint_bytes = 0; int n_hint = 0, hint_h = 0, hint_w = 0; double strength = 1, start = 0, end = 1; } ctrl_;
     int opt_op_f32_ = 0;             // tests: op_conv2d runs the fp32 route (fp32 weight, input and output) at every precision -- the route of the ControlNet hint convolutions
     hipStream_t stream_ = nullptr;
@@ -689,6 +713,8 @@ private:
     // per-call UNet state
     struct UNetState {
         int nb = 0, t_max = 0, steps = 0;
+        std::vector<int> eval_step;   // a k-sampler's call: the step of the call each evaluation (row) belongs to, of call_steps; empty otherwise
+        int call_steps = 0;
         std::vector<float*> temb;   // per ResBlock [steps][cout]
         std::vector<float*> kc, vc; // per SpatialTransformer [nb][t_max][c]
         int* kv_len_dev = nullptr;

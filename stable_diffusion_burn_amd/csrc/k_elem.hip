@@ -225,6 +225,21 @@ __global__ void timestep_embedding_kernel(const int* __restrict__ t, int n_t, in
     }
 }
 
+// The same embedding at a fractional timestep (the sigma-schedule samplers): t arrives as f32, narrowed once from the host's f64.  The
+// arithmetic is the int kernel's from `(float)t[s]` on, so an integer t gives its bits.
+__global__ void timestep_embedding_f_kernel(const float* __restrict__ t, int n_t, int dim, float* __restrict__ out) {
+    const int half = dim / 2;
+    const float coef = (float)(-log(10000.0) / (double)half);
+    const int total = n_t * half;
+    GRID_STRIDE(i, total) {
+        const int s = (int)(i / half), j = (int)(i - (long long)s * half);
+        const float freq = expf((float)j * coef);
+        const float arg = t[s] * freq;
+        out[(long long)s * dim + j] = cosf(arg);
+        out[(long long)s * dim + half + j] = sinf(arg);
+    }
+}
+
 __global__ void cfg_ddim_kernel(const float* __restrict__ eps, float* __restrict__ latent, float* __restrict__ unet_in,
                                 long long per_half, DdimCoef c) {
     GRID_STRIDE(i, per_half) {
@@ -364,6 +379,12 @@ hipError_t launch_transpose2d(const float* src, float* dst, int rows, int cols, 
 }
 hipError_t launch_timestep_embedding(const int* t_dev, int n_t, int dim, float* out, hipStream_t s) {
     hipLaunchKernelGGL(timestep_embedding_kernel, dim3(blocks_for((long long)n_t * dim / 2)), dim3(256), 0, s, t_dev,
+                       n_t, dim, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_timestep_embedding_f(const float* t_dev, int n_t, int dim, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(timestep_embedding_f_kernel, dim3(blocks_for((long long)n_t * dim / 2)), dim3(256), 0, s, t_dev,
                        n_t, dim, out);
     return hipGetLastError();
 }

@@ -29,14 +29,15 @@ struct SamplerHist { const f32x4* prev[3]; f32x4* out; };
 
 // eps [2 pixels] (unconditional half first), latent [pixels] in place, unet_in [2 pixels]; hw pixels per image.  DEPTH history slots:
 // h.prev[k] is read where k < c.n_hist, h.out is written (it may alias the oldest slot: a thread reads its pixel first).  NOISE: image
-// b's element i is normal_draw(noise_key + b, i), i in NCHW order (launch_fill_normal's).  MASK: launch_cfg_ddim_masked's blend.
-template <int DEPTH, bool NOISE, bool MASK>
-__global__ void sampler_step_kernel(const f32x4* __restrict__ eps, f32x4* __restrict__ latent, f32x4* __restrict__ unet_in, long long pixels,
-                                    long long hw, SamplerStep c, SamplerHist h, uint64_t noise_key, const float* __restrict__ mask,
-                                    const f32x4* __restrict__ z0, const f32x4* __restrict__ e0) {
+// b's element i is normal_draw(noise_key + b, i), i in NCHW order (launch_fill_normal's); NOISE = 2 (dpmpp_sde's second stage) adds
+// cz2 z2, z2 drawn the same way from noise_key2, behind the update -- 0 and 1 are the arithmetic they were.  MASK: launch_cfg_ddim_masked's blend.
+template <int DEPTH, int NOISE, bool MASK>
+__device__ __forceinline__ void sampler_step_body(const f32x4* __restrict__ eps, f32x4* __restrict__ latent, f32x4* __restrict__ unet_in, long long pixels,
+                                                  long long hw, const SamplerStep& c, const SamplerHist& h, uint64_t noise_key, uint64_t noise_key2,
+                                                  const float* __restrict__ mask, const f32x4* __restrict__ z0, const f32x4* __restrict__ e0) {
     GRID_STRIDE(i, pixels) {
         const f32x4 eu = eps[i], ec = eps[pixels + i], x = latent[i];
-        f32x4 q1 = f32x4{0.f, 0.f, 0.f, 0.f}, q2 = q1, q3 = q1, z = q1;
+        f32x4 q1 = f32x4{0.f, 0.f, 0.f, 0.f}, q2 = q1, q3 = q1, z = q1, z2 = q1;
         if (DEPTH >= 1 && c.n_hist >= 1) q1 = h.prev[0][i];
         if (DEPTH >= 3 && c.n_hist >= 2) q2 = h.prev[1][i];
         if (DEPTH >= 3 && c.n_hist >= 3) q3 = h.prev[2][i];
@@ -45,6 +46,11 @@ __global__ void sampler_step_kernel(const f32x4* __restrict__ eps, f32x4* __rest
             const uint64_t key = noise_key + (uint64_t)b;
             z = f32x4{normal_draw(key, (uint64_t)p), normal_draw(key, (uint64_t)(hw + p)), normal_draw(key, (uint64_t)(2 * hw + p)),
                       normal_draw(key, (uint64_t)(3 * hw + p))};
+            if (NOISE == 2) {
+                const uint64_t key2 = noise_key2 + (uint64_t)b;
+                z2 = f32x4{normal_draw(key2, (uint64_t)p), normal_draw(key2, (uint64_t)(hw + p)), normal_draw(key2, (uint64_t)(2 * hw + p)),
+                           normal_draw(key2, (uint64_t)(3 * hw + p))};
+            }
         }
         f32x4 nx;
         float qx, qy, qz, qw;
@@ -52,6 +58,7 @@ __global__ void sampler_step_kernel(const f32x4* __restrict__ eps, f32x4* __rest
         nx.y = sampler_update(eu.y, ec.y, x.y, q1.y, q2.y, q3.y, z.y, c, &qy);
         nx.z = sampler_update(eu.z, ec.z, x.z, q1.z, q2.z, q3.z, z.z, c, &qz);
         nx.w = sampler_update(eu.w, ec.w, x.w, q1.w, q2.w, q3.w, z.w, c, &qw);
+        if (NOISE == 2) { nx.x += c.cz2 * z2.x; nx.y += c.cz2 * z2.y; nx.z += c.cz2 * z2.z; nx.w += c.cz2 * z2.w; }
         if (DEPTH >= 1) h.out[i] = f32x4{qx, qy, qz, qw};   // the pre-blend q
         if (MASK) {
             const f32x4 zs = z0[i], es = e0[i];
@@ -67,6 +74,22 @@ __global__ void sampler_step_kernel(const f32x4* __restrict__ eps, f32x4* __rest
     }
 }
 
+// the twelve forms of the sampler choice (section 9b), which the k-samplers share: history depth 0 / 1 / 3 x one draw or none x mask
+template <int DEPTH, bool NOISE, bool MASK>
+__global__ void sampler_step_kernel(const f32x4* __restrict__ eps, f32x4* __restrict__ latent, f32x4* __restrict__ unet_in, long long pixels,
+                                    long long hw, SamplerStep c, SamplerHist h, uint64_t noise_key, const float* __restrict__ mask,
+                                    const f32x4* __restrict__ z0, const f32x4* __restrict__ e0) {
+    sampler_step_body<DEPTH, NOISE ? 1 : 0, MASK>(eps, latent, unet_in, pixels, hw, c, h, noise_key, 0, mask, z0, e0);
+}
+
+// dpmpp_sde's second stage (section 9i): history depth 1 and TWO draws, z from noise_key -- stage 1's, drawn again instead of stored -- and z2 from noise_key2
+template <bool MASK>
+__global__ void sampler_two_draw_kernel(const f32x4* __restrict__ eps, f32x4* __restrict__ latent, f32x4* __restrict__ unet_in, long long pixels,
+                                        long long hw, SamplerStep c, SamplerHist h, uint64_t noise_key, uint64_t noise_key2,
+                                        const float* __restrict__ mask, const f32x4* __restrict__ z0, const f32x4* __restrict__ e0) {
+    sampler_step_body<1, 2, MASK>(eps, latent, unet_in, pixels, hw, c, h, noise_key, noise_key2, mask, z0, e0);
+}
+
 template <int DEPTH>
 static void launch_depth(bool noise, bool mask, int blocks, hipStream_t s, const f32x4* eps, f32x4* latent, f32x4* unet_in, long long pixels, long long hw,
                          const SamplerStep& c, const SamplerHist& h, uint64_t noise_key, const float* m, const f32x4* z0, const f32x4* e0) {
@@ -80,8 +103,8 @@ static void launch_depth(bool noise, bool mask, int blocks, hipStream_t s, const
 }
 
 hipError_t launch_sampler_step(const float* eps, float* latent, float* unet_in, long long per_half, long long hw, SamplerStep c, int depth,
-                               const float* const q_prev[3], float* q_out, uint64_t noise_key, const float* mask, const float* z0, const float* e0,
-                               hipStream_t s) {
+                               const float* const q_prev[3], float* q_out, uint64_t noise_key, uint64_t noise_key2, const float* mask, const float* z0,
+                               const float* e0, hipStream_t s) {
     if ((per_half & 3) || hw <= 0 || (per_half / 4) % hw) return hipErrorInvalidValue;
     if (depth != 0 && depth != 1 && depth != 3) return hipErrorInvalidValue;
     if (c.n_hist < 0 || c.n_hist > depth || (depth && !q_out)) return hipErrorInvalidValue;
@@ -91,6 +114,7 @@ hipError_t launch_sampler_step(const float* eps, float* latent, float* unet_in, 
     const long long pixels = per_half / 4;
     SamplerHist h{{nullptr, nullptr, nullptr}, reinterpret_cast<f32x4*>(q_out)};
     for (int k = 0; k < c.n_hist; ++k) h.prev[k] = reinterpret_cast<const f32x4*>(q_prev[k]);
+    if (c.cz2 != 0.0f && (depth != 1 || c.cz == 0.0f)) return hipErrorInvalidValue;   // the second draw follows a first one, in a kind of history depth 1
     const bool noise = c.cz != 0.0f;   // z is never drawn where the step has none
     auto* e4 = reinterpret_cast<const f32x4*>(eps);
     auto* l4 = reinterpret_cast<f32x4*>(latent);
@@ -98,7 +122,11 @@ hipError_t launch_sampler_step(const float* eps, float* latent, float* unet_in, 
     auto* z4 = reinterpret_cast<const f32x4*>(z0);
     auto* n4 = reinterpret_cast<const f32x4*>(e0);
     const int blocks = blocks_for(pixels);
-    if (depth == 0) launch_depth<0>(noise, mask != nullptr, blocks, s, e4, l4, u4, pixels, hw, c, h, noise_key, mask, z4, n4);
+    if (c.cz2 != 0.0f) {
+        if (mask) hipLaunchKernelGGL((sampler_two_draw_kernel<true>), dim3(blocks), dim3(256), 0, s, e4, l4, u4, pixels, hw, c, h, noise_key, noise_key2, mask, z4, n4);
+        else hipLaunchKernelGGL((sampler_two_draw_kernel<false>), dim3(blocks), dim3(256), 0, s, e4, l4, u4, pixels, hw, c, h, noise_key, noise_key2, mask, z4, n4);
+    }
+    else if (depth == 0) launch_depth<0>(noise, mask != nullptr, blocks, s, e4, l4, u4, pixels, hw, c, h, noise_key, mask, z4, n4);
     else if (depth == 1) launch_depth<1>(noise, mask != nullptr, blocks, s, e4, l4, u4, pixels, hw, c, h, noise_key, mask, z4, n4);
     else launch_depth<3>(noise, mask != nullptr, blocks, s, e4, l4, u4, pixels, hw, c, h, noise_key, mask, z4, n4);
     return hipGetLastError();

@@ -239,6 +239,8 @@ hipError_t launch_clip_reweight(float* z, const float* w, int n, int T, int C, h
 hipError_t launch_transpose2d(const float* src, float* dst, int rows, int cols, int src_ld, hipStream_t s);
 // out[s][0:half] = cos(t_s * f_i), out[s][half:dim] = sin(t_s * f_i)  (unet/mod.rs:19-30)
 hipError_t launch_timestep_embedding(const int* t_dev, int n_t, int dim, float* out, hipStream_t s);
+// the same at fractional timesteps (f32 on the device): an integer t gives the bits of the int form
+hipError_t launch_timestep_embedding_f(const float* t_dev, int n_t, int dim, float* out, hipStream_t s);
 // CFG combine + DDIM update on NHWC latents (stablediffusion/mod.rs:152-156,190-191).
 // eps [2n][hw][4] (uncond rows first), latent [n][hw][4] updated in place, and
 // copied twice into unet_in [2n][hw][4] for the next step.
@@ -293,13 +295,15 @@ hipError_t launch_resize_axis(const float* x, float* y, const int* first, const 
 //   e = eu + (ec - eu) scale;  q = qx x + qe e;  x' = cx x + ce e + h[0] q_-1 + h[1] q_-2 + h[2] q_-3 + cz z
 // then the optional mask blend of launch_cfg_ddim_masked (blend_prev = sqrt(a_prev), blend_dir = sqrt(1 - a_prev)).  n_hist = how many of the
 // history slots hold a q of this call (the others are not read).  Plain Euler / Euler-ancestral are DDIM at eta = 0 / 1: no kinds of their own.
-struct SamplerStep { float scale, cx, ce, h[3], cz, qx, qe, blend_prev, blend_dir; int n_hist; };
+// cz2 (the sigma-schedule samplers, section 9i): the weight of a SECOND draw z2, x' += cz2 z2 -- dpmpp_sde's second stage, which draws its first one again.
+struct SamplerStep { float scale, cx, ce, h[3], cz, qx, qe, blend_prev, blend_dir; int n_hist; float cz2; };
 // eps [2n][hw][4], latent [n][hw][4] in place, unet_in [2n][hw][4].  depth = 0 / 1 / 3 history slots: q_prev[k] = q of k + 1 steps ago
 // ([n][hw][4], read where k < n_hist), q_out receives this step's q (it may be the oldest slot: every thread reads its pixel before it writes it).
-// Noise (cz != 0 only): element i (NCHW order within the image) of image b is normal_draw(noise_key + b, i).  mask / z0 / e0: all or none.
+// Noise (cz != 0 only): element i (NCHW order within the image) of image b is normal_draw(noise_key + b, i); z2 (cz2 != 0 only) the same from noise_key2.
+// mask / z0 / e0: all or none.
 hipError_t launch_sampler_step(const float* eps, float* latent, float* unet_in, long long per_half, long long hw, SamplerStep c, int depth,
-                               const float* const q_prev[3], float* q_out, uint64_t noise_key, const float* mask, const float* z0, const float* e0,
-                               hipStream_t s);
+                               const float* const q_prev[3], float* q_out, uint64_t noise_key, uint64_t noise_key2, const float* mask, const float* z0,
+                               const float* e0, hipStream_t s);
 
 // ---- bf16-storage variants (k_bf16.hip) ---------------------------------------------------------------
 // Launch geometry of the bf16 GroupNorm passes (statistics, apply, the MXFP8 apply of k_fp8.hip): a sample's hw rows are cut into `chunks` ranges, one workgroup

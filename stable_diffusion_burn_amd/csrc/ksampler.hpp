@@ -1,0 +1,23 @@
+// ksampler.hpp -- the sigma-schedule samplers (include/sdmi.h "sigma-schedule samplers"): schedules, sigma <-> t and the evaluation plan,
+// host only and in f64.  ONE implementation: sdmi_ksampler_sigmas / sdmi_sigma_to_t / sdmi_ksampler_plan export it, the engine calls it.  Everything throws
+// sdmi::Error(SDMI_ERR_INVALID) for what the header lists.
+#pragma once
+#include <cstddef>
+#include <vector>
+
+#include "../../include/sdmi.h"
+
+namespace sdmi {
+
+constexpr int KPLAN_COLS = 12;   // step, stage, t, sigma, cx, ce, h1, cz, cz2, qx, qe, a_end
+enum { KP_STEP = 0, KP_STAGE, KP_T, KP_SIGMA, KP_CX, KP_CE, KP_H1, KP_CZ, KP_CZ2, KP_QX, KP_QE, KP_AEND };
+
+// what sdmi_set_ksampler refuses; alphas (total entries) gives the range of the sigma bounds (null and 0: the range is not checked)
+void check_ksampler(const sdmi_ksampler& k, const float* alphas, int total);
+double sigma_to_t(const float* alphas, int total, double sigma);
+// steps + 1 sigmas, the last 0; ts (may be null) receives the integer timesteps of schedule 0 (empty for the others)
+std::vector<double> ksampler_sigmas(const sdmi_ksampler& k, const float* alphas, int total, size_t n_steps, std::vector<int>* ts = nullptr);
+// KPLAN_COLS doubles per UNet evaluation of the call; *call_steps = the steps the call runs
+std::vector<double> ksampler_plan(const sdmi_ksampler& k, const float* alphas, int total, size_t n_steps, double strength, int* call_steps = nullptr);
+
+}  // namespace sdmi

@@ -172,9 +172,7 @@ public:
                         SDMI_HIP(launch_fill_normal(x0 + (size_t)i * lat_elems, (long long)lat_elems, seed + (uint64_t)(g0 + i), e.stream()));
                 }
                 {   // step noise of a stochastic sampler is keyed by the global image index too
-                    sdmi_sampler sp = e.sampler();
-                    sp.image_base = g0;
-                    e.set_sampler(&sp);
+                    e.set_image_base(g0);   // (of the sampler or the k-sampler, whichever is set)
                 }
                 e.sample_latent_dev(ctx, n, T, prompt + n_cond, Tu, scale, n_steps, x0, lat);
                 e.decode_latent_dev(lat, n, (float)(1.0 / 0.18215), nullptr, reinterpret_cast<uint8_t*>(sh.rgb.p));
@@ -188,6 +186,14 @@ public:
     void set_sampler(const sdmi_sampler* s) {
         if (s) Engine::check_sampler(*s);
         for (int r = 0; r < size(); ++r) engine(r).set_sampler(s);
+    }
+    // sdmi_multi_set_ksampler: the same for the k-sampler (every context carries the same schedule table)
+    void set_ksampler(const sdmi_ksampler* k) {
+        if (k) {
+            const std::vector<float>& a = engine(0).alphas();
+            sdmi::check_ksampler(*k, a.empty() ? nullptr : a.data(), (int)a.size());
+        }
+        for (int r = 0; r < size(); ++r) engine(r).set_ksampler(k);
     }
 
     long long broadcasts() const { return broadcasts_; }
@@ -301,6 +307,13 @@ int sdmi_multi_set_sampler(sdmi_multi* m, const sdmi_sampler* sampler) {
     return multi_guard([&] {
         if (!m) throw sdmi::Error(SDMI_ERR_INVALID, "null sdmi_multi");
         m->m->set_sampler(sampler);
+    });
+}
+
+int sdmi_multi_set_ksampler(sdmi_multi* m, const sdmi_ksampler* ksampler) {
+    return multi_guard([&] {
+        if (!m) throw sdmi::Error(SDMI_ERR_INVALID, "null sdmi_multi");
+        m->m->set_ksampler(ksampler);
     });
 }
 

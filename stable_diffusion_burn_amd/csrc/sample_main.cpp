@@ -19,6 +19,9 @@
 //   * SDMI_LORA=<file>[:scale[:te_scale]] (no reference counterpart) attaches a kohya-ss / LyCORIS LoRA .safetensors file before the prompt is encoded
 //     (sdmi_lora_load_safetensors): scale defaults to 1, te_scale -- the text encoder's -- to scale.  It sets the engine option keep_masters itself.  Only finite
 //     decimal numbers are scales; a file name that itself ends in ":<number>" needs its scale spelled out ("name:2:1").
+//   * SDMI_KSAMPLER=kind:schedule[:eta] (no reference counterpart; unset: the reference's DDIM) selects a sigma-schedule sampler (sdmi_set_ksampler) by name:
+//     kind euler | dpmpp_2m | heun | dpm2 | dpmpp_2s | dpmpp_sde | dpmpp_2m_sde, schedule model | karras | exponential | uniform, eta 0 .. 1 (default 0); its step
+//     noise is seeded by SDMI_SEED.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -86,6 +89,29 @@ static std::string parse_lora_spec(const char* spec, double* scale, double* te_s
     return path;
 }
 
+// "kind:schedule[:eta]" by name; false for a name or a number that is none
+static bool parse_ksampler_spec(const char* spec, sdmi_ksampler* k) {
+    static const char* const kinds[] = {"euler", "dpmpp_2m", "heun", "dpm2", "dpmpp_2s", "dpmpp_sde", "dpmpp_2m_sde"};
+    static const char* const schedules[] = {"model", "karras", "exponential", "uniform"};
+    const std::string s(spec);
+    const size_t c1 = s.find(':');
+    if (c1 == std::string::npos) return false;
+    const size_t c2 = s.find(':', c1 + 1);
+    const std::string kind = s.substr(0, c1), sched = s.substr(c1 + 1, c2 == std::string::npos ? std::string::npos : c2 - c1 - 1);
+    *k = sdmi_ksampler{};
+    k->kind = k->schedule = -1;
+    for (int i = 0; i < 7; ++i) if (kind == kinds[i]) k->kind = i;
+    for (int i = 0; i < 4; ++i) if (sched == schedules[i]) k->schedule = i;
+    if (k->kind < 0 || k->schedule < 0) return false;
+    if (c2 != std::string::npos) {
+        const std::string eta = s.substr(c2 + 1);
+        char* end = nullptr;
+        k->eta = std::strtod(eta.c_str(), &end);
+        if (eta.empty() || *end) return false;
+    }
+    return true;
+}
+
 static void attach_lora(sdmi_ctx* ctx, const char* spec) {
     double scale, te_scale;
     bool has_te;
@@ -128,6 +154,15 @@ int main(int argc, char** argv) {
     if (const char* o = std::getenv("SDMI_CONFIG")) apply_overrides(cfg, o);
     if (cfg.clip_layers <= 0) { std::fprintf(stderr, "Error: the sample binary needs the CLIP text encoder (clip_layers > 0)\n"); return 1; }
 
+    // SDMI_KSAMPLER: a spec that names no sampler ends the run before anything is loaded
+    sdmi_ksampler ksampler;
+    const char* ks = std::getenv("SDMI_KSAMPLER");
+    const bool has_ksampler = ks && *ks;
+    if (has_ksampler) {
+        if (!parse_ksampler_spec(ks, &ksampler)) { std::fprintf(stderr, "Error: SDMI_KSAMPLER must be kind:schedule[:eta], got '%s'\n", ks); return 1; }
+        if (const char* sd = std::getenv("SDMI_SEED")) ksampler.noise_seed = std::strtoull(sd, nullptr, 10);
+    }
+
     std::printf("Loading tokenizer...\n");
     const char* vocab = std::getenv("SDMI_BPE_VOCAB");
     sdmi_tokenizer* tok = nullptr;
@@ -136,6 +171,7 @@ int main(int argc, char** argv) {
     std::printf("Loading model...\n");
     sdmi_ctx* ctx = nullptr;
     if (sdmi_create(&ctx, &cfg) != SDMI_OK) die("Error creating device context");
+    if (has_ksampler && sdmi_set_ksampler(ctx, &ksampler) != SDMI_OK) die("Error setting the k-sampler");   // sticky: set before the weights, refused at once
     const char* lora = std::getenv("SDMI_LORA");
     if (lora && *lora && sdmi_set_option(ctx, "keep_masters", "1") != SDMI_OK) die("Error setting keep_masters");
     if (model_type == "burn") {

@@ -646,6 +646,62 @@ int sdmi_get_sampler(sdmi_ctx* ctx, sdmi_sampler* out) {
     });
 }
 
+// ---- sigma-schedule samplers (ksampler.cpp) ----------------------------------------------------------------------------
+int sdmi_set_ksampler(sdmi_ctx* ctx, const sdmi_ksampler* ksampler) {
+    return guarded([&] { eng(ctx).set_ksampler(ksampler); });
+}
+
+int sdmi_get_ksampler(sdmi_ctx* ctx, sdmi_ksampler* out, int32_t* is_set) {
+    return guarded([&] {
+        if (!out || !is_set) throw Error(SDMI_ERR_INVALID, "get_ksampler: null output");
+        Engine& e = eng(ctx);
+        *is_set = e.ksampler_set() ? 1 : 0;
+        *out = e.ksampler_set() ? e.ksampler() : sdmi_ksampler{};
+    });
+}
+
+int sdmi_ksampler_sigmas(const sdmi_ksampler* ksampler, const float* alphas_cumprod, int32_t total, size_t n_steps, double* sigmas, int32_t capacity, int32_t* count) {
+    return guarded([&] {
+        if (!ksampler || !count) throw Error(SDMI_ERR_INVALID, "ksampler_sigmas: null pointer");
+        const std::vector<double> sg = sdmi::ksampler_sigmas(*ksampler, alphas_cumprod, total, n_steps);
+        *count = (int32_t)sg.size();
+        if (!sigmas || capacity < (int32_t)sg.size()) throw Error(SDMI_ERR_INVALID, "ksampler_sigmas: capacity too small");
+        std::memcpy(sigmas, sg.data(), sg.size() * sizeof(double));
+    });
+}
+
+int sdmi_sigma_to_t(const float* alphas_cumprod, int32_t total, double sigma, double* t) {
+    return guarded([&] {
+        if (!t) throw Error(SDMI_ERR_INVALID, "sigma_to_t: null output");
+        *t = sdmi::sigma_to_t(alphas_cumprod, total, sigma);
+    });
+}
+
+int sdmi_ksampler_plan(const sdmi_ksampler* ksampler, const float* alphas_cumprod, int32_t total, size_t n_steps, double strength, double* rows, int32_t capacity,
+                       int32_t* count) {
+    return guarded([&] {
+        if (!ksampler || !count) throw Error(SDMI_ERR_INVALID, "ksampler_plan: null pointer");
+        const std::vector<double> plan = sdmi::ksampler_plan(*ksampler, alphas_cumprod, total, n_steps, strength);
+        const size_t n = plan.size() / sdmi::KPLAN_COLS;
+        *count = (int32_t)n;
+        if (!rows || capacity < (int32_t)n) throw Error(SDMI_ERR_INVALID, "ksampler_plan: capacity too small");
+        std::memcpy(rows, plan.data(), plan.size() * sizeof(double));
+    });
+}
+
+int sdmi_op_timestep_embedding_f(sdmi_ctx* ctx, double t, int32_t dim, float* out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (dim <= 0 || dim % 2) throw Error(SDMI_ERR_INVALID, "timestep_embedding: dim must be even");
+        if (!std::isfinite(t)) throw Error(SDMI_ERR_INVALID, "timestep_embedding: t must be finite");
+        Engine::Call call(e);
+        DevOut dout(e, out, (size_t)dim * sizeof(float));
+        e.op_timestep_embedding_f(t, dim, dout.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
 // optional host input (mask, noise): staged when given
 static std::unique_ptr<DevIn> dev_in_opt(Engine& e, const void* host, size_t bytes) {
     return host ? std::unique_ptr<DevIn>(new DevIn(e, host, bytes)) : nullptr;

@@ -24,7 +24,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _capi
-from ._capi import SdmiConfig, SdmiControl, SdmiError, SdmiHires, SdmiInpaint, SdmiOpView, SdmiPromptOpts, SdmiSampler, check, load_library
+from ._capi import SdmiConfig, SdmiControl, SdmiError, SdmiHires, SdmiInpaint, SdmiKSampler, SdmiOpView, SdmiPromptOpts, SdmiSampler, check, load_library
 
 def mpk_list(path) -> list:
     """[(dump name, shape, file offset)] of a Burn .mpk record, parsed by the C++ reader (host only, no GPU)."""
@@ -156,6 +156,56 @@ def sampler_coefs(kind: str, eta: float, alphas_cumprod, ts, step_size: int) -> 
     check(lib.sdmi_sampler_coefs(C.byref(s), _fp(a), a.size, t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, int(step_size),
                                  out.ctypes.data_as(C.POINTER(C.c_double))))
     return out
+
+
+KSAMPLER_KINDS = ("euler", "dpmpp_2m", "heun", "dpm2", "dpmpp_2s", "dpmpp_sde", "dpmpp_2m_sde")   # sdmi_ksampler.kind 0 .. 6
+KSAMPLER_SCHEDULES = ("model", "karras", "exponential", "uniform")                                # sdmi_ksampler.schedule 0 .. 3
+KSAMPLER_PLAN_COLUMNS = ("step", "stage", "t", "sigma", "cx", "ce", "h1", "cz", "cz2", "qx", "qe", "a_end")
+
+
+def _ksampler_struct(kind, schedule="karras", eta=0.0, rho=7.0, sigma_min=None, sigma_max=None, noise_seed=0, image_base=0) -> SdmiKSampler:
+    """Names -> sdmi_ksampler.  Only the names are checked here: the numbers are the library's to refuse (SdmiError)."""
+    if kind not in KSAMPLER_KINDS:
+        raise ValueError(f"k-sampler kind must be one of {KSAMPLER_KINDS}, got {kind!r}")
+    if schedule not in KSAMPLER_SCHEDULES:
+        raise ValueError(f"k-sampler schedule must be one of {KSAMPLER_SCHEDULES}, got {schedule!r}")
+    k = SdmiKSampler()
+    k.kind, k.schedule, k.eta, k.rho = KSAMPLER_KINDS.index(kind), KSAMPLER_SCHEDULES.index(schedule), float(eta), float(rho)
+    k.sigma_min, k.sigma_max = float(sigma_min or 0.0), float(sigma_max or 0.0)
+    k.noise_seed, k.image_base = int(noise_seed) & 0xFFFFFFFFFFFFFFFF, int(image_base)
+    return k
+
+
+def ksampler_sigmas(kind: str, alphas_cumprod, n_steps: int, schedule: str = "karras", **kw) -> np.ndarray:
+    """The steps + 1 sigmas (float64, the last 0) of a k-sampler's schedule for n_steps (sdmi_ksampler_sigmas; host only, no GPU)."""
+    lib = load_library()
+    k = _ksampler_struct(kind, schedule, **kw)
+    a = np.ascontiguousarray(alphas_cumprod, dtype=np.float32)
+    out = np.empty(a.size + 2, dtype=np.float64)
+    count = C.c_int32()
+    check(lib.sdmi_ksampler_sigmas(C.byref(k), _fp(a), a.size, int(n_steps), out.ctypes.data_as(C.POINTER(C.c_double)), out.size, C.byref(count)))
+    return out[:count.value].copy()
+
+
+def sigma_to_t(alphas_cumprod, sigma: float) -> float:
+    """The fractional timestep of sigma by k-diffusion's rule (sdmi_sigma_to_t; host only): exactly j at sigma(alphas_cumprod[j])."""
+    lib = load_library()
+    a = np.ascontiguousarray(alphas_cumprod, dtype=np.float32)
+    t = C.c_double()
+    check(lib.sdmi_sigma_to_t(_fp(a), a.size, float(sigma), C.byref(t)))
+    return t.value
+
+
+def ksampler_plan(kind: str, alphas_cumprod, n_steps: int, schedule: str = "karras", strength: float = 1.0, **kw) -> np.ndarray:
+    """The evaluation plan [evaluations, 12] (KSAMPLER_PLAN_COLUMNS, float64) of a call of n_steps at `strength` (sdmi_ksampler_plan; host only):
+    one row per UNet evaluation,  q = qx x + qe e,  x' = cx x + ce e + h1 q_-1 + cz z + cz2 z2  on the VP latent."""
+    lib = load_library()
+    k = _ksampler_struct(kind, schedule, **kw)
+    a = np.ascontiguousarray(alphas_cumprod, dtype=np.float32)
+    out = np.empty((2 * (a.size + 1), 12), dtype=np.float64)
+    count = C.c_int32()
+    check(lib.sdmi_ksampler_plan(C.byref(k), _fp(a), a.size, int(n_steps), float(strength), out.ctypes.data_as(C.POINTER(C.c_double)), out.shape[0], C.byref(count)))
+    return out[:count.value].copy()
 
 
 RESIZE_MODES = ("nearest", "bilinear", "bicubic")   # sdmi_resize_weights / sdmi_hires.mode 0, 1, 2 ("nearest" = torch's "nearest-exact")
@@ -387,7 +437,7 @@ class MultiLoraAdapter:
             self._owner = None
 
 
-__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "safetensors_list", "checkpoint_key", "default_alphas_cumprod", "control_step_on", "control_residual_shapes", "img2img_timesteps", "sampler_coefs", "resize_weights", "load_lora_npz", "save_lora_npz", "lora_module_name", "lora_check_safetensors", "LoraAdapter", "LoraFileAdapter", "LORA_UNET", "LORA_TE", "LORA_SKIP_UNKNOWN", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
+__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "safetensors_list", "checkpoint_key", "default_alphas_cumprod", "control_step_on", "control_residual_shapes", "img2img_timesteps", "sampler_coefs", "ksampler_sigmas", "sigma_to_t", "ksampler_plan", "KSAMPLER_KINDS", "KSAMPLER_SCHEDULES", "KSAMPLER_PLAN_COLUMNS", "resize_weights", "load_lora_npz", "save_lora_npz", "lora_module_name", "lora_check_safetensors", "LoraAdapter", "LoraFileAdapter", "LORA_UNET", "LORA_TE", "LORA_SKIP_UNKNOWN", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
 
 
 @dataclass(frozen=True)
@@ -666,6 +716,26 @@ class StableDiffusion:
         s = SdmiSampler()
         check(self._lib.sdmi_get_sampler(self._ctx, C.byref(s)))
         return {"kind": SAMPLER_KINDS[s.kind], "eta": s.eta, "noise_seed": s.noise_seed, "image_base": s.image_base}
+
+    def set_ksampler(self, kind="dpmpp_2m", schedule="karras", eta: float = 0.0, rho: float = 7.0, sigma_min=None, sigma_max=None, noise_seed: int = 0,
+                     image_base: int = 0) -> None:
+        """Choose a sigma-schedule sampler for every later sampling call of this context (sdmi_set_ksampler; sticky): kind one of KSAMPLER_KINDS, schedule one of
+        KSAMPLER_SCHEDULES, eta 0 .. 1 for the kinds that take noise ("euler" at eta 1 is Euler-ancestral), rho of the Karras spacing, sigma_min / sigma_max (None: the
+        model's).  None clears it.  Setting it resets set_sampler's choice to the default, and any set_sampler call clears it."""
+        if kind is None:
+            check(self._lib.sdmi_set_ksampler(self._ctx, None))
+            return
+        k = _ksampler_struct(kind, schedule, eta, rho, sigma_min, sigma_max, noise_seed, image_base)
+        check(self._lib.sdmi_set_ksampler(self._ctx, C.byref(k)))
+
+    def get_ksampler(self):
+        """The k-sampler in force as a dict, or None."""
+        k, is_set = SdmiKSampler(), C.c_int32()
+        check(self._lib.sdmi_get_ksampler(self._ctx, C.byref(k), C.byref(is_set)))
+        if not is_set.value:
+            return None
+        return {"kind": KSAMPLER_KINDS[k.kind], "schedule": KSAMPLER_SCHEDULES[k.schedule], "eta": k.eta, "rho": k.rho, "sigma_min": k.sigma_min,
+                "sigma_max": k.sigma_max, "noise_seed": k.noise_seed, "image_base": k.image_base}
 
     # ---- LoRA adapters (include/sdmi.h "LoRA adapters"; DESIGN.md section 9c) ----------------
     def lora_attach(self, tensors, scale: float = 1.0) -> LoraAdapter:
@@ -1399,6 +1469,12 @@ class StableDiffusion:
         check(self._lib.sdmi_op_timestep_embedding(self._ctx, int(t), dim, _fp(out)))
         return out
 
+    def op_timestep_embedding_f(self, t: float, dim: int):
+        """timestep_embedding at a fractional t (the k-samplers' evaluation times); an integer t gives op_timestep_embedding's bits"""
+        out = np.empty((1, dim), dtype=np.float32)
+        check(self._lib.sdmi_op_timestep_embedding_f(self._ctx, float(t), dim, _fp(out)))
+        return out
+
     def qkv_attention(self, q, k, v, mask, n_head: int):
         """attention.rs:5-45: q [n,nq,c], k,v [n,nk,c], mask [>=nq, >=nk] or None.
 
@@ -1520,6 +1596,14 @@ class MultiStableDiffusion:
             return
         s = _sampler_struct(kind, eta, noise_seed, 0)
         check(self._lib.sdmi_multi_set_sampler(self._m, C.byref(s)))
+
+    def set_ksampler(self, kind="dpmpp_2m", schedule="karras", eta: float = 0.0, rho: float = 7.0, sigma_min=None, sigma_max=None, noise_seed: int = 0) -> None:
+        """StableDiffusion.set_ksampler on every device (sdmi_multi_set_ksampler); image_base per shard, as set_sampler."""
+        if kind is None:
+            check(self._lib.sdmi_multi_set_ksampler(self._m, None))
+            return
+        k = _ksampler_struct(kind, schedule, eta, rho, sigma_min, sigma_max, noise_seed, 0)
+        check(self._lib.sdmi_multi_set_ksampler(self._m, C.byref(k)))
 
     def set_latent_size(self, h: int, w: int) -> None:
         """StableDiffusion.set_latent_size on every device context; if one refuses, every context keeps the size it had."""

@@ -34,6 +34,13 @@ def set_shard_sampler(sd, global_batch: int, rank: int, world: int, kind="ddim",
     return shard
 
 
+def set_shard_ksampler(sd, global_batch: int, rank: int, world: int, kind="dpmpp_2m", schedule="karras", **kw) -> range:
+    """set_shard_sampler for a sigma-schedule sampler: StableDiffusion.set_ksampler with image_base = the first global image index of rank's shard."""
+    shard = shard_range(global_batch, rank, world)
+    sd.set_ksampler(kind, schedule=schedule, image_base=shard.start, **kw)
+    return shard
+
+
 def pack_prompt(cond, uncond):
     """[cond | uncond] as one flat float32 buffer + the two row counts (torch tensors)."""
     import torch
