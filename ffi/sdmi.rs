@@ -37,6 +37,21 @@ pub struct SdmiConfig {
 impl SdmiConfig {
     pub fn control_hint_ch(&self) -> i32 { self.reserved[0] }
     pub fn set_control_hint_ch(&mut self, v: i32) { self.reserved[0] = v; }
+    /// `sdmi_config.variant` (0 = SD v1, 1 = SD 2.x: 64-wide UNet heads, OpenCLIP text tower) is the second of them.
+    pub fn variant(&self) -> i32 { self.reserved[1] }
+    pub fn set_variant(&mut self, v: i32) { self.reserved[1] = v; }
+}
+
+/// `sdmi_attn_plan` (`sdmi_attention_plan`): kernel 0 = unfused, 1 = k_attn.hip, 2 = k_attn_split.hip, 3 = k_attn_bf16.hip.
+#[repr(C)]
+#[derive(Default, Debug, Clone, Copy)]
+pub struct SdmiAttnPlan {
+    pub kernel: i32,
+    pub waves: i32,
+    pub q_rows: i32,
+    pub kv_tile: i32,
+    pub kv_splits: i32,
+    pub reserved: [i32; 3],
 }
 
 /// `sdmi_control` (include/sdmi.h "ControlNet"): the sticky control of a context built with `control_hint_ch = 3`.  `hint_rgb`: HOST, `n_hint` pictures of
@@ -182,6 +197,14 @@ extern "C" {
     fn sdmi_sigma_to_t(alphas_cumprod: *const c_float, total: i32, sigma: c_double, t: *mut c_double) -> c_int;
     fn sdmi_ksampler_plan(ksampler: *const SdmiKSampler, alphas_cumprod: *const c_float, total: i32, n_steps: usize, strength: c_double, rows: *mut c_double,
                           capacity: i32, count: *mut i32) -> c_int;
+    fn sdmi_ksampler_plan_ex(ksampler: *const SdmiKSampler, alphas_cumprod: *const c_float, total: i32, n_steps: usize, strength: c_double, prediction: i32,
+                             rows: *mut c_double, capacity: i32, count: *mut i32) -> c_int;
+    fn sdmi_sampler_coefs_ex(sampler: *const SdmiSampler, alphas_cumprod: *const c_float, total: i32, ts: *const i32, count: i32, step_size: i64, prediction: i32,
+                             coefs: *mut c_double) -> c_int;
+    fn sdmi_set_prediction(ctx: *mut c_void, kind: i32) -> c_int;
+    fn sdmi_attention_plan(ctx: *mut c_void, n: i32, n_head: i32, nq: i32, nk: i32, d_head: i32, has_mask: i32, out: *mut SdmiAttnPlan) -> c_int;
+    fn sdmi_checkpoint_key_ex(dump_name: *const c_char, variant: i32, out: *mut c_char, capacity: usize, needed: *mut usize, transposed: *mut i32, slice: *mut i32) -> c_int;
+    fn sdmi_safetensors_model_family(path: *const c_char, family: *mut i32) -> c_int;
     fn sdmi_op_timestep_embedding_f(ctx: *mut c_void, t: c_double, dim: i32, out: *mut c_float) -> c_int;
     fn sdmi_load_control_safetensors(ctx: *mut c_void, path: *const c_char) -> c_int;
     fn sdmi_control_ready(ctx: *mut c_void) -> c_int;
@@ -339,6 +362,23 @@ impl StableDiffusionMi355 {
             return Err(last_error().into());
         }
         Ok(())
+    }
+
+    /// What the loaded UNet predicts (`sdmi_set_prediction`, sticky): 0 = eps (the default), 1 = v (SD 2.x's 768-v models).  The checkpoint does not say: the caller chooses.
+    pub fn set_prediction(&mut self, kind: i32) -> Result<(), Box<dyn Error>> {
+        if unsafe { sdmi_set_prediction(self.ctx, kind) } != 0 {
+            return Err(last_error().into());
+        }
+        Ok(())
+    }
+
+    /// What this context would run for a qkv_attention of the shape under its current options (`sdmi_attention_plan`; host only, no launch).
+    pub fn attention_plan(&self, n: i32, n_head: i32, nq: i32, nk: i32, d_head: i32, has_mask: bool) -> Result<SdmiAttnPlan, Box<dyn Error>> {
+        let mut p = SdmiAttnPlan::default();
+        if unsafe { sdmi_attention_plan(self.ctx, n, n_head, nq, nk, d_head, has_mask as i32, &mut p) } != 0 {
+            return Err(last_error().into());
+        }
+        Ok(p)
     }
 
     /// The latent size [h, w] of every later call (`sdmi_set_latent_size`, sticky; no reference counterpart: the reference's latent is 4x64x64):
@@ -605,6 +645,26 @@ impl StableDiffusionMi355 {
         if st != 0 { return Err(last_error().into()); }
         buf.truncate(needed.saturating_sub(1));
         Ok((String::from_utf8(buf)?, transposed != 0))
+    }
+
+    /// The same for a model variant (`sdmi_checkpoint_key_ex`): 1 = SD 2.x in Stability's layout.  The third element is -1 for the key's whole tensor, 0 / 1 / 2 for the
+    /// query / key / value third of a fused `attn.in_proj_weight` / `in_proj_bias`.
+    pub fn checkpoint_key_ex(dump_name: &str, variant: i32) -> Result<(String, bool, i32), Box<dyn Error>> {
+        let name = CString::new(dump_name)?;
+        let mut buf = vec![0u8; 512];
+        let (mut needed, mut transposed, mut slice) = (0usize, 0i32, -1i32);
+        let st = unsafe { sdmi_checkpoint_key_ex(name.as_ptr(), variant, buf.as_mut_ptr() as *mut c_char, buf.len(), &mut needed, &mut transposed, &mut slice) };
+        if st != 0 { return Err(last_error().into()); }
+        buf.truncate(needed.saturating_sub(1));
+        Ok((String::from_utf8(buf)?, transposed != 0, slice))
+    }
+
+    /// 1 = an SD v1 checkpoint, 2 = SD 2.x, 0 = neither text encoder's final LayerNorm is in the file (`sdmi_safetensors_model_family`, host only).
+    pub fn safetensors_model_family(path: &str) -> Result<i32, Box<dyn Error>> {
+        let p = CString::new(path)?;
+        let mut family = 0i32;
+        if unsafe { sdmi_safetensors_model_family(p.as_ptr(), &mut family) } != 0 { return Err(last_error().into()); }
+        Ok(family)
     }
 
     /// `key\tdtype\tshape\tfile offset\tdump name or -` lines of a `.safetensors` file (`sdmi_safetensors_list`, host only).

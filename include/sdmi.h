@@ -85,7 +85,12 @@ typedef struct sdmi_config {
                               * without the field), 3 = an RGB hint: the model gets a fourth weight group "controlnet/..." (section "ControlNet" below).  Anything else is
                               * SDMI_ERR_INVALID from sdmi_create; control_hint_ch != 0 with unet_in_ch != 4 is SDMI_ERR_UNSUPPORTED (the control encoder's first convolution
                               * takes the 4 latent channels). */
-    int32_t reserved[1];
+    int32_t variant;         /* 0 = SD v1 (a zeroed field keeps meaning what it meant), 1 = SD 2.x: every UNet attention has model_channels-level width / 64 heads of width 64
+                              * (n_head is ignored; model_channels % 64 != 0 is SDMI_ERR_INVALID; the ".../n_head" metadata entries carry the per-level count), the text
+                              * encoder's MLP uses the exact (erf) GELU and sdmi_encode_prompt pads each chunk behind its <|endoftext|> with token id 0 (OpenCLIP), and option
+                              * "attn_d64" defaults to 2 (head dim 64 on the bf16-pipe attention kernels where measured faster).  Anything else is SDMI_ERR_INVALID from sdmi_create; variant = 1 with control_hint_ch != 0 is SDMI_ERR_UNSUPPORTED.
+                              * The OpenCLIP ViT-H tower of SD 2.x is ctx_dim = 1024, clip_layers = 23, clip_heads = 16: 23 blocks + the final LayerNorm are its "penultimate"
+                              * output.  Whether a checkpoint predicts eps (512-base) or v (768-v) is not in the file: the caller chooses, sdmi_set_prediction. */
 } sdmi_config;
 
 int sdmi_default_config(sdmi_config* cfg);
@@ -138,8 +143,15 @@ int sdmi_mpk_list(const char* mpk_path, char* out, size_t capacity, size_t* need
  * inpainting conv_in into a 4-channel context, or the reverse, is refused here), no
  * matching key at all; SDMI_ERR_UNSUPPORTED: F64 or an integer dtype on a tensor of the model; SDMI_ERR_STATE: a LoRA adapter with a non-zero
  * scale.  Everything is checked before the first tensor is staged: a refused file leaves the context as it was.  The CLIP and VAE-encoder groups are
- * all-or-nothing by sdmi_finalize_weights' rule; call it after.  Out of scope: .ckpt pickles, diffusers-layout and sharded checkpoints, SD 2.x / SDXL. */
+ * all-or-nothing by sdmi_finalize_weights' rule; call it after.  Out of scope: .ckpt pickles, diffusers-layout and sharded checkpoints, SDXL.
+ * On a variant = 1 context the file is an SD 2.x checkpoint in Stability's layout: the UNet and VAE keys of v1 -- the transformers' proj_in /
+ * proj_out as Linear [C, C], taken as [C, C, 1, 1] -- and the OpenCLIP text encoder under "cond_stage_model.model." (sdmi_checkpoint_key_ex), whose fused
+ * attn.in_proj_weight [3C, C] / in_proj_bias [3C] is uploaded as three views of the mapped bytes: rows 0..C-1 query, C..2C-1 key, 2C..3C-1 value.  A file of the other
+ * family (sdmi_safetensors_model_family) is SDMI_ERR_WEIGHTS before anything is looked up, naming the key that gives it away. */
 int sdmi_load_weights_safetensors(sdmi_ctx* ctx, const char* path);
+/* Host only.  *family = 1: an SD v1 checkpoint (the file has "cond_stage_model.transformer.text_model.final_layer_norm.weight"), 2: SD 2.x
+ * ("cond_stage_model.model.ln_final.weight"), 0: neither key (a bare UNet, a ControlNet, a LoRA ...).  Errors as sdmi_safetensors_list. */
+int sdmi_safetensors_model_family(const char* path, int32_t* family);
 /* Host only (no context): the tensors of a .safetensors file as text, one "key<TAB>dtype<TAB>d0,d1,..<TAB>file offset<TAB>dump name or -" line each, in
  * header order.  A backslash, tab, newline or other control character inside a key is written as its JSON escape, so that a key stays one field.  The dump
  * name is the one whose sdmi_checkpoint_key is the key (SD v1.4's tensor set), "-" for any other key.  *needed = bytes incl. the terminator; out may be
@@ -151,6 +163,9 @@ int sdmi_safetensors_list(const char* path, char* out, size_t capacity, size_t* 
  * incl. the terminator; out may be NULL to query it.
  * SDMI_ERR_INVALID for a name that has no checkpoint source: module metadata such as eps / n_group, n_steps. */
 int sdmi_checkpoint_key(const char* dump_name, char* out, size_t capacity, size_t* needed, int32_t* transposed);
+/* The same for sdmi_config.variant `variant` (0: exactly the above; 1: SD 2.x, tests/golden/sd2_ckpt_keys.txt; anything else SDMI_ERR_INVALID).  *slice (may be NULL):
+ * -1 = the key's whole tensor, 0 / 1 / 2 = the first / second / third third of its rows (query / key / value of a fused attn.in_proj_weight or in_proj_bias). */
+int sdmi_checkpoint_key_ex(const char* dump_name, int32_t variant, char* out, size_t capacity, size_t* needed, int32_t* transposed, int32_t* slice);
 /* Host only.  The schedule sdmi_load_weights_safetensors installs when the file has no alphas_cumprod: the LDM "scaled linear" one,
  * float32(cumprod(1 - linspace(sqrt(0.00085), sqrt(0.012), n)^2)) computed in f64.  out [n], n >= 1. */
 int sdmi_default_alphas_cumprod(float* out, int32_t n);
@@ -291,7 +306,7 @@ int sdmi_get_sampler(sdmi_ctx* ctx, sdmi_sampler* out);
  * blend follows a step's LAST evaluation, with 1 / (1 + s'^2) for a_prev.  sdmi_sample_latent's init_latent is the VP latent at the schedule's first sigma.
  * The two sticky states exclude each other: a successful sdmi_set_ksampler(non-NULL) resets the sdmi_sampler to its default, and any sdmi_set_sampler call (NULL included)
  * clears the k-sampler.  With no k-sampler set every call runs the launches and gives the bits it gave before.  A ControlNet window counts the call's STEPS: both
- * evaluations of a step agree.  Out of scope: LMS / PLMS on non-uniform schedules, UniPC, s_churn, v-prediction, bit-compatibility with k-diffusion's noise. */
+ * evaluations of a step agree.  Out of scope: LMS / PLMS on non-uniform schedules, UniPC, s_churn, bit-compatibility with k-diffusion's noise.  (v-prediction: sdmi_set_prediction.) */
 typedef struct sdmi_ksampler {
     int32_t kind;      /* 0 euler (eta), 1 dpmpp_2m, 2 heun, 3 dpm2, 4 dpmpp_2s (eta), 5 dpmpp_sde (eta), 6 dpmpp_2m_sde (eta) */
     int32_t schedule;  /* 0 model (the reference's integer timesteps), 1 karras, 2 exponential, 3 uniform */
@@ -318,6 +333,21 @@ int sdmi_ksampler_sigmas(const sdmi_ksampler* ksampler, const float* alphas_cump
 int sdmi_sigma_to_t(const float* alphas_cumprod, int32_t total, double sigma, double* t);
 int sdmi_ksampler_plan(const sdmi_ksampler* ksampler, const float* alphas_cumprod, int32_t total, size_t n_steps, double strength, double* rows, int32_t capacity,
                        int32_t* count);
+
+/* ---- what the model predicts: eps or v (no reference counterpart) ----
+ * SD 2.x's 768 models predict v = sqrt(a) eps - sqrt(1 - a) x0 instead of eps.  kind: 0 = eps (the default), 1 = v; sticky; anything else is SDMI_ERR_INVALID and
+ * changes nothing.  Every update the engine launches is linear in x and in the guided model output, and so is classifier-free guidance: with a = sqrt(a_t),
+ * b = sqrt(1 - a_t) at the evaluation's (possibly fractional) timestep, eps = a v + b x, and the step for v is the step for eps with its coefficient row rewritten --
+ * cx += ce b, ce *= a, qx += qe b, qe *= a.  No kernel changes and no launch is added.  It holds for every sdmi_set_sampler and sdmi_set_ksampler kind (there
+ * a = 1 / sqrt(1 + sigma^2), b = sigma / sqrt(1 + sigma^2)) and for the default path, which under v runs DDIM(eta = 0) through the sampler-choice step kernel on that
+ * table (the default path's own update divides by sqrt(a_t) and is kept as it is) -- and with them for img2img, masks, the hires pass, inpainting and the sharded loop.
+ * With eps set every call runs the launches and gives the bits it gave before.  A checkpoint does not say what it predicts (512-base: eps, 768-v: v; the .yaml that says
+ * so is not read): the caller chooses.  The _ex forms of the host-only table functions take the same `prediction`. */
+int sdmi_set_prediction(sdmi_ctx* ctx, int32_t kind);
+int sdmi_sampler_coefs_ex(const sdmi_sampler* sampler, const float* alphas_cumprod, int32_t total, const int32_t* ts, int32_t count,
+                          int64_t step_size, int32_t prediction, double* coefs);
+int sdmi_ksampler_plan_ex(const sdmi_ksampler* ksampler, const float* alphas_cumprod, int32_t total, size_t n_steps, double strength, int32_t prediction, double* rows,
+                          int32_t capacity, int32_t* count);
 
 /* ---- ControlNet (SD v1; no reference counterpart) -----------------------------------------------------
  * A context created with sdmi_config.control_hint_ch = 3 has a fourth weight group, "controlnet/...": a second copy of the UNet's time MLP
@@ -856,6 +886,19 @@ int sdmi_bench_conv(sdmi_ctx* ctx, int32_t n, int32_t cin, int32_t h, int32_t w,
  * average kernel ms over `iters` launches (HIP events). */
 int sdmi_bench_attention(sdmi_ctx* ctx, int32_t n, int32_t nq, int32_t nk, int32_t n_state, int32_t n_head,
                          int32_t iters, double* ms_out);
+/* What the context WOULD run for a qkv_attention of this shape under its current options: host only, no launch.  The call planned is the one
+ * sdmi_qkv_attention makes (and the UNet's transformer blocks): dense rows of n_head * d_head elements, the context's storage type (fp32 when has_mask is set:
+ * the masked path is fp32 at every precision), the three-plane output where option gemm_planes takes it.  Errors are the planner's (SDMI_ERR_UNSUPPORTED for
+ * a head dim no kernel serves). */
+typedef struct sdmi_attn_plan {
+    int32_t kernel;      /* 0 = unfused (GEMM kernels), 1 = k_attn.hip (fp32 matrix instructions), 2 = k_attn_split.hip (fp32 on the bf16 pipe), 3 = k_attn_bf16.hip */
+    int32_t waves;       /* per workgroup; 0 for the unfused path                                                                             */
+    int32_t q_rows;      /* query rows per workgroup                                                                                          */
+    int32_t kv_tile;     /* keys per K / V tile                                                                                               */
+    int32_t kv_splits;   /* key slices; > 1: partial results + a merge launch                                                                 */
+    int32_t reserved[3];
+} sdmi_attn_plan;
+int sdmi_attention_plan(sdmi_ctx* ctx, int32_t n, int32_t n_head, int32_t nq, int32_t nk, int32_t d_head, int32_t has_mask, sdmi_attn_plan* out);
 
 #ifdef __cplusplus
 }

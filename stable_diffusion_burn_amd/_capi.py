@@ -39,6 +39,20 @@ class SdmiConfig(C.Structure):
     def control_hint_ch(self, v: int) -> None:
         self.reserved[0] = int(v)
 
+    # sdmi_config.variant (0 = SD v1, 1 = SD 2.x) is the second of them
+    @property
+    def variant(self) -> int:
+        return int(self.reserved[1])
+
+    @variant.setter
+    def variant(self, v: int) -> None:
+        self.reserved[1] = int(v)
+
+
+class SdmiAttnPlan(C.Structure):
+    """sdmi_attn_plan: what a context would run for an attention shape (sdmi_attention_plan; host only)"""
+    _fields_ = [("kernel", C.c_int32), ("waves", C.c_int32), ("q_rows", C.c_int32), ("kv_tile", C.c_int32), ("kv_splits", C.c_int32), ("reserved", C.c_int32 * 3)]
+
 
 class SdmiOpView(C.Structure):
     """sdmi_op_view: where an operator's input and output sit inside wider parent buffers (sdmi_op_*_view; tests)"""
@@ -109,6 +123,8 @@ SIGNATURES = {
     "sdmi_load_weights_safetensors": (C.c_int, [_CTX, C.c_char_p]),
     "sdmi_safetensors_list": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sdmi_checkpoint_key": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
+    "sdmi_checkpoint_key_ex": (C.c_int, [C.c_char_p, C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sdmi_safetensors_model_family": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32)]),
     "sdmi_default_alphas_cumprod": (C.c_int, [_F, C.c_int32]),
     "sdmi_load_weights_packed": (C.c_int, [_CTX, _F, C.c_size_t, C.c_int32]),
     "sdmi_packed_size": (C.c_int64, [_CTX, C.c_int32]),
@@ -135,6 +151,7 @@ SIGNATURES = {
     "sdmi_ksampler_sigmas": (C.c_int, [_KSAMPLER, _F, C.c_int32, C.c_size_t, _F64, C.c_int32, C.POINTER(C.c_int32)]),
     "sdmi_sigma_to_t": (C.c_int, [_F, C.c_int32, C.c_double, _F64]),
     "sdmi_ksampler_plan": (C.c_int, [_KSAMPLER, _F, C.c_int32, C.c_size_t, C.c_double, _F64, C.c_int32, C.POINTER(C.c_int32)]),
+    "sdmi_ksampler_plan_ex": (C.c_int, [_KSAMPLER, _F, C.c_int32, C.c_size_t, C.c_double, C.c_int32, _F64, C.c_int32, C.POINTER(C.c_int32)]),
     "sdmi_load_control_safetensors": (C.c_int, [_CTX, C.c_char_p]),
     "sdmi_control_ready": (C.c_int, [_CTX]),
     "sdmi_set_control": (C.c_int, [_CTX, C.POINTER(SdmiControl)]),
@@ -143,6 +160,8 @@ SIGNATURES = {
     "sdmi_control_residuals_size": (C.c_int64, [_CTX, C.c_int32]),
     "sdmi_control_residuals": (C.c_int, [_CTX, _F, C.c_int32, _F, C.c_int32, C.c_int32, _F]),
     "sdmi_sampler_coefs": (C.c_int, [_SAMPLER, _F, C.c_int32, _I32, C.c_int32, C.c_int64, C.POINTER(C.c_double)]),
+    "sdmi_sampler_coefs_ex": (C.c_int, [_SAMPLER, _F, C.c_int32, _I32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_double)]),
+    "sdmi_set_prediction": (C.c_int, [_CTX, C.c_int32]),
     "sdmi_set_latent_size": (C.c_int, [_CTX, C.c_int32, C.c_int32]),
     "sdmi_get_latent_size": (C.c_int, [_CTX, _I32, _I32]),
     "sdmi_resize_weights": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I32, _I32, C.POINTER(C.c_double), C.c_int32, _I32, _I32]),
@@ -224,6 +243,7 @@ SIGNATURES = {
     "sdmi_profile_overhead": (C.c_int, [_CTX, C.POINTER(C.c_double)]),
     "sdmi_bench_conv": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "sdmi_bench_attention": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
+    "sdmi_attention_plan": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SdmiAttnPlan)]),
 }
 
 _lib = None

@@ -40,6 +40,20 @@ static int plan_kv_splits(const AttnPlanIn& p, const AttnPlanOpts& o, bool on_sp
     return (int)std::max<long long>(1, s);
 }
 
+// attn_d64 = 2, fp32: the d = 64 calls that stay on k_attn.hip because the interleaved A/B measured k_attn_split.hip slower there (profiles/r13a_attn_d64_ab.txt, 216
+// shapes).  k_attn_split.hip wins wherever k_attn.hip needs more than one round of workgroups or walks a long key loop (1.1 - 2.0 x); it loses 2 - 8 % in the
+// latency-bound regime -- k_attn.hip's 64-row workgroups, key slices included, fit the CUs in ONE round and each walks a handful of key tiles: a 128-row workgroup then
+// is a longer serial chain (3.6 against 3.2 us per 64-key tile, measured) and nothing is left for it to overlap.  Two measured constants: a tile of k_attn_split.hip
+// costs 9/8 of one of k_attn.hip's, a merge launch 15/8.  At nq <= 64 both kernels run one partly filled query tile: equal within 1.5 %, the call goes to the new instance.
+static bool d64_stays_on_flash(const AttnPlanIn& p, const AttnPlanOpts& o) {
+    if (p.nq <= 64) return false;
+    const int tiles = (p.nk + 63) / 64;
+    const int sf = plan_kv_splits(p, o, false), ss = plan_kv_splits(p, o, true);
+    if (workgroups(p, 64) * sf > kCUs) return false;
+    const int tf = (tiles + sf - 1) / sf, ts = (tiles + ss - 1) / ss;
+    return 8 * tf + (sf > 1 ? 15 : 0) <= 9 * ts + (ss > 1 ? 15 : 0);
+}
+
 // k_attn.hip: 8-wave workgroups once they still fill the chip (>= 1.5 workgroups per CU), else 4-wave
 static AttnPlan plan_flash(const AttnPlanIn& p, int kv_splits) {
     return form(p, AttnKernel::Flash, 2 * workgroups(p, 128) >= 3 * kCUs ? 8 : 4, kv_splits);
@@ -87,8 +101,8 @@ AttnPlan plan_attention(const AttnPlanIn& p, const AttnPlanOpts& o) {
         return a;
     }
     if (p.bf16 && p.has_mask) throw Error(SDMI_ERR_UNSUPPORTED, "attention: additive mask is fp32-only");
-    if (p.bf16 && o.attn_bf16 && attn_bf16_head_dim(d)) return plan_bf16(p, o);
-    const bool on_split = !p.bf16 && !p.has_mask && o.attn_split && p.rows_aligned && attn_geom(AttnKernel::Split, d);
+    if (p.bf16 && o.attn_bf16 && attn_bf16_head_dim(d, o.attn_d64)) return plan_bf16(p, o);
+    const bool on_split = !p.bf16 && !p.has_mask && o.attn_split && p.rows_aligned && attn_split_head_dim(d, o.attn_d64) && !(d == 64 && o.attn_d64 == 2 && d64_stays_on_flash(p, o));
     const int kv_splits = plan_kv_splits(p, o, on_split);
     return on_split ? plan_split(p, o, kv_splits) : plan_flash(p, kv_splits);
 }

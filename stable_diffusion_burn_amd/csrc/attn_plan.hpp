@@ -18,9 +18,9 @@ enum class AttnKernel {
 struct AttnGeom { AttnKernel kernel; int d_head, qr, rows_per_wave, kv_tile; };
 inline constexpr AttnGeom kAttnGeom[] = {
     {AttnKernel::Flash, 40, 1, 16, 64}, {AttnKernel::Flash, 64, 1, 16, 64}, {AttnKernel::Flash, 80, 1, 16, 64}, {AttnKernel::Flash, 160, 1, 16, 32},   // 64: CLIP (768 / 12)
-    {AttnKernel::Split, 40, 1, 32, 64}, {AttnKernel::Split, 80, 1, 32, 64},
+    {AttnKernel::Split, 40, 1, 32, 64}, {AttnKernel::Split, 64, 1, 32, 64}, {AttnKernel::Split, 80, 1, 32, 64},   // 64: SD 2.x's UNet, behind option attn_d64
     {AttnKernel::Bf16, 40, 1, 32, 128}, {AttnKernel::Bf16, 40, 2, 64, 64},   // d = 40 is softmax-bound: fewer / longer iterations; with two query blocks per wave 64 keys fit the registers
-    {AttnKernel::Bf16, 80, 1, 32, 64}, {AttnKernel::Bf16, 160, 1, 32, 64},
+    {AttnKernel::Bf16, 64, 1, 32, 64}, {AttnKernel::Bf16, 80, 1, 32, 64}, {AttnKernel::Bf16, 160, 1, 32, 64},     // 64: behind option attn_d64
 };
 constexpr const AttnGeom* attn_geom(AttnKernel k, int d_head, int qr = 1) {
     for (const AttnGeom& g : kAttnGeom)
@@ -30,7 +30,10 @@ constexpr const AttnGeom* attn_geom(AttnKernel k, int d_head, int qr = 1) {
 // the head dims with a fused kernel (every one of them has a k_attn.hip instance) ...
 constexpr bool attn_supported_head_dim(int d) { return attn_geom(AttnKernel::Flash, d) != nullptr; }
 // ... and those k_attn_bf16.hip serves.  Bf16 q tensors of these head dims arrive multiplied by attn_bf16_q_scale (kernels.hpp), whichever kernel runs.
-constexpr bool attn_bf16_head_dim(int d) { return attn_geom(AttnKernel::Bf16, d) != nullptr; }
+// d = 64 has instances of k_attn_split.hip and k_attn_bf16.hip that only option attn_d64 opens (AttnPlanOpts): without it d = 64 is what it was before they existed,
+// k_attn.hip at every precision and no pre-scaled query.
+constexpr bool attn_bf16_head_dim(int d, int attn_d64 = 0) { return attn_geom(AttnKernel::Bf16, d) != nullptr && (d != 64 || attn_d64); }
+constexpr bool attn_split_head_dim(int d, int attn_d64 = 0) { return attn_geom(AttnKernel::Split, d) != nullptr && (d != 64 || attn_d64); }
 
 struct AttnPlanIn {
     int n, n_head, nq;
@@ -51,6 +54,9 @@ struct AttnPlanOpts {
                                  // reference maximum as accumulator input and the row sum from a ones column (LG) (A/B, tests)
     int attn_kv_splits = 0;      // fp32, no mask: key slices + merge launch where the query-tile grid leaves CUs idle: 0 = automatic, 1 = never, S = forced
     int attn_kv_prefer8 = 1;     // ... and, for k_attn_split.hip, as many slices as let its 8-wave form fill the chip (A/B switch)
+    int attn_d64 = 0;            // d_head 64: 0 = on k_attn.hip as before; 1 = on k_attn_split.hip (fp32, no mask, aligned rows) and k_attn_bf16.hip (bf16) wherever they
+                                 // take the call (tests, A/B); 2 = the same, except the fp32 calls measured slower there (attn_plan.cpp: d64_stays_on_flash).  The engine's
+                                 // default is 2 on an SD 2.x context (sdmi_config.variant = 1), whose UNet has 64-wide heads at every level
 };
 
 struct AttnPlan {

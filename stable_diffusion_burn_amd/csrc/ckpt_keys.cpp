@@ -234,9 +234,53 @@ bool clip(Walk& w) {
     return renamed(w, k);
 }
 
+// SD 2.x: the OpenCLIP text tower as Stability's checkpoints name it (open_clip's TextTransformer under FrozenOpenCLIPEmbedder.model)
+bool open_clip(Walk& w, int* slice) {
+    w.key = "cond_stage_model.model";
+    int i = 0;
+    if (w.take("blocks")) {
+        if (!take_numbered(w, "", 0, 999, &i)) return false;
+        w.key += ".transformer.resblocks." + std::to_string(i);
+        if (w.take("attn")) {
+            w.key += ".attn";
+            static const char* const part[3] = {"query", "key", "value"};
+            for (int p = 0; p < 3; ++p)
+                if (w.take(part[p])) {   // nn.MultiheadAttention's fused projection: rows [p C, (p + 1) C) of in_proj_weight / in_proj_bias
+                    if (w.i + 1 != w.t.size() || (w.cur() != "weight" && w.cur() != "bias")) return false;
+                    w.transposed = w.cur() == "weight";
+                    w.key += w.cur() == "weight" ? ".in_proj_weight" : ".in_proj_bias";
+                    *slice = p;
+                    return true;
+                }
+            static const Rename k[] = {{"out", ".out_proj", L_LINEAR}};
+            return renamed(w, k);
+        }
+        if (w.take("mlp")) {
+            w.key += ".mlp";
+            static const Rename k[] = {{"fc1", ".c_fc", L_LINEAR}, {"fc2", ".c_proj", L_LINEAR}};
+            return renamed(w, k);
+        }
+        static const Rename k[] = {{"attn_ln", ".ln_1", L_PLAIN}, {"mlp_ln", ".ln_2", L_PLAIN}};
+        return renamed(w, k);
+    }
+    if (w.take("position_embedding")) {   // a bare nn.Parameter: no ".weight"
+        if (w.i + 1 != w.t.size() || w.cur() != "weight") return false;
+        w.key += ".positional_embedding";
+        return true;
+    }
+    static const Rename k[] = {{"token_embedding", ".token_embedding", L_TABLE}, {"layer_norm", ".ln_final", L_PLAIN}};
+    return renamed(w, k);
+}
+
 }  // namespace
 
-bool checkpoint_key(const std::string& dump_name, std::string* key, bool* transposed) {
+const char* const kFamilyKeySd1 = "cond_stage_model.transformer.text_model.final_layer_norm.weight";
+const char* const kFamilyKeySd2 = "cond_stage_model.model.ln_final.weight";
+
+bool checkpoint_key(const std::string& dump_name, std::string* key, bool* transposed) { return checkpoint_key(dump_name, 0, key, transposed, nullptr); }
+
+bool checkpoint_key(const std::string& dump_name, int variant, std::string* key, bool* transposed, int* slice) {
+    int sl = -1;
     Walk w;
     size_t start = 0;
     for (;;) {
@@ -251,10 +295,11 @@ bool checkpoint_key(const std::string& dump_name, std::string* key, bool* transp
     else if (w.take("unet")) ok = unet(w);
     else if (w.take("controlnet")) ok = unet(w, true);
     else if (w.take("autoencoder")) ok = autoencoder(w);
-    else if (w.take("clip")) ok = clip(w);
+    else if (w.take("clip")) ok = variant == 1 ? open_clip(w, &sl) : clip(w);
     if (!ok) return false;
     if (key) *key = w.key;
     if (transposed) *transposed = w.transposed;
+    if (slice) *slice = sl;
     return true;
 }
 

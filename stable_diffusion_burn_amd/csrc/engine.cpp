@@ -224,13 +224,17 @@ Engine::Engine(const sdmi_config& cfg) : cfg_(cfg) {
         throw Error(SDMI_ERR_UNSUPPORTED, "precision=1 (bf16) needs model_channels, vae_ch and ctx_dim to be multiples of 64");
     if (cfg.model_channels % 32 || cfg.model_channels <= 0) throw Error(SDMI_ERR_INVALID, "model_channels must be a positive multiple of 32");
     if (cfg.vae_ch % 32 || cfg.vae_ch <= 0) throw Error(SDMI_ERR_INVALID, "vae_ch must be a positive multiple of 32");
-    if (cfg.n_head <= 0 || cfg.model_channels % cfg.n_head) throw Error(SDMI_ERR_INVALID, "n_head must divide model_channels");
+    if (cfg.variant != 0 && cfg.variant != 1) throw Error(SDMI_ERR_INVALID, "variant must be 0 (SD v1) or 1 (SD 2.x)");
+    if (cfg.variant == 1 && cfg.model_channels % 64) throw Error(SDMI_ERR_INVALID, "variant = 1 (SD 2.x): model_channels must be a multiple of 64, the head width");
+    if (cfg.variant == 0 && (cfg.n_head <= 0 || cfg.model_channels % cfg.n_head)) throw Error(SDMI_ERR_INVALID, "n_head must divide model_channels");
     if (cfg.ctx_dim % 32 || cfg.ctx_dim <= 0) throw Error(SDMI_ERR_INVALID, "ctx_dim must be a positive multiple of 32");
     if (cfg_.unet_in_ch == 0) cfg_.unet_in_ch = 4;   // a zeroed field: the latent alone
     if (cfg_.unet_in_ch < 4 || cfg_.unet_in_ch > 12) throw Error(SDMI_ERR_INVALID, "unet_in_ch must be 4 (the latent alone) or 5 .. 12 (the latent + conditioning channels)");
     if (cfg_.control_hint_ch != 0 && cfg_.control_hint_ch != 3) throw Error(SDMI_ERR_INVALID, "control_hint_ch must be 0 (no ControlNet) or 3 (an RGB hint)");
     if (cfg_.control_hint_ch != 0 && cfg_.unet_in_ch != 4)
         throw Error(SDMI_ERR_UNSUPPORTED, "control_hint_ch != 0 needs unet_in_ch = 4: the control encoder's first convolution takes the 4 latent channels");
+    if (cfg_.control_hint_ch != 0 && cfg_.variant == 1) throw Error(SDMI_ERR_UNSUPPORTED, "control_hint_ch != 0 is not supported on a variant = 1 (SD 2.x) context");
+    aopt_.attn_d64 = cfg_.variant == 1 ? 2 : 0;   // before build_model: the query weights' pre-scale follows it (q_prescaled)
     check_latent_size(cfg.latent_h, cfg.latent_w);
     lat_h_ = cfg.latent_h;
     lat_w_ = cfg.latent_w;
@@ -415,14 +419,16 @@ void Engine::build_model() {
         lin(m.q, path + "/query", c, c, false);
         // precision >= 1: the bf16 attention kernel takes q in log2 units -- d_head^-0.5 log2(e) is folded into the query weight here, in
         // fp32, before its only rounding (attention.rs:15-26 applies d_head^-0.25 to q and to k)
-        if (q_prescaled(m.q.dt, c / cfg_.n_head)) entries_[entry_index_.at(path + "/query/weight")].pre_scale = attn_bf16_q_scale(c / cfg_.n_head);
+        const int heads = unet_heads(c);
+        if (q_prescaled(m.q.dt, c / heads)) entries_[entry_index_.at(path + "/query/weight")].pre_scale = attn_bf16_q_scale(c / heads);
+        if (m.q.dt && c / heads == 64) q64_entries_.push_back(entry_index_.at(path + "/query/weight"));   // option attn_d64 decides their pre-scale
         lin(m.k, path + "/key", cctx, c, false);
         lin(m.v, path + "/value", cctx, c, false);
         lin(m.out, path + "/out", c, c, true);
         fp8_copy_lin(m.q, path + "/query/weight");
         if (c == cctx) { fp8_copy_lin(m.k, path + "/key/weight"); fp8_copy_lin(m.v, path + "/value/weight"); }   // (cross-attention K / V: hoisted, once per call, bf16)
         fp8_copy_lin(m.out, path + "/out/weight");
-        add_meta(path + "/n_head", 1, (float)cfg_.n_head, 0.f, nullptr);
+        add_meta(path + "/n_head", 1, (float)heads, 0.f, nullptr);
     };
     auto spatial = [&](SpatialW& s, const std::string& path, int c) {  // unet/mod.rs:436-527
         s.c = c;
@@ -1038,15 +1044,24 @@ void Engine::load_safetensors_groups(const char* path, bool control) {
     SDMI_HIP(hipSetDevice(cfg_.device));
     lora_refuse_bulk_load(fn_name.c_str());
     SafetensorsFile f(path);
-    struct Job { WeightEntry* e; const StTensor* t; int dtype; int transform; };
+    // data / nbytes: the bytes the entry is made from -- the key's whole tensor, or (variant = 1: the text encoder's fused attn.in_proj_*) one of its three row
+    // blocks, a view of the mapping: no host copy, the same widen-and-transpose launch
+    struct Job { WeightEntry* e; const StTensor* t; int dtype; int transform; const unsigned char* data; size_t nbytes; };
     std::vector<Job> jobs;
+    if (!control) {   // a file of the other model family: refused here, before anything is looked up or staged
+        const char* other = cfg_.variant == 1 ? kFamilyKeySd1 : kFamilyKeySd2;
+        if (f.find(other))
+            throw Error(SDMI_ERR_WEIGHTS, fn_name + ": " + path + " holds '" + other + "': " + (cfg_.variant == 1 ? "an SD v1 checkpoint, and this context is SD 2.x (variant = 1)"
+                                                                                                              : "an SD 2.x checkpoint, and this context is SD v1 (variant = 0)"));
+    }
     const StTensor* alphas = nullptr;
     WeightEntry* alphas_entry = nullptr;
     for (auto& e : entries_) {
         if ((e.group == 3) != control) continue;   // a ControlNet comes in a file of its own (load_control_safetensors)
         std::string key;
         bool transposed = false;
-        if (!checkpoint_key(e.name, &key, &transposed)) throw Error(SDMI_ERR_STATE, fn_name + ": no checkpoint key rule for '" + e.name + "'");
+        int slice = -1;
+        if (!checkpoint_key(e.name, cfg_.variant, &key, &transposed, &slice)) throw Error(SDMI_ERR_STATE, fn_name + ": no checkpoint key rule for '" + e.name + "'");
         const StTensor* t = f.find(key);
         if (e.kind == 3) { alphas = t; alphas_entry = &e; continue; }   // optional: the LDM schedule is computed when the file has none
         if (!t) {
@@ -1060,12 +1075,17 @@ void Engine::load_safetensors_groups(const char* path, bool control) {
         int64_t want[4];
         for (int i = 0; i < e.ndim; ++i) want[i] = e.dims[i];
         if (transposed) std::swap(want[0], want[1]);   // torch's [out, in]
+        if (slice >= 0) want[0] *= 3;                  // the fused [3C, C] / [3C]: this entry is rows [slice C, (slice + 1) C)
         bool ok = (int)t->shape.size() == e.ndim;
         for (int i = 0; ok && i < e.ndim; ++i) ok = t->shape[i] == want[i];
+        // SD 2.x: the transformers' proj_in / proj_out are Linear layers, [C, C] in the file -- the bytes of the [C, C, 1, 1] convolution weight
+        if (!ok && cfg_.variant == 1 && e.kind == 0 && e.ndim == 4 && e.dims[2] == 1 && e.dims[3] == 1 && t->shape.size() == 2)
+            ok = t->shape[0] == e.dims[0] && t->shape[1] == e.dims[1];
         if (!ok)
             throw Error(SDMI_ERR_WEIGHTS, fn_name + ": '" + key + "' has shape " + shape_str(t->shape.data(), t->shape.size()) +
                                               ", the configured model expects " + shape_str(want, (size_t)e.ndim) + " ('" + e.name + "')");
-        jobs.push_back(Job{&e, t, dt, transposed ? 1 : (e.kind == 0 && padded_cin(e) != e.dims[1]) ? 2 : 0});
+        const size_t part = slice >= 0 ? t->nbytes / 3 : t->nbytes;
+        jobs.push_back(Job{&e, t, dt, transposed ? 1 : (e.kind == 0 && padded_cin(e) != e.dims[1]) ? 2 : 0, t->data + (slice >= 0 ? (size_t)slice * part : 0), part});
     }
     if (jobs.empty()) throw Error(SDMI_ERR_WEIGHTS, std::string(fn_name + ": no tensor of ") + path + " matches the configured model");
     std::vector<float> schedule;
@@ -1103,10 +1123,10 @@ void Engine::load_safetensors_groups(const char* path, bool control) {
         WeightEntry& e = *j.e;
         ensure_arena(e.group);
         size_t off; int half;
-        char* pinned = stage_reserve(j.t->nbytes, &off, &half);
-        std::memcpy(pinned, j.t->data, j.t->nbytes);   // any file alignment
+        char* pinned = stage_reserve(j.nbytes, &off, &half);
+        std::memcpy(pinned, j.data, j.nbytes);   // any file alignment
         char* dev = stager_->dev[half] + off;
-        SDMI_HIP(hipMemcpyAsync(dev, pinned, j.t->nbytes, hipMemcpyHostToDevice, stream_));
+        SDMI_HIP(hipMemcpyAsync(dev, pinned, j.nbytes, hipMemcpyHostToDevice, stream_));
         float* out = e.kind <= 1 ? static_cast<float*>(conv_stage.p) : *e.dst;
         fold_touch(e);
         long long d0, d1;
@@ -1114,7 +1134,7 @@ void Engine::load_safetensors_groups(const char* path, bool control) {
         else if (j.transform == 2) { d0 = e.dims[0]; d1 = e.dims[2] * e.dims[3]; }
         else { d0 = (long long)entry_count(e); d1 = 1; }
         {
-            ProfScope ps_o(this, PC_OTHER, 0, (double)j.t->nbytes + (double)(e.kind <= 1 ? stage_elems(e) : entry_count(e)) * 4);
+            ProfScope ps_o(this, PC_OTHER, 0, (double)j.nbytes + (double)(e.kind <= 1 ? stage_elems(e) : entry_count(e)) * 4);
             ps_o.set_tag("unpack %s t%d %lldx%lld", j.t->dtype.c_str(), j.transform, d0, d1);
             SDMI_HIP(launch_unpack_tensor(dev, j.dtype, j.transform, d0, d1, out, stream_, (int)e.dims[1]));
         }
@@ -1676,6 +1696,16 @@ void Engine::set_option(const std::string& key, const std::string& value) {
     else if (key == "attn_bf16") aopt_.attn_bf16 = std::stoi(value);
     else if (key == "attn_bf16_variant") aopt_.attn_bf16_variant = (value == "default") ? AttnPlanOpts().attn_bf16_variant : std::stoi(value, nullptr, 0);
     else if (key == "attn_split") aopt_.attn_split = std::stoi(value);
+    else if (key == "attn_d64") {   // d_head = 64 on k_attn_split.hip / k_attn_bf16.hip: 0 never, 1 wherever they take the call, 2 where measured faster; "default": 2 on an SD 2.x context
+        const int v = (value == "default") ? (cfg_.variant == 1 ? 2 : 0) : std::stoi(value);
+        if (v < 0 || v > 2) throw Error(SDMI_ERR_INVALID, "attn_d64: 0 (never), 1 (wherever supported) or 2 (where measured faster)");
+        if ((v != 0) != (aopt_.attn_d64 != 0) && !q64_entries_.empty()) {   // a bf16 UNet with 64-wide heads: the option decides whether its query weights are packed pre-scaled
+            for (int i : q64_entries_)
+                if (entries_[(size_t)i].set) throw Error(SDMI_ERR_STATE, "attn_d64 decides the scale the 64-wide heads' query weights are packed with: set it before they are loaded");
+            for (int i : q64_entries_) entries_[(size_t)i].pre_scale = v ? attn_bf16_q_scale(64) : 1.f;
+        }
+        aopt_.attn_d64 = v;
+    }
     else if (key == "gemm_bf16x") gopt_.gemm_bf16x = std::stoi(value);
     else if (key == "gemm_x32") gopt_.gemm_x32 = std::stoi(value);
     else if (key == "gemm_f32s") gopt_.gemm_f32s = std::stoi(value);
@@ -2428,7 +2458,7 @@ void Engine::spatial_transformer(const SpatialW& w, const Act& x, Act& y) {
         return d2;
     };
     const int C = w.c, hw = x.h * x.w;
-    const int heads = cfg_.n_head, d = C / heads;
+    const int heads = unet_heads(C), d = C / heads;
     if (y.n != x.n && use_fp8_wide(w.proj_in.bt8, y.rows()) && x.dt == 1 && y.dt == 1) {   // option fp8_linear: no shared form -- duplicate first
         Act x2 = duplicate(x);
         spatial_transformer(w, x2, y);
@@ -2993,7 +3023,7 @@ void Engine::clip_forward_dev(const int32_t* tokens, const int32_t* emb_row, con
         gemm(a.f(), (int)M, b.out.bt, b.out.bias, C, C, x.f(), C, x.f(), C, 0);               // x += out(attn)
         layer_norm(b.mlp_ln, x.f(), M, h.f(), 0);
         gemm(h.f(), (int)M, b.fc1.bt, b.fc1.bias, C, 4 * C, f.f(), 4 * C, nullptr, 0, 0);
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_quick_gelu(f.f(), M * 4 * C, stream_)); }
+        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(cfg_.variant == 1 ? launch_gelu_erf(f.f(), M * 4 * C, stream_) : launch_quick_gelu(f.f(), M * 4 * C, stream_)); }
         count_kernel();
         gemm(f.f(), (int)M, b.fc2.bt, b.fc2.bias, 4 * C, C, x.f(), C, x.f(), C, 0);           // x += fc2(gelu(fc1))
     }
@@ -3168,6 +3198,11 @@ void Engine::set_sampler(const sdmi_sampler* s) {
     kset_ = false;
 }
 
+void Engine::set_prediction(int kind) {
+    if (kind != 0 && kind != 1) throw Error(SDMI_ERR_INVALID, "set_prediction: kind must be 0 (eps) or 1 (v)");
+    prediction_ = kind;
+}
+
 void Engine::set_ksampler(const sdmi_ksampler* k) {
     if (!k) { ksampler_ = sdmi_ksampler{}; kset_ = false; return; }
     check_ksampler(*k, alphas_.empty() ? nullptr : alphas_.data(), (int)alphas_.size());
@@ -3177,7 +3212,7 @@ void Engine::set_ksampler(const sdmi_ksampler* k) {
 }
 
 std::vector<double> Engine::kplan_for(size_t n_steps, double strength, double* a0) const {
-    std::vector<double> rows = ksampler_plan(ksampler_, alphas_.data(), (int)alphas_.size(), n_steps, strength);
+    std::vector<double> rows = ksampler_plan(ksampler_, alphas_.data(), (int)alphas_.size(), n_steps, strength, nullptr, prediction_);
     const double s0 = rows[KP_SIGMA];
     if (a0) *a0 = 1.0 / (1.0 + s0 * s0);
     return rows;
@@ -3218,13 +3253,14 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
     std::unique_ptr<Buf> unet_in_c;
     if (cond_nhwc) unet_in_c.reset(new Buf(this, (size_t)(2 * per_half / 4) * unet_in_padded() * 4));
     // sampler choice: the coefficient table of the call and its history slots (x0 for DPM-Solver++(2M), three e for PLMS)
-    const bool custom = !kplan && (sampler_.kind != 0 || sampler_.eta != 0.0);
+    // (v-prediction: the default path too runs on the table -- DDIM(eta = 0), depth 0 -- because cfg_ddim_update divides by sqrt(a_t) and is kept as it is)
+    const bool custom = !kplan && (sampler_.kind != 0 || sampler_.eta != 0.0 || prediction_ != 0);
     const int depth = !custom ? 0 : sampler_.kind == 1 ? 1 : sampler_.kind == 2 ? 3 : 0;
     std::vector<double> coefs;
     std::unique_ptr<Buf> hist[3];
     if (custom) {
         coefs.resize(ts.size() * 8);
-        const int st = sdmi_sampler_coefs(&sampler_, alphas_.data(), (int32_t)alphas_.size(), ts.data(), (int32_t)ts.size(), (int64_t)step_size, coefs.data());
+        const int st = sdmi_sampler_coefs_ex(&sampler_, alphas_.data(), (int32_t)alphas_.size(), ts.data(), (int32_t)ts.size(), (int64_t)step_size, prediction_, coefs.data());
         if (st != SDMI_OK) throw Error(st, "sample_loop: sdmi_sampler_coefs refused the schedule");
         for (int k = 0; k < depth; ++k) hist[k].reset(new Buf(this, per_half * 4));
     }
@@ -4378,6 +4414,19 @@ double Engine::bench_conv(int n, int cin, int h, int w, int cout, int k, int str
     }
     release(a); release(y);
     return (double)ms / std::max(1, iters);
+}
+
+// sdmi_attention_plan: the AttnPlanIn of qkv_attention_dev (dense rows, bf16 storage on a bf16 context unless masked, plane output under gemm_planes), planned
+// under the current options.  No device call.
+AttnPlan Engine::attention_plan(int n, int n_head, int nq, int nk, int d_head, bool has_mask) const {
+    if (n <= 0 || nq <= 0 || nk <= 0 || n_head <= 0 || d_head <= 0) throw Error(SDMI_ERR_INVALID, "attention_plan: bad shape");
+    const int n_state = n_head * d_head;
+    AttnPlanIn in{};
+    in.n = n; in.n_head = n_head; in.nq = nq; in.nk = nk; in.d_head = d_head; in.has_mask = has_mask;
+    in.bf16 = (bf16_ && !has_mask) ? 1 : 0;
+    in.planes_out = !in.bf16 && plane_gemm(n_state, n_state) && attn_supported_head_dim(d_head);
+    in.rows_aligned = !(n_state & (in.bf16 ? 7 : 3));
+    return plan_attention(in, aopt_);
 }
 
 double Engine::bench_attention(int n, int nq, int nk, int n_state, int n_head, int iters) {

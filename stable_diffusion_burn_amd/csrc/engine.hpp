@@ -325,6 +325,8 @@ public:
                       int iters);
 
     double bench_attention(int n, int nq, int nk, int n_state, int n_head, int iters);
+    void set_prediction(int kind);   // 0 eps, 1 v
+    AttnPlan attention_plan(int n, int n_head, int nq, int nk, int d_head, bool has_mask) const;   // what qkv_attention_dev would run now; host only
     void set_option(const std::string& key, const std::string& value);
     void sync();
     // Every C-ABI entry point runs inside a Call: the constructor orders the engine's stream behind the caller's work
@@ -520,7 +522,10 @@ private:
     // ONE rule for "the query arrives multiplied by attn_bf16_q_scale(d_head)": bf16 storage at the head dims the fused bf16 kernel serves.  The weight loader
     // folds the factor into the query projection by it, the fp32 -> bf16 conversions of the operator entry points apply it by it, and every attention() call
     // passes it as q_log2 -- the kernel launcher refuses a bf16 call that does not state it.
-    static bool q_prescaled(int dt, int d_head) { return dt != 0 && attn_bf16_head_dim(d_head); }
+    // d_head = 64 follows option attn_d64 (0: as before k_attn_bf16.hip had a d = 64 instance -- plain q on k_attn.hip).
+    bool q_prescaled(int dt, int d_head) const { return dt != 0 && attn_bf16_head_dim(d_head, aopt_.attn_d64); }
+    // heads of a UNet attention at channel width c: n_head of them (SD v1), or c / 64 of width 64 (variant = 1, SD 2.x)
+    int unet_heads(int c) const { return cfg_.variant == 1 ? c / 64 : cfg_.n_head; }
 
     // composite blocks
     void res_block(const ResW& w, const Act& x, Act& y, int step);
@@ -564,6 +569,7 @@ private:
     // kplan (a k-sampler is set): the rows of ksampler_plan for the call -- the loop walks its evaluations instead of ts, which is unused then.
     // kplan_for: the plan of a call of n_steps at `strength`, *a0 = 1 / (1 + sigma_start^2), the alpha of the img2img start.
     std::vector<double> kplan_for(size_t n_steps, double strength, double* a0) const;
+    int prediction_ = 0;   // sdmi_set_prediction: 0 = the UNet predicts eps, 1 = v (the coefficient tables are rewritten)
     // cond_nhwc (a conditioned model): [n][hw][padded_in_ch - 4]; every unet_run is preceded by assemble_unet_in into a buffer of the call
     float* cond_to_nhwc(const float* cond_nchw, int n);
     void assemble_unet_in(const float* unet_in, const float* cond_nhwc, int rows, int n, float* dst);
@@ -633,6 +639,7 @@ private:
                                      // measured at batch 1: GroupNorm class 21.3 -> 17.3 ms per image (profiles/r05d, r05f, r05o, r05p)
     GnTune gn_tune_;                 // launch geometry of the bf16 / MXFP8 GroupNorm passes (kernels.hpp; options gn_target_wgs, gn_max_threads, gn_unroll)
     int opt_b3_grouped_ = 1;         // precision 0: weight planes in 16-row fragment groups (1 KiB DMA pieces, sequential per group); 0 = row-major planes.  Before the weights are loaded.
+    std::vector<int> q64_entries_;   // bf16 query weights of 64-wide UNet heads: their pre_scale follows option attn_d64
     AttnPlanOpts aopt_;              // options attn_split, attn_bf16, attn_bf16_variant, attn_pack_tail, attn_kv_splits, attn_kv_prefer8 (attn_plan.hpp)
     int opt_cfg_share_ = 1;          // sample_latent: the part of the UNet in front of the first cross attention is computed once for the two identical halves of a CFG step (unet_run)
     int opt_skip_slices_ = 1;        // fp32 ResBlocks with a 1x1 shortcut: 1 = the shortcut runs on extra K slices of conv_out's split-K launch (conv_pair); 0 = its own launches

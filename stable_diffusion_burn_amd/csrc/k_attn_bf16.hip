@@ -1,5 +1,5 @@
 // Flash-style attention on the bf16 matrix cores (precision = 1): qkv_attention of the UNet's
-// self/cross attention (attention.rs:5-45, head dims 40 / 80 / 160) with bf16 q/k/v/o in HBM,
+// self/cross attention (attention.rs:5-45, head dims 40 / 80 / 160, and 64 for SD 2.x) with bf16 q/k/v/o in HBM,
 // fp32 scores, fp32 online softmax and fp32 accumulation.
 //
 // One wave owns 32 query rows and all of the head's d columns; a workgroup of NW waves shares
@@ -426,6 +426,7 @@ hipError_t launch_attention_bf16(const AttnParams& p, const AttnPlan& plan, hipS
     if ((p.ldq | p.ldk | p.ldv | p.ldo) & 7) return hipErrorInvalidValue;  // 16-byte row alignment
     switch (p.d_head) {
         case 40: return launch_attn_bf16_any<40>(p, plan, stream);
+        case 64: return launch_attn_bf16_any<64>(p, plan, stream);   // SD 2.x (option attn_d64): no spare row of O^T, the row sum is lane-local as at d = 160
         case 80: return launch_attn_bf16_any<80>(p, plan, stream);
         case 160: return launch_attn_bf16_any<160>(p, plan, stream);
     }

@@ -1,4 +1,4 @@
-// k_attn_split.hip -- fp32 qkv_attention (attention.rs:5-45) on the bf16 matrix pipe, precision = 0, head dims 40 / 80.
+// k_attn_split.hip -- fp32 qkv_attention (attention.rs:5-45) on the bf16 matrix pipe, precision = 0, head dims 40 / 80, and 64 (SD 2.x) behind option attn_d64.
 //
 // The same idea as k_gemm3x.hip: an fp32 number is exactly the sum of three bf16 numbers (x = h + m + l, round-to-nearest
 // splits), a bf16 x bf16 product is exact in fp32, and the MFMA accumulates in fp32 -- so S = Q K^T and O = P V are computed
@@ -115,6 +115,10 @@ __global__ __launch_bounds__(NW * 64) void attn_split_kernel(const AttnParams p)
     // m is raised only when a tile exceeds it by 2^8 (a wave-uniform slow path rescales O, m and the scores -- the three bf16 planes carry 24 bits of a probability
     // whatever its magnitude); the row sum is a COLUMN OF ONES appended to V's high plane, accumulated by the P V instructions in a spare row of the last O^T tile.
     constexpr int SUM_R = PACK ? 12 : 4 * ((D % 32) / 8);   // ... that row: register SUM_R of the lanes with hi = 0 (packed tile: row 24; otherwise row D % 32)
+    // d = 64: both O^T tiles are full, there is no spare row, and a third tile for one row would cost six more matrix instructions per 32 keys.  As in k_attn_bf16.hip at
+    // d = 160 (its SUMCOL), the row sum is then taken lane-locally from the fp32 probabilities -- S^T keeps a query's scores in one lane, one add each -- and follows
+    // the deferred rescale; the log2-unit scores and the maximum as accumulator input stay.
+    constexpr bool SUMCOL = LG && (PACK || NDT * 32 > D);
     constexpr float kDefer = 8.0f;
     static_assert(!PK || D == 40, "the packed tail is the d = 40 form");
 
@@ -150,7 +154,7 @@ __global__ __launch_bounds__(NW * 64) void attn_split_kernel(const AttnParams p)
     if constexpr (PACK) {         // V plane 0, columns 56..63 (rows 24..31 of the packed tail tile) = (1, 0, .., 0) in both buffers, once: row 24 sums the probabilities (LG)
         for (int i = tid; i < 2 * BKV; i += NT)
             *reinterpret_cast<u32x4*>(Vs + (i / BKV) * 3 * Cfg::V_BYTES + (i % BKV) * RSV + 7 * 16) = u32x4{LG ? 0x3F80u : 0u, 0u, 0u, 0u};
-    } else if constexpr (LG) {    // V[key][D] = 1 in the high plane, 0 in the other two, both buffers, once (the staging never touches that chunk)
+    } else if constexpr (SUMCOL) {    // V[key][D] = 1 in the high plane, 0 in the other two, both buffers, once (the staging never touches that chunk)
         for (int i = tid; i < 6 * BKV; i += NT)
             *reinterpret_cast<u32x4*>(Vs + (i / BKV) * Cfg::V_BYTES + (i % BKV) * RSV + CPR * 16) = u32x4{(i / BKV) % 3 == 0 ? 0x3F80u : 0u, 0u, 0u, 0u};
     }
@@ -350,7 +354,7 @@ __global__ __launch_bounds__(NW * 64) void attn_split_kernel(const AttnParams p)
             for (int r = 0; r < 16; r += 2) {
                 const float e0 = __builtin_amdgcn_exp2f(LG ? s[kt][r] : __builtin_fmaf(s[kt][r], cs, -mc));
                 const float e1 = __builtin_amdgcn_exp2f(LG ? s[kt][r + 1] : __builtin_fmaf(s[kt][r + 1], cs, -mc));
-                if constexpr (!LG) psum += e0 + e1;
+                if constexpr (!SUMCOL) psum += e0 + e1;
                 sp_split2(e0, e1, pa[r >> 3][(r & 7) >> 1], pb[r >> 3][(r & 7) >> 1], pc[r >> 3][(r & 7) >> 1]);
             }
             u32x4 ph[2], pm[2], pl[2];
@@ -399,7 +403,7 @@ __global__ __launch_bounds__(NW * 64) void attn_split_kernel(const AttnParams p)
                 for (int dt = 0; dt < NDT; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_bf(vf[dt][0]), sp_bf(ph[h2]), o[dt], 0, 0, 0);
             }
         }
-        if constexpr (!LG) l_run = l_run * alpha + psum;
+        if constexpr (!SUMCOL) l_run = l_run * alpha + psum;   // (LG: alpha is 1 unless the reference maximum moved on this tile)
 
         if (more) lstore(cur ^ 1);
         __syncthreads();
@@ -410,7 +414,7 @@ __global__ __launch_bounds__(NW * 64) void attn_split_kernel(const AttnParams p)
         for (int r = 0; r < 4; ++r) o[NDT - 1][r] = (o[NDT - 1][r + 8] + o[NDT - 1][r + 4]) + o[NDT - 1][r];
     }
 
-    if constexpr (LG) l_run = hi ? 0.f : o[NDT - 1][SUM_R];    // the ones column's row of O^T: the whole row sum, in the lane with hi = 0
+    if constexpr (SUMCOL) l_run = hi ? 0.f : o[NDT - 1][SUM_R];    // the ones column's row of O^T: the whole row sum, in the lane with hi = 0
     const float m_log2 = LG ? (t_begin < t_end ? -(NEGM1 ? negm1 : negm[0]) : -INFINITY) : m_run * cs;
     if (n_split > 1) {   // a key slice: unnormalised rows + (maximum in log2 units, row sum) for launch_attention_combine
         const float l_tot = sp_partner_sum(l_run);
@@ -476,12 +480,13 @@ static hipError_t launch_attn_split_any(const AttnParams& p, const AttnPlan& pla
     else return w8 ? launch_attn_split_d<D, 8, false, false>(p, plan, stream) : launch_attn_split_d<D, 4, false, false>(p, plan, stream);
 }
 
-// fp32 q/k/v/o, no additive mask, d_head 40 or 80, 16-byte aligned rows
+// fp32 q/k/v/o, no additive mask, d_head 40, 64 or 80, 16-byte aligned rows
 hipError_t launch_attention_split(const AttnParams& p, const AttnPlan& plan, hipStream_t stream) {
     if (plan.kernel != AttnKernel::Split || plan.kv_splits != (p.kv_splits > 1 ? p.kv_splits : 1)) return hipErrorInvalidValue;
     if (p.bf16 || p.mask || ((p.ldq | p.ldk | p.ldv | p.ldo) & 3)) return hipErrorInvalidValue;
     if (p.kv_splits > 1 && (!p.part_o || !p.part_ml)) return hipErrorInvalidValue;
     if (p.d_head == 40) return launch_attn_split_any<40>(p, plan, stream);
+    if (p.d_head == 64) return launch_attn_split_any<64>(p, plan, stream);
     if (p.d_head == 80) return launch_attn_split_any<80>(p, plan, stream);
     return hipErrorInvalidValue;
 }

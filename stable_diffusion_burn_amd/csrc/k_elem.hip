@@ -121,6 +121,14 @@ __global__ void quick_gelu_kernel(float* __restrict__ x, long long n) {
     }
 }
 
+// the exact GELU, x * 0.5 (1 + erf(x / sqrt 2)): the MLP activation of SD 2.x's OpenCLIP text tower
+__global__ void gelu_erf_kernel(float* __restrict__ x, long long n) {
+    GRID_STRIDE(i, n) {
+        const float v = x[i];
+        x[i] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+    }
+}
+
 // CLIP::forward embedding (clip/mod.rs:62-67): out[b, t, :] = token_table[tokens[b, t], :] + position_table[t, :]
 __global__ void clip_embed_kernel(const int* __restrict__ tokens, const float* __restrict__ tok_table,
                                   const float* __restrict__ pos_table, float* __restrict__ out, int n, int T, int C) {
@@ -347,6 +355,10 @@ hipError_t launch_nchw3_to_nhwc4(const float* src, float* dst, int n, int h, int
 }
 hipError_t launch_quick_gelu(float* x, long long n, hipStream_t s) {
     hipLaunchKernelGGL(quick_gelu_kernel, dim3(blocks_for(n)), dim3(256), 0, s, x, n);
+    return hipGetLastError();
+}
+hipError_t launch_gelu_erf(float* x, long long n, hipStream_t s) {
+    hipLaunchKernelGGL(gelu_erf_kernel, dim3(blocks_for(n)), dim3(256), 0, s, x, n);
     return hipGetLastError();
 }
 hipError_t launch_clip_embed(const int* tokens, const float* tok_table, const float* pos_table, float* out, int n, int T, int C,

@@ -227,6 +227,7 @@ hipError_t launch_nhwc_to_nchw_slice(const float* src, float* dst, int n, int c_
 hipError_t launch_nchw3_to_nhwc4(const float* src, float* dst, int n, int h, int w, hipStream_t s);
 // CLIP text encoder pieces (clip/mod.rs): QuickGELU in place, token + position embedding, decoder mask
 hipError_t launch_quick_gelu(float* x, long long n, hipStream_t s);
+hipError_t launch_gelu_erf(float* x, long long n, hipStream_t s);   // x * Phi(x), the exact GELU of the OpenCLIP text tower (SD 2.x)
 hipError_t launch_clip_embed(const int* tokens, const float* tok_table, const float* pos_table, float* out, int n, int T, int C,
                              hipStream_t s);
 hipError_t launch_causal_mask(float* mask, int T, hipStream_t s);

@@ -177,7 +177,8 @@ std::vector<double> ksampler_sigmas(const sdmi_ksampler& k, const float* alphas,
     return sg;
 }
 
-std::vector<double> ksampler_plan(const sdmi_ksampler& k, const float* alphas, int total, size_t n_steps, double strength, int* call_steps) {
+std::vector<double> ksampler_plan(const sdmi_ksampler& k, const float* alphas, int total, size_t n_steps, double strength, int* call_steps, int prediction) {
+    if (prediction != 0 && prediction != 1) bad("ksampler_plan: prediction must be 0 (eps) or 1 (v)");
     std::vector<int> ts;
     const std::vector<double> sg = ksampler_sigmas(k, alphas, total, n_steps, &ts);
     if (!(strength > 0.0 && strength <= 1.0)) bad("ksampler_plan: strength must satisfy 0 < strength <= 1");
@@ -187,7 +188,11 @@ std::vector<double> ksampler_plan(const sdmi_ksampler& k, const float* alphas, i
     const Table tb(alphas, total);
     auto node = [&](size_t i) { return k.schedule == 0 && i < L ? node_of_table(alphas, ts[i]) : node_of(tb, sg[i]); };
     std::vector<double> rows;
-    auto push = [&](size_t step, int stage, const Node& at, const Row& r, double a_end) {
+    auto push = [&](size_t step, int stage, const Node& at, Row r, double a_end) {
+        if (prediction == 1) {   // eps = a v + b x at the evaluation (ksampler.hpp)
+            const double a = 1.0 / std::sqrt(1.0 + at.s * at.s), b = at.s / std::sqrt(1.0 + at.s * at.s);
+            r.cx += r.ce * b; r.ce *= a; r.qx += r.qe * b; r.qe *= a;
+        }
         const double v[KPLAN_COLS] = {(double)step, (double)stage, at.t, at.s, r.cx, r.ce, r.h1, r.cz, r.cz2, r.qx, r.qe, a_end};
         rows.insert(rows.end(), v, v + KPLAN_COLS);
     };

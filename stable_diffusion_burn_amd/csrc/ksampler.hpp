@@ -18,6 +18,9 @@ double sigma_to_t(const float* alphas, int total, double sigma);
 // steps + 1 sigmas, the last 0; ts (may be null) receives the integer timesteps of schedule 0 (empty for the others)
 std::vector<double> ksampler_sigmas(const sdmi_ksampler& k, const float* alphas, int total, size_t n_steps, std::vector<int>* ts = nullptr);
 // KPLAN_COLS doubles per UNet evaluation of the call; *call_steps = the steps the call runs
-std::vector<double> ksampler_plan(const sdmi_ksampler& k, const float* alphas, int total, size_t n_steps, double strength, int* call_steps = nullptr);
+// prediction (sdmi_set_prediction): 0 = the model output is eps, the rows are what they always were; 1 = it is v = sqrt(a) eps - sqrt(1 - a) x0.  With
+// a = 1 / sqrt(1 + sigma^2), b = sigma / sqrt(1 + sigma^2) at the evaluation, eps = a v + b x, and every row is linear in x and in the model output: the row for v
+// is cx += ce b, ce *= a, qx += qe b, qe *= a -- the history q keeps holding what it held (x0, eps or the start latent).
+std::vector<double> ksampler_plan(const sdmi_ksampler& k, const float* alphas, int total, size_t n_steps, double strength, int* call_steps = nullptr, int prediction = 0);
 
 }  // namespace sdmi

@@ -131,7 +131,7 @@ std::vector<PromptFragment> parse_prompt(const std::string& s) {
 }
 
 PromptChunks prompt_chunks(const Tokenizer& tok, const std::string& text, int clip_ctx, bool emphasis, int min_chunks,
-                           const std::vector<PromptEmbedding>& embeddings) {
+                           const std::vector<PromptEmbedding>& embeddings, int pad_id) {
     if (clip_ctx < 3) throw Error(SDMI_ERR_INVALID, "prompt_chunks: clip_ctx must be at least 3");
     if (min_chunks < 0) throw Error(SDMI_ERR_INVALID, "prompt_chunks: min_chunks must not be negative");
     const int L = clip_ctx - 2;
@@ -156,7 +156,7 @@ PromptChunks prompt_chunks(const Tokenizer& tok, const std::string& text, int cl
         out.ids.push_back(sot); out.weights.push_back(1.0f); out.emb_row.push_back(-1);
         for (int p = 0; p < L + 1; ++p) {
             const bool content = p < (int)c_ids.size();
-            out.ids.push_back(content ? c_ids[p] : eot);
+            out.ids.push_back(content ? c_ids[p] : (pad_id < 0 || p == (int)c_ids.size()) ? eot : pad_id);
             out.weights.push_back(content ? c_w[p] : 1.0f);
             out.emb_row.push_back(content ? c_rows[p] : -1);
         }

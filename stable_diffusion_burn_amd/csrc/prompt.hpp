@@ -38,7 +38,8 @@ struct PromptChunks {
 
 // embeddings: rows are numbered over the list in order (first_row(i) = sum of n_vectors before i).  SDMI_ERR_INVALID: clip_ctx < 3, min_chunks < 0,
 // an embedding with no ids, n_vectors < 1 or n_vectors > clip_ctx - 2.
+// pad_id: what fills a chunk BEHIND its first <|endoftext|>; < 0 = <|endoftext|> again (CLIP as SD v1 uses it), 0 = OpenCLIP's padding (SD 2.x)
 PromptChunks prompt_chunks(const Tokenizer& tok, const std::string& text, int clip_ctx, bool emphasis, int min_chunks,
-                           const std::vector<PromptEmbedding>& embeddings);
+                           const std::vector<PromptEmbedding>& embeddings, int pad_id = -1);
 
 }  // namespace sdmi

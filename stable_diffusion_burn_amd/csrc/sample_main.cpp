@@ -22,6 +22,8 @@
 //   * SDMI_KSAMPLER=kind:schedule[:eta] (no reference counterpart; unset: the reference's DDIM) selects a sigma-schedule sampler (sdmi_set_ksampler) by name:
 //     kind euler | dpmpp_2m | heun | dpm2 | dpmpp_2s | dpmpp_sde | dpmpp_2m_sde, schedule model | karras | exponential | uniform, eta 0 .. 1 (default 0); its step
 //     noise is seeded by SDMI_SEED.
+//   * SDMI_PREDICTION=v | eps (no reference counterpart; unset: eps) says what the checkpoint's UNet predicts (sdmi_set_prediction): v for SD 2.x's 768-v models.  An
+//     SD 2.x checkpoint needs SDMI_CONFIG="variant=1,ctx_dim=1024,clip_layers=23,clip_heads=16" and, for OpenCLIP's padding, SDMI_PROMPT_STYLE=webui.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -58,6 +60,7 @@ static void apply_overrides(sdmi_config& cfg, const char* spec) {
         else if (k == "clip_heads") cfg.clip_heads = v;
         else if (k == "clip_vocab") cfg.clip_vocab = v;
         else if (k == "clip_ctx") cfg.clip_ctx = v;
+        else if (k == "variant") cfg.variant = v;
         else { std::fprintf(stderr, "SDMI_CONFIG: unknown key %s\n", k.c_str()); std::exit(1); }
     }
 }
@@ -163,6 +166,13 @@ int main(int argc, char** argv) {
         if (const char* sd = std::getenv("SDMI_SEED")) ksampler.noise_seed = std::strtoull(sd, nullptr, 10);
     }
 
+    // SDMI_PREDICTION: likewise refused before anything is loaded
+    int32_t prediction = 0;
+    if (const char* pr = std::getenv("SDMI_PREDICTION")) {
+        if (!std::strcmp(pr, "v")) prediction = 1;
+        else if (*pr && std::strcmp(pr, "eps")) { std::fprintf(stderr, "Error: SDMI_PREDICTION must be v or eps, got '%s'\n", pr); return 1; }
+    }
+
     std::printf("Loading tokenizer...\n");
     const char* vocab = std::getenv("SDMI_BPE_VOCAB");
     sdmi_tokenizer* tok = nullptr;
@@ -172,6 +182,7 @@ int main(int argc, char** argv) {
     sdmi_ctx* ctx = nullptr;
     if (sdmi_create(&ctx, &cfg) != SDMI_OK) die("Error creating device context");
     if (has_ksampler && sdmi_set_ksampler(ctx, &ksampler) != SDMI_OK) die("Error setting the k-sampler");   // sticky: set before the weights, refused at once
+    if (sdmi_set_prediction(ctx, prediction) != SDMI_OK) die("Error setting the prediction kind");
     const char* lora = std::getenv("SDMI_LORA");
     if (lora && *lora && sdmi_set_option(ctx, "keep_masters", "1") != SDMI_OK) die("Error setting keep_masters");
     if (model_type == "burn") {

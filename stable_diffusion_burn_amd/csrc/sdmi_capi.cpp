@@ -223,6 +223,28 @@ int sdmi_checkpoint_key(const char* dump_name, char* out, size_t capacity, size_
     });
 }
 
+int sdmi_checkpoint_key_ex(const char* dump_name, int32_t variant, char* out, size_t capacity, size_t* needed, int32_t* transposed, int32_t* slice) {
+    return guarded([&] {
+        if (!dump_name || !needed) throw Error(SDMI_ERR_INVALID, "checkpoint_key: null argument");
+        if (variant != 0 && variant != 1) throw Error(SDMI_ERR_INVALID, "checkpoint_key: variant must be 0 (SD v1) or 1 (SD 2.x)");
+        std::string key;
+        bool tr = false;
+        int sl = -1;
+        if (!sdmi::checkpoint_key(dump_name, variant, &key, &tr, &sl)) throw Error(SDMI_ERR_INVALID, std::string("checkpoint_key: '") + dump_name + "' has no checkpoint source");
+        if (transposed) *transposed = tr ? 1 : 0;
+        if (slice) *slice = sl;
+        text_out(key, out, capacity, needed, "checkpoint_key");
+    });
+}
+
+int sdmi_safetensors_model_family(const char* path, int32_t* family) {
+    return guarded([&] {
+        if (!path || !family) throw Error(SDMI_ERR_INVALID, "safetensors_model_family: null argument");
+        sdmi::SafetensorsFile f(path);
+        *family = f.find(sdmi::kFamilyKeySd2) ? 2 : f.find(sdmi::kFamilyKeySd1) ? 1 : 0;
+    });
+}
+
 int sdmi_default_alphas_cumprod(float* out, int32_t n) {
     return guarded([&] {
         if (!out || n < 1) throw Error(SDMI_ERR_INVALID, "default_alphas_cumprod: null output or n < 1");
@@ -501,7 +523,7 @@ int sdmi_encode_prompt(sdmi_ctx* ctx, const sdmi_tokenizer* tok, const char* tex
         std::vector<sdmi::PromptEmbedding> embs;
         for (const Engine::Embedding& em : e.embeddings()) embs.push_back({em.ids, em.n_vectors});
         const int cc = e.config().clip_ctx;
-        const sdmi::PromptChunks c = sdmi::prompt_chunks(tok->tok, text, cc, o.emphasis != 0, o.min_chunks, embs);
+        const sdmi::PromptChunks c = sdmi::prompt_chunks(tok->tok, text, cc, o.emphasis != 0, o.min_chunks, embs, e.config().variant == 1 ? 0 : -1);
         if ((int64_t)c.k * cc > INT32_MAX) throw Error(SDMI_ERR_INVALID, "encode_prompt: too many chunks");
         *T = c.k * cc;
         if (*T > capacity_tokens) throw Error(SDMI_ERR_INVALID, "encode_prompt: capacity_tokens too small");
@@ -679,9 +701,14 @@ int sdmi_sigma_to_t(const float* alphas_cumprod, int32_t total, double sigma, do
 
 int sdmi_ksampler_plan(const sdmi_ksampler* ksampler, const float* alphas_cumprod, int32_t total, size_t n_steps, double strength, double* rows, int32_t capacity,
                        int32_t* count) {
+    return sdmi_ksampler_plan_ex(ksampler, alphas_cumprod, total, n_steps, strength, 0, rows, capacity, count);
+}
+
+int sdmi_ksampler_plan_ex(const sdmi_ksampler* ksampler, const float* alphas_cumprod, int32_t total, size_t n_steps, double strength, int32_t prediction, double* rows,
+                          int32_t capacity, int32_t* count) {
     return guarded([&] {
         if (!ksampler || !count) throw Error(SDMI_ERR_INVALID, "ksampler_plan: null pointer");
-        const std::vector<double> plan = sdmi::ksampler_plan(*ksampler, alphas_cumprod, total, n_steps, strength);
+        const std::vector<double> plan = sdmi::ksampler_plan(*ksampler, alphas_cumprod, total, n_steps, strength, nullptr, prediction);
         const size_t n = plan.size() / sdmi::KPLAN_COLS;
         *count = (int32_t)n;
         if (!rows || capacity < (int32_t)n) throw Error(SDMI_ERR_INVALID, "ksampler_plan: capacity too small");
@@ -1033,7 +1060,14 @@ int sdmi_lora_effective_weight(sdmi_ctx* ctx, const char* name, float* out, size
 // sn = sqrt(1 - cur), sp = sqrt(prev):  x0 = x / sc - (sn / sc) e.
 int sdmi_sampler_coefs(const sdmi_sampler* sampler, const float* alphas_cumprod, int32_t total, const int32_t* ts, int32_t count,
                        int64_t step_size, double* coefs) {
+    return sdmi_sampler_coefs_ex(sampler, alphas_cumprod, total, ts, count, step_size, 0, coefs);
+}
+
+// prediction = 1 (v): eps = sc v + sn x at the step's timestep, and the update is linear in x and in the model output -- the table is rewritten, nothing else changes
+int sdmi_sampler_coefs_ex(const sdmi_sampler* sampler, const float* alphas_cumprod, int32_t total, const int32_t* ts, int32_t count,
+                          int64_t step_size, int32_t prediction, double* coefs) {
     return guarded([&] {
+        if (prediction != 0 && prediction != 1) throw Error(SDMI_ERR_INVALID, "sampler_coefs: prediction must be 0 (eps) or 1 (v)");
         if (!sampler || !alphas_cumprod || !ts || !coefs) throw Error(SDMI_ERR_INVALID, "sampler_coefs: null pointer");
         Engine::check_sampler(*sampler);
         if (total <= 0 || count <= 0 || step_size < 1) throw Error(SDMI_ERR_INVALID, "sampler_coefs: total, count and step_size must be positive");
@@ -1080,8 +1114,13 @@ int sdmi_sampler_coefs(const sdmi_sampler* sampler, const float* alphas_cumprod,
                 k[1] = ce * w[0]; k[2] = ce * w[1]; k[3] = ce * w[2]; k[4] = ce * w[3];
                 k[7] = 1.0;                                     // q = e
             }
+            if (prediction == 1) { k[0] += k[1] * sn; k[1] *= sc; k[6] += k[7] * sn; k[7] *= sc; }
         }
     });
+}
+
+int sdmi_set_prediction(sdmi_ctx* ctx, int32_t kind) {
+    return guarded([&] { eng(ctx).set_prediction(kind); });
 }
 
 int sdmi_img2img_latent(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale,
@@ -1713,6 +1752,16 @@ int sdmi_bench_attention(sdmi_ctx* ctx, int32_t n, int32_t nq, int32_t nk, int32
     return guarded([&] {
         if (!ms_out) throw Error(SDMI_ERR_INVALID, "bench_attention: null output");
         *ms_out = eng(ctx).bench_attention(n, nq, nk, n_state, n_head, iters);
+    });
+}
+
+int sdmi_attention_plan(sdmi_ctx* ctx, int32_t n, int32_t n_head, int32_t nq, int32_t nk, int32_t d_head, int32_t has_mask, sdmi_attn_plan* out) {
+    return guarded([&] {
+        if (!out) throw Error(SDMI_ERR_INVALID, "attention_plan: null output");
+        const sdmi::AttnPlan a = eng(ctx).attention_plan(n, n_head, nq, nk, d_head, has_mask != 0);
+        *out = sdmi_attn_plan{};
+        out->kernel = a.kernel == sdmi::AttnKernel::Unfused ? 0 : a.kernel == sdmi::AttnKernel::Flash ? 1 : a.kernel == sdmi::AttnKernel::Split ? 2 : 3;
+        out->waves = a.waves; out->q_rows = a.q_rows; out->kv_tile = a.kv_tile; out->kv_splits = a.kv_splits;
     });
 }
 

@@ -24,7 +24,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _capi
-from ._capi import SdmiConfig, SdmiControl, SdmiError, SdmiHires, SdmiInpaint, SdmiKSampler, SdmiOpView, SdmiPromptOpts, SdmiSampler, check, load_library
+from ._capi import SdmiAttnPlan, SdmiConfig, SdmiControl, SdmiError, SdmiHires, SdmiInpaint, SdmiKSampler, SdmiOpView, SdmiPromptOpts, SdmiSampler, check, load_library
 
 def mpk_list(path) -> list:
     """[(dump name, shape, file offset)] of a Burn .mpk record, parsed by the C++ reader (host only, no GPU)."""
@@ -78,14 +78,27 @@ def parse_prompt(text: str) -> list:
     return out
 
 
-def checkpoint_key(name: str) -> tuple:
-    """(CompVis checkpoint key, transposed?) of a dump-tree tensor name (sdmi_checkpoint_key, host only, no GPU); SdmiError for a name without one."""
+def checkpoint_key(name: str, variant: int = 0, with_slice: bool = False) -> tuple:
+    """(checkpoint key, transposed?) of a dump-tree tensor name (sdmi_checkpoint_key_ex, host only, no GPU); SdmiError for a name without one.
+    variant: ModelConfig.variant -- 0 the CompVis SD v1 layout, 1 Stability's SD 2.x layout (OpenCLIP text encoder under cond_stage_model.model.).
+    with_slice: a third element -- None = the key's whole tensor, 0 / 1 / 2 = the first / second / third third of its rows (the query / key / value parts of
+    SD 2.x's fused attn.in_proj_weight / in_proj_bias)."""
     lib = load_library()
-    need, tr = C.c_size_t(), C.c_int32()
-    check(lib.sdmi_checkpoint_key(name.encode(), None, 0, C.byref(need), C.byref(tr)))
+    need, tr, sl = C.c_size_t(), C.c_int32(), C.c_int32()
+    check(lib.sdmi_checkpoint_key_ex(name.encode(), int(variant), None, 0, C.byref(need), C.byref(tr), C.byref(sl)))
     buf = C.create_string_buffer(need.value)
-    check(lib.sdmi_checkpoint_key(name.encode(), buf, need.value, C.byref(need), C.byref(tr)))
+    check(lib.sdmi_checkpoint_key_ex(name.encode(), int(variant), buf, need.value, C.byref(need), C.byref(tr), C.byref(sl)))
+    if with_slice:
+        return buf.value.decode(), bool(tr.value), None if sl.value < 0 else int(sl.value)
     return buf.value.decode(), bool(tr.value)
+
+
+def safetensors_model_family(path):
+    """"sd1" | "sd2" | None: the checkpoint family of a .safetensors file (sdmi_safetensors_model_family, host only) -- decided by which text encoder's final
+    LayerNorm it holds: cond_stage_model.transformer.text_model.final_layer_norm.weight (SD v1) or cond_stage_model.model.ln_final.weight (SD 2.x)."""
+    fam = C.c_int32()
+    check(load_library().sdmi_safetensors_model_family(str(path).encode(), C.byref(fam)))
+    return {1: "sd1", 2: "sd2"}.get(fam.value)
 
 
 def control_step_on(start: float, end: float, step: int, n_steps: int) -> bool:
@@ -145,16 +158,26 @@ def _sampler_struct(kind, eta=0.0, noise_seed=0, image_base=0) -> SdmiSampler:
     return s
 
 
-def sampler_coefs(kind: str, eta: float, alphas_cumprod, ts, step_size: int) -> np.ndarray:
+PREDICTIONS = ("eps", "v")   # sdmi_set_prediction's kind 0, 1
+
+
+def _prediction(p) -> int:
+    if p not in PREDICTIONS:
+        raise ValueError(f"prediction must be one of {PREDICTIONS}, got {p!r}")
+    return PREDICTIONS.index(p)
+
+
+def sampler_coefs(kind: str, eta: float, alphas_cumprod, ts, step_size: int, prediction: str = "eps") -> np.ndarray:
     """The per-step coefficients [len(ts), 8] = (cx, ce, h1, h2, h3, cz, qx, qe) of a sampler over the timesteps `ts` a call runs
-    (sdmi_sampler_coefs, host only, no GPU; float64):  q = qx x + qe e,  x' = cx x + ce e + h1 q_-1 + h2 q_-2 + h3 q_-3 + cz z."""
+    (sdmi_sampler_coefs_ex, host only, no GPU; float64):  q = qx x + qe e,  x' = cx x + ce e + h1 q_-1 + h2 q_-2 + h3 q_-3 + cz z.
+    prediction "v": e is the model's v output, the table is the eps table rewritten."""
     lib = load_library()
     s = _sampler_struct(kind, eta)
     a = np.ascontiguousarray(alphas_cumprod, dtype=np.float32)
     t = np.ascontiguousarray(ts, dtype=np.int32)
     out = np.empty((t.size, 8), dtype=np.float64)
-    check(lib.sdmi_sampler_coefs(C.byref(s), _fp(a), a.size, t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, int(step_size),
-                                 out.ctypes.data_as(C.POINTER(C.c_double))))
+    check(lib.sdmi_sampler_coefs_ex(C.byref(s), _fp(a), a.size, t.ctypes.data_as(C.POINTER(C.c_int32)), t.size, int(step_size), _prediction(prediction),
+                                    out.ctypes.data_as(C.POINTER(C.c_double))))
     return out
 
 
@@ -196,15 +219,16 @@ def sigma_to_t(alphas_cumprod, sigma: float) -> float:
     return t.value
 
 
-def ksampler_plan(kind: str, alphas_cumprod, n_steps: int, schedule: str = "karras", strength: float = 1.0, **kw) -> np.ndarray:
-    """The evaluation plan [evaluations, 12] (KSAMPLER_PLAN_COLUMNS, float64) of a call of n_steps at `strength` (sdmi_ksampler_plan; host only):
-    one row per UNet evaluation,  q = qx x + qe e,  x' = cx x + ce e + h1 q_-1 + cz z + cz2 z2  on the VP latent."""
+def ksampler_plan(kind: str, alphas_cumprod, n_steps: int, schedule: str = "karras", strength: float = 1.0, prediction: str = "eps", **kw) -> np.ndarray:
+    """The evaluation plan [evaluations, 12] (KSAMPLER_PLAN_COLUMNS, float64) of a call of n_steps at `strength` (sdmi_ksampler_plan_ex; host only):
+    one row per UNet evaluation,  q = qx x + qe e,  x' = cx x + ce e + h1 q_-1 + cz z + cz2 z2  on the VP latent.  prediction "v": e is the model's v output."""
     lib = load_library()
     k = _ksampler_struct(kind, schedule, **kw)
     a = np.ascontiguousarray(alphas_cumprod, dtype=np.float32)
     out = np.empty((2 * (a.size + 1), 12), dtype=np.float64)
     count = C.c_int32()
-    check(lib.sdmi_ksampler_plan(C.byref(k), _fp(a), a.size, int(n_steps), float(strength), out.ctypes.data_as(C.POINTER(C.c_double)), out.shape[0], C.byref(count)))
+    check(lib.sdmi_ksampler_plan_ex(C.byref(k), _fp(a), a.size, int(n_steps), float(strength), _prediction(prediction), out.ctypes.data_as(C.POINTER(C.c_double)),
+                                    out.shape[0], C.byref(count)))
     return out[:count.value].copy()
 
 
@@ -437,7 +461,7 @@ class MultiLoraAdapter:
             self._owner = None
 
 
-__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "safetensors_list", "checkpoint_key", "default_alphas_cumprod", "control_step_on", "control_residual_shapes", "img2img_timesteps", "sampler_coefs", "ksampler_sigmas", "sigma_to_t", "ksampler_plan", "KSAMPLER_KINDS", "KSAMPLER_SCHEDULES", "KSAMPLER_PLAN_COLUMNS", "resize_weights", "load_lora_npz", "save_lora_npz", "lora_module_name", "lora_check_safetensors", "LoraAdapter", "LoraFileAdapter", "LORA_UNET", "LORA_TE", "LORA_SKIP_UNKNOWN", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
+__all__ = ["ModelConfig", "StableDiffusion", "MultiStableDiffusion", "mpk_list", "safetensors_list", "safetensors_model_family", "checkpoint_key", "default_alphas_cumprod", "control_step_on", "control_residual_shapes", "img2img_timesteps", "sampler_coefs", "ksampler_sigmas", "sigma_to_t", "ksampler_plan", "KSAMPLER_KINDS", "KSAMPLER_SCHEDULES", "KSAMPLER_PLAN_COLUMNS", "resize_weights", "load_lora_npz", "save_lora_npz", "lora_module_name", "lora_check_safetensors", "LoraAdapter", "LoraFileAdapter", "LORA_UNET", "LORA_TE", "LORA_SKIP_UNKNOWN", "UNet", "Autoencoder", "CLIP", "SimpleTokenizer", "qkv_attention", "SdmiError"]
 
 
 @dataclass(frozen=True)
@@ -461,11 +485,19 @@ class ModelConfig:
     unet_in_ch: int = 4
     # channels of a ControlNet's hint picture: 0 = no ControlNet, 3 = an RGB hint (the model gets the weight group controlnet/...)
     control_hint_ch: int = 0
+    # 0 = SD v1; 1 = SD 2.x: model_channels-level width / 64 UNet heads of width 64 (n_head is ignored), exact GELU in the text encoder, encode_prompt pads with token 0
+    variant: int = 0
 
     @classmethod
     def sd_v1_4(cls, precision: int = 0, clip: bool = True) -> "ModelConfig":
         """The reference's full StableDiffusionConfig::init (stablediffusion/mod.rs:22-39), text encoder included."""
         return cls(precision=precision, clip_layers=12 if clip else 0)
+
+    @classmethod
+    def sd_v2(cls, precision: int = 0, clip: bool = True) -> "ModelConfig":
+        """SD 2.x (512-base, 768-v, 2.1): sd_v1_4 with 64-wide UNet heads and the OpenCLIP ViT-H text tower -- width 1024, 16 heads, 23 blocks + the final
+        LayerNorm (its "penultimate" output, so clip_skip = 1 is SD 2's standard conditioning)."""
+        return cls(precision=precision, ctx_dim=1024, clip_layers=23 if clip else 0, clip_heads=16, variant=1)
 
 
 def _f32(a, shape=None, name="array") -> np.ndarray:
@@ -508,6 +540,7 @@ class StableDiffusion:
         cfg.clip_ctx = config.clip_ctx
         cfg.unet_in_ch = config.unet_in_ch
         cfg.control_hint_ch = config.control_hint_ch
+        cfg.variant = config.variant
         self._ctx = C.c_void_p()
         check(self._lib.sdmi_create(C.byref(self._ctx), C.byref(cfg)))
         # every option this context was given, in order (bench.py prints the non-default ones next to its figures: `applied_options`)
@@ -609,7 +642,8 @@ class StableDiffusion:
         check(self._lib.sdmi_finalize_weights(self._ctx))
 
     def load_weights_safetensors(self, path) -> None:
-        """An SD v1.x checkpoint in the CompVis layout, one .safetensors file (F32 / F16 / BF16), converted on the device + finalize."""
+        """An SD v1.x checkpoint in the CompVis layout -- on a variant = 1 context an SD 2.x checkpoint in Stability's layout --, one
+        .safetensors file (F32 / F16 / BF16), converted on the device + finalize.  A file of the other family is refused (safetensors_model_family)."""
         check(self._lib.sdmi_load_weights_safetensors(self._ctx, str(path).encode()))
         check(self._lib.sdmi_finalize_weights(self._ctx))
 
@@ -1169,6 +1203,20 @@ class StableDiffusion:
                                         C.byref(ms)))
         return ms.value
 
+    def set_prediction(self, kind: str = "eps") -> None:
+        """What the loaded UNet predicts: "eps" (the default; SD v1, SD 2.x 512-base) or "v" (SD 2.x 768-v, 2.1-768).  Sticky; applies to every sampling entry
+        point and sampler (sdmi_set_prediction).  The checkpoint does not say which: the caller chooses."""
+        check(self._lib.sdmi_set_prediction(self._ctx, _prediction(kind)))
+
+    ATTN_KERNELS = ("unfused", "flash", "split", "bf16")   # sdmi_attn_plan.kernel: GEMM path, k_attn.hip, k_attn_split.hip, k_attn_bf16.hip
+
+    def attention_plan(self, n, n_head, nq, nk, d_head, has_mask=False) -> dict:
+        """What this context would run for qkv_attention of the shape under its current options (sdmi_attention_plan; host only, no launch):
+        {"kernel": one of ATTN_KERNELS, "waves", "q_rows", "kv_tile", "kv_splits"}."""
+        p = SdmiAttnPlan()
+        check(self._lib.sdmi_attention_plan(self._ctx, int(n), int(n_head), int(nq), int(nk), int(d_head), int(bool(has_mask)), C.byref(p)))
+        return {"kernel": self.ATTN_KERNELS[p.kernel], "waves": int(p.waves), "q_rows": int(p.q_rows), "kv_tile": int(p.kv_tile), "kv_splits": int(p.kv_splits)}
+
     def bench_attention(self, n, nq, nk, n_state, n_head, iters=10) -> float:
         ms = C.c_double()
         check(self._lib.sdmi_bench_attention(self._ctx, n, nq, nk, n_state, n_head, iters, C.byref(ms)))
@@ -1519,7 +1567,7 @@ def _make_cfg(lib, config: ModelConfig, device: int = 0) -> SdmiConfig:
     check(lib.sdmi_default_config(C.byref(cfg)))
     cfg.device = device
     for f in ("model_channels", "n_head", "ctx_dim", "latent_h", "latent_w", "vae_ch", "precision", "clip_layers", "clip_heads",
-              "clip_vocab", "clip_ctx", "unet_in_ch", "control_hint_ch"):
+              "clip_vocab", "clip_ctx", "unet_in_ch", "control_hint_ch", "variant"):
         setattr(cfg, f, getattr(config, f))
     return cfg
 
@@ -1596,6 +1644,11 @@ class MultiStableDiffusion:
             return
         s = _sampler_struct(kind, eta, noise_seed, 0)
         check(self._lib.sdmi_multi_set_sampler(self._m, C.byref(s)))
+
+    def set_prediction(self, kind: str = "eps") -> None:
+        """StableDiffusion.set_prediction on every device."""
+        for i in range(len(self.devices)):
+            self.device_view(i).set_prediction(kind)
 
     def set_ksampler(self, kind="dpmpp_2m", schedule="karras", eta: float = 0.0, rho: float = 7.0, sigma_min=None, sigma_max=None, noise_seed: int = 0) -> None:
         """StableDiffusion.set_ksampler on every device (sdmi_multi_set_ksampler); image_base per shard, as set_sampler."""

@@ -202,28 +202,44 @@ def write_safetensors(path, tensors: dict, metadata: dict | None = None) -> None
                 f.write(arr.view(np.uint8).data)
 
 
-def write_checkpoint_safetensors(path, specs, get_tensor, alphas_cumprod, dtype: str = "F32", key_of=None, extra: dict | None = None) -> None:
+def write_checkpoint_safetensors(path, specs, get_tensor, alphas_cumprod, dtype: str = "F32", key_of=None, extra: dict | None = None, variant: int = 0) -> None:
     """Write a model in the CHECKPOINT's naming and layouts: the inverse of the loader's key map and the twin of write_dump_tree.
 
     specs: [(dump name, shape)] from StableDiffusion.weight_specs(); get_tensor(name, shape) -> ndarray in the dump's own layout (Linear
     [in,out], Conv [Cout,Cin,kh,kw]): a Linear weight is stored transposed back to torch's [out,in].  dtype "F32" | "F16" | "BF16" for the
     model's tensors; alphas_cumprod stays F32 (None: the file gets none).  key_of(dump name) -> (checkpoint key, transposed?), default
     pipeline.checkpoint_key (the C++ rules).  extra: further {key: tensor} entries, written as write_safetensors takes them.
+    variant (ModelConfig.variant of the context the specs come from) 1: Stability's SD 2.x layout -- the text encoder's query / key / value weights and biases
+    fused into attn.in_proj_weight [3C, C] / in_proj_bias [3C] (all three must be among the specs), the transformers' proj_in / proj_out written 2-D [C, C].
     """
     if dtype not in ("F32", "F16", "BF16"):
         raise ValueError(f"write_checkpoint_safetensors: dtype must be F32, F16 or BF16, got {dtype!r}")
+    if variant not in (0, 1):
+        raise ValueError(f"write_checkpoint_safetensors: variant must be 0 or 1, got {variant!r}")
     if key_of is None:
-        from .pipeline import checkpoint_key as key_of
-    tensors = {}
+        from .pipeline import checkpoint_key
+        key_of = (lambda name: checkpoint_key(name, variant, with_slice=True)) if variant else checkpoint_key
+    tensors, fused = {}, {}
     for name, shape in specs:
         if name == "alphas_cumprod":
             if alphas_cumprod is not None:
                 tensors["alphas_cumprod"] = np.asarray(alphas_cumprod, np.float32)
             continue
-        key, transposed = key_of(name)
+        key, transposed, *part = key_of(name)
         a = np.asarray(get_tensor(name, shape), np.float32)
         if transposed:
             a = np.ascontiguousarray(a.T)
+        if variant == 1 and a.ndim == 4 and a.shape[2:] == (1, 1) and key.startswith("model.diffusion_model.") and key.endswith((".proj_in.weight", ".proj_out.weight")):
+            a = a.reshape(a.shape[:2])   # nn.Linear in SD 2.x
+        if part and part[0] is not None:   # a third of a fused tensor: kept until the key's three parts are there
+            fused.setdefault(key, {})[part[0]] = a
+            tensors.setdefault(key, None)   # the key's place in the file's order
+            continue
+        tensors[key] = a if dtype == "F32" else a.astype(np.float16) if dtype == "F16" else (bf16_bits(a), "BF16")
+    for key, parts in fused.items():
+        if sorted(parts) != [0, 1, 2]:
+            raise ValueError(f"write_checkpoint_safetensors: '{key}' needs its query, key and value parts, got {sorted(parts)}")
+        a = np.concatenate([parts[0], parts[1], parts[2]], axis=0)
         tensors[key] = a if dtype == "F32" else a.astype(np.float16) if dtype == "F16" else (bf16_bits(a), "BF16")
     tensors.update(extra or {})
     write_safetensors(path, tensors)
