@@ -202,6 +202,15 @@ extern "C" {
     fn sdmi_sampler_coefs_ex(sampler: *const SdmiSampler, alphas_cumprod: *const c_float, total: i32, ts: *const i32, count: i32, step_size: i64, prediction: i32,
                              coefs: *mut c_double) -> c_int;
     fn sdmi_set_prediction(ctx: *mut c_void, kind: i32) -> c_int;
+    fn sdmi_set_guidance_rescale(ctx: *mut c_void, phi: c_double) -> c_int;
+    fn sdmi_rescale_zero_snr(input: *const c_float, out: *mut c_float, n: i32) -> c_int;
+    fn sdmi_set_zero_snr(ctx: *mut c_void, on: i32) -> c_int;
+    fn sdmi_schedule(ctx: *mut c_void, out: *mut c_float, capacity: i32, count: *mut i32) -> c_int;
+    fn sdmi_op_sampler_step(ctx: *mut c_void, eps: *const c_float, latent: *const c_float, n: i32, h: i32, w: i32, scale: c_double, rescale: c_double,
+                            row: *const c_double, depth: i32, n_hist: i32, q_hist: *const c_float, noise_key: u64, noise_key2: u64, mask: *const c_float,
+                            z0: *const c_float, e0: *const c_float, blend_prev: c_double, blend_dir: c_double, latent_out: *mut c_float, q_out: *mut c_float) -> c_int;
+    fn sdmi_multi_set_guidance_rescale(m: *mut c_void, phi: c_double) -> c_int;
+    fn sdmi_multi_set_zero_snr(m: *mut c_void, on: i32) -> c_int;
     fn sdmi_attention_plan(ctx: *mut c_void, n: i32, n_head: i32, nq: i32, nk: i32, d_head: i32, has_mask: i32, out: *mut SdmiAttnPlan) -> c_int;
     fn sdmi_checkpoint_key_ex(dump_name: *const c_char, variant: i32, out: *mut c_char, capacity: usize, needed: *mut usize, transposed: *mut i32, slice: *mut i32) -> c_int;
     fn sdmi_safetensors_model_family(path: *const c_char, family: *mut i32) -> c_int;
@@ -370,6 +379,36 @@ impl StableDiffusionMi355 {
             return Err(last_error().into());
         }
         Ok(())
+    }
+
+    /// CFG rescale (`sdmi_set_guidance_rescale`, sticky): the guided model output of every evaluation is multiplied per image by
+    /// phi * std(cond) / std(guided) + (1 - phi).  phi in [0, 1]; 0 (the default) is off.
+    pub fn set_guidance_rescale(&mut self, phi: f64) -> Result<(), Box<dyn Error>> {
+        if unsafe { sdmi_set_guidance_rescale(self.ctx, phi) } != 0 {
+            return Err(last_error().into());
+        }
+        Ok(())
+    }
+
+    /// Sample on the loaded schedule rescaled to zero terminal SNR (`sdmi_set_zero_snr`, sticky); `false` restores the loaded table bit for bit.
+    pub fn set_zero_snr(&mut self, on: bool) -> Result<(), Box<dyn Error>> {
+        if unsafe { sdmi_set_zero_snr(self.ctx, on as i32) } != 0 {
+            return Err(last_error().into());
+        }
+        Ok(())
+    }
+
+    /// The alphas_cumprod table in force (`sdmi_schedule`).
+    pub fn schedule(&self) -> Result<Vec<f32>, Box<dyn Error>> {
+        let mut count = 0i32;
+        if unsafe { sdmi_schedule(self.ctx, std::ptr::null_mut(), 0, &mut count) } != 0 {
+            return Err(last_error().into());
+        }
+        let mut out = vec![0f32; count as usize];
+        if count > 0 && unsafe { sdmi_schedule(self.ctx, out.as_mut_ptr(), count, &mut count) } != 0 {
+            return Err(last_error().into());
+        }
+        Ok(out)
     }
 
     /// What this context would run for a qkv_attention of the shape under its current options (`sdmi_attention_plan`; host only, no launch).
@@ -685,6 +724,13 @@ impl StableDiffusionMi355 {
         Ok(out)
     }
 
+    /// A schedule rescaled to zero terminal SNR (`sdmi_rescale_zero_snr`, host only): the last entry is exactly 0, the first keeps its bits.
+    pub fn rescale_zero_snr(alphas_cumprod: &[f32]) -> Result<Vec<f32>, Box<dyn Error>> {
+        let mut out = vec![0f32; alphas_cumprod.len()];
+        if unsafe { sdmi_rescale_zero_snr(alphas_cumprod.as_ptr(), out.as_mut_ptr(), alphas_cumprod.len() as i32) } != 0 { return Err(last_error().into()); }
+        Ok(out)
+    }
+
     /// The checkpoint conversion kernel on its own (`sdmi_op_unpack_tensor`): `raw` = the tensor's bytes, dtype 0 F32 / 1 F16 / 2 BF16,
     /// transform 0 copy / 1 2-D transpose / 2 `[cout,3,kh,kw]` padded to 4 input channels.
     pub fn op_unpack_tensor(&self, raw: &[u8], dtype: i32, dims: &[i64], transform: i32) -> Result<Vec<f32>, Box<dyn Error>> {
@@ -889,6 +935,18 @@ impl StableDiffusionMi355Node {
             }
             Ok(Self { m, ctx_dim: cfg.ctx_dim as usize, image_bytes: 3 * 64 * (cfg.latent_h * cfg.latent_w) as usize })
         }
+    }
+
+    /// `StableDiffusionMi355::set_guidance_rescale` on every device (`sdmi_multi_set_guidance_rescale`): the statistic is per image, sharding changes nothing.
+    pub fn set_guidance_rescale(&mut self, phi: f64) -> Result<(), Box<dyn Error>> {
+        let st = unsafe { sdmi_multi_set_guidance_rescale(self.m, phi) };
+        if st != 0 { Err(last_error().into()) } else { Ok(()) }
+    }
+
+    /// `StableDiffusionMi355::set_zero_snr` on every device (`sdmi_multi_set_zero_snr`).
+    pub fn set_zero_snr(&mut self, on: bool) -> Result<(), Box<dyn Error>> {
+        let st = unsafe { sdmi_multi_set_zero_snr(self.m, on as i32) };
+        if st != 0 { Err(last_error().into()) } else { Ok(()) }
     }
 
     /// `StableDiffusionMi355::set_ksampler` on every device (`sdmi_multi_set_ksampler`); image_base per shard, as `set_sampler`.

@@ -349,6 +349,38 @@ int sdmi_sampler_coefs_ex(const sdmi_sampler* sampler, const float* alphas_cumpr
 int sdmi_ksampler_plan_ex(const sdmi_ksampler* ksampler, const float* alphas_cumprod, int32_t total, size_t n_steps, double strength, int32_t prediction, double* rows,
                           int32_t capacity, int32_t* count);
 
+/* ---- CFG rescale and zero-terminal-SNR schedules (no reference counterpart) ----
+ * The other two parts of the recipe v-prediction models are trained by (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed"); the third,
+ * trailing spacing, is the reference's step_by rule wherever n_steps divides the table.
+ *
+ * sdmi_set_guidance_rescale: phi in [0, 1], sticky, 0 = off (the default).  NaN or a value outside [0, 1] is SDMI_ERR_INVALID and the value in force stays.  With
+ * phi != 0 the guided model output g = eu + (ec - eu) scale (eps or v alike) of every evaluation is multiplied, per image b, by
+ *     f_b = phi std(ec_b) / std(g_b) + (1 - phi)            (std over the image's 4 h w elements; f_b = 1 where std(g_b) = 0 or a statistic is not finite)
+ * before the sampler's linear step -- diffusers' rescale_noise_cfg.  It holds for every sampler, k-sampler, img2img, mask, hires pass, inpainting call and for the
+ * sharded loop, still with ONE update launch per UNet evaluation: a step kernel with one workgroup per image, which sweeps the image three times (means, squared
+ * deviations, update) with fixed-order sums, so that an image's result depends neither on the batch size nor on its place in the batch.  With phi = 0 every call runs
+ * the launches and gives the bits it gave before.
+ *
+ * sdmi_rescale_zero_snr (host only, f64): s = sqrt(a); s <- (s - s_T) s_0 / (s_0 - s_T); out = float(s^2).  out[n - 1] is exactly 0, out[0] has in[0]'s bits.
+ * SDMI_ERR_INVALID for n < 2, entries outside [0, 1], or in[0] <= in[n - 1].  in and out may be the same array.
+ * sdmi_set_zero_snr: sticky; the context keeps the table it loaded and samples on the rescaled one, whether set before or after a loader; 0 restores the loaded table
+ * bit for bit.  sdmi_schedule reads the table in force (out NULL: *count alone; capacity below the count is SDMI_ERR_INVALID).
+ * On a table that holds a = 0: sdmi_sampler_coefs_ex writes the rows with a_t = 0 from x0 = -v, eps = x (nothing is singular under v) and leaves every other row as it
+ * was; eps-prediction is SDMI_ERR_INVALID there -- from sdmi_sampler_coefs(_ex) and from every sampling entry, before any launch: eps does not determine x0 at a = 0 --
+ * and a sigma-schedule sampler is SDMI_ERR_UNSUPPORTED (sigma_max is infinite), from sdmi_set_ksampler, sdmi_ksampler_sigmas / _plan(_ex) or the sampling call,
+ * whichever comes last.  The context stays as it was either way.  img2img at strength 1 starts from x = noise there.
+ *
+ * sdmi_op_sampler_step: one update launch on host NCHW tensors.  eps [2n][4][h][w] (unconditional half first), latent [n][4][h][w]; row[9] = cx ce h1 h2 h3 cz cz2
+ * qx qe; depth 0 / 1 / 3, q_hist [n_hist][n][4][h][w] (NULL where n_hist = 0), q_out [n][4][h][w] (NULL where depth = 0); mask [n][h][w], z0, e0 [n][4][h][w]: all
+ * three or none.  rescale = 0 launches the elementwise kernels of the sampler choice. */
+int sdmi_set_guidance_rescale(sdmi_ctx* ctx, double phi);
+int sdmi_rescale_zero_snr(const float* in, float* out, int32_t n);
+int sdmi_set_zero_snr(sdmi_ctx* ctx, int32_t on);
+int sdmi_schedule(sdmi_ctx* ctx, float* out, int32_t capacity, int32_t* count);
+int sdmi_op_sampler_step(sdmi_ctx* ctx, const float* eps, const float* latent, int32_t n, int32_t h, int32_t w, double scale, double rescale, const double* row,
+                         int32_t depth, int32_t n_hist, const float* q_hist, uint64_t noise_key, uint64_t noise_key2, const float* mask, const float* z0,
+                         const float* e0, double blend_prev, double blend_dir, float* latent_out, float* q_out);
+
 /* ---- ControlNet (SD v1; no reference counterpart) -----------------------------------------------------
  * A context created with sdmi_config.control_hint_ch = 3 has a fourth weight group, "controlnet/...": a second copy of the UNet's time MLP
  * (controlnet/lin1_time_embed, lin2_time_embed), its 12 input blocks and its middle block under the UNet's own names, the eight hint convolutions
@@ -714,6 +746,9 @@ int sdmi_sample_image_sharded(sdmi_multi* m, const float* context, int32_t T, co
 int sdmi_multi_set_sampler(sdmi_multi* m, const sdmi_sampler* sampler);
 /* sdmi_set_ksampler on every device context (checked once; NULL clears); image_base per shard, as sdmi_multi_set_sampler */
 int sdmi_multi_set_ksampler(sdmi_multi* m, const sdmi_ksampler* ksampler);
+/* sdmi_set_guidance_rescale / sdmi_set_zero_snr on every device context: the statistic is per image, so sharding needs nothing else */
+int sdmi_multi_set_guidance_rescale(sdmi_multi* m, double phi);
+int sdmi_multi_set_zero_snr(sdmi_multi* m, int32_t on);
 /* the contiguous global image range [begin, end) device `rank` of `n_ranks` samples (host only): the partition rule of
  * sdmi_sample_image_sharded, and of the one-process-per-GPU launcher (bench.py / sharding.py use the same rule) */
 int sdmi_shard_range(int32_t n_images, int32_t rank, int32_t n_ranks, int32_t* begin, int32_t* end);

@@ -845,7 +845,8 @@ void Engine::stage_commit(WeightEntry& e, size_t offset, int half) {
     const size_t count = entry_count(e);
     const float* host = reinterpret_cast<const float*>(st.pinned[half] + offset);
     if (e.kind == 3) {
-        alphas_.assign(host, host + count);
+        alphas_loaded_.assign(host, host + count);
+        refresh_schedule();
         e.set = true;
         return;
     }
@@ -1146,7 +1147,7 @@ void Engine::load_safetensors_groups(const char* path, bool control) {
         e.set = true;
         if (e.group != 3) finalized_ = false;
     }
-    if (alphas_entry) { alphas_ = schedule; alphas_entry->set = true; }
+    if (alphas_entry) { alphas_loaded_ = schedule; refresh_schedule(); alphas_entry->set = true; }
     if (control && finalized_) rebuild_folds();   // a ControlNet loaded behind finalize_weights: its folds are built here (the UNet's: by finalize_weights)
     SDMI_HIP(hipStreamSynchronize(stream_));
     if (profiling_) prof_flush();
@@ -3170,6 +3171,7 @@ void Engine::sample_latent_dev(const float* context, int n, int T, const float* 
     check_cond("sample_latent", false);
     if (n <= 0 || T <= 0 || Tu <= 0) throw Error(SDMI_ERR_INVALID, "sample_latent: n, T, Tu must be positive");
     check_batch(n);
+    check_schedule("sample_latent");
     const size_t total = alphas_.size();
     if (n_steps == 0 || n_steps > total) throw Error(SDMI_ERR_INVALID, "sample_latent: n_steps out of range");
     const int H = lat_h_, W = lat_w_;
@@ -3203,6 +3205,51 @@ void Engine::set_prediction(int kind) {
     prediction_ = kind;
 }
 
+void Engine::set_guidance_rescale(double phi) {
+    if (!(phi >= 0.0 && phi <= 1.0)) throw Error(SDMI_ERR_INVALID, "set_guidance_rescale: phi must satisfy 0 <= phi <= 1");
+    rescale_ = phi;
+}
+
+void Engine::rescale_zero_snr(const float* in, float* out, int n) {
+    if (!in || !out) throw Error(SDMI_ERR_INVALID, "rescale_zero_snr: null pointer");
+    if (n < 2) throw Error(SDMI_ERR_INVALID, "rescale_zero_snr: the table needs at least two entries");
+    for (int j = 0; j < n; ++j)
+        if (!(in[j] >= 0.0f && in[j] <= 1.0f)) throw Error(SDMI_ERR_INVALID, "rescale_zero_snr: alphas_cumprod must lie inside [0, 1]");
+    const double s0 = std::sqrt((double)in[0]), sT = std::sqrt((double)in[n - 1]);
+    if (!(s0 > sT)) throw Error(SDMI_ERR_INVALID, "rescale_zero_snr: the first entry must be larger than the last");
+    const double k = s0 / (s0 - sT);
+    for (int j = 1; j < n - 1; ++j) {
+        const double s = (std::sqrt((double)in[j]) - sT) * k;
+        out[j] = (float)(s * s);
+    }
+    out[0] = in[0];     // (s_0 - s_T) s_0 / (s_0 - s_T) = s_0: the bits it had
+    out[n - 1] = 0.0f;
+}
+
+void Engine::refresh_schedule() {
+    alphas_ = alphas_loaded_;
+    if (zero_snr_ && alphas_loaded_.size() >= 2) rescale_zero_snr(alphas_loaded_.data(), alphas_.data(), (int)alphas_.size());
+}
+
+void Engine::set_zero_snr(bool on) {
+    if (on && alphas_loaded_.size() >= 2) {   // refused before the state moves
+        std::vector<float> probe(alphas_loaded_.size());
+        rescale_zero_snr(alphas_loaded_.data(), probe.data(), (int)probe.size());
+    }
+    zero_snr_ = on;
+    refresh_schedule();
+}
+
+void Engine::check_schedule(const char* entry) const {
+    bool zero = false;
+    for (float a : alphas_) zero = zero || a == 0.0f;
+    if (!zero) return;
+    if (kset_)
+        throw Error(SDMI_ERR_UNSUPPORTED, std::string(entry) + ": a sigma-schedule sampler cannot run on a schedule that holds alphas_cumprod = 0 (zero terminal SNR): sigma_max is infinite");
+    if (prediction_ == 0)
+        throw Error(SDMI_ERR_INVALID, std::string(entry) + ": eps-prediction on a schedule that holds alphas_cumprod = 0 (zero terminal SNR): eps does not determine x0 there; set v-prediction");
+}
+
 void Engine::set_ksampler(const sdmi_ksampler* k) {
     if (!k) { ksampler_ = sdmi_ksampler{}; kset_ = false; return; }
     check_ksampler(*k, alphas_.empty() ? nullptr : alphas_.data(), (int)alphas_.size());
@@ -3223,6 +3270,7 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
                          const Blend* blend, float* latent_out, bool out_nhwc, const float* cond_nhwc, const std::vector<double>* kplan) {
     const int H = lat_h_, W = lat_w_, cd = cfg_.ctx_dim;
     const int nb = 2 * n, t_max = std::max(T, Tu);
+    check_schedule("sample_loop");
 
     // packed context [2n][t_max][cd]: rows 0..n-1 = uncond (broadcast, :173-177), n..2n-1 = cond
     Buf ctx(this, (size_t)nb * t_max * cd * 4);
@@ -3254,7 +3302,9 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
     if (cond_nhwc) unet_in_c.reset(new Buf(this, (size_t)(2 * per_half / 4) * unet_in_padded() * 4));
     // sampler choice: the coefficient table of the call and its history slots (x0 for DPM-Solver++(2M), three e for PLMS)
     // (v-prediction: the default path too runs on the table -- DDIM(eta = 0), depth 0 -- because cfg_ddim_update divides by sqrt(a_t) and is kept as it is)
-    const bool custom = !kplan && (sampler_.kind != 0 || sampler_.eta != 0.0 || prediction_ != 0);
+    // (CFG rescale, section 9k: the same -- the statistics need launch_sampler_step's one-workgroup-per-image kernel; with rescale_ = 0 nothing here changes)
+    const float rescale = (float)rescale_;
+    const bool custom = !kplan && (sampler_.kind != 0 || sampler_.eta != 0.0 || prediction_ != 0 || rescale_ != 0.0);
     const int depth = !custom ? 0 : sampler_.kind == 1 ? 1 : sampler_.kind == 2 ? 3 : 0;
     std::vector<double> coefs;
     std::unique_ptr<Buf> hist[3];
@@ -3282,7 +3332,7 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
         const uint64_t key = ksampler_.noise_seed + (uint64_t)ksampler_.image_base + (((uint64_t)k[KP_STEP] + 1) << 32);
         const bool bl = blend && last;
         { ProfScope ps_o(this, PC_OTHER);
-          SDMI_HIP(launch_sampler_step(eps.f(), latent.f(), unet_in.f(), per_half, (long long)H * W, p, depth, q_prev, depth ? hist[0]->f() : nullptr, key,
+          SDMI_HIP(launch_sampler_step(eps.f(), latent.f(), unet_in.f(), per_half, (long long)H * W, p, rescale, depth, q_prev, depth ? hist[0]->f() : nullptr, key,
                                        key + (1ull << 62), bl ? blend->mask : nullptr, bl ? blend->z0 : nullptr, bl ? blend->eps : nullptr, stream_)); }
         count_kernel();
     }
@@ -3314,7 +3364,7 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
             const uint64_t s_full = (uint64_t)((alphas_.size() - 1 - t) / step_size);
             const uint64_t key = sampler_.noise_seed + (uint64_t)sampler_.image_base + ((s_full + 1) << 32);
             ProfScope ps_o(this, PC_OTHER);
-            SDMI_HIP(launch_sampler_step(eps.f(), latent.f(), unet_in.f(), per_half, (long long)H * W, p, depth, q_prev, q_out, key, 0,
+            SDMI_HIP(launch_sampler_step(eps.f(), latent.f(), unet_in.f(), per_half, (long long)H * W, p, rescale, depth, q_prev, q_out, key, 0,
                                          blend ? blend->mask : nullptr, blend ? blend->z0 : nullptr, blend ? blend->eps : nullptr, stream_));
         } else
         if (blend) { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_cfg_ddim_masked(eps.f(), latent.f(), unet_in.f(), per_half, c, blend->mask, blend->z0, blend->eps, stream_)); }
@@ -3335,6 +3385,7 @@ std::vector<int> Engine::img2img_schedule(int n, int T, int Tu, size_t n_steps, 
     if (!finalized_) throw Error(SDMI_ERR_STATE, "weights not finalized");
     if (n <= 0 || T <= 0 || Tu <= 0) throw Error(SDMI_ERR_INVALID, "img2img: n, T, Tu must be positive");
     check_batch(n);
+    check_schedule("img2img");
     const size_t total = alphas_.size();
     if (n_steps == 0 || n_steps > total) throw Error(SDMI_ERR_INVALID, "img2img: n_steps out of range");
     *step_size = total / n_steps;
@@ -3523,6 +3574,37 @@ void Engine::op_resize(const float* x_nchw, int n, int h, int w, int oh, int ow,
     resize_nhwc4(xin.f(), n, h, w, oh, ow, mode, antialias, xout.f());
     { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(xout.f(), out_nchw, n, 4, oh, ow, stream_)); }
     count_kernel();
+}
+
+void Engine::op_sampler_step(const float* eps, const float* latent, int n, int h, int w, const SamplerStep& c, float rescale, int depth, const float* q_hist,
+                             uint64_t noise_key, uint64_t noise_key2, const float* mask, const float* z0, const float* e0, float* latent_out, float* q_out) {
+    const size_t img = (size_t)h * w * 16, half = (size_t)n * img;
+    const long long per_half = (long long)n * h * w * 4;
+    Buf de(this, 2 * half), dl(this, half), du(this, 2 * half), dq(this, 3 * half), dqo(this, half), dz(this, half), dn(this, half);
+    auto to_nhwc = [&](const float* src, float* dst, int images) {
+        ProfScope ps_o(this, PC_OTHER);
+        SDMI_HIP(launch_nchw_to_nhwc(src, dst, images, 4, h, w, 1.0f, stream_));
+        count_kernel();
+    };
+    to_nhwc(eps, de.f(), 2 * n);
+    to_nhwc(latent, dl.f(), n);
+    const float* q_prev[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < c.n_hist; ++k) {
+        to_nhwc(q_hist + (size_t)k * per_half, dq.f() + (size_t)k * per_half, n);
+        q_prev[k] = dq.f() + (size_t)k * per_half;
+    }
+    if (mask) { to_nhwc(z0, dz.f(), n); to_nhwc(e0, dn.f(), n); }
+    { ProfScope ps_o(this, PC_OTHER);
+      SDMI_HIP(launch_sampler_step(de.f(), dl.f(), du.f(), per_half, (long long)h * w, c, rescale, depth, q_prev, depth ? dqo.f() : nullptr, noise_key, noise_key2,
+                                   mask, mask ? dz.f() : nullptr, mask ? dn.f() : nullptr, stream_)); }
+    count_kernel();
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(dl.f(), latent_out, n, 4, h, w, stream_)); }
+    count_kernel();
+    if (depth) {
+        ProfScope ps_o(this, PC_OTHER);
+        SDMI_HIP(launch_nhwc_to_nchw(dqo.f(), q_out, n, 4, h, w, stream_));
+        count_kernel();
+    }
 }
 
 void Engine::check_hires(const sdmi_hires* hr) {

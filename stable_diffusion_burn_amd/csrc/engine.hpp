@@ -326,6 +326,17 @@ public:
 
     double bench_attention(int n, int nq, int nk, int n_state, int n_head, int iters);
     void set_prediction(int kind);   // 0 eps, 1 v
+    // CFG rescale and zero-terminal-SNR schedules, sticky like the prediction kind.  set_guidance_rescale: phi in [0, 1], 0 = off (SDMI_ERR_INVALID
+    // otherwise, the state kept).  set_zero_snr: sample on the loaded table rescaled to a_T = 0 (rescale_zero_snr); off restores the loaded one bit for bit.
+    void set_guidance_rescale(double phi);
+    double guidance_rescale() const { return rescale_; }
+    void set_zero_snr(bool on);
+    static void rescale_zero_snr(const float* in, float* out, int n);   // the paper's Algorithm 1 on sqrt(a), f64; throws SDMI_ERR_INVALID
+    // the sampling entries' refusals on a table that holds a = 0, before any launch: eps does not determine x0 there (INVALID), a k-sampler's sigma_max is infinite (UNSUPPORTED)
+    void check_schedule(const char* entry) const;
+    // one launch_sampler_step on NCHW device tensors (sdmi_op_sampler_step): eps [2n], latent [n], q_hist [n_hist][n], mask [n][hw], z0 / e0 [n]
+    void op_sampler_step(const float* eps, const float* latent, int n, int h, int w, const SamplerStep& c, float rescale, int depth, const float* q_hist,
+                         uint64_t noise_key, uint64_t noise_key2, const float* mask, const float* z0, const float* e0, float* latent_out, float* q_out);
     AttnPlan attention_plan(int n, int n_head, int nq, int nk, int d_head, bool has_mask) const;   // what qkv_attention_dev would run now; host only
     void set_option(const std::string& key, const std::string& value);
     void sync();
@@ -569,6 +580,10 @@ private:
     // kplan (a k-sampler is set): the rows of ksampler_plan for the call -- the loop walks its evaluations instead of ts, which is unused then.
     // kplan_for: the plan of a call of n_steps at `strength`, *a0 = 1 / (1 + sigma_start^2), the alpha of the img2img start.
     std::vector<double> kplan_for(size_t n_steps, double strength, double* a0) const;
+    double rescale_ = 0.0;   // sdmi_set_guidance_rescale
+    bool zero_snr_ = false;  // sdmi_set_zero_snr: alphas_ = rescale_zero_snr(alphas_loaded_) while on
+    std::vector<float> alphas_loaded_;
+    void refresh_schedule();   // alphas_ from alphas_loaded_ and zero_snr_
     int prediction_ = 0;   // sdmi_set_prediction: 0 = the UNet predicts eps, 1 = v (the coefficient tables are rewritten)
     // cond_nhwc (a conditioned model): [n][hw][padded_in_ch - 4]; every unet_run is preceded by assemble_unet_in into a buffer of the call
     float* cond_to_nhwc(const float* cond_nchw, int n);

@@ -38,10 +38,16 @@ __device__ __forceinline__ float cfg_ddim_update(float eu, float ec, float x, co
 // sdmi_sampler_coefs.  q1..q3 = the q of one / two / three steps ago (pass 0 where there is none: its weight is 0 then), z = the
 // step's N(0,1) draw (0 where cz = 0).  *q = what the step pushes to history (x0 for DPM-Solver++, e for PLMS).
 // Plain Euler on sigma = sqrt((1 - a) / a) is this step with DDIM's eta = 0 coefficients, Euler-ancestral with eta = 1.
-__device__ __forceinline__ float sampler_update(float eu, float ec, float x, float q1, float q2, float q3, float z, const SamplerStep& c, float* q) {
-    const float e = eu + (ec - eu) * c.scale;
+// The update is the CFG combine followed by the linear step on the guided output e: CFG rescale scales e per image between the two.
+__device__ __forceinline__ float sampler_combine(float eu, float ec, const SamplerStep& c) { return eu + (ec - eu) * c.scale; }
+
+__device__ __forceinline__ float sampler_apply(float e, float x, float q1, float q2, float q3, float z, const SamplerStep& c, float* q) {
     *q = c.qx * x + c.qe * e;
     return c.cx * x + c.ce * e + c.h[0] * q1 + c.h[1] * q2 + c.h[2] * q3 + c.cz * z;
+}
+
+__device__ __forceinline__ float sampler_update(float eu, float ec, float x, float q1, float q2, float q3, float z, const SamplerStep& c, float* q) {
+    return sampler_apply(sampler_combine(eu, ec, c), x, q1, q2, q3, z, c, q);
 }
 
 }  // namespace sdmi

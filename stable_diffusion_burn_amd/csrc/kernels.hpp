@@ -302,7 +302,10 @@ struct SamplerStep { float scale, cx, ce, h[3], cz, qx, qe, blend_prev, blend_di
 // ([n][hw][4], read where k < n_hist), q_out receives this step's q (it may be the oldest slot: every thread reads its pixel before it writes it).
 // Noise (cz != 0 only): element i (NCHW order within the image) of image b is normal_draw(noise_key + b, i); z2 (cz2 != 0 only) the same from noise_key2.
 // mask / z0 / e0: all or none.
-hipError_t launch_sampler_step(const float* eps, float* latent, float* unet_in, long long per_half, long long hw, SamplerStep c, int depth,
+// rescale (CFG rescale, sdmi_set_guidance_rescale; section 9k), in [0, 1]: 0 launches the elementwise kernels above, as always.  Otherwise e is multiplied by
+// f_b = rescale std(ec_b) / std(e_b) + (1 - rescale) before q and x' are formed, the statistics over image b's 4 hw elements (f_b = 1 where std(e_b) = 0 or
+// one of them is not finite): sampler_step_rescale_kernel, one workgroup per image, still ONE launch.
+hipError_t launch_sampler_step(const float* eps, float* latent, float* unet_in, long long per_half, long long hw, SamplerStep c, float rescale, int depth,
                                const float* const q_prev[3], float* q_out, uint64_t noise_key, uint64_t noise_key2, const float* mask, const float* z0,
                                const float* e0, hipStream_t s);
 

@@ -46,6 +46,8 @@ struct Table {
 void check_table(const float* alphas, int total) {
     if (!alphas) bad("ksampler: null alphas_cumprod");
     if (total < 1) bad("ksampler: total must be positive");
+    for (int j = 0; j < total; ++j)   // zero terminal SNR: sigma_max = inf, no sigma schedule
+        if (alphas[j] == 0.0f) throw Error(SDMI_ERR_UNSUPPORTED, "ksampler: the schedule holds alphas_cumprod = 0 (zero terminal SNR): sigma_max is infinite");
     for (int j = 0; j < total; ++j)
         if (!(alphas[j] > 0.0f && alphas[j] < 1.0f)) bad("ksampler: alphas_cumprod must lie inside (0, 1)");
 }

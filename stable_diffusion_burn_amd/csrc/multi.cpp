@@ -196,6 +196,15 @@ public:
         for (int r = 0; r < size(); ++r) engine(r).set_ksampler(k);
     }
 
+    // sdmi_multi_set_guidance_rescale / sdmi_multi_set_zero_snr: every context holds the same table and
+    // applies the same check: a refusal comes from the first one and leaves all of them as they were
+    void set_guidance_rescale(double phi) {
+        for (int r = 0; r < size(); ++r) engine(r).set_guidance_rescale(phi);
+    }
+    void set_zero_snr(bool on) {
+        for (int r = 0; r < size(); ++r) engine(r).set_zero_snr(on);
+    }
+
     long long broadcasts() const { return broadcasts_; }
 
 private:
@@ -314,6 +323,20 @@ int sdmi_multi_set_ksampler(sdmi_multi* m, const sdmi_ksampler* ksampler) {
     return multi_guard([&] {
         if (!m) throw sdmi::Error(SDMI_ERR_INVALID, "null sdmi_multi");
         m->m->set_ksampler(ksampler);
+    });
+}
+
+int sdmi_multi_set_guidance_rescale(sdmi_multi* m, double phi) {
+    return multi_guard([&] {
+        if (!m) throw sdmi::Error(SDMI_ERR_INVALID, "null sdmi_multi");
+        m->m->set_guidance_rescale(phi);
+    });
+}
+
+int sdmi_multi_set_zero_snr(sdmi_multi* m, int32_t on) {
+    return multi_guard([&] {
+        if (!m) throw sdmi::Error(SDMI_ERR_INVALID, "null sdmi_multi");
+        m->m->set_zero_snr(on != 0);
     });
 }
 

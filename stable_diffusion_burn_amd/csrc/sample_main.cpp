@@ -24,6 +24,9 @@
 //     noise is seeded by SDMI_SEED.
 //   * SDMI_PREDICTION=v | eps (no reference counterpart; unset: eps) says what the checkpoint's UNet predicts (sdmi_set_prediction): v for SD 2.x's 768-v models.  An
 //     SD 2.x checkpoint needs SDMI_CONFIG="variant=1,ctx_dim=1024,clip_layers=23,clip_heads=16" and, for OpenCLIP's padding, SDMI_PROMPT_STYLE=webui.
+//   * SDMI_GUIDANCE_RESCALE=phi (0 .. 1; unset: 0, off) and SDMI_ZERO_SNR=1 (no reference counterpart): CFG rescale
+//     (sdmi_set_guidance_rescale) and the schedule rescaled to zero terminal SNR (sdmi_set_zero_snr; needs SDMI_PREDICTION=v) -- what the 768-v models and most
+//     v-prediction fine-tunes are sampled with (phi = 0.7).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -172,6 +175,23 @@ int main(int argc, char** argv) {
         if (!std::strcmp(pr, "v")) prediction = 1;
         else if (*pr && std::strcmp(pr, "eps")) { std::fprintf(stderr, "Error: SDMI_PREDICTION must be v or eps, got '%s'\n", pr); return 1; }
     }
+    // SDMI_GUIDANCE_RESCALE / SDMI_ZERO_SNR: likewise
+    double guidance_rescale = 0.0;
+    if (const char* gr = std::getenv("SDMI_GUIDANCE_RESCALE")) {
+        char* end = nullptr;
+        guidance_rescale = std::strtod(gr, &end);
+        if (!*gr || *end || !(guidance_rescale >= 0.0 && guidance_rescale <= 1.0)) {
+            std::fprintf(stderr, "Error: SDMI_GUIDANCE_RESCALE must be a number in [0, 1], got '%s'\n", gr);
+            return 1;
+        }
+    }
+    int32_t zero_snr = 0;
+    if (const char* zs = std::getenv("SDMI_ZERO_SNR")) {
+        if (!std::strcmp(zs, "1")) zero_snr = 1;
+        else if (*zs && std::strcmp(zs, "0")) { std::fprintf(stderr, "Error: SDMI_ZERO_SNR must be 0 or 1, got '%s'\n", zs); return 1; }
+    }
+    if (zero_snr && prediction != 1) { std::fprintf(stderr, "Error: SDMI_ZERO_SNR=1 needs SDMI_PREDICTION=v (eps does not determine x0 where alphas_cumprod is 0)\n"); return 1; }
+    if (zero_snr && has_ksampler) { std::fprintf(stderr, "Error: SDMI_ZERO_SNR=1 excludes SDMI_KSAMPLER (sigma_max is infinite)\n"); return 1; }
 
     std::printf("Loading tokenizer...\n");
     const char* vocab = std::getenv("SDMI_BPE_VOCAB");
@@ -183,6 +203,8 @@ int main(int argc, char** argv) {
     if (sdmi_create(&ctx, &cfg) != SDMI_OK) die("Error creating device context");
     if (has_ksampler && sdmi_set_ksampler(ctx, &ksampler) != SDMI_OK) die("Error setting the k-sampler");   // sticky: set before the weights, refused at once
     if (sdmi_set_prediction(ctx, prediction) != SDMI_OK) die("Error setting the prediction kind");
+    if (sdmi_set_guidance_rescale(ctx, guidance_rescale) != SDMI_OK) die("Error setting the guidance rescale");
+    if (sdmi_set_zero_snr(ctx, zero_snr) != SDMI_OK) die("Error setting the zero-terminal-SNR schedule");
     const char* lora = std::getenv("SDMI_LORA");
     if (lora && *lora && sdmi_set_option(ctx, "keep_masters", "1") != SDMI_OK) die("Error setting keep_masters");
     if (model_type == "burn") {

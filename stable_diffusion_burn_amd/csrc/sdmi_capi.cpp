@@ -1073,6 +1073,10 @@ int sdmi_sampler_coefs_ex(const sdmi_sampler* sampler, const float* alphas_cumpr
         if (total <= 0 || count <= 0 || step_size < 1) throw Error(SDMI_ERR_INVALID, "sampler_coefs: total, count and step_size must be positive");
         for (int32_t j = 0; j < count; ++j)
             if (ts[j] < 0 || ts[j] >= total) throw Error(SDMI_ERR_INVALID, "sampler_coefs: timestep outside [0, total)");
+        if (prediction == 0)
+            for (int32_t j = 0; j < total; ++j)
+                if (alphas_cumprod[j] == 0.0f)
+                    throw Error(SDMI_ERR_INVALID, "sampler_coefs: eps-prediction on a schedule that holds alphas_cumprod = 0 (zero terminal SNR): eps does not determine x0 there");
         auto lambda = [](double a) { return 0.5 * std::log(a / (1.0 - a)); };
         static const double AB[4][4] = {{1.0, 0.0, 0.0, 0.0}, {3.0 / 2, -1.0 / 2, 0.0, 0.0}, {23.0 / 12, -16.0 / 12, 5.0 / 12, 0.0},
                                         {55.0 / 24, -59.0 / 24, 37.0 / 24, -9.0 / 24}};
@@ -1083,6 +1087,26 @@ int sdmi_sampler_coefs_ex(const sdmi_sampler* sampler, const float* alphas_cumpr
             const double sc = std::sqrt(cur), sn = std::sqrt(1.0 - cur), sp = std::sqrt(prev);
             double* k = coefs + (size_t)j * 8;
             for (int i = 0; i < 8; ++i) k[i] = 0.0;
+            if (cur == 0.0) {
+                // zero terminal SNR (v only, checked above): the eps basis is singular at a = 0 and v is not -- x0 = -v, eps = x.  The row is
+                // written in v at once: x' = sp x0 + dir eps + sigma z.
+                const double om = 1.0 - prev;
+                if (sampler->kind == 0) {
+                    const double sigma = sampler->eta * std::sqrt(om);
+                    k[0] = std::sqrt(om - sigma * sigma);
+                    k[1] = -sp;
+                    k[5] = sigma;
+                } else if (sampler->kind == 1) {
+                    k[6] = 0.0; k[7] = -1.0;                    // q = x0 = -v
+                    if (prev >= 1.0) { k[0] = 0.0; k[1] = -1.0; }
+                    else { k[0] = std::sqrt(om); k[1] = -sp; }  // h = inf: first order whatever came before, no weight on the history
+                } else {
+                    k[0] = std::sqrt(om);
+                    k[1] = -sp;
+                    k[6] = 1.0; k[7] = 0.0;                     // q = eps = x: the model output has no part in it
+                }
+                continue;
+            }
             if (sampler->kind == 0) {
                 const double sigma = sampler->eta * std::sqrt((1.0 - prev) / (1.0 - cur)) * std::sqrt(1.0 - cur / prev);
                 const double dir = std::sqrt(1.0 - prev - sigma * sigma);
@@ -1098,7 +1122,7 @@ int sdmi_sampler_coefs_ex(const sdmi_sampler* sampler, const float* alphas_cumpr
                     const double h = lambda(prev) - lambda(cur);
                     const double A = std::sqrt((1.0 - prev) / (1.0 - cur)), B = -sp * std::expm1(-h);
                     double w0 = 1.0, w1 = 0.0;
-                    if (j > 0) {
+                    if (j > 0 && alphas_cumprod[ts[j - 1]] != 0.0f) {   // (behind a zero row lambda = -inf, r = +inf: first order, written out)
                         const double r = (lambda(cur) - lambda((double)alphas_cumprod[ts[j - 1]])) / h;
                         w0 = 1.0 + 1.0 / (2.0 * r);
                         w1 = -1.0 / (2.0 * r);
@@ -1121,6 +1145,66 @@ int sdmi_sampler_coefs_ex(const sdmi_sampler* sampler, const float* alphas_cumpr
 
 int sdmi_set_prediction(sdmi_ctx* ctx, int32_t kind) {
     return guarded([&] { eng(ctx).set_prediction(kind); });
+}
+
+// ---- CFG rescale and zero-terminal-SNR schedules ---------------------------------------------------------------------
+int sdmi_set_guidance_rescale(sdmi_ctx* ctx, double phi) {
+    return guarded([&] { eng(ctx).set_guidance_rescale(phi); });
+}
+
+int sdmi_rescale_zero_snr(const float* in, float* out, int32_t n) {
+    return guarded([&] { Engine::rescale_zero_snr(in, out, n); });
+}
+
+int sdmi_set_zero_snr(sdmi_ctx* ctx, int32_t on) {
+    return guarded([&] { eng(ctx).set_zero_snr(on != 0); });
+}
+
+int sdmi_schedule(sdmi_ctx* ctx, float* out, int32_t capacity, int32_t* count) {
+    return guarded([&] {
+        const std::vector<float>& a = eng(ctx).alphas();
+        if (!count) throw Error(SDMI_ERR_INVALID, "schedule: count is NULL");
+        *count = (int32_t)a.size();
+        if (!out) return;   // the size alone
+        if (capacity < (int32_t)a.size()) throw Error(SDMI_ERR_INVALID, "schedule: capacity below the table's " + std::to_string(a.size()) + " entries");
+        std::copy(a.begin(), a.end(), out);
+    });
+}
+
+int sdmi_op_sampler_step(sdmi_ctx* ctx, const float* eps, const float* latent, int32_t n, int32_t h, int32_t w, double scale, double rescale, const double* row,
+                         int32_t depth, int32_t n_hist, const float* q_hist, uint64_t noise_key, uint64_t noise_key2, const float* mask, const float* z0,
+                         const float* e0, double blend_prev, double blend_dir, float* latent_out, float* q_out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (n <= 0 || h <= 0 || w <= 0) throw Error(SDMI_ERR_INVALID, "sampler_step: bad shape");
+        if (!eps || !latent || !row || !latent_out) throw Error(SDMI_ERR_INVALID, "sampler_step: null pointer");
+        if (depth != 0 && depth != 1 && depth != 3) throw Error(SDMI_ERR_INVALID, "sampler_step: depth must be 0, 1 or 3");
+        if (n_hist < 0 || n_hist > depth || (n_hist && !q_hist) || (depth && !q_out)) throw Error(SDMI_ERR_INVALID, "sampler_step: history does not fit depth");
+        if (!(rescale >= 0.0 && rescale <= 1.0)) throw Error(SDMI_ERR_INVALID, "sampler_step: rescale must satisfy 0 <= rescale <= 1");
+        if ((!mask) != (!z0) || (!mask) != (!e0)) throw Error(SDMI_ERR_INVALID, "sampler_step: mask, z0 and e0 come together");
+        if (row[6] != 0.0 && (depth != 1 || row[5] == 0.0)) throw Error(SDMI_ERR_INVALID, "sampler_step: cz2 needs depth 1 and cz != 0");
+        sdmi::SamplerStep c{};
+        c.scale = (float)scale;
+        c.cx = (float)row[0]; c.ce = (float)row[1]; c.h[0] = (float)row[2]; c.h[1] = (float)row[3]; c.h[2] = (float)row[4];
+        c.cz = (float)row[5]; c.cz2 = (float)row[6]; c.qx = (float)row[7]; c.qe = (float)row[8];
+        c.blend_prev = (float)blend_prev; c.blend_dir = (float)blend_dir;
+        c.n_hist = n_hist;
+        const size_t hw = (size_t)h * w, lat = (size_t)n * 4 * hw * sizeof(float);
+        Engine::Call call(e);
+        DevIn de(e, eps, 2 * lat), dl(e, latent, lat);
+        auto dq = dev_in_opt(e, n_hist ? q_hist : nullptr, (size_t)n_hist * lat);
+        auto dm = dev_in_opt(e, mask, (size_t)n * hw * sizeof(float));
+        auto dz = dev_in_opt(e, z0, lat);
+        auto dn = dev_in_opt(e, e0, lat);
+        DevOut dout(e, latent_out, lat);
+        std::unique_ptr<DevOut> dqo;
+        if (depth) dqo.reset(new DevOut(e, q_out, lat));
+        e.op_sampler_step(de.f(), dl.f(), n, h, w, c, (float)rescale, depth, dq ? dq->f() : nullptr, noise_key, noise_key2, dm ? dm->f() : nullptr,
+                          dz ? dz->f() : nullptr, dn ? dn->f() : nullptr, dout.f(), dqo ? dqo->f() : nullptr);
+        call.finish();
+        dout.fetch();
+        if (dqo) dqo->fetch();
+    });
 }
 
 int sdmi_img2img_latent(sdmi_ctx* ctx, const float* context, int32_t n, int32_t T, const float* uncond, int32_t Tu, double scale,

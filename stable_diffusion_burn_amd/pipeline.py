@@ -181,6 +181,18 @@ def sampler_coefs(kind: str, eta: float, alphas_cumprod, ts, step_size: int, pre
     return out
 
 
+def rescale_zero_snr(alphas_cumprod) -> np.ndarray:
+    """The schedule rescaled to zero terminal SNR (sdmi_rescale_zero_snr; host only, no GPU): Algorithm 1 of Lin et al. on sqrt(alphas_cumprod) in float64,
+    narrowed to float32.  The last entry is exactly 0, the first keeps its bits."""
+    lib = load_library()
+    a = np.ascontiguousarray(alphas_cumprod, dtype=np.float32)
+    if a.ndim != 1:
+        raise ValueError(f"alphas_cumprod must be one-dimensional, got {a.shape}")
+    out = np.empty_like(a)
+    check(lib.sdmi_rescale_zero_snr(_fp(a), _fp(out), a.size))
+    return out
+
+
 KSAMPLER_KINDS = ("euler", "dpmpp_2m", "heun", "dpm2", "dpmpp_2s", "dpmpp_sde", "dpmpp_2m_sde")   # sdmi_ksampler.kind 0 .. 6
 KSAMPLER_SCHEDULES = ("model", "karras", "exponential", "uniform")                                # sdmi_ksampler.schedule 0 .. 3
 KSAMPLER_PLAN_COLUMNS = ("step", "stage", "t", "sigma", "cx", "ce", "h1", "cz", "cz2", "qx", "qe", "a_end")
@@ -1208,6 +1220,26 @@ class StableDiffusion:
         point and sampler (sdmi_set_prediction).  The checkpoint does not say which: the caller chooses."""
         check(self._lib.sdmi_set_prediction(self._ctx, _prediction(kind)))
 
+    def set_guidance_rescale(self, phi: float = 0.0) -> None:
+        """CFG rescale (sdmi_set_guidance_rescale): the guided model output of every evaluation is multiplied per image by
+        phi * std(cond) / std(guided) + (1 - phi).  phi in [0, 1]; 0 (the default) is off and runs what ran before; sticky.  0.7 is the value v-prediction
+        models trained with zero terminal SNR are usually sampled at."""
+        check(self._lib.sdmi_set_guidance_rescale(self._ctx, float(phi)))
+
+    def set_zero_snr(self, on: bool = True) -> None:
+        """Sample on the loaded schedule rescaled to zero terminal SNR (sdmi_set_zero_snr; rescale_zero_snr); False restores the loaded table bit for bit.
+        Sticky, before or after the weights.  Needs set_prediction("v"); sigma-schedule samplers are refused on such a table."""
+        check(self._lib.sdmi_set_zero_snr(self._ctx, 1 if on else 0))
+
+    def schedule(self) -> np.ndarray:
+        """The alphas_cumprod table in force (sdmi_schedule): the loaded one, or its zero-terminal-SNR rescale."""
+        count = C.c_int32()
+        check(self._lib.sdmi_schedule(self._ctx, None, 0, C.byref(count)))
+        out = np.empty(count.value, dtype=np.float32)
+        if count.value:
+            check(self._lib.sdmi_schedule(self._ctx, _fp(out), out.size, C.byref(count)))
+        return out
+
     ATTN_KERNELS = ("unfused", "flash", "split", "bf16")   # sdmi_attn_plan.kernel: GEMM path, k_attn.hip, k_attn_split.hip, k_attn_bf16.hip
 
     def attention_plan(self, n, n_head, nq, nk, d_head, has_mask=False) -> dict:
@@ -1239,6 +1271,34 @@ class StableDiffusion:
         dims = (C.c_int64 * raw.ndim)(*shape)
         check(self._lib.sdmi_op_unpack_tensor(self._ctx, raw.ctypes.data_as(C.c_void_p), code, raw.ndim, dims, int(transform), _fp(out)))
         return out
+
+    def op_sampler_step(self, eps, latent, scale: float, row, rescale: float = 0.0, depth: int = 0, q_hist=None, noise_key: int = 0, noise_key2: int = 0,
+                        mask=None, z0=None, e0=None, blend_prev: float = 0.0, blend_dir: float = 0.0):
+        """One update launch of the sampler choice on its own (sdmi_op_sampler_step): eps [2n,4,h,w] (unconditional half first), latent [n,4,h,w],
+        row = (cx, ce, h1, h2, h3, cz, cz2, qx, qe), q_hist [n_hist,n,4,h,w] (newest first).  Returns (latent_out, q_out); q_out is None at depth 0.
+        rescale = 0 launches the elementwise kernels, otherwise the CFG-rescale kernel."""
+        latent = _f32(latent)
+        if latent.ndim != 4 or latent.shape[1] != 4:
+            raise ValueError(f"op_sampler_step: latent must be [n,4,h,w], got {latent.shape}")
+        n, _, h, w = latent.shape
+        eps = _f32(eps, (2 * n, 4, h, w), "eps")
+        row = np.ascontiguousarray(row, dtype=np.float64)
+        if row.shape != (9,):
+            raise ValueError(f"op_sampler_step: row must hold 9 coefficients, got {row.shape}")
+        n_hist = 0
+        if q_hist is not None:
+            q_hist = _f32(q_hist)
+            n_hist = q_hist.shape[0]
+            q_hist = _f32(q_hist, (n_hist, n, 4, h, w), "q_hist")
+        if mask is not None:
+            mask, z0, e0 = _f32(mask, (n, h, w), "mask"), _f32(z0, (n, 4, h, w), "z0"), _f32(e0, (n, 4, h, w), "e0")
+        out = np.empty_like(latent)
+        q_out = np.empty_like(latent) if depth else None
+        opt = lambda a: None if a is None else _fp(a)
+        check(self._lib.sdmi_op_sampler_step(self._ctx, _fp(eps), _fp(latent), n, h, w, float(scale), float(rescale), row.ctypes.data_as(C.POINTER(C.c_double)),
+                                             int(depth), n_hist, opt(q_hist) if n_hist else None, int(noise_key) & 0xFFFFFFFFFFFFFFFF,
+                                             int(noise_key2) & 0xFFFFFFFFFFFFFFFF, opt(mask), opt(z0), opt(e0), float(blend_prev), float(blend_dir), _fp(out), opt(q_out)))
+        return out, q_out
 
     def op_resize(self, x, out_size, mode="bicubic", antialias: bool = False):
         """The resampler of the hires fix on its own (sdmi_op_resize): x [n,4,h,w] -> [n,4,out_h,out_w]."""
@@ -1649,6 +1709,18 @@ class MultiStableDiffusion:
         """StableDiffusion.set_prediction on every device."""
         for i in range(len(self.devices)):
             self.device_view(i).set_prediction(kind)
+
+    def set_guidance_rescale(self, phi: float = 0.0) -> None:
+        """StableDiffusion.set_guidance_rescale on every device (sdmi_multi_set_guidance_rescale): the statistic is per image, sharding changes nothing."""
+        check(self._lib.sdmi_multi_set_guidance_rescale(self._m, float(phi)))
+
+    def set_zero_snr(self, on: bool = True) -> None:
+        """StableDiffusion.set_zero_snr on every device (sdmi_multi_set_zero_snr)."""
+        check(self._lib.sdmi_multi_set_zero_snr(self._m, 1 if on else 0))
+
+    def schedule(self) -> np.ndarray:
+        """StableDiffusion.schedule of device 0 (every device holds the same table)."""
+        return self.device_view(0).schedule()
 
     def set_ksampler(self, kind="dpmpp_2m", schedule="karras", eta: float = 0.0, rho: float = 7.0, sigma_min=None, sigma_max=None, noise_seed: int = 0) -> None:
         """StableDiffusion.set_ksampler on every device (sdmi_multi_set_ksampler); image_base per shard, as set_sampler."""
