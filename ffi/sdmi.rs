@@ -211,6 +211,13 @@ extern "C" {
                             z0: *const c_float, e0: *const c_float, blend_prev: c_double, blend_dir: c_double, latent_out: *mut c_float, q_out: *mut c_float) -> c_int;
     fn sdmi_multi_set_guidance_rescale(m: *mut c_void, phi: c_double) -> c_int;
     fn sdmi_multi_set_zero_snr(m: *mut c_void, on: i32) -> c_int;
+    fn sdmi_set_freeu(ctx: *mut c_void, version: i32, b1: c_float, b2: c_float, s1: c_float, s2: c_float, start: c_double, end: c_double) -> c_int;
+    fn sdmi_get_freeu(ctx: *mut c_void, version: *mut i32, b1: *mut c_float, b2: *mut c_float, s1: *mut c_float, s2: *mut c_float, start: *mut c_double,
+                      end: *mut c_double) -> c_int;
+    fn sdmi_freeu_plan(cfg: *const SdmiConfig, latent_h: i32, latent_w: i32, out: *mut i32) -> c_int;
+    fn sdmi_op_freeu(ctx: *mut c_void, x: *const c_float, n: i32, c: i32, h: i32, w: i32, cx: i32, version: i32, b: c_float, s: c_float, y: *mut c_float,
+                     y_from_planes: *mut c_float) -> c_int;
+    fn sdmi_multi_set_freeu(m: *mut c_void, version: i32, b1: c_float, b2: c_float, s1: c_float, s2: c_float, start: c_double, end: c_double) -> c_int;
     fn sdmi_attention_plan(ctx: *mut c_void, n: i32, n_head: i32, nq: i32, nk: i32, d_head: i32, has_mask: i32, out: *mut SdmiAttnPlan) -> c_int;
     fn sdmi_checkpoint_key_ex(dump_name: *const c_char, variant: i32, out: *mut c_char, capacity: usize, needed: *mut usize, transposed: *mut i32, slice: *mut i32) -> c_int;
     fn sdmi_safetensors_model_family(path: *const c_char, family: *mut i32) -> c_int;
@@ -385,6 +392,17 @@ impl StableDiffusionMi355 {
     /// phi * std(cond) / std(guided) + (1 - phi).  phi in [0, 1]; 0 (the default) is off.
     pub fn set_guidance_rescale(&mut self, phi: f64) -> Result<(), Box<dyn Error>> {
         if unsafe { sdmi_set_guidance_rescale(self.ctx, phi) } != 0 {
+            return Err(last_error().into());
+        }
+        Ok(())
+    }
+
+    /// FreeU (`sdmi_set_freeu`, sticky): the backbone half of every decoder concatenation scaled by b1 / b2, the low frequencies of its skip
+    /// half by s1 / s2 -- the rule keyed on the backbone's channel count, as ComfyUI ships it.  `version` 0 clears, 1 is FreeU, 2 FreeU_V2; `start` / `end`: the
+    /// step window of a sampling call.
+    #[allow(clippy::too_many_arguments)]
+    pub fn set_freeu(&mut self, version: i32, b1: f32, b2: f32, s1: f32, s2: f32, start: f64, end: f64) -> Result<(), Box<dyn Error>> {
+        if unsafe { sdmi_set_freeu(self.ctx, version, b1, b2, s1, s2, start, end) } != 0 {
             return Err(last_error().into());
         }
         Ok(())
@@ -940,6 +958,13 @@ impl StableDiffusionMi355Node {
     /// `StableDiffusionMi355::set_guidance_rescale` on every device (`sdmi_multi_set_guidance_rescale`): the statistic is per image, sharding changes nothing.
     pub fn set_guidance_rescale(&mut self, phi: f64) -> Result<(), Box<dyn Error>> {
         let st = unsafe { sdmi_multi_set_guidance_rescale(self.m, phi) };
+        if st != 0 { Err(last_error().into()) } else { Ok(()) }
+    }
+
+    /// `StableDiffusionMi355::set_freeu` on every device (`sdmi_multi_set_freeu`): the edits are per sample, sharding changes nothing.
+    #[allow(clippy::too_many_arguments)]
+    pub fn set_freeu(&mut self, version: i32, b1: f32, b2: f32, s1: f32, s2: f32, start: f64, end: f64) -> Result<(), Box<dyn Error>> {
+        let st = unsafe { sdmi_multi_set_freeu(self.m, version, b1, b2, s1, s2, start, end) };
         if st != 0 { Err(last_error().into()) } else { Ok(()) }
     }
 

@@ -435,6 +435,39 @@ int sdmi_control_residuals(sdmi_ctx* ctx, const float* x, int32_t t, const float
 int sdmi_sampler_coefs(const sdmi_sampler* sampler, const float* alphas_cumprod, int32_t total, const int32_t* ts, int32_t count,
                        int64_t step_size, double* coefs);
 
+/* ---- FreeU (no reference counterpart) -----------------------------------------------------
+ * Si et al., "FreeU: Free Lunch in Diffusion U-Net", as ComfyUI's FreeU / FreeU_V2 nodes ship it: in front of every output block of the UNet the two halves of
+ * torch.cat([h, hs]) are re-balanced -- no weights, no training.  The rule is PER BLOCK, keyed on the channel count cx of the backbone tensor h entering the block
+ * (mc = model_channels):    cx == 4 mc (output blocks 0..6): (b, s) = (b1, s1);    cx == 2 mc (blocks 7..9): (b2, s2);    otherwise (blocks 10, 11) nothing happens.
+ * (diffusers' enable_freeu keys on the resolution instead -- its resolution_idx rule touches other blocks, and is NOT what runs here.)
+ *   skip      hs <- Fourier_filter(hs, threshold 1, scale s): fftn over (H, W), fftshift, the box [H/2-1 : H/2+1, W/2-1 : W/2+1] times s, ifftshift, ifftn, real part.
+ *             The box holds at most four coefficients, so the engine evaluates it in closed form (csrc/k_freeu.hip) -- one launch per forward for all filtered skips.
+ *   backbone  version 1: h[:, :cx/2] *= b.   version 2: m = mean of h over its cx channels, per sample m^ = (m - min m) / (max m - min m),
+ *             h[:, :cx/2] *= (b - 1) m^ + 1.  The one deviation from the published code: where max m == min m (a 1 x 1 level) it divides by zero; here m^ = 0.
+ *             One launch (version 1) or two (version 2) per affected block.
+ * A ControlNet adds to the saved skips and to the middle block's output first; FreeU works on the sums.  Both halves of a CFG batch are treated alike.  fp32
+ * arithmetic at every precision; at precision 0 the fp32 tensor and its bf16 planes are both rewritten, at precisions 1 / 2 the bf16 value is rounded once.
+ *
+ * sdmi_set_freeu: sticky, like sdmi_set_sampler; it applies to every later forward of the context (sdmi_unet_forward*: every call; the sampling entries: the steps
+ * of the window start * S <= i < end * S, sdmi_control_step_on's rule and step index -- both evaluations of a two-evaluation sampler's step agree).  version 0
+ * clears the state (the other arguments are ignored).  SDMI_ERR_INVALID -- and the state in force stays --: a version outside 0..2, a non-finite parameter, b <= 0,
+ * s < 0, start > end or a bound outside [0, 1].  SDMI_ERR_UNSUPPORTED -- likewise --: a model whose cx / 2 or skip widths of the affected blocks are no multiples of
+ * 32 (precisions 1 and 2: 64).  A group whose b == 1 runs no backbone launch, one whose s == 1 filters nothing: with all four at 1, with an empty window or with
+ * the state cleared every call runs the launches and gives the bits it gave before.
+ * sdmi_get_freeu: the state in force (version 0: the other outputs hold the defaults 1, 1, 1, 1, 0, 1); any output may be NULL.
+ * sdmi_freeu_plan (host only, needs no context): THE block rule.  For output block i of a model with cfg's model_channels at latent_h x latent_w it writes
+ * out[5 i .. 5 i + 4] = group (0 none, 1: b1 / s1, 2: b2 / s2), cx, cskip, h, w -- the shape of the concatenation the block reads.  SDMI_ERR_INVALID: a NULL
+ * pointer, model_channels < 1, a latent size sdmi_set_latent_size refuses.
+ * sdmi_op_freeu (tests): x [n, c, h, w] = cat([h, hs]) with cx backbone channels, laid out as the engine keeps a block's input -- its precision's storage type, rows
+ * wider than c, at precision 0 with bf16 planes beside the fp32 copy where c % 32 == 0 -- through the launches the model runs (the filter where s != 1, the backbone
+ * where b != 1), back as y [n, c, h, w].  y_from_planes (may be NULL): h + m + l of the planes.  Returns 1 when the buffer had planes and y_from_planes (if given)
+ * was written, 0 when it had none and y_from_planes was left alone, a negative status on an error. */
+int sdmi_set_freeu(sdmi_ctx* ctx, int32_t version, float b1, float b2, float s1, float s2, double start, double end);
+int sdmi_get_freeu(sdmi_ctx* ctx, int32_t* version, float* b1, float* b2, float* s1, float* s2, double* start, double* end);
+int sdmi_freeu_plan(const sdmi_config* cfg, int32_t latent_h, int32_t latent_w, int32_t* out /* 12 x 5 */);
+int sdmi_op_freeu(sdmi_ctx* ctx, const float* x, int32_t n, int32_t c, int32_t h, int32_t w, int32_t cx, int32_t version, float b, float s, float* y,
+                  float* y_from_planes);
+
 /* ---- latent size per call, and the two-pass "hires fix" (no reference counterpart: its latent is hard-coded 4x64x64, stablediffusion/mod.rs:116;
  * DESIGN.md section 9d) ----
  * The weights do not depend on the picture size and the context caches nothing per size, so one context serves any size.  sdmi_config.latent_h / latent_w are
@@ -749,6 +782,8 @@ int sdmi_multi_set_ksampler(sdmi_multi* m, const sdmi_ksampler* ksampler);
 /* sdmi_set_guidance_rescale / sdmi_set_zero_snr on every device context: the statistic is per image, so sharding needs nothing else */
 int sdmi_multi_set_guidance_rescale(sdmi_multi* m, double phi);
 int sdmi_multi_set_zero_snr(sdmi_multi* m, int32_t on);
+/* sdmi_set_freeu on every device context (checked by each; a refusal leaves every context as it was): the edits are per sample, so sharding needs nothing else */
+int sdmi_multi_set_freeu(sdmi_multi* m, int32_t version, float b1, float b2, float s1, float s2, double start, double end);
 /* the contiguous global image range [begin, end) device `rank` of `n_ranks` samples (host only): the partition rule of
  * sdmi_sample_image_sharded, and of the one-process-per-GPU launcher (bench.py / sharding.py use the same rule) */
 int sdmi_shard_range(int32_t n_images, int32_t rank, int32_t n_ranks, int32_t* begin, int32_t* end);

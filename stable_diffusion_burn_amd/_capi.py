@@ -170,6 +170,11 @@ SIGNATURES = {
                                        C.c_uint64, C.c_uint64, _F, _F, _F, C.c_double, C.c_double, _F, _F]),
     "sdmi_multi_set_guidance_rescale": (C.c_int, [C.c_void_p, C.c_double]),
     "sdmi_multi_set_zero_snr": (C.c_int, [C.c_void_p, C.c_int32]),
+    "sdmi_set_freeu": (C.c_int, [_CTX, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_double, C.c_double]),
+    "sdmi_get_freeu": (C.c_int, [_CTX, _I32, _F, _F, _F, _F, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "sdmi_freeu_plan": (C.c_int, [C.POINTER(SdmiConfig), C.c_int32, C.c_int32, _I32]),
+    "sdmi_op_freeu": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _F, _F]),
+    "sdmi_multi_set_freeu": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_double, C.c_double]),
     "sdmi_set_latent_size": (C.c_int, [_CTX, C.c_int32, C.c_int32]),
     "sdmi_get_latent_size": (C.c_int, [_CTX, _I32, _I32]),
     "sdmi_resize_weights": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I32, _I32, C.POINTER(C.c_double), C.c_int32, _I32, _I32]),

@@ -2659,6 +2659,7 @@ void Engine::unet_prepare_rows(const float* ctx_packed, int nb, int t_max, const
     }
     const int mc = cfg_.model_channels, ed = 4 * mc, cd = cfg_.ctx_dim;
     us_.nb = nb; us_.t_max = t_max; us_.steps = S;
+    us_.window = window;
     us_.kv_len_host.assign(kv_len_host, kv_len_host + nb);
     auto own = [&](size_t bytes) { void* p = pool_.alloc(bytes); us_.owned.push_back(p); return p; };
     us_.kv_len_dev = (int*)own(nb * sizeof(int));
@@ -2764,6 +2765,121 @@ void Engine::set_control(const sdmi_control* c) {
 }
 
 // input_hint_block (cldm.py): eight 3x3 convolutions, SiLU after all but the last, fp32 at every precision.  u8 -> v / 255 with a zero 4th channel first.
+// ---- FreeU (include/sdmi.h "FreeU") ------------------------------------------------------------------------------------
+// THE block rule: keyed on the channel count of the backbone tensor entering output block i, as ComfyUI's FreeU nodes ship it (not on the resolution)
+void Engine::freeu_plan(int model_channels, int latent_h, int latent_w, int (&out)[60]) {
+    if (model_channels < 1) throw Error(SDMI_ERR_INVALID, "freeu_plan: model_channels must be positive");
+    check_latent_size(latent_h, latent_w);
+    const int c1 = model_channels, c2 = 2 * c1, c4 = 4 * c1;
+    const int cx[12] = {c4, c4, c4, c4, c4, c4, c4, c2, c2, c2, c1, c1};          // what the block below (or the middle block) hands up
+    const int cskip[12] = {c4, c4, c4, c4, c4, c2, c2, c2, c1, c1, c1, c1};       // what input block 11 - i saved
+    for (int i = 0; i < 12; ++i) {
+        const int level = 3 - i / 3;   // down-convolutions between the latent and the block's input (stride 2, pad 1: the size is halved, rounded up)
+        int h = latent_h, w = latent_w;
+        for (int l = 0; l < level; ++l) { h = (h + 1) / 2; w = (w + 1) / 2; }
+        int* o = out + 5 * i;
+        o[0] = cx[i] == c4 ? 1 : cx[i] == c2 ? 2 : 0;
+        o[1] = cx[i]; o[2] = cskip[i]; o[3] = h; o[4] = w;
+    }
+}
+
+void Engine::check_freeu(const FreeU& f) {
+    if (f.version < 0 || f.version > 2) throw Error(SDMI_ERR_INVALID, "freeu: version must be 0 (off), 1 or 2");
+    if (!f.version) return;
+    for (float v : {f.b1, f.b2, f.s1, f.s2})
+        if (!std::isfinite(v)) throw Error(SDMI_ERR_INVALID, "freeu: b1, b2, s1, s2 must be finite");
+    if (!(f.b1 > 0.f && f.b2 > 0.f)) throw Error(SDMI_ERR_INVALID, "freeu: b1 and b2 must be positive");
+    if (!(f.s1 >= 0.f && f.s2 >= 0.f)) throw Error(SDMI_ERR_INVALID, "freeu: s1 and s2 must not be negative");
+    if (!(f.start >= 0.0 && f.start <= f.end && f.end <= 1.0)) throw Error(SDMI_ERR_INVALID, "freeu: the step window must satisfy 0 <= start <= end <= 1");
+}
+
+void Engine::set_freeu(const FreeU& f) {
+    check_freeu(f);
+    if (!f.version) { freeu_ = FreeU{}; return; }
+    int plan[60];
+    freeu_plan(cfg_.model_channels, lat_h_, lat_w_, plan);
+    const int g = freeu_granule();
+    for (int i = 0; i < 12; ++i)
+        if (plan[5 * i] && (plan[5 * i + 1] % (2 * g) || plan[5 * i + 2] % g))
+            throw Error(SDMI_ERR_UNSUPPORTED, "freeu: output block " + std::to_string(i) + " joins " + std::to_string(plan[5 * i + 1]) + " backbone and " + std::to_string(plan[5 * i + 2]) +
+                                                  " skip channels; the kernels take half the former and the latter in multiples of " + std::to_string(g));
+    freeu_ = f;
+}
+
+void Engine::freeu_filter(const Act* const* cats, const int* cx, const float* s, int n_cats) {
+    FreeuFilter ff{};
+    ff.dt = edt();
+    double bytes = 0;
+    int planes = 0;
+    for (int i = 0; i < n_cats; ++i) {
+        if (s[i] == 1.0f) continue;
+        if (ff.n_seg == kFreeuMaxSegs) throw Error(SDMI_ERR_STATE, "freeu: more filtered skips than the segment table holds");
+        const Act hs = slice(*cats[i], cx[i], cats[i]->c - cx[i]);
+        if (!hs.p || hs.dt != edt() || hs.c % freeu_granule()) throw Error(SDMI_ERR_STATE, "freeu: a skip does not have the form the filter takes");
+        FreeuSeg& g = ff.seg[ff.n_seg++];
+        g.y = hs.p; g.y3 = hs.p3; g.n = hs.n; g.h = hs.h; g.w = hs.w; g.c = hs.c; g.ld = hs.stride(); g.ld3 = hs.ld3; g.k = s[i] - 1.0f;
+        planes += g.y3 ? 1 : 0;
+        bytes += (double)hs.rows() * hs.c * (edt() ? 6.0 : (g.y3 ? 18.0 : 12.0));   // read twice (the second time from L2), written once in every form
+    }
+    if (!ff.n_seg) return;
+    if (record_shapes_) ++choice_counts_["freeu_filter segs=" + std::to_string(ff.n_seg) + " planes=" + std::to_string(planes) + " dt=" + std::to_string(ff.dt)];
+    { ProfScope ps_o(this, PC_OTHER, 0, bytes); ps_o.set_tag("freeu_filter"); SDMI_HIP(launch_freeu_filter(ff, stream_)); }
+    count_kernel();
+}
+
+void Engine::freeu_backbone(const Act& cat, int cx, float b, int version) {
+    if (b == 1.0f) return;
+    const Act h = slice(cat, 0, cx / 2);
+    if (!h.p || h.dt != edt() || cx % 2 || h.c % freeu_granule()) throw Error(SDMI_ERR_STATE, "freeu: a backbone tensor does not have the form the kernel takes");
+    FreeuBackbone a{};
+    a.y = h.p; a.y3 = h.p3; a.n = h.n; a.hw = h.h * h.w; a.c = h.c; a.ld = h.stride(); a.ld3 = h.ld3; a.dt = edt(); a.version = version; a.b = b;
+    if (record_shapes_)
+        ++choice_counts_["freeu_backbone v" + std::to_string(version) + " rows=" + std::to_string(h.rows()) + " c=" + std::to_string(h.c) + " cx=" + std::to_string(cx) +
+                         " planes=" + std::to_string(a.y3 ? 1 : 0) + " dt=" + std::to_string(a.dt)];
+    const double es = edt() ? 2.0 : 4.0;
+    std::unique_ptr<Buf> mean;
+    if (version == 2) {
+        mean.reset(new Buf(this, (size_t)h.rows() * sizeof(float)));
+        { ProfScope ps_o(this, PC_OTHER, 0, (double)h.rows() * (cx * es + 4.0)); ps_o.set_tag("freeu_mean");
+          SDMI_HIP(launch_freeu_mean(cat.p, mean->f(), h.rows(), cx, cat.stride(), edt(), stream_)); }
+        count_kernel();
+        a.mean = mean->f();
+    }
+    { ProfScope ps_o(this, PC_OTHER, 0, (double)h.rows() * h.c * (edt() ? 4.0 : (a.y3 ? 14.0 : 8.0))); ps_o.set_tag("freeu_backbone");
+      SDMI_HIP(launch_freeu_backbone(a, stream_)); }
+    count_kernel();
+}
+
+bool Engine::op_freeu(float* parent, int n, int c, int h, int w, int ld, int cx, int version, float b, float s, float* parent3) {
+    if (n <= 0 || c <= 0 || h <= 0 || w <= 0 || cx <= 0 || cx >= c || ld < c) throw Error(SDMI_ERR_INVALID, "op_freeu: bad shape");
+    FreeU f; f.version = version; f.b1 = f.b2 = b; f.s1 = f.s2 = s;
+    check_freeu(f);
+    if (version < 1) throw Error(SDMI_ERR_INVALID, "op_freeu: version must be 1 or 2");
+    const int g = freeu_granule(), dt = edt();
+    if (cx % (2 * g) || (c - cx) % g || (ld * (dt ? 2 : 4)) % 16) throw Error(SDMI_ERR_UNSUPPORTED, "op_freeu: cx / 2 and c - cx must be multiples of " + std::to_string(g));
+    if (!freeu_filter_size_ok(h, w)) throw Error(SDMI_ERR_UNSUPPORTED, "op_freeu: the size is beyond what the filter kernel's tables hold");
+    const bool planes = !dt && plane_gemm(c, c) && ld % 32 == 0;   // (cx and c - cx are multiples of 32 here)
+    // the parent, as unet_run allocates the input of an output block; the cat is its first c columns
+    Act a = planes ? new_act3(n, h, w, ld, 3) : new_act(n, h, w, ld, dt);
+    if (dt) SDMI_HIP(launch_f32_to_bf16(parent, a.p, a.rows() * ld, stream_));
+    else {
+        SDMI_HIP(hipMemcpyAsync(a.p, parent, a.bytes(), hipMemcpyDeviceToDevice, stream_));
+        if (a.p3) SDMI_HIP(launch_split3_rows(parent, a.p3, a.rows(), ld, ld, a.ld3, stream_));
+    }
+    const Act cat = slice(a, 0, c);
+    Act catv = cat; catv.view = false;   // (slice refuses a view of a view; the cuts below are taken on the same rows)
+    const Act* cats[1] = {&catv};
+    freeu_filter(cats, &cx, &s, 1);
+    freeu_backbone(catv, cx, b, version);
+    if (dt) SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(a.p, parent, (int)a.rows(), ld, 1, 1, stream_));
+    else {
+        SDMI_HIP(hipMemcpyAsync(parent, a.p, a.bytes(), hipMemcpyDeviceToDevice, stream_));
+        if (a.p3 && parent3) SDMI_HIP(launch_join3_rows(a.p3, parent3, a.rows(), ld, a.ld3, ld, stream_));
+    }
+    release(a);
+    return planes;
+}
+
 Act Engine::control_hint_embed(const uint8_t* hint_rgb_dev, int n, int hint_h, int hint_w) {
     Range rng(this, "ControlNet hint");
     // one picture at a time, like the VAE encoder (encode_image_dev): the launches of a picture -- tiles, split-K, summation order -- do not depend on how many hints the
@@ -2911,6 +3027,14 @@ void Engine::unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bo
     if (controlled) control_run(x_nhwc, nb, step, ctl_r);
 
     const int nblk = (int)in_blocks_.size();
+    // a FreeU step: which output blocks take which pair of parameters is freeu_plan's to say; nothing below runs when none is left
+    const bool freeu = freeu_on(step);
+    int fplan[60];
+    if (freeu) {
+        if (nblk != 12) throw Error(SDMI_ERR_STATE, "freeu: the block rule is stated for 12 output blocks");
+        if (!freeu_filter_size_ok(H, W)) throw Error(SDMI_ERR_UNSUPPORTED, "freeu: the latent size in force is beyond what the filter kernel's tables hold");
+        freeu_plan(cfg_.model_channels, H, W, fplan);
+    }
     std::vector<Act> cats(nblk);
     for (int j = 0; j < nblk; ++j) {
         const UBlock& b = in_blocks_[j];
@@ -2970,10 +3094,21 @@ void Engine::unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bo
         count_kernel();
         for (auto& a : ctl_r) release(a);
     }
+    if (freeu) {
+        // every affected skip exists now (with the control's residuals in it): ONE launch filters them all.  The backbone halves follow block by block below.
+        const Act* fc[12]; int fcx[12]; float fs[12];
+        for (int i = 0; i < nblk; ++i) {
+            const int* pl = fplan + 5 * i;
+            if (pl[0] && (cats[i].c != pl[1] + pl[2] || cats[i].h != pl[3] || cats[i].w != pl[4])) throw Error(SDMI_ERR_STATE, "freeu: the block plan does not match the model");
+            fc[i] = &cats[i]; fcx[i] = pl[1]; fs[i] = pl[0] == 1 ? freeu_.s1 : pl[0] == 2 ? freeu_.s2 : 1.0f;
+        }
+        freeu_filter(fc, fcx, fs, nblk);
+    }
     Act last{};
     for (int i = 0; i < nblk; ++i) {
         const UBlock& b = out_blocks_[i];
         Range rb(this, "output_block " + std::to_string(i));
+        if (freeu && fplan[5 * i]) freeu_backbone(cats[i], fplan[5 * i + 1], fplan[5 * i] == 1 ? freeu_.b1 : freeu_.b2, freeu_.version);
         const bool up = b.kind == BK_RES_UP || b.kind == BK_RES_ST_UP;
         Act y;
         if (i + 1 < nblk) {

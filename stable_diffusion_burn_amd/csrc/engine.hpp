@@ -228,6 +228,17 @@ public:
     // the 13 residuals of the sticky hint (strength ignored) for x [n,4,h,w], t, context [n,T,cd]: NCHW fp32, back to back (device pointers)
     void control_residuals_dev(const float* x_nchw, int t, const float* context, int n, int T, float* out);
     size_t control_residual_elems(int n) const;   // floats control_residuals_dev writes
+    // FreeU (include/sdmi.h "FreeU"): sticky, like the control.  freeu_plan is THE block rule (sdmi_freeu_plan; unet_run reads it too):
+    // out[5 i ..] = group (0 none, 1: b1 / s1, 2: b2 / s2), cx, cskip, h, w of output block i.  check_freeu: SDMI_ERR_INVALID for what the header lists.
+    struct FreeU { int version = 0; float b1 = 1, b2 = 1, s1 = 1, s2 = 1; double start = 0, end = 1; };
+    static void freeu_plan(int model_channels, int latent_h, int latent_w, int (&out)[60]);
+    static void check_freeu(const FreeU& f);
+    void set_freeu(const FreeU& f);   // version 0 clears; SDMI_ERR_UNSUPPORTED for a model whose widths the kernels do not take -- the state in force stays
+    const FreeU& freeu() const { return freeu_; }
+    // tests (sdmi_op_freeu): parent [n h w][ld] fp32 on the device, columns [0, c) = cat([h, hs]) with cx backbone channels, the others the caller's filler -> the
+    // engine's storage type (+ planes at precision 0 where c and ld are multiples of 32), the model's launches, back into parent; parent3 (may be null): the joined
+    // planes.  Returns whether the buffer had planes.
+    bool op_freeu(float* parent, int n, int c, int h, int w, int ld, int cx, int version, float b, float s, float* parent3);
     // Autoencoder::encode_image (autoencoder/mod.rs:60-66): img [n,3,8h,8w] NCHW -> latent mean [n,4,h,w] NCHW (device pointers)
     void encode_image_dev(const float* img_nchw, int n, float* latent_nchw);
     void sample_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale,
@@ -563,6 +574,18 @@ private:
         if (!us_.eval_step.empty()) return control_step_on(ctrl_.start, ctrl_.end, us_.eval_step[(size_t)step], us_.call_steps);
         return control_step_on(ctrl_.start, ctrl_.end, step, us_.steps);
     }
+    // FreeU: is evaluation `step` of the call in flight inside the window (control_on's rule); the two edits on a block's input buffer `cat` = [cx backbone channels |
+    // skip channels]: segments for the one filter launch of a forward, and the backbone launches in front of the block
+    bool freeu_on(int step) const {
+        if (!freeu_.version) return false;
+        if (!us_.window) return true;
+        if (!us_.eval_step.empty()) return control_step_on(freeu_.start, freeu_.end, us_.eval_step[(size_t)step], us_.call_steps);
+        return control_step_on(freeu_.start, freeu_.end, step, us_.steps);
+    }
+    int freeu_granule() const { return bf16_ ? 64 : 32; }
+    void freeu_filter(const Act* const* cats, const int* cx, const float* s, int n_cats);   // the entries with s != 1, one launch (none without one)
+    void freeu_backbone(const Act& cat, int cx, float b, int version);
+    FreeU freeu_;
     void unet_release();
     void unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bool cfg_pair = false);
     void decode_one(const float* z_nhwc, int n, Act& img);
@@ -742,6 +765,7 @@ private:
         int* kv_len_dev = nullptr;
         std::vector<int> kv_len_host;
         std::vector<void*> owned;
+        bool window = true;                      // the call counts steps (the sampling entries); false: sdmi_unet_forward*, where the control and FreeU are simply on
         bool ctrl = false, ctrl_window = true;   // a controlled call: the control blocks' tables are prepared, hint_rows holds the hint embedding
         float* hint_rows = nullptr;              // [nb][h][w][mc] fp32: row block i = the embedding of hint (i mod n_images) mod n_hint
     } us_;

@@ -374,4 +374,23 @@ constexpr int kControlMaxSegs = 13;
 struct ControlAdd { ControlSeg seg[kControlMaxSegs]; int n_seg; int dt; float strength; };
 hipError_t launch_control_add(const ControlAdd& a, hipStream_t s);
 
+// ---- FreeU (k_freeu.hip) ------------------------------------------------------------------------------------------
+// ONE launch for every filtered skip of a UNet forward: segment i is the tensor y [n][h w][c] inside rows of ld elements (a skip slice of a cats buffer), each
+// (sample, channel) plane of it replaced by Fourier_filter(., threshold 1, scale 1 + k): v' = v + k / (h w) x (the sum of its <= 4 lowest Fourier modes; k_freeu.hip).
+//   dt 0: y fp32 and, where y3 != null, the three bf16 planes of the NEW value (ld3 bytes between rows), as launch_control_add writes them;
+//   dt 1: y bf16, fp32 arithmetic, one round to nearest even.
+// c % 32 == 0 (dt 0) / c % 64 == 0 (dt 1); every base and row stride a multiple of 16 bytes; freeu_filter_size_ok(h, w): the row and column tables fit the LDS.
+// Sums in a fixed order, no atomics: two runs give the same bits, and a sample's result does not depend on the batch it is in.
+struct FreeuSeg { void* y; void* y3; int n, h, w, c, ld, ld3; float k; };
+constexpr int kFreeuMaxSegs = 12;
+struct FreeuFilter { FreeuSeg seg[kFreeuMaxSegs]; int n_seg; int dt; };
+bool freeu_filter_size_ok(int h, int w);
+hipError_t launch_freeu_filter(const FreeuFilter& f, hipStream_t s);
+// version 2's map: mean[row] = the mean of the cx channels of row `row` of x (rows ld elements apart), fp32; cx % 4 == 0 (dt 0) / % 8 (dt 1)
+hipError_t launch_freeu_mean(const void* x, float* mean, long long rows, int cx, int ld, int dt, hipStream_t s);
+// y [n][hw][c] (c = cx / 2 channels inside rows of ld elements; the forms and rules of FreeuSeg) *= b (version 1), or *= (b - 1) m^ + 1 with
+// m^ = (mean - min) / (max - min) over the sample's hw values of `mean` [n][hw] (version 2; m^ = 0 where max == min)
+struct FreeuBackbone { void* y; void* y3; const float* mean; int n, hw, c, ld, ld3, dt, version; float b; };
+hipError_t launch_freeu_backbone(const FreeuBackbone& a, hipStream_t s);
+
 }  // namespace sdmi

@@ -204,6 +204,10 @@ public:
     void set_zero_snr(bool on) {
         for (int r = 0; r < size(); ++r) engine(r).set_zero_snr(on);
     }
+    // sdmi_multi_set_freeu: every context holds the same model, so the first one's refusal is everyone's
+    void set_freeu(const Engine::FreeU& f) {
+        for (int r = 0; r < size(); ++r) engine(r).set_freeu(f);
+    }
 
     long long broadcasts() const { return broadcasts_; }
 
@@ -337,6 +341,16 @@ int sdmi_multi_set_zero_snr(sdmi_multi* m, int32_t on) {
     return multi_guard([&] {
         if (!m) throw sdmi::Error(SDMI_ERR_INVALID, "null sdmi_multi");
         m->m->set_zero_snr(on != 0);
+    });
+}
+
+int sdmi_multi_set_freeu(sdmi_multi* m, int32_t version, float b1, float b2, float s1, float s2, double start, double end) {
+    return multi_guard([&] {
+        sdmi::Engine::FreeU f;
+        f.version = version; f.b1 = b1; f.b2 = b2; f.s1 = s1; f.s2 = s2; f.start = start; f.end = end;
+        sdmi::Engine::check_freeu(f);
+        if (!m) throw sdmi::Error(SDMI_ERR_INVALID, "null sdmi_multi");
+        m->m->set_freeu(f);
     });
 }
 

@@ -27,6 +27,8 @@
 //   * SDMI_GUIDANCE_RESCALE=phi (0 .. 1; unset: 0, off) and SDMI_ZERO_SNR=1 (no reference counterpart): CFG rescale
 //     (sdmi_set_guidance_rescale) and the schedule rescaled to zero terminal SNR (sdmi_set_zero_snr; needs SDMI_PREDICTION=v) -- what the 768-v models and most
 //     v-prediction fine-tunes are sampled with (phi = 0.7).
+//   * SDMI_FREEU=b1:b2:s1:s2[:version] (no reference counterpart; unset: off) switches FreeU on (sdmi_set_freeu) for every step: version 1
+//     (the default) or 2 (ComfyUI's FreeU_V2).  The paper's values for SD 1.4 are 1.2:1.4:0.9:0.2, for SD 2.1 1.1:1.2:0.9:0.2.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -190,6 +192,33 @@ int main(int argc, char** argv) {
         if (!std::strcmp(zs, "1")) zero_snr = 1;
         else if (*zs && std::strcmp(zs, "0")) { std::fprintf(stderr, "Error: SDMI_ZERO_SNR must be 0 or 1, got '%s'\n", zs); return 1; }
     }
+    // SDMI_FREEU: likewise
+    int32_t freeu_version = 0;
+    float freeu_p[4] = {1.f, 1.f, 1.f, 1.f};
+    if (const char* fu = std::getenv("SDMI_FREEU")) {
+        if (*fu) {
+            double v[5] = {0, 0, 0, 0, 1};
+            int got = 0;
+            const char* q = fu;
+            bool ok = true;
+            while (ok && got < 5) {
+                char* end = nullptr;
+                v[got] = std::strtod(q, &end);
+                if (end == q) { ok = false; break; }
+                ++got;
+                if (!*end) break;
+                if (*end != ':') { ok = false; break; }
+                q = end + 1;
+                if (got == 5) ok = false;
+            }
+            if (!ok || got < 4 || !(v[4] == 1 || v[4] == 2)) {
+                std::fprintf(stderr, "Error: SDMI_FREEU must be b1:b2:s1:s2[:version] with version 1 or 2, got '%s'\n", fu);
+                return 1;
+            }
+            for (int i = 0; i < 4; ++i) freeu_p[i] = (float)v[i];
+            freeu_version = (int32_t)v[4];
+        }
+    }
     if (zero_snr && prediction != 1) { std::fprintf(stderr, "Error: SDMI_ZERO_SNR=1 needs SDMI_PREDICTION=v (eps does not determine x0 where alphas_cumprod is 0)\n"); return 1; }
     if (zero_snr && has_ksampler) { std::fprintf(stderr, "Error: SDMI_ZERO_SNR=1 excludes SDMI_KSAMPLER (sigma_max is infinite)\n"); return 1; }
 
@@ -205,6 +234,7 @@ int main(int argc, char** argv) {
     if (sdmi_set_prediction(ctx, prediction) != SDMI_OK) die("Error setting the prediction kind");
     if (sdmi_set_guidance_rescale(ctx, guidance_rescale) != SDMI_OK) die("Error setting the guidance rescale");
     if (sdmi_set_zero_snr(ctx, zero_snr) != SDMI_OK) die("Error setting the zero-terminal-SNR schedule");
+    if (freeu_version && sdmi_set_freeu(ctx, freeu_version, freeu_p[0], freeu_p[1], freeu_p[2], freeu_p[3], 0.0, 1.0) != SDMI_OK) die("Error setting FreeU");
     const char* lora = std::getenv("SDMI_LORA");
     if (lora && *lora && sdmi_set_option(ctx, "keep_masters", "1") != SDMI_OK) die("Error setting keep_masters");
     if (model_type == "burn") {

@@ -620,6 +620,80 @@ int sdmi_control_step_on(double start, double end, int32_t step, int32_t n_steps
     return Engine::control_step_on(start, end, step, n_steps) ? 1 : 0;
 }
 
+// ---- FreeU -----------------------------------------------------------------------------------------------------------
+int sdmi_set_freeu(sdmi_ctx* ctx, int32_t version, float b1, float b2, float s1, float s2, double start, double end) {
+    return guarded([&] {
+        Engine::FreeU f;
+        f.version = version; f.b1 = b1; f.b2 = b2; f.s1 = s1; f.s2 = s2; f.start = start; f.end = end;
+        Engine::check_freeu(f);   // the argument errors first: they need no context
+        eng(ctx).set_freeu(f);
+    });
+}
+
+int sdmi_get_freeu(sdmi_ctx* ctx, int32_t* version, float* b1, float* b2, float* s1, float* s2, double* start, double* end) {
+    return guarded([&] {
+        const Engine::FreeU& f = eng(ctx).freeu();
+        if (version) *version = f.version;
+        if (b1) *b1 = f.b1;
+        if (b2) *b2 = f.b2;
+        if (s1) *s1 = f.s1;
+        if (s2) *s2 = f.s2;
+        if (start) *start = f.start;
+        if (end) *end = f.end;
+    });
+}
+
+int sdmi_freeu_plan(const sdmi_config* cfg, int32_t latent_h, int32_t latent_w, int32_t* out) {
+    return guarded([&] {
+        if (!cfg || !out) throw Error(SDMI_ERR_INVALID, "freeu_plan: null pointer");
+        int plan[60];
+        Engine::freeu_plan(cfg->model_channels, latent_h, latent_w, plan);
+        std::copy(plan, plan + 60, out);
+    });
+}
+
+int sdmi_op_freeu(sdmi_ctx* ctx, const float* x, int32_t n, int32_t c, int32_t h, int32_t w, int32_t cx, int32_t version, float b, float s, float* y,
+                  float* y_from_planes) {
+    bool planes = false;
+    const int st = guarded([&] {
+        Engine& e = eng(ctx);
+        if (!x || !y) throw Error(SDMI_ERR_INVALID, "op_freeu: null pointer");
+        if (n <= 0 || c <= 0 || h <= 0 || w <= 0 || cx <= 0 || cx >= c) throw Error(SDMI_ERR_INVALID, "op_freeu: bad shape");
+        // rows one granule wider than the tensor, the columns next to it NaN: whatever is written there shows
+        const int ld = c + (e.config().precision ? 64 : 32);
+        const size_t hw = (size_t)h * w, rows = (size_t)n * hw, pbytes = rows * ld * sizeof(float);
+        std::vector<float> xp((size_t)rows * ld, std::nanf(""));
+        for (int bi = 0; bi < n; ++bi)
+            for (int j = 0; j < c; ++j) {
+                const float* src = x + ((size_t)bi * c + j) * hw;
+                float* dst = xp.data() + (size_t)bi * hw * ld + j;
+                for (size_t i = 0; i < hw; ++i) dst[i * ld] = src[i];
+            }
+        std::vector<float> yp(rows * ld), yp3(y_from_planes ? rows * ld : 0);
+        Engine::Call call(e);
+        DevIn dpre(e, xp.data(), pbytes);
+        DevOut dout(e, yp.data(), pbytes);
+        SDMI_HIP(hipMemcpyAsync(dout.buf.p, dpre.buf.p, pbytes, hipMemcpyDeviceToDevice, e.stream()));
+        std::unique_ptr<DevOut> dout3;
+        if (y_from_planes) dout3.reset(new DevOut(e, yp3.data(), pbytes));
+        planes = e.op_freeu(dout.f(), n, c, h, w, ld, cx, version, b, s, dout3 ? dout3->f() : nullptr);
+        call.finish();
+        dout.fetch();
+        if (planes && dout3) dout3->fetch();
+        auto back = [&](const std::vector<float>& p, float* dst, const char* what) {
+            for (size_t r = 0; r < rows; ++r)
+                for (int j = c; j < ld; ++j)
+                    if (!std::isnan(p[r * ld + j])) throw Error(SDMI_ERR_STATE, std::string("op_freeu: a column next to the tensor was written (") + what + ")");
+            for (int bi = 0; bi < n; ++bi)
+                for (int j = 0; j < c; ++j)
+                    for (size_t i = 0; i < hw; ++i) dst[((size_t)bi * c + j) * hw + i] = p[((size_t)bi * hw + i) * ld + j];
+        };
+        back(yp, y, "fp32 / bf16");
+        if (planes && y_from_planes) back(yp3, y_from_planes, "planes");
+    });
+    return st != SDMI_OK ? st : (planes ? 1 : 0);
+}
+
 int sdmi_control_hint_embed(sdmi_ctx* ctx, const uint8_t* hint_rgb, int32_t n, int32_t hint_h, int32_t hint_w, float* out) {
     return guarded([&] {
         Engine& e = eng(ctx);

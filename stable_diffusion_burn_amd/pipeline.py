@@ -109,6 +109,18 @@ def control_step_on(start: float, end: float, step: int, n_steps: int) -> bool:
     return bool(r)
 
 
+def freeu_plan(cfg, latent_h: int, latent_w: int) -> list:
+    """THE block rule of FreeU (sdmi_freeu_plan, host only, no GPU): for each of the 12 output blocks of a model with cfg.model_channels at
+    latent_h x latent_w, (group, cx, cskip, h, w) -- group 0: untouched, 1: (b1, s1), 2: (b2, s2); cx backbone and cskip skip channels of the h x w concatenation."""
+    lib = load_library()
+    c = SdmiConfig()
+    check(lib.sdmi_default_config(C.byref(c)))
+    c.model_channels = int(cfg.model_channels)
+    out = (C.c_int32 * 60)()
+    check(lib.sdmi_freeu_plan(C.byref(c), int(latent_h), int(latent_w), out))
+    return [tuple(int(v) for v in out[5 * i:5 * i + 5]) for i in range(12)]
+
+
 def control_residual_shapes(model_channels: int) -> list:
     """[(channels, log2 of the downscale)] of the 13 ControlNet residuals: the 12 input blocks' outputs, then the middle block's."""
     mc = model_channels
@@ -1226,6 +1238,40 @@ class StableDiffusion:
         models trained with zero terminal SNR are usually sampled at."""
         check(self._lib.sdmi_set_guidance_rescale(self._ctx, float(phi)))
 
+    def set_freeu(self, b1=1.0, b2=1.0, s1=1.0, s2=1.0, version: int = 1, start: float = 0.0, end: float = 1.0) -> None:
+        """FreeU (sdmi_set_freeu), sticky: in front of the output blocks whose backbone input has 4 x model_channels channels (blocks 0..6)
+        its first half is scaled by b1 and the low frequencies of the skip by s1; b2 / s2 where it has 2 x model_channels (blocks 7..9).  version 2 is ComfyUI's
+        FreeU_V2 (the backbone factor follows the normalised channel mean).  start / end: the step window of a sampling call, as a control's.  set_freeu(None)
+        clears; all four parameters at 1 run what ran before.  The paper's values: SD 1.4 (1.2, 1.4, 0.9, 0.2), SD 2.1 (1.1, 1.2, 0.9, 0.2)."""
+        if b1 is None:
+            check(self._lib.sdmi_set_freeu(self._ctx, 0, 1.0, 1.0, 1.0, 1.0, 0.0, 1.0))
+            return
+        check(self._lib.sdmi_set_freeu(self._ctx, int(version), float(b1), float(b2), float(s1), float(s2), float(start), float(end)))
+
+    def get_freeu(self):
+        """The FreeU state in force (sdmi_get_freeu): None when off, else {"version", "b1", "b2", "s1", "s2", "start", "end"}."""
+        v = C.c_int32()
+        p = [C.c_float() for _ in range(4)]
+        st, en = C.c_double(), C.c_double()
+        check(self._lib.sdmi_get_freeu(self._ctx, C.byref(v), *(C.byref(q) for q in p), C.byref(st), C.byref(en)))
+        if not v.value:
+            return None
+        return {"version": int(v.value), "b1": p[0].value, "b2": p[1].value, "s1": p[2].value, "s2": p[3].value, "start": st.value, "end": en.value}
+
+    def op_freeu(self, x, cx: int, version: int, b: float, s: float, planes: bool = False):
+        """tests (sdmi_op_freeu): x [n, c, h, w] = cat([h, hs]) with cx backbone channels, through the model's FreeU launches in the engine's own layout -> y.
+        planes = True: (y, what the bf16 planes of the buffer hold, or None where the buffer had none)."""
+        x = _f32(x)
+        if x.ndim != 4:
+            raise ValueError(f"op_freeu: x must be [n, c, h, w], got {x.shape}")
+        n, c, h, w = x.shape
+        y = np.empty_like(x)
+        y3 = np.empty_like(x) if planes else None
+        r = self._lib.sdmi_op_freeu(self._ctx, _fp(x), n, c, h, w, int(cx), int(version), float(b), float(s), _fp(y), None if y3 is None else _fp(y3))
+        if r < 0:
+            check(r)
+        return (y, y3 if r == 1 else None) if planes else y
+
     def set_zero_snr(self, on: bool = True) -> None:
         """Sample on the loaded schedule rescaled to zero terminal SNR (sdmi_set_zero_snr; rescale_zero_snr); False restores the loaded table bit for bit.
         Sticky, before or after the weights.  Needs set_prediction("v"); sigma-schedule samplers are refused on such a table."""
@@ -1717,6 +1763,13 @@ class MultiStableDiffusion:
     def set_zero_snr(self, on: bool = True) -> None:
         """StableDiffusion.set_zero_snr on every device (sdmi_multi_set_zero_snr)."""
         check(self._lib.sdmi_multi_set_zero_snr(self._m, 1 if on else 0))
+
+    def set_freeu(self, b1=1.0, b2=1.0, s1=1.0, s2=1.0, version: int = 1, start: float = 0.0, end: float = 1.0) -> None:
+        """StableDiffusion.set_freeu on every device (sdmi_multi_set_freeu): the edits are per sample, sharding changes nothing.  set_freeu(None) clears."""
+        if b1 is None:
+            check(self._lib.sdmi_multi_set_freeu(self._m, 0, 1.0, 1.0, 1.0, 1.0, 0.0, 1.0))
+            return
+        check(self._lib.sdmi_multi_set_freeu(self._m, int(version), float(b1), float(b2), float(s1), float(s2), float(start), float(end)))
 
     def schedule(self) -> np.ndarray:
         """StableDiffusion.schedule of device 0 (every device holds the same table)."""
