@@ -899,6 +899,32 @@ int sdmi_op_geglu(sdmi_ctx* ctx, const float* proj, int32_t rows, int32_t hidden
  * the others. No mask. out [n,nq,n_state]. */
 int sdmi_op_qkv_attention_ragged(sdmi_ctx* ctx, const float* q, const float* k, const float* v, const int32_t* kv_len,
                                  int32_t n, int32_t nq, int32_t nk, int32_t n_state, int32_t n_head, float* out);
+/* qkv_attention on strided and packed VIEWS (no reference counterpart; for tests).  The model never hands attention dense tensors where it matters: the
+ * UNet's self attention and every CLIP layer read q, k and v out of ONE buffer written by one GEMM (row stride 3C, bases at +0 / +C / +2C, batch stride
+ * rows * 3C), cross attention reads K and V from the per-call context buffers.  This entry runs the operator the same way: q [n,nq,n_state] and
+ * k, v [n,nk,n_state] arrive dense, are brought to the device exactly as sdmi_qkv_attention brings them (fp32 at precision 0 and whenever a mask is
+ * given, bf16 otherwise, q pre-scaled where the engine's convention says so) and are scattered into parent buffers [n][rows][ld] at columns
+ * [off, off + n_state); every other cell of a parent holds in_fill (NaN in the tests).  The batch stride is rows * ld.  packed = 1: q, k and v are
+ * slices of one parent (equal ld and rows, disjoint columns); 0: three parents.  The engine then calls the routine the model calls with these
+ * pointers, row strides and batch strides.  mask, mask_ld as sdmi_qkv_attention; kv_len as sdmi_op_qkv_attention_ragged, or NULL.
+ * Output: the result goes to rows [0, nq) and columns [out_off, out_off + n_state) of every sample of a parent [n][out_rows][out_ld]; the caller
+ * passes that parent PREFILLED as fp32 and gets the whole of it back (through the call's storage type: bf16 at precision >= 1 without a mask), so
+ * the cells around the slice are the caller's to judge.  out_planes = 1 (precision 0, a fused head dim, n_state a multiple of 32): the kernels'
+ * plane-writing epilogue, joined back (exact) -- a dense output only (out_ld = n_state, out_off = 0, out_rows = nq).
+ * SDMI_ERR_INVALID, on the host before anything is allocated or launched: ld < off + n_state, rows below nq / nk, packed slices that overlap or
+ * differ in ld / rows, an output slice that leaves its parent, a strided plane output, and any ld or off that is no multiple of 16 bytes (4 fp32 /
+ * 8 bf16 elements: the kernels load 16 bytes at a time). */
+typedef struct sdmi_attn_view {
+    int32_t q_ld, q_off, q_rows;
+    int32_t k_ld, k_off, k_rows;
+    int32_t v_ld, v_off, v_rows;
+    int32_t packed;
+    float in_fill;
+    int32_t out_ld, out_off, out_rows, out_planes;
+} sdmi_attn_view;
+int sdmi_op_qkv_attention_view(sdmi_ctx* ctx, const float* q, const float* k, const float* v, const float* mask, int32_t mask_ld,
+                               const int32_t* kv_len, int32_t n, int32_t nq, int32_t nk, int32_t n_state, int32_t n_head, sdmi_attn_view view,
+                               float* parent);
 /* The resampler of the hires fix on its own (csrc/k_resize.hip; no reference counterpart): x [n,4,h,w] -> out [n,4,out_h,out_w] by the tables of
  * sdmi_resize_weights(mode, antialias), applied as f32: the horizontal pass, then the vertical one, taps summed in ascending order (bit-identical run to
  * run); an axis whose size does not change is skipped.  Any positive sizes. */

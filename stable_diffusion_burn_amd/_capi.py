@@ -60,6 +60,13 @@ class SdmiOpView(C.Structure):
                 ("in_planes", C.c_int32), ("out_planes", C.c_int32)]
 
 
+class SdmiAttnView(C.Structure):
+    """sdmi_attn_view: where q, k, v and the result of an attention call sit inside wider parent buffers (sdmi_op_qkv_attention_view; tests)"""
+    _fields_ = [("q_ld", C.c_int32), ("q_off", C.c_int32), ("q_rows", C.c_int32), ("k_ld", C.c_int32), ("k_off", C.c_int32), ("k_rows", C.c_int32),
+                ("v_ld", C.c_int32), ("v_off", C.c_int32), ("v_rows", C.c_int32), ("packed", C.c_int32), ("in_fill", C.c_float),
+                ("out_ld", C.c_int32), ("out_off", C.c_int32), ("out_rows", C.c_int32), ("out_planes", C.c_int32)]
+
+
 class SdmiSampler(C.Structure):
     """sdmi_sampler: the sampler choice of a context (sdmi_set_sampler)"""
     _fields_ = [("kind", C.c_int32), ("reserved0", C.c_int32), ("eta", C.c_double), ("noise_seed", C.c_uint64), ("image_base", C.c_int64),
@@ -248,6 +255,7 @@ SIGNATURES = {
     "sdmi_op_geglu_forward": (C.c_int, [_CTX, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, _F]),
     "sdmi_op_geglu": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F]),
     "sdmi_op_qkv_attention_ragged": (C.c_int, [_CTX, _F, _F, _F, _I32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),
+    "sdmi_op_qkv_attention_view": (C.c_int, [_CTX, _F, _F, _F, _F, C.c_int32, _I32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, SdmiAttnView, _F]),
     "sdmi_op_timestep_embedding": (C.c_int, [_CTX, C.c_int32, C.c_int32, _F]),
     "sdmi_op_timestep_embedding_f": (C.c_int, [_CTX, C.c_double, C.c_int32, _F]),
     "sdmi_set_option": (C.c_int, [_CTX, C.c_char_p, C.c_char_p]),

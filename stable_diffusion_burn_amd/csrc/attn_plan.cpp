@@ -3,6 +3,7 @@
 #include "attn_plan.hpp"
 
 #include <algorithm>
+#include <string>
 
 #include "error.hpp"
 
@@ -105,6 +106,26 @@ AttnPlan plan_attention(const AttnPlanIn& p, const AttnPlanOpts& o) {
     const bool on_split = !p.bf16 && !p.has_mask && o.attn_split && p.rows_aligned && attn_split_head_dim(d, o.attn_d64) && !(d == 64 && o.attn_d64 == 2 && d64_stays_on_flash(p, o));
     const int kv_splits = plan_kv_splits(p, o, on_split);
     return on_split ? plan_split(p, o, kv_splits) : plan_flash(p, kv_splits);
+}
+
+void check_attention_view(const AttnViewIn& v) {
+    if (v.n <= 0 || v.nq <= 0 || v.nk <= 0 || v.n_state <= 0) throw Error(SDMI_ERR_INVALID, "attention view: bad shape");
+    const int unit = v.bf16 ? 8 : 4;   // elements in 16 bytes
+    auto slice = [&](const AttnViewSlice& s, int need_rows, const char* what) {
+        if (s.off < 0 || s.ld <= 0 || (long long)s.off + v.n_state > s.ld) throw Error(SDMI_ERR_INVALID, std::string("attention view: ") + what + " leaves its parent (need 0 <= off, off + n_state <= ld)");
+        if (s.rows < need_rows) throw Error(SDMI_ERR_INVALID, std::string("attention view: ") + what + " has fewer parent rows than the operand");
+        if (s.ld % unit || s.off % unit) throw Error(SDMI_ERR_INVALID, std::string("attention view: ") + what + ": ld and off must be multiples of 16 bytes");
+    };
+    slice(v.q, v.nq, "q");
+    slice(v.k, v.nk, "k");
+    slice(v.v, v.nk, "v");
+    slice(v.out, v.nq, "the output");
+    if (v.packed) {
+        if (v.q.ld != v.k.ld || v.q.ld != v.v.ld || v.q.rows != v.k.rows || v.q.rows != v.v.rows) throw Error(SDMI_ERR_INVALID, "attention view: packed q, k and v share one parent (equal ld and rows)");
+        auto apart = [&](const AttnViewSlice& a, const AttnViewSlice& b) { return a.off + v.n_state <= b.off || b.off + v.n_state <= a.off; };
+        if (!apart(v.q, v.k) || !apart(v.q, v.v) || !apart(v.k, v.v)) throw Error(SDMI_ERR_INVALID, "attention view: packed slices overlap");
+    }
+    if (v.out_planes && (v.out.ld != v.n_state || v.out.off || v.out.rows != v.nq)) throw Error(SDMI_ERR_INVALID, "attention view: the plane output is dense (out_ld = n_state, out_off = 0, out_rows = nq)");
 }
 
 }  // namespace sdmi

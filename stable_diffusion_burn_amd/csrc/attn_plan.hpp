@@ -71,4 +71,21 @@ struct AttnPlan {
 
 AttnPlan plan_attention(const AttnPlanIn& in, const AttnPlanOpts& o);   // throws Error
 
+// Where an attention call's operands and result lie inside wider parent buffers (tests: sdmi_op_qkv_attention_view, which feeds Engine::attention the way the
+// model does -- q, k, v as column slices of one packed [n][rows][3C] buffer, or of buffers of their own -- instead of dense [n][rows][C] tensors).  A slice is the
+// columns [off, off + n_state) of a parent [n][rows][ld]: ld elements between rows, rows * ld between samples.
+struct AttnViewSlice { int ld, off, rows; };
+struct AttnViewIn {
+    int n, nq, nk, n_state;
+    int bf16;               // storage type of the parents: 0 fp32, 1 bf16
+    AttnViewSlice q, k, v;
+    bool packed;            // q, k and v are slices of ONE parent (equal ld and rows, disjoint columns)
+    AttnViewSlice out;      // the output slice: nq rows per sample
+    bool out_planes;        // the result leaves as three bf16 planes (Engine::attention's o3), joined back: a dense output only
+};
+// SDMI_ERR_INVALID (thrown) for a view no launch may see: a slice that leaves its parent (ld < off + n_state, rows below the operand's), packed slices that
+// overlap or disagree about their parent, a strided plane output, and any ld or off that is no multiple of 16 bytes -- the kernels load 16 bytes at a time
+// and plan_attention knows of the row strides only rows_aligned.  Host-only, like the planner.
+void check_attention_view(const AttnViewIn& v);
+
 }  // namespace sdmi

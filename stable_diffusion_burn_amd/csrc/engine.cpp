@@ -3937,6 +3937,90 @@ void Engine::qkv_attention_dev(const float* q, const float* k, const float* v, c
               kv_len_dev, kv_len_host, mask, mask_ld, 0);
 }
 
+void Engine::check_qkv_attention_view(const sdmi_attn_view& view, bool has_mask, int mask_ld, const int* kv_len_host, int n, int nq, int nk, int n_state,
+                                      int n_head) const {
+    if (n <= 0 || nq <= 0 || nk <= 0 || n_state <= 0 || n_head <= 0 || n_state % n_head) throw Error(SDMI_ERR_INVALID, "qkv_attention_view: bad shape");
+    if (has_mask && mask_ld < nk) throw Error(SDMI_ERR_INVALID, "qkv_attention_view: mask_ld < nk");
+    if (has_mask && kv_len_host) throw Error(SDMI_ERR_INVALID, "qkv_attention_view: a mask or kv_len, not both");
+    if (kv_len_host)
+        for (int b = 0; b < n; ++b)
+            if (kv_len_host[b] < 1 || kv_len_host[b] > nk) throw Error(SDMI_ERR_INVALID, "qkv_attention_view: kv_len entries must lie in 1 .. nk");
+    AttnViewIn in{};
+    in.n = n; in.nq = nq; in.nk = nk; in.n_state = n_state; in.bf16 = (bf16_ && !has_mask) ? 1 : 0;
+    in.q = {view.q_ld, view.q_off, view.q_rows}; in.k = {view.k_ld, view.k_off, view.k_rows}; in.v = {view.v_ld, view.v_off, view.v_rows};
+    in.packed = view.packed != 0; in.out = {view.out_ld, view.out_off, view.out_rows}; in.out_planes = view.out_planes != 0;
+    check_attention_view(in);
+}
+
+// The operands take qkv_attention_dev's way to the device (the same conversions in the same order on the dense tensors), then are copied row by row into
+// parents full of in_fill; attention() gets the slices' bases, row strides and batch strides.
+void Engine::op_qkv_attention_view(const float* q, const float* k, const float* v, const float* mask, int mask_ld, const int* kv_len_host, int n, int nq, int nk,
+                                   int n_state, int n_head, const sdmi_attn_view& view, float* parent) {
+    check_qkv_attention_view(view, mask != nullptr, mask_ld, kv_len_host, n, nq, nk, n_state, n_head);
+    const int dt = (bf16_ && !mask) ? 1 : 0, dh = n_state / n_head;
+    const size_t es = dt ? 2 : 4;
+    std::unique_ptr<Buf> kl;
+    const int* kv_len_dev = nullptr;
+    if (kv_len_host) {
+        kl.reset(new Buf(this, (size_t)n * sizeof(int)));
+        SDMI_HIP(hipMemcpyAsync(kl->p, kv_len_host, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream_));
+        kv_len_dev = reinterpret_cast<const int*>(kl->p);
+    }
+    const long long qe = (long long)n * nq * n_state, ke = (long long)n * nk * n_state;
+    std::unique_ptr<Buf> qh, kh, vh;
+    if (dt) {   // precision >= 1: as qkv_attention_dev converts them
+        qh.reset(new Buf(this, qe * 2)); kh.reset(new Buf(this, ke * 2)); vh.reset(new Buf(this, ke * 2));
+        if (q_prescaled(1, dh)) SDMI_HIP(launch_f32_to_bf16_scaled(q, qh->p, qe, attn_bf16_q_scale(dh), stream_));
+        else SDMI_HIP(launch_f32_to_bf16(q, qh->p, qe, stream_));
+        SDMI_HIP(launch_f32_to_bf16(k, kh->p, ke, stream_));
+        SDMI_HIP(launch_f32_to_bf16(v, vh->p, ke, stream_));
+        q = qh->f(); k = kh->f(); v = vh->f();
+    }
+    // in_fill in the parents' storage type (bf16: round to nearest even, a NaN stays one)
+    uint32_t fill32;
+    std::memcpy(&fill32, &view.in_fill, 4);
+    const uint16_t fill16 = (fill32 & 0x7FFFFFFFu) > 0x7F800000u ? (uint16_t)((fill32 >> 16) | 0x40) : (uint16_t)((fill32 + 0x7FFFu + ((fill32 >> 16) & 1u)) >> 16);
+    auto new_parent = [&](int ld, int rows) {
+        const size_t elems = (size_t)n * rows * ld;
+        std::unique_ptr<Buf> b(new Buf(this, elems * es));
+        if (dt) SDMI_HIP(hipMemsetD16Async(b->p, fill16, elems, stream_));
+        else SDMI_HIP(hipMemsetD32Async(b->p, (int)fill32, elems, stream_));
+        return b;
+    };
+    auto scatter = [&](const float* dense, int used, Buf& par, int ld, int off, int rows) {   // -> the slice's base
+        float* base = adv(par.f(), off, dt);
+        for (int b = 0; b < n; ++b)
+            SDMI_HIP(hipMemcpy2DAsync(adv(base, (long long)b * rows * ld, dt), (size_t)ld * es, adv(dense, (long long)b * used * n_state, dt), (size_t)n_state * es,
+                                      (size_t)n_state * es, (size_t)used, hipMemcpyDeviceToDevice, stream_));
+        return base;
+    };
+    std::unique_ptr<Buf> pq = new_parent(view.q_ld, view.q_rows), pk, pv;
+    if (!view.packed) { pk = new_parent(view.k_ld, view.k_rows); pv = new_parent(view.v_ld, view.v_rows); }
+    const float* qs = scatter(q, nq, *pq, view.q_ld, view.q_off, view.q_rows);
+    const float* ks = scatter(k, nk, view.packed ? *pq : *pk, view.k_ld, view.k_off, view.k_rows);
+    const float* vs = scatter(v, nk, view.packed ? *pq : *pv, view.v_ld, view.v_off, view.v_rows);
+    const long long q_bs = (long long)view.q_rows * view.q_ld, k_bs = (long long)view.k_rows * view.k_ld, v_bs = (long long)view.v_rows * view.v_ld;
+    const long long o_bs = (long long)view.out_rows * view.out_ld;
+    if (view.out_planes) {   // the kernels' plane-writing epilogue, joined back (dense: check_attention_view); what cannot write planes is plan_attention's to refuse
+        Buf o3(this, (size_t)n * nq * (n_state / 32) * 192 + 256);
+        attention(qs, view.q_ld, q_bs, ks, view.k_ld, k_bs, vs, view.v_ld, v_bs, nullptr, view.out_ld, o_bs, n, nq, nk, n_head, dh, kv_len_dev, kv_len_host,
+                  mask, mask_ld, dt, o3.p, q_prescaled(dt, dh));
+        SDMI_HIP(launch_join3_rows(o3.p, parent, (long long)n * nq, n_state, (long long)(n_state / 32) * 192, n_state, stream_));
+        return;
+    }
+    if (dt) {
+        const long long pe = (long long)n * o_bs;
+        Buf y(this, pe * 2);
+        SDMI_HIP(launch_f32_to_bf16(parent, y.p, pe, stream_));
+        attention(qs, view.q_ld, q_bs, ks, view.k_ld, k_bs, vs, view.v_ld, v_bs, adv(y.f(), view.out_off, 1), view.out_ld, o_bs, n, nq, nk, n_head, dh,
+                  kv_len_dev, kv_len_host, nullptr, 0, 1, nullptr, q_prescaled(1, dh));
+        SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(y.p, parent, (int)((long long)n * view.out_rows), view.out_ld, 1, 1, stream_));
+        return;
+    }
+    attention(qs, view.q_ld, q_bs, ks, view.k_ld, k_bs, vs, view.v_ld, v_bs, parent + view.out_off, view.out_ld, o_bs, n, nq, nk, n_head, dh, kv_len_dev,
+              kv_len_host, mask, mask_ld, 0, nullptr, false);
+}
+
 // =============================================================================
 // operator-level entry points (device pointers, reference layouts)
 // =============================================================================

@@ -289,6 +289,12 @@ public:
     // kv_len_host: null, or a HOST array [n] of per-sample key counts (1 .. nk; the CFG batch's cross attention, Engine::attention's kv_len)
     void qkv_attention_dev(const float* q, const float* k, const float* v, const float* mask, int mask_ld, int n,
                            int nq, int nk, int n_state, int n_head, float* out, const int* kv_len_host = nullptr);
+    // tests (sdmi_op_qkv_attention_view): qkv_attention_dev with q, k, v scattered into parents [n][rows][ld] full of view.in_fill and the result written into
+    // a slice of parent [n][out_rows][out_ld] (fp32 on the device, prefilled by the caller, returned whole) -- attention() sees the strides the model gives it
+    void op_qkv_attention_view(const float* q, const float* k, const float* v, const float* mask, int mask_ld, const int* kv_len_host, int n, int nq, int nk,
+                               int n_state, int n_head, const sdmi_attn_view& view, float* parent);
+    // every host-side check of that call (check_attention_view, attn_plan.hpp, in the storage type the call would run in): allocates and launches nothing
+    void check_qkv_attention_view(const sdmi_attn_view& view, bool has_mask, int mask_ld, const int* kv_len_host, int n, int nq, int nk, int n_state, int n_head) const;
 
     // operator-level (device pointers, reference layouts)
     void op_group_norm(const float* x, const float* gamma, const float* beta, int n, int c, int h, int w, int groups,

@@ -1517,6 +1517,26 @@ int sdmi_op_qkv_attention_ragged(sdmi_ctx* ctx, const float* q, const float* k, 
     });
 }
 
+int sdmi_op_qkv_attention_view(sdmi_ctx* ctx, const float* q, const float* k, const float* v, const float* mask, int32_t mask_ld, const int32_t* kv_len,
+                               int32_t n, int32_t nq, int32_t nk, int32_t n_state, int32_t n_head, sdmi_attn_view view, float* parent) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (!q || !k || !v || !parent) throw Error(SDMI_ERR_INVALID, "qkv_attention_view: null pointer");
+        e.check_qkv_attention_view(view, mask != nullptr, mask_ld, kv_len, n, nq, nk, n_state, n_head);   // every refusal before anything is allocated or launched
+        const size_t qb = (size_t)n * nq * n_state * sizeof(float), kb = (size_t)n * nk * n_state * sizeof(float);
+        const size_t pbytes = (size_t)n * view.out_rows * view.out_ld * sizeof(float);
+        Engine::Call call(e);
+        DevIn dq(e, q, qb), dk(e, k, kb), dv(e, v, kb);
+        Engine::Buf dm(&e, mask ? (size_t)nq * mask_ld * sizeof(float) : 256);
+        if (mask) SDMI_HIP(hipMemcpyAsync(dm.p, mask, (size_t)nq * mask_ld * sizeof(float), hipMemcpyHostToDevice, e.stream()));
+        DevOut dout(e, parent, pbytes);
+        SDMI_HIP(hipMemcpyAsync(dout.buf.p, parent, pbytes, hipMemcpyHostToDevice, e.stream()));
+        e.op_qkv_attention_view(dq.f(), dk.f(), dv.f(), mask ? dm.f() : nullptr, mask_ld, kv_len, n, nq, nk, n_state, n_head, view, dout.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
 // ---- operator-level entry points -----------------------------------------------------------
 int sdmi_op_group_norm(sdmi_ctx* ctx, const float* x, const float* gamma, const float* beta, int32_t n, int32_t c,
                        int32_t h, int32_t w, int32_t n_group, float eps, int32_t fuse_silu, float* out) {

@@ -24,7 +24,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _capi
-from ._capi import SdmiAttnPlan, SdmiConfig, SdmiControl, SdmiError, SdmiHires, SdmiInpaint, SdmiKSampler, SdmiOpView, SdmiPromptOpts, SdmiSampler, check, load_library
+from ._capi import SdmiAttnPlan, SdmiAttnView, SdmiConfig, SdmiControl, SdmiError, SdmiHires, SdmiInpaint, SdmiKSampler, SdmiOpView, SdmiPromptOpts, SdmiSampler, check, load_library
 
 def mpk_list(path) -> list:
     """[(dump name, shape, file offset)] of a Burn .mpk record, parsed by the C++ reader (host only, no GPU)."""
@@ -1665,6 +1665,34 @@ class StableDiffusion:
         out = np.empty_like(q)
         check(self._lib.sdmi_op_qkv_attention_ragged(self._ctx, _fp(q), _fp(k), _fp(v), None if kl is None else kl.ctypes.data_as(C.POINTER(C.c_int32)),
                                                      n, nq, nk, c, n_head, _fp(out)))
+        return out
+
+    def op_qkv_attention_view(self, q, k, v, mask, n_head: int, kv_len=None, *, q_view, k_view, v_view, packed, parent, out_off, out_planes=0, in_fill=float("nan")):
+        """qkv_attention (with kv_len: qkv_attention_ragged) the way the model calls it (sdmi_op_qkv_attention_view; tests): q [n,nq,c], k,v [n,nk,c] are
+        scattered into parents [n][rows][ld] full of in_fill at columns [off, off + c) -- q_view / k_view / v_view = (ld, off, rows); packed: the three are
+        slices of one parent -- and the result is written to rows [0, nq), columns [out_off, out_off + c) of every sample of `parent` [n, out_rows, out_ld]
+        (prefilled by the caller; not modified).  Returns the whole parent as the engine left it.  out_planes = 1 (a dense parent): through the kernels'
+        plane-writing epilogue."""
+        q, k, v = _f32(q), _f32(k), _f32(v)
+        n, nq, c = q.shape
+        nk = k.shape[1]
+        if k.shape != (n, nk, c) or v.shape != (n, nk, c):
+            raise ValueError("qkv_attention_view: q/k/v shapes disagree")
+        m = None if mask is None else _f32(mask)
+        if m is not None and (m.ndim != 2 or m.shape[0] < nq):
+            raise SdmiError(-1, f"qkv_attention_view: mask must be [>= nq = {nq}, >= nk = {nk}], got {m.shape}")
+        kl = None
+        if kv_len is not None:
+            kl = np.ascontiguousarray(kv_len, dtype=np.int32)
+            if kl.shape != (n,):
+                raise ValueError(f"qkv_attention_view: kv_len must have shape ({n},), got {kl.shape}")
+        out = np.array(parent, dtype=np.float32, order="C", copy=True)
+        if out.ndim != 3 or out.shape[0] != n:
+            raise ValueError(f"qkv_attention_view: parent must be [{n}, out_rows, out_ld], got {out.shape}")
+        view = SdmiAttnView(*q_view, *k_view, *v_view, int(bool(packed)), in_fill, out.shape[2], out_off, out.shape[1], out_planes)
+        self._view_call(out, lambda: check(self._lib.sdmi_op_qkv_attention_view(
+            self._ctx, _fp(q), _fp(k), _fp(v), None if m is None else _fp(m), 0 if m is None else m.shape[1],
+            None if kl is None else kl.ctypes.data_as(C.POINTER(C.c_int32)), n, nq, nk, c, n_head, view, _fp(out))))
         return out
 
 

@@ -7,6 +7,12 @@
 //                            ("f32|bf16 [mask] [planes] [unaligned] d<D> n<N> h<H> q<NQ> k<NK>:", the words setting has_mask, planes_out and
 //                            !rows_aligned), planned under every option variant and compared with the line.  No grid, no form census:
 //                            tests/golden/attn_plan_masked_cases.txt, the shapes of tests/test_attention_mask_gpu.py
+//   attn_plan --views <f>    answers the lines of <f>, one line of output each (tests/test_attention_views_cpu.py writes them from tests/attn_view_cases.py):
+//                            "plan <bf16> <mask> <planes> <d> <n> <heads> <nq> <nk> <attn_split> <attn_bf16> <attn_bf16_variant> <attn_pack_tail> <attn_kv_splits>
+//                            <attn_kv_prefer8> <attn_d64>" -> "<kernel> <waves> <q_rows> <kv_splits>" (kernel: unfused / flash / split / bf16) or "E<status>";
+//                            "view <bf16> <n> <nq> <nk> <n_state> <packed> <ld off rows of q, k, v, out> <out_planes>" -> "ok" or "E<status>" (check_attention_view)
+//
+// Every run without --replay / --views first puts check_attention_view through its own accept and refuse cases (view_selftest below).
 //
 // One line per (storage, d, n, heads, nq, nk), one token per option variant in the order of variants() below; equal neighbours are
 // folded into "token*count".  A token is
@@ -143,8 +149,104 @@ static int replay(const char* path) {
     return bad ? 1 : 0;
 }
 
+// --views: see the head of this file
+static int views(const char* path) {
+    std::ifstream f(path);
+    if (!f) { std::fprintf(stderr, "cannot read %s\n", path); return 2; }
+    std::string a;
+    int ln = 0;
+    while (std::getline(f, a)) {
+        ++ln;
+        if (a.empty() || a[0] == '#') continue;
+        std::istringstream is(a);
+        std::string kind;
+        is >> kind;
+        std::vector<int> x;
+        for (int t; is >> t;) x.push_back(t);
+        try {
+            if (kind == "plan" && x.size() == 15) {
+                const AttnPlanIn in = make_in(x[0] != 0, x[3], x[4], x[5], x[6], x[7], x[1] != 0, x[2] != 0);
+                AttnPlanOpts o;
+                o.attn_split = x[8]; o.attn_bf16 = x[9]; o.attn_bf16_variant = x[10]; o.attn_pack_tail = x[11]; o.attn_kv_splits = x[12]; o.attn_kv_prefer8 = x[13]; o.attn_d64 = x[14];
+                const AttnPlan p = plan_attention(in, o);
+                static const char* names[] = {"unfused", "flash", "split", "bf16"};
+                std::printf("%s %d %d %d\n", names[(int)p.kernel], p.waves, p.q_rows, p.kv_splits);
+            } else if (kind == "view" && x.size() == 19) {
+                AttnViewIn v{};
+                v.bf16 = x[0]; v.n = x[1]; v.nq = x[2]; v.nk = x[3]; v.n_state = x[4]; v.packed = x[5] != 0;
+                v.q = {x[6], x[7], x[8]}; v.k = {x[9], x[10], x[11]}; v.v = {x[12], x[13], x[14]}; v.out = {x[15], x[16], x[17]}; v.out_planes = x[18] != 0;
+                check_attention_view(v);
+                std::printf("ok\n");
+            } else {
+                std::fprintf(stderr, "line %d is no case: %s\n", ln, a.c_str());
+                return 2;
+            }
+        } catch (const Error& e) {
+            std::printf("E%d\n", e.status);
+        }
+    }
+    return 0;
+}
+
+// check_attention_view on views it must take and views it must refuse (SDMI_ERR_INVALID), at both element sizes: the model's packed [n][T][3C] buffer, gaps
+// and filler rows, three parents with different strides; every way a slice can leave its parent, overlap a neighbour or miss a 16-byte boundary
+static int view_selftest() {
+    int bad = 0;
+    auto expect = [&](const AttnViewIn& v, bool ok, const char* what) {
+        int st = 0;
+        try { check_attention_view(v); } catch (const Error& e) { st = e.status; }
+        if ((st == 0) != ok || (!ok && st != SDMI_ERR_INVALID)) { std::fprintf(stderr, "check_attention_view: %s (bf16=%d): status %d\n", what, v.bf16, st); ++bad; }
+    };
+    for (int bf16 = 0; bf16 < 2; ++bf16) {
+        const int g = bf16 ? 8 : 4, c = 80, nq = 100, nk = 520;
+        AttnViewIn self{};
+        self.n = 2; self.nq = nq; self.nk = nq; self.n_state = c; self.bf16 = bf16; self.packed = true;
+        self.q = {3 * c, 0, nq}; self.k = {3 * c, c, nq}; self.v = {3 * c, 2 * c, nq}; self.out = {c, 0, nq};
+        expect(self, true, "the model's packed buffer");
+        AttnViewIn planes = self;
+        planes.out_planes = true;
+        expect(planes, true, "the model's packed buffer, plane output");
+        AttnViewIn pk = self;
+        pk.nk = nk;
+        pk.q = {3 * c + 3 * g, g, nk + 5}; pk.k = {3 * c + 3 * g, c + 2 * g, nk + 5}; pk.v = {3 * c + 3 * g, 2 * c + 3 * g, nk + 5}; pk.out = {c + 2 * g, g, nq + 3};
+        expect(pk, true, "packed with gaps");
+        AttnViewIn ap = pk;
+        ap.packed = false;
+        ap.q = {c + g, 0, nq + 1}; ap.k = {c + 2 * g, 2 * g, nk + 2}; ap.v = {c + 3 * g, g, nk + 3}; ap.out = {c + 4 * g, g, nq + 2};
+        expect(ap, true, "three parents");
+        AttnViewIn same = ap;       // slices of different parents may share columns
+        same.k = same.v;
+        expect(same, true, "three parents, equal slices");
+        AttnViewIn t;
+        t = ap; t.q.off = 2 * g; expect(t, false, "q: ld < off + n_state");
+        t = ap; t.k.ld = c - g; expect(t, false, "k: ld < n_state");
+        t = ap; t.v.off = -g; expect(t, false, "v: negative off");
+        t = ap; t.q.rows = nq - 1; expect(t, false, "q: rows < nq");
+        t = ap; t.k.rows = nk - 1; expect(t, false, "k: rows < nk");
+        t = ap; t.v.rows = 0; expect(t, false, "v: no rows");
+        t = ap; t.out.off = t.out.ld - c + g; expect(t, false, "out: leaves its parent");
+        t = ap; t.out.rows = nq - 1; expect(t, false, "out: rows < nq");
+        t = ap; t.q.ld += g / 2; expect(t, false, "q: ld off 16 bytes");
+        t = ap; t.k.off = g / 2; expect(t, false, "k: off off 16 bytes");
+        t = ap; t.v.ld += 1; expect(t, false, "v: ld off 16 bytes");
+        t = ap; t.out.off = g / 2; expect(t, false, "out: off off 16 bytes");
+        t = ap; t.out.ld += g / 2; expect(t, false, "out: ld off 16 bytes");
+        t = ap; t.out_planes = true; expect(t, false, "a strided plane output");
+        t = pk; t.k.off = t.q.off + c - g; expect(t, false, "packed: q and k overlap");
+        t = pk; t.v.off = t.k.off; expect(t, false, "packed: k and v coincide");
+        t = pk; t.k.ld += g; expect(t, false, "packed: different ld");
+        t = pk; t.v.rows += 1; expect(t, false, "packed: different rows");
+        t = ap; t.n = 0; expect(t, false, "no samples");
+        t = ap; t.q.ld = 0x7FFFFFF8; t.q.off = 0x7FFFFFF0; expect(t, false, "off + n_state past INT_MAX");
+    }
+    if (bad) std::fprintf(stderr, "%d view cases went wrong\n", bad);
+    return bad;
+}
+
 int main(int argc, char** argv) {
     if (argc == 3 && std::string(argv[1]) == "--replay") return replay(argv[2]);
+    if (argc == 3 && std::string(argv[1]) == "--views") return views(argv[2]);
+    if (view_selftest()) return 2;
     std::ostringstream os;
     os << "# written by the planner's first form, Engine::attention's and the launchers' rules moved out verbatim; never regenerated since\n";
     for (int bf16 = 0; bf16 < 2; ++bf16) {
