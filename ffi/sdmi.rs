@@ -68,6 +68,24 @@ pub struct SdmiControl {
     pub reserved: [i64; 4],
 }
 
+/// `sdmi_ip_adapter` (include/sdmi.h "IP-Adapter"): the sticky image prompt of a context with a loaded adapter.  Exactly one of `tokens`
+/// (`[n_sets, T_ip, token_dim]`, projected outside) and `embeds` (`[n_sets, T_ip / T, embed_dim]`, projected by image_proj) is non-null; `neg_tokens` (may be null:
+/// image_proj(0)) is what the unconditional half of a CFG batch reads.  HOST pointers, copied by the call.
+#[repr(C)]
+pub struct SdmiIpAdapter {
+    pub tokens: *const c_float,
+    pub embeds: *const c_float,
+    pub neg_tokens: *const c_float,
+    pub n_sets: i32,
+    pub t_ip: i32,
+    pub token_dim: i32,
+    pub embed_dim: i32,
+    pub scale: c_float,
+    pub start: f64,
+    pub end: f64,
+    pub reserved: [i64; 4],
+}
+
 /// `sdmi_sampler` (include/sdmi.h "sampler choice"): kind 0 DDIM(eta) -- eta 0 = the reference's sampler = plain Euler, eta 1 =
 /// Euler-ancestral --, 1 DPM-Solver++(2M), 2 PLMS.
 #[repr(C)]
@@ -225,6 +243,23 @@ extern "C" {
     fn sdmi_load_control_safetensors(ctx: *mut c_void, path: *const c_char) -> c_int;
     fn sdmi_control_ready(ctx: *mut c_void) -> c_int;
     fn sdmi_set_control(ctx: *mut c_void, control: *const SdmiControl) -> c_int;
+    fn sdmi_ip_adapter_load_safetensors(ctx: *mut c_void, path: *const c_char) -> c_int;
+    fn sdmi_ip_adapter_check_safetensors(cfg: *const SdmiConfig, path: *const c_char, d: *mut i32, t: *mut i32) -> c_int;
+    fn sdmi_ip_adapter_set_weights(ctx: *mut c_void, proj_w: *const c_float, proj_b: *const c_float, norm_g: *const c_float, norm_b: *const c_float, d: i32, t: i32,
+                                   wk: *const *const c_float, wv: *const *const c_float) -> c_int;
+    fn sdmi_ip_adapter_ready(ctx: *mut c_void) -> c_int;
+    fn sdmi_ip_adapter_dims(ctx: *mut c_void, d: *mut i32, t: *mut i32) -> c_int;
+    fn sdmi_ip_adapter_clear(ctx: *mut c_void) -> c_int;
+    fn sdmi_ip_image_tokens(ctx: *mut c_void, embeds: *const c_float, n: i32, d: i32, out: *mut c_float) -> c_int;
+    fn sdmi_set_ip_adapter(ctx: *mut c_void, adapter: *const SdmiIpAdapter) -> c_int;
+    fn sdmi_set_ip_adapter_file(ctx: *mut c_void, embeds_path: *const c_char, scale: c_float, start: c_double, end: c_double) -> c_int;
+    fn sdmi_get_ip_adapter(ctx: *mut c_void, out: *mut SdmiIpAdapter) -> c_int;
+    fn sdmi_ip_adapter_key(cfg: *const SdmiConfig, ctx_index: i32, which: i32, out: *mut c_char, capacity: usize, needed: *mut usize, j: *mut i32, c: *mut i32) -> c_int;
+    fn sdmi_op_ip_attention(ctx: *mut c_void, q: *const c_float, k_ip: *const c_float, v_ip: *const c_float, o_text: *const c_float, scale: *const c_float, n: i32,
+                            nq: i32, t_ip: i32, n_state: i32, n_head: i32, planes: i32, out: *mut c_float) -> c_int;
+    fn sdmi_ip_kv_size(ctx: *mut c_void, n: i32, cfg_pair: i32) -> i64;
+    fn sdmi_ip_kv(ctx: *mut c_void, n: i32, cfg_pair: i32, out: *mut c_float) -> c_int;
+    fn sdmi_multi_set_ip_adapter(m: *mut c_void, adapter: *const SdmiIpAdapter) -> c_int;
     fn sdmi_control_step_on(start: c_double, end: c_double, step: i32, n_steps: i32) -> c_int;
     fn sdmi_control_hint_embed(ctx: *mut c_void, hint_rgb: *const u8, n: i32, hint_h: i32, hint_w: i32, out: *mut c_float) -> c_int;
     fn sdmi_control_residuals_size(ctx: *mut c_void, n: i32) -> i64;
@@ -493,6 +528,30 @@ impl StableDiffusionMi355 {
     /// Whether every tensor of the ControlNet group is set (`sdmi_control_ready`).
     pub fn control_ready(&self) -> bool {
         unsafe { sdmi_control_ready(self.ctx) == 1 }
+    }
+
+    /// Load an IP-Adapter in h94's `ip-adapter_sd15.safetensors` layout (`sdmi_ip_adapter_load_safetensors`).
+    pub fn load_ip_adapter_safetensors(&mut self, path: &str) -> Result<(), Box<dyn Error>> {
+        let p = std::ffi::CString::new(path)?;
+        if unsafe { sdmi_ip_adapter_load_safetensors(self.ctx, p.as_ptr()) } != 0 {
+            return Err(last_error().into());
+        }
+        Ok(())
+    }
+
+    /// The image prompt of every later forward / sampling call (`sdmi_set_ip_adapter`, sticky): `embeds` = `n_img` CLIP image embeddings of width `embed_dim` back to
+    /// back (one set, concatenated along the token axis), `t` = the adapter's tokens per picture; `None` clears.
+    pub fn set_ip_adapter(&mut self, prompt: Option<(&[f32], i32, i32, i32, f32, f64, f64)>) -> Result<(), Box<dyn Error>> {
+        let st = match prompt {
+            None => unsafe { sdmi_set_ip_adapter(self.ctx, std::ptr::null()) },
+            Some((embeds, n_img, embed_dim, t, scale, start, end)) => {
+                if embeds.len() != (n_img as usize) * (embed_dim as usize) { return Err("set_ip_adapter: embeds must hold n_img * embed_dim values".into()); }
+                let a = SdmiIpAdapter { tokens: std::ptr::null(), embeds: embeds.as_ptr(), neg_tokens: std::ptr::null(), n_sets: 1, t_ip: n_img * t, token_dim: 0, embed_dim,
+                                        scale, start, end, reserved: [0; 4] };
+                unsafe { sdmi_set_ip_adapter(self.ctx, &a) }
+            }
+        };
+        if st != 0 { Err(last_error().into()) } else { Ok(()) }
     }
 
     /// The control of every later forward / sampling call (`sdmi_set_control`, sticky): `hint` = `n_hint` pictures `[hint_h, hint_w, 3]` u8 back to back,

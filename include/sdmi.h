@@ -468,6 +468,75 @@ int sdmi_freeu_plan(const sdmi_config* cfg, int32_t latent_h, int32_t latent_w, 
 int sdmi_op_freeu(sdmi_ctx* ctx, const float* x, int32_t n, int32_t c, int32_t h, int32_t w, int32_t cx, int32_t version, float b, float s, float* y,
                   float* y_from_planes);
 
+/* ---- IP-Adapter (SD v1; no reference counterpart) ----------------------------------------------------------
+ * Ye et al., "IP-Adapter", as diffusers' IPAdapterAttnProcessor runs it: an image prompt enters every cross attention of the UNet through a SECOND attention on
+ * the same queries,     a = Attn(q, K_text, V_text) + scale * Attn(q, K_ip, V_ip),     K_ip = tokens Wk_i^T, V_ip = tokens Wv_i^T (no bias),
+ * with the same heads and d_head^-1/2 score scale and a softmax of its own over the T_ip image tokens; attn2's output projection then runs on a as before.  The text
+ * attention launches exactly as without an adapter; one small launch per cross attention (csrc/k_ipattn.hip) adds the image term to its output.  The ControlNet's
+ * transformers are not adapted.  K_ip / V_ip are made once per call, next to the text K / V; they and the adapter's arithmetic are fp32 at every precision.
+ *   tokens = image_proj(embeds) = LayerNorm(reshape(Linear(embeds), [T, ctx_dim])): embeds [n, D] is the CALLER's CLIP image embedding (the image encoder is out of
+ *   scope, like the ControlNet hint preprocessor); D = 1024 and T = 4 for the published SD 1.5 adapters; eps 1e-5.  Several pictures concatenate along the token axis:
+ *   T_ip = T * pictures, 1 <= T_ip <= 64.  The unconditional half of a CFG batch reads image_proj(0) (diffusers' zeros_like negative) unless negative tokens are given.
+ * Out of scope: the image encoder, the "plus" / "full-face" / FaceID Resampler (project outside and pass tokens), several adapters at once, per-region image prompts.
+ *
+ * The adapter's weights (not a weight group: they arrive whole, through one of two calls, before or after sdmi_finalize_weights):
+ * sdmi_ip_adapter_load_safetensors: ONE file in h94's ip-adapter_sd15.safetensors layout, F32 / F16 / BF16, through the mapped reader, widened on the device:
+ *   image_proj.proj.weight [T ctx_dim, D], image_proj.proj.bias, image_proj.norm.weight, image_proj.norm.bias [ctx_dim],
+ *   ip_adapter.<j>.to_k_ip.weight / ip_adapter.<j>.to_v_ip.weight [C, ctx_dim], j odd, counting the cross attentions in diffusers' processor order -- down blocks
+ *   (UNet input blocks 1, 2, 4, 5, 7, 8 -> 1 .. 11), up blocks (output blocks 3 .. 11 -> 13 .. 29), then mid (31); sdmi_ip_adapter_key is the rule
+ *   (tests/golden/ip_adapter_keys.txt).  The rule is written from the published code and UNPINNED against a real file: none exists offline.
+ *   Refused with the key named, before anything is uploaded (SDMI_ERR_WEIGHTS; the adapter in force stays): a missing or extra layer, a shape that does not match the
+ *   model, a dtype other than the three; SDMI_ERR_UNSUPPORTED: image_proj.latents / image_proj.layers.* (the "plus" Resampler), a .bin / pickle file.
+ * sdmi_ip_adapter_set_weights: the same tensors as HOST fp32 arrays in the file's layouts; wk / wv: 16 pointers, in the engine's order (sdmi_ip_adapter_key's
+ *   ctx_index).  SDMI_ERR_INVALID: a null pointer, T < 1, T > 64, D < 32 or D % 32 != 0.  SDMI_ERR_UNSUPPORTED: a model whose UNet head widths are not 40 / 64 / 80 / 160.
+ * sdmi_ip_adapter_ready: 1 when an adapter is loaded, else 0.  sdmi_ip_adapter_dims: its D and T (SDMI_ERR_STATE without one).  sdmi_ip_adapter_clear: frees the weights and clears the setting.
+ * sdmi_ip_image_tokens: image_proj alone, embeds [n, D] -> out [n, T, ctx_dim] (host pointers).  SDMI_ERR_STATE without an adapter, SDMI_ERR_INVALID: D is not the adapter's.
+ * sdmi_ip_adapter_key (host only): cross attention ctx_index (0 .. 15: the input blocks' six, the middle block's, the output blocks' nine) of a model with cfg's
+ *   model_channels -> the file key of its to_k_ip (which 0) / to_v_ip (which 1) weight, *j its index in the file and *c its width C; text by the sdmi_checkpoint_key
+ *   convention (capacity / needed). */
+typedef struct sdmi_ip_adapter {
+    const float* tokens;       /* HOST [n_sets, T_ip, token_dim], or NULL when embeds is given */
+    const float* embeds;       /* HOST [n_sets, T_ip / T, embed_dim], or NULL: projected by image_proj; exactly one of tokens / embeds */
+    const float* neg_tokens;   /* HOST [n_sets, T_ip, token_dim] or NULL: image_proj(0) per picture */
+    int32_t n_sets;            /* image i of either half of a CFG batch reads token set i mod n_sets */
+    int32_t T_ip;              /* image tokens per set, 1 .. 64 */
+    int32_t token_dim;         /* width of tokens / neg_tokens: must be ctx_dim (ignored when neither is given) */
+    int32_t embed_dim;         /* width of embeds: must be the adapter's D (ignored without embeds) */
+    float scale;               /* finite; 0: the plain forward */
+    double start, end;         /* the step window, sdmi_control's rule (sdmi_control_step_on); sdmi_unet_forward*: the adapter is simply on */
+    int64_t reserved[4];
+} sdmi_ip_adapter;
+/* sdmi_set_ip_adapter: sticky, like sdmi_set_control; it applies to every later sdmi_unet_forward* / sdmi_sample_* / sdmi_img2img_* / sdmi_hires_* / sdmi_inpaint_*
+ * call, controlled or not, and to each device of a multi-context.  NULL clears the setting (the weights stay).  With no adapter, a cleared setting, scale == 0 or on a
+ * step outside the window a forward runs the launches and gives the bits it gave before.  SDMI_ERR_STATE: no adapter is loaded.  SDMI_ERR_INVALID -- the setting in
+ * force stays --: both or neither of tokens / embeds, n_sets < 1, T_ip < 1, T_ip not a multiple of T with embeds, token_dim != ctx_dim, embed_dim != D, a non-finite
+ * scale, start > end or a bound outside [0, 1].  SDMI_ERR_UNSUPPORTED: T_ip > 64.
+ * sdmi_set_ip_adapter_file: sdmi_set_ip_adapter with embeds read from the tensor "image_embeds" [n, D] (F32 / F16 / BF16) of a .safetensors file: one set of n pictures
+ * (what the sdmi_sample twin's SDMI_IP_EMBEDS uses).  SDMI_ERR_WEIGHTS: no such tensor, or another dtype.
+ * sdmi_get_ip_adapter: the setting in force (pointers NULL); returns 1 when one is set, 0 when none (out untouched).
+ * sdmi_op_ip_attention (tests): the operator alone on dense HOST tensors -- q, o_text [n, nq, n_state], k_ip, v_ip [n, T_ip, n_state], scale [n] -- brought to the
+ * device in the context's storage type as sdmi_op_qkv_attention_view does (a bf16 q carries the score scale, as the model's), through the launch the model runs, out
+ * [n, nq, n_state] fp32.  planes != 0 (precision 0 only, n_state % 32 == 0): O_text goes in as the three bf16 planes and out is what they hold afterwards.
+ * sdmi_ip_kv (tests): the per-call K_ip / V_ip a call with n images would hoist (cfg_pair != 0: 2 n batch rows, the unconditional half first), per cross attention
+ * i = 0 .. 15 the blocks K_i, V_i [nb, T_ip, C_i] back to back; sdmi_ip_kv_size: floats in all. */
+int sdmi_ip_adapter_load_safetensors(sdmi_ctx* ctx, const char* path);
+/* host only, needs no context: every check sdmi_ip_adapter_load_safetensors makes, against a model with cfg's model_channels and ctx_dim; *D / *T (may be NULL): the file's */
+int sdmi_ip_adapter_check_safetensors(const sdmi_config* cfg, const char* path, int32_t* D, int32_t* T);
+int sdmi_ip_adapter_set_weights(sdmi_ctx* ctx, const float* proj_w, const float* proj_b, const float* norm_g, const float* norm_b, int32_t D, int32_t T,
+                                const float* const* wk, const float* const* wv);
+int sdmi_ip_adapter_ready(sdmi_ctx* ctx);
+int sdmi_ip_adapter_dims(sdmi_ctx* ctx, int32_t* D, int32_t* T);
+int sdmi_ip_adapter_clear(sdmi_ctx* ctx);
+int sdmi_ip_image_tokens(sdmi_ctx* ctx, const float* embeds, int32_t n, int32_t D, float* out);
+int sdmi_set_ip_adapter(sdmi_ctx* ctx, const sdmi_ip_adapter* adapter);
+int sdmi_set_ip_adapter_file(sdmi_ctx* ctx, const char* embeds_path, float scale, double start, double end);
+int sdmi_get_ip_adapter(sdmi_ctx* ctx, sdmi_ip_adapter* out);
+int sdmi_ip_adapter_key(const sdmi_config* cfg, int32_t ctx_index, int32_t which, char* out, size_t capacity, size_t* needed, int32_t* j, int32_t* c);
+int sdmi_op_ip_attention(sdmi_ctx* ctx, const float* q, const float* k_ip, const float* v_ip, const float* o_text, const float* scale, int32_t n, int32_t nq,
+                         int32_t T_ip, int32_t n_state, int32_t n_head, int32_t planes, float* out);
+int64_t sdmi_ip_kv_size(sdmi_ctx* ctx, int32_t n, int32_t cfg_pair);
+int sdmi_ip_kv(sdmi_ctx* ctx, int32_t n, int32_t cfg_pair, float* out);
+
 /* ---- latent size per call, and the two-pass "hires fix" (no reference counterpart: its latent is hard-coded 4x64x64, stablediffusion/mod.rs:116;
  * DESIGN.md section 9d) ----
  * The weights do not depend on the picture size and the context caches nothing per size, so one context serves any size.  sdmi_config.latent_h / latent_w are
@@ -784,6 +853,10 @@ int sdmi_multi_set_guidance_rescale(sdmi_multi* m, double phi);
 int sdmi_multi_set_zero_snr(sdmi_multi* m, int32_t on);
 /* sdmi_set_freeu on every device context (checked by each; a refusal leaves every context as it was): the edits are per sample, so sharding needs nothing else */
 int sdmi_multi_set_freeu(sdmi_multi* m, int32_t version, float b1, float b2, float s1, float s2, double start, double end);
+/* sdmi_set_ip_adapter on every device context (each holds its own copy of the adapter's weights, loaded through sdmi_multi_ctx).  Every context checks the
+ * setting before any takes it, so a refusal, such as SDMI_ERR_STATE from a context without an adapter, leaves every context as it was.
+ * Each shard numbers its own images from 0 when it picks a token set, as a control's hints are picked. */
+int sdmi_multi_set_ip_adapter(sdmi_multi* m, const sdmi_ip_adapter* adapter);
 /* the contiguous global image range [begin, end) device `rank` of `n_ranks` samples (host only): the partition rule of
  * sdmi_sample_image_sharded, and of the one-process-per-GPU launcher (bench.py / sharding.py use the same rule) */
 int sdmi_shard_range(int32_t n_images, int32_t rank, int32_t n_ranks, int32_t* begin, int32_t* end);

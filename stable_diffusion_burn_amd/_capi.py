@@ -79,6 +79,12 @@ class SdmiKSampler(C.Structure):
                 ("noise_seed", C.c_uint64), ("image_base", C.c_int64), ("reserved", C.c_int64 * 4)]
 
 
+class SdmiIpAdapter(C.Structure):
+    """sdmi_ip_adapter (include/sdmi.h "IP-Adapter")"""
+    _fields_ = [("tokens", C.POINTER(C.c_float)), ("embeds", C.POINTER(C.c_float)), ("neg_tokens", C.POINTER(C.c_float)), ("n_sets", C.c_int32), ("T_ip", C.c_int32),
+                ("token_dim", C.c_int32), ("embed_dim", C.c_int32), ("scale", C.c_float), ("start", C.c_double), ("end", C.c_double), ("reserved", C.c_int64 * 4)]
+
+
 class SdmiControl(C.Structure):
     """sdmi_control: the sticky ControlNet state of a context (sdmi_set_control)"""
     _fields_ = [("hint_rgb", C.POINTER(C.c_uint8)), ("n_hint", C.c_int32), ("hint_h", C.c_int32), ("hint_w", C.c_int32), ("strength", C.c_double),
@@ -182,6 +188,21 @@ SIGNATURES = {
     "sdmi_freeu_plan": (C.c_int, [C.POINTER(SdmiConfig), C.c_int32, C.c_int32, _I32]),
     "sdmi_op_freeu": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _F, _F]),
     "sdmi_multi_set_freeu": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_double, C.c_double]),
+    "sdmi_ip_adapter_load_safetensors": (C.c_int, [_CTX, C.c_char_p]),
+    "sdmi_ip_adapter_check_safetensors": (C.c_int, [C.POINTER(SdmiConfig), C.c_char_p, _I32, _I32]),
+    "sdmi_ip_adapter_set_weights": (C.c_int, [_CTX, _F, _F, _F, _F, C.c_int32, C.c_int32, C.POINTER(_F), C.POINTER(_F)]),
+    "sdmi_ip_adapter_ready": (C.c_int, [_CTX]),
+    "sdmi_ip_adapter_dims": (C.c_int, [_CTX, _I32, _I32]),
+    "sdmi_ip_adapter_clear": (C.c_int, [_CTX]),
+    "sdmi_ip_image_tokens": (C.c_int, [_CTX, _F, C.c_int32, C.c_int32, _F]),
+    "sdmi_set_ip_adapter": (C.c_int, [_CTX, C.POINTER(SdmiIpAdapter)]),
+    "sdmi_set_ip_adapter_file": (C.c_int, [_CTX, C.c_char_p, C.c_float, C.c_double, C.c_double]),
+    "sdmi_get_ip_adapter": (C.c_int, [_CTX, C.POINTER(SdmiIpAdapter)]),
+    "sdmi_ip_adapter_key": (C.c_int, [C.POINTER(SdmiConfig), C.c_int32, C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), _I32, _I32]),
+    "sdmi_op_ip_attention": (C.c_int, [_CTX, _F, _F, _F, _F, _F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F]),
+    "sdmi_ip_kv_size": (C.c_int64, [_CTX, C.c_int32, C.c_int32]),
+    "sdmi_ip_kv": (C.c_int, [_CTX, C.c_int32, C.c_int32, _F]),
+    "sdmi_multi_set_ip_adapter": (C.c_int, [C.c_void_p, C.POINTER(SdmiIpAdapter)]),
     "sdmi_set_latent_size": (C.c_int, [_CTX, C.c_int32, C.c_int32]),
     "sdmi_get_latent_size": (C.c_int, [_CTX, _I32, _I32]),
     "sdmi_resize_weights": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I32, _I32, C.POINTER(C.c_double), C.c_int32, _I32, _I32]),

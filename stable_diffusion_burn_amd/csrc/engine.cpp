@@ -283,6 +283,11 @@ void Engine::destroy() noexcept {
     emb_bank_ = nullptr; emb_rows_ = 0; embeddings_.clear();
     if (ctrl_.hint_dev) (void)hipFree(ctrl_.hint_dev);   // a control still set: its hint pictures
     ctrl_ = Control{};
+    if (ip_.tokens) (void)hipFree(ip_.tokens);
+    if (ip_.neg) (void)hipFree(ip_.neg);
+    ip_ = IpState{};
+    for (void* p : ipw_.allocs) (void)hipFree(p);
+    ipw_ = IpWeights{};
     for (void* p : weight_allocs_) (void)hipFree(p);
     for (auto& p : prof_pending_) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (hipEvent_t e : prof_free_) (void)hipEventDestroy(e);
@@ -1635,6 +1640,7 @@ void Engine::abort_call() noexcept {
     (void)hipStreamSynchronize(stream_);
     try {
         us_ = UNetState{};
+        ip_live_ = false;
         pool_.free_since(call_mark_);
     } catch (...) {}
 }
@@ -2498,6 +2504,7 @@ void Engine::spatial_transformer(const SpatialW& w, const Act& x, Act& y) {
             const long long cbs = (long long)us_.t_max * C;
             attention(q.f(), C, (long long)hw * C, us_.kc.at(w.ctx_index), C, cbs, us_.vc.at(w.ctx_index), C, cbs, a.f(),
                       C, (long long)hw * C, nb, hw, us_.t_max, heads, d, us_.kv_len_dev, us_.kv_len_host.data(), nullptr, 0, -1, nullptr, q_prescaled(edt(), d));
+            ip_attention(w, q.f(), a.f(), nullptr, nb, hw, heads, d);   // IP-Adapter: + the image term, in front of the quantisation
             quantize(av, aq);
             gemm_fp8(aq, w.attn2.out, C, h.p, C, h.p, C);
             layer_norm_fp8(w.ln3, h.p, M, lnq);
@@ -2563,6 +2570,7 @@ void Engine::spatial_transformer(const SpatialW& w, const Act& x, Act& y) {
         const long long cbs = (long long)us_.t_max * C;
         attention(q.f(), C, (long long)hw * C, us_.kc.at(w.ctx_index), C, cbs, us_.vc.at(w.ctx_index), C, cbs, af,
                   C, (long long)hw * C, nb, hw, us_.t_max, heads, d, us_.kv_len_dev, us_.kv_len_host.data(), nullptr, 0, -1, a3, q_prescaled(edt(), d));
+        ip_attention(w, q.f(), af, a3, nb, hw, heads, d);   // IP-Adapter: + the image term (planes: read-modify-write)
         // Option proj_out_fold: y = x + proj_out(h + mlp_lin(u)) has no nonlinearity between its two layers, so with Wf = proj_out x mlp_lin folded at load
         // (rebuild_folds) it is y = x + Wf u + proj_out h + (bf + b_proj): ONE paired launch (linear_pair) whose extra K slices carry proj_out h.  h is then needed
         // as planes: the cross attention's output projection writes them next to its fp32 result.  A block whose fold is not fresh, or whose shape the planner does
@@ -2621,6 +2629,7 @@ void Engine::vae_attn(const VaeAttnW& w, const Act& x, Act& y) {
 void Engine::unet_release() {
     for (void* p : us_.owned) pool_.free(p);
     us_ = UNetState{};
+    ip_live_ = false;
 }
 
 // Hoists everything that does not depend on the latent out of the step loop:
@@ -2716,6 +2725,9 @@ void Engine::unet_prepare_rows(const float* ctx_packed, int nb, int t_max, const
         gemm(ctx_e, nb * t_max, s.attn2.k.bt, nullptr, cd, s.c, us_.kc[i], s.c, nullptr, 0);
         gemm(ctx_e, nb * t_max, s.attn2.v.bt, nullptr, cd, s.c, us_.vc[i], s.c, nullptr, 0);
     }
+    // an adapted call (IP-Adapter): K_ip / V_ip of the nb batch rows are made by the first step inside the window (unet_run), so a call without one runs the plain launches
+    us_.ip_want = ip_.set && ip_.scale != 0.f && n_images > 0;
+    us_.n_images = n_images;
     if (ctrl) {
         // the hint embedding, once per call: n_hint pictures through the eight hint convolutions, then laid out as the residual of the control encoder's first
         // convolution -- one block of h w rows per batch row, image i of either CFG half reading hint i mod n_hint (device copies, no launch)
@@ -3025,6 +3037,13 @@ void Engine::unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bo
     const bool controlled = control_on(step);
     Act ctl_r[13];
     if (controlled) control_run(x_nhwc, nb, step, ctl_r);
+    // an adapted step (IP-Adapter): the UNet's own cross attentions add the image term (spatial_transformer); the control encoder above does not
+    struct IpLive { bool& f; ~IpLive() { f = false; } } ip_guard{ip_live_};
+    ip_live_ = ip_on(step);
+    if (ip_live_ && us_.kip.empty()) {
+        if (nb != us_.nb) throw Error(SDMI_ERR_STATE, "ip_adapter: batch mismatch");
+        ip_prepare(nb, us_.n_images, [&](size_t bytes) { void* p = pool_.alloc(bytes); us_.owned.push_back(p); return p; });
+    }
 
     const int nblk = (int)in_blocks_.size();
     // a FreeU step: which output blocks take which pair of parameters is freeu_plan's to say; nothing below runs when none is left
@@ -4759,6 +4778,399 @@ double Engine::bench_attention(int n, int nq, int nk, int n_state, int n_head, i
     SDMI_HIP(hipEventSynchronize(ev1_));
     SDMI_HIP(hipEventElapsedTime(&ms, ev0_, ev1_));
     return (double)ms / std::max(1, iters);
+}
+
+// ---- IP-Adapter (include/sdmi.h "IP-Adapter") ------------------------------------------------------------------------
+void Engine::ip_adapter_layer(int model_channels, int ctx_index, int* j, int* c) {
+    if (ctx_index < 0 || ctx_index >= kIpLayers) throw Error(SDMI_ERR_INVALID, "ip_adapter: ctx_index must be 0 .. 15");
+    // st_list_ order (build_model): input blocks 1, 2, 4, 5, 7, 8 -- the middle block -- output blocks 3 .. 11; the file counts down, up, mid
+    static const int kMul[kIpLayers] = {1, 1, 2, 2, 4, 4, 4, 4, 4, 4, 2, 2, 2, 1, 1, 1};
+    const int rank = ctx_index < 6 ? ctx_index : (ctx_index == 6 ? 15 : ctx_index - 1);
+    if (j) *j = 2 * rank + 1;
+    if (c) *c = kMul[ctx_index] * model_channels;
+}
+
+std::string Engine::ip_adapter_key(int model_channels, int ctx_index, int which) {
+    if (which != 0 && which != 1) throw Error(SDMI_ERR_INVALID, "ip_adapter_key: which must be 0 (to_k_ip) or 1 (to_v_ip)");
+    int j = 0;
+    ip_adapter_layer(model_channels, ctx_index, &j, nullptr);
+    return "ip_adapter." + std::to_string(j) + (which ? ".to_v_ip.weight" : ".to_k_ip.weight");
+}
+
+void Engine::ip_set_weights(const IpTensor& proj_w, const IpTensor& proj_b, const IpTensor& norm_g, const IpTensor& norm_b, int D, int T, const IpTensor* wk,
+                            const IpTensor* wv) {
+    SDMI_HIP(hipSetDevice(cfg_.device));
+    const int cd = cfg_.ctx_dim, mc = cfg_.model_channels;
+    if (!proj_w.p || !proj_b.p || !norm_g.p || !norm_b.p || !wk || !wv) throw Error(SDMI_ERR_INVALID, "ip_adapter: null pointer");
+    if (T < 1 || T > kIpMaxTokens) throw Error(SDMI_ERR_INVALID, "ip_adapter: T (tokens per image) must be 1 .. 64");
+    if (D < 32 || D % 32) throw Error(SDMI_ERR_INVALID, "ip_adapter: D (the image embedding's width) must be a positive multiple of 32");
+    if ((int)n_st_unet_ != kIpLayers || st_list_[6] != &mid_st_) throw Error(SDMI_ERR_STATE, "ip_adapter: the layer rule is stated for 16 cross attentions");
+    for (int i = 0; i < kIpLayers; ++i) {
+        if (!wk[i].p || !wv[i].p) throw Error(SDMI_ERR_INVALID, "ip_adapter: null layer weight");
+        int c = 0;
+        ip_adapter_layer(mc, i, nullptr, &c);
+        const SpatialW& st = *st_list_[(size_t)i];
+        if (st.c != c) throw Error(SDMI_ERR_STATE, "ip_adapter: the layer rule does not match this model's cross attention " + std::to_string(i));
+        if (!ip_attention_head_dim(c / unet_heads(c)))
+            throw Error(SDMI_ERR_UNSUPPORTED, "ip_adapter: head width " + std::to_string(c / unet_heads(c)) + " of cross attention " + std::to_string(i) + " (40, 64, 80, 160 are served)");
+    }
+    IpWeights nw;
+    nw.D = D; nw.T = T;
+    auto dalloc = [&](size_t bytes) { void* p = nullptr; SDMI_HIP(hipMalloc(&p, bytes)); nw.allocs.push_back(p); return static_cast<float*>(p); };
+    // raw bytes -> device -> fp32 by k_unpack.hip (a Linear weight: torch [out, in] -> [in, out]) -> the loader's Linear packing
+    auto widen = [&](const IpTensor& t, long long d0, long long d1, int transform, float* out) {
+        if (t.dtype < 0 || t.dtype > 2) throw Error(SDMI_ERR_INVALID, "ip_adapter: element type must be F32, F16 or BF16");
+        const size_t bytes = (size_t)d0 * d1 * (t.dtype ? 2 : 4);
+        Buf raw(this, bytes);
+        SDMI_HIP(hipMemcpyAsync(raw.p, t.p, bytes, hipMemcpyHostToDevice, stream_));
+        SDMI_HIP(launch_unpack_tensor(raw.p, t.dtype, transform, d0, d1, out, stream_));
+        SDMI_HIP(hipStreamSynchronize(stream_));   // the host bytes (a mapped file) and the staging block are free again
+    };
+    auto linear = [&](const IpTensor& t, int cin, int cout) {
+        float* bt = dalloc((size_t)cin * cout * 4);
+        Buf stage(this, (size_t)cin * cout * 4);
+        widen(t, cout, cin, 1, stage.f());
+        SDMI_HIP(launch_pack_linear_weight(stage.f(), bt, cin, cout, stream_));
+        SDMI_HIP(hipStreamSynchronize(stream_));
+        return bt;
+    };
+    try {
+        nw.proj_bt = linear(proj_w, D, T * cd);
+        nw.proj_b = dalloc((size_t)T * cd * 4);
+        widen(proj_b, (long long)T * cd, 1, 0, nw.proj_b);
+        nw.norm.c = cd; nw.norm.eps = 1e-5f;
+        nw.norm.gamma = dalloc((size_t)cd * 4);
+        nw.norm.beta = dalloc((size_t)cd * 4);
+        widen(norm_g, cd, 1, 0, nw.norm.gamma);
+        widen(norm_b, cd, 1, 0, nw.norm.beta);
+        for (int i = 0; i < kIpLayers; ++i) {
+            const int c = st_list_[(size_t)i]->c;
+            nw.kbt.push_back(linear(wk[i], cd, c));
+            nw.vbt.push_back(linear(wv[i], cd, c));
+        }
+        ip_clear();   // the old adapter and a setting made for it; in here, so that its refusal frees the new blocks
+    } catch (...) {
+        (void)hipStreamSynchronize(stream_);
+        for (void* p : nw.allocs) (void)hipFree(p);
+        throw;
+    }
+    nw.ready = true;
+    ipw_ = std::move(nw);
+}
+
+void Engine::ip_clear() {
+    SDMI_HIP(hipSetDevice(cfg_.device));
+    SDMI_HIP(hipStreamSynchronize(stream_));
+    set_ip_adapter(nullptr);
+    for (void* p : ipw_.allocs) (void)hipFree(p);
+    ipw_ = IpWeights{};
+}
+
+// every refusal of sdmi_ip_adapter_load_safetensors, host only: the file against a model with mc model channels and a cd-wide context
+void Engine::ip_check_safetensors(const char* path, int mc, int cd, int* D_out, int* T_out) {
+    if (!path) throw Error(SDMI_ERR_INVALID, "ip_adapter: null path");
+    const std::string ps(path);
+    auto ends_with = [&](const char* suf) { const size_t n = std::strlen(suf); return ps.size() >= n && ps.compare(ps.size() - n, n, suf) == 0; };
+    if (ends_with(".bin") || ends_with(".pt") || ends_with(".pth") || ends_with(".ckpt"))
+        throw Error(SDMI_ERR_UNSUPPORTED, "ip_adapter: '" + ps + "' is a pickle file; convert it to .safetensors");
+    {   // a pickle under another name.  A .safetensors file opens with its header's length as a little-endian u64, and any byte can stand there: so only a file
+        // that cannot be one (the header would pass the file's end, or does not open with '{') is looked at for a zip archive's or a pickle stream's signature
+        unsigned char m[9] = {0};
+        if (FILE* f = std::fopen(path, "rb")) {
+            const size_t got = std::fread(m, 1, 9, f);
+            long long size = -1;
+            if (std::fseek(f, 0, SEEK_END) == 0) size = (long long)std::ftell(f);
+            std::fclose(f);
+            uint64_t hlen = 0;
+            for (int i = 7; i >= 0; --i) hlen = (hlen << 8) | m[i];
+            const bool plausible = got == 9 && size >= 9 && hlen >= 2 && hlen <= (uint64_t)size - 8 && m[8] == '{';
+            const bool zip = got >= 4 && m[0] == 'P' && m[1] == 'K' && m[2] == 3 && m[3] == 4;
+            const bool pickle = got >= 2 && m[0] == 0x80 && m[1] >= 2 && m[1] <= 5;
+            if (!plausible && (zip || pickle)) throw Error(SDMI_ERR_UNSUPPORTED, "ip_adapter: '" + ps + "' is a pickle file; convert it to .safetensors");
+        }
+    }
+    SafetensorsFile file(ps);
+    auto dtype_of = [&](const StTensor& t) {
+        if (t.dtype == "F32") return 0;
+        if (t.dtype == "F16") return 1;
+        if (t.dtype == "BF16") return 2;
+        throw Error(SDMI_ERR_WEIGHTS, "ip_adapter: '" + t.key + "' has dtype " + t.dtype + " (F32, F16, BF16 are read)");
+    };
+    auto shape_str = [](const std::vector<int64_t>& sh) { std::string o = "["; for (size_t i = 0; i < sh.size(); ++i) o += (i ? ", " : "") + std::to_string(sh[i]); return o + "]"; };
+    std::map<std::string, std::vector<int64_t>> want;   // every key the adapter has, with the shape this model needs (the projection's: checked below)
+    for (int i = 0; i < kIpLayers; ++i) {
+        int c = 0;
+        ip_adapter_layer(mc, i, nullptr, &c);
+        want[ip_adapter_key(mc, i, 0)] = {c, cd};
+        want[ip_adapter_key(mc, i, 1)] = {c, cd};
+    }
+    for (const StTensor& t : file.tensors()) {
+        if (t.key.rfind("image_proj.latents", 0) == 0 || t.key.rfind("image_proj.layers.", 0) == 0 || t.key.rfind("image_proj.proj_in", 0) == 0 || t.key.rfind("image_proj.proj_out", 0) == 0)
+            throw Error(SDMI_ERR_UNSUPPORTED, "ip_adapter: '" + t.key + "' belongs to the \"plus\" Resampler; project outside and pass tokens");
+        if (t.key.rfind("ip_adapter.", 0) == 0 && !want.count(t.key)) throw Error(SDMI_ERR_WEIGHTS, "ip_adapter: '" + t.key + "' is not a layer of this model");
+    }
+    auto need = [&](const std::string& key) -> const StTensor& {
+        const StTensor* t = file.find(key);
+        if (!t) throw Error(SDMI_ERR_WEIGHTS, "ip_adapter: '" + key + "' is missing");
+        (void)dtype_of(*t);
+        return *t;
+    };
+    const StTensor& pw = need("image_proj.proj.weight");
+    if (pw.shape.size() != 2 || pw.shape[0] < cd || pw.shape[0] % cd || pw.shape[0] / cd > kIpMaxTokens || pw.shape[1] < 32 || pw.shape[1] % 32)
+        throw Error(SDMI_ERR_WEIGHTS, "ip_adapter: 'image_proj.proj.weight' is " + shape_str(pw.shape) + ", need [T x " + std::to_string(cd) + ", D] with T <= 64 and D a multiple of 32");
+    const int T = (int)(pw.shape[0] / cd), D = (int)pw.shape[1];
+    want["image_proj.proj.bias"] = {(int64_t)T * cd};
+    want["image_proj.norm.weight"] = {cd};
+    want["image_proj.norm.bias"] = {cd};
+    for (auto& kv : want) {
+        const StTensor& t = need(kv.first);
+        if (t.shape != kv.second) throw Error(SDMI_ERR_WEIGHTS, "ip_adapter: '" + kv.first + "' is " + shape_str(t.shape) + ", this model needs " + shape_str(kv.second));
+    }
+    if (D_out) *D_out = D;
+    if (T_out) *T_out = T;
+}
+
+void Engine::ip_load_safetensors(const char* path) {
+    const int cd = cfg_.ctx_dim, mc = cfg_.model_channels;
+    int D = 0, T = 0;
+    ip_check_safetensors(path, mc, cd, &D, &T);   // the whole file, before anything is uploaded
+    SafetensorsFile file(path);
+    auto src = [&](const std::string& key) {
+        const StTensor* t = file.find(key);
+        if (!t) throw Error(SDMI_ERR_WEIGHTS, "ip_adapter: '" + key + "' is missing");
+        return IpTensor{t->data, t->dtype == "F32" ? 0 : t->dtype == "F16" ? 1 : 2};
+    };
+    IpTensor wk[kIpLayers], wv[kIpLayers];
+    for (int i = 0; i < kIpLayers; ++i) { wk[i] = src(ip_adapter_key(mc, i, 0)); wv[i] = src(ip_adapter_key(mc, i, 1)); }
+    ip_set_weights(src("image_proj.proj.weight"), src("image_proj.proj.bias"), src("image_proj.norm.weight"), src("image_proj.norm.bias"), D, T, wk, wv);
+}
+
+void Engine::ip_image_tokens_dev(const float* embeds, int n, float* out) {
+    if (!ipw_.ready) throw Error(SDMI_ERR_STATE, "ip_image_tokens: no adapter is loaded");
+    if (n < 1) throw Error(SDMI_ERR_INVALID, "ip_image_tokens: n must be at least 1");
+    const int cd = cfg_.ctx_dim, T = ipw_.T;
+    Buf lin(this, (size_t)n * T * cd * 4);
+    gemm(embeds, n, ipw_.proj_bt, ipw_.proj_b, ipw_.D, T * cd, lin.f(), T * cd, nullptr, 0, /*dt=*/0);
+    layer_norm(ipw_.norm, lin.f(), (long long)n * T, out, /*dt=*/0);
+}
+
+void Engine::check_ip_adapter(const sdmi_ip_adapter& a) {
+    if ((a.tokens != nullptr) == (a.embeds != nullptr)) throw Error(SDMI_ERR_INVALID, "ip_adapter: give exactly one of tokens and embeds");
+    if (a.n_sets < 1) throw Error(SDMI_ERR_INVALID, "ip_adapter: n_sets must be at least 1");
+    if (a.T_ip < 1) throw Error(SDMI_ERR_INVALID, "ip_adapter: T_ip must be at least 1");
+    if (a.T_ip > kIpMaxTokens) throw Error(SDMI_ERR_UNSUPPORTED, "ip_adapter: more than 64 image tokens");
+    if (!std::isfinite(a.scale)) throw Error(SDMI_ERR_INVALID, "ip_adapter: scale must be finite");
+    if (!(a.start >= 0.0 && a.start <= a.end && a.end <= 1.0)) throw Error(SDMI_ERR_INVALID, "ip_adapter: the step window must satisfy 0 <= start <= end <= 1");
+}
+
+// every refusal of set_ip_adapter: the arguments, then against this context's adapter.  Host only, changes nothing.
+void Engine::check_ip_setting(const sdmi_ip_adapter& a) const {
+    check_ip_adapter(a);
+    if (!ipw_.ready) throw Error(SDMI_ERR_STATE, "set_ip_adapter: no adapter is loaded (sdmi_ip_adapter_load_safetensors / sdmi_ip_adapter_set_weights)");
+    const int cd = cfg_.ctx_dim, T = ipw_.T;
+    if ((a.tokens || a.neg_tokens) && a.token_dim != cd)
+        throw Error(SDMI_ERR_INVALID, "ip_adapter: tokens are " + std::to_string(a.token_dim) + " wide, ctx_dim is " + std::to_string(cd));
+    if (a.embeds && a.embed_dim != ipw_.D) throw Error(SDMI_ERR_INVALID, "ip_adapter: embeds are " + std::to_string(a.embed_dim) + " wide, the adapter's D is " + std::to_string(ipw_.D));
+    if (a.embeds && a.T_ip % T) throw Error(SDMI_ERR_INVALID, "ip_adapter: with embeds T_ip must be a multiple of the adapter's T = " + std::to_string(T));
+}
+
+void Engine::set_ip_adapter(const sdmi_ip_adapter* a) {
+    SDMI_HIP(hipSetDevice(cfg_.device));
+    if (!a) {
+        SDMI_HIP(hipStreamSynchronize(stream_));
+        if (ip_.tokens) (void)hipFree(ip_.tokens);
+        if (ip_.neg) (void)hipFree(ip_.neg);
+        ip_ = IpState{};
+        return;
+    }
+    check_ip_setting(*a);
+    const int cd = cfg_.ctx_dim, T = ipw_.T, Tip = a->T_ip;
+    const size_t set_elems = (size_t)Tip * cd;
+    IpState ns;
+    ns.set = true; ns.n_sets = a->n_sets; ns.T_ip = Tip; ns.scale = a->scale; ns.start = a->start; ns.end = a->end; ns.neg_given = a->neg_tokens != nullptr;
+    ns.neg_sets = a->neg_tokens ? a->n_sets : 1;
+    try {
+        SDMI_HIP(hipMalloc((void**)&ns.tokens, (size_t)ns.n_sets * set_elems * 4));
+        SDMI_HIP(hipMalloc((void**)&ns.neg, (size_t)ns.neg_sets * set_elems * 4));
+        if (a->tokens) SDMI_HIP(hipMemcpyAsync(ns.tokens, a->tokens, (size_t)ns.n_sets * set_elems * 4, hipMemcpyHostToDevice, stream_));
+        else {
+            const int rows = ns.n_sets * (Tip / T);
+            Buf e(this, (size_t)rows * ipw_.D * 4);
+            SDMI_HIP(hipMemcpyAsync(e.p, a->embeds, (size_t)rows * ipw_.D * 4, hipMemcpyHostToDevice, stream_));
+            ip_image_tokens_dev(e.f(), rows, ns.tokens);
+        }
+        if (a->neg_tokens) SDMI_HIP(hipMemcpyAsync(ns.neg, a->neg_tokens, (size_t)ns.neg_sets * set_elems * 4, hipMemcpyHostToDevice, stream_));
+        else {   // image_proj(0), its T tokens repeated along the token axis
+            Buf z(this, (size_t)ipw_.D * 4), t0(this, (size_t)T * cd * 4);
+            SDMI_HIP(hipMemsetAsync(z.p, 0, (size_t)ipw_.D * 4, stream_));
+            ip_image_tokens_dev(z.f(), 1, t0.f());
+            for (int t = 0; t < Tip; t += T)
+                SDMI_HIP(hipMemcpyAsync(ns.neg + (size_t)t * cd, t0.f(), (size_t)std::min(T, Tip - t) * cd * 4, hipMemcpyDeviceToDevice, stream_));
+        }
+        SDMI_HIP(hipStreamSynchronize(stream_));
+    } catch (...) {
+        (void)hipStreamSynchronize(stream_);
+        if (ns.tokens) (void)hipFree(ns.tokens);
+        if (ns.neg) (void)hipFree(ns.neg);
+        throw;
+    }
+    if (ip_.tokens) (void)hipFree(ip_.tokens);
+    if (ip_.neg) (void)hipFree(ip_.neg);
+    ip_ = ns;
+}
+
+// sdmi_set_ip_adapter_file: the tensor "image_embeds" [n, D] (F32 / F16 / BF16) of a .safetensors file, widened on the host, as ONE set of n pictures
+void Engine::set_ip_adapter_file(const char* path, float scale, double start, double end) {
+    if (!path) throw Error(SDMI_ERR_INVALID, "ip_adapter: null path");
+    if (!ipw_.ready) throw Error(SDMI_ERR_STATE, "set_ip_adapter: no adapter is loaded (sdmi_ip_adapter_load_safetensors / sdmi_ip_adapter_set_weights)");
+    SafetensorsFile file(path);
+    const StTensor* t = file.find("image_embeds");
+    if (!t) throw Error(SDMI_ERR_WEIGHTS, std::string("ip_adapter: '") + path + "' holds no tensor 'image_embeds'");
+    if (t->shape.size() != 2 || t->shape[0] < 1 || t->shape[1] != ipw_.D)
+        throw Error(SDMI_ERR_INVALID, "ip_adapter: 'image_embeds' must be [n, " + std::to_string(ipw_.D) + "]");
+    if (t->shape[0] * ipw_.T > kIpMaxTokens) throw Error(SDMI_ERR_UNSUPPORTED, "ip_adapter: more than 64 image tokens");
+    std::vector<float> e(t->count);
+    if (t->dtype == "F32") std::memcpy(e.data(), t->data, t->count * 4);
+    else if (t->dtype == "BF16" || t->dtype == "F16") {
+        const bool bf = t->dtype == "BF16";
+        for (size_t i = 0; i < t->count; ++i) {
+            uint16_t h;
+            std::memcpy(&h, t->data + 2 * i, 2);
+            uint32_t u;
+            if (bf) u = (uint32_t)h << 16;
+            else {   // IEEE half -> float, exact
+                const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, ex = (h >> 10) & 31u, man = h & 1023u;
+                if (ex == 31) u = sign | 0x7f800000u | (man << 13);
+                else if (ex) u = sign | ((ex + 112u) << 23) | (man << 13);
+                else if (!man) u = sign;
+                else { int sh = 0; uint32_t m = man; while (!(m & 1024u)) { m <<= 1; ++sh; } u = sign | ((113u - sh) << 23) | ((m & 1023u) << 13); }
+            }
+            std::memcpy(&e[i], &u, 4);
+        }
+    } else throw Error(SDMI_ERR_WEIGHTS, "ip_adapter: 'image_embeds' has dtype " + t->dtype + " (F32, F16, BF16 are read)");
+    sdmi_ip_adapter a{};
+    a.embeds = e.data(); a.n_sets = 1; a.T_ip = (int32_t)t->shape[0] * ipw_.T; a.embed_dim = ipw_.D; a.scale = scale; a.start = start; a.end = end;
+    check_ip_adapter(a);
+    set_ip_adapter(&a);
+}
+
+bool Engine::get_ip_adapter(sdmi_ip_adapter* out) const {
+    if (!ip_.set) return false;
+    if (out) {
+        *out = sdmi_ip_adapter{};
+        out->n_sets = ip_.n_sets; out->T_ip = ip_.T_ip; out->token_dim = cfg_.ctx_dim; out->embed_dim = ipw_.D;
+        out->scale = ip_.scale; out->start = ip_.start; out->end = ip_.end;
+    }
+    return true;
+}
+
+// K_ip / V_ip of the nb batch rows of the call, once per call: image i of either half reads token set i mod n_sets, the unconditional half (the first n_images rows of
+// a 2 n_images batch) the negative tokens.  fp32 at every precision: the adapter's matrices are packed for the fp32 GEMM.
+void Engine::ip_prepare(int nb, int n_images, const std::function<void*(size_t)>& own) {
+    if (!ipw_.ready) throw Error(SDMI_ERR_STATE, "ip_adapter: the adapter's weights are gone");
+    const int cd = cfg_.ctx_dim, Tip = ip_.T_ip;
+    const size_t set_elems = (size_t)Tip * cd;
+    Buf rows(this, (size_t)nb * set_elems * 4);
+    for (int b = 0; b < nb; ++b) {
+        const bool uncond = nb == 2 * n_images && b < n_images;
+        const int img = b % n_images;
+        const float* src = uncond ? ip_.neg + (size_t)(img % ip_.neg_sets) * set_elems : ip_.tokens + (size_t)(img % ip_.n_sets) * set_elems;
+        SDMI_HIP(hipMemcpyAsync(rows.f() + (size_t)b * set_elems, src, set_elems * 4, hipMemcpyDeviceToDevice, stream_));
+    }
+    us_.kip.resize(kIpLayers);
+    us_.vip.resize(kIpLayers);
+    for (int i = 0; i < kIpLayers; ++i) {
+        const int c = st_list_[(size_t)i]->c;
+        us_.kip[i] = (float*)own((size_t)nb * Tip * c * 4);
+        us_.vip[i] = (float*)own((size_t)nb * Tip * c * 4);
+        gemm(rows.f(), nb * Tip, ipw_.kbt[(size_t)i], nullptr, cd, c, us_.kip[i], c, nullptr, 0, /*dt=*/0);
+        gemm(rows.f(), nb * Tip, ipw_.vbt[(size_t)i], nullptr, cd, c, us_.vip[i], c, nullptr, 0, /*dt=*/0);
+    }
+    us_.ip_s_host.assign((size_t)nb, ip_.scale);
+    us_.ip_s = (float*)own((size_t)nb * 4);
+    SDMI_HIP(hipMemcpyAsync(us_.ip_s, us_.ip_s_host.data(), (size_t)nb * 4, hipMemcpyHostToDevice, stream_));
+}
+
+void Engine::ip_attention(const SpatialW& w, const float* q, float* o, void* o3, int nb, int hw, int heads, int d) {
+    if (!ip_live_ || w.ctx_index < 0 || w.ctx_index >= (int)us_.kip.size()) return;
+    if (nb != us_.nb) throw Error(SDMI_ERR_STATE, "ip_attention: batch mismatch");
+    IpAttnParams p{};
+    p.q = q; p.k = us_.kip[(size_t)w.ctx_index]; p.v = us_.vip[(size_t)w.ctx_index]; p.s = us_.ip_s;
+    p.o_text = o3 ? o3 : (void*)o; p.o = o3 ? o3 : (void*)o;
+    p.n = nb; p.nq = hw; p.T = ip_.T_ip; p.n_head = heads; p.d_head = d;
+    p.ldq = heads * d; p.q_bs = (long long)hw * heads * d;
+    p.ldo3 = (heads * d / 32) * 192;
+    p.bf16 = edt(); p.form = o3 ? 2 : (edt() ? 1 : 0);
+    p.q_log2 = q_prescaled(edt(), d) ? 1 : 0;
+    p.scale = (float)std::pow((double)d, -0.25);
+    const double fl = 4.0 * nb * heads * (double)hw * p.T * d;
+    ProfScope ps(this, PC_ATTENTION, fl, 0);
+    ps.set_tag("ip_attention n%d nq%d T%d h%d d%d", nb, hw, p.T, heads, d);
+    SDMI_HIP(launch_ip_attention(p, stream_));
+    count_kernel(fl);
+}
+
+void Engine::op_ip_attention(const float* q, const float* k_ip, const float* v_ip, const float* o_text, const float* s, int n, int nq, int T, int n_state, int n_head,
+                             bool planes, float* out) {
+    if (n < 1 || nq < 1 || n_head < 1 || n_state < 1 || n_state % n_head) throw Error(SDMI_ERR_INVALID, "op_ip_attention: bad shape");
+    if (T < 1) throw Error(SDMI_ERR_INVALID, "op_ip_attention: T_ip must be at least 1");
+    if (T > kIpMaxTokens) throw Error(SDMI_ERR_UNSUPPORTED, "op_ip_attention: more than 64 image tokens");
+    const int d = n_state / n_head, dt = edt();
+    if (!ip_attention_head_dim(d)) throw Error(SDMI_ERR_UNSUPPORTED, "op_ip_attention: head width " + std::to_string(d) + " (40, 64, 80, 160 are served)");
+    if (planes && (dt || n_state % 32)) throw Error(SDMI_ERR_INVALID, "op_ip_attention: planes are the fp32 engine's format and need n_state % 32 == 0");
+    const long long qe = (long long)n * nq * n_state;
+    IpAttnParams p{};
+    p.k = k_ip; p.v = v_ip; p.s = s;
+    p.n = n; p.nq = nq; p.T = T; p.n_head = n_head; p.d_head = d;
+    p.ldq = n_state; p.q_bs = (long long)nq * n_state; p.ldo3 = (n_state / 32) * 192;
+    p.bf16 = dt; p.q_log2 = q_prescaled(dt, d) ? 1 : 0; p.scale = (float)std::pow((double)d, -0.25);
+    const double fl = 4.0 * n * n_head * (double)nq * T * d;
+    auto run = [&] {
+        ProfScope ps(this, PC_ATTENTION, fl, 0);
+        SDMI_HIP(launch_ip_attention(p, stream_));
+        count_kernel(fl);
+    };
+    if (dt) {
+        Buf qh(this, qe * 2), oh(this, qe * 2), yh(this, qe * 2);
+        SDMI_HIP(launch_f32_to_bf16_scaled(q, qh.p, qe, p.q_log2 ? attn_bf16_q_scale(d) : 1.f, stream_));   // Engine::attention's q convention
+        SDMI_HIP(launch_f32_to_bf16(o_text, oh.p, qe, stream_));
+        p.q = qh.p; p.o_text = oh.p; p.o = yh.p; p.form = 1;
+        run();
+        SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(yh.p, out, n * nq, n_state, 1, 1, stream_));
+    } else if (planes) {
+        Buf o3(this, (size_t)n * nq * p.ldo3);
+        SDMI_HIP(launch_split3_rows(o_text, o3.p, (long long)n * nq, n_state, n_state, p.ldo3, stream_));
+        p.q = q; p.o_text = o3.p; p.o = o3.p; p.form = 2;
+        run();
+        SDMI_HIP(launch_join3_rows(o3.p, out, (long long)n * nq, n_state, p.ldo3, n_state, stream_));
+    } else {
+        p.q = q; p.o_text = o_text; p.o = out; p.form = 0;
+        run();
+    }
+}
+
+size_t Engine::ip_kv_elems(int nb) const {
+    size_t e = 0;
+    for (int i = 0; i < kIpLayers && i < (int)n_st_unet_; ++i) e += 2 * (size_t)nb * ip_.T_ip * st_list_[(size_t)i]->c;
+    return e;
+}
+
+void Engine::ip_kv_dev(int n_images, bool cfg_pair, float* out) {
+    if (!ip_.set) throw Error(SDMI_ERR_STATE, "ip_kv: no adapter is set");
+    if (n_images < 1) throw Error(SDMI_ERR_INVALID, "ip_kv: n must be at least 1");
+    const int nb = cfg_pair ? 2 * n_images : n_images;
+    unet_release();
+    us_.nb = nb;
+    ip_prepare(nb, n_images, [&](size_t bytes) { void* p = pool_.alloc(bytes); us_.owned.push_back(p); return p; });
+    size_t off = 0;
+    for (int i = 0; i < kIpLayers; ++i) {
+        const size_t e = (size_t)nb * ip_.T_ip * st_list_[(size_t)i]->c;
+        SDMI_HIP(hipMemcpyAsync(out + off, us_.kip[(size_t)i], e * 4, hipMemcpyDeviceToDevice, stream_));
+        SDMI_HIP(hipMemcpyAsync(out + off + e, us_.vip[(size_t)i], e * 4, hipMemcpyDeviceToDevice, stream_));
+        off += 2 * e;
+    }
+    SDMI_HIP(hipStreamSynchronize(stream_));
+    unet_release();
 }
 
 }  // namespace sdmi

@@ -239,6 +239,36 @@ public:
     // engine's storage type (+ planes at precision 0 where c and ld are multiples of 32), the model's launches, back into parent; parent3 (may be null): the joined
     // planes.  Returns whether the buffer had planes.
     bool op_freeu(float* parent, int n, int c, int h, int w, int ld, int cx, int version, float b, float s, float* parent3);
+    // IP-Adapter (include/sdmi.h "IP-Adapter"): image-prompt tokens through a second, decoupled cross attention.  The adapter's weights --
+    // image_proj (Linear [T ctx_dim, D] + bias, LayerNorm over ctx_dim) and one to_k_ip / to_v_ip pair [C_i, ctx_dim] per cross attention of the UNet -- live in
+    // allocations of their own, packed by the loader's Linear packing for the fp32 GEMM (dt = 0) at every precision.  The setting (tokens, scale, window) is sticky,
+    // like the control.  IpTensor: a HOST tensor in the file's layout and element type (0 F32, 1 F16, 2 BF16), widened on the device (k_unpack.hip).
+    struct IpTensor { const void* p; int dtype; };
+    static constexpr int kIpLayers = 16;
+    // THE layer rule: cross attention ctx_index (st_list_ order: input blocks, middle, output blocks) -> the odd index j of "ip_adapter.<j>.to_k_ip.weight"
+    // (diffusers' processor order: down, up, mid) and its width C
+    static void ip_adapter_layer(int model_channels, int ctx_index, int* j, int* c);
+    static std::string ip_adapter_key(int model_channels, int ctx_index, int which);   // which 0: to_k_ip, 1: to_v_ip
+    void ip_set_weights(const IpTensor& proj_w, const IpTensor& proj_b, const IpTensor& norm_g, const IpTensor& norm_b, int D, int T, const IpTensor* wk, const IpTensor* wv);
+    void ip_load_safetensors(const char* path);   // h94's ip-adapter_sd15 layout; the whole file is checked before anything is uploaded
+    static void ip_check_safetensors(const char* path, int model_channels, int ctx_dim, int* D, int* T);   // that check alone: host only
+    bool ip_ready() const { return ipw_.ready; }
+    int ip_embed_dim() const { return ipw_.D; }
+    int ip_tokens_per_image() const { return ipw_.T; }
+    void ip_clear();                               // the weights and the setting
+    void ip_image_tokens_dev(const float* embeds, int n, float* out);   // embeds [n, D] -> LayerNorm(reshape(Linear(embeds))) [n, T, ctx_dim]; device pointers, fp32
+    static void check_ip_adapter(const sdmi_ip_adapter& a);             // the argument errors that need no context
+    void check_ip_setting(const sdmi_ip_adapter& a) const;              // every refusal of set_ip_adapter, host only: those, then against this context's adapter
+    void set_ip_adapter(const sdmi_ip_adapter* a);                      // null clears the setting (the weights stay)
+    void set_ip_adapter_file(const char* path, float scale, double start, double end);   // embeds from the tensor "image_embeds" [n, D] of a .safetensors file
+    bool get_ip_adapter(sdmi_ip_adapter* out) const;                    // the setting in force, pointers null; false: none
+    // tests (sdmi_op_ip_attention): dense fp32 device tensors q / o_text [n, nq, C], k_ip / v_ip [n, T, C], s [n] -> the storage type of the context (bf16: q scaled as
+    // the model's query weights are), the launch the model runs, out [n, nq, C] fp32.  planes (precision 0): O_text as planes, read-modify-write, joined.
+    void op_ip_attention(const float* q, const float* k_ip, const float* v_ip, const float* o_text, const float* s, int n, int nq, int T, int n_state, int n_head, bool planes,
+                         float* out);
+    // the hoisted K_ip / V_ip of the call a forward would run, for tests: out [n_layers] concatenated [nb, T_ip, C_i] blocks, K then V per layer (device)
+    size_t ip_kv_elems(int nb) const;
+    void ip_kv_dev(int n_images, bool cfg_pair, float* out);
     // Autoencoder::encode_image (autoencoder/mod.rs:60-66): img [n,3,8h,8w] NCHW -> latent mean [n,4,h,w] NCHW (device pointers)
     void encode_image_dev(const float* img_nchw, int n, float* latent_nchw);
     void sample_latent_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale,
@@ -592,6 +622,20 @@ private:
     void freeu_filter(const Act* const* cats, const int* cx, const float* s, int n_cats);   // the entries with s != 1, one launch (none without one)
     void freeu_backbone(const Act& cat, int cx, float b, int version);
     FreeU freeu_;
+    // IP-Adapter: the weights (ipw_), the sticky setting (ip_: tokens [n_sets][T_ip][cd] and negative tokens [neg_sets][T_ip][cd] on the device), whether evaluation
+    // `step` of the call in flight is inside the window (control_on's rule), and the launch behind a cross attention: o (dense, the storage type) or o3 (planes)
+    // += s_b softmax(q K_ip^T) V_ip.  ip_live_: the forward in flight is an adapted one (set by unet_run for its own blocks; a ControlNet's transformers are not adapted).
+    struct IpWeights { bool ready = false; int D = 0, T = 0; float* proj_bt = nullptr; float* proj_b = nullptr; NormW norm; std::vector<float*> kbt, vbt; std::vector<void*> allocs; } ipw_;
+    struct IpState { bool set = false; float* tokens = nullptr; float* neg = nullptr; int n_sets = 0, neg_sets = 0, T_ip = 0; bool neg_given = false; float scale = 1.f; double start = 0, end = 1; } ip_;
+    bool ip_live_ = false;
+    bool ip_on(int step) const {
+        if (!us_.ip_want) return false;
+        if (!us_.window) return true;
+        if (!us_.eval_step.empty()) return control_step_on(ip_.start, ip_.end, us_.eval_step[(size_t)step], us_.call_steps);
+        return control_step_on(ip_.start, ip_.end, step, us_.steps);
+    }
+    void ip_prepare(int nb, int n_images, const std::function<void*(size_t)>& own);
+    void ip_attention(const SpatialW& w, const float* q, float* o, void* o3, int nb, int hw, int heads, int d);
     void unet_release();
     void unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bool cfg_pair = false);
     void decode_one(const float* z_nhwc, int n, Act& img);
@@ -774,6 +818,11 @@ private:
         bool window = true;                      // the call counts steps (the sampling entries); false: sdmi_unet_forward*, where the control and FreeU are simply on
         bool ctrl = false, ctrl_window = true;   // a controlled call: the control blocks' tables are prepared, hint_rows holds the hint embedding
         float* hint_rows = nullptr;              // [nb][h][w][mc] fp32: row block i = the embedding of hint (i mod n_images) mod n_hint
+        bool ip_want = false;                    // an adapted call (IP-Adapter): an adapter is set with a scale other than 0
+        int n_images = 0;
+        std::vector<float*> kip, vip;            // per cross attention of the UNet [nb][T_ip][c] fp32, made by the first adapted step of the call; empty before
+        float* ip_s = nullptr;                   // [nb] the adapter's scale per batch row
+        std::vector<float> ip_s_host;
     } us_;
 
     // options

@@ -393,4 +393,26 @@ hipError_t launch_freeu_mean(const void* x, float* mean, long long rows, int cx,
 struct FreeuBackbone { void* y; void* y3; const float* mean; int n, hw, c, ld, ld3, dt, version; float b; };
 hipError_t launch_freeu_backbone(const FreeuBackbone& a, hipStream_t s);
 
+// ---- IP-Adapter (k_ipattn.hip) -----------------------------------------------------------------------------------
+// O = O_text + s_b softmax(q K_ip^T scale^2) V_ip per batch row b and head: the image half of a decoupled cross attention, added to what the text attention wrote.
+//   q        the storage type (bf16 != 0: 2-byte elements), rows ldq and batch rows q_bs elements apart, as AttnParams has them; q_log2 / scale: Engine::attention's pair
+//            (a q that arrives in log2 units is used as it is, otherwise the scores are multiplied by scale^2 log2(e)); the softmax runs in exp2
+//   k, v     [n][T][C] fp32 dense at every precision, C = n_head d_head, 1 <= T <= kIpMaxTokens
+//   o_text/o form 0: fp32 dense [n][nq][C]; form 1 (bf16 q only): bf16 dense; form 2 (fp32 q): the three bf16 planes, ldo3 bytes between rows, read-modify-write.
+//            o may be o_text.
+//   s        [n] on the device: a row with s_b == 0 keeps O_text's bits
+// d_head 40 / 64 / 80 / 160 (ip_attention_head_dim); bases 16-byte aligned, ldq and q_bs multiples of 4 (bf16: 8) elements.  Anything else: hipErrorInvalidValue.
+constexpr int kIpMaxTokens = 64;
+struct IpAttnParams {
+    const void* q; const float* k; const float* v; const void* o_text; void* o; const float* s;
+    int n, nq, T, n_head, d_head;
+    int ldq; long long q_bs;
+    int ldo3;
+    int bf16, form, q_log2;
+    float scale;
+    float sl2;   // set by the launcher
+};
+bool ip_attention_head_dim(int d);
+hipError_t launch_ip_attention(const IpAttnParams& p, hipStream_t s);
+
 }  // namespace sdmi

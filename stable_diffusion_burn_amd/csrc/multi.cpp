@@ -209,6 +209,18 @@ public:
         for (int r = 0; r < size(); ++r) engine(r).set_freeu(f);
     }
 
+    // sdmi_multi_set_ip_adapter: every context holds its own copy of the adapter and projects / uploads the tokens itself.
+    // Every context is asked first (host only), so a refusal by any of them leaves all of them as they were.
+    void set_ip_adapter(const sdmi_ip_adapter* a) {
+        if (a)
+            for (int r = 0; r < size(); ++r) engine(r).check_ip_setting(*a);
+        for (int r = 0; r < size(); ++r) {
+            Engine::Call call(engine(r));
+            engine(r).set_ip_adapter(a);
+            call.finish();
+        }
+    }
+
     long long broadcasts() const { return broadcasts_; }
 
 private:
@@ -351,6 +363,14 @@ int sdmi_multi_set_freeu(sdmi_multi* m, int32_t version, float b1, float b2, flo
         sdmi::Engine::check_freeu(f);
         if (!m) throw sdmi::Error(SDMI_ERR_INVALID, "null sdmi_multi");
         m->m->set_freeu(f);
+    });
+}
+
+int sdmi_multi_set_ip_adapter(sdmi_multi* m, const sdmi_ip_adapter* adapter) {
+    return multi_guard([&] {
+        if (adapter) sdmi::Engine::check_ip_adapter(*adapter);
+        if (!m) throw sdmi::Error(SDMI_ERR_INVALID, "null sdmi_multi");
+        m->m->set_ip_adapter(adapter);
     });
 }
 

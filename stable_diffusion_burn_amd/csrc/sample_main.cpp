@@ -27,6 +27,8 @@
 //   * SDMI_GUIDANCE_RESCALE=phi (0 .. 1; unset: 0, off) and SDMI_ZERO_SNR=1 (no reference counterpart): CFG rescale
 //     (sdmi_set_guidance_rescale) and the schedule rescaled to zero terminal SNR (sdmi_set_zero_snr; needs SDMI_PREDICTION=v) -- what the 768-v models and most
 //     v-prediction fine-tunes are sampled with (phi = 0.7).
+//   * SDMI_IP_ADAPTER=<file>[:scale[:start:end]] with SDMI_IP_EMBEDS=<.safetensors holding "image_embeds" [n, D]> (no reference counterpart; DESIGN.md section 9m;
+//     unset: off) loads an IP-Adapter (sdmi_ip_adapter_load_safetensors) and sets the caller's CLIP image embeddings as the image prompt (sdmi_set_ip_adapter_file).
 //   * SDMI_FREEU=b1:b2:s1:s2[:version] (no reference counterpart; unset: off) switches FreeU on (sdmi_set_freeu) for every step: version 1
 //     (the default) or 2 (ComfyUI's FreeU_V2).  The paper's values for SD 1.4 are 1.2:1.4:0.9:0.2, for SD 2.1 1.1:1.2:0.9:0.2.
 #include <cstdio>
@@ -219,6 +221,29 @@ int main(int argc, char** argv) {
             freeu_version = (int32_t)v[4];
         }
     }
+    // SDMI_IP_ADAPTER=<file>[:scale[:start:end]] + SDMI_IP_EMBEDS=<.safetensors holding "image_embeds" [n, D]>: an image prompt
+    std::string ip_file;
+    double ip_p[3] = {1.0, 0.0, 1.0};
+    const char* ip_embeds = std::getenv("SDMI_IP_EMBEDS");
+    if (const char* ia = std::getenv("SDMI_IP_ADAPTER")) {
+        if (*ia) {
+            std::vector<std::string> parts;
+            std::string cur;
+            for (const char* q = ia;; ++q) {
+                if (*q == ':' || !*q) { parts.push_back(cur); cur.clear(); if (!*q) break; }
+                else cur += *q;
+            }
+            bool ok = parts.size() == 1 || parts.size() == 2 || parts.size() == 4;
+            ip_file = parts[0];
+            for (size_t i = 1; ok && i < parts.size(); ++i) {
+                char* end = nullptr;
+                ip_p[i - 1] = std::strtod(parts[i].c_str(), &end);
+                if (end == parts[i].c_str() || *end) ok = false;
+            }
+            if (!ok || ip_file.empty()) { std::fprintf(stderr, "Error: SDMI_IP_ADAPTER must be <file>[:scale[:start:end]], got '%s'\n", ia); return 1; }
+            if (!ip_embeds || !*ip_embeds) { std::fprintf(stderr, "Error: SDMI_IP_ADAPTER needs SDMI_IP_EMBEDS=<.safetensors holding \"image_embeds\" [n, D]>\n"); return 1; }
+        }
+    }
     if (zero_snr && prediction != 1) { std::fprintf(stderr, "Error: SDMI_ZERO_SNR=1 needs SDMI_PREDICTION=v (eps does not determine x0 where alphas_cumprod is 0)\n"); return 1; }
     if (zero_snr && has_ksampler) { std::fprintf(stderr, "Error: SDMI_ZERO_SNR=1 excludes SDMI_KSAMPLER (sigma_max is infinite)\n"); return 1; }
 
@@ -247,6 +272,10 @@ int main(int argc, char** argv) {
         die("Error loading model dump");
     }
     if (lora && *lora) attach_lora(ctx, lora);
+    if (!ip_file.empty()) {
+        if (sdmi_ip_adapter_load_safetensors(ctx, ip_file.c_str()) != SDMI_OK) die("Error loading the IP-Adapter");
+        if (sdmi_set_ip_adapter_file(ctx, ip_embeds, (float)ip_p[0], ip_p[1], ip_p[2]) != SDMI_OK) die("Error setting the image prompt");
+    }
 
     // sd.unconditional_context(&tokenizer); sd.context(&tokenizer, prompt)   (main.rs:100-101)
     const int cd = cfg.ctx_dim, cap = cfg.clip_ctx;

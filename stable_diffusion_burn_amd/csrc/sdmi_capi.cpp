@@ -694,6 +694,154 @@ int sdmi_op_freeu(sdmi_ctx* ctx, const float* x, int32_t n, int32_t c, int32_t h
     return st != SDMI_OK ? st : (planes ? 1 : 0);
 }
 
+// ---- IP-Adapter ------------------------------------------------------------------------------------------------------
+int sdmi_ip_adapter_load_safetensors(sdmi_ctx* ctx, const char* path) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        Engine::Call call(e);
+        e.ip_load_safetensors(path);
+        call.finish();
+    });
+}
+
+int sdmi_ip_adapter_check_safetensors(const sdmi_config* cfg, const char* path, int32_t* D, int32_t* T) {
+    return guarded([&] {
+        if (!cfg || !path) throw Error(SDMI_ERR_INVALID, "ip_adapter_check_safetensors: null argument");
+        int d = 0, t = 0;
+        Engine::ip_check_safetensors(path, cfg->model_channels, cfg->ctx_dim, &d, &t);
+        if (D) *D = d;
+        if (T) *T = t;
+    });
+}
+
+int sdmi_ip_adapter_set_weights(sdmi_ctx* ctx, const float* proj_w, const float* proj_b, const float* norm_g, const float* norm_b, int32_t D, int32_t T,
+                                const float* const* wk, const float* const* wv) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (!wk || !wv) throw Error(SDMI_ERR_INVALID, "ip_adapter: null pointer");
+        Engine::IpTensor k[Engine::kIpLayers], v[Engine::kIpLayers];
+        for (int i = 0; i < Engine::kIpLayers; ++i) { k[i] = {wk[i], 0}; v[i] = {wv[i], 0}; }
+        Engine::Call call(e);
+        e.ip_set_weights({proj_w, 0}, {proj_b, 0}, {norm_g, 0}, {norm_b, 0}, D, T, k, v);
+        call.finish();
+    });
+}
+
+int sdmi_ip_adapter_ready(sdmi_ctx* ctx) {
+    int ready = 0;
+    const int st = guarded([&] { ready = eng(ctx).ip_ready() ? 1 : 0; });
+    return st == SDMI_OK ? ready : st;
+}
+
+int sdmi_ip_adapter_dims(sdmi_ctx* ctx, int32_t* D, int32_t* T) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (!e.ip_ready()) throw Error(SDMI_ERR_STATE, "ip_adapter_dims: no adapter is loaded");
+        if (D) *D = e.ip_embed_dim();
+        if (T) *T = e.ip_tokens_per_image();
+    });
+}
+
+int sdmi_ip_adapter_clear(sdmi_ctx* ctx) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        Engine::Call call(e);
+        e.ip_clear();
+        call.finish();
+    });
+}
+
+int sdmi_ip_image_tokens(sdmi_ctx* ctx, const float* embeds, int32_t n, int32_t D, float* out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (!embeds || !out) throw Error(SDMI_ERR_INVALID, "ip_image_tokens: null pointer");
+        if (!e.ip_ready()) throw Error(SDMI_ERR_STATE, "ip_image_tokens: no adapter is loaded");
+        if (n < 1 || D != e.ip_embed_dim()) throw Error(SDMI_ERR_INVALID, "ip_image_tokens: embeds must be [n >= 1, D = " + std::to_string(e.ip_embed_dim()) + "]");
+        Engine::Call call(e);
+        DevIn de(e, embeds, (size_t)n * D * sizeof(float));
+        DevOut dout(e, out, (size_t)n * e.ip_tokens_per_image() * e.config().ctx_dim * sizeof(float));
+        e.ip_image_tokens_dev(de.f(), n, dout.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
+int sdmi_set_ip_adapter(sdmi_ctx* ctx, const sdmi_ip_adapter* adapter) {
+    return guarded([&] {
+        if (adapter) Engine::check_ip_adapter(*adapter);   // the argument errors first: they need no context
+        Engine& e = eng(ctx);
+        Engine::Call call(e);
+        e.set_ip_adapter(adapter);
+        call.finish();
+    });
+}
+
+int sdmi_set_ip_adapter_file(sdmi_ctx* ctx, const char* embeds_path, float scale, double start, double end) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        Engine::Call call(e);
+        e.set_ip_adapter_file(embeds_path, scale, start, end);
+        call.finish();
+    });
+}
+
+int sdmi_get_ip_adapter(sdmi_ctx* ctx, sdmi_ip_adapter* out) {
+    int set = 0;
+    const int st = guarded([&] { set = eng(ctx).get_ip_adapter(out) ? 1 : 0; });
+    return st == SDMI_OK ? set : st;
+}
+
+int sdmi_ip_adapter_key(const sdmi_config* cfg, int32_t ctx_index, int32_t which, char* out, size_t capacity, size_t* needed, int32_t* j, int32_t* c) {
+    return guarded([&] {
+        if (!cfg || !needed) throw Error(SDMI_ERR_INVALID, "ip_adapter_key: null argument");
+        if (cfg->model_channels < 1) throw Error(SDMI_ERR_INVALID, "ip_adapter_key: model_channels must be positive");
+        const std::string key = Engine::ip_adapter_key(cfg->model_channels, ctx_index, which);
+        int jj = 0, cc = 0;
+        Engine::ip_adapter_layer(cfg->model_channels, ctx_index, &jj, &cc);
+        if (j) *j = jj;
+        if (c) *c = cc;
+        text_out(key, out, capacity, needed, "ip_adapter_key");
+    });
+}
+
+int sdmi_op_ip_attention(sdmi_ctx* ctx, const float* q, const float* k_ip, const float* v_ip, const float* o_text, const float* scale, int32_t n, int32_t nq,
+                         int32_t T_ip, int32_t n_state, int32_t n_head, int32_t planes, float* out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (!q || !k_ip || !v_ip || !o_text || !scale || !out) throw Error(SDMI_ERR_INVALID, "op_ip_attention: null pointer");
+        if (n < 1 || nq < 1 || T_ip < 1 || n_state < 1 || n_head < 1) throw Error(SDMI_ERR_INVALID, "op_ip_attention: bad shape");
+        if (T_ip > 64) throw Error(SDMI_ERR_UNSUPPORTED, "op_ip_attention: more than 64 image tokens");
+        const size_t qb = (size_t)n * nq * n_state * sizeof(float), kb = (size_t)n * T_ip * n_state * sizeof(float);
+        Engine::Call call(e);
+        DevIn dq(e, q, qb), dk(e, k_ip, kb), dv(e, v_ip, kb), dot(e, o_text, qb), ds(e, scale, (size_t)n * sizeof(float));
+        DevOut dout(e, out, qb);
+        e.op_ip_attention(dq.f(), dk.f(), dv.f(), dot.f(), ds.f(), n, nq, T_ip, n_state, n_head, planes != 0, dout.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
+int64_t sdmi_ip_kv_size(sdmi_ctx* ctx, int32_t n, int32_t cfg_pair) {
+    int64_t r = 0;
+    const int st = guarded([&] {
+        if (n < 1) throw Error(SDMI_ERR_INVALID, "ip_kv: n must be at least 1");
+        r = (int64_t)eng(ctx).ip_kv_elems(cfg_pair ? 2 * n : n);
+    });
+    return st == SDMI_OK ? r : st;
+}
+
+int sdmi_ip_kv(sdmi_ctx* ctx, int32_t n, int32_t cfg_pair, float* out) {
+    return guarded([&] {
+        Engine& e = eng(ctx);
+        if (!out || n < 1) throw Error(SDMI_ERR_INVALID, "ip_kv: bad argument");
+        Engine::Call call(e);
+        DevOut dout(e, out, e.ip_kv_elems(cfg_pair ? 2 * n : n) * sizeof(float));
+        e.ip_kv_dev(n, cfg_pair != 0, dout.f());
+        call.finish();
+        dout.fetch();
+    });
+}
+
 int sdmi_control_hint_embed(sdmi_ctx* ctx, const uint8_t* hint_rgb, int32_t n, int32_t hint_h, int32_t hint_w, float* out) {
     return guarded([&] {
         Engine& e = eng(ctx);

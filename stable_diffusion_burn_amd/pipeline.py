@@ -24,7 +24,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _capi
-from ._capi import SdmiAttnPlan, SdmiAttnView, SdmiConfig, SdmiControl, SdmiError, SdmiHires, SdmiInpaint, SdmiKSampler, SdmiOpView, SdmiPromptOpts, SdmiSampler, check, load_library
+from ._capi import SdmiAttnPlan, SdmiAttnView, SdmiConfig, SdmiControl, SdmiIpAdapter, SdmiError, SdmiHires, SdmiInpaint, SdmiKSampler, SdmiOpView, SdmiPromptOpts, SdmiSampler, check, load_library
 
 def mpk_list(path) -> list:
     """[(dump name, shape, file offset)] of a Burn .mpk record, parsed by the C++ reader (host only, no GPU)."""
@@ -119,6 +119,75 @@ def freeu_plan(cfg, latent_h: int, latent_w: int) -> list:
     out = (C.c_int32 * 60)()
     check(lib.sdmi_freeu_plan(C.byref(c), int(latent_h), int(latent_w), out))
     return [tuple(int(v) for v in out[5 * i:5 * i + 5]) for i in range(12)]
+
+
+def ip_adapter_key(cfg, ctx_index: int, which: str = "k", with_shape: bool = False):
+    """THE layer rule of an IP-Adapter file (sdmi_ip_adapter_key, host only, no GPU): cross attention ctx_index (0 .. 15: the input blocks'
+    six, the middle block's, the output blocks' nine) of a model with cfg.model_channels -> "ip_adapter.<j>.to_k_ip.weight" (which = "k") or "...to_v_ip.weight"
+    ("v").  with_shape: (key, j, C) -- the tensor is [C, ctx_dim]."""
+    if which not in ("k", "v"):
+        raise ValueError("which must be 'k' or 'v'")
+    lib = load_library()
+    c = SdmiConfig()
+    check(lib.sdmi_default_config(C.byref(c)))
+    c.model_channels = int(cfg.model_channels)
+    need, j, cc = C.c_size_t(), C.c_int32(), C.c_int32()
+    w = 0 if which == "k" else 1
+    check(lib.sdmi_ip_adapter_key(C.byref(c), int(ctx_index), w, None, 0, C.byref(need), C.byref(j), C.byref(cc)))
+    buf = C.create_string_buffer(need.value)
+    check(lib.sdmi_ip_adapter_key(C.byref(c), int(ctx_index), w, buf, need.value, C.byref(need), C.byref(j), C.byref(cc)))
+    return (buf.value.decode(), int(j.value), int(cc.value)) if with_shape else buf.value.decode()
+
+
+def ip_adapter_check_safetensors(cfg, path) -> tuple:
+    """Every check load_ip_adapter_safetensors makes, host only (sdmi_ip_adapter_check_safetensors): the file against a model with cfg.model_channels and
+    cfg.ctx_dim.  Returns the file's (D, T); SdmiError names the offending key."""
+    lib = load_library()
+    c = SdmiConfig()
+    check(lib.sdmi_default_config(C.byref(c)))
+    c.model_channels, c.ctx_dim = int(cfg.model_channels), int(cfg.ctx_dim)
+    d, t = C.c_int32(), C.c_int32()
+    check(lib.sdmi_ip_adapter_check_safetensors(C.byref(c), str(path).encode(), C.byref(d), C.byref(t)))
+    return int(d.value), int(t.value)
+
+
+def _ip_adapter_struct(keep, embeds, tokens, negative_tokens, scale, start, end):
+    """sdmi_ip_adapter of Python arrays; `keep` receives the arrays the struct points into"""
+    if (embeds is None) == (tokens is None):
+        raise ValueError("set_ip_adapter: give exactly one of embeds and tokens")
+    a = SdmiIpAdapter()
+    if tokens is not None:
+        t = _f32(tokens)
+        if t.ndim == 2:
+            t = t[None]
+        if t.ndim != 3:
+            raise ValueError(f"tokens must be [n_sets, T_ip, ctx_dim] or [T_ip, ctx_dim], got {t.shape}")
+        keep.append(t)
+        a.tokens = _fp(t)
+        a.n_sets, a.T_ip, a.token_dim = int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
+    else:
+        e = _f32(embeds)
+        if e.ndim == 2:     # [n_img, D]: one set of n_img pictures
+            e = e[None]
+        if e.ndim != 3:
+            raise ValueError(f"embeds must be [n_sets, n_img, D] or [n_img, D], got {e.shape}")
+        keep.append(e)
+        a.embeds = _fp(e)
+        a.n_sets, a.embed_dim = int(e.shape[0]), int(e.shape[2])
+        a.T_ip = -int(e.shape[1])   # pictures; the caller multiplies by the adapter's T
+    if negative_tokens is not None:
+        g = _f32(negative_tokens)
+        if g.ndim == 2:
+            g = g[None]
+        if g.ndim != 3:
+            raise ValueError(f"negative_tokens must be [n_sets, T_ip, ctx_dim] or [T_ip, ctx_dim], got {g.shape}")
+        if tokens is not None and g.shape != keep[0].shape:
+            raise ValueError(f"negative_tokens {g.shape} must have the shape of tokens {keep[0].shape}")
+        keep.append(g)
+        a.neg_tokens = _fp(g)
+        a.token_dim = int(g.shape[2])
+    a.scale, a.start, a.end = float(scale), float(start), float(end)
+    return a
 
 
 def control_residual_shapes(model_channels: int) -> list:
@@ -703,6 +772,116 @@ class StableDiffusion:
         c.n_hint, c.hint_h, c.hint_w = int(hint.shape[0]), int(hint.shape[1]), int(hint.shape[2])
         c.strength, c.start, c.end = float(strength), float(start), float(end)
         check(self._lib.sdmi_set_control(self._ctx, C.byref(c)))
+
+    # ---- IP-Adapter (include/sdmi.h "IP-Adapter") -------------------
+    def load_ip_adapter_safetensors(self, path) -> None:
+        """An IP-Adapter in h94's ip-adapter_sd15.safetensors layout (F32 / F16 / BF16): image_proj.* and ip_adapter.<j>.to_k_ip / to_v_ip
+        (sdmi_ip_adapter_load_safetensors).  The "plus" Resampler files and pickles are refused; the base model is not touched."""
+        check(self._lib.sdmi_ip_adapter_load_safetensors(self._ctx, str(path).encode()))
+
+    def set_ip_adapter_weights(self, proj_w, proj_b, norm_g, norm_b, wk, wv) -> None:
+        """The adapter's tensors as arrays in the file's layouts (sdmi_ip_adapter_set_weights): proj_w [T ctx_dim, D], proj_b [T ctx_dim], norm_g / norm_b [ctx_dim],
+        wk / wv: 16 matrices [C_i, ctx_dim] in the engine's order (ip_adapter_key's ctx_index)."""
+        cd = self.config.ctx_dim
+        proj_w = _f32(proj_w)
+        if proj_w.ndim != 2 or proj_w.shape[0] % cd:
+            raise ValueError(f"proj_w must be [T * {cd}, D], got {proj_w.shape}")
+        T, D = proj_w.shape[0] // cd, proj_w.shape[1]
+        proj_b, norm_g, norm_b = _f32(proj_b, (T * cd,), "proj_b"), _f32(norm_g, (cd,), "norm_g"), _f32(norm_b, (cd,), "norm_b")
+        if len(wk) != 16 or len(wv) != 16:
+            raise ValueError("wk / wv must hold 16 matrices")
+        ks, vs = [], []
+        for i in range(16):
+            _, _, c = ip_adapter_key(self.config, i, "k", with_shape=True)
+            ks.append(_f32(wk[i], (c, cd), f"wk[{i}]"))
+            vs.append(_f32(wv[i], (c, cd), f"wv[{i}]"))
+        pk, pv = (_capi._F * 16)(*[_fp(a) for a in ks]), (_capi._F * 16)(*[_fp(a) for a in vs])
+        check(self._lib.sdmi_ip_adapter_set_weights(self._ctx, _fp(proj_w), _fp(proj_b), _fp(norm_g), _fp(norm_b), int(D), int(T), pk, pv))
+
+    @property
+    def ip_adapter_ready(self) -> bool:
+        r = self._lib.sdmi_ip_adapter_ready(self._ctx)
+        if r < 0:
+            check(r)
+        return bool(r)
+
+    def clear_ip_adapter_weights(self) -> None:
+        """Frees the adapter's weights and clears the setting (sdmi_ip_adapter_clear)."""
+        check(self._lib.sdmi_ip_adapter_clear(self._ctx))
+
+    def ip_image_tokens(self, embeds) -> np.ndarray:
+        """image_proj alone (sdmi_ip_image_tokens): embeds [n, D] -> LayerNorm(reshape(Linear(embeds))) [n, T, ctx_dim]."""
+        e = _f32(embeds)
+        if e.ndim != 2:
+            raise ValueError(f"embeds must be [n, D], got {e.shape}")
+        n, D = e.shape
+        T = self.ip_adapter_dims()[1]
+        out = np.empty((n, T, self.config.ctx_dim), np.float32)
+        check(self._lib.sdmi_ip_image_tokens(self._ctx, _fp(e), n, D, _fp(out)))
+        return out
+
+    def ip_adapter_dims(self) -> tuple:
+        """(D, T) of the loaded adapter (sdmi_ip_adapter_dims): the image embedding's width and the tokens one picture becomes."""
+        d, t = C.c_int32(), C.c_int32()
+        check(self._lib.sdmi_ip_adapter_dims(self._ctx, C.byref(d), C.byref(t)))
+        return int(d.value), int(t.value)
+
+    def set_ip_adapter(self, embeds=None, tokens=None, negative_tokens=None, scale: float = 1.0, start: float = 0.0, end: float = 1.0) -> None:
+        """The image prompt of every later forward / sampling call (sdmi_set_ip_adapter; sticky).  embeds [n_img, D] (or [n_sets, n_img, D]): the caller's CLIP
+        image embeddings, projected by image_proj, the pictures of a set concatenated along the token axis; or tokens [T_ip, ctx_dim] (or [n_sets, T_ip, ctx_dim])
+        projected outside.  negative_tokens: what the unconditional half of a CFG batch reads (default image_proj(0)).  Image i of a call reads set i mod n_sets.
+        scale multiplies the image attention (0: the plain forward); step i of S is adapted iff start * S <= i < end * S.  set_ip_adapter(None) clears."""
+        if embeds is None and tokens is None:
+            check(self._lib.sdmi_set_ip_adapter(self._ctx, None))
+            return
+        keep = []
+        a = _ip_adapter_struct(keep, embeds, tokens, negative_tokens, scale, start, end)
+        if a.T_ip < 0:
+            a.T_ip = -a.T_ip * self.ip_adapter_dims()[1]
+        check(self._lib.sdmi_set_ip_adapter(self._ctx, C.byref(a)))
+
+    def set_ip_adapter_file(self, embeds_path, scale: float = 1.0, start: float = 0.0, end: float = 1.0) -> None:
+        """set_ip_adapter with embeds read from the tensor "image_embeds" [n, D] of a .safetensors file (sdmi_set_ip_adapter_file): one set of n pictures."""
+        check(self._lib.sdmi_set_ip_adapter_file(self._ctx, str(embeds_path).encode(), float(scale), float(start), float(end)))
+
+    def get_ip_adapter(self):
+        """The setting in force (sdmi_get_ip_adapter): None, or {"n_sets", "T_ip", "scale", "start", "end"}."""
+        a = SdmiIpAdapter()
+        r = self._lib.sdmi_get_ip_adapter(self._ctx, C.byref(a))
+        if r < 0:
+            check(r)
+        if not r:
+            return None
+        return {"n_sets": int(a.n_sets), "T_ip": int(a.T_ip), "scale": float(a.scale), "start": float(a.start), "end": float(a.end)}
+
+    def op_ip_attention(self, q, k_ip, v_ip, o_text, scale, n_head: int, planes: bool = False) -> np.ndarray:
+        """tests (sdmi_op_ip_attention): O_text + scale_b softmax(q K_ip^T d^-1/2) V_ip through the launch the model runs, in the context's storage type.
+        q, o_text [n, nq, C]; k_ip, v_ip [n, T_ip, C]; scale [n].  planes (precision 0): O_text as bf16 planes, read-modify-write, joined."""
+        q, k_ip, v_ip, o_text, scale = _f32(q), _f32(k_ip), _f32(v_ip), _f32(o_text), _f32(scale)
+        if q.ndim != 3 or k_ip.ndim != 3:
+            raise ValueError("op_ip_attention: q must be [n, nq, C] and k_ip [n, T_ip, C]")
+        n, nq, c = q.shape
+        T = k_ip.shape[1]
+        _f32(k_ip, (n, T, c), "k_ip"); _f32(v_ip, (n, T, c), "v_ip"); _f32(o_text, (n, nq, c), "o_text"); _f32(scale, (n,), "scale")
+        out = np.empty_like(q)
+        check(self._lib.sdmi_op_ip_attention(self._ctx, _fp(q), _fp(k_ip), _fp(v_ip), _fp(o_text), _fp(scale), n, nq, T, c, int(n_head), 1 if planes else 0, _fp(out)))
+        return out
+
+    def ip_kv(self, n: int, cfg_pair: bool = False) -> list:
+        """tests (sdmi_ip_kv): the K_ip / V_ip a call with n images would hoist -- [(K_i, V_i)] for the 16 cross attentions, each [nb, T_ip, C_i]."""
+        size = self._lib.sdmi_ip_kv_size(self._ctx, int(n), 1 if cfg_pair else 0)
+        if size < 0:
+            check(int(size))
+        flat = np.empty(int(size), np.float32)
+        check(self._lib.sdmi_ip_kv(self._ctx, int(n), 1 if cfg_pair else 0, _fp(flat)))
+        nb, T = (2 * n if cfg_pair else n), self.get_ip_adapter()["T_ip"]
+        out, off = [], 0
+        for i in range(16):
+            _, _, c = ip_adapter_key(self.config, i, "k", with_shape=True)
+            e = nb * T * c
+            out.append((flat[off:off + e].reshape(nb, T, c), flat[off + e:off + 2 * e].reshape(nb, T, c)))
+            off += 2 * e
+        return out
 
     def control_hint_embed(self, hint) -> np.ndarray:
         """The hint embedding [n, model_channels, H / 8, W / 8] of hint uint8 [n, H, W, 3] (sdmi_control_hint_embed)."""
@@ -1798,6 +1977,18 @@ class MultiStableDiffusion:
             check(self._lib.sdmi_multi_set_freeu(self._m, 0, 1.0, 1.0, 1.0, 1.0, 0.0, 1.0))
             return
         check(self._lib.sdmi_multi_set_freeu(self._m, int(version), float(b1), float(b2), float(s1), float(s2), float(start), float(end)))
+
+    def set_ip_adapter(self, embeds=None, tokens=None, negative_tokens=None, scale: float = 1.0, start: float = 0.0, end: float = 1.0) -> None:
+        """StableDiffusion.set_ip_adapter on every device (sdmi_multi_set_ip_adapter); each device holds its own copy of the adapter's weights
+        (device_view(i).load_ip_adapter_safetensors).  set_ip_adapter(None) clears."""
+        if embeds is None and tokens is None:
+            check(self._lib.sdmi_multi_set_ip_adapter(self._m, None))
+            return
+        keep = []
+        a = _ip_adapter_struct(keep, embeds, tokens, negative_tokens, scale, start, end)
+        if a.T_ip < 0:
+            a.T_ip = -a.T_ip * self.device_view(0).ip_adapter_dims()[1]
+        check(self._lib.sdmi_multi_set_ip_adapter(self._m, C.byref(a)))
 
     def schedule(self) -> np.ndarray:
         """StableDiffusion.schedule of device 0 (every device holds the same table)."""

@@ -105,3 +105,41 @@ def cond_context(global_index: int, t: int = 77, dim: int = 768) -> np.ndarray:
 
 def uncond_context(t: int = 77, dim: int = 768) -> np.ndarray:
     return _rng(UNCOND_SEED, "unconditional_context").standard_normal((t, dim), dtype=np.float32)
+
+
+# ---- IP-Adapter (DESIGN.md section 9m) ----------------------------------------------------------------------------------------------
+def ip_adapter_layers(model_channels: int) -> list:
+    """[(to_k_ip key, to_v_ip key, C)] of the 16 cross attentions of an SD v1 UNet in the engine's order (input blocks 1, 2, 4, 5, 7, 8; the middle block; output
+    blocks 3 .. 11), the keys as h94's ip-adapter_sd15 file spells them.  The rule itself is the library's (sdmi_ip_adapter_key, host only): it is asked, not restated."""
+    from types import SimpleNamespace
+
+    from .pipeline import ip_adapter_key
+    cfg = SimpleNamespace(model_channels=int(model_channels))
+    out = []
+    for i in range(16):
+        kk, _, c = ip_adapter_key(cfg, i, "k", with_shape=True)
+        out.append((kk, ip_adapter_key(cfg, i, "v"), c))
+    return out
+
+
+def ip_adapter(model_channels: int, ctx_dim: int, embed_dim: int = 64, tokens: int = 4, provider=None, gain: float = 1.0) -> dict:
+    """A deterministic synthetic IP-Adapter: {file key: float32 array in the file's layout} -- image_proj.proj.weight [tokens ctx_dim, embed_dim] / bias,
+    image_proj.norm.weight / bias [ctx_dim], ip_adapter.<j>.to_k_ip.weight / to_v_ip.weight [C, ctx_dim] (torch's [out, in]).  Linear tensors are
+    gain * U(-1, 1) / sqrt(fan_in), the norm as every norm here."""
+    provider = provider or SyntheticWeights()
+    g = np.float32(gain)
+    out = {
+        "image_proj.proj.weight": g * provider.get("ip_adapter/image_proj.proj.weight", (tokens * ctx_dim, embed_dim), "w", embed_dim),
+        "image_proj.proj.bias": g * provider.get("ip_adapter/image_proj.proj.bias", (tokens * ctx_dim,), "b", embed_dim),
+        "image_proj.norm.weight": provider.get("ip_adapter/image_proj.norm.weight", (ctx_dim,), "gamma"),
+        "image_proj.norm.bias": provider.get("ip_adapter/image_proj.norm.bias", (ctx_dim,), "beta"),
+    }
+    for kk, kv, c in ip_adapter_layers(model_channels):
+        out[kk] = g * provider.get("ip_adapter/" + kk, (c, ctx_dim), "w", ctx_dim)
+        out[kv] = g * provider.get("ip_adapter/" + kv, (c, ctx_dim), "w", ctx_dim)
+    return out
+
+
+def image_embeds(index: int, n_img: int = 1, dim: int = 64) -> np.ndarray:
+    """"Random CLIP image embedding" of prompt picture set `index`: [n_img, dim]."""
+    return _rng(COND_SEED, f"image_embeds/{index}").standard_normal((n_img, dim), dtype=np.float32)

@@ -382,3 +382,16 @@ def write_control_safetensors(path, provider_or_dict, dims, dtype: str = "F32", 
                 raise ValueError(f"write_control_safetensors: '{name}' has shape {tuple(a.shape)}, expected {tuple(shape)}")
             return a
     write_checkpoint_safetensors(path, specs, get, None, dtype, key_of=key_of, extra=extra)
+
+
+# ---- IP-Adapter: h94's ip-adapter_sd15.safetensors layout -------------------------------------------------------
+def write_ip_adapter_safetensors(path, arrays: dict, dtype: str = "F32") -> None:
+    """Write an IP-Adapter {file key: array in the file's layout} (synthetic.ip_adapter makes one): the inverse of sdmi_ip_adapter_load_safetensors.
+    dtype "F32" | "F16" | "BF16": what every tensor is stored as."""
+    if dtype not in ("F32", "F16", "BF16"):
+        raise ValueError(f"write_ip_adapter_safetensors: dtype must be F32, F16 or BF16, got {dtype!r}")
+    out = {}
+    for key, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float32)
+        out[key] = a if dtype == "F32" else a.astype(np.float16) if dtype == "F16" else (bf16_bits(a).reshape(a.shape), "BF16")
+    write_safetensors(path, out)
