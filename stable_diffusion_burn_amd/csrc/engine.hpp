@@ -327,6 +327,7 @@ public:
     void check_qkv_attention_view(const sdmi_attn_view& view, bool has_mask, int mask_ld, const int* kv_len_host, int n, int nq, int nk, int n_state, int n_head) const;
 
     // operator-level (device pointers, reference layouts)
+    // (defined in engine_ops.cpp, with every other op_* / bench_* member and qkv_attention_dev)
     void op_group_norm(const float* x, const float* gamma, const float* beta, int n, int c, int h, int w, int groups,
                        float eps, bool silu, float* out);
     void op_group_norm_fp8(const float* x, const float* gamma, const float* beta, int n, int c, int h, int w, int groups, float eps,
@@ -356,6 +357,11 @@ public:
     // parent [rows][out_ld] fp32 NHWC, prefilled by the caller and returned whole; yp3 (may be null): the joined plane copy when the parent exists both
     // as fp32 and as planes.  Parents take the storage type of the route (bf16 at precision >= 1; v.in_planes / v.out_planes at precision 0).
     static void check_view(const sdmi_op_view& v, int cin, int cout);
+    // the output size of conv(): k x k, pad, stride over the input upsampled 2x when ups
+    static void conv_out_hw(int h, int w, int k, int stride, int pad, int ups, int* ho, int* wo) {
+        *ho = ((h << ups) + 2 * pad - k) / stride + 1;
+        *wo = ((w << ups) + 2 * pad - k) / stride + 1;
+    }
     void op_conv2d_view(const float* xp, const float* w, const float* bias, int n, int cin, int h, int wd, int cout, int k, int stride, int pad, int ups,
                         const sdmi_op_view& v, const EpiOps* epi, float* yp, float* yp3);
     void op_linear_view(const float* x, const float* w, const float* bias, int rows, int cin, int cout, const sdmi_op_view& v, const EpiOps* epi, float* yp);
@@ -537,6 +543,29 @@ private:
         TempUpFold& operator=(const TempUpFold&) = delete;
     };
     static Act slice(const Act& parent, int c_off, int c);   // channel-slice view
+    // operator-level entry points (engine_ops.cpp): what they share.  A new storage form is taught to the route, OpConvW / OpLinW and OpParent once.
+    // OpRoute: the kernels an operator-level conv2d / Linear of the shape runs on this context -- q8: MXFP8 (input quantised, MXFP8 weight, bf16 output);
+    // otherwise the storage types of the packed weight, the input and the output (0 fp32, 1 bf16)
+    struct OpRoute { bool q8; int wdt, xdt, ydt; };
+    // f32: option op_f32 (the dense conv entry only); refuse: throw where the context has no kernel for the shape (bench_conv leaves that to conv())
+    OpRoute conv_route(int cin, int cout, int k, int stride, int ups, bool f32 = false, bool refuse = true) const;
+    OpRoute lin_route(int cin, int cout) const;
+    struct OpConvW;    // a reference-layout conv weight packed for a route, with its planes and phase weights, for the duration of a call
+    struct OpLinW;     // ... a Linear weight
+    struct OpParent;   // the parent of a channel-slice view in the route's storage type, filled from / given back to the caller's fp32 NHWC image
+    Act act_from_nchw(const float* x, int n, int c, int h, int w, int dt);      // x [n,c,h,w] fp32 -> a new NHWC activation of type dt
+    void act_to_nchw(const Act& a, float* out);                                 // a dense NHWC activation (fp32 or bf16) -> out [n,c,h,w] fp32
+    void rows_to_f32(const void* bf16_rows, float* out, long long rows, int c);   // dense bf16 rows -> fp32
+    const int* kv_len_to_dev(std::unique_ptr<Buf>& b, const int* kv_len_host, int n);   // null without per-sample key counts
+    // q / k / v (dense fp32) -> bf16 in bufs[3], q in Engine::attention's convention (q_prescaled); the pointers are redirected to the copies
+    void qkv_to_bf16(const float*& q, const float*& k, const float*& v, long long qe, long long ke, int dh, std::unique_ptr<Buf> (&bufs)[3]);
+    // what op_conv2d and op_conv2d_view share once their input xs and output ys stand: temb and residual staged (self_resid: option op_resid's x), the weight packed
+    // for the route, an MXFP8 input quantised from xs (fp32: the dense entry; bf16: a view's slice), then conv_fp8 or conv
+    void op_conv_run(const OpRoute& r, const float* wt, const float* bias, int k, int stride, int ups, const EpiOps* epi, const Act& xs, Act& ys, const Act* self_resid);
+    // ... op_linear and op_linear_view: x [rows][cin] dense fp32 -> C (rows ldc elements apart, the route's output type) on the MXFP8, bf16 or fp32 kernels; resid: staged
+    // by the caller (may be null); self_resid (option op_resid): without one, the input in the route's storage type is the residual of the bf16 / fp32 kernels
+    void op_linear_run(const OpRoute& r, const float* x, const float* wt, const float* bias, int rows, int cin, int cout, float* C, int ldc, const float* resid, int ldr,
+                       bool self_resid);
     // A3 / C3: the input / output as three bf16 planes (dense rows: 192 bytes per 32 channels); A and / or C may then be null
     void gemm(const float* A, int a_rows, const float* bt, const float* bias, int cin, int cout, float* C, int ldc,
               const float* resid, int ldr, int dt = -1, int out_mode = 0, const void* A3 = nullptr, void* C3 = nullptr);
