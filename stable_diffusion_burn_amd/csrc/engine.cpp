@@ -405,6 +405,7 @@ void Engine::build_model() {
                 weight_allocs_.push_back(pl);
                 split_regions_.push_back(SplitRegion{reinterpret_cast<char*>(p), (size_t)3 * c * c * 4, reinterpret_cast<char*>(pl)});
             }
+            m.q.fused = 3;
             m.k.bt = adv(m.q.bt, (long long)c * c, edt());
             m.v.bt = adv(m.q.bt, (long long)2 * c * c, edt());
             if (fp8_ && c % 32 == 0) {   // the packed [3c][Kp] MXFP8 copy + its scales: one N = 3c GEMM as well
@@ -568,6 +569,7 @@ void Engine::build_model() {
             weight_allocs_.push_back(bias);
             b.q.bt = reinterpret_cast<float*>(w); b.k.bt = b.q.bt + (size_t)cs * cs; b.v.bt = b.q.bt + (size_t)2 * cs * cs;
             b.q.bias = reinterpret_cast<float*>(bias); b.k.bias = b.q.bias + cs; b.v.bias = b.q.bias + 2 * cs;
+            b.q.fused = 3;
             norm(b.attn_ln, bp + "/attn_ln", cs, false);
             lin(b.q, bp + "/attn/query", cs, cs, true, true);   // MultiHeadSelfAttention: all four Linears carry a bias
             lin(b.k, bp + "/attn/key", cs, cs, true, true);
@@ -1142,9 +1144,8 @@ void Engine::load_safetensors_groups(const char* path, bool control) {
         {
             ProfScope ps_o(this, PC_OTHER, 0, (double)j.nbytes + (double)(e.kind <= 1 ? stage_elems(e) : entry_count(e)) * 4);
             ps_o.set_tag("unpack %s t%d %lldx%lld", j.t->dtype.c_str(), j.transform, d0, d1);
-            SDMI_HIP(launch_unpack_tensor(dev, j.dtype, j.transform, d0, d1, out, stream_, (int)e.dims[1]));
+            SDMI_LAUNCH_IN(ps_o, 0, launch_unpack_tensor(dev, j.dtype, j.transform, d0, d1, out, stream_, (int)e.dims[1]));
         }
-        count_kernel();
         if (e.kind <= 1) {
             if (e.master) SDMI_HIP(hipMemcpyAsync(e.master, out, stage_elems(e) * sizeof(float), hipMemcpyDeviceToDevice, stream_));
             pack_entry(e, out);
@@ -1772,8 +1773,7 @@ void Engine::run_gemm(ConvGemm& p, const GemmRun& r) {
         p.slabs = nullptr; p.slab_stride = 0;
         ProfScope ps(this, r.pc, r.flops, r.bytes);
         ps.set_tag("%s %d,%d,%d k%d%s%s%s cfg=%d splits=1", r.what, p.M, p.N, p.K, p.KH, p.geglu ? " geglu" : "", p.resid ? " resid" : "", p.rowvec ? " rowvec" : "", r.cfg);
-        SDMI_HIP(r.launch(p, r.index, stream_));
-        count_kernel(r.flops);
+        SDMI_LAUNCH_IN(ps, r.flops, r.launch(p, r.index, stream_));
         return;
     }
     p.slab_stride = (long long)p.M * p.N;
@@ -1782,13 +1782,11 @@ void Engine::run_gemm(ConvGemm& p, const GemmRun& r) {
     {
         ProfScope ps(this, r.pc, r.flops, r.bytes);
         ps.set_tag("%s %d,%d,%d k%d%s cfg=%d splits=%d", r.what, p.M, p.N, p.K, p.KH, p.geglu ? " geglu" : "", r.cfg, p.splits);
-        SDMI_HIP(r.launch(p, r.index, stream_));
+        SDMI_LAUNCH_IN(ps, r.flops, r.launch(p, r.index, stream_));
     }
-    count_kernel(r.flops);
     ProfScope ps(this, PC_SPLITK_REDUCE, 0, (double)(p.splits + 1) * p.slab_stride * 4.0);
     if (r.reduce_tag) ps.set_tag("reduce %d,%d,%d k%d cfg=%d splits=%d", p.M, p.N, p.K, p.KH, r.cfg, p.splits);
-    SDMI_HIP(r.bf16_reduce ? launch_splitk_reduce_bf16(p, stream_) : launch_splitk_reduce(p, stream_));
-    count_kernel();
+    SDMI_LAUNCH_IN(ps, 0, r.bf16_reduce ? launch_splitk_reduce_bf16(p, stream_) : launch_splitk_reduce(p, stream_));
 }
 
 // what the planner (gemm_plan.hpp) is told about a launch; p.kt_total, p.Bt3 and the shape are set
@@ -1858,8 +1856,7 @@ void Engine::launch_gemm(ConvGemm& p, int in_dt, int force_cfg, int force_splits
         p.a3_ld = (p.Cin / 32) * 192;
         a3_tmp.reset(new Buf(this, (size_t)rows * p.a3_ld));
         ProfScope ps(this, PC_SPLIT_ROWS, 0, (double)rows * p.Cin * 10.0);
-        SDMI_HIP(launch_split3_rows(p.A, a3_tmp->p, rows, p.Cin, p.a_ld, p.a3_ld, stream_));
-        count_kernel();
+        SDMI_LAUNCH_IN(ps, 0, launch_split3_rows(p.A, a3_tmp->p, rows, p.Cin, p.a_ld, p.a3_ld, stream_));
         p.A3 = a3_tmp->p;
     }
     // the large-tile bf16 kernels take the residual as the accumulators' initial value (k_gemm_bf16_epi.hpp gemm_acc_init_bf16) where their 8-byte loads apply
@@ -1878,8 +1875,7 @@ void Engine::launch_gemm(ConvGemm& p, int in_dt, int force_cfg, int force_splits
     run_gemm(p, GemmRun{kLaunchers[in_dt ? 1 : 0][g.tile.family], g.tile.index, "gemm", g.cfg, w_planes ? PC_CONV_SPLIT : PC_CONV_GEMM, in_dt != 0, true, flops, gemm_bytes});
     if (c3_want && !c3_native) {
         ProfScope ps(this, PC_SPLIT_ROWS, 0, (double)p.M * p.N * 10.0);
-        SDMI_HIP(launch_split3_rows(p.C, c3_want, p.M, p.N, p.ldc, ldc3_want, stream_));
-        count_kernel();
+        SDMI_LAUNCH_IN(ps, 0, launch_split3_rows(p.C, c3_want, p.M, p.N, p.ldc, ldc3_want, stream_));
     }
 }
 
@@ -1959,8 +1955,7 @@ bool Engine::conv_ups_phase(const ConvW& w, const Act& x, Act& y, const float* r
         p.a3_ld = (p.Cin / 32) * 192;
         a3_tmp.reset(new Buf(this, (size_t)rows * p.a3_ld));
         ProfScope ps(this, PC_SPLIT_ROWS, 0, (double)rows * p.Cin * 10.0);
-        SDMI_HIP(launch_split3_rows(p.A, a3_tmp->p, rows, p.Cin, p.a_ld, p.a3_ld, stream_));
-        count_kernel();
+        SDMI_LAUNCH_IN(ps, 0, launch_split3_rows(p.A, a3_tmp->p, rows, p.Cin, p.a_ld, p.a3_ld, stream_));
         p.A3 = a3_tmp->p;
     }
     // from here on the struct describes the phase launch: M = the rows of one phase, K = 4 cin
@@ -1979,14 +1974,12 @@ bool Engine::conv_ups_phase(const ConvW& w, const Act& x, Act& y, const float* r
     {
         ProfScope ps(this, PC_CONV_SPLIT, flops, bytes);
         ps.set_tag("gemm 4x%d,%d,%d k3 phase cfg=%d splits=%d", p.M, p.N, p.K, g.cfg, p.splits);
-        SDMI_HIP(launch_conv_gemm3p(p, g.tile.index, stream_));
+        SDMI_LAUNCH_IN(ps, flops, launch_conv_gemm3p(p, g.tile.index, stream_));
     }
-    count_kernel(flops);
     if (p.splits > 1) {
         ProfScope ps(this, PC_SPLITK_REDUCE, 0, (double)(p.splits + 1) * p.slab_stride * 4.0);
         ps.set_tag("reduce 4x%d,%d,%d k3 phase cfg=%d splits=%d", p.M, p.N, p.K, g.cfg, p.splits);
-        SDMI_HIP(launch_splitk_reduce(p, stream_));
-        count_kernel();
+        SDMI_LAUNCH_IN(ps, 0, launch_splitk_reduce(p, stream_));
     }
     return true;
 }
@@ -2036,13 +2029,11 @@ bool Engine::conv_pair(const ConvW& w_out, const Act& h, const ConvW& w_skip, co
     {
         ProfScope ps(this, PC_CONV_SPLIT, flops, bytes);
         ps.set_tag("gemm %d,%d,%d+%d k3+1 cfg=%d splits=%d+%d", p.M, p.N, p.K, w_skip.cin, g.cfg, g.splits_main, g.splits_aux);
-        SDMI_HIP(launch_conv_gemm3p(p, g.tile.index, stream_));
+        SDMI_LAUNCH_IN(ps, flops, launch_conv_gemm3p(p, g.tile.index, stream_));
     }
-    count_kernel(flops);
     ProfScope ps(this, PC_SPLITK_REDUCE, 0, (double)(p.splits + 1) * p.slab_stride * 4.0);
     ps.set_tag("reduce %d,%d,%d+%d k3+1 cfg=%d splits=%d+%d", p.M, p.N, p.K, w_skip.cin, g.cfg, g.splits_main, g.splits_aux);
-    SDMI_HIP(launch_splitk_reduce(p, stream_));
-    count_kernel();
+    SDMI_LAUNCH_IN(ps, 0, launch_splitk_reduce(p, stream_));
     return true;
 }
 
@@ -2104,72 +2095,79 @@ bool Engine::linear_pair(const LinearPair& a, bool plan_only) {
     {
         ProfScope ps(this, PC_CONV_SPLIT, flops, bytes);
         ps.set_tag("gemm %d,%d,%d+%d k1+1%s cfg=%d splits=%d+%d", p.M, p.N, p.K, a.k_aux, p.resid ? " resid" : "", g.cfg, g.splits_main, g.splits_aux);
-        SDMI_HIP(launch_conv_gemm3p(p, g.tile.index, stream_));
+        SDMI_LAUNCH_IN(ps, flops, launch_conv_gemm3p(p, g.tile.index, stream_));
     }
-    count_kernel(flops);
     ProfScope ps(this, PC_SPLITK_REDUCE, 0, (double)(p.splits + 1) * p.slab_stride * 4.0);
     ps.set_tag("reduce %d,%d,%d+%d k1+1 cfg=%d splits=%d+%d", p.M, p.N, p.K, a.k_aux, g.cfg, g.splits_main, g.splits_aux);
-    SDMI_HIP(launch_splitk_reduce(p, stream_));
-    count_kernel();
+    SDMI_LAUNCH_IN(ps, 0, launch_splitk_reduce(p, stream_));
     return true;
 }
 
-void Engine::gemm(const float* A, int a_rows, const float* bt, const float* bias, int cin, int cout, float* C, int ldc,
-                  const float* resid, int ldr, int dt, int out_mode, const void* A3, void* C3) {
-    if (dt < 0) dt = edt();
-    if (cin % 32) throw Error(SDMI_ERR_UNSUPPORTED, "linear: in_features must be a multiple of 32");
-    ConvGemm p = linear_gemm(A, a_rows, bt, bias, cin, cout, C, ldc, resid, ldr);
-    p.A3 = A3; p.a3_ld = (cin / 32) * 192;          // dense planes in ...
-    p.C3 = C3; p.ldc3 = (cout / 32) * 192;          // ... and out
-    if (C3 && (cout % 32)) throw Error(SDMI_ERR_STATE, "linear: plane output needs out_features % 32 == 0");
-    p.out_mode = out_mode;
-    launch_gemm(p, dt);
+// what linear() and its MXFP8 form check alike: the shapes of x (c channels), y and resid against the weight
+static void check_linear(const LinW& w, long long rows, int c, const Act& y, const Act* resid) {
+    if (c != w.cin || y.rows() != rows || (y.c != w.cout && (w.fused < 2 || y.c != w.fused * w.cout)))
+        throw Error(SDMI_ERR_STATE, "linear: the tensors do not have the weight's shape");
+    if (resid && (resid->rows() != rows || resid->c != y.c || resid->dt != y.dt || !resid->p)) throw Error(SDMI_ERR_STATE, "linear: the residual does not have the output's shape and type");
 }
 
-void Engine::gemm_geglu(const float* x, long long rows, const float* bt, const float* bias, int cin, int hidden, float* out, int dt,
-                        const void* x3, void* out3) {
-    if (dt < 0) dt = edt();
-    if (x3 && (out3 || out) && !dt && opt_geglu_fuse_ && hidden % 32 == 0 && cin % 32 == 0 && split_planes(bt)) {
+void Engine::linear(const LinW& w, const Act& x, const Act& y, const Act* resid) {
+    check_linear(w, x.rows(), x.c, y, resid);
+    if (x.dt != y.dt || x.stride() != x.c) throw Error(SDMI_ERR_STATE, "linear: dense input rows of the output's storage type expected");
+    if (w.cin % 32) throw Error(SDMI_ERR_UNSUPPORTED, "linear: in_features must be a multiple of 32");
+    ConvGemm p = linear_gemm(x.p, (int)x.rows(), w.bt, w.bias, w.cin, y.c, y.p, y.stride(), resid ? resid->p : nullptr, resid ? resid->stride() : 0);
+    p.A3 = x.p3; p.a3_ld = (w.cin / 32) * 192;      // dense planes in ...
+    p.C3 = y.p3; p.ldc3 = (y.c / 32) * 192;         // ... and out
+    if (y.p3 && (y.c % 32 || y.ld3 != p.ldc3)) throw Error(SDMI_ERR_STATE, "linear: plane output needs out_features % 32 == 0 and dense planes");
+    launch_gemm(p, x.dt);
+}
+
+void Engine::gemm_geglu(const LinW& w, const Act& x, const Act& y) {
+    const int dt = x.dt, cin = w.cin, hidden = w.cout / 2;
+    const long long rows = x.rows();
+    if (x.c != cin || y.c != hidden || w.cout != 2 * hidden || y.rows() != rows || y.dt != dt || x.stride() != cin || y.stride() != hidden)
+        throw Error(SDMI_ERR_STATE, "geglu: dense tensors of the projection's shape expected");
+    if (dt && (x.p3 || y.p3)) throw Error(SDMI_ERR_STATE, "geglu: planes are an fp32-engine format");
+    if (x.p3 && !dt && opt_geglu_fuse_ && hidden % 32 == 0 && cin % 32 == 0 && split_planes(w.bt)) {
         // the gate in the plane GEMM's epilogue -- value / gate rows split by WAVE column, so the tiles with an odd fragment count per wave (256 x 160: the batch-1 model's) qualify
         const int cfg = plan_geglu_plane_tile(rows, hidden, cin, gopt_, tuning_);
         if (cfg >= 0) {
-            ConvGemm p = linear_gemm(x, (int)rows, bt, bias, cin, hidden, out, hidden, nullptr, hidden);
-            p.A3 = x3; p.a3_ld = (cin / 32) * 192;
-            p.C3 = out3; p.ldc3 = (hidden / 32) * 192;
+            ConvGemm p = linear_gemm(x.p, (int)rows, w.bt, w.bias, cin, hidden, y.p, hidden, nullptr, hidden);
+            p.A3 = x.p3; p.a3_ld = (cin / 32) * 192;
+            p.C3 = y.p3; p.ldc3 = (hidden / 32) * 192;
             p.geglu = 2;
             launch_gemm(p, 0, cfg, 1);
             return;
         }
     }
-    if (x3 || out3) {   // plane form: projection on a plane tile, gate kernel writing planes (the MLP's second Linear reads them)
-        Buf proj(this, (size_t)rows * 2 * hidden * 4);
-        gemm(x, (int)rows, bt, bias, cin, 2 * hidden, proj.f(), 2 * hidden, nullptr, 0, dt, 0, x3, nullptr);
+    if (x.p3 || y.p3) {   // plane form: projection on a plane tile, gate kernel writing planes (the MLP's second Linear reads them)
+        Act proj = new_rows(rows, 2 * hidden, 1, 0);
+        linear(w, x, proj);
         {
-            ProfScope ps(this, PC_GEGLU, 0, (double)rows * hidden * (8.0 + (out3 ? 6.0 : 4.0)));
-            if (out3) SDMI_HIP(launch_geglu_planes(proj.f(), out3, rows, hidden, stream_));
+            ProfScope ps(this, PC_GEGLU, 0, (double)rows * hidden * (8.0 + (y.p3 ? 6.0 : 4.0)));
+            if (y.p3) SDMI_LAUNCH_IN(ps, 0, launch_geglu_planes(proj.p, y.p3, rows, hidden, stream_));
             // (both asked for -- op_geglu_forward with geglu_fuse = 8: the fused launch above writes both, so must this form; the model asks for one)
-            if (out) { SDMI_HIP(launch_geglu(proj.f(), out, rows, hidden, stream_)); if (out3) count_kernel(); }
+            if (y.p) SDMI_LAUNCH_IN(ps, 0, launch_geglu(proj.p, y.p, rows, hidden, stream_));
         }
-        count_kernel();
+        release(proj);
         return;
     }
     // the fused form needs a large-tile kernel with an even fragment count per wave (256x256 or 256x128 tiles, no split-K)
     const bool eligible = opt_geglu_fuse_ && hidden % 8 == 0 && cin % (dt ? 64 : 32) == 0 && (dt ? gopt_.gemm_bf16x : gopt_.gemm_x32);
-    const int cfg = eligible ? plan_geglu_paired_tile(rows, hidden, opt_geglu_fuse_, !dt && gopt_.gemm_f32s && split_planes(bt)) : -1;
+    const int cfg = eligible ? plan_geglu_paired_tile(rows, hidden, opt_geglu_fuse_, !dt && gopt_.gemm_f32s && split_planes(w.bt)) : -1;
     if (cfg >= 0) {
-        ConvGemm p = linear_gemm(x, (int)rows, bt, bias, cin, hidden, out, hidden, nullptr, hidden);
+        ConvGemm p = linear_gemm(x.p, (int)rows, w.bt, w.bias, cin, hidden, y.p, hidden, nullptr, hidden);
         p.geglu = 1;
         launch_gemm(p, dt, cfg, 1);
         return;
     }
-    Buf proj(this, (size_t)rows * 2 * hidden * (dt ? 2 : 4));
-    gemm(x, (int)rows, bt, bias, cin, 2 * hidden, proj.f(), 2 * hidden, nullptr, 0, dt);
+    Act proj = new_rows(rows, 2 * hidden, 1, dt);
+    linear(w, x, proj);
     {
         ProfScope ps(this, PC_GEGLU, 0, (double)rows * hidden * (dt ? 6.0 : 12.0));
-        if (dt) SDMI_HIP(launch_geglu_bf16(proj.p, out, rows, hidden, stream_));
-        else SDMI_HIP(launch_geglu(proj.f(), out, rows, hidden, stream_));
+        if (dt) SDMI_LAUNCH_IN(ps, 0, launch_geglu_bf16(proj.p, y.p, rows, hidden, stream_));
+        else SDMI_LAUNCH_IN(ps, 0, launch_geglu(proj.p, y.p, rows, hidden, stream_));
     }
-    count_kernel();
+    release(proj);
 }
 
 void Engine::group_norm(const NormW& w, const Act& x, Act& y, bool silu) {
@@ -2182,37 +2180,37 @@ void Engine::group_norm(const NormW& w, const Act& x, Act& y, bool silu) {
     if (!x.p) throw Error(SDMI_ERR_STATE, "group_norm: the input must exist as fp32");
     if (y.p3 && !y.p) {   // the consumer is a plane GEMM: the normalised tensor is written as three bf16 planes only
         if (x.dt) throw Error(SDMI_ERR_STATE, "group_norm: planes are an fp32-engine format");
-        SDMI_HIP(launch_group_norm_planes(x.p, y.p3, w.gamma, w.beta, x.n, hw, x.c, x.stride(), 32, w.eps, silu, part.p, stream_, opt_gn32_min_wgs_));
+        SDMI_LAUNCH_IN(ps, 0, launch_group_norm_planes(x.p, y.p3, w.gamma, w.beta, x.n, hw, x.c, x.stride(), 32, w.eps, silu, part.p, stream_, opt_gn32_min_wgs_));
     }
-    else if (x.dt) SDMI_HIP(launch_group_norm_bf16(x.p, y.p, w.gamma, w.beta, x.n, hw, x.c, x.stride(), 32, w.eps, silu, part.p, stream_, gn_tune_));
-    else SDMI_HIP(launch_group_norm(x.p, y.p, w.gamma, w.beta, x.n, hw, x.c, x.stride(), 32, w.eps, silu, part.p, stream_, opt_gn32_min_wgs_));
-    count_kernel(); count_kernel();
+    else if (x.dt) SDMI_LAUNCH_IN(ps, 0, launch_group_norm_bf16(x.p, y.p, w.gamma, w.beta, x.n, hw, x.c, x.stride(), 32, w.eps, silu, part.p, stream_, gn_tune_));
+    else SDMI_LAUNCH_IN(ps, 0, launch_group_norm(x.p, y.p, w.gamma, w.beta, x.n, hw, x.c, x.stride(), 32, w.eps, silu, part.p, stream_, opt_gn32_min_wgs_));
+    count_kernel();   // each launcher enqueues two kernels: statistics, apply
 }
 
-void Engine::layer_norm(const NormW& w, const float* x, long long rows, float* y, int dt, void* y3) {
-    if (dt < 0) dt = edt();
+void Engine::layer_norm(const NormW& w, const Act& x, const Act& y) {
+    const long long rows = x.rows();
+    const int dt = x.dt;
+    if (x.c != w.c || y.c != w.c || y.rows() != rows || y.dt != dt || !x.p || x.stride() != w.c || y.stride() != w.c || (y.p != nullptr) == (y.p3 != nullptr))
+        throw Error(SDMI_ERR_STATE, "layer_norm: dense rows of the norm's width and one storage type expected, the output in one form");
     ProfScope ps(this, PC_LAYER_NORM, 0, 2.0 * (double)rows * w.c * (dt ? 2.0 : 4.0));
     ps.set_tag("layer_norm rows%lld c%d", rows, w.c);
-    if (y3) {
+    if (y.p3) {
         if (dt) throw Error(SDMI_ERR_STATE, "layer_norm: planes are an fp32-engine format");
-        SDMI_HIP(launch_layer_norm_planes(x, y3, w.gamma, w.beta, (int)rows, w.c, w.eps, stream_));
-    } else if (dt) SDMI_HIP(launch_layer_norm_bf16(x, y, w.gamma, w.beta, (int)rows, w.c, w.eps, stream_));
-    else SDMI_HIP(launch_layer_norm(x, y, w.gamma, w.beta, (int)rows, w.c, w.eps, stream_));
-    count_kernel();
+        SDMI_LAUNCH_IN(ps, 0, launch_layer_norm_planes(x.p, y.p3, w.gamma, w.beta, (int)rows, w.c, w.eps, stream_));
+    } else if (dt) SDMI_LAUNCH_IN(ps, 0, launch_layer_norm_bf16(x.p, y.p, w.gamma, w.beta, (int)rows, w.c, w.eps, stream_));
+    else SDMI_LAUNCH_IN(ps, 0, launch_layer_norm(x.p, y.p, w.gamma, w.beta, (int)rows, w.c, w.eps, stream_));
 }
 
 // qkv_attention (attention.rs:5-45).  Head dims with a fused instance use the flash
 // kernel; others (the VAE's single 512-wide head) run QK^T -> row softmax -> PV on
 // the GEMM kernel, one (batch, head) at a time.
-void Engine::attention(const float* q, int ldq, long long q_bs, const float* k, int ldk, long long k_bs,
-                       const float* v, int ldv, long long v_bs, float* o, int ldo, long long o_bs, int n, int nq,
-                       int nk, int n_head, int d_head, const int* kv_len_dev, const int* kv_len_host,
-                       const float* mask, int mask_ld, int dt, void* o3, bool q_log2) {
-    if (dt < 0) dt = edt();
+void Engine::attention(const Attn& a) {
+    const int dt = a.dt < 0 ? edt() : a.dt, n = a.n, nq = a.nq, nk = a.nk, n_head = a.n_head, d_head = a.d_head;
+    const bool q_log2 = a.q_log2;
     if (nq <= 0 || nk <= 0) throw Error(SDMI_ERR_INVALID, "attention: empty sequence");
     AttnPlanIn in{};
-    in.n = n; in.n_head = n_head; in.nq = nq; in.nk = nk; in.d_head = d_head; in.bf16 = dt; in.has_mask = mask != nullptr; in.planes_out = o3 != nullptr;
-    in.rows_aligned = !((ldq | ldk | ldv | ldo) & (dt ? 7 : 3));
+    in.n = n; in.n_head = n_head; in.nq = nq; in.nk = nk; in.d_head = d_head; in.bf16 = dt; in.has_mask = a.mask != nullptr; in.planes_out = a.o3 != nullptr;
+    in.rows_aligned = !((a.q.ld | a.k.ld | a.v.ld | a.o.ld) & (dt ? 7 : 3));
     const AttnPlan plan = plan_attention(in, aopt_);   // kernel, workgroup form, key slices (attn_plan.cpp); refuses what no kernel serves
     // q_log2 (stated by the caller, Engine::q_prescaled): q arrives in log2 units (attn_bf16_q_scale: folded into the query weights at load, applied by
     // qkv_attention_dev's conversion); the bf16 kernel needs no scale, the widened fp32 kernel (attn_bf16=0) gets scale^2 = ln 2
@@ -2220,13 +2218,13 @@ void Engine::attention(const float* q, int ldq, long long q_bs, const float* k, 
     const float scale = q_log2 ? 0.83255461115769775635f : (float)std::pow((double)d_head, -0.25);
     if (plan.kernel != AttnKernel::Unfused) {
         AttnParams p{};
-        p.q = q; p.k = k; p.v = v; p.o = o; p.kv_len = kv_len_dev; p.mask = mask; p.mask_ld = mask_ld;
+        p.q = a.q.p; p.k = a.k.p; p.v = a.v.p; p.o = const_cast<float*>(a.o.p); p.kv_len = a.kv_len_dev; p.mask = a.mask; p.mask_ld = a.mask_ld;
         p.n = n; p.n_head = n_head; p.nq = nq; p.nk = nk; p.d_head = d_head;
-        p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-        p.q_bs = q_bs; p.k_bs = k_bs; p.v_bs = v_bs; p.o_bs = o_bs; p.scale = scale;
+        p.ldq = a.q.ld; p.ldk = a.k.ld; p.ldv = a.v.ld; p.ldo = a.o.ld;
+        p.q_bs = a.q.bs; p.k_bs = a.k.bs; p.v_bs = a.v.bs; p.o_bs = a.o.bs; p.scale = scale;
         p.bf16 = dt;
         p.q_log2 = q_log2 ? 1 : 0;
-        p.o3 = o3; p.ldo3 = (n_head * d_head / 32) * 192;
+        p.o3 = a.o3; p.ldo3 = (n_head * d_head / 32) * 192;
         const double fl = 4.0 * n * n_head * (double)nq * nk * d_head;
         const int kv_splits = plan.kv_splits;
         std::unique_ptr<Buf> part_o, part_ml;
@@ -2237,16 +2235,14 @@ void Engine::attention(const float* q, int ldq, long long q_bs, const float* k, 
         }
         ProfScope ps(this, PC_ATTENTION, fl, 0, kv_splits > 1 ? 2 : 1);
         ps.set_tag("attention n%d nq%d nk%d h%d d%d slices=%d", n, nq, nk, n_head, d_head, kv_splits);
-        if (plan.kernel == AttnKernel::Bf16) SDMI_HIP(launch_attention_bf16(p, plan, stream_));
-        else if (plan.kernel == AttnKernel::Split) SDMI_HIP(launch_attention_split(p, plan, stream_));
-        else SDMI_HIP(launch_attention(p, plan, stream_));
-        count_kernel(fl);
-        if (kv_splits > 1) {
-            SDMI_HIP(launch_attention_combine(p, stream_));
-            count_kernel();
-        }
+        if (plan.kernel == AttnKernel::Bf16) SDMI_LAUNCH_IN(ps, fl, launch_attention_bf16(p, plan, stream_));
+        else if (plan.kernel == AttnKernel::Split) SDMI_LAUNCH_IN(ps, fl, launch_attention_split(p, plan, stream_));
+        else SDMI_LAUNCH_IN(ps, fl, launch_attention(p, plan, stream_));
+        if (kv_splits > 1) SDMI_LAUNCH_IN(ps, 0, launch_attention_combine(p, stream_));
         return;
     }
+    const int* kv_len_host = a.kv_len_host;
+    const int ldq = a.q.ld, ldk = a.k.ld, ldv = a.v.ld, ldo = a.o.ld;
     for (int b = 0; b < n; ++b)   // every sample's key count before the first launch
         if ((kv_len_host ? kv_len_host[b] : nk) % (dt ? 64 : 32)) throw Error(SDMI_ERR_UNSUPPORTED, "attention (unfused path): key count must be a multiple of 32 (64 for bf16)");
     for (int b = 0; b < n; ++b) {
@@ -2255,22 +2251,20 @@ void Engine::attention(const float* q, int ldq, long long q_bs, const float* k, 
         Buf pb(this, dt ? (size_t)nq * nkb * 2 : 256);             // bf16 probabilities (precision = 1)
         Buf vt(this, (size_t)d_head * nkb * (dt ? 2 : 4));
         for (int h = 0; h < n_head; ++h) {
-            const float* qb = adv(q, b * q_bs + h * d_head, dt);
-            const float* kb = adv(k, b * k_bs + h * d_head, dt);
-            const float* vb = adv(v, b * v_bs + h * d_head, dt);
-            float* ob = adv(o, b * o_bs + h * d_head, dt);
+            const float* qb = adv(a.q.p, b * a.q.bs + h * d_head, dt);
+            const float* kb = adv(a.k.p, b * a.k.bs + h * d_head, dt);
+            const float* vb = adv(a.v.p, b * a.v.bs + h * d_head, dt);
+            float* ob = adv(a.o.p, b * a.o.bs + h * d_head, dt);
             ConvGemm g{};
             g.A = qb; g.Bt = kb; g.C = s.f();
             g.M = nq; g.N = nkb; g.K = d_head; g.NB = 1; g.Hs = 1; g.Ws = nq; g.Cin = d_head; g.Ho = 1; g.Wo = nq;
             g.KH = g.KW = 1; g.stride = 1; g.ldc = nkb; g.ldr = nkb; g.a_ld = ldq; g.b_ld = ldk; g.CS = 32;
             g.out_mode = dt ? 1 : 0;
             launch_gemm(g, dt);
-            if (dt) { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_softmax_rows_f32_to_bf16(s.f(), pb.p, nq, nkb, scale * scale, stream_)); }
-            else { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_softmax_rows(s.f(), nq, nkb, scale * scale, stream_)); }
-            count_kernel();
-            if (dt) { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_transpose2d_bf16(vb, vt.p, nkb, d_head, ldv, stream_)); }
-            else { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_transpose2d(vb, vt.f(), nkb, d_head, ldv, stream_)); }
-            count_kernel();
+            if (dt) SDMI_LAUNCH(launch_softmax_rows_f32_to_bf16(s.f(), pb.p, nq, nkb, scale * scale, stream_));
+            else SDMI_LAUNCH(launch_softmax_rows(s.f(), nq, nkb, scale * scale, stream_));
+            if (dt) SDMI_LAUNCH(launch_transpose2d_bf16(vb, vt.p, nkb, d_head, ldv, stream_));
+            else SDMI_LAUNCH(launch_transpose2d(vb, vt.f(), nkb, d_head, ldv, stream_));
             ConvGemm g2{};
             g2.A = dt ? pb.f() : s.f(); g2.Bt = vt.f(); g2.C = ob;
             g2.M = nq; g2.N = d_head; g2.K = nkb; g2.NB = 1; g2.Hs = 1; g2.Ws = nq; g2.Cin = nkb; g2.Ho = 1; g2.Wo = nq;
@@ -2368,8 +2362,8 @@ void Engine::group_norm_fp8(const NormW& w, const Act& x, ActQ& y, bool silu) {
     if (x.dt != 1 || y.c != x.c) throw Error(SDMI_ERR_STATE, "group_norm_fp8: bf16 input of matching width expected");
     Buf part(this, gn_partials_bytes_bf16(x.n, hw, x.c, gn_tune_));
     ProfScope ps(this, PC_GROUP_NORM, 0, (double)x.bytes() + (double)x.rows() * (y.cp + y.cp / 32), 2);
-    SDMI_HIP(launch_group_norm_fp8(x.p, y.q, y.s, w.gamma, w.beta, x.n, hw, x.c, x.stride(), 32, w.eps, silu, part.p, stream_, &gn_tune_));
-    count_kernel(); count_kernel();
+    SDMI_LAUNCH_IN(ps, 0, launch_group_norm_fp8(x.p, y.q, y.s, w.gamma, w.beta, x.n, hw, x.c, x.stride(), 32, w.eps, silu, part.p, stream_, &gn_tune_));
+    count_kernel();   // statistics + apply
 }
 
 void Engine::conv_fp8(const ConvW& w, const ActQ& x, Act& y, const float* rowvec, const Act* resid, int stride, int ups, int rowvec_stride) {
@@ -2389,10 +2383,11 @@ void Engine::conv_fp8(const ConvW& w, const ActQ& x, Act& y, const float* rowvec
     launch_fp8(p, 2.0 * p.M * (double)p.N * w.cin * w.k * w.k);   // algorithmic (unpadded) work
 }
 
-// C[rows][n_rows_w] (bf16) = x W^T + bias (+ resid): a Linear layer on MXFP8 operands (n_rows_w = w.cout, or 3 cout for the packed q | k | v)
-void Engine::gemm_fp8(const ActQ& x, const LinW& w, int n_rows_w, void* C, int ldc, const float* resid, int ldr) {
-    if (x.c != w.cin || !w.bt8) throw Error(SDMI_ERR_STATE, "gemm_fp8: not an MXFP8-packed Linear layer");
-    ConvGemm p = linear_gemm(reinterpret_cast<const float*>(x.q), (int)x.rows(), w.bt8, w.bias, x.cp, n_rows_w, reinterpret_cast<float*>(C), ldc, resid, ldr);
+// y (bf16) = x W^T + bias (+ resid): a Linear layer on MXFP8 operands
+void Engine::linear(const LinW& w, const ActQ& x, const Act& y, const Act* resid) {
+    check_linear(w, x.rows(), x.c, y, resid);
+    if (!w.bt8 || y.dt != 1 || !y.p) throw Error(SDMI_ERR_STATE, "linear: not an MXFP8-packed Linear layer with a bf16 output");
+    ConvGemm p = linear_gemm(reinterpret_cast<const float*>(x.q), (int)x.rows(), w.bt8, w.bias, x.cp, y.c, y.p, y.stride(), resid ? resid->p : nullptr, resid ? resid->stride() : 0);
     p.a_scale = x.s; p.b_scale = w.bs8; p.CS = 128;
     launch_fp8(p, 2.0 * p.M * (double)p.N * w.cin);
 }
@@ -2428,15 +2423,14 @@ void Engine::conv_raw(const ConvW& w, const Act& x, Act& y, int stride, int ups)
 void Engine::quantize(const Act& x, ActQ& y) {
     if (x.dt != 1 || !x.p || y.c != x.c || y.rows() != x.rows()) throw Error(SDMI_ERR_STATE, "quantize: bf16 input of matching shape expected");
     ProfScope ps(this, PC_OTHER, 0, (double)x.rows() * (x.c * 2.0 + y.cp * 1.03));
-    SDMI_HIP(launch_quantize_bf16_fp8(x.p, y.q, y.s, x.rows(), x.c, x.stride(), stream_));
-    count_kernel();
+    SDMI_LAUNCH_IN(ps, 0, launch_quantize_bf16_fp8(x.p, y.q, y.s, x.rows(), x.c, x.stride(), stream_));
 }
 
-void Engine::layer_norm_fp8(const NormW& w, const float* x, long long rows, ActQ& y) {
-    if (y.c != w.c || y.rows() != rows) throw Error(SDMI_ERR_STATE, "layer_norm_fp8: output shape mismatch");
+void Engine::layer_norm(const NormW& w, const Act& x, ActQ& y) {
+    const long long rows = x.rows();
+    if (y.c != w.c || y.rows() != rows || x.c != w.c || x.dt != 1 || !x.p || x.stride() != w.c) throw Error(SDMI_ERR_STATE, "layer_norm (MXFP8 out): dense bf16 rows of the norm's width expected");
     ProfScope ps(this, PC_LAYER_NORM, 0, (double)rows * (w.c * 2.0 + y.cp * 1.03));
-    SDMI_HIP(launch_layer_norm_fp8(x, y.q, y.s, w.gamma, w.beta, (int)rows, w.c, w.eps, stream_));
-    count_kernel();
+    SDMI_LAUNCH_IN(ps, 0, launch_layer_norm_fp8(x.p, y.q, y.s, w.gamma, w.beta, (int)rows, w.c, w.eps, stream_));
 }
 
 // SpatialTransformer::forward (unet/mod.rs:462-480) + TransformerBlock (:522-526) +
@@ -2450,12 +2444,25 @@ void Engine::spatial_transformer(const SpatialW& w, const Act& x, Act& y) {
     auto duplicate = [&](const Act& src) {   // [n] -> [2n] (dense, same type): both halves = src
         Act d2 = new_act(2 * src.n, src.h, src.w, src.c);
         ProfScope ps_o(this, PC_OTHER, 0, 3.0 * (double)src.bytes());
-        SDMI_HIP(launch_repeat_rows(src.p, d2.p, 2, (long long)(src.bytes() / 4), stream_));
-        count_kernel();
+        SDMI_LAUNCH_IN(ps_o, 0, launch_repeat_rows(src.p, d2.p, 2, (long long)(src.bytes() / 4), stream_));
         return d2;
     };
     const int C = w.c, hw = x.h * x.w;
     const int heads = unet_heads(C), d = C / heads;
+    // both attentions of the block: n samples of hw queries against nk keys -> o (fp32 / bf16 rows, or planes)
+    auto attend = [&](Attn& at, int n, int nk, const Act& o) {
+        at.o = attn_rows(o, hw); at.o3 = o.p3;
+        at.n = n; at.nq = hw; at.nk = nk; at.n_head = heads; at.d_head = d; at.q_log2 = q_prescaled(edt(), d);
+        attention(at);
+    };
+    auto cross_attend = [&](const Act& q, const Act& o) {   // against the hoisted K / V of the text context
+        Attn at;
+        const long long ctx_rows = (long long)y.n * us_.t_max;
+        at.k = attn_rows(rows_view(us_.kc.at(w.ctx_index), ctx_rows, C, edt()), us_.t_max);
+        at.v = attn_rows(rows_view(us_.vc.at(w.ctx_index), ctx_rows, C, edt()), us_.t_max);
+        at.q = attn_rows(q, hw); at.kv_len_dev = us_.kv_len_dev; at.kv_len_host = us_.kv_len_host.data();
+        attend(at, y.n, us_.t_max, o);
+    };
     if (y.n != x.n && use_fp8_wide(w.proj_in.bt8, y.rows()) && x.dt == 1 && y.dt == 1) {   // option fp8_linear: no shared form -- duplicate first
         Act x2 = duplicate(x);
         spatial_transformer(w, x2, y);
@@ -2477,40 +2484,38 @@ void Engine::spatial_transformer(const SpatialW& w, const Act& x, Act& y) {
         release(gq);
         {
             ActQ lnq = new_rowsq(M, C), aq = new_rowsq(M, C);
-            Buf q(this, (size_t)M * C * 2), a(this, (size_t)M * C * 2);
-            Act av; av.p = a.f(); av.n = 1; av.h = 1; av.w = (int)M; av.c = C; av.dt = 1;
-            layer_norm_fp8(w.ln1, h.p, M, lnq);
+            Act q = new_rows(M, C), a = new_rows(M, C);
+            layer_norm(w.ln1, h, lnq);
             {
-                Buf qkv(this, (size_t)M * 3 * C * 2);
-                gemm_fp8(lnq, w.attn1.q, 3 * C, qkv.p, 3 * C, nullptr, 0);      // q | k | v: the packed [3C][Kp] weight
-                const long long bs3 = (long long)hw * 3 * C;
-                attention(qkv.f(), 3 * C, bs3, adv(qkv.f(), C, 1), 3 * C, bs3, adv(qkv.f(), 2 * C, 1), 3 * C, bs3, a.f(), C,
-                          (long long)hw * C, nb, hw, hw, heads, d, nullptr, nullptr, nullptr, 0, -1, nullptr, q_prescaled(edt(), d));
+                Act qkv = new_rows(M, 3 * C);
+                linear(w.attn1.q, lnq, qkv);      // q | k | v: the packed [3C][Kp] weight
+                Attn at;
+                attn_packed_qkv(qkv, hw, at); attend(at, nb, hw, a);
+                release(qkv);
             }
-            quantize(av, aq);
-            gemm_fp8(aq, w.attn1.out, C, h.p, C, h.p, C);
-            layer_norm_fp8(w.ln2, h.p, M, lnq);
-            gemm_fp8(lnq, w.attn2.q, C, q.p, C, nullptr, 0);
-            const long long cbs = (long long)us_.t_max * C;
-            attention(q.f(), C, (long long)hw * C, us_.kc.at(w.ctx_index), C, cbs, us_.vc.at(w.ctx_index), C, cbs, a.f(),
-                      C, (long long)hw * C, nb, hw, us_.t_max, heads, d, us_.kv_len_dev, us_.kv_len_host.data(), nullptr, 0, -1, nullptr, q_prescaled(edt(), d));
-            ip_attention(w, q.f(), a.f(), nullptr, nb, hw, heads, d);   // IP-Adapter: + the image term, in front of the quantisation
-            quantize(av, aq);
-            gemm_fp8(aq, w.attn2.out, C, h.p, C, h.p, C);
-            layer_norm_fp8(w.ln3, h.p, M, lnq);
+            quantize(a, aq);
+            linear(w.attn1.out, aq, h, &h);
+            layer_norm(w.ln2, h, lnq);
+            linear(w.attn2.q, lnq, q);
+            cross_attend(q, a);
+            ip_attention(w, q, a, nb, hw, heads, d);   // IP-Adapter: + the image term, in front of the quantisation
+            quantize(a, aq);
+            linear(w.attn2.out, aq, h, &h);
+            layer_norm(w.ln3, h, lnq);
             {
-                Buf proj(this, (size_t)M * 8 * C * 2);
-                gemm_fp8(lnq, w.geglu_proj, 8 * C, proj.p, 8 * C, nullptr, 0);
+                Act proj = new_rows(M, 8 * C);
+                linear(w.geglu_proj, lnq, proj);
                 ActQ uq = new_rowsq(M, 4 * C);
                 {
                     ProfScope ps(this, PC_GEGLU, 0, (double)M * (8.0 * C * 2.0 + 4.0 * C * 1.03));
-                    SDMI_HIP(launch_geglu_fp8(proj.p, uq.q, uq.s, M, 4 * C, stream_));
-                    count_kernel();
+                    SDMI_LAUNCH_IN(ps, 0, launch_geglu_fp8(proj.p, uq.q, uq.s, M, 4 * C, stream_));
                 }
-                gemm_fp8(uq, w.mlp_lin, C, h.p, C, h.p, C);
+                linear(w.mlp_lin, uq, h, &h);
                 release(uq);
+                release(proj);
             }
             release(lnq); release(aq);
+            release(a); release(q);
         }
         ActQ hq = new_actq(x.n, x.h, x.w, C);
         quantize(h, hq);
@@ -2531,61 +2536,60 @@ void Engine::spatial_transformer(const SpatialW& w, const Act& x, Act& y) {
     Act x2{};                                                 // shared prefix: the block input once per half (proj_out's residual)
     bool folded = false;                                      // mlp_lin + proj_out ran as one paired launch (option proj_out_fold)
     {
-        const size_t es = esz();
+        // the row tensors of the block: planes only where their one consumer is a plane GEMM (pl), the storage type otherwise
+        const int form = pl ? 2 : 1;
         const size_t row3 = (size_t)(C / 32) * 192;
-        Buf ln(this, pl ? (size_t)M * row3 : (size_t)M * C * es), q(this, (size_t)M * C * es), a(this, pl ? (size_t)M * row3 : (size_t)M * C * es);
-        float* lnf = pl ? nullptr : ln.f();
-        void* ln3 = pl ? ln.p : nullptr;
-        float* af = pl ? nullptr : a.f();
-        void* a3 = pl ? a.p : nullptr;
+        Act ln = new_rows(M, C, form), q = new_rows(M, C), a = new_rows(M, C, form);
+        const Act ln1 = top(ln, M1), a1 = top(a, M1);   // in front of the cross attention: n1 samples
         // self attention: q, k, v in one GEMM (N = 3C) on the packed [3C][C] weight
-        layer_norm(w.ln1, h.p, M1, lnf, -1, ln3);
+        layer_norm(w.ln1, h, ln1);
         {
-            Buf qkv(this, (size_t)M1 * 3 * C * es);
-            gemm(lnf, (int)M1, w.attn1.q.bt, nullptr, C, 3 * C, qkv.f(), 3 * C, nullptr, 0, -1, 0, ln3);
-            const long long bs3 = (long long)hw * 3 * C;
-            attention(qkv.f(), 3 * C, bs3, adv(qkv.f(), C, edt()), 3 * C, bs3, adv(qkv.f(), 2 * C, edt()), 3 * C, bs3, af, C,
-                      (long long)hw * C, n1, hw, hw, heads, d, nullptr, nullptr, nullptr, 0, -1, a3, q_prescaled(edt(), d));
+            Act qkv = new_rows(M1, 3 * C);
+            linear(w.attn1.q, ln1, qkv);
+            Attn at;
+            attn_packed_qkv(qkv, hw, at); attend(at, n1, hw, a1);
+            release(qkv);
         }
-        gemm(af, (int)M1, w.attn1.out.bt, w.attn1.out.bias, C, C, h.p, C, h.p, C, -1, 0, a3);
+        linear(w.attn1.out, a1, h, &h);
         if (share) {   // from here on the halves differ: the hidden state and the block input, once per half
             Act h2 = duplicate(h);
             release(h);
             h = h2;
             x2 = duplicate(x);
         }
-        // cross attention against the hoisted K/V of the text context
-        layer_norm(w.ln2, h.p, M, lnf, -1, ln3);
-        gemm(lnf, (int)M, w.attn2.q.bt, nullptr, C, C, q.f(), C, nullptr, 0, -1, 0, ln3);
-        const long long cbs = (long long)us_.t_max * C;
-        attention(q.f(), C, (long long)hw * C, us_.kc.at(w.ctx_index), C, cbs, us_.vc.at(w.ctx_index), C, cbs, af,
-                  C, (long long)hw * C, nb, hw, us_.t_max, heads, d, us_.kv_len_dev, us_.kv_len_host.data(), nullptr, 0, -1, a3, q_prescaled(edt(), d));
-        ip_attention(w, q.f(), af, a3, nb, hw, heads, d);   // IP-Adapter: + the image term (planes: read-modify-write)
+        layer_norm(w.ln2, h, ln);
+        linear(w.attn2.q, ln, q);
+        cross_attend(q, a);
+        ip_attention(w, q, a, nb, hw, heads, d);   // IP-Adapter: + the image term (planes: read-modify-write)
         // Option proj_out_fold: y = x + proj_out(h + mlp_lin(u)) has no nonlinearity between its two layers, so with Wf = proj_out x mlp_lin folded at load
         // (rebuild_folds) it is y = x + Wf u + proj_out h + (bf + b_proj): ONE paired launch (linear_pair) whose extra K slices carry proj_out h.  h is then needed
         // as planes: the cross attention's output projection writes them next to its fp32 result.  A block whose fold is not fresh, or whose shape the planner does
         // not pair, runs the two launches.
         const Act& xr = share ? x2 : x;
-        std::unique_ptr<Buf> h3;
-        if (pl && opt_proj_out_fold_ && w.fold_fresh) h3.reset(new Buf(this, (size_t)M * row3));
-        void* const h3p = h3 ? h3->p : nullptr;
-        LinearPair lp{h3p /* (for the plan: any plane buffer) */, (int)(4 * row3), w.fold_bt, w.fold_bias, 4 * C, h3p, (int)row3, w.proj_out.bt, w.proj_out.bias, C,
+        Act h3{};
+        if (pl && opt_proj_out_fold_ && w.fold_fresh) h3 = new_rows(M, C, 2);
+        LinearPair lp{h3.p3 /* (for the plan: any plane buffer) */, (int)(4 * row3), w.fold_bt, w.fold_bias, 4 * C, h3.p3, (int)row3, w.proj_out.bt, w.proj_out.bias, C,
                       (int)M, C, xr.p, xr.stride(), y.p, y.stride(), y.p3, y.ld3, opt_proj_out_fold_ == 2};
-        const bool fold = h3p && xr.p && !xr.dt && !y.dt && xr.rows() == M && xr.c == C && y.rows() == M && y.c == C && linear_pair(lp, /*plan_only=*/true);
-        gemm(af, (int)M, w.attn2.out.bt, w.attn2.out.bias, C, C, h.p, C, h.p, C, -1, 0, a3, fold ? h3p : nullptr);
+        const bool fold = h3.p3 && xr.p && !xr.dt && !y.dt && xr.rows() == M && xr.c == C && y.rows() == M && y.c == C && linear_pair(lp, /*plan_only=*/true);
+        Act hh = h;   // the hidden state as attn2.out writes it, a view: fp32 and, for the pair, the planes h3 next to it
+        hh.view = true; hh.p3 = fold ? h3.p3 : nullptr; hh.ld3 = h3.ld3;
+        linear(w.attn2.out, a, hh, &h);
         // GEGLU MLP
-        layer_norm(w.ln3, h.p, M, lnf, -1, ln3);
+        layer_norm(w.ln3, h, ln);
         {
-            Buf u(this, pl ? (size_t)M * 4 * row3 : (size_t)M * 4 * C * es);
-            gemm_geglu(lnf, M, w.geglu_proj.bt, w.geglu_proj.bias, C, 4 * C, pl ? nullptr : u.f(), -1, ln3, pl ? u.p : nullptr);
-            lp.u3 = u.p;
+            Act u = new_rows(M, 4 * C, form);
+            gemm_geglu(w.geglu_proj, ln, u);
+            lp.u3 = u.p3;
             if (fold && linear_pair(lp)) folded = true;
             else if (pl) {
                 hp = new_act3(nb, x.h, x.w, C, 2);
-                gemm(nullptr, (int)M, w.mlp_lin.bt, w.mlp_lin.bias, 4 * C, C, nullptr, C, h.p, C, -1, 0, u.p, hp.p3);   // h + mlp -> planes only
+                linear(w.mlp_lin, u, hp, &h);   // h + mlp -> planes only
             }
-            else gemm(u.f(), (int)M, w.mlp_lin.bt, w.mlp_lin.bias, 4 * C, C, h.p, C, h.p, C);
+            else linear(w.mlp_lin, u, h, &h);
+            release(u);
         }
+        if (h3.p3) release(h3);
+        release(a); release(q); release(ln);
     }
     const Act& xr = share ? x2 : x;
     if (pl && !folded) { conv(w.proj_out, hp, y, 1, 0, nullptr, 0, &xr); release(hp); }
@@ -2606,8 +2610,9 @@ void Engine::vae_attn(const VaeAttnW& w, const Act& x, Act& y) {
     conv(w.v, g, v, 1, 0, nullptr, 0, nullptr);
     release(g);
     Act a = new_act(x.n, x.h, x.w, C);
-    const long long bs = (long long)hw * C;
-    attention(q.p, C, bs, k.p, C, bs, v.p, C, bs, a.p, C, bs, x.n, hw, hw, 1, C, nullptr, nullptr, nullptr, 0);
+    Attn at;
+    at.q = attn_rows(q, hw); at.k = attn_rows(k, hw); at.v = attn_rows(v, hw); at.o = attn_rows(a, hw); at.n = x.n; at.nq = hw; at.nk = hw; at.n_head = 1; at.d_head = C;
+    attention(at);
     release(q); release(k); release(v);
     conv(w.proj_out, a, y, 1, 0, nullptr, 0, &x);
     release(a);
@@ -2668,52 +2673,45 @@ void Engine::unet_prepare_rows(const float* ctx_packed, int nb, int t_max, const
     SDMI_HIP(hipMemcpyAsync(t_dev, ti ? (const void*)ti : (const void*)tf, S * sizeof(int), hipMemcpyHostToDevice, stream_));
     SDMI_HIP(hipStreamSynchronize(stream_));  // host vectors may go away; once per call, outside the step loop
 
-    Buf te(this, (size_t)S * mc * 4), e1(this, (size_t)S * ed * 4), e2(this, (size_t)S * ed * 4);
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(ti ? launch_timestep_embedding(t_dev, S, mc, te.f(), stream_)
-                                                  : launch_timestep_embedding_f(reinterpret_cast<const float*>(t_dev), S, mc, te.f(), stream_)); }
-    count_kernel();
-    gemm(te.f(), S, lin1_time_.bt, lin1_time_.bias, mc, ed, e1.f(), ed, nullptr, 0, /*dt=*/0);
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_silu(e1.f(), e1.f(), (long long)S * ed, stream_)); }
-    count_kernel();
-    gemm(e1.f(), S, lin2_time_.bt, lin2_time_.bias, ed, ed, e2.f(), ed, nullptr, 0, /*dt=*/0);
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_silu(e2.f(), e2.f(), (long long)S * ed, stream_)); }  // SiLU(emb), shared by all ResBlocks
-    count_kernel();
+    // the time embedding and everything made from it are fp32 at every precision
+    Buf te_buf(this, (size_t)S * mc * 4), e1_buf(this, (size_t)S * ed * 4), e2_buf(this, (size_t)S * ed * 4);
+    const Act te = rows_view(te_buf.p, S, mc, 0), e1 = rows_view(e1_buf.p, S, ed, 0), e2 = rows_view(e2_buf.p, S, ed, 0);
+    SDMI_LAUNCH(ti ? launch_timestep_embedding(t_dev, S, mc, te.p, stream_) : launch_timestep_embedding_f(reinterpret_cast<const float*>(t_dev), S, mc, te.p, stream_));
+    auto time_mlp = [&](const LinW& l1, const LinW& l2) {   // e2 = SiLU(emb), shared by all ResBlocks
+        linear(l1, te, e1);
+        SDMI_LAUNCH(launch_silu(e1.p, e1.p, (long long)S * ed, stream_));
+        linear(l2, e1, e2);
+        SDMI_LAUNCH(launch_silu(e2.p, e2.p, (long long)S * ed, stream_));
+    };
+    auto embed_rows = [&](size_t i) {   // ResBlock i's Linear(SiLU(emb)) for every step
+        const ResW& r = *res_list_[i];
+        us_.temb[i] = (float*)own((size_t)S * r.cout * 4);
+        linear(r.lin_embed, e2, rows_view(us_.temb[i], S, r.cout, 0));
+    };
+    time_mlp(lin1_time_, lin2_time_);
     // (the ControlNet's blocks follow the UNet's in res_list_ / st_list_: their rows exist in a controlled call only)
     const size_t n_res = ctrl ? res_list_.size() : n_res_unet_, n_st = ctrl ? st_list_.size() : n_st_unet_;
     us_.temb.resize(n_res);
-    for (size_t i = 0; i < n_res_unet_; ++i) {
-        const ResW& r = *res_list_[i];
-        us_.temb[i] = (float*)own((size_t)S * r.cout * 4);
-        gemm(e2.f(), S, r.lin_embed.bt, r.lin_embed.bias, ed, r.cout, us_.temb[i], r.cout, nullptr, 0, /*dt=*/0);
-    }
+    for (size_t i = 0; i < n_res_unet_; ++i) embed_rows(i);
     if (ctrl) {   // the ControlNet has a time MLP of its own (cldm.py: self.time_embed)
-        gemm(te.f(), S, ctl_lin1_time_.bt, ctl_lin1_time_.bias, mc, ed, e1.f(), ed, nullptr, 0, /*dt=*/0);
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_silu(e1.f(), e1.f(), (long long)S * ed, stream_)); }
-        count_kernel();
-        gemm(e1.f(), S, ctl_lin2_time_.bt, ctl_lin2_time_.bias, ed, ed, e2.f(), ed, nullptr, 0, /*dt=*/0);
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_silu(e2.f(), e2.f(), (long long)S * ed, stream_)); }
-        count_kernel();
-        for (size_t i = n_res_unet_; i < n_res; ++i) {
-            const ResW& r = *res_list_[i];
-            us_.temb[i] = (float*)own((size_t)S * r.cout * 4);
-            gemm(e2.f(), S, r.lin_embed.bt, r.lin_embed.bias, ed, r.cout, us_.temb[i], r.cout, nullptr, 0, /*dt=*/0);
-        }
+        time_mlp(ctl_lin1_time_, ctl_lin2_time_);
+        for (size_t i = n_res_unet_; i < n_res; ++i) embed_rows(i);
     }
     us_.kc.resize(n_st);
     us_.vc.resize(n_st);
-    const float* ctx_e = ctx_packed;  // text context in the engine's storage type
-    Buf ctx_h(this, bf16_ ? (size_t)nb * t_max * cd * 2 : 256);
+    const long long ctx_rows = (long long)nb * t_max;
+    Act ctx = rows_view(ctx_packed, ctx_rows, cd, 0);  // text context in the engine's storage type
+    Buf ctx_h(this, bf16_ ? (size_t)ctx_rows * cd * 2 : 256);
     if (bf16_) {
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_f32_to_bf16(ctx_packed, ctx_h.p, (long long)nb * t_max * cd, stream_)); }
-        count_kernel();
-        ctx_e = ctx_h.f();
+        SDMI_LAUNCH(launch_f32_to_bf16(ctx_packed, ctx_h.p, ctx_rows * cd, stream_));
+        ctx = rows_view(ctx_h.p, ctx_rows, cd, 1);
     }
     for (size_t i = 0; i < n_st; ++i) {
         const SpatialW& s = *st_list_[i];
-        us_.kc[i] = (float*)own((size_t)nb * t_max * s.c * esz());
-        us_.vc[i] = (float*)own((size_t)nb * t_max * s.c * esz());
-        gemm(ctx_e, nb * t_max, s.attn2.k.bt, nullptr, cd, s.c, us_.kc[i], s.c, nullptr, 0);
-        gemm(ctx_e, nb * t_max, s.attn2.v.bt, nullptr, cd, s.c, us_.vc[i], s.c, nullptr, 0);
+        us_.kc[i] = (float*)own((size_t)ctx_rows * s.c * esz());
+        us_.vc[i] = (float*)own((size_t)ctx_rows * s.c * esz());
+        linear(s.attn2.k, ctx, rows_view(us_.kc[i], ctx_rows, s.c, edt()));
+        linear(s.attn2.v, ctx, rows_view(us_.vc[i], ctx_rows, s.c, edt()));
     }
     // an adapted call (IP-Adapter): K_ip / V_ip of the nb batch rows are made by the first step inside the window (unet_run), so a call without one runs the plain launches
     us_.ip_want = ip_.set && ip_.scale != 0.f && n_images > 0;
@@ -2825,8 +2823,7 @@ void Engine::freeu_filter(const Act* const* cats, const int* cx, const float* s,
     }
     if (!ff.n_seg) return;
     if (record_shapes_) ++choice_counts_["freeu_filter segs=" + std::to_string(ff.n_seg) + " planes=" + std::to_string(planes) + " dt=" + std::to_string(ff.dt)];
-    { ProfScope ps_o(this, PC_OTHER, 0, bytes); ps_o.set_tag("freeu_filter"); SDMI_HIP(launch_freeu_filter(ff, stream_)); }
-    count_kernel();
+    { ProfScope ps_o(this, PC_OTHER, 0, bytes); ps_o.set_tag("freeu_filter"); SDMI_LAUNCH_IN(ps_o, 0, launch_freeu_filter(ff, stream_)); }
 }
 
 void Engine::freeu_backbone(const Act& cat, int cx, float b, int version) {
@@ -2843,13 +2840,11 @@ void Engine::freeu_backbone(const Act& cat, int cx, float b, int version) {
     if (version == 2) {
         mean.reset(new Buf(this, (size_t)h.rows() * sizeof(float)));
         { ProfScope ps_o(this, PC_OTHER, 0, (double)h.rows() * (cx * es + 4.0)); ps_o.set_tag("freeu_mean");
-          SDMI_HIP(launch_freeu_mean(cat.p, mean->f(), h.rows(), cx, cat.stride(), edt(), stream_)); }
-        count_kernel();
+          SDMI_LAUNCH_IN(ps_o, 0, launch_freeu_mean(cat.p, mean->f(), h.rows(), cx, cat.stride(), edt(), stream_)); }
         a.mean = mean->f();
     }
     { ProfScope ps_o(this, PC_OTHER, 0, (double)h.rows() * h.c * (edt() ? 4.0 : (a.y3 ? 14.0 : 8.0))); ps_o.set_tag("freeu_backbone");
-      SDMI_HIP(launch_freeu_backbone(a, stream_)); }
-    count_kernel();
+      SDMI_LAUNCH_IN(ps_o, 0, launch_freeu_backbone(a, stream_)); }
 }
 
 Act Engine::control_hint_embed(const uint8_t* hint_rgb_dev, int n, int hint_h, int hint_w) {
@@ -2860,8 +2855,7 @@ Act Engine::control_hint_embed(const uint8_t* hint_rgb_dev, int n, int hint_h, i
     const size_t per = (size_t)emb.h * emb.w * emb.c;
     for (int img = 0; img < n; ++img) {
         Act x = new_act(1, hint_h, hint_w, 4, /*dt=*/0);
-        { ProfScope ps_o(this, PC_OTHER, 0, (double)x.rows() * 19.0); SDMI_HIP(launch_hint_u8_to_nhwc4(hint_rgb_dev + (size_t)img * hint_h * hint_w * 3, x.p, x.rows(), stream_)); }
-        count_kernel();
+        { ProfScope ps_o(this, PC_OTHER, 0, (double)x.rows() * 19.0); SDMI_LAUNCH_IN(ps_o, 0, launch_hint_u8_to_nhwc4(hint_rgb_dev + (size_t)img * hint_h * hint_w * 3, x.p, x.rows(), stream_)); }
         for (int i = 0; i < 8; ++i) {
             const ConvW& w = ctl_hint_[i];
             const int stride = (i == 2 || i == 4 || i == 6) ? 2 : 1;
@@ -2871,8 +2865,8 @@ Act Engine::control_hint_embed(const uint8_t* hint_rgb_dev, int n, int hint_h, i
             conv(w, x, y, stride, 0, nullptr, 0, nullptr);
             release(x);
             if (i != 7) {
-                { ProfScope ps_o(this, PC_OTHER, 0, (double)y.rows() * y.c * 8.0); SDMI_HIP(launch_silu(y.p, y.p, y.rows() * y.c, stream_)); }
-                count_kernel();
+                ProfScope ps_o(this, PC_OTHER, 0, (double)y.rows() * y.c * 8.0);
+                SDMI_LAUNCH_IN(ps_o, 0, launch_silu(y.p, y.p, y.rows() * y.c, stream_));
             }
             x = y;
         }
@@ -2918,8 +2912,7 @@ void Engine::control_hint_embed_dev(const uint8_t* hint_rgb, int n, int hint_h, 
     if (n < 1 || hint_h < 64 || hint_w < 64 || hint_h % 64 || hint_w % 64) throw Error(SDMI_ERR_INVALID, "control_hint_embed: n >= 1, hint_h / hint_w positive multiples of 64");
     check_batch(n);
     Act emb = control_hint_embed(hint_rgb, n, hint_h, hint_w);
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(emb.p, out_nchw, n, emb.c, emb.h, emb.w, stream_)); }
-    count_kernel();
+    SDMI_LAUNCH(launch_nhwc_to_nchw(emb.p, out_nchw, n, emb.c, emb.h, emb.w, stream_));
     release(emb);
 }
 
@@ -2943,15 +2936,13 @@ void Engine::control_residuals_dev(const float* x_nchw, int t, const float* cont
     std::vector<int> kv(n, T), ts(1, t);
     unet_prepare(context, n, T, kv.data(), ts, n, /*window=*/false, /*force_control=*/true);
     Buf xin(this, (size_t)n * H * W * 4 * 4);
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nchw_to_nhwc(x_nchw, xin.f(), n, 4, H, W, 1.0f, stream_)); }
-    count_kernel();
+    SDMI_LAUNCH(launch_nchw_to_nhwc(x_nchw, xin.f(), n, 4, H, W, 1.0f, stream_));
     Act r[13];
     control_run(xin.f(), n, 0, r);
     size_t off = 0;
     for (auto& a : r) {
-        if (a.dt) SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(a.p, out + off, a.n, a.c, a.h, a.w, stream_));
-        else { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(a.p, out + off, a.n, a.c, a.h, a.w, stream_)); }
-        count_kernel();
+        if (a.dt) { SDMI_HIP(launch_nhwc_bf16_to_nchw_f32(a.p, out + off, a.n, a.c, a.h, a.w, stream_)); count_kernel(); }   // (outside the profile, counted)
+        else SDMI_LAUNCH(launch_nhwc_to_nchw(a.p, out + off, a.n, a.c, a.h, a.w, stream_));
         off += (size_t)a.rows() * a.c;
         release(a);
     }
@@ -3069,8 +3060,7 @@ void Engine::unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bo
             for (int j = 0; j < ca.n_seg; ++j) planes += ca.seg[j].y3 ? 1 : 0;
             ++choice_counts_["control_add segs=" + std::to_string(ca.n_seg) + " planes=" + std::to_string(planes) + " dt=" + std::to_string(ca.dt)];
         }
-        { ProfScope ps_o(this, PC_OTHER, 0, bytes); ps_o.set_tag("control_add"); SDMI_HIP(launch_control_add(ca, stream_)); }
-        count_kernel();
+        { ProfScope ps_o(this, PC_OTHER, 0, bytes); ps_o.set_tag("control_add"); SDMI_LAUNCH_IN(ps_o, 0, launch_control_add(ca, stream_)); }
         for (auto& a : ctl_r) release(a);
     }
     if (freeu) {
@@ -3122,31 +3112,34 @@ void Engine::clip_forward_dev(const int32_t* tokens, const int32_t* emb_row, con
     if (emb_row && !emb_bank_) throw Error(SDMI_ERR_INVALID, "clip_forward: embedding rows given, but the context has no embeddings");
     const int C = cfg_.ctx_dim, H = cfg_.clip_heads;
     const long long M = (long long)n * T;
-    Buf x(this, (size_t)M * C * 4), h(this, (size_t)M * C * 4), qkv(this, (size_t)M * 3 * C * 4), a(this, (size_t)M * C * 4);
-    Buf f(this, (size_t)M * 4 * C * 4), mask(this, (size_t)T * T * 4);
-    if (emb_row) { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_clip_embed_bank(tokens, emb_row, clip_tok_, emb_bank_, clip_pos_, x.f(), n, T, C, stream_)); }
-    else { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_clip_embed(tokens, clip_tok_, clip_pos_, x.f(), n, T, C, stream_)); }
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_causal_mask(mask.f(), T, stream_)); }
-    count_kernel(); count_kernel();
+    Act x = new_rows(M, C, 1, 0), h = new_rows(M, C, 1, 0), qkv = new_rows(M, 3 * C, 1, 0), a = new_rows(M, C, 1, 0), f = new_rows(M, 4 * C, 1, 0);
+    Act mask = new_rows(T, T, 1, 0);
+    if (emb_row) SDMI_LAUNCH(launch_clip_embed_bank(tokens, emb_row, clip_tok_, emb_bank_, clip_pos_, x.p, n, T, C, stream_));
+    else SDMI_LAUNCH(launch_clip_embed(tokens, clip_tok_, clip_pos_, x.p, n, T, C, stream_));
+    SDMI_LAUNCH(launch_causal_mask(mask.p, T, stream_));
+    Attn at;
+    attn_packed_qkv(qkv, T, at); at.o = attn_rows(a, T);
+    at.n = n; at.nq = T; at.nk = T; at.n_head = H; at.d_head = C / H;
+    at.mask = mask.p; at.mask_ld = T; at.dt = 0;
     const int n_blocks = cfg_.clip_layers - clip_skip + 1;   // the web UI's "CLIP skip s": hidden_states[-s] through the final LayerNorm
     for (int bi = 0; bi < n_blocks; ++bi) {
         const ClipBlockW& b = clip_blocks_[bi];
-        layer_norm(b.attn_ln, x.f(), M, h.f(), 0);
-        gemm(h.f(), (int)M, b.q.bt, b.q.bias, C, 3 * C, qkv.f(), 3 * C, nullptr, 0, 0);       // query | key | value, one GEMM
-        attention(qkv.f(), 3 * C, (long long)T * 3 * C, qkv.f() + C, 3 * C, (long long)T * 3 * C, qkv.f() + 2 * C, 3 * C,
-                  (long long)T * 3 * C, a.f(), C, (long long)T * C, n, T, T, H, C / H, nullptr, nullptr, mask.f(), T, 0);
-        gemm(a.f(), (int)M, b.out.bt, b.out.bias, C, C, x.f(), C, x.f(), C, 0);               // x += out(attn)
-        layer_norm(b.mlp_ln, x.f(), M, h.f(), 0);
-        gemm(h.f(), (int)M, b.fc1.bt, b.fc1.bias, C, 4 * C, f.f(), 4 * C, nullptr, 0, 0);
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(cfg_.variant == 1 ? launch_gelu_erf(f.f(), M * 4 * C, stream_) : launch_quick_gelu(f.f(), M * 4 * C, stream_)); }
-        count_kernel();
-        gemm(f.f(), (int)M, b.fc2.bt, b.fc2.bias, 4 * C, C, x.f(), C, x.f(), C, 0);           // x += fc2(gelu(fc1))
+        layer_norm(b.attn_ln, x, h);
+        linear(b.q, h, qkv);         // query | key | value, one GEMM
+        attention(at);
+        linear(b.out, a, x, &x);     // x += out(attn)
+        layer_norm(b.mlp_ln, x, h);
+        linear(b.fc1, h, f);
+        SDMI_LAUNCH(cfg_.variant == 1 ? launch_gelu_erf(f.p, M * 4 * C, stream_) : launch_quick_gelu(f.p, M * 4 * C, stream_));
+        linear(b.fc2, f, x, &x);     // x += fc2(gelu(fc1))
     }
-    layer_norm(clip_ln_, x.f(), M, out, 0);
+    layer_norm(clip_ln_, x, rows_view(out, M, C, 0));
     if (weights) {
-        { ProfScope ps_o(this, PC_OTHER, 0, (double)M * C * 12.0); ps_o.set_tag("clip_reweight"); SDMI_HIP(launch_clip_reweight(out, weights, n, T, C, stream_)); }
-        count_kernel();
+        ProfScope ps(this, PC_OTHER, 0, (double)M * C * 12.0);
+        ps.set_tag("clip_reweight");
+        SDMI_LAUNCH_IN(ps, 0, launch_clip_reweight(out, weights, n, T, C, stream_));
     }
+    release(mask); release(f); release(a); release(qkv); release(h); release(x);
 }
 
 // ---- textual-inversion embeddings (include/sdmi.h "web-UI prompt encoding") ------------------------------------------------
@@ -3221,8 +3214,7 @@ void Engine::embedding_load_safetensors(const std::string& name, const std::vect
     if (v > cfg_.clip_ctx - 2) throw Error(SDMI_ERR_INVALID, "embedding_load_safetensors: '" + t->key + "' has " + std::to_string(v) + " vectors; at most clip_ctx - 2 fit a chunk");
     Buf raw(this, t->nbytes), wide(this, t->count * sizeof(float));
     SDMI_HIP(hipMemcpyAsync(raw.p, t->data, t->nbytes, hipMemcpyHostToDevice, stream_));
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_unpack_tensor(raw.p, dt, 0, (long long)t->count, 1, wide.f(), stream_)); }
-    count_kernel();
+    SDMI_LAUNCH(launch_unpack_tensor(raw.p, dt, 0, (long long)t->count, 1, wide.f(), stream_));
     embedding_add(name, ids, wide.f(), (int)v, true);   // synchronises: the mapping and the two buffers outlive the copies
 }
 
@@ -3240,8 +3232,7 @@ float* Engine::cond_to_nhwc(const float* cond_nchw, int n) {
     const long long hw = (long long)lat_h_ * lat_w_;
     const int pcc = unet_in_padded() - 4;
     float* c = reinterpret_cast<float*>(pool_.alloc((size_t)n * hw * pcc * sizeof(float)));
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_cond_nchw_to_nhwc(cond_nchw, c, n, cond_ch(), hw, pcc, stream_)); }
-    count_kernel();
+    SDMI_LAUNCH(launch_cond_nchw_to_nhwc(cond_nchw, c, n, cond_ch(), hw, pcc, stream_));
     return c;
 }
 
@@ -3250,8 +3241,7 @@ void Engine::assemble_unet_in(const float* unet_in, const float* cond_nhwc, int 
     const long long hw = (long long)lat_h_ * lat_w_;
     const int pc = unet_in_padded();
     ProfScope ps_o(this, PC_OTHER, 0, (double)rows * hw * (4 + (pc - 4) + pc) * 4.0);
-    SDMI_HIP(launch_assemble_unet_in(unet_in, cond_nhwc, dst, (long long)rows * hw, (long long)n * hw, pc, cond_ch(), stream_));
-    count_kernel();
+    SDMI_LAUNCH_IN(ps_o, 0, launch_assemble_unet_in(unet_in, cond_nhwc, dst, (long long)rows * hw, (long long)n * hw, pc, cond_ch(), stream_));
 }
 
 void Engine::unet_forward_dev(const float* x_nchw, int t, const float* context, int n, int T, float* out_nchw, const float* cond_nchw) {
@@ -3263,8 +3253,7 @@ void Engine::unet_forward_dev(const float* x_nchw, int t, const float* context, 
     std::vector<int> kv(n, T), ts(1, t);
     unet_prepare(context, n, T, kv.data(), ts, n, /*window=*/false);
     Buf xin(this, (size_t)n * H * W * 4 * 4), xout(this, (size_t)n * H * W * 4 * 4);
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nchw_to_nhwc(x_nchw, xin.f(), n, 4, H, W, 1.0f, stream_)); }
-    count_kernel();
+    SDMI_LAUNCH(launch_nchw_to_nhwc(x_nchw, xin.f(), n, 4, H, W, 1.0f, stream_));
     if (cond_nchw) {
         Buf xc(this, (size_t)n * H * W * unet_in_padded() * 4);
         float* c = cond_to_nhwc(cond_nchw, n);
@@ -3273,8 +3262,7 @@ void Engine::unet_forward_dev(const float* x_nchw, int t, const float* context, 
         unet_run(xc.f(), n, 0, xout.f());
     } else
     unet_run(xin.f(), n, 0, xout.f());
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(xout.f(), out_nchw, n, 4, H, W, stream_)); }
-    count_kernel();
+    SDMI_LAUNCH(launch_nhwc_to_nchw(xout.f(), out_nchw, n, 4, H, W, stream_));
     unet_release();
 }
 
@@ -3295,9 +3283,9 @@ void Engine::sample_latent_dev(const float* context, int n, int T, const float* 
     std::vector<double> kplan;   // a k-sampler plans its own schedule; init_latent is the VP latent at its first sigma
     if (kset_) kplan = kplan_for(n_steps, 1.0, nullptr);
     sample_loop(context, n, T, uncond, Tu, scale, ts, step_size, [&](float* latent, float* unet_in, long long per_half) {
-        SDMI_HIP(launch_nchw_to_nhwc(init_latent, latent, n, 4, H, W, 1.0f, stream_));
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_dup_latent(latent, unet_in, per_half, stream_)); }
-        count_kernel(); count_kernel();
+        SDMI_HIP(launch_nchw_to_nhwc(init_latent, latent, n, 4, H, W, 1.0f, stream_));   // (outside the profile, counted)
+        count_kernel();
+        SDMI_LAUNCH(launch_dup_latent(latent, unet_in, per_half, stream_));
     }, nullptr, latent_out, out_nhwc, nullptr, kset_ ? &kplan : nullptr);
 }
 
@@ -3445,10 +3433,8 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
         const float* q_prev[3] = {p.n_hist ? hist[0]->f() : nullptr, nullptr, nullptr};
         const uint64_t key = ksampler_.noise_seed + (uint64_t)ksampler_.image_base + (((uint64_t)k[KP_STEP] + 1) << 32);
         const bool bl = blend && last;
-        { ProfScope ps_o(this, PC_OTHER);
-          SDMI_HIP(launch_sampler_step(eps.f(), latent.f(), unet_in.f(), per_half, (long long)H * W, p, rescale, depth, q_prev, depth ? hist[0]->f() : nullptr, key,
-                                       key + (1ull << 62), bl ? blend->mask : nullptr, bl ? blend->z0 : nullptr, bl ? blend->eps : nullptr, stream_)); }
-        count_kernel();
+        SDMI_LAUNCH(launch_sampler_step(eps.f(), latent.f(), unet_in.f(), per_half, (long long)H * W, p, rescale, depth, q_prev, depth ? hist[0]->f() : nullptr, key,
+                                        key + (1ull << 62), bl ? blend->mask : nullptr, bl ? blend->z0 : nullptr, bl ? blend->eps : nullptr, stream_));
     }
     for (size_t s = 0; s < (kplan ? 0 : ts.size()); ++s) {
         const size_t t = (size_t)ts[s];
@@ -3477,19 +3463,16 @@ void Engine::sample_loop(const float* context, int n, int T, const float* uncond
             // index of this step in the FULL schedule (ts may be its img2img tail): the noise key does not depend on strength
             const uint64_t s_full = (uint64_t)((alphas_.size() - 1 - t) / step_size);
             const uint64_t key = sampler_.noise_seed + (uint64_t)sampler_.image_base + ((s_full + 1) << 32);
-            ProfScope ps_o(this, PC_OTHER);
-            SDMI_HIP(launch_sampler_step(eps.f(), latent.f(), unet_in.f(), per_half, (long long)H * W, p, rescale, depth, q_prev, q_out, key, 0,
-                                         blend ? blend->mask : nullptr, blend ? blend->z0 : nullptr, blend ? blend->eps : nullptr, stream_));
+            SDMI_LAUNCH(launch_sampler_step(eps.f(), latent.f(), unet_in.f(), per_half, (long long)H * W, p, rescale, depth, q_prev, q_out, key, 0,
+                                            blend ? blend->mask : nullptr, blend ? blend->z0 : nullptr, blend ? blend->eps : nullptr, stream_));
         } else
-        if (blend) { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_cfg_ddim_masked(eps.f(), latent.f(), unet_in.f(), per_half, c, blend->mask, blend->z0, blend->eps, stream_)); }
-        else { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_cfg_ddim(eps.f(), latent.f(), unet_in.f(), per_half, c, stream_)); }
-        count_kernel();
+        if (blend) SDMI_LAUNCH(launch_cfg_ddim_masked(eps.f(), latent.f(), unet_in.f(), per_half, c, blend->mask, blend->z0, blend->eps, stream_));
+        else SDMI_LAUNCH(launch_cfg_ddim(eps.f(), latent.f(), unet_in.f(), per_half, c, stream_));
     }
     if (out_nhwc) {
         SDMI_HIP(hipMemcpyAsync(latent_out, latent.p, (size_t)per_half * 4, hipMemcpyDeviceToDevice, stream_));
     } else {
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(latent.f(), latent_out, n, 4, H, W, stream_)); }
-        count_kernel();
+        SDMI_LAUNCH(launch_nhwc_to_nchw(latent.f(), latent_out, n, 4, H, W, stream_));
     }
     unet_release();
 }
@@ -3531,9 +3514,8 @@ void Engine::img2img_latent_dev(const float* context, int n, int T, const float*
     Buf z0k(this, mask ? elems * 4 : 256), e0k(this, mask ? elems * 4 : 256);   // z0 and eps for the blend (NHWC)
     const Blend blend{mask, z0k.f(), e0k.f()};
     sample_loop(context, n, T, uncond, Tu, scale, ts, step_size, [&](float* latent, float* unet_in, long long per_half) {
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_img2img_start(z0, false, noise, seed, sqrt_a, sqrt_1ma, latent, unet_in, per_half,
-                                                                        mask ? z0k.f() : nullptr, mask ? e0k.f() : nullptr, n, hw, stream_)); }
-        count_kernel();
+        SDMI_LAUNCH(launch_img2img_start(z0, false, noise, seed, sqrt_a, sqrt_1ma, latent, unet_in, per_half, mask ? z0k.f() : nullptr, mask ? e0k.f() : nullptr, n, hw,
+                                         stream_));
     }, mask ? &blend : nullptr, latent_out, false, cond.p, kset_ ? &kplan : nullptr);
 }
 
@@ -3554,14 +3536,11 @@ void Engine::img2img_image_dev(const float* context, int n, int T, const float* 
     sample_loop(context, n, T, uncond, Tu, scale, ts, step_size, [&](float* latent, float* unet_in, long long per_half) {
         for (int i = 0; i < n; ++i) {   // one image at a time through the encoder, as encode_image_dev; its start latent right behind its quant_conv
             Act rgb = new_act(1, 8 * H, 8 * W, 4, /*dt=*/0);
-            { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_rgb_u8_to_nhwc4(init_rgb + (size_t)i * 3 * 64 * hw, rgb.p, 64 * hw, stream_)); }
-            count_kernel();
+            SDMI_LAUNCH(launch_rgb_u8_to_nhwc4(init_rgb + (size_t)i * 3 * 64 * hw, rgb.p, 64 * hw, stream_));
             Act q8 = encode_one(rgb);
             const long long off = (long long)i * hw * 4;
-            { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_img2img_start(q8.p, true, noise ? noise + off : nullptr, seed + (uint64_t)i, sqrt_a, sqrt_1ma,
-                                                                            latent + off, unet_in + off, per_half, mask ? z0k.f() + off : nullptr,
-                                                                            mask ? e0k.f() + off : nullptr, 1, hw, stream_)); }
-            count_kernel();
+            SDMI_LAUNCH(launch_img2img_start(q8.p, true, noise ? noise + off : nullptr, seed + (uint64_t)i, sqrt_a, sqrt_1ma, latent + off, unet_in + off, per_half,
+                                             mask ? z0k.f() + off : nullptr, mask ? e0k.f() + off : nullptr, 1, hw, stream_));
             release(q8);
         }
     }, mask ? &blend : nullptr, latent_out, false, cond_nhwc, kset_ ? &kplan : nullptr);
@@ -3583,11 +3562,9 @@ void Engine::inpaint_cond_nhwc(const uint8_t* init_rgb, const uint8_t* mask_u8, 
     const long long hw = (long long)H * W;
     for (int i = 0; i < n; ++i) {
         Act rgb = new_act(1, 8 * H, 8 * W, 4, /*dt=*/0);
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_rgb_u8_masked_to_nhwc4(init_rgb + (size_t)i * 3 * 64 * hw, mask_u8 + (size_t)i * 64 * hw, rgb.p, 64 * hw, stream_)); }
-        count_kernel();
+        SDMI_LAUNCH(launch_rgb_u8_masked_to_nhwc4(init_rgb + (size_t)i * 3 * 64 * hw, mask_u8 + (size_t)i * 64 * hw, rgb.p, 64 * hw, stream_));
         Act q8 = encode_one(rgb);
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_inpaint_cond_pack(q8.p, mask_u8 + (size_t)i * 64 * hw, cond_nhwc + (size_t)i * hw * 8, lat_mask ? lat_mask + (size_t)i * hw : nullptr, H, W, stream_)); }
-        count_kernel();
+        SDMI_LAUNCH(launch_inpaint_cond_pack(q8.p, mask_u8 + (size_t)i * 64 * hw, cond_nhwc + (size_t)i * hw * 8, lat_mask ? lat_mask + (size_t)i * hw : nullptr, H, W, stream_));
         release(q8);
     }
 }
@@ -3599,8 +3576,7 @@ void Engine::inpaint_cond_dev(const uint8_t* init_rgb, const uint8_t* mask_u8, i
     const int H = lat_h_, W = lat_w_;
     Buf cond(this, (size_t)n * H * W * 8 * sizeof(float));
     inpaint_cond_nhwc(init_rgb, mask_u8, n, cond.f(), nullptr);
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw_slice(cond.f(), cond_nchw, n, 8, 5, H, W, stream_)); }
-    count_kernel();
+    SDMI_LAUNCH(launch_nhwc_to_nchw_slice(cond.f(), cond_nchw, n, 8, 5, H, W, stream_));
 }
 
 void Engine::inpaint_image_dev(const float* context, int n, int T, const float* uncond, int Tu, double scale, size_t n_steps, double strength,
@@ -3616,8 +3592,7 @@ void Engine::inpaint_image_dev(const float* context, int n, int T, const float* 
     img2img_image_dev(context, n, T, uncond, Tu, scale, n_steps, strength, init_rgb, latent_blend ? lmask.f() : nullptr, noise, seed, lat.f(), cond.f());
     decode_latent_dev(lat.f(), n, (float)(1.0 / 0.18215), nullptr, rgb_out);
     if (paste_back) {
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_inpaint_paste(rgb_out, init_rgb, mask_u8, rgb_out, (long long)n * 64 * hw, stream_)); }
-        count_kernel();
+        SDMI_LAUNCH(launch_inpaint_paste(rgb_out, init_rgb, mask_u8, rgb_out, (long long)n * 64 * hw, stream_));
     }
 }
 
@@ -3669,14 +3644,12 @@ void Engine::resize_nhwc4(const float* x, int n, int h, int w, int oh, int ow, i
         float* dst = y;
         if (h != oh) { mid.reset(new Buf(this, (size_t)n * h * ow * 16)); dst = mid->f(); }
         AxisTable t = upload_axis(*this, w, ow, mode, antialias);
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_resize_axis(src, dst, t.first(), t.count(), t.taps(), t.max_taps, (long long)n * h, w, ow, 1, mode == 0, stream_)); }
-        count_kernel();
+        SDMI_LAUNCH(launch_resize_axis(src, dst, t.first(), t.count(), t.taps(), t.max_taps, (long long)n * h, w, ow, 1, mode == 0, stream_));
         src = dst;
     }
     if (h != oh) {   // vertical: [n][h][ow] -> [n][oh][ow]
         AxisTable t = upload_axis(*this, h, oh, mode, antialias);
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_resize_axis(src, y, t.first(), t.count(), t.taps(), t.max_taps, n, h, oh, ow, mode == 0, stream_)); }
-        count_kernel();
+        SDMI_LAUNCH(launch_resize_axis(src, y, t.first(), t.count(), t.taps(), t.max_taps, n, h, oh, ow, mode == 0, stream_));
     }
 }
 
@@ -3708,8 +3681,7 @@ void Engine::hires_latent_dev(const float* context, int n, int T, const float* u
     }
     resize_nhwc4(zb.f(), n, hr.base_h, hr.base_w, H, W, hr.mode, hr.antialias, zr.f());
     // launch_img2img_start reads its caller's z0 as NCHW: one transposing launch in front of it, and the second pass is img2img_latent_dev itself
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(zr.f(), z0.f(), n, 4, H, W, stream_)); }
-    count_kernel();
+    SDMI_LAUNCH(launch_nhwc_to_nchw(zr.f(), z0.f(), n, 4, H, W, stream_));
     img2img_latent_dev(context, n, T, uncond, Tu, scale, steps2, hr.strength, z0.f(), nullptr, hires_noise, hr.hires_seed, latent_out);
 }
 
@@ -3765,12 +3737,10 @@ void Engine::encode_image_dev(const float* img_nchw, int n, float* latent_nchw) 
     const size_t img_elems = (size_t)3 * H * W, lat_elems = (size_t)4 * lat_h_ * lat_w_;
     for (int i = 0; i < n; ++i) {
         Act rgb = new_act(1, H, W, 4, /*dt=*/0);
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nchw3_to_nhwc4(img_nchw + i * img_elems, rgb.p, 1, H, W, stream_)); }
-        count_kernel();
+        SDMI_LAUNCH(launch_nchw3_to_nhwc4(img_nchw + i * img_elems, rgb.p, 1, H, W, stream_));
         Act q8 = encode_one(rgb);
         // latent.slice([0..n, 0..4]): the first 4 of the 8 channels, NHWC8 -> NCHW4
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw_slice(q8.p, latent_nchw + i * lat_elems, 1, 8, 4, q8.h, q8.w, stream_)); }
-        count_kernel();
+        SDMI_LAUNCH(launch_nhwc_to_nchw_slice(q8.p, latent_nchw + i * lat_elems, 1, 8, 4, q8.h, q8.w, stream_));
         release(q8);
     }
 }
@@ -3822,13 +3792,11 @@ void Engine::decode_latent_dev(const float* latent_nchw, int n, float in_scale, 
     const size_t lat_elems = (size_t)4 * H * W, img_elems = (size_t)3 * 64 * H * W;
     for (int i = 0; i < n; ++i) {  // one image at a time: peak activations are ~1 GB per image at 512x512
         Buf z(this, lat_elems * 4);
-        { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nchw_to_nhwc(latent_nchw + i * lat_elems, z.f(), 1, 4, H, W, in_scale, stream_)); }
-        count_kernel();
+        SDMI_LAUNCH(launch_nchw_to_nhwc(latent_nchw + i * lat_elems, z.f(), 1, 4, H, W, in_scale, stream_));
         Act img = new_act(1, 8 * H, 8 * W, 3, /*dt=*/0);  // RGB stays fp32 (conv_out writes fp32 in both precisions)
         decode_one(z.f(), 1, img);
-        if (rgb_u8) { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_image_to_u8(img.p, rgb_u8 + i * img_elems, (long long)img_elems, stream_)); }
-        else { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(img.p, img_nchw + i * img_elems, 1, 3, 8 * H, 8 * W, stream_)); }
-        count_kernel();
+        if (rgb_u8) SDMI_LAUNCH(launch_image_to_u8(img.p, rgb_u8 + i * img_elems, (long long)img_elems, stream_));
+        else SDMI_LAUNCH(launch_nhwc_to_nchw(img.p, img_nchw + i * img_elems, 1, 3, 8 * H, 8 * W, stream_));
         release(img);
     }
 }
@@ -4002,9 +3970,10 @@ void Engine::ip_image_tokens_dev(const float* embeds, int n, float* out) {
     if (!ipw_.ready) throw Error(SDMI_ERR_STATE, "ip_image_tokens: no adapter is loaded");
     if (n < 1) throw Error(SDMI_ERR_INVALID, "ip_image_tokens: n must be at least 1");
     const int cd = cfg_.ctx_dim, T = ipw_.T;
-    Buf lin(this, (size_t)n * T * cd * 4);
-    gemm(embeds, n, ipw_.proj_bt, ipw_.proj_b, ipw_.D, T * cd, lin.f(), T * cd, nullptr, 0, /*dt=*/0);
-    layer_norm(ipw_.norm, lin.f(), (long long)n * T, out, /*dt=*/0);
+    Act lin = new_rows(n, T * cd, 1, 0);   // fp32 at every precision, like the adapter's weights
+    linear(LinW{ipw_.proj_bt, ipw_.proj_b, ipw_.D, T * cd}, rows_view(embeds, n, ipw_.D, 0), lin);
+    layer_norm(ipw_.norm, rows_view(lin.p, (long long)n * T, cd, 0), rows_view(out, (long long)n * T, cd, 0));
+    release(lin);
 }
 
 void Engine::check_ip_adapter(const sdmi_ip_adapter& a) {
@@ -4132,19 +4101,21 @@ void Engine::ip_prepare(int nb, int n_images, const std::function<void*(size_t)>
     }
     us_.kip.resize(kIpLayers);
     us_.vip.resize(kIpLayers);
+    const Act tokens = rows_view(rows.p, nb * Tip, cd, 0);
     for (int i = 0; i < kIpLayers; ++i) {
         const int c = st_list_[(size_t)i]->c;
         us_.kip[i] = (float*)own((size_t)nb * Tip * c * 4);
         us_.vip[i] = (float*)own((size_t)nb * Tip * c * 4);
-        gemm(rows.f(), nb * Tip, ipw_.kbt[(size_t)i], nullptr, cd, c, us_.kip[i], c, nullptr, 0, /*dt=*/0);
-        gemm(rows.f(), nb * Tip, ipw_.vbt[(size_t)i], nullptr, cd, c, us_.vip[i], c, nullptr, 0, /*dt=*/0);
+        linear(LinW{ipw_.kbt[(size_t)i], nullptr, cd, c}, tokens, rows_view(us_.kip[i], nb * Tip, c, 0));
+        linear(LinW{ipw_.vbt[(size_t)i], nullptr, cd, c}, tokens, rows_view(us_.vip[i], nb * Tip, c, 0));
     }
     us_.ip_s_host.assign((size_t)nb, ip_.scale);
     us_.ip_s = (float*)own((size_t)nb * 4);
     SDMI_HIP(hipMemcpyAsync(us_.ip_s, us_.ip_s_host.data(), (size_t)nb * 4, hipMemcpyHostToDevice, stream_));
 }
 
-void Engine::ip_attention(const SpatialW& w, const float* q, float* o, void* o3, int nb, int hw, int heads, int d) {
+void Engine::ip_attention(const SpatialW& w, const Act& qa, const Act& oa, int nb, int hw, int heads, int d) {
+    const float* q = qa.p; float* o = oa.p; void* o3 = oa.p3;
     if (!ip_live_ || w.ctx_index < 0 || w.ctx_index >= (int)us_.kip.size()) return;
     if (nb != us_.nb) throw Error(SDMI_ERR_STATE, "ip_attention: batch mismatch");
     IpAttnParams p{};
@@ -4159,8 +4130,7 @@ void Engine::ip_attention(const SpatialW& w, const float* q, float* o, void* o3,
     const double fl = 4.0 * nb * heads * (double)hw * p.T * d;
     ProfScope ps(this, PC_ATTENTION, fl, 0);
     ps.set_tag("ip_attention n%d nq%d T%d h%d d%d", nb, hw, p.T, heads, d);
-    SDMI_HIP(launch_ip_attention(p, stream_));
-    count_kernel(fl);
+    SDMI_LAUNCH_IN(ps, fl, launch_ip_attention(p, stream_));
 }
 
 size_t Engine::ip_kv_elems(int nb) const {

@@ -35,6 +35,12 @@ namespace sdmi {
                                                   __FILE__ + ":" + std::to_string(__LINE__) + ")");      \
     } while (0)
 
+// THE launch bookkeeping of Engine's members.  SDMI_LAUNCH_IN(ps, flops, expr): the launch expression is evaluated inside the open ProfScope ps -- between its two
+// events -- its status checked, the kernel counted (with its flops).  A scope with a class, bytes and a tag, or two launches under one scope, open the scope
+// themselves; SDMI_LAUNCH(expr) is the common case, class PC_OTHER with no bytes and no tag.
+#define SDMI_LAUNCH_IN(ps, flops, expr) do { (void)static_cast<const ProfScope&>(ps); SDMI_HIP(expr); count_kernel(flops); } while (0)
+#define SDMI_LAUNCH(expr) do { ProfScope ps_o(this, PC_OTHER); SDMI_LAUNCH_IN(ps_o, 0, expr); } while (0)
+
 // ---- device memory pool: host-side first-fit allocator over big slabs -------------
 // All work is on one stream, so a block may be reused as soon as it is freed
 // (kernel order == program order).  Addresses are deterministic for a given call
@@ -107,7 +113,8 @@ struct ActQ {
     int n = 0, h = 0, w = 0, c = 0, cp = 0;
     long long rows() const { return (long long)n * h * w; }
 };
-struct LinW { float* bt = nullptr; float* bias = nullptr; int cin = 0, cout = 0; int dt = 0; float* bt8 = nullptr; float* bs8 = nullptr; };   // bt8 / bs8: MXFP8 copy (precision = 2, option fp8_linear)
+// bt8 / bs8: MXFP8 copy (precision = 2, option fp8_linear).  fused: the weights packed behind this one as further rows of ONE GEMM, itself included (3: q | k | v)
+struct LinW { float* bt = nullptr; float* bias = nullptr; int cin = 0, cout = 0; int dt = 0; float* bt8 = nullptr; float* bs8 = nullptr; int fused = 1; };
 struct NormW { float* gamma = nullptr; float* beta = nullptr; int c = 0; float eps = 1e-5f; };  // eps: Q3 default, overridden by the dump's eps file
 
 struct ResW {  // UNet ResBlock (unet/mod.rs:700-734) and VAE ResnetBlock (autoencoder/mod.rs:503-528)
@@ -500,6 +507,14 @@ private:
     // fp32 engines: what = 1 fp32 only, 2 planes only, 3 both (c % 32 == 0 for planes)
     Act new_act3(int n, int h, int w, int c, int what);
     void release(Act& a);
+    // [rows][c] tensors (what the Linear layers, LayerNorm, GEGLU and attention work on): n = h = 1, w = rows.  new_rows: what = 1 storage type dt (-1: the engine's),
+    // 2 planes only, 3 fp32 + planes (new_act3's rule).  rows_view: a buffer somebody else owns (release() leaves it alone) -- p (may be null) rows ld elements apart
+    // (0: dense) and / or p3, dense planes.  top: the first `rows` rows of a dense tensor, a view.
+    Act new_rows(long long rows, int c, int what = 1, int dt = -1) { return (what & 2) ? new_act3(1, 1, (int)rows, c, what) : new_act(1, 1, (int)rows, c, dt); }
+    static Act rows_view(const void* p, long long rows, int c, int dt, int ld = 0, void* p3 = nullptr) {
+        Act a; a.p = (float*)const_cast<void*>(p); a.n = 1; a.h = 1; a.w = (int)rows; a.c = c; a.dt = dt; a.ld = ld; a.view = true; a.p3 = p3; a.ld3 = (c / 32) * 192; return a;
+    }
+    static Act top(const Act& a, long long rows) { if (rows > a.rows()) throw Error(SDMI_ERR_STATE, "top: more rows than the tensor has"); return rows_view(a.p, rows, a.c, a.dt, a.ld, a.p3); }
     // pad_br: zero padding on the bottom / right only (PaddingCfg::new(0, 1, 0, 1), the VAE encoder's downsampler)
     void probe_report(void* pb_dev, size_t max_blocks, int n, int cin, int h, int w, int cout, int k, int tile_cfg, int splitk);
     void conv(const ConvW& w, const Act& x, Act& y, int stride, int ups, const float* rowvec, int rowvec_stride,
@@ -566,9 +581,12 @@ private:
     // by the caller (may be null); self_resid (option op_resid): without one, the input in the route's storage type is the residual of the bf16 / fp32 kernels
     void op_linear_run(const OpRoute& r, const float* x, const float* wt, const float* bias, int rows, int cin, int cout, float* C, int ldc, const float* resid, int ldr,
                        bool self_resid);
-    // A3 / C3: the input / output as three bf16 planes (dense rows: 192 bytes per 32 channels); A and / or C may then be null
-    void gemm(const float* A, int a_rows, const float* bt, const float* bias, int cin, int cout, float* C, int ldc,
-              const float* resid, int ldr, int dt = -1, int out_mode = 0, const void* A3 = nullptr, void* C3 = nullptr);
+    // y [rows][y.c] = x W^T + bias (+ resid).  Everything comes from the structs: in_features, bias and packing from w; the number of weight rows from y.c, which
+    // must be w.cout or, for a weight with others packed behind it (q | k | v), w.fused * w.cout; rows and the storage type from x (y and resid agree); the
+    // plane forms from x.p3 (input; x.p may then be null) and y.p3 (written next to, or instead of, y.p); the output's and the residual's row strides from their ld.
+    // A weight that is no model entry is a LinW built in place.
+    void linear(const LinW& w, const Act& x, const Act& y, const Act* resid = nullptr);
+    void linear(const LinW& w, const ActQ& x, const Act& y, const Act* resid = nullptr);   // ... on MXFP8 operands (w.bt8), bf16 out
     // fp32 engine, option gemm_planes: does the GEMM cin -> cout take its activations as planes (k_gemm3p.hip)?
     bool plane_gemm(int cin, int cout) const { return !bf16_ && gopt_.gemm_planes != 0 && gopt_.gemm_f32s != 0 && cin % 32 == 0 && cout >= 32; }
     void launch_gemm(ConvGemm& p, int in_dt, int force_cfg = -1, int force_splits = 0);   // plan (gemm_plan.hpp), temporary plane / fp32 buffers, run_gemm
@@ -593,22 +611,33 @@ private:
     bool use_fp8_wide(const float* bt8, long long rows) const { return fp8_ && opt_fp8_convs_ && opt_fp8_linear_ && bt8 && rows >= opt_fp8_min_rows_; }
     void set_resid_acc(ConvGemm& p, bool eligible, bool resid_ok) const;          // ConvGemm::resid_acc of a launch (option resid_acc, strides, base alignment)
     void launch_fp8(ConvGemm& p, double flops);                                   // tile / split-K choice + launch (+ reduce) of conv_gemm_fp8x_kernel
-    void gemm_fp8(const ActQ& x, const LinW& w, int n_rows_w, void* C, int ldc, const float* resid, int ldr);   // C[rows][n_rows_w] = x W^T + b (+ resid), bf16 out
     void conv_raw(const ConvW& w, const Act& x, Act& y, int stride, int ups);     // conv() or, at precision = 2, quantize() + conv_fp8()
     void quantize(const Act& x, ActQ& y);                                         // bf16 activation -> MXFP8 (quantize_bf16_fp8_kernel)
-    void layer_norm_fp8(const NormW& w, const float* x, long long rows, ActQ& y);
+    void layer_norm(const NormW& w, const Act& x, ActQ& y);                        // ... writing MXFP8
     ActQ new_rowsq(long long rows, int c) { return new_actq(1, 1, (int)rows, c); }
-    void layer_norm(const NormW& w, const float* x, long long rows, float* y, int dt = -1, void* y3 = nullptr);   // y3: output as planes instead of y
-    // GEGLU::forward (unet/mod.rs:579-591): out[rows, hidden] = (x W + b)[:, :hidden] * gelu((x W + b)[:, hidden:]); bt is the
-    // packed [2 hidden][cin] weight.  Fused into a large-tile GEMM when possible, else GEMM into `proj_scratch` + gate kernel.
-    void gemm_geglu(const float* x, long long rows, const float* bt, const float* bias, int cin, int hidden, float* out, int dt,
-                    const void* x3 = nullptr, void* out3 = nullptr);
-    void attention(const float* q, int ldq, long long q_bs, const float* k, int ldk, long long k_bs, const float* v,
-                   int ldv, long long v_bs, float* o, int ldo, long long o_bs, int n, int nq, int nk, int n_head,
-                   int d_head, const int* kv_len_dev, const int* kv_len_host, const float* mask, int mask_ld, int dt = -1, void* o3 = nullptr, bool q_log2 = false);
+    void layer_norm(const NormW& w, const Act& x, const Act& y);   // dense rows of x's storage type; y.p3: the output as planes (y.p must then be null)
+    // GEGLU::forward (unet/mod.rs:579-591): y[rows, hidden] = (x W + b)[:, :hidden] * gelu((x W + b)[:, hidden:]), hidden = w.cout / 2 = y.c; w.bt is the
+    // packed [2 hidden][cin] weight.  Fused into a large-tile GEMM when possible, else linear() into a scratch tensor + gate kernel.  Plane forms as linear().
+    void gemm_geglu(const LinW& w, const Act& x, const Act& y);
+    // qkv_attention's arguments, filled by field name.  An operand is rows ld elements apart and samples bs elements apart; o.p may be null where o3 (the output
+    // as planes, fp32 kernels) is given.  kv_len_dev / kv_len_host: the same per-sample key counts on both sides, or both null.  dt -1: the engine's storage type.
+    struct AttnOperand { const float* p = nullptr; int ld = 0; long long bs = 0; };
+    struct Attn {
+        AttnOperand q, k, v, o;
+        int n = 0, nq = 0, nk = 0, n_head = 0, d_head = 0;
+        const int* kv_len_dev = nullptr; const int* kv_len_host = nullptr; const float* mask = nullptr; int mask_ld = 0;
+        void* o3 = nullptr; int dt = -1; bool q_log2 = false;   // q_log2: see q_prescaled
+    };
+    // a dense-or-strided [n * rows][c] tensor as an operand, `rows` rows per sample; the three operands of a packed [n * rows][3 c] q | k | v buffer
+    static AttnOperand attn_rows(const Act& a, long long rows) { return AttnOperand{a.p, a.stride(), rows * a.stride()}; }
+    static void attn_packed_qkv(const Act& qkv, long long rows, Attn& a) {
+        a.q = a.k = a.v = attn_rows(qkv, rows);
+        a.k.p = adv(qkv.p, qkv.c / 3, qkv.dt); a.v.p = adv(qkv.p, 2 * (qkv.c / 3), qkv.dt);
+    }
+    void attention(const Attn& a);
     // ONE rule for "the query arrives multiplied by attn_bf16_q_scale(d_head)": bf16 storage at the head dims the fused bf16 kernel serves.  The weight loader
     // folds the factor into the query projection by it, the fp32 -> bf16 conversions of the operator entry points apply it by it, and every attention() call
-    // passes it as q_log2 -- the kernel launcher refuses a bf16 call that does not state it.
+    // states it as Attn::q_log2 -- the kernel launcher refuses a bf16 call that does not state it.
     // d_head = 64 follows option attn_d64 (0: as before k_attn_bf16.hip had a d = 64 instance -- plain q on k_attn.hip).
     bool q_prescaled(int dt, int d_head) const { return dt != 0 && attn_bf16_head_dim(d_head, aopt_.attn_d64); }
     // heads of a UNet attention at channel width c: n_head of them (SD v1), or c / 64 of width 64 (variant = 1, SD 2.x)
@@ -664,7 +693,7 @@ private:
         return control_step_on(ip_.start, ip_.end, step, us_.steps);
     }
     void ip_prepare(int nb, int n_images, const std::function<void*(size_t)>& own);
-    void ip_attention(const SpatialW& w, const float* q, float* o, void* o3, int nb, int hw, int heads, int d);
+    void ip_attention(const SpatialW& w, const Act& q, const Act& o, int nb, int hw, int heads, int d);
     void unet_release();
     void unet_run(const float* x_nhwc, int nb, int step, float* out_nhwc, bool cfg_pair = false);
     void decode_one(const float* z_nhwc, int n, Act& img);

@@ -156,8 +156,7 @@ void Engine::op_unpack_tensor(const void* raw, int dtype, int ndim, const int64_
     if (transform == 1) { d0 = dims[0]; d1 = dims[1]; }
     else if (transform == 2) { d0 = dims[0]; d1 = dims[2] * dims[3]; }
     else { d0 = 1; for (int i = 0; i < ndim; ++i) d0 *= dims[i]; d1 = 1; }
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_unpack_tensor(raw, dtype, transform, d0, d1, out, stream_, transform == 2 ? (int)dims[1] : 3)); }
-    count_kernel();
+    SDMI_LAUNCH(launch_unpack_tensor(raw, dtype, transform, d0, d1, out, stream_, transform == 2 ? (int)dims[1] : 3));
 }
 
 bool Engine::op_freeu(float* parent, int n, int c, int h, int w, int ld, int cx, int version, float b, float s, float* parent3) {
@@ -183,11 +182,9 @@ bool Engine::op_freeu(float* parent, int n, int c, int h, int w, int ld, int cx,
 void Engine::op_resize(const float* x_nchw, int n, int h, int w, int oh, int ow, int mode, int antialias, float* out_nchw) {
     if (n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0) throw Error(SDMI_ERR_INVALID, "resize: sizes must be positive");
     Buf xin(this, (size_t)n * h * w * 16), xout(this, (size_t)n * oh * ow * 16);
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nchw_to_nhwc(x_nchw, xin.f(), n, 4, h, w, 1.0f, stream_)); }
-    count_kernel();
+    SDMI_LAUNCH(launch_nchw_to_nhwc(x_nchw, xin.f(), n, 4, h, w, 1.0f, stream_));
     resize_nhwc4(xin.f(), n, h, w, oh, ow, mode, antialias, xout.f());
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(xout.f(), out_nchw, n, 4, oh, ow, stream_)); }
-    count_kernel();
+    SDMI_LAUNCH(launch_nhwc_to_nchw(xout.f(), out_nchw, n, 4, oh, ow, stream_));
 }
 
 void Engine::op_sampler_step(const float* eps, const float* latent, int n, int h, int w, const SamplerStep& c, float rescale, int depth, const float* q_hist,
@@ -196,9 +193,7 @@ void Engine::op_sampler_step(const float* eps, const float* latent, int n, int h
     const long long per_half = (long long)n * h * w * 4;
     Buf de(this, 2 * half), dl(this, half), du(this, 2 * half), dq(this, 3 * half), dqo(this, half), dz(this, half), dn(this, half);
     auto to_nhwc = [&](const float* src, float* dst, int images) {
-        ProfScope ps_o(this, PC_OTHER);
-        SDMI_HIP(launch_nchw_to_nhwc(src, dst, images, 4, h, w, 1.0f, stream_));
-        count_kernel();
+        SDMI_LAUNCH(launch_nchw_to_nhwc(src, dst, images, 4, h, w, 1.0f, stream_));
     };
     to_nhwc(eps, de.f(), 2 * n);
     to_nhwc(latent, dl.f(), n);
@@ -208,17 +203,10 @@ void Engine::op_sampler_step(const float* eps, const float* latent, int n, int h
         q_prev[k] = dq.f() + (size_t)k * per_half;
     }
     if (mask) { to_nhwc(z0, dz.f(), n); to_nhwc(e0, dn.f(), n); }
-    { ProfScope ps_o(this, PC_OTHER);
-      SDMI_HIP(launch_sampler_step(de.f(), dl.f(), du.f(), per_half, (long long)h * w, c, rescale, depth, q_prev, depth ? dqo.f() : nullptr, noise_key, noise_key2,
-                                   mask, mask ? dz.f() : nullptr, mask ? dn.f() : nullptr, stream_)); }
-    count_kernel();
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_nhwc_to_nchw(dl.f(), latent_out, n, 4, h, w, stream_)); }
-    count_kernel();
-    if (depth) {
-        ProfScope ps_o(this, PC_OTHER);
-        SDMI_HIP(launch_nhwc_to_nchw(dqo.f(), q_out, n, 4, h, w, stream_));
-        count_kernel();
-    }
+    SDMI_LAUNCH(launch_sampler_step(de.f(), dl.f(), du.f(), per_half, (long long)h * w, c, rescale, depth, q_prev, depth ? dqo.f() : nullptr, noise_key, noise_key2,
+                                    mask, mask ? dz.f() : nullptr, mask ? dn.f() : nullptr, stream_));
+    SDMI_LAUNCH(launch_nhwc_to_nchw(dl.f(), latent_out, n, 4, h, w, stream_));
+    if (depth) SDMI_LAUNCH(launch_nhwc_to_nchw(dqo.f(), q_out, n, 4, h, w, stream_));
 }
 
 void Engine::qkv_attention_dev(const float* q, const float* k, const float* v, const float* mask, int mask_ld, int n,
@@ -232,9 +220,16 @@ void Engine::qkv_attention_dev(const float* q, const float* k, const float* v, c
     const int* kv_len_dev = kv_len_to_dev(kl, kv_len_host, n);
     const long long q_bs = (long long)nq * n_state, k_bs = (long long)nk * n_state;
     const int dh = n_state / n_head;
-    auto run = [&](float* o, int dt, void* o3) {
-        attention(q, n_state, q_bs, k, n_state, k_bs, v, n_state, k_bs, o, n_state, q_bs, n, nq, nk, n_head, dh, kv_len_dev, kv_len_host, mask, dt ? 0 : mask_ld, dt, o3,
-                  q_prescaled(dt, dh));
+    auto run = [&](float* o, int dt, void* o3) {   // q, k, v: dense, fp32 or already converted
+        Attn at;
+        at.q = attn_rows(rows_view(q, (long long)n * nq, n_state, dt), nq);
+        at.k = attn_rows(rows_view(k, (long long)n * nk, n_state, dt), nk);
+        at.v = attn_rows(rows_view(v, (long long)n * nk, n_state, dt), nk);
+        at.o = attn_rows(rows_view(o, (long long)n * nq, n_state, dt), nq); at.o3 = o3;
+        at.n = n; at.nq = nq; at.nk = nk; at.n_head = n_head; at.d_head = dh;
+        at.kv_len_dev = kv_len_dev; at.kv_len_host = kv_len_host;
+        at.mask = mask; at.mask_ld = dt ? 0 : mask_ld; at.dt = dt; at.q_log2 = q_prescaled(dt, dh);
+        attention(at);
     };
     if (bf16_ && !mask) {
         qkv_to_bf16(q, k, v, n * q_bs, n * k_bs, dh, qkv);
@@ -301,8 +296,13 @@ void Engine::op_qkv_attention_view(const float* q, const float* k, const float* 
     const long long q_bs = (long long)view.q_rows * view.q_ld, k_bs = (long long)view.k_rows * view.k_ld, v_bs = (long long)view.v_rows * view.v_ld;
     const long long o_bs = (long long)view.out_rows * view.out_ld;
     auto run = [&](float* o, int mld, void* o3) {
-        attention(qs, view.q_ld, q_bs, ks, view.k_ld, k_bs, vs, view.v_ld, v_bs, o, view.out_ld, o_bs, n, nq, nk, n_head, dh, kv_len_dev, kv_len_host, mask, mld, dt, o3,
-                  q_prescaled(dt, dh));
+        Attn at;
+        at.q = AttnOperand{qs, view.q_ld, q_bs}; at.k = AttnOperand{ks, view.k_ld, k_bs}; at.v = AttnOperand{vs, view.v_ld, v_bs};
+        at.o = AttnOperand{o, view.out_ld, o_bs}; at.o3 = o3;
+        at.n = n; at.nq = nq; at.nk = nk; at.n_head = n_head; at.d_head = dh;
+        at.kv_len_dev = kv_len_dev; at.kv_len_host = kv_len_host;
+        at.mask = mask; at.mask_ld = mld; at.dt = dt; at.q_log2 = q_prescaled(dt, dh);
+        attention(at);
     };
     if (view.out_planes) {   // the kernels' plane-writing epilogue, joined back (dense: check_attention_view); what cannot write planes is plan_attention's to refuse
         Buf o3(this, (size_t)n * nq * (n_state / 32) * 192 + 256);
@@ -492,18 +492,18 @@ void Engine::op_linear_run(const OpRoute& r, const float* x, const float* wt, co
         return xh->f();
     };
     if (r.q8) {
-        Act xa; xa.p = x_bf16(); xa.n = 1; xa.h = 1; xa.w = rows; xa.c = cin; xa.dt = 1;
+        const Act xa = rows_view(x_bf16(), rows, cin, 1), ra = rows_view(resid, rows, cout, 1, ldr);
         OpLinW w(this, wt, bias, cin, cout, r);
         ActQ q = new_rowsq(rows, cin);
         quantize(xa, q);
-        gemm_fp8(q, w.w, cout, C, ldc, resid, ldr);
+        linear(w.w, q, rows_view(C, rows, cout, 1, ldc), resid ? &ra : nullptr);
         release(q);
         return;
     }
     OpLinW w(this, wt, bias, cin, cout, r);
-    const float* xin = r.xdt ? x_bf16() : x;
-    if (!resid && self_resid) { resid = xin; ldr = cin; }
-    gemm(xin, rows, w.w.bt, bias, cin, cout, C, ldc, resid, ldr, r.xdt);
+    const Act xa = rows_view(r.xdt ? x_bf16() : x, rows, cin, r.xdt);
+    const Act ra = resid ? rows_view(resid, rows, cout, r.xdt, ldr) : xa;
+    linear(w.w, xa, rows_view(C, rows, cout, r.xdt, ldc), (resid || self_resid) ? &ra : nullptr);
 }
 
 void Engine::op_linear(const float* x, const float* wt, const float* bias, int rows, int cin, int cout, float* out, const EpiOps* epi) {
@@ -639,11 +639,10 @@ void Engine::op_cat_chain(const float* x, const float* w_x, const float* b_x, co
 void Engine::op_geglu_forward(const float* x, const float* wt, const float* bias, int rows, int cin, int hidden, float* out) {
     const int dt = (bf16_ && cin % 64 == 0 && hidden % 8 == 0) ? 1 : 0;
     OpLinW w(this, wt, bias, cin, 2 * hidden, OpRoute{false, dt, dt, dt});
-    const float* bt = w.w.bt;
     if (dt) {
         Buf xh(this, (size_t)rows * cin * 2), yh(this, (size_t)rows * hidden * 2);
         SDMI_HIP(launch_f32_to_bf16(x, xh.p, (long long)rows * cin, stream_));
-        gemm_geglu(xh.f(), rows, bt, bias, cin, hidden, yh.f(), 1);
+        gemm_geglu(w.w, rows_view(xh.p, rows, cin, 1), rows_view(yh.p, rows, hidden, 1));
         rows_to_f32(yh.p, out, rows, hidden);
         return;
     }
@@ -654,15 +653,15 @@ void Engine::op_geglu_forward(const float* x, const float* wt, const float* bias
         SDMI_HIP(launch_split3_rows(x, x3.p, rows, cin, cin, (long long)(cin / 32) * 192, stream_));
         if (opt_geglu_fuse_ == 8) {
             Buf o32(this, (size_t)rows * hidden * 4);
-            gemm_geglu(nullptr, rows, bt, bias, cin, hidden, o32.f(), 0, x3.p, o3.p);
+            gemm_geglu(w.w, rows_view(nullptr, rows, cin, 0, 0, x3.p), rows_view(o32.p, rows, hidden, 0, 0, o3.p));
             SDMI_HIP(hipMemcpyAsync(out, o32.p, (size_t)rows * hidden * 4, hipMemcpyDeviceToDevice, stream_));   // the fp32 output of a launch that writes both
         } else {
-            gemm_geglu(nullptr, rows, bt, bias, cin, hidden, nullptr, 0, x3.p, o3.p);
+            gemm_geglu(w.w, rows_view(nullptr, rows, cin, 0, 0, x3.p), rows_view(nullptr, rows, hidden, 0, 0, o3.p));
             SDMI_HIP(launch_join3_rows(o3.p, out, rows, hidden, (long long)(hidden / 32) * 192, hidden, stream_));
         }
         return;
     }
-    gemm_geglu(x, rows, bt, bias, cin, hidden, out, 0);
+    gemm_geglu(w.w, rows_view(x, rows, cin, 0), rows_view(out, rows, hidden, 0));
 }
 
 // out = u x w_main + b_main + h x w_aux + b_aux + resid as Engine::spatial_transformer computes the tail of a transformer block: both inputs as planes, option
@@ -677,8 +676,6 @@ void Engine::op_linear_pair(const float* u, const float* h, const float* w_main,
     if (out3 && (cout % 32 || out_ld % 32)) throw Error(SDMI_ERR_UNSUPPORTED, "linear_pair: a plane output needs cout and out_ld in multiples of 32");
     const OpRoute r{false, 0, 0, 0};
     OpLinW wm(this, w_main, b_main, k_main, cout, r), wa(this, w_aux, b_aux, k_aux, cout, r);
-    const float* bt_m = wm.w.bt;
-    const float* bt_a = wa.w.bt;
     const int u_ld = k_main / 32 * 192, h_ld = k_aux / 32 * 192, ld3 = out_ld / 32 * 192;
     Buf u3(this, (size_t)rows * u_ld), h3(this, (size_t)rows * h_ld);
     SDMI_HIP(launch_split3_rows(u, u3.p, rows, k_main, k_main, u_ld, stream_));
@@ -687,14 +684,15 @@ void Engine::op_linear_pair(const float* u, const float* h, const float* w_main,
     if (out) y.reset(new Buf(this, (size_t)rows * out_ld * 4));
     if (out3) y3.reset(new Buf(this, (size_t)rows * ld3));
     if (opt_proj_out_fold_) {
-        const LinearPair lp{u3.p, u_ld, bt_m, b_main, k_main, h3.p, h_ld, bt_a, b_aux, k_aux, rows, cout, resid, resid_ld ? resid_ld : cout,
+        const LinearPair lp{u3.p, u_ld, wm.w.bt, b_main, k_main, h3.p, h_ld, wa.w.bt, b_aux, k_aux, rows, cout, resid, resid_ld ? resid_ld : cout,
                             y ? y->f() : nullptr, out_ld, y3 ? y3->p : nullptr, ld3};
         if (!linear_pair(lp)) throw Error(SDMI_ERR_UNSUPPORTED, "linear_pair: this shape / these options do not pair (proj_out_fold=0 runs the two launches)");
     } else {
         if (out_ld != cout) throw Error(SDMI_ERR_UNSUPPORTED, "linear_pair: the two launches keep the result dense (out_ld = cout)");
         Buf t(this, (size_t)rows * cout * 4);
-        gemm(nullptr, rows, bt_a, b_aux, k_aux, cout, t.f(), cout, resid, resid_ld ? resid_ld : cout, 0, 0, h3.p);
-        gemm(nullptr, rows, bt_m, b_main, k_main, cout, y ? y->f() : nullptr, cout, t.f(), cout, 0, 0, u3.p, y3 ? y3->p : nullptr);
+        const Act ta = rows_view(t.p, rows, cout, 0), ra = rows_view(resid, rows, cout, 0, resid_ld);
+        linear(wa.w, rows_view(nullptr, rows, k_aux, 0, 0, h3.p), ta, resid ? &ra : nullptr);
+        linear(wm.w, rows_view(nullptr, rows, k_main, 0, 0, u3.p), rows_view(y ? y->p : nullptr, rows, cout, 0, 0, y3 ? y3->p : nullptr), &ta);
     }
     if (y) SDMI_HIP(hipMemcpy2DAsync(out, (size_t)cout * 4, y->p, (size_t)out_ld * 4, (size_t)cout * 4, (size_t)rows, hipMemcpyDeviceToDevice, stream_));
     if (y3) SDMI_HIP(launch_join3_rows(y3->p, out3, rows, cout, ld3, cout, stream_));
@@ -740,7 +738,7 @@ void Engine::op_timestep_embedding_f(double t, int dim, float* out) {
     Buf td(this, sizeof(float));
     SDMI_HIP(hipMemcpyAsync(td.p, &tf, sizeof(float), hipMemcpyHostToDevice, stream_));
     SDMI_HIP(hipStreamSynchronize(stream_));
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_timestep_embedding_f((const float*)td.p, 1, dim, out, stream_)); }
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_timestep_embedding_f((const float*)td.p, 1, dim, out, stream_)); }   // (profiled, not counted: as ever)
     SDMI_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -748,7 +746,7 @@ void Engine::op_timestep_embedding(int t, int dim, float* out) {
     Buf td(this, sizeof(int));
     SDMI_HIP(hipMemcpyAsync(td.p, &t, sizeof(int), hipMemcpyHostToDevice, stream_));
     SDMI_HIP(hipStreamSynchronize(stream_));
-    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_timestep_embedding((const int*)td.p, 1, dim, out, stream_)); }
+    { ProfScope ps_o(this, PC_OTHER); SDMI_HIP(launch_timestep_embedding((const int*)td.p, 1, dim, out, stream_)); }       // (profiled, not counted: as ever)
     SDMI_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -912,10 +910,13 @@ double Engine::bench_attention(int n, int nq, int nk, int n_state, int n_head, i
         SDMI_HIP(launch_f32_to_bf16(v.f(), vh.p, ke, stream_));
     }
     const float* qp = dt ? qh.f() : q.f(); const float* kp = dt ? kh.f() : k.f(); const float* vp = dt ? vh.f() : v.f();
-    auto run = [&] {
-        attention(qp, n_state, (long long)nq * n_state, kp, n_state, (long long)nk * n_state, vp, n_state, (long long)nk * n_state,
-                  o.f(), n_state, (long long)nq * n_state, n, nq, nk, n_head, n_state / n_head, nullptr, nullptr, nullptr, 0, dt, nullptr, q_prescaled(dt, n_state / n_head));
-    };
+    Attn at;
+    at.q = attn_rows(rows_view(qp, (long long)n * nq, n_state, dt), nq);
+    at.k = attn_rows(rows_view(kp, (long long)n * nk, n_state, dt), nk);
+    at.v = attn_rows(rows_view(vp, (long long)n * nk, n_state, dt), nk);
+    at.o = attn_rows(rows_view(o.p, (long long)n * nq, n_state, dt), nq);
+    at.n = n; at.nq = nq; at.nk = nk; at.n_head = n_head; at.d_head = n_state / n_head; at.dt = dt; at.q_log2 = q_prescaled(dt, at.d_head);
+    auto run = [&] { attention(at); };
     run();
     float ms = 0;
     SDMI_HIP(hipEventRecord(ev0_, stream_));
@@ -943,8 +944,7 @@ void Engine::op_ip_attention(const float* q, const float* k_ip, const float* v_i
     const double fl = 4.0 * n * n_head * (double)nq * T * d;
     auto run = [&] {
         ProfScope ps(this, PC_ATTENTION, fl, 0);
-        SDMI_HIP(launch_ip_attention(p, stream_));
-        count_kernel(fl);
+        SDMI_LAUNCH_IN(ps, fl, launch_ip_attention(p, stream_));
     };
     if (dt) {
         Buf qh(this, qe * 2), oh(this, qe * 2), yh(this, qe * 2);
